@@ -67,6 +67,9 @@ def parse():
                     help="ONE process driving --gpus N devices through rlr_multi (persistent shard workers, ncclAllGather of the "
                          "partial top-k lists + merge kernel behind the C ABI) instead of one rank per GPU over torch.distributed: "
                          "the form a single-process Rust server uses (INTEGRATION.md section 5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rows as float64, cosines as "
+                         "float32) to DIR/<name>.npy, for output-for-output comparison of two builds")
     ap.add_argument("--batch", type=int, default=1,
                     help="queries per step; >= 16 takes the matrix-core (MFMA) batched path (BASELINE config 3 uses 256)")
     return ap.parse_args()
@@ -75,6 +78,27 @@ def parse():
 def queries_without_oracle(rlr, dim, n, seed):
     rng = np.random.default_rng(seed)
     return np.stack([rlr.normalize(rng.standard_normal(dim).astype(np.float32)) for _ in range(n)])
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, last):
+    """What the last timed step handed its caller -- (rows [Q, k], cosines [Q, k]) -- as DIR/rows.npy (float64: row ids
+    stay exact below 2^53) and DIR/scores.npy (float32).  Over DUMP_LIMIT_BYTES, a fixed seeded sample of the queries is
+    kept and its indices go to DIR/query_index.npy.  The queries and the corpus come from --seed, so the same arguments
+    dump the same computation on every run."""
+    os.makedirs(d, exist_ok=True)
+    rows = np.asarray(last[0]).astype(np.float64)
+    scores = np.asarray(last[1]).astype(np.float32)
+    per_query = rows[:1].nbytes + scores[:1].nbytes
+    keep = np.arange(rows.shape[0])
+    if rows.nbytes + scores.nbytes > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0x5EED00D0).choice(rows.shape[0], DUMP_LIMIT_BYTES // max(per_query, 1),
+                                                                replace=False))
+        np.save(os.path.join(d, "query_index.npy"), keep.astype(np.float64))
+    np.save(os.path.join(d, "rows.npy"), rows[keep])
+    np.save(os.path.join(d, "scores.npy"), scores[keep])
 
 
 def q8_kernel_name(dim):
@@ -267,7 +291,15 @@ def ensure_built():
 
     import __graft_entry__
 
-    with open(os.path.join(ROOT, "rust-local-rag_amd", ".build.lock"), "w") as lk:
+    try:
+        lk = open(os.path.join(ROOT, "rust-local-rag_amd", ".build.lock"), "w")
+    except OSError:
+        # a read-only tree cannot be rebuilt: it runs the library that build() left in it, and a missing one is an error
+        so = os.path.join(ROOT, "rust-local-rag_amd", "librlr_gpu.so")
+        if not os.path.exists(so):
+            raise SystemExit(f"{so} is missing and the tree is read-only: run build() first")
+        return
+    with lk:
         fcntl.flock(lk, fcntl.LOCK_EX)
         __graft_entry__._load_build_module().build()
 
@@ -591,6 +623,8 @@ def in_process(args):
         last = mi.search_topk(qs[args.warmup + i], args.k)   # returns after the merged result is in host memory
     elapsed = time.perf_counter() - t0
     st = mi.stats()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
     elem = 2 if args.dtype == "f16" else 4
     print(json.dumps({
         "metric": "queries/sec + achieved HBM GB/s, 768-d cosine top-100 over 10M chunks",
@@ -752,6 +786,8 @@ def main():
         if dist:
             dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
 
     elem = 2 if args.dtype == "f16" else 4
     scan_ms = prof.scan_ms / max(prof.n_scan_launches, 1)
