@@ -375,6 +375,9 @@ typedef struct rlr_profile {
      * the batched throughput (10 M x 768, 256 queries: 31 k instead of 59 k queries/s).  A host that sees this count
      * grow and has dim * 2 bytes per row of HBM to spare should switch the image on. */
     uint64_t n_batches_without_image;
+    /* queries that skipped a binary16 nomination (the batched GEMM, the nomination image) because a query
+     * element or a stored f32 row element lies outside binary16 range: they ran over the f32 rows instead */
+    uint64_t n_f16_range_fallbacks;
 } rlr_profile;
 /* enable != 0: record HIP events around each stage on the stream it is launched on
  * (adds one event pair per stage).  Disabled by default. */

@@ -1166,18 +1166,23 @@ __global__ __launch_bounds__(1024) void batch_emit_kernel(const uint64_t *__rest
 
 } // namespace
 
-// upper bound of |nominated score - reference-order dot| for unit-norm operands
-float nomination_eps(uint32_t dim, int dtype)
+// upper bound of |nominated score - reference-order dot|.  prod >= |q|*|r| and >= 1, norm_sum >= |q| + |r|, for the
+// largest query and row norms of the call; unit-norm operands pass (1, 2).
+float nomination_eps(uint32_t dim, int dtype, float prod, float norm_sum)
 {
-    // operand roundings to binary16 (round to nearest even): 2^-11 relative each.  f32 rows:
-    // both operands rounded -> 2^-10 (+ cross term); f16 rows are already exact -> 2^-11.
-    // Products of two binary16 values are exact in f32; the f32 accumulation (MFMA k-order
-    // chain) and the reference's own left-to-right error add (dim + 64) * 2^-24 each; binary16
-    // subnormal flushes add < 2 * 2^-25 * sqrt(dim).
+    // operand roundings to binary16 (round to nearest even) in the normal range: 2^-11 relative each.  f32 rows: both
+    // operands rounded -> 2^-10 (+ cross term) of |q|*|r|; f16 rows are already exact -> 2^-11.  Products of two binary16
+    // values are exact in f32; the f32 accumulation (MFMA k-order chain) and the reference's own left-to-right error add
+    // (dim + 64) * 2^-24 each, of sum |q_i * r_i| <= |q|*|r|.  These terms are linear in |q|*|r|: they scale with prod.
+    // Binary16 subnormals (|x| < 2^-14) are rounded to a fixed grid of 2^-24: an absolute error of at most 2^-25 per
+    // element whatever the other operand's size.  A row element's error e_i adds sum |q_i| * |e_i| <= 2^-25 * |q|_1
+    // <= 2^-25 * sqrt(dim) * |q|, a query element's 2^-25 * sqrt(dim) * |r|: together 2^-25 * sqrt(dim) * (|q| + |r|),
+    // which no multiple of the clamped prod bounds (a query of norm 1e-6 against rows of norm 1e6: prod 1, error
+    // ~2^-25 * sqrt(dim) * 1e6).  (f16 rows carry no rounding of their own; the same term stays as a bound.)
     const float op = dtype == RLR_F16 ? 4.8828125e-4f : 9.765625e-4f;
     const float acc = 2.0f * (static_cast<float>(dim) + 64.0f) * 5.9604645e-8f;
-    const float sub = 2.0f * 2.9802322e-8f * __builtin_sqrtf(static_cast<float>(dim));
-    return (op * 1.001f + acc + sub) * 1.0625f;
+    const float sub = 2.9802322e-8f * __builtin_sqrtf(static_cast<float>(dim));
+    return ((op * 1.001f + acc) * prod + sub * norm_sum) * 1.0625f;
 }
 
 hipError_t launch_prep_queries(const float *q, uint32_t n_queries, uint32_t q_pitch, uint32_t dim, int dtype,

@@ -133,6 +133,7 @@ struct Ctx {
     uint32_t *d_gsync = nullptr;   // 256 words: sibling-group arrival counters of the persistent batched GEMM (gemm.hip)
     void *h_batch = nullptr;       // pinned: SelectState[bq_cap] | status[bq_cap] (pageable staging makes the async copies synchronous)
     uint32_t bq_cap = 0;            // queries the four arrays above are sized for
+    bool no_f16 = false;            // this call's queries or the rows leave binary16 range: no binary16 nomination
     uint64_t *d_bcand = nullptr;    // q x fin_cap packed candidates
     uint64_t bcand_cap = 0;         // entries
     float *d_sample = nullptr;      // q x S nominated scores of the sample rows
@@ -186,6 +187,9 @@ struct rlr_index {
                               // RLR_BATCH_MIN=n forces a threshold (a huge n disables the path)
     float max_row_sumsq = 1.0f; // largest sum of squares of a row stored with normalize_on_device = 0 (>= 1): the guard
                                 // bands are derived for unit-norm operands and scale with |row| * |query|
+    bool f16_overflow = false;  // an f32 row stored as given holds an element outside binary16 range (|x| > 65504):
+                                // binary16 nomination would see it as +-Inf (and Inf - Inf = NaN); such rows stay
+                                // on the f32 paths until the next upload
     bool image_enabled = false; // keep a binary16 nomination image of the rows for the batched GEMM
     bool image_scan = false;    // single queries nominate over the image too (half the bytes of f32 rows)
     // optional 8-bit nomination copy for single queries (q8.hip): a quarter of the f32 bytes
@@ -797,6 +801,20 @@ int32_t sync_image(rlr_index *ix, uint64_t first_row)
     return RLR_OK;
 }
 
+// does any of the n values lie outside binary16 range (|x| > 65504, Inf included)?  NaN does not count: a NaN operand
+// makes the reference's score NaN as well, which orders last on every path.
+static bool beyond_f16(const float *v, uint32_t n)
+{
+    for (uint32_t i = 0; i < n; ++i)
+        if (std::fabs(v[i]) > 65504.0f)
+            return true;
+    return false;
+}
+
+// a vector with an element beyond binary16 range has a sum of squares above 65504^2 -- the cheap test in front of the
+// element-wise one (row sums of squares come from an f32 reduction: the ingest test leaves it 0.1 % of slack)
+constexpr double kF16MaxSq = 65504.0 * 65504.0;
+
 // Copy host rows in, normalise (optionally) and store them at row `first`.
 int32_t ingest(rlr_index *ix, const float *rows, uint64_t n, uint64_t first, int normalize)
 {
@@ -826,9 +844,13 @@ int32_t ingest(rlr_index *ix, const float *rows, uint64_t n, uint64_t first, int
             // rows stored as given: remember the largest norm (NaN rows order last anyway; they do not widen the band)
             h_norm.resize(m);
             e = hipMemcpy(h_norm.data(), d_norm, m * sizeof(float), hipMemcpyDeviceToHost);
-            for (uint64_t i = 0; i < m && e == hipSuccess; ++i)
+            for (uint64_t i = 0; i < m && e == hipSuccess; ++i) {
                 if (h_norm[i] > ix->max_row_sumsq)
                     ix->max_row_sumsq = h_norm[i];
+                if (ix->dtype == RLR_F32 && !ix->f16_overflow && h_norm[i] > 0.999 * kF16MaxSq &&
+                    beyond_f16(rows + (r0 + i) * ix->dim, ix->dim))
+                    ix->f16_overflow = true;
+            }
         }
         if (e != hipSuccess)
             st = fail(RLR_E_HIP, "row ingest failed: %s", hipGetErrorString(e));
@@ -1010,13 +1032,13 @@ namespace {
 
 // Will this index's single-query scans take their query in the kernel arguments?  (Then nothing is uploaded in front of
 // them: workgroup 0 of the scan leaves the query in the context's device buffer for the kernels behind it.)
-bool scans_take_host_query(const rlr_index *ix, const float *h_q);
+bool scans_take_host_query(const rlr_index *ix, const Ctx *c, const float *h_q);
 
 // The queries of a call whose pipelines start with enqueue_query_scan: by the scans themselves where they can, else uploaded.
 hipError_t upload_queries(Ctx *c, const float *h_q, size_t q_bytes, hipStream_t s);
 hipError_t stage_queries_for_scans(const rlr_index *ix, Ctx *c, const float *h_q, size_t q_bytes, hipStream_t s)
 {
-    c->h_q_kq = scans_take_host_query(ix, h_q) ? h_q : nullptr;
+    c->h_q_kq = scans_take_host_query(ix, c, h_q) ? h_q : nullptr;
     return c->h_q_kq ? hipSuccess : upload_queries(c, h_q, q_bytes, s);
 }
 
@@ -1038,6 +1060,8 @@ struct SearchPlan {
     float two_eps;
     float two_eps_img; // band when the nomination scan ran over the binary16 image
     float scale = 1.0f; // |row|_max * |query|_max when that exceeds 1 (the bands above already carry it)
+    float norm_sum = 2.0f; // |row|_max + |query|_max, rounded up: the binary16 subnormal term of nomination_eps
+    bool f16_ok = true;    // every operand fits binary16 (see plan_bands)
     bool unordered = false; // the consumer wants the best k as a SET (the hybrid blend re-orders everything anyway)
 };
 
@@ -1059,22 +1083,30 @@ static double sumsq_f64(const float *v, uint32_t n)
     return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
 }
 
-float band_scale(const rlr_index *ix, const float *queries, uint32_t nq)
+// The plan's band factors for this call's queries: p->scale (above), p->norm_sum (nomination_eps) and p->f16_ok.
+void plan_bands(const rlr_index *ix, const float *queries, uint32_t nq, SearchPlan *p)
 {
     double qmax = 0.0;
+    bool f16_ok = !(ix->dtype == RLR_F32 && ix->f16_overflow);
     for (uint32_t q = 0; q < nq; ++q) {
         const double s2 = sumsq_f64(queries + static_cast<size_t>(q) * ix->dim, ix->dim);
         if (s2 > qmax) // (a NaN query compares false: its scores are NaN and order last whatever the band)
             qmax = s2;
+        if (f16_ok && s2 > kF16MaxSq && beyond_f16(queries + static_cast<size_t>(q) * ix->dim, ix->dim))
+            f16_ok = false;
     }
-    const double f = std::sqrt(qmax) * std::sqrt(static_cast<double>(ix->max_row_sumsq)) * 1.000002;
-    if (!(f > 1.0001))
-        return 1.0f;
-    return std::isfinite(f) ? static_cast<float>(f) : 3.0e38f;
+    const double qn = std::sqrt(qmax), rn = std::sqrt(static_cast<double>(ix->max_row_sumsq));
+    const double f = qn * rn * 1.000002;
+    p->scale = !(f > 1.0001) ? 1.0f : std::isfinite(f) ? static_cast<float>(f) : 3.0e38f;
+    // unit-norm operands give exactly 2, so the unit-norm band is unchanged
+    const double sum = qn + rn;
+    p->norm_sum = !(sum > 2.0001) ? 2.0f : sum * 1.000002 < 3.0e38 ? static_cast<float>(sum * 1.000002) : 3.0e38f;
+    p->f16_ok = f16_ok;
 }
 
 int32_t ctx_prepare(rlr_index *ix, Ctx *c, uint32_t nq, const SearchPlan &p)
 {
+    c->no_f16 = !p.f16_ok;
     if (c->q_cap < nq || !c->d_query) {
         if (c->d_query) (void)hipFree(c->d_query);
         if (c->d_state) (void)hipFree(c->d_state);
@@ -1624,9 +1656,9 @@ __global__ __launch_bounds__(256) void hybrid_emit_kernel(const uint32_t *__rest
 namespace {
 
 // f32 rows with an up-to-date image and the opt-in set: the nomination scan reads the binary16 image
-bool scan_over_image(const rlr_index *ix)
+bool scan_over_image(const rlr_index *ix, const Ctx *c)
 {
-    return ix->image_scan && ix->image_enabled && ix->d_image && ix->dtype == RLR_F32;
+    return ix->image_scan && ix->image_enabled && ix->d_image && ix->dtype == RLR_F32 && !(c && c->no_f16);
 }
 
 // ||q||_2 per staged query, rounded up (only the 8-bit nomination band needs it)
@@ -1647,9 +1679,9 @@ bool scan_over_q8(const rlr_index *ix)
     return ix->q8_enabled && ix->d_q8 && !ix->q8_has_inf;
 }
 
-bool scans_take_host_query(const rlr_index *ix, const float *h_q)
+bool scans_take_host_query(const rlr_index *ix, const Ctx *c, const float *h_q)
 {
-    if (scan_over_q8(ix) || scan_over_image(ix) || ix->n_rows == 0)
+    if (scan_over_q8(ix) || scan_over_image(ix, c) || ix->n_rows == 0)
         return false;
     ScanArgs sa;
     sa.rows = ix->d_rows;
@@ -1675,12 +1707,23 @@ float q8_two_eps(const rlr_index *ix, float q_norm, float guard_eps)
     return 2.0f * (ix->q8_delta * qn + q8_arith_eps(ix->dim, ix->q8_scale_max, qn) + dflt) * scale;
 }
 
-// band for image-nominated scores: the nomination bound, scaled like the caller scaled guard_eps
-float image_two_eps(const rlr_index *ix, float guard_eps)
+// band for image-nominated scores: the nomination bound for the plan's norms, scaled like the caller scaled guard_eps
+// (eps = the caller's guard_eps, or the default, times p.scale)
+float image_two_eps(const rlr_index *ix, float eps, const SearchPlan &p)
 {
-    const float dflt = rlr_default_guard_eps(ix->dim);
-    const float scale = guard_eps > dflt ? guard_eps / dflt : 1.0f;
-    return 2.0f * nomination_eps(ix->dim, ix->dtype) * scale;
+    const float dflt = rlr_default_guard_eps(ix->dim) * p.scale;
+    const float scale = eps > dflt ? eps / dflt : 1.0f;
+    return 2.0f * nomination_eps(ix->dim, ix->dtype, p.scale, p.norm_sum) * scale;
+}
+
+// A call whose operands leave binary16 range (plan_bands) nominates over the f32 rows: count the queries a binary16
+// nomination would have served otherwise -- the batched GEMM (`batch_f16`) or the scan over the image.
+void count_f16_fallbacks(rlr_index *ix, const SearchPlan &p, uint32_t nq, bool batch_f16)
+{
+    if (p.f16_ok || !(batch_f16 || scan_over_image(ix, nullptr)))
+        return;
+    std::lock_guard<std::mutex> lk(ix->mu);
+    ix->prof.n_f16_range_fallbacks += nq;
 }
 
 // after a synchronisation: did the zero-histogram assertion of a poisoned run fire?
@@ -1731,7 +1774,7 @@ hipError_t enqueue_query_scan(rlr_index *ix, Ctx *c, uint32_t qi, bool timed)
         if (const char *v = getenv("RLR_SCAN_VARIANT"))
             sa.variant = static_cast<int>(strtol(v, nullptr, 0));
     const bool q8 = scan_over_q8(ix);
-    const bool img = !q8 && scan_over_image(ix);
+    const bool img = !q8 && scan_over_image(ix, c);
     if (q8)
         e = launch_q8_scan(ix->d_q8, ix->d_q8_scale, n, ix->dim, dq, c->d_scores, hist1, ix->n_cu, s);
     else if (img)
@@ -1757,7 +1800,7 @@ hipError_t enqueue_query_rest(rlr_index *ix, Ctx *c, uint32_t qi, const SearchPl
     SelectState *st = c->d_state + qi;
     const float *dq = c->d_query + static_cast<size_t>(qi) * ix->q_pitch;
     const bool q8 = scan_over_q8(ix);
-    const bool img = !q8 && scan_over_image(ix);
+    const bool img = !q8 && scan_over_image(ix, c);
     const float band = q8 ? q8_two_eps(ix, qi < c->q_norm.size() ? c->q_norm[qi] : 1.0f, p.two_eps * 0.5f)
                           : (img ? p.two_eps_img : p.two_eps);
     // Up to a few million rows the k-th score's digit-1 bin holds a few hundred scores and the tail's one-pass (DIRECT)
@@ -1900,9 +1943,18 @@ bool env_is_one(const char *name)
     return v && v[0] == '1';
 }
 
-bool batch_eligible(const rlr_index *ix, uint32_t nq, uint32_t k)
+// 2..8 queries over f32 rows of these shapes share one VALU scan (scan_multi_kernel) in run_batched
+bool batch_multi_shape(const rlr_index *ix, uint32_t nq)
+{
+    return nq <= 8 && ix->dtype == RLR_F32 && ix->pitch16 % 64 == 0 && ix->pitch16 / 64 <= 4 && ix->pitch16 * 4 == ix->dim;
+}
+
+bool batch_eligible(const rlr_index *ix, uint32_t nq, uint32_t k, bool f16_ok = true)
 {
     if (nq < 2 || ix->dim % 128 != 0 || ix->n_rows < 4096 || k * 8 > batch_finish_capacity())
+        return false;
+    // operands beyond binary16 range: only the f32 shared scan may nominate
+    if (!f16_ok && !(batch_multi_shape(ix, nq) && !(ix->image_enabled && ix->d_image) && !env_is_one("RLR_NO_MULTI_SCAN")))
         return false;
     if (ix->batch_min > 0)
         return nq >= ix->batch_min;
@@ -1913,14 +1965,13 @@ bool batch_eligible(const rlr_index *ix, uint32_t nq, uint32_t k)
     const double row_bytes = static_cast<double>(ix->n_rows) * ix->dim * (ix->dtype == RLR_F16 ? 2.0 : 4.0);
     // the single-query scan streams the 8-bit copy / the binary16 image when those are switched on
     const double scan_bytes = static_cast<double>(ix->n_rows) * ix->dim *
-                              (scan_over_q8(ix) ? 1.0 : (scan_over_image(ix) || ix->dtype == RLR_F16) ? 2.0 : 4.0);
+                              (scan_over_q8(ix) ? 1.0 : (scan_over_image(ix, nullptr) || ix->dtype == RLR_F16) ? 2.0 : 4.0);
     const double t_single = 60e-6 + scan_bytes / 6.2e12;
     const bool image = ix->image_enabled && ix->d_image;
     // (over the image, batches of <= 128 queries take the resident-query kernel: ~5 TB/s of binary16)
     const double pass = image ? static_cast<double>(ix->n_rows) * ix->dim * 2.0 / (nq <= 128 ? 5.0e12 : 3.0e12)
                               : row_bytes / 3.7e12;
-    const bool multi = nq <= 8 && ix->dtype == RLR_F32 && ix->pitch16 % 64 == 0 && ix->pitch16 / 64 <= 4 &&
-                       ix->pitch16 * 4 == ix->dim && !image;
+    const bool multi = batch_multi_shape(ix, nq) && !image;
     if (multi) // one VALU pass for all of them + the per-query selects over the materialised scores
         return nq * t_single > 0.3e-3 + row_bytes / 5.5e12 + nq * (static_cast<double>(ix->n_rows) * 12.0 / 3.0e12);
     const double t_batch = 0.8e-3 + pass * ((nq + 255) / 256);
@@ -1939,9 +1990,8 @@ int32_t run_batched(rlr_index *ix, Ctx *c, uint32_t q0, uint32_t nq, const Searc
     const uint32_t n_qblocks = (nq + 255) / 256;
     // 2..8 queries over f32 rows: one VALU pass over the rows for all of them (scan_multi_kernel) instead of the
     // matrix-core pipeline -- about the cost of a single scan, scores in wavefront order (the tight f32 band)
-    const bool use_multi = nq <= 8 && ix->dtype == RLR_F32 && ix->pitch16 % 64 == 0 && ix->pitch16 / 64 <= 4 &&
-                           ix->pitch16 * 4 == ix->dim && !(ix->image_enabled && ix->d_image) && !env_is_one("RLR_NO_MULTI_SCAN");
-    const float eps_nom = use_multi ? 0.5f * p.two_eps : nomination_eps(ix->dim, ix->dtype) * p.scale;
+    const bool use_multi = batch_multi_shape(ix, nq) && !(ix->image_enabled && ix->d_image) && !env_is_one("RLR_NO_MULTI_SCAN");
+    const float eps_nom = use_multi ? 0.5f * p.two_eps : nomination_eps(ix->dim, ix->dtype, p.scale, p.norm_sum);
     const float two_eps = 2.0f * eps_nom;
     // Sample rows [0, S): the floor for the rest of the corpus is the sample's rank-th score, and S is large enough that
     // the expected number of later rows above it (rank * N / S) stays well inside the per-query candidate capacity.
@@ -2129,10 +2179,10 @@ int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uin
     const uint32_t n = static_cast<uint32_t>(ix->n_rows);
     SearchPlan p;
     p.k = std::min<uint32_t>(k_req, n);
-    p.scale = band_scale(ix, queries, nq);
+    plan_bands(ix, queries, nq, &p);
     const float eps = (guard_eps >= 0.0f ? guard_eps : rlr_default_guard_eps(ix->dim)) * p.scale;
     p.two_eps = 2.0f * eps;
-    p.two_eps_img = image_two_eps(ix, eps);
+    p.two_eps_img = image_two_eps(ix, eps, p);
     p.cap = kLdsSortCap;
     *plan_out = p;
     if (h_results)
@@ -2159,7 +2209,9 @@ int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uin
     stage_query_norms(ix, c, queries, nq);
     hipStream_t s = c->stream;
     c->hist_dirty = true; // cleared when every enqueued pipeline has run to its histogram-clearing stage
-    const bool batched = batch_eligible(ix, nq, p.k);
+    const bool batched = batch_eligible(ix, nq, p.k, p.f16_ok);
+    if (!batched)
+        count_f16_fallbacks(ix, p, nq, batch_eligible(ix, nq, p.k));
     c->h_q_kq = nullptr;
     if (batched) // (the matrix-core pipeline reads the queries from device memory)
         RLR_HIP(upload_queries(c, h_q, q_bytes, s));
@@ -2282,7 +2334,7 @@ int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uin
             ix->prof.rescore_ms += rescore_ms;
             ix->prof.total_ms += total_ms;
             ix->prof.scan_bytes += static_cast<uint64_t>(nq) * ix->n_rows * ix->dim *
-                                   (scan_over_q8(ix) ? 1 : (ix->dtype == RLR_F16 || scan_over_image(ix)) ? 2 : 4);
+                                   (scan_over_q8(ix) ? 1 : (ix->dtype == RLR_F16 || scan_over_image(ix, c)) ? 2 : 4);
         }
     }
     return RLR_OK;
@@ -2437,6 +2489,7 @@ int32_t rlr_index_upload(rlr_index *ix, const float *rows, uint64_t n_rows, int3
     RLR_TRY(use_device(ix));
     ix->n_rows = 0;
     ix->max_row_sumsq = 1.0f;
+    ix->f16_overflow = false;
     RLR_TRY(ensure_rows(ix, n_rows));
     RLR_TRY(ingest(ix, rows, n_rows, 0, normalize_on_device));
     ix->n_rows = n_rows;
@@ -2696,11 +2749,12 @@ int32_t rlr_search_topk_device_begin(rlr_index *ix, const float *queries, uint32
     lease.c = c; // released on every error path below
     SearchPlan p;
     p.k = k;
-    p.scale = band_scale(ix, queries, n_queries);
+    plan_bands(ix, queries, n_queries, &p);
     p.two_eps = 2.0f * (guard_eps >= 0.0f ? guard_eps : rlr_default_guard_eps(ix->dim)) * p.scale;
-    p.two_eps_img = image_two_eps(ix, p.two_eps * 0.5f);
+    p.two_eps_img = image_two_eps(ix, p.two_eps * 0.5f, p);
     p.cap = kLdsSortCap;
     RLR_TRY(ctx_prepare(ix, c, n_queries, p));
+    count_f16_fallbacks(ix, p, n_queries, false);
     const size_t q_bytes = static_cast<size_t>(n_queries) * ix->q_pitch * sizeof(float);
     RLR_TRY(pin_reserve(c, q_bytes + (static_cast<size_t>(n_queries) * k + n_queries) * sizeof(uint64_t)));
     float *h_q = static_cast<float *>(c->h_pin);
@@ -2784,7 +2838,7 @@ int32_t rlr_search_topk_device_end(rlr_index *ix, void *ticket, uint32_t *n_over
             ix->prof.rescore_ms += t_res;
             ix->prof.total_ms += t_scan + t_sel + t_res;
             ix->prof.scan_bytes += static_cast<uint64_t>(c->pending_q) * ix->n_rows * ix->dim *
-                                   (scan_over_q8(ix) ? 1 : (ix->dtype == RLR_F16 || scan_over_image(ix)) ? 2 : 4);
+                                   (scan_over_q8(ix) ? 1 : (ix->dtype == RLR_F16 || scan_over_image(ix, c)) ? 2 : 4);
         }
     }
     c->pending_q = 0;
@@ -2805,6 +2859,9 @@ int32_t rlr_merge_topk(int32_t device_id, const void *d_gathered, uint32_t world
         return fail(RLR_E_INVALID, "world size %u not in [1, 16]", world);
     if (static_cast<uint64_t>(world) * k > 8192)
         return fail(RLR_E_INVALID, "world * k = %llu exceeds the 8192-entry merge", static_cast<unsigned long long>(world) * k);
+    for (uint32_t r = 0; r < world; ++r) // (the merge key holds the global row in 32 bits: corpora of < 2^32 rows)
+        if (bases[r] >= 0xFFFFFFFFull)
+            return fail(RLR_E_INVALID, "shard base %llu is not below 2^32 - 1", static_cast<unsigned long long>(bases[r]));
     RLR_HIP(hipSetDevice(device_id));
     // results are written straight into pinned, device-mapped host memory: no D2H copy
     thread_local void *h_buf = nullptr;
@@ -3019,10 +3076,11 @@ int32_t rlr_search_diverse(rlr_index *ix, const float *query, uint32_t pool, uin
     hipStream_t s = c->stream;
     SearchPlan p;
     p.k = fetch;
-    p.scale = band_scale(ix, query, 1);
+    plan_bands(ix, query, 1, &p);
     const float eps = (guard_eps >= 0.0f ? guard_eps : rlr_default_guard_eps(ix->dim)) * p.scale;
     p.two_eps = 2.0f * eps;
-    p.two_eps_img = image_two_eps(ix, eps);
+    p.two_eps_img = image_two_eps(ix, eps, p);
+    count_f16_fallbacks(ix, p, 1, false);
     p.cap = kLdsSortCap;
     RLR_TRY(ctx_prepare(ix, c, 1, p));
     const uint32_t P = need;
@@ -3100,7 +3158,7 @@ int32_t rlr_search_diverse(rlr_index *ix, const float *query, uint32_t pool, uin
             ix->prof.select_ms += b;
             ix->prof.rescore_ms += d;
             ix->prof.total_ms += a + b + d + m;
-            ix->prof.scan_bytes += ix->n_rows * ix->dim * (scan_over_q8(ix) ? 1 : (ix->dtype == RLR_F16 || scan_over_image(ix)) ? 2 : 4);
+            ix->prof.scan_bytes += ix->n_rows * ix->dim * (scan_over_q8(ix) ? 1 : (ix->dtype == RLR_F16 || scan_over_image(ix, c)) ? 2 : 4);
             ix->prof.n_mmr += 1;
             ix->prof.mmr_ms += m;
         }
@@ -3175,10 +3233,11 @@ static int32_t hybrid_begin_impl(rlr_index *ix, const float *query, uint32_t nee
     hipStream_t s = c->stream;
     SearchPlan p;
     p.k = fetch;
-    p.scale = band_scale(ix, query, 1);
+    plan_bands(ix, query, 1, &p);
     const float eps = (guard_eps >= 0.0f ? guard_eps : rlr_default_guard_eps(ix->dim)) * p.scale;
     p.two_eps = 2.0f * eps;
-    p.two_eps_img = image_two_eps(ix, eps);
+    p.two_eps_img = image_two_eps(ix, eps, p);
+    count_f16_fallbacks(ix, p, 1, false);
     p.cap = kLdsSortCap;
     p.unordered = true; // the blend orders fetched and lexical rows together: it needs the fetched SET and its minimum
     RLR_TRY(ctx_prepare(ix, c, 1, p));
@@ -3353,7 +3412,7 @@ static int32_t hybrid_finish_impl(HybridTicket *ticket, const HybridLexSrc &src,
             ix->prof.select_ms += b;
             ix->prof.rescore_ms += d;
             ix->prof.total_ms += a + b + d + m;
-            ix->prof.scan_bytes += ix->n_rows * ix->dim * (scan_over_q8(ix) ? 1 : (ix->dtype == RLR_F16 || scan_over_image(ix)) ? 2 : 4);
+            ix->prof.scan_bytes += ix->n_rows * ix->dim * (scan_over_q8(ix) ? 1 : (ix->dtype == RLR_F16 || scan_over_image(ix, c)) ? 2 : 4);
             ix->prof.n_mmr += 1;
             ix->prof.mmr_ms += m;
         }

@@ -119,7 +119,7 @@ hipError_t launch_tail_stage1(const TailArgs &a, hipStream_t s);
 hipError_t launch_tail_stage2(const TailArgs &a, hipStream_t s);
 
 // ---- gemm.hip : batched queries, MFMA nomination + per-query exact finish ----------------
-float nomination_eps(uint32_t dim, int dtype);
+float nomination_eps(uint32_t dim, int dtype, float prod = 1.0f, float norm_sum = 2.0f);
 uint32_t batch_finish_capacity();
 hipError_t launch_prep_queries(const float *q, uint32_t n_queries, uint32_t q_pitch, uint32_t dim, int dtype,
                                void *qfrag, hipStream_t s);

@@ -49,6 +49,7 @@ class Profile:
     n_mmr: int = 0
     mmr_ms: float = 0.0
     n_batches_without_image: int = 0
+    n_f16_range_fallbacks: int = 0
 
 
 class GpuIndex:

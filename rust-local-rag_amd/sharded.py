@@ -43,14 +43,17 @@ def merge_packed(gathered, bases, k: int):
     local = 0xFFFFFFFF - (gathered & 0xFFFFFFFF)
     valid = gathered != 0
     glob = local + bases.view(world, 1, 1)
-    # one descending int64 per candidate: score key, then lower global row first
-    comp = (key << 31) | ((1 << 31) - 1 - glob)
-    comp = torch.where(valid, comp, torch.full_like(comp, -1))
+    # one descending int64 per candidate: score key (biased by -2^31 into the signed high word), then lower global row
+    # first in the low 32 bits (global rows < 2^32 - 1, ShardedIndex's limit); INT64_MIN, below every valid entry,
+    # marks padding
+    comp = ((key - (1 << 31)) << 32) | (0xFFFFFFFF - glob)
+    pad = -(1 << 63)
+    comp = torch.where(valid, comp, torch.full_like(comp, pad))
     comp = comp.permute(1, 0, 2).reshape(nq, world * kk)
     top = torch.topk(comp, min(k, world * kk), dim=1, largest=True, sorted=True).values
-    ok = top >= 0
-    rows = torch.where(ok, (1 << 31) - 1 - (top & ((1 << 31) - 1)), torch.full_like(top, -1))
-    skey = torch.where(ok, top >> 31, torch.zeros_like(top))
+    ok = top != pad
+    rows = torch.where(ok, 0xFFFFFFFF - (top & 0xFFFFFFFF), torch.full_like(top, -1))
+    skey = torch.where(ok, (top >> 32) + (1 << 31), torch.zeros_like(top))
     return rows, skey
 
 

@@ -114,6 +114,32 @@ def test_merge_handles_short_shards_and_padding():
     assert rows6[0].tolist() == [4, 1, 2, 5, 0, 3, -1, -1]
 
 
+@pytest.mark.parametrize("base1", [1000, (1 << 31) - 1, 1 << 31, (1 << 31) + 10, (1 << 32) - 40])
+def test_merge_keeps_global_rows_past_2_31(base1):
+    """merge_packed over shard bases up to ShardedIndex's limit of 2^32 rows: the best hit sits on shard 1, past
+    2^31 for the larger bases; every slot keeps its global row and score, ties still go to the lower global row"""
+    import torch
+    rlr = importlib.import_module("rust-local-rag_amd")
+    sharded = importlib.import_module("rust-local-rag_amd.sharded")
+    L = rlr.lib()
+    k = 3
+    g = np.zeros((2, 1, k), dtype=np.uint64)
+    for j, (s, r) in enumerate(((0.5, 3), (0.25, 0), (-0.75, 7))):
+        g[0, 0, j] = L.rlr_pack_result(s, r)
+    for j, (s, r) in enumerate(((0.9, 5), (0.25, 10), (-1.0, 39))):
+        g[1, 0, j] = L.rlr_pack_result(s, r)
+    bases = torch.tensor([0, base1], dtype=torch.int64)
+    rows, key = sharded.merge_packed(torch.from_numpy(g.view(np.int64)), bases, 6)
+    assert rows[0].tolist() == [base1 + 5, 3, 0, base1 + 10, 7, base1 + 39]
+    want = np.array([0.9, 0.5, 0.25, 0.25, -0.75, -1.0], np.float32)
+    assert sharded.key_to_score(key.numpy())[0].view(np.uint32).tolist() == want.view(np.uint32).tolist()
+    rows8, _ = sharded.merge_packed(torch.from_numpy(g.view(np.int64)), bases, 8)   # 6 valid of 6: no padding slots
+    assert rows8[0].tolist() == rows[0].tolist()
+    g[1, 0, 2] = 0                                                                  # one padding slot
+    rows8, _ = sharded.merge_packed(torch.from_numpy(g.view(np.int64)), bases, 8)
+    assert rows8[0].tolist() == [base1 + 5, 3, 0, base1 + 10, 7, -1]
+
+
 # ---- MMR on sharded data: winner-row exchange (all-to-all) + pick-list all-gather ---------------
 def _mmr_worker(rank, world, port, n_total, dim, nq, P, k, lam, seed, ret):
     sys.path.insert(0, ROOT)
