@@ -340,6 +340,42 @@ typedef struct rlr_multi_stats_t {
 } rlr_multi_stats_t;
 int32_t rlr_multi_stats(rlr_multi *m, rlr_multi_stats_t *out, int32_t reset);
 
+/* ---- coalescing of concurrent single-query searches ----------------------- */
+/* Serve concurrent single-query rlr_search_topk calls on this index from shared passes over the rows.
+ * max_group 0 or 1: off (the default).  2..8: at most this many queries share one pass.
+ * linger_us: how long a caller that finds the index idle waits for others before it launches (0 = never waits).
+ * Mutator-class call: needs the same external exclusion as append / delete.
+ *
+ * What is grouped: rlr_search_topk with n_queries == 1 (and so rlr_engine_search without lexical candidates and
+ * rlr_engine_embedding_candidates), on an index where a shared pass beats separate scans -- the rows' shape has the
+ * shared-pass kernel (f32 rows of 256/512/768/1024 elements, binary16 rows of 256/512/768/1024 elements), the corpus is
+ * large enough for the batched cost model (about a million 768-d rows and up; a 100 k-row index runs as without
+ * coalescing), k <= 1024 and neither the nomination image nor the 8-bit copy is switched on.  A caller that finds no
+ * coalesced pass running launches its own pipeline at once (after linger_us, if set); callers that arrive while one
+ * runs join a pending group (one per guard_eps value) that launches as one pass when the running one retires.  The
+ * first member stages every member's query, runs the group and copies each member's prefix of the group's top-k into
+ * that member's buffers; a member whose guard band overflows re-runs on the single-query pipeline inside that pass.
+ * Results are exactly those of the call without coalescing.  Waiting members block on a condition variable (no
+ * polling, no CPU while they wait).  The pass holding a group of G keeps n_rows * G * 4 B of scores in its context
+ * (320 MB at 10 M rows x 8); an allocation failure is reported to every member as RLR_E_OOM.
+ * Not covered: calls with n_queries > 1, the _device / _device_begin variants, rlr_multi_*.  The fused one-enqueue
+ * calls (rlr_search_diverse, rlr_search_hybrid) return *fallback = 1 while coalescing is on and groups qualify, so that
+ * their two-call path's rlr_search_topk is grouped. */
+int32_t rlr_index_set_coalescing(rlr_index *idx, uint32_t max_group, uint32_t linger_us);
+
+typedef struct rlr_coalesce_stats {
+    uint64_t n_calls;            /* single-query calls that went through the coalescer */
+    uint64_t n_solo;             /* ... that ran alone on today's single-query path */
+    uint64_t n_groups;           /* shared passes launched */
+    uint64_t n_grouped_queries;  /* queries served by those passes */
+    uint64_t group_size[9];      /* histogram of group sizes, index = size */
+    uint64_t n_groups_f16;       /* shared passes over binary16 rows (the new kernel) */
+    uint64_t n_handed_back;      /* group members whose guard band overflowed and that re-ran alone */
+    uint64_t n_engine_handbacks; /* fused diverse / hybrid calls that took the two-call path */
+} rlr_coalesce_stats;
+/* reset != 0: zero the counters after reading them */
+int32_t rlr_index_coalesce_stats(rlr_index *idx, rlr_coalesce_stats *out, int32_t reset);
+
 /* ---- measurement hooks --------------------------------------------------- */
 typedef struct rlr_profile {
     uint64_t n_searches;   /* rlr_search_topk* calls (queries, not batches) since reset */

@@ -66,6 +66,12 @@ class ProfileC(C.Structure):
                 ("n_f16_range_fallbacks", C.c_uint64)]
 
 
+class CoalesceStatsC(C.Structure):
+    _fields_ = [("n_calls", C.c_uint64), ("n_solo", C.c_uint64), ("n_groups", C.c_uint64),
+                ("n_grouped_queries", C.c_uint64), ("group_size", C.c_uint64 * 9), ("n_groups_f16", C.c_uint64),
+                ("n_handed_back", C.c_uint64), ("n_engine_handbacks", C.c_uint64)]
+
+
 class MultiStatsC(C.Structure):
     _fields_ = [("n_topk_rccl", C.c_uint64), ("n_topk_host_merge", C.c_uint64), ("n_topk_rccl_fell_back", C.c_uint64),
                 ("topk_rccl_ms", C.c_double), ("n_mmr_exchanges", C.c_uint64), ("mmr_exchange_bytes", C.c_uint64),
@@ -131,6 +137,8 @@ PROTOTYPES = [
     ("rlr_index_row_bytes", C.c_int32, [_H, u32p]),
     ("rlr_mmr_select_staged", C.c_int32, [_H, C.c_void_p, C.c_uint64, u64p, f32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32,
                                           C.c_float, u32p, f32p, u32p]),
+    ("rlr_index_set_coalescing", C.c_int32, [_H, C.c_uint32, C.c_uint32]),
+    ("rlr_index_coalesce_stats", C.c_int32, [_H, C.POINTER(CoalesceStatsC), C.c_int32]),
     ("rlr_profile_enable", C.c_int32, [_H, C.c_int32]),
     ("rlr_profile_read", C.c_int32, [_H, C.POINTER(ProfileC), C.c_int32]),
     ("rlr_index_probe_bandwidth", C.c_int32, [_H, C.c_int32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

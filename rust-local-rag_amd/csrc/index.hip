@@ -155,6 +155,27 @@ struct Ctx {
     const uint64_t *pending_meta = nullptr;
 };
 
+// One caller's part in a coalesced group: its query and where its results go (the caller's own buffers; the caller
+// blocks until the group is done, so they outlive the group's use of them).
+struct CoalesceMember {
+    const float *query;
+    uint32_t k;
+    uint64_t *rows_out;
+    float *cos_out;
+    uint32_t *n_out;
+};
+
+struct CoalesceGroup {
+    uint32_t key = 0;      // bits of the members' guard_eps
+    uint32_t cap = 0;      // members it takes
+    std::vector<CoalesceMember *> members; // [0] is the leader
+    bool sealed = false;   // takes no more members
+    bool go = false;       // holds a pipeline slot
+    bool done = false;     // results written (or status set)
+    int32_t status = 0;
+    char msg[512] = "";
+};
+
 } // namespace
 
 struct rlr_index {
@@ -209,6 +230,14 @@ struct rlr_index {
     int ctx_cap = 16;               // RLR_MAX_CONTEXTS (1..64)
     bool profiling = false;
     rlr_profile prof{};
+    // coalescing of concurrent single-query searches (rlr_index_set_coalescing; the coalescer section below)
+    std::atomic<uint32_t> co_max{0};  // 0: off -- the only thing a single-query call reads when it is
+    uint32_t co_linger_us = 0;        // (co_mu)
+    std::mutex co_mu;
+    std::condition_variable co_cv;    // leaders wait for a pipeline slot / their group to fill, members for their results
+    int co_running = 0;               // coalescer pipelines in flight (co_mu)
+    std::vector<std::shared_ptr<CoalesceGroup>> co_pending; // groups waiting for a slot, oldest first (co_mu)
+    rlr_coalesce_stats co_stats{};    // (co_mu)
 };
 
 namespace {
@@ -1943,18 +1972,23 @@ bool env_is_one(const char *name)
     return v && v[0] == '1';
 }
 
-// 2..8 queries over f32 rows of these shapes share one VALU scan (scan_multi_kernel) in run_batched
-bool batch_multi_shape(const rlr_index *ix, uint32_t nq)
+// 2..8 queries over f32 rows of these shapes share one VALU scan (scan_multi_kernel) in run_batched.  `coalesced`: the
+// queries are a group of concurrent single-query calls (rlr_index_set_coalescing) -- those also share one pass over
+// binary16 rows of 256 / 512 / 768 / 1024 elements (scan_multi_h_kernel); explicit multi-query calls over binary16
+// rows keep the matrix-core pipeline.
+bool batch_multi_shape(const rlr_index *ix, uint32_t nq, bool coalesced = false)
 {
+    if (coalesced && ix->dtype == RLR_F16)
+        return nq <= 8 && ix->pitch16 % 32 == 0 && ix->pitch16 / 32 <= 4 && ix->pitch16 * 8 == ix->dim;
     return nq <= 8 && ix->dtype == RLR_F32 && ix->pitch16 % 64 == 0 && ix->pitch16 / 64 <= 4 && ix->pitch16 * 4 == ix->dim;
 }
 
-bool batch_eligible(const rlr_index *ix, uint32_t nq, uint32_t k, bool f16_ok = true)
+bool batch_eligible(const rlr_index *ix, uint32_t nq, uint32_t k, bool f16_ok = true, bool coalesced = false)
 {
     if (nq < 2 || ix->dim % 128 != 0 || ix->n_rows < 4096 || k * 8 > batch_finish_capacity())
         return false;
     // operands beyond binary16 range: only the f32 shared scan may nominate
-    if (!f16_ok && !(batch_multi_shape(ix, nq) && !(ix->image_enabled && ix->d_image) && !env_is_one("RLR_NO_MULTI_SCAN")))
+    if (!f16_ok && !(batch_multi_shape(ix, nq, coalesced) && !(ix->image_enabled && ix->d_image) && !env_is_one("RLR_NO_MULTI_SCAN")))
         return false;
     if (ix->batch_min > 0)
         return nq >= ix->batch_min;
@@ -1971,7 +2005,7 @@ bool batch_eligible(const rlr_index *ix, uint32_t nq, uint32_t k, bool f16_ok = 
     // (over the image, batches of <= 128 queries take the resident-query kernel: ~5 TB/s of binary16)
     const double pass = image ? static_cast<double>(ix->n_rows) * ix->dim * 2.0 / (nq <= 128 ? 5.0e12 : 3.0e12)
                               : row_bytes / 3.7e12;
-    const bool multi = batch_multi_shape(ix, nq) && !image;
+    const bool multi = batch_multi_shape(ix, nq, coalesced) && !image;
     if (multi) // one VALU pass for all of them + the per-query selects over the materialised scores
         return nq * t_single > 0.3e-3 + row_bytes / 5.5e12 + nq * (static_cast<double>(ix->n_rows) * 12.0 / 3.0e12);
     const double t_batch = 0.8e-3 + pass * ((nq + 255) / 256);
@@ -1982,7 +2016,7 @@ bool batch_eligible(const rlr_index *ix, uint32_t nq, uint32_t k, bool f16_ok = 
 // and leaves k packed results per query in d_out; h_status[q] != 0 marks queries the caller must
 // re-run through the single-query pipeline.
 int32_t run_batched(rlr_index *ix, Ctx *c, uint32_t q0, uint32_t nq, const SearchPlan &p, uint64_t *d_out,
-                    std::vector<uint32_t> &h_status, uint64_t *h_res_out)
+                    std::vector<uint32_t> &h_status, uint64_t *h_res_out, bool coalesced = false)
 {
     hipStream_t s = c->stream;
     const uint32_t n = static_cast<uint32_t>(ix->n_rows);
@@ -1990,7 +2024,7 @@ int32_t run_batched(rlr_index *ix, Ctx *c, uint32_t q0, uint32_t nq, const Searc
     const uint32_t n_qblocks = (nq + 255) / 256;
     // 2..8 queries over f32 rows: one VALU pass over the rows for all of them (scan_multi_kernel) instead of the
     // matrix-core pipeline -- about the cost of a single scan, scores in wavefront order (the tight f32 band)
-    const bool use_multi = batch_multi_shape(ix, nq) && !(ix->image_enabled && ix->d_image) && !env_is_one("RLR_NO_MULTI_SCAN");
+    const bool use_multi = batch_multi_shape(ix, nq, coalesced) && !(ix->image_enabled && ix->d_image) && !env_is_one("RLR_NO_MULTI_SCAN");
     const float eps_nom = use_multi ? 0.5f * p.two_eps : nomination_eps(ix->dim, ix->dtype, p.scale, p.norm_sum);
     const float two_eps = 2.0f * eps_nom;
     // Sample rows [0, S): the floor for the rest of the corpus is the sample's rank-th score, and S is large enough that
@@ -2099,7 +2133,9 @@ int32_t run_batched(rlr_index *ix, Ctx *c, uint32_t q0, uint32_t nq, const Searc
         sa.n_cu = ix->n_cu;
         sa.variant = ix->scan_variant;
         hipError_t e = hipSuccess;
-        if (!launch_scan_multi(sa, ix->q_pitch, nq, s_stride, s, &e))
+        // (binary16 rows: the same band -- the widening is exact and the products and sums are f32 as in the single-query scan)
+        if (!(ix->dtype == RLR_F16 ? launch_scan_multi_f16(sa, ix->q_pitch, nq, s_stride, s, &e)
+                                   : launch_scan_multi(sa, ix->q_pitch, nq, s_stride, s, &e)))
             return fail(RLR_E_INTERNAL, "multi-query scan refused a shape its gate accepted");
         RLR_HIP(e);
     } else {
@@ -2173,9 +2209,14 @@ int32_t run_batched(rlr_index *ix, Ctx *c, uint32_t q0, uint32_t nq, const Searc
 // variant), else in the context buffer AND in pinned host memory (*h_results, nq x k u64) -- one
 // H2D (queries), one D2H (results + per-query candidate counts) and one stream synchronisation
 // per call on the common path.
+// coalesced: the queries are a group of concurrent single-query calls (batch_multi_shape); *n_handed_back (optional):
+// how many of them the batched pipeline handed back to the single-query pipeline.
 int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uint32_t k_req, float guard_eps,
-                   uint64_t *d_out_user, SearchPlan *plan_out, const uint64_t **h_results)
+                   uint64_t *d_out_user, SearchPlan *plan_out, const uint64_t **h_results, bool coalesced = false,
+                   uint32_t *n_handed_back = nullptr)
 {
+    if (n_handed_back)
+        *n_handed_back = 0;
     const uint32_t n = static_cast<uint32_t>(ix->n_rows);
     SearchPlan p;
     p.k = std::min<uint32_t>(k_req, n);
@@ -2209,7 +2250,7 @@ int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uin
     stage_query_norms(ix, c, queries, nq);
     hipStream_t s = c->stream;
     c->hist_dirty = true; // cleared when every enqueued pipeline has run to its histogram-clearing stage
-    const bool batched = batch_eligible(ix, nq, p.k, p.f16_ok);
+    const bool batched = batch_eligible(ix, nq, p.k, p.f16_ok, coalesced);
     if (!batched)
         count_f16_fallbacks(ix, p, nq, batch_eligible(ix, nq, p.k));
     c->h_q_kq = nullptr;
@@ -2235,11 +2276,13 @@ int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uin
         for (uint32_t q0 = 0; q0 < nq; q0 += kBatchMaxQueries) {
             const uint32_t m = std::min(kBatchMaxQueries, nq - q0);
             RLR_TRY(run_batched(ix, c, q0, m, p, d_out + static_cast<size_t>(q0) * p.k, status,
-                                d_out_user ? nullptr : h_res + static_cast<size_t>(q0) * p.k));
+                                d_out_user ? nullptr : h_res + static_cast<size_t>(q0) * p.k, coalesced));
             for (uint32_t i = 0; i < m; ++i)
                 if (status[i] != 0)
                     redo.push_back(q0 + i);
         }
+        if (n_handed_back)
+            *n_handed_back = static_cast<uint32_t>(redo.size());
         for (uint32_t q : redo) {
             RLR_HIP(enqueue_query(ix, c, q, p, d_out + static_cast<size_t>(q) * p.k, d_meta + q, false));
             RLR_HIP(hipMemcpyAsync(h_meta + q, d_meta + q, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
@@ -2365,6 +2408,215 @@ int32_t upload_list(rlr_index *ix, Ctx *c, const uint64_t *rows, uint32_t n, uin
     }
     RLR_HIP(hipMemcpyAsync(c->d_list, h, static_cast<size_t>(n) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     return RLR_OK;
+}
+
+// unpack_result of `take` packed results into a caller's rows / cosines, written without branches so that the loop
+// vectorises (a batch of 1024 x 308 results is 315 k of them)
+void unpack_results(const uint64_t *__restrict__ src, uint32_t take, uint64_t *__restrict__ ro, float *cos_out)
+{
+    uint32_t *__restrict__ co = reinterpret_cast<uint32_t *>(cos_out);
+    for (uint32_t i = 0; i < take; ++i) {
+        const uint64_t w = src[i];
+        const uint32_t key = static_cast<uint32_t>(w >> 32);
+        const uint32_t neg = static_cast<uint32_t>(static_cast<int32_t>(key) >> 31);        // all ones: key of a value >= +0
+        const uint32_t bits = key ^ (0xFFFFFFFFu ^ (neg & 0x7FFFFFFFu));                     // key_score(): & 0x7FFFFFFF or ~
+        co[i] = key == 0u ? 0x7FC00000u : bits;
+        ro[i] = 0xFFFFFFFFu - static_cast<uint32_t>(w);
+    }
+}
+
+// rlr_search_topk on a context of its own (n_rows > 0, k > 0)
+int32_t search_topk_host(rlr_index *ix, const float *queries, uint32_t n_queries, uint32_t k, float guard_eps, uint64_t *rows_out,
+                         float *cos_out, uint32_t *n_out)
+{
+    CtxLease lease(ix);
+    RLR_TRY(ctx_acquire(ix, &lease.c));
+    Ctx *c = lease.c;
+    SearchPlan p;
+    const uint64_t *h = nullptr;
+    RLR_TRY(run_search(ix, c, queries, n_queries, k, guard_eps, nullptr, &p, &h));
+    if (!h)
+        return fail(RLR_E_INTERNAL, "search produced no result buffer");
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        n_out[q] = p.k;
+        unpack_results(h + static_cast<size_t>(q) * p.k, p.k, rows_out + static_cast<size_t>(q) * k, cos_out + static_cast<size_t>(q) * k);
+    }
+    return RLR_OK;
+}
+
+// ---- coalescer: concurrent single-query calls served from shared passes (rlr_index_set_coalescing) ----------------
+// A caller that finds no coalescer pipeline running and nothing pending runs today's single-query pipeline at once
+// (after linger_us, if set, as the leader of a group others may join meanwhile).  A caller that arrives while one runs
+// joins the oldest open group of its guard band, or opens one as its leader.  A group is sealed when it is full or when
+// it gets a pipeline slot -- a retiring pipeline hands its slot to the oldest pending group.  The leader runs the group
+// as one multi-query call (run_search -> run_batched: one shared pass, the per-query selects, the finish; queries whose
+// band overflows are re-run on the single-query pipeline inside it) and copies each member's prefix into the member's
+// buffers.  Everything waits on one condition variable: no polling.
+constexpr int kCoalesceInflight = 1; // coalescer pipelines per index (coalescing)
+
+// Would two concurrent single-query calls with this k share a pass?  (Everything else runs today's path at once.)
+bool coalesce_eligible(const rlr_index *ix, uint32_t k)
+{
+    return !ix->image_enabled && !ix->q8_enabled && batch_multi_shape(ix, 2, true) && !env_is_one("RLR_NO_MULTI_SCAN") &&
+           batch_eligible(ix, 2, std::min<uint64_t>(k, ix->n_rows), true, true);
+}
+
+// co_mu held: a retiring pipeline hands its slot to the oldest pending group without one
+void coalesce_retire(rlr_index *ix)
+{
+    ix->co_running--;
+    for (auto &g : ix->co_pending)
+        if (!g->go && ix->co_running < kCoalesceInflight) {
+            g->go = true;
+            g->sealed = true;
+            ix->co_running++;
+        }
+    ix->co_cv.notify_all();
+}
+
+// the group's queries as one call; every member's results written or g->status set
+void coalesce_run(rlr_index *ix, CoalesceGroup *g, float guard_eps)
+{
+    const uint32_t nq = static_cast<uint32_t>(g->members.size());
+    uint32_t kmax = 0;
+    for (const CoalesceMember *m : g->members)
+        kmax = std::max(kmax, m->k);
+    int32_t st = RLR_OK;
+    uint32_t handed = 0;
+    bool ran = false;
+    {
+        std::vector<float> qs;
+        try {
+            qs.resize(static_cast<size_t>(nq) * ix->dim);
+        } catch (const std::bad_alloc &) {
+            st = fail(RLR_E_OOM, "host allocation failed");
+        }
+        for (uint32_t i = 0; st == RLR_OK && i < nq; ++i)
+            std::memcpy(qs.data() + static_cast<size_t>(i) * ix->dim, g->members[i]->query, ix->dim * sizeof(float));
+        CtxLease lease(ix);
+        if (st == RLR_OK)
+            st = ctx_acquire(ix, &lease.c);
+        SearchPlan p;
+        const uint64_t *h = nullptr;
+        if (st == RLR_OK)
+            st = run_search(ix, lease.c, qs.data(), nq, kmax, guard_eps, nullptr, &p, &h, /*coalesced=*/true, &handed);
+        if (st == RLR_OK && !h)
+            st = fail(RLR_E_INTERNAL, "search produced no result buffer");
+        if (st == RLR_OK) {
+            ran = true;
+            for (uint32_t i = 0; i < nq; ++i) {
+                CoalesceMember *m = g->members[i];
+                const uint32_t take = std::min(m->k, p.k); // a prefix of the group's top-kmax: the order is total
+                *m->n_out = take;
+                unpack_results(h + static_cast<size_t>(i) * p.k, take, m->rows_out, m->cos_out);
+            }
+        }
+    }
+    std::lock_guard<std::mutex> lk(ix->co_mu);
+    g->status = st;
+    if (st != RLR_OK)
+        snprintf(g->msg, sizeof(g->msg), "%s", g_err);
+    if (ran) {
+        rlr_coalesce_stats &s = ix->co_stats;
+        s.n_groups += 1;
+        s.n_grouped_queries += nq;
+        s.group_size[nq] += 1;
+        s.n_groups_f16 += ix->dtype == RLR_F16;
+        s.n_handed_back += handed;
+    }
+}
+
+int32_t coalesced_search(rlr_index *ix, const float *query, uint32_t k, float guard_eps, uint64_t *rows_out, float *cos_out,
+                         uint32_t *n_out)
+{
+    uint32_t key;
+    std::memcpy(&key, &guard_eps, sizeof(key));
+    CoalesceMember me{query, k, rows_out, cos_out, n_out};
+    std::unique_lock<std::mutex> lk(ix->co_mu);
+    ix->co_stats.n_calls += 1;
+    const uint32_t cap = std::min<uint32_t>(ix->co_max.load(std::memory_order_relaxed), 8);
+    for (const std::shared_ptr<CoalesceGroup> &open : ix->co_pending) {
+        if (open->sealed || open->key != key)
+            continue;
+        std::shared_ptr<CoalesceGroup> g = open; // (the leader drops the group from co_pending before it runs it)
+        g->members.push_back(&me);
+        if (g->members.size() >= g->cap) {
+            g->sealed = true;
+            ix->co_cv.notify_all(); // a lingering leader launches now
+        }
+        ix->co_cv.wait(lk, [&] { return g->done; });
+        if (g->status != RLR_OK)
+            return fail(g->status, "%s", g->msg);
+        return RLR_OK;
+    }
+    const bool idle = ix->co_running < kCoalesceInflight && ix->co_pending.empty();
+    const uint32_t linger_us = ix->co_linger_us;
+    if (idle && linger_us == 0) { // nobody to wait for: today's pipeline at once
+        ix->co_running++;
+        ix->co_stats.n_solo += 1;
+        lk.unlock();
+        const int32_t st = search_topk_host(ix, query, 1, k, guard_eps, rows_out, cos_out, n_out);
+        lk.lock();
+        coalesce_retire(ix);
+        return st;
+    }
+    auto g = std::make_shared<CoalesceGroup>();
+    g->key = key;
+    g->cap = std::max<uint32_t>(cap, 1);
+    g->members.push_back(&me);
+    g->sealed = g->cap <= 1;
+    ix->co_pending.push_back(g);
+    const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(linger_us);
+    for (;;) {
+        if (g->go)
+            break;
+        // a free slot: a group opened while the index was busy takes it at once, a lingering one once it is full or
+        // its linger is over
+        const bool ready = !idle || g->sealed || std::chrono::steady_clock::now() >= deadline;
+        if (ix->co_running < kCoalesceInflight && ready) {
+            g->go = true;
+            ix->co_running++;
+            break;
+        }
+        if (idle && !g->sealed && ix->co_running < kCoalesceInflight) {
+            // (the deadline is steady; the wait itself is a system_clock one -- pthread_cond_timedwait, which the thread
+            // sanitizer's runtime intercepts, where a steady_clock wait becomes pthread_cond_clockwait)
+            const auto left = deadline - std::chrono::steady_clock::now();
+            ix->co_cv.wait_until(lk, std::chrono::system_clock::now() +
+                                         std::chrono::duration_cast<std::chrono::system_clock::duration>(left));
+        } else
+            ix->co_cv.wait(lk);
+    }
+    g->sealed = true;
+    ix->co_pending.erase(std::find(ix->co_pending.begin(), ix->co_pending.end(), g));
+    int32_t st;
+    if (g->members.size() == 1) { // nobody joined: today's pipeline
+        ix->co_stats.n_solo += 1;
+        lk.unlock();
+        st = search_topk_host(ix, query, 1, k, guard_eps, rows_out, cos_out, n_out);
+        lk.lock();
+        g->status = st;
+    } else {
+        lk.unlock();
+        coalesce_run(ix, g.get(), guard_eps);
+        lk.lock();
+        st = g->status;
+    }
+    g->done = true;
+    coalesce_retire(ix); // (notifies the members too)
+    return st;
+}
+
+// The fused one-enqueue calls (rlr_search_diverse / rlr_search_hybrid / search_hybrid_begin) cannot share their scan:
+// while coalescing is on and a group of two with this k would qualify, they hand the query back (*fallback = 1) so that
+// the caller's two-call path reaches the coalescer through rlr_search_topk.
+bool coalesce_hands_back(rlr_index *ix, uint32_t k)
+{
+    if (ix->co_max.load(std::memory_order_relaxed) < 2 || !coalesce_eligible(ix, k))
+        return false;
+    std::lock_guard<std::mutex> lk(ix->co_mu);
+    ix->co_stats.n_engine_handbacks += 1;
+    return true;
 }
 
 } // namespace
@@ -2663,30 +2915,9 @@ int32_t rlr_search_topk(rlr_index *ix, const float *queries, uint32_t n_queries,
             n_out[q] = 0;
         return RLR_OK;
     }
-    CtxLease lease(ix);
-    RLR_TRY(ctx_acquire(ix, &lease.c));
-    Ctx *c = lease.c;
-    SearchPlan p;
-    const uint64_t *h = nullptr;
-    RLR_TRY(run_search(ix, c, queries, n_queries, k, guard_eps, nullptr, &p, &h));
-    if (!h)
-        return fail(RLR_E_INTERNAL, "search produced no result buffer");
-    for (uint32_t q = 0; q < n_queries; ++q) {
-        n_out[q] = p.k;
-        // unpack_result, written without branches so that the loop vectorises (a batch of 1024 x 308 results is 315 k of them)
-        const uint64_t *__restrict__ src = h + static_cast<size_t>(q) * p.k;
-        uint64_t *__restrict__ ro = rows_out + static_cast<size_t>(q) * k;
-        uint32_t *__restrict__ co = reinterpret_cast<uint32_t *>(cos_out + static_cast<size_t>(q) * k);
-        for (uint32_t i = 0; i < p.k; ++i) {
-            const uint64_t w = src[i];
-            const uint32_t key = static_cast<uint32_t>(w >> 32);
-            const uint32_t neg = static_cast<uint32_t>(static_cast<int32_t>(key) >> 31);        // all ones: key of a value >= +0
-            const uint32_t bits = key ^ (0xFFFFFFFFu ^ (neg & 0x7FFFFFFFu));                     // key_score(): & 0x7FFFFFFF or ~
-            co[i] = key == 0u ? 0x7FC00000u : bits;
-            ro[i] = 0xFFFFFFFFu - static_cast<uint32_t>(w);
-        }
-    }
-    return RLR_OK;
+    if (n_queries == 1 && ix->co_max.load(std::memory_order_relaxed) >= 2 && coalesce_eligible(ix, k))
+        return coalesced_search(ix, queries, k, guard_eps, rows_out, cos_out, n_out);
+    return search_topk_host(ix, queries, n_queries, k, guard_eps, rows_out, cos_out, n_out);
 }
 
 int32_t rlr_search_topk_device(rlr_index *ix, const float *queries, uint32_t n_queries, uint32_t k, float guard_eps,
@@ -3069,6 +3300,10 @@ int32_t rlr_search_diverse(rlr_index *ix, const float *query, uint32_t pool, uin
         *fallback = 1; // outside what the fused kernels cover: the caller's two-call path handles it
         return RLR_OK;
     }
+    if (coalesce_hands_back(ix, need)) {
+        *fallback = 1; // the two-call path's rlr_search_topk shares a pass with concurrent callers
+        return RLR_OK;
+    }
     RLR_TRY(use_device(ix));
     CtxLease lease(ix);
     RLR_TRY(ctx_acquire(ix, &lease.c));
@@ -3221,6 +3456,10 @@ static int32_t hybrid_begin_impl(rlr_index *ix, const float *query, uint32_t nee
     if (n == 0 || need == 0 || need > kPoolMax || n_lex_bound > kHybridLexMax || fetch_full + n_lex_bound > kHybridSlots ||
         !(w_embedding > 0.0f) || !std::isfinite(w_embedding) || !std::isfinite(w_lexical)) {
         *fallback = 1; // outside what the fused kernels cover: the caller's host path handles it
+        return RLR_OK;
+    }
+    if (coalesce_hands_back(ix, need)) {
+        *fallback = 1; // the host path's rlr_search_topk shares a pass with concurrent callers
         return RLR_OK;
     }
     const uint32_t fetch = static_cast<uint32_t>(fetch64);
@@ -3758,6 +3997,33 @@ int32_t rlr_index_probe_bandwidth(rlr_index *ix, int32_t mode, uint32_t reps, do
     *gbps_out = static_cast<double>(moved) / (best_ms * 1e-3) / 1e9;
     if (ms_out)
         *ms_out = best_ms;
+    return RLR_OK;
+}
+
+int32_t rlr_index_set_coalescing(rlr_index *ix, uint32_t max_group, uint32_t linger_us)
+{
+    RLR_TRY(check_handle(ix));
+    if (max_group > 8)
+        return fail(RLR_E_INVALID, "max_group %u: at most 8 queries share one pass", max_group);
+    if (linger_us > 1000000)
+        return fail(RLR_E_INVALID, "linger_us %u: at most 1 s", linger_us);
+    {
+        std::lock_guard<std::mutex> lk(ix->co_mu);
+        ix->co_linger_us = linger_us;
+    }
+    ix->co_max.store(max_group >= 2 ? max_group : 0, std::memory_order_relaxed);
+    return RLR_OK;
+}
+
+int32_t rlr_index_coalesce_stats(rlr_index *ix, rlr_coalesce_stats *out, int32_t reset)
+{
+    RLR_TRY(check_handle(ix));
+    if (!out)
+        return fail(RLR_E_INVALID, "out is null");
+    std::lock_guard<std::mutex> lk(ix->co_mu);
+    *out = ix->co_stats;
+    if (reset)
+        ix->co_stats = rlr_coalesce_stats{};
     return RLR_OK;
 }
 

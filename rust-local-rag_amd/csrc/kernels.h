@@ -41,6 +41,10 @@ bool launch_scan_takes_host_query(const ScanArgs &a);
 // false when the shape is not served (then nothing was launched)
 bool launch_scan_multi(const ScanArgs &a, uint32_t q_pitch, uint32_t n_queries, size_t score_stride, hipStream_t s,
                        hipError_t *err);
+// the same over binary16 rows of C x 512 B (C = 1..4), f32 arithmetic on the exactly widened elements (coalesced
+// single-query calls only; see run_batched)
+bool launch_scan_multi_f16(const ScanArgs &a, uint32_t q_pitch, uint32_t n_queries, size_t score_stride, hipStream_t s,
+                           hipError_t *err);
 
 // read-only streaming probe over `bytes` of device memory (sink: blocks * 256 floats, blocks <= n_cu * 8); shape 0..2
 hipError_t launch_probe_read(const void *p, size_t bytes, float *sink, int n_cu, int shape, hipStream_t s);

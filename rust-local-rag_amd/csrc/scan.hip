@@ -243,6 +243,99 @@ __global__ __launch_bounds__(256) void scan_multi_kernel(const float4 *__restric
 }
 
 // ---------------------------------------------------------------------------
+// Multi-query kernel over binary16 rows: 2..8 queries share one pass, rows of C x 512 B (256/512/768/1024-d).  A
+// wave reads a row as C loads of 8 B per lane (64 lanes x 8 B = 512 B, coalesced); every row element is widened to f32
+// ONCE (exact) and then feeds all Q queries.  Each query keeps a pair of f32 partial sums per lane (even / odd
+// elements of the lane's slice), so the inner loop is v_pk_fma_f32: at Q = 8 and 1024-d that is ~4 FMA per byte read,
+// more than scalar v_fma_f32 delivers at HBM rate.  The pair is added, then the DPP wave sum; the order differs from
+// the single-query binary16 scan but the band (the summation-order bound over exact f32 products) is the same.
+// Scores go to Q arrays (stride score_stride) exactly like scan_multi_kernel, for the same batched select behind it.
+// ---------------------------------------------------------------------------
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+__device__ inline f32x2 h2f_lo(uint32_t w)
+{
+    return f32x2{h2f(static_cast<uint16_t>(w & 0xFFFF)), h2f(static_cast<uint16_t>(w >> 16))};
+}
+
+template <int C, int Q>
+__global__ __launch_bounds__(256) void scan_multi_h_kernel(const uint2 *__restrict__ rows, const float *__restrict__ queries,
+                                                           uint32_t q_pitch, uint32_t n_queries, float *__restrict__ scores,
+                                                           size_t score_stride, uint32_t n_rows, uint32_t group_rows)
+{
+    constexpr int P8 = C * 64; // 8-byte units per row
+    constexpr int R = 2;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // query q, slice c: the lane's four elements [c * 256 + lane * 4, +4) as two pairs
+    f32x2 qv[Q][C][2];
+#pragma unroll
+    for (int q = 0; q < Q; ++q)
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (static_cast<uint32_t>(q) < n_queries)
+                v = reinterpret_cast<const float4 *>(queries + static_cast<size_t>(q) * q_pitch)[c * 64 + lane];
+            qv[q][c][0] = f32x2{v.x, v.y};
+            qv[q][c][1] = f32x2{v.z, v.w};
+        }
+
+    const uint32_t n_groups = (n_rows + group_rows - 1) / group_rows;
+    const uint32_t n_waves = gridDim.x * 4;
+    for (uint32_t g = blockIdx.x * 4 + wave; g < n_groups; g += n_waves) {
+        const uint32_t row0 = g * group_rows;
+        const uint32_t nr = min(group_rows, n_rows - row0);
+        float mine[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q)
+            mine[q] = 0.0f;
+        for (uint32_t r = 0; r < nr; r += R) {
+            uint2 x[R][C];
+#pragma unroll
+            for (int rr = 0; rr < R; ++rr) {
+                // rows past the group end are clamped to its last row (their lanes are never stored)
+                const uint32_t row = min(row0 + r + rr, row0 + nr - 1);
+                const uint2 *p = rows + static_cast<size_t>(row) * P8 + lane;
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+                    const u32x2 v = __builtin_nontemporal_load(reinterpret_cast<const u32x2 *>(p + c * 64));
+                    x[rr][c] = make_uint2(v.x, v.y);
+                }
+            }
+#pragma unroll
+            for (int rr = 0; rr < R; ++rr) {
+                f32x2 xf[C][2];
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    xf[c][0] = h2f_lo(x[rr][c].x);
+                    xf[c][1] = h2f_lo(x[rr][c].y);
+                }
+#pragma unroll
+                for (int q = 0; q < Q; ++q) {
+                    f32x2 acc = f32x2{0.0f, 0.0f};
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        acc = __builtin_elementwise_fma(xf[c][0], qv[q][c][0], acc);
+                        acc = __builtin_elementwise_fma(xf[c][1], qv[q][c][1], acc);
+                    }
+                    const float tot = wave_sum(acc.x + acc.y);
+                    if (static_cast<uint32_t>(lane) == r + rr)
+                        mine[q] = tot;
+                }
+            }
+        }
+        if (static_cast<uint32_t>(lane) < nr) {
+#pragma unroll
+            for (int q = 0; q < Q; ++q)
+                if (static_cast<uint32_t>(q) < n_queries)
+                    scores[static_cast<size_t>(q) * score_stride + row0 + lane] = mine[q];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Packed kernel: row pitch a multiple of 256 B but not of 1 KiB (384-d f32, 768-d f16, ...).
 // G = 64 / gcd(P16, 64) consecutive rows form a contiguous "pack" of exactly M = G * P16 / 64
 // wave-wide 16-byte loads, so every load instruction is still 64 lanes x 16 B of consecutive
@@ -727,6 +820,41 @@ hipError_t launch_probe_read(const void *p, size_t bytes, float *sink, int n_cu,
     else
         hipLaunchKernelGGL(probe_read_kernel<4>, dim3(n_cu * 8), dim3(256), 0, s, p4, n_kib, sink);
     return hipGetLastError();
+}
+
+// 2..8 queries over binary16 rows whose pitch is a multiple of 512 B (256/512/768/1024-d); false otherwise
+bool launch_scan_multi_f16(const ScanArgs &a, uint32_t q_pitch, uint32_t n_queries, size_t score_stride, hipStream_t s,
+                           hipError_t *err)
+{
+    if (a.dtype != RLR_F16 || n_queries < 2 || n_queries > 8 || a.pitch16 % 32 != 0 || a.pitch16 / 32 < 1 ||
+        a.pitch16 / 32 > 4 || a.pitch16 * 8 != a.dim || q_pitch < a.dim)
+        return false;
+    const uint32_t group = 32;
+    const uint32_t n_groups = (a.n_rows + group - 1) / group;
+    // as many workgroups as stay resident: at Q = 8 over 768 / 1024-d rows the queries take ~170 / ~230 VGPRs (two
+    // waves per SIMD), below that four workgroups per CU fit
+    const uint32_t wgs = n_queries > 4 && a.pitch16 / 32 >= 3 ? 2u : 4u;
+    const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((n_groups + 3) / 4, static_cast<uint32_t>(a.n_cu) * wgs));
+    const uint2 *rows = static_cast<const uint2 *>(a.rows);
+#define RLR_MULTI_H(CV, QV)                                                                                      \
+    hipLaunchKernelGGL((scan_multi_h_kernel<CV, QV>), dim3(blocks), dim3(256), 0, s, rows, a.query, q_pitch,     \
+                       n_queries, a.scores, score_stride, a.n_rows, group)
+#define RLR_MULTI_H_Q(CV)                                 \
+    do {                                                  \
+        if (n_queries <= 2) RLR_MULTI_H(CV, 2);           \
+        else if (n_queries <= 4) RLR_MULTI_H(CV, 4);      \
+        else RLR_MULTI_H(CV, 8);                          \
+    } while (0)
+    switch (a.pitch16 / 32) {
+    case 1: RLR_MULTI_H_Q(1); break;
+    case 2: RLR_MULTI_H_Q(2); break;
+    case 3: RLR_MULTI_H_Q(3); break;
+    default: RLR_MULTI_H_Q(4); break;
+    }
+#undef RLR_MULTI_H_Q
+#undef RLR_MULTI_H
+    *err = hipGetLastError();
+    return true;
 }
 
 // 2..8 queries over f32 rows whose pitch is a multiple of 1 KiB (256/512/768/1024-d); false otherwise

@@ -211,6 +211,21 @@ class GpuIndex:
                                               order.ctypes.data_as(N.u32p), _fp(mmr), n.ctypes.data_as(N.u32p)))
         return order, mmr, n[:nq]
 
+    # -- coalescing of concurrent single-query searches -----------------------
+    def set_coalescing(self, max_group: int, linger_us: int = 0) -> None:
+        """concurrent single-query searches share one pass over the rows, up to max_group (2..8) at a time; 0 or 1:
+        off (the default).  linger_us: how long a caller that finds the index idle waits for others.  A mutator: no
+        search may run on the index meanwhile."""
+        N.check(self._L.rlr_index_set_coalescing(self._h, max_group, linger_us))
+
+    def coalesce_stats(self, reset: bool = False) -> dict:
+        """the coalescer's counters (rlr_coalesce_stats) as a dict; group_size is a list indexed by group size"""
+        st = N.CoalesceStatsC()
+        N.check(self._L.rlr_index_coalesce_stats(self._h, C.byref(st), int(reset)))
+        out = {f: getattr(st, f) for f, _ in N.CoalesceStatsC._fields_}
+        out["group_size"] = list(st.group_size)
+        return out
+
     # -- measurement ---------------------------------------------------------
     def profile_enable(self, on: bool = True) -> None:
         N.check(self._L.rlr_profile_enable(self._h, int(on)))
