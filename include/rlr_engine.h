@@ -99,6 +99,32 @@ int32_t rlr_engine_search_text(rlr_index *idx, rlr_lexical *lex, const float *qu
                                int32_t stage, const rlr_query_weights *weights, rlr_search_hit *out, uint32_t cap,
                                uint32_t *n_out);
 
+/* rlr_engine_search_text for many queries at once: what a host with a batch of query texts at hand (an eval run, a
+ * request queue) would otherwise get from n_queries single calls, bit for bit -- same rows, order and score bits per query,
+ * whichever path a query takes inside.  Query q: raw embedding queries_raw + q * dq, tokens
+ * tokens[token_offsets[q] .. token_offsets[q + 1]) (space separated, as for rlr_lexical_score); hits at out[q * cap],
+ * n_out[q] of them.  top_k, diversity_factor, stage and weights apply to the whole batch with the meaning they have in
+ * rlr_engine_search_text.  The BM25 of every query runs in one chain on the lexical index' stream (LDS accumulators per
+ * (query, row slice), term-order sums, no dense per-query accumulator), beside one batched top-k of the cosine side;
+ * exact cosines of the lexical rows, blend, order and cut follow for every query at once, then one batched MMR: two host
+ * synchronisations per sub-batch of up to 256 queries.  Queries the fused kernels cannot decide are re-run alone through
+ * rlr_engine_search_text (`info`, may be NULL, says how many and why).  Holds the lexical readers' lock per sub-batch;
+ * other searches may run concurrently; never joins a coalesced group.  RLR_E_INVALID: a null index, lexical index or
+ * output, decreasing token_offsets, or cap below the result count of a query (min(top_k, N) or initial_k). */
+typedef struct rlr_text_batch_info {
+    uint32_t n_batched;        /* queries served end to end by the batched kernels */
+    uint32_t n_single;         /* queries re-run alone through rlr_engine_search_text; the three below sum to it */
+    uint32_t n_single_lexical; /* ... because their BM25 selection handed back (the batched selection is exact: 0 today) */
+    uint32_t n_single_blend;   /* ... because a rounding tie reached the cosine fetch boundary / pool undecidable */
+    uint32_t n_single_shape;   /* ... because the request is outside the fused kernels (w_embedding == 0, pool > 1024,
+                                *     > 2048 lexical pairs, > 128 unique known terms in the query, a batch of one) */
+} rlr_text_batch_info;
+int32_t rlr_engine_search_text_batch(rlr_index *idx, rlr_lexical *lex, const float *queries_raw, uint32_t dq,
+                                     uint32_t n_queries, const char *tokens, const uint64_t *token_offsets,
+                                     uint32_t top_k, float diversity_factor, int32_t stage,
+                                     const rlr_query_weights *weights, rlr_search_hit *out, uint32_t cap,
+                                     uint32_t *n_out, rlr_text_batch_info *info);
+
 /* Additive batched entry point (the reference has no batched API; its oracle is "loop
  * search_with_diversity over the batch"): n_queries raw query embeddings,
  * no lexical candidates.  Hits of query q start at out[q * cap]; n_out[q] = their count.

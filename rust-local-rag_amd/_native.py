@@ -48,6 +48,11 @@ class SearchHitC(C.Structure):
                 ("lexical_score", C.c_float), ("initial_score", C.c_float)]
 
 
+class TextBatchInfoC(C.Structure):
+    _fields_ = [("n_batched", C.c_uint32), ("n_single", C.c_uint32), ("n_single_lexical", C.c_uint32),
+                ("n_single_blend", C.c_uint32), ("n_single_shape", C.c_uint32)]
+
+
 class JsonCorpusC(C.Structure):
     _fields_ = [("rows", C.POINTER(C.c_float)), ("n_rows", C.c_uint64), ("dim", C.c_uint32),
                 ("meta_json", C.c_void_p), ("meta_len", C.c_uint64)]
@@ -153,6 +158,9 @@ PROTOTYPES = [
                                                      C.POINTER(SearchHitC), C.c_uint32, u32p]),
     ("rlr_engine_search_text", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_char_p, C.c_size_t, C.c_uint32, C.c_float, C.c_int32,
                                            C.POINTER(QueryWeightsC), C.POINTER(SearchHitC), C.c_uint32, u32p]),
+    ("rlr_engine_search_text_batch", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, C.c_char_p, u64p, C.c_uint32,
+                                                 C.c_float, C.c_int32, C.POINTER(QueryWeightsC), C.POINTER(SearchHitC),
+                                                 C.c_uint32, u32p, C.POINTER(TextBatchInfoC)]),
     ("rlr_engine_search_with_diversity_batch", C.c_int32, [_H, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
                                                            C.POINTER(QueryWeightsC), C.POINTER(SearchHitC), C.c_uint32,
                                                            u32p]),

@@ -138,6 +138,29 @@ __global__ __launch_bounds__(64) void score_rows_kernel(const float4 *__restrict
     out[i] = dot_ref_row<F16>(rows + static_cast<size_t>(r) * pitch16, s_q, dim);
 }
 
+// score_rows_kernel for many queries at once: grid row q scores query q (queries + q * q_pitch) against its own list
+// (list + q * stride, length min(stride, n_dev[q * n_dev_stride])) into out + q * stride
+template <bool F16>
+__global__ __launch_bounds__(64) void score_rows_batch_kernel(const float4 *__restrict__ rows, uint32_t pitch16, uint32_t dim,
+                                                              const float *__restrict__ queries, uint32_t q_pitch,
+                                                              const uint32_t *__restrict__ list, uint32_t stride,
+                                                              float *__restrict__ out, const uint32_t *__restrict__ n_dev,
+                                                              uint32_t n_dev_stride, uint32_t n_rows_clamp)
+{
+    const uint32_t q = blockIdx.y;
+    const uint32_t n = min(stride, n_dev[static_cast<size_t>(q) * n_dev_stride]);
+    if (blockIdx.x * 64 >= n)
+        return; // (uniform)
+    extern __shared__ __attribute__((aligned(16))) float s_q[];
+    stage_query(s_q, queries + static_cast<size_t>(q) * q_pitch, dim);
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n)
+        return;
+    const size_t at = static_cast<size_t>(q) * stride + i;
+    const uint32_t r = list[at] < n_rows_clamp ? list[at] : 0u;
+    out[at] = dot_ref_row<F16>(rows + static_cast<size_t>(r) * pitch16, s_q, dim);
+}
+
 // The same scores with the rows staged through LDS (coalesced loads, products in parallel, then one reference-order
 // chain per row): 8 rows per workgroup instead of 64 sequential lanes in one wave -- 1500 lexical rows of a hybrid
 // search spread over 188 workgroups instead of 24 (24.5 -> 7.9 us at 768-d).
@@ -1170,6 +1193,24 @@ hipError_t launch_score_rows(const void *rows, uint32_t pitch16, uint32_t dim, i
     else
         hipLaunchKernelGGL(score_rows_kernel<false>, dim3(blocks), dim3(64), lds, s, r4, pitch16, dim, query, list, n,
                            cos_out, n_dev, n_rows_clamp);
+    return hipGetLastError();
+}
+
+hipError_t launch_score_rows_batch(const void *rows, uint32_t pitch16, uint32_t dim, int dtype, const float *queries,
+                                   uint32_t q_pitch, uint32_t n_queries, const uint32_t *list, uint32_t stride, float *cos_out,
+                                   const uint32_t *n_dev, uint32_t n_dev_stride, uint32_t n_rows_clamp, hipStream_t s)
+{
+    if (stride == 0 || n_queries == 0)
+        return hipSuccess;
+    const float4 *r4 = static_cast<const float4 *>(rows);
+    const dim3 grid((stride + 63) / 64, n_queries);
+    const size_t lds = static_cast<size_t>(dim) * sizeof(float);
+    if (dtype == RLR_F16)
+        hipLaunchKernelGGL(score_rows_batch_kernel<true>, grid, dim3(64), lds, s, r4, pitch16, dim, queries, q_pitch, list, stride,
+                           cos_out, n_dev, n_dev_stride, n_rows_clamp);
+    else
+        hipLaunchKernelGGL(score_rows_batch_kernel<false>, grid, dim3(64), lds, s, r4, pitch16, dim, queries, q_pitch, list, stride,
+                           cos_out, n_dev, n_dev_stride, n_rows_clamp);
     return hipGetLastError();
 }
 

@@ -1425,9 +1425,9 @@ struct HybridLexHeader {
 // A scoring call's result (pack_result(score, row) keys, in any order) -> rows, scores, header.  Rows outside the index
 // (a lexical index that ran ahead of the embedding matrix) keep their place but are marked: they still count for
 // max_lexical, as in the reference, and never become candidates.  One workgroup (<= kHybridLexMax pairs).
-__global__ __launch_bounds__(1024) void lex_unpack_kernel(const uint64_t *__restrict__ packed, const uint32_t *__restrict__ count,
-                                                          uint32_t limit, uint32_t n_rows, uint32_t *__restrict__ lrow,
-                                                          float *__restrict__ lscore, HybridLexHeader *__restrict__ hdr)
+__device__ inline void lex_unpack_body(const uint64_t *__restrict__ packed, const uint32_t *__restrict__ count, uint32_t limit,
+                                       uint32_t n_rows, uint32_t *__restrict__ lrow, float *__restrict__ lscore,
+                                       HybridLexHeader *__restrict__ hdr)
 {
     __shared__ uint32_t s_max;
     if (threadIdx.x == 0)
@@ -1457,6 +1457,26 @@ __global__ __launch_bounds__(1024) void lex_unpack_kernel(const uint64_t *__rest
         const float m = s_max ? fmaxf(0.0f, key_score(s_max)) : 0.0f; // NaN scores (key 0) are ignored like f32::max does
         hdr->max_lex = m >= 1.1920929e-07f ? m : 1.1920929e-07f;
     }
+}
+
+__global__ __launch_bounds__(1024) void lex_unpack_kernel(const uint64_t *__restrict__ packed, const uint32_t *__restrict__ count,
+                                                          uint32_t limit, uint32_t n_rows, uint32_t *__restrict__ lrow,
+                                                          float *__restrict__ lscore, HybridLexHeader *__restrict__ hdr)
+{
+    lex_unpack_body(packed, count, limit, n_rows, lrow, lscore, hdr);
+}
+
+// one query per workgroup (rlr_engine_search_text_batch): query q's keys at packed + q * sel_stride, its count at
+// count + q * count_stride, its pairs at lrow / lscore + q * bound
+__global__ __launch_bounds__(1024) void lex_unpack_batch_kernel(const uint64_t *__restrict__ packed, uint32_t sel_stride,
+                                                                const uint32_t *__restrict__ count, uint32_t count_stride,
+                                                                uint32_t limit, uint32_t n_rows, uint32_t bound,
+                                                                uint32_t *__restrict__ lrow, float *__restrict__ lscore,
+                                                                HybridLexHeader *__restrict__ hdr)
+{
+    const uint32_t q = blockIdx.x;
+    lex_unpack_body(packed + static_cast<size_t>(q) * sel_stride, count + static_cast<size_t>(q) * count_stride, limit, n_rows,
+                    lrow + static_cast<size_t>(q) * bound, lscore + static_cast<size_t>(q) * bound, hdr + q);
 }
 
 // [row u32 | cos f32 | combined f32 | lexical f32] x k_cap, then n, status, checksum, done (the layout the greedy kernel's
@@ -1492,17 +1512,14 @@ __device__ inline void hybrid_emit_body(const uint32_t *list, const float *comb,
     }
 }
 
-__global__ __launch_bounds__(1024) void hybrid_pool_kernel(const uint64_t *__restrict__ packed, uint32_t fetch, uint32_t need,
-                                                           uint32_t n_rows, float w_e, float w_l,
-                                                           const uint32_t *__restrict__ lrow, const float *__restrict__ lscore,
-                                                           const float *__restrict__ lcos,
-                                                           const HybridLexHeader *__restrict__ hdr,
-                                                           float *__restrict__ cand, // 3 x kHybridSlots: combined | cos | lex
-                                                           uint32_t *__restrict__ list, float *__restrict__ comb,
-                                                           float *__restrict__ cosv, float *__restrict__ lexv,
-                                                           uint32_t *__restrict__ info,
-                                                           uint32_t k_cap, uint32_t *__restrict__ h_out) // h_out != null: a search
-                                                           // without diversification -- the pool IS the result, emitted here
+__device__ inline void hybrid_pool_body(const uint64_t *__restrict__ packed, uint32_t fetch, uint32_t need, uint32_t n_rows,
+                                        float w_e, float w_l, const uint32_t *__restrict__ lrow, const float *__restrict__ lscore,
+                                        const float *__restrict__ lcos, const HybridLexHeader *__restrict__ hdr,
+                                        float *__restrict__ cand, // 3 x kHybridSlots: combined | cos | lex
+                                        uint32_t *__restrict__ list, float *__restrict__ comb, float *__restrict__ cosv,
+                                        float *__restrict__ lexv, uint32_t *__restrict__ info, uint32_t k_cap,
+                                        uint32_t *__restrict__ h_out) // h_out != null: a search without diversification --
+                                                                      // the pool IS the result, emitted here
 {
     __shared__ uint64_t s_key[kHybridSlots];   // slot -> (ordered combined score, ~row); 0 = empty
     __shared__ uint64_t s_sel[kHybridSelMax];  // the keys that can be among the first `need`
@@ -1669,6 +1686,41 @@ __global__ __launch_bounds__(1024) void hybrid_pool_kernel(const uint64_t *__res
         const uint32_t status = s_pick[0];
         hybrid_emit_body(list, comb, cosv, lexv, status ? 0u : min(n_pool, k_cap), status, k_cap, h_out);
     }
+}
+
+__global__ __launch_bounds__(1024) void hybrid_pool_kernel(const uint64_t *__restrict__ packed, uint32_t fetch, uint32_t need,
+                                                           uint32_t n_rows, float w_e, float w_l,
+                                                           const uint32_t *__restrict__ lrow, const float *__restrict__ lscore,
+                                                           const float *__restrict__ lcos,
+                                                           const HybridLexHeader *__restrict__ hdr,
+                                                           float *__restrict__ cand, uint32_t *__restrict__ list,
+                                                           float *__restrict__ comb, float *__restrict__ cosv,
+                                                           float *__restrict__ lexv, uint32_t *__restrict__ info,
+                                                           uint32_t k_cap, uint32_t *__restrict__ h_out)
+{
+    hybrid_pool_body(packed, fetch, need, n_rows, w_e, w_l, lrow, lscore, lcos, hdr, cand, list, comb, cosv, lexv, info, k_cap,
+                     h_out);
+}
+
+// hybrid_pool_kernel for many queries (rlr_engine_search_text_batch), one workgroup each: query q's fetched keys at
+// packed + q * fetch, pairs at + q * bound, header q, pool at + q * need; info[2q .. 2q + 1] = (pool size, status), and
+// sizes[q] = the pool size again (the stride-1 array the batched greedy kernel reads)
+__global__ __launch_bounds__(1024) void hybrid_pool_batch_kernel(const uint64_t *__restrict__ packed, uint32_t fetch, uint32_t need,
+                                                                 uint32_t n_rows, float w_e, float w_l, uint32_t bound,
+                                                                 const uint32_t *__restrict__ lrow, const float *__restrict__ lscore,
+                                                                 const float *__restrict__ lcos,
+                                                                 const HybridLexHeader *__restrict__ hdr, float *__restrict__ cand,
+                                                                 uint32_t *__restrict__ list, float *__restrict__ comb,
+                                                                 float *__restrict__ cosv, float *__restrict__ lexv,
+                                                                 uint32_t *__restrict__ info, uint32_t *__restrict__ sizes)
+{
+    const uint32_t q = blockIdx.x;
+    const size_t lo = static_cast<size_t>(q) * bound, po = static_cast<size_t>(q) * need;
+    hybrid_pool_body(packed + static_cast<size_t>(q) * fetch, fetch, need, n_rows, w_e, w_l, lrow + lo, lscore + lo, lcos + lo,
+                     hdr + q, cand + static_cast<size_t>(q) * 3 * kHybridSlots, list + po, comb + po, cosv + po, lexv + po,
+                     info + 2 * q, 0u, nullptr);
+    if (threadIdx.x == 0) // (thread 0 wrote info itself)
+        sizes[q] = info[2 * q];
 }
 
 // the first info[0] candidates in their sorted order (no diversification) -> pinned host memory: hybrid_emit_body, below
@@ -3701,6 +3753,142 @@ void search_hybrid_abort(HybridTicket *ticket)
         return;
     (void)hipStreamSynchronize(ticket->lease.c->stream);
     delete ticket;
+}
+
+void launch_lex_unpack_batch(const uint64_t *d_sel, uint32_t sel_stride, const uint32_t *d_count, uint32_t count_stride,
+                             uint32_t nq, uint32_t limit, const LexBatchSink &sink, void *stream)
+{
+    hipLaunchKernelGGL(lex_unpack_batch_kernel, dim3(nq), dim3(1024), 0, static_cast<hipStream_t>(stream), d_sel, sel_stride,
+                       d_count, count_stride, limit, sink.n_index_rows, sink.bound, sink.d_rows, sink.d_scores,
+                       static_cast<HybridLexHeader *>(sink.d_headers));
+}
+
+int32_t search_hybrid_batch(rlr_index *ix, const float *queries, uint32_t nq, uint32_t need_in, uint32_t k, float lambda,
+                            int32_t diversify, float w_embedding, float w_lexical, uint32_t n_lex_bound,
+                            int32_t (*lex_launch)(void *, const LexBatchSink *, void **ready), void *lex_arg, uint64_t *rows_out,
+                            float *cos_out, float *score_out, float *lex_out, uint32_t *n_out, uint32_t *status)
+{
+    RLR_TRY(check_handle(ix));
+    const uint32_t n = static_cast<uint32_t>(ix->n_rows);
+    const uint32_t need = std::min<uint32_t>(n, need_in);
+    if (nq == 0 || n == 0 || need == 0 || need > kPoolMax || n_lex_bound == 0 || n_lex_bound > kHybridLexMax || !lex_launch ||
+        !queries || !rows_out || !cos_out || !score_out || !lex_out || !n_out || !status || !(w_embedding > 0.0f) ||
+        !std::isfinite(w_embedding) || !std::isfinite(w_lexical))
+        return fail(RLR_E_INVALID, "batched hybrid search: arguments outside the fused kernels");
+    const uint32_t fetch = static_cast<uint32_t>(std::min<uint64_t>(n, static_cast<uint64_t>(need) + kHybridFetchMargin));
+    if (fetch + n_lex_bound > kHybridSlots)
+        return fail(RLR_E_INVALID, "batched hybrid search: %u fetched + %u lexical rows exceed the blend's slots", fetch, n_lex_bound);
+    RLR_TRY(use_device(ix));
+    CtxLease lease(ix);
+    RLR_TRY(ctx_acquire(ix, &lease.c));
+    Ctx *c = lease.c;
+    hipStream_t s = c->stream;
+    const uint32_t P = need, B = n_lex_bound, qp = ix->q_pitch;
+    const uint32_t k_cap = diversify ? std::max<uint32_t>(std::min<uint32_t>(std::max<uint32_t>(k, 1u), P), 1u) : P;
+    // workspace (4-byte words): fetched keys nq x fetch (u64) | queries nq x q_pitch | lexical rows, scores, cosines nq x B
+    // each | headers nq x 2 | blend candidates nq x 3 x kHybridSlots | results: list, combined, cos, lex, order, mmr nq x P
+    // each, n_sel nq, sizes nq, info 2 nq | gram nq x P x P (diversify)
+    const uint64_t Q = nq;
+    const uint64_t o_q = 2 * Q * fetch, o_lrow = o_q + Q * qp, o_lsc = o_lrow + Q * B, o_lcos = o_lsc + Q * B;
+    const uint64_t o_hdr = o_lcos + Q * B, o_cand = o_hdr + 2 * Q, o_res = o_cand + Q * 3 * kHybridSlots;
+    const uint64_t res_words = 6 * Q * P + 4 * Q, o_gram = o_res + res_words;
+    const uint64_t words = o_gram + (diversify ? Q * P * P : 0);
+    RLR_TRY(grow(&c->d_pool, &c->pool_cap, words));
+    float *w = c->d_pool;
+    uint64_t *d_packed = reinterpret_cast<uint64_t *>(w);
+    float *d_q = w + o_q;
+    uint32_t *d_lrow = reinterpret_cast<uint32_t *>(w + o_lrow);
+    float *d_lscore = w + o_lsc, *d_lcos = w + o_lcos;
+    HybridLexHeader *d_hdr = reinterpret_cast<HybridLexHeader *>(w + o_hdr);
+    float *d_cand = w + o_cand;
+    uint32_t *d_list = reinterpret_cast<uint32_t *>(w + o_res);
+    float *d_comb = w + o_res + Q * P, *d_cos = w + o_res + 2 * Q * P, *d_lexv = w + o_res + 3 * Q * P;
+    uint32_t *d_order = reinterpret_cast<uint32_t *>(w + o_res + 4 * Q * P);
+    float *d_mmr = w + o_res + 5 * Q * P;
+    uint32_t *d_nsel = reinterpret_cast<uint32_t *>(w + o_res + 6 * Q * P);
+    uint32_t *d_sizes = d_nsel + Q, *d_info = d_nsel + 2 * Q;
+    float *d_gram = w + o_gram;
+    // whatever goes wrong from here on: the BM25 chain (another stream, writing into this workspace) and this stream must
+    // be drained before the context goes back
+    struct Drain {
+        hipStream_t s;
+        hipEvent_t lex_ready = nullptr;
+        bool armed = true;
+        ~Drain()
+        {
+            if (lex_ready)
+                (void)hipEventSynchronize(lex_ready);
+            if (armed)
+                (void)hipStreamSynchronize(s);
+        }
+    } drain{s};
+    // 1. the BM25 chain on the lexical index' stream, into this workspace
+    LexBatchSink sink;
+    sink.d_rows = d_lrow;
+    sink.d_scores = d_lscore;
+    sink.d_headers = d_hdr;
+    sink.bound = B;
+    sink.n_index_rows = n;
+    void *ready = nullptr;
+    RLR_TRY(lex_launch(lex_arg, &sink, &ready));
+    drain.lex_ready = static_cast<hipEvent_t>(ready);
+    // 2. beside it: the fetch of every query, the batched top-k (GEMM / shared scan / per-query pipeline as the planner picks);
+    //    its overflow handling needs the host, hence the first synchronisation
+    SearchPlan p;
+    const uint64_t *h = nullptr;
+    RLR_TRY(run_search(ix, c, queries, nq, fetch, -1.0f, nullptr, &p, &h));
+    if (!h || p.k != fetch)
+        return fail(RLR_E_INTERNAL, "batched hybrid search: the cosine batch produced no result");
+    // (the fetch goes through the host on purpose: run_search's single-query pipelines -- the planner's choice for batches
+    // too small for a shared pass -- write their results straight into pinned host memory, not into c->d_out, so the host
+    // copy is the one place every path leaves them; Q x fetch x 8 bytes each way)
+    std::vector<uint64_t> fetched(h, h + Q * fetch); // (the pinned buffer is re-laid out below)
+    const size_t b_packed = Q * fetch * 8, b_q = Q * qp * 4, b_res = res_words * 4;
+    RLR_TRY(pin_reserve(c, b_packed + b_q + b_res + 64));
+    char *hp = static_cast<char *>(c->h_pin);
+    std::memcpy(hp, fetched.data(), b_packed);
+    float *h_q = reinterpret_cast<float *>(hp + b_packed);
+    std::memset(h_q, 0, b_q);
+    for (uint32_t q = 0; q < nq; ++q)
+        std::memcpy(h_q + static_cast<size_t>(q) * qp, queries + static_cast<size_t>(q) * ix->dim, ix->dim * sizeof(float));
+    RLR_HIP(hipMemcpyAsync(d_packed, hp, b_packed, hipMemcpyHostToDevice, s));
+    RLR_HIP(hipMemcpyAsync(d_q, h_q, b_q, hipMemcpyHostToDevice, s));
+    // 3. join the BM25 chain; exact cosines of the lexical rows, blend, order, cut -- one workgroup per query
+    RLR_HIP(hipStreamWaitEvent(s, static_cast<hipEvent_t>(ready), 0));
+    RLR_HIP(launch_score_rows_batch(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, d_q, qp, nq, d_lrow, B, d_lcos,
+                                    reinterpret_cast<const uint32_t *>(d_hdr), 2, n, s));
+    hipLaunchKernelGGL(hybrid_pool_batch_kernel, dim3(nq), dim3(1024), 0, s, d_packed, fetch, P, n, w_embedding, w_lexical, B,
+                       d_lrow, d_lscore, d_lcos, d_hdr, d_cand, d_list, d_comb, d_cos, d_lexv, d_info, d_sizes);
+    RLR_HIP(hipGetLastError());
+    // 4. MMR over every pool at once
+    if (diversify) {
+        RLR_HIP(launch_gram_rows(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, d_list, P, d_gram, nq, s));
+        RLR_HIP(launch_mmr_greedy(d_gram, d_comb, P, k, lambda, d_order, d_mmr, d_nsel, d_sizes, nq, s));
+    }
+    uint32_t *h_res = reinterpret_cast<uint32_t *>(hp + b_packed + b_q);
+    RLR_HIP(hipMemcpyAsync(h_res, d_list, b_res, hipMemcpyDeviceToHost, s));
+    RLR_HIP(hipStreamSynchronize(s));
+    drain.armed = false;
+    const uint32_t *h_list = h_res, *h_order = h_res + 4 * Q * P, *h_nsel = h_res + 6 * Q * P, *h_info = h_nsel + 2 * Q;
+    const float *h_comb = reinterpret_cast<const float *>(h_res + Q * P), *h_cos = reinterpret_cast<const float *>(h_res + 2 * Q * P);
+    const float *h_lex = reinterpret_cast<const float *>(h_res + 3 * Q * P);
+    for (uint32_t q = 0; q < nq; ++q) {
+        status[q] = h_info[2 * q + 1];
+        n_out[q] = 0;
+        if (status[q])
+            continue;
+        const size_t base = static_cast<size_t>(q) * P, ob = static_cast<size_t>(q) * k_cap;
+        const uint32_t cnt = std::min<uint32_t>(diversify ? h_nsel[q] : h_info[2 * q], k_cap);
+        for (uint32_t i = 0; i < cnt; ++i) {
+            const size_t o = base + (diversify ? h_order[base + i] : i);
+            rows_out[ob + i] = h_list[o];
+            cos_out[ob + i] = h_cos[o];
+            score_out[ob + i] = h_comb[o];
+            lex_out[ob + i] = h_lex[o];
+        }
+        n_out[q] = cnt;
+    }
+    return RLR_OK;
 }
 
 } // namespace rlr

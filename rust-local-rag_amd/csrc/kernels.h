@@ -174,6 +174,11 @@ bool launch_rescore_staged(const void *rows, uint32_t pitch16, uint32_t dim, int
 hipError_t launch_score_rows(const void *rows, uint32_t pitch16, uint32_t dim, int dtype, const float *query,
                              const uint32_t *list, uint32_t n, float *cos_out, hipStream_t s,
                              const uint32_t *n_dev = nullptr, uint32_t n_rows_clamp = 0xFFFFFFFFu);
+// the same for n_queries queries at once: query q (queries + q * q_pitch) against list + q * stride, length
+// min(stride, n_dev[q * n_dev_stride]), into cos_out + q * stride
+hipError_t launch_score_rows_batch(const void *rows, uint32_t pitch16, uint32_t dim, int dtype, const float *queries,
+                                   uint32_t q_pitch, uint32_t n_queries, const uint32_t *list, uint32_t stride, float *cos_out,
+                                   const uint32_t *n_dev, uint32_t n_dev_stride, uint32_t n_rows_clamp, hipStream_t s);
 // Reference normalize() of n rows of f32 staging data (in place), then store as dtype.
 hipError_t launch_normalize_store(float *staging, uint32_t n, uint32_t dim, int do_normalize,
                                   void *rows_out, uint32_t pitch16, int dtype, float *norm_tmp,

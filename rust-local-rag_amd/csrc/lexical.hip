@@ -34,6 +34,7 @@
 #include <atomic>
 #include <cmath>
 #include <condition_variable>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -491,9 +492,8 @@ __device__ inline void lex_derive_state(const LexControl *ctl, uint32_t limit, i
 // PACK (pass 0 only): the keys do not exist yet -- build them from the accumulators on the way (this used to be a
 // launch of its own in front of the eight passes).
 template <bool PACK>
-__global__ __launch_bounds__(256) void lex_select_pass_kernel(uint64_t *__restrict__ keys, LexControl *__restrict__ ctl,
-                                                              uint32_t limit, int pass, const float *__restrict__ scores,
-                                                              const uint32_t *__restrict__ touched)
+__device__ inline void lex_select_pass_body(uint64_t *__restrict__ keys, LexControl *__restrict__ ctl, uint32_t limit, int pass,
+                                            const float *__restrict__ scores, const uint32_t *__restrict__ touched)
 {
     __shared__ uint32_t s_h[256];
     uint64_t prefix;
@@ -526,8 +526,17 @@ __global__ __launch_bounds__(256) void lex_select_pass_kernel(uint64_t *__restri
         atomicAdd(&ctl->hist[pass][threadIdx.x], c);
 }
 
-__global__ __launch_bounds__(256) void lex_collect_kernel(const uint64_t *__restrict__ keys, LexControl *__restrict__ ctl,
-                                                          uint32_t limit, uint64_t *__restrict__ sel)
+template <bool PACK>
+__global__ __launch_bounds__(256) void lex_select_pass_kernel(uint64_t *__restrict__ keys, LexControl *__restrict__ ctl,
+                                                              uint32_t limit, int pass, const float *__restrict__ scores,
+                                                              const uint32_t *__restrict__ touched)
+{
+    lex_select_pass_body<PACK>(keys, ctl, limit, pass, scores, touched);
+}
+
+// sel_cap: slots of sel (the exact count is min(limit, n_touched): keys are unique)
+__device__ inline void lex_collect_body(const uint64_t *__restrict__ keys, LexControl *__restrict__ ctl, uint32_t limit,
+                                        uint64_t *__restrict__ sel, uint32_t sel_cap)
 {
     uint64_t kth;
     uint32_t k_rem;
@@ -539,9 +548,15 @@ __global__ __launch_bounds__(256) void lex_collect_kernel(const uint64_t *__rest
         const uint64_t key = i < n ? keys[i] : 0ull;
         const bool take = i < n && key >= kth;
         const uint32_t slot = wave_append_slot(take, &ctl->n_sel);
-        if (take && slot < kMaxLimit)
+        if (take && slot < sel_cap)
             sel[slot] = key;
     }
+}
+
+__global__ __launch_bounds__(256) void lex_collect_kernel(const uint64_t *__restrict__ keys, LexControl *__restrict__ ctl,
+                                                          uint32_t limit, uint64_t *__restrict__ sel)
+{
+    lex_collect_body(keys, ctl, limit, sel, kMaxLimit);
 }
 
 // ---- sampled selection: 3 launches instead of 8 radix passes + collect ------------------------------------------
@@ -791,6 +806,176 @@ __global__ __launch_bounds__(256) void csr_scatter_kernel(const uint32_t *__rest
     }
 }
 
+// ---- batched BM25 (rlr_engine_search_text_batch) ---------------------------------------------------------------------
+// Many queries' LexicalIndex::score in one chain, without a dense accumulator per query: workgroup (slice, q) owns rows
+// [slice * kLdsRows, ...) of query q, finds its share of each of q's posting lists (both segments) by the estimated-window
+// search of bm25_terms_lds_kernel, and
+// adds the postings in query-term order into LDS accumulators -- the f32 sum order of bm25_terms_lds_kernel.  The rows whose
+// sum became positive go out as pack_result(score, row) keys into q's region of one key buffer (sized by the host from the
+// df counts: at most one key per row that has a posting).  A slice with no postings of q exits after the searches.
+constexpr uint32_t kBatchTermsMax = 128; // unique known terms per query (more: the query takes the single path)
+
+struct BatchTerm {
+    uint64_t off_m, off_d;
+    uint32_t cnt_m, cnt_d;
+    float idf;
+    uint32_t pad;
+};
+struct BatchQuery {
+    uint32_t t0, nt;  // its terms: [t0, t0 + nt) of the term table, in query-term order
+    uint64_t key_off; // its region of the key buffer
+};
+
+__global__ __launch_bounds__(256) void bm25_batch_kernel(const BatchQuery *__restrict__ bq, const BatchTerm *__restrict__ bt,
+                                                         const uint32_t *__restrict__ post_row, const uint32_t *__restrict__ post_tf,
+                                                         const uint32_t *__restrict__ dpost_row, const uint32_t *__restrict__ dpost_tf,
+                                                         const uint32_t *__restrict__ doc_len, uint32_t n_rows, float avg,
+                                                         uint64_t *__restrict__ keys, LexControl *__restrict__ ctls)
+{
+    __shared__ uint32_t s_range[kBatchTermsMax][4]; // [term][main lo, main hi, appended lo, appended hi]
+    __shared__ float s_sc[kLdsRows], s_dl[kLdsRows], s_nk[kLdsRows];
+    __shared__ uint8_t s_fl[kLdsRows];
+    __shared__ uint32_t s_cnt, s_base;
+    const uint32_t tid = threadIdx.x;
+    const BatchQuery Q = bq[blockIdx.y];
+    const uint32_t r0 = blockIdx.x * kLdsRows;
+    if (Q.nt == 0 || r0 >= n_rows)
+        return;
+    const uint32_t r1 = min(r0 + kLdsRows, n_rows), nr = r1 - r0;
+    const BatchTerm *terms = bt + Q.t0;
+    // the slice's share of every posting list, one search per wave at a time (uniform per wave): the estimated-window search
+    // of bm25_terms_lds_kernel -- one coalesced window of kSearchWin entries around cnt * key / n_rows decides it as a rule,
+    // the 64-ary wave search takes the side the window points to otherwise
+    const uint32_t lane = tid & 63, wave = tid >> 6;
+    for (uint32_t id = wave; id < Q.nt * 4; id += 4) {
+        const uint32_t t = id >> 2, which = id & 3;
+        const bool delta = which >= 2;
+        const uint32_t cnt = delta ? terms[t].cnt_d : terms[t].cnt_m;
+        uint32_t res = 0;
+        if (cnt) {
+            const uint32_t *rows = delta ? dpost_row + terms[t].off_d : post_row + terms[t].off_m;
+            const uint32_t key = (which & 1) ? r1 : r0;
+            const uint32_t est = min(cnt, static_cast<uint32_t>(static_cast<float>(cnt) * (static_cast<float>(key) / static_cast<float>(n_rows))));
+            const uint32_t whi = min(max(est, kSearchWin / 2) + kSearchWin / 2, cnt);
+            const uint32_t wlo = whi > kSearchWin ? whi - kSearchWin : 0u;
+            uint32_t c = 0; // entries of the window below the key (a prefix of it: the list is sorted)
+#pragma unroll
+            for (uint32_t u = 0; u < kSearchWin / 64; ++u) {
+                const uint32_t i = wlo + lane + 64 * u;
+                const uint32_t v = i < whi ? rows[i] : 0xFFFFFFFFu;
+                c += static_cast<uint32_t>(__popcll(__ballot(v < key)));
+            }
+            if ((wlo == 0 || c > 0) && (whi == cnt || c < whi - wlo))
+                res = wlo + c; // the boundary lies inside the window
+            else if (c == 0)
+                res = wave_lower_bound_rows(rows, wlo, key, lane); // the whole window is at or above the key
+            else
+                res = whi + wave_lower_bound_rows(rows + whi, cnt - whi, key, lane);
+        }
+        if (lane == 0)
+            s_range[t][which] = res;
+    }
+    __syncthreads();
+    int any = 0;
+    for (uint32_t t = tid; t < Q.nt; t += 256)
+        any |= (s_range[t][1] > s_range[t][0]) || (s_range[t][3] > s_range[t][2]);
+    if (!__syncthreads_or(any))
+        return; // (uniform) no posting of this query in the slice
+    for (uint32_t r = tid; r < nr; r += 256) {
+        const float dl = static_cast<float>(doc_len[r0 + r]);
+        s_sc[r] = 0.0f;
+        s_dl[r] = dl;
+        s_nk[r] = kK1 * ((1.0f - kB) + kB * (dl / avg)); // (the operations of bm25_terms_lds_kernel)
+        s_fl[r] = 0;
+    }
+    if (tid == 0)
+        s_cnt = 0;
+    __syncthreads();
+    for (uint32_t t = 0; t < Q.nt; ++t) {
+        const float idf = terms[t].idf;
+#pragma unroll
+        for (int seg = 0; seg < 2; ++seg) { // a row lives in exactly one segment and once in a list: no barrier in between
+            const uint32_t lo = s_range[t][2 * seg], hi = s_range[t][2 * seg + 1];
+            const uint32_t *rows = seg ? dpost_row + terms[t].off_d : post_row + terms[t].off_m;
+            const uint32_t *tfs = seg ? dpost_tf + terms[t].off_d : post_tf + terms[t].off_m;
+            for (uint32_t i = lo + tid; i < hi; i += 256) {
+                const uint32_t r = rows[i] - r0;
+                const float dl = s_dl[r];
+                const float tf = static_cast<float>(tfs[i]);
+                const float denom = tf + s_nk[r];
+                if (dl != 0.0f && denom != 0.0f) {
+                    const float sc = idf * (tf * (kK1 + 1.0f)) / denom;
+                    const float old = s_sc[r];
+                    const float now = old + sc; // `*scores.entry(doc).or_insert(0.0) += score`
+                    s_sc[r] = now;
+                    s_fl[r] = static_cast<uint8_t>(s_fl[r] | ((old == 0.0f && now > 0.0f) ? 1u : 0u));
+                }
+            }
+        }
+        __syncthreads(); // the next term adds to the sums this one wrote
+    }
+    uint32_t mine = 0;
+    for (uint32_t r = tid; r < nr; r += 256)
+        mine += s_fl[r] & 1u;
+    uint32_t at = mine ? atomicAdd(&s_cnt, mine) : 0u;
+    __syncthreads();
+    if (tid == 0)
+        s_base = s_cnt ? atomicAdd(&ctls[blockIdx.y].n_touched, s_cnt) : 0u;
+    __syncthreads();
+    at += s_base;
+    if (mine)
+        for (uint32_t r = tid; r < nr; r += 256)
+            if (s_fl[r] & 1u)
+                keys[Q.key_off + at++] = pack_result(s_sc[r], r0 + r);
+}
+
+// per query: up to kMaxLimit keys -> sorted in LDS, the best min(n, limit) into its `sel` slots (lex_sort_kernel's order);
+// more keys: left to the radix passes below
+__global__ __launch_bounds__(1024) void lex_batch_sort_kernel(const BatchQuery *__restrict__ bq, const uint64_t *__restrict__ keys,
+                                                              LexControl *__restrict__ ctls, uint32_t limit,
+                                                              uint64_t *__restrict__ sel)
+{
+    __shared__ uint64_t s[kMaxLimit];
+    LexControl *ctl = ctls + blockIdx.x;
+    const uint32_t n = ctl->n_touched;
+    if (n > kMaxLimit)
+        return;
+    const uint64_t *k = keys + bq[blockIdx.x].key_off;
+    uint32_t n_pad = 1;
+    while (n_pad < n)
+        n_pad <<= 1;
+    for (uint32_t i = threadIdx.x; i < n_pad; i += blockDim.x)
+        s[i] = i < n ? k[i] : 0ull;
+    __syncthreads();
+    lds_sort_desc(s, n_pad);
+    const uint32_t m = min(n, limit);
+    for (uint32_t i = threadIdx.x; i < m; i += blockDim.x)
+        sel[static_cast<uint64_t>(blockIdx.x) * limit + i] = s[i];
+    if (threadIdx.x == 0)
+        ctl->n_sel = m;
+}
+
+// the eight MSD radix passes and the collect of lexical_enqueue's exact path, one query per grid row, for the queries with
+// more than kMaxLimit keys (exact under any number of score ties: the keys are unique)
+__global__ __launch_bounds__(256) void lex_batch_pass_kernel(const BatchQuery *__restrict__ bq, uint64_t *__restrict__ keys,
+                                                             LexControl *__restrict__ ctls, uint32_t limit, int pass)
+{
+    LexControl *ctl = ctls + blockIdx.y;
+    if (ctl->n_touched <= kMaxLimit)
+        return;
+    lex_select_pass_body<false>(keys + bq[blockIdx.y].key_off, ctl, limit, pass, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void lex_batch_collect_kernel(const BatchQuery *__restrict__ bq, const uint64_t *__restrict__ keys,
+                                                                LexControl *__restrict__ ctls, uint32_t limit,
+                                                                uint64_t *__restrict__ sel)
+{
+    LexControl *ctl = ctls + blockIdx.y;
+    if (ctl->n_touched <= kMaxLimit)
+        return;
+    lex_collect_body(keys + bq[blockIdx.y].key_off, ctl, limit, sel + static_cast<uint64_t>(blockIdx.y) * limit, limit);
+}
+
 template <typename T>
 int32_t dev_grow(T **p, uint64_t *cap, uint64_t need, bool zero = false)
 {
@@ -845,6 +1030,10 @@ struct LexWorkspace {
     uint64_t *d_out = nullptr; // kMaxLimit keys + count
     uint64_t *h_out = nullptr; // pinned mirror
     bool dirty = false;        // a call failed after enqueuing work: accumulators / control may be non-zero
+    // batched calls (lexical_batch_enqueue): term table, keys of every query, per-query control blocks and results
+    uint64_t *d_btab = nullptr, *d_bkeys = nullptr, *d_bsel = nullptr;
+    uint64_t btab_cap = 0, bkeys_cap = 0, bsel_cap = 0, bctl_cap = 0;
+    LexControl *d_bctl = nullptr;
 };
 
 constexpr int kMaxWorkspaces = 8; // callers beyond this wait for a free one
@@ -922,7 +1111,7 @@ void workspace_destroy(LexWorkspace *ws)
     }
     if (ws->ready)
         (void)hipEventDestroy(ws->ready);
-    void *dev[] = {ws->d_scores, ws->d_touched, ws->d_keys, ws->d_sel, ws->d_ctl, ws->d_out};
+    void *dev[] = {ws->d_scores, ws->d_touched, ws->d_keys, ws->d_sel, ws->d_ctl, ws->d_out, ws->d_btab, ws->d_bkeys, ws->d_bsel, ws->d_bctl};
     for (void *p : dev)
         if (p)
             (void)hipFree(p);
@@ -1721,6 +1910,156 @@ void lexical_finish(LexPending *p, bool ok)
         }
         lx->ws_cv.notify_one();
         p->ws = nullptr;
+    }
+    if (p->locked) {
+        lx->mu.unlock_shared();
+        p->locked = false;
+    }
+}
+
+namespace {
+struct BatchGuard { // releases whatever lexical_batch_enqueue had taken when it fails half way
+    LexBatchPending *p;
+    bool armed = true;
+    ~BatchGuard()
+    {
+        if (armed)
+            lexical_batch_finish(p, false);
+    }
+};
+} // namespace
+
+int32_t lexical_batch_enqueue(rlr_lexical *lx, uint32_t nq, const char *tokens, const uint64_t *offsets, uint32_t limit,
+                              const LexBatchSink &sink, uint8_t *too_many_terms, LexBatchPending *out)
+{
+    out->lx = lx;
+    out->ws = nullptr;
+    out->ready = nullptr;
+    out->locked = false;
+    if (nq == 0 || limit == 0 || limit > kMaxLimit || limit > sink.bound)
+        return set_error(RLR_E_INVALID, "lexical batch: bad arguments");
+    lx->mu.lock_shared(); // held until lexical_batch_finish: mutators wait, scoring calls do not
+    out->locked = true;
+    BatchGuard guard{out};
+    LEX_HIP(hipSetDevice(lx->device));
+    while (lx->full_dirty || lx->delta_dirty) {
+        lx->mu.unlock_shared();
+        out->locked = false;
+        {
+            std::unique_lock<std::shared_mutex> wr(lx->mu);
+            if (lx->full_dirty || lx->delta_dirty)
+                LEX_TRY(commit(lx));
+        }
+        lx->mu.lock_shared();
+        out->locked = true;
+    }
+    // the term table: [BatchQuery x nq][BatchTerm ...], each query's unique known terms in order of first occurrence (the
+    // order lexical_enqueue adds them in)
+    const uint64_t n_rows = lx->doc_terms.size();
+    const bool any_docs = lx->total_docs > 0;
+    const float n_docs = static_cast<float>(lx->total_docs);
+    const float avg = any_docs ? static_cast<float>(lx->total_length) / n_docs : 1.0f; // :2184-2188
+    std::vector<BatchQuery> qs(nq);
+    std::vector<BatchTerm> ts;
+    std::vector<std::string> toks;
+    std::vector<uint32_t> terms;
+    uint64_t total_keys = 0, max_keys = 0;
+    for (uint32_t q = 0; q < nq; ++q) {
+        too_many_terms[q] = 0;
+        toks.clear();
+        terms.clear();
+        if (any_docs)
+            split_tokens(tokens + offsets[q], static_cast<size_t>(offsets[q + 1] - offsets[q]), &toks);
+        for (const auto &t : toks) {
+            auto it = lx->term_id.find(t);
+            if (it == lx->term_id.end() || lx->df[it->second] == 0)
+                continue; // `if let Some(postings) = self.term_postings.get(&term)` :2196
+            if (std::find(terms.begin(), terms.end(), it->second) == terms.end())
+                terms.push_back(it->second);
+        }
+        if (terms.size() > kBatchTermsMax) {
+            too_many_terms[q] = 1; // (scored by the single path)
+            terms.clear();
+        }
+        qs[q].t0 = static_cast<uint32_t>(ts.size());
+        qs[q].nt = static_cast<uint32_t>(terms.size());
+        qs[q].key_off = total_keys;
+        uint64_t upper = 0;
+        for (uint32_t t : terms) {
+            const float df = static_cast<float>(lx->df[t]);
+            float idf = std::log((n_docs - df + 0.5f) / (df + 0.5f)); // f32 ln (:2198-2200), as lexical_enqueue
+            idf = idf > 0.0f ? idf : 0.0f;
+            BatchTerm bt{};
+            bt.cnt_m = t < lx->main_df.size() ? lx->main_df[t] : 0u;
+            bt.off_m = bt.cnt_m ? lx->term_off[t] : 0;
+            bt.cnt_d = lx->dterm_off.empty() ? 0u : static_cast<uint32_t>(lx->dterm_off[t + 1] - lx->dterm_off[t]);
+            bt.off_d = bt.cnt_d ? lx->dterm_off[t] : 0;
+            bt.idf = idf;
+            ts.push_back(bt);
+            upper += std::max<uint64_t>(lx->df[t], static_cast<uint64_t>(bt.cnt_m) + bt.cnt_d);
+        }
+        upper = std::min<uint64_t>(upper, n_rows); // at most one key per row
+        total_keys += upper;
+        max_keys = std::max(max_keys, upper);
+    }
+    const size_t q_bytes = static_cast<size_t>(nq) * sizeof(BatchQuery);
+    const size_t tab_bytes = q_bytes + ts.size() * sizeof(BatchTerm);
+    out->table.resize((tab_bytes + 7) / 8);
+    std::memcpy(out->table.data(), qs.data(), q_bytes);
+    if (!ts.empty())
+        std::memcpy(reinterpret_cast<char *>(out->table.data()) + q_bytes, ts.data(), ts.size() * sizeof(BatchTerm));
+
+    LexWorkspace *ws = nullptr;
+    LEX_TRY(workspace_acquire(lx, &ws));
+    out->ws = ws;
+    LEX_TRY(dev_grow(&ws->d_btab, &ws->btab_cap, out->table.size()));
+    LEX_TRY(dev_grow(&ws->d_bkeys, &ws->bkeys_cap, std::max<uint64_t>(total_keys, 1)));
+    LEX_TRY(dev_grow(&ws->d_bsel, &ws->bsel_cap, static_cast<uint64_t>(nq) * limit));
+    LEX_TRY(dev_grow(&ws->d_bctl, &ws->bctl_cap, nq));
+    hipStream_t s = ws->stream;
+    const BatchQuery *d_q = reinterpret_cast<const BatchQuery *>(ws->d_btab);
+    const BatchTerm *d_t = reinterpret_cast<const BatchTerm *>(reinterpret_cast<const char *>(ws->d_btab) + q_bytes);
+    LEX_HIP(hipMemsetAsync(ws->d_bctl, 0, static_cast<size_t>(nq) * sizeof(LexControl), s));
+    LEX_HIP(hipMemcpyAsync(ws->d_btab, out->table.data(), tab_bytes, hipMemcpyHostToDevice, s));
+    if (!ts.empty() && n_rows > 0) {
+        const uint32_t slices = static_cast<uint32_t>((n_rows + kLdsRows - 1) / kLdsRows);
+        hipLaunchKernelGGL(bm25_batch_kernel, dim3(slices, nq), dim3(256), 0, s, d_q, d_t, lx->d_post_row, lx->d_post_tf,
+                           lx->d_dpost_row, lx->d_dpost_tf, lx->d_doc_len, static_cast<uint32_t>(n_rows), avg, ws->d_bkeys,
+                           ws->d_bctl);
+    }
+    hipLaunchKernelGGL(lex_batch_sort_kernel, dim3(nq), dim3(1024), 0, s, d_q, ws->d_bkeys, ws->d_bctl, limit, ws->d_bsel);
+    if (max_keys > kMaxLimit) { // some query may have more keys than the LDS sort holds: the radix passes take those
+        const uint32_t blocks_u = std::min<uint32_t>(static_cast<uint32_t>((max_keys + 255) / 256), static_cast<uint32_t>(lx->n_cu) * 8);
+        for (int p = 0; p < kPasses; ++p)
+            hipLaunchKernelGGL(lex_batch_pass_kernel, dim3(blocks_u, nq), dim3(256), 0, s, d_q, ws->d_bkeys, ws->d_bctl, limit, p);
+        hipLaunchKernelGGL(lex_batch_collect_kernel, dim3(blocks_u, nq), dim3(256), 0, s, d_q, ws->d_bkeys, ws->d_bctl, limit,
+                           ws->d_bsel);
+    }
+    static_assert(sizeof(LexControl) % 4 == 0 && offsetof(LexControl, n_sel) % 4 == 0, "count words");
+    launch_lex_unpack_batch(ws->d_bsel, limit, &ws->d_bctl[0].n_sel, static_cast<uint32_t>(sizeof(LexControl) / 4), nq, limit,
+                            sink, s);
+    LEX_HIP(hipGetLastError());
+    LEX_HIP(hipEventRecord(ws->ready, s));
+    out->ready = ws->ready;
+    guard.armed = false;
+    return RLR_OK;
+}
+
+void lexical_batch_finish(LexBatchPending *p, bool ok)
+{
+    (void)ok; // (the batch buffers hold no invariant between calls: the control blocks are cleared at every start)
+    rlr_lexical *lx = p->lx;
+    if (p->ws) {
+        LexWorkspace *ws = static_cast<LexWorkspace *>(p->ws);
+        if (hipStreamSynchronize(ws->stream) != hipSuccess) // (the postings are read until here: keep the lock until then)
+            (void)hipDeviceSynchronize();
+        {
+            std::lock_guard<std::mutex> lk(lx->ws_mu);
+            lx->ws_free.push_back(ws);
+        }
+        lx->ws_cv.notify_one();
+        p->ws = nullptr;
+        p->ready = nullptr;
     }
     if (p->locked) {
         lx->mu.unlock_shared();

@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 struct rlr_lexical;
 struct rlr_index;
 
@@ -71,5 +73,44 @@ int32_t search_hybrid_begin(rlr_index *ix, const float *query, uint32_t need, ui
 int32_t search_hybrid_finish(HybridTicket *ticket, const LexPending *lex, uint64_t *rows_out, float *cos_out, float *score_out,
                              float *lex_out, uint32_t *n_out, int32_t *fallback);
 void search_hybrid_abort(HybridTicket *ticket);
+
+// ---- many queries at once (csrc/engine.cpp: rlr_engine_search_text_batch) ------------------------------------------------
+// Where a batched hybrid search wants the lexical pairs of query q: rows / scores at [q * bound, ...), header q (index.hip's
+// HybridLexHeader: count, max score), as lex_unpack_kernel writes them for one query.
+struct LexBatchSink {
+    uint32_t *d_rows = nullptr;
+    float *d_scores = nullptr;
+    void *d_headers = nullptr;
+    uint32_t bound = 0;        // slots per query (>= limit)
+    uint32_t n_index_rows = 0; // rows of the embedding index (pairs beyond it are marked)
+};
+struct LexBatchPending {
+    rlr_lexical *lx = nullptr;
+    void *ws = nullptr;    // the leased workspace
+    void *ready = nullptr; // hipEvent_t recorded behind the unpack: the sink is complete there
+    bool locked = false;   // the readers' lock, held from enqueue to finish
+    std::vector<uint64_t> table; // the uploaded term table (kept until the copy has run)
+};
+// BM25 of nq queries (tokens[offsets[q] .. offsets[q + 1]) each) -> the best `limit` (<= sink.bound, <= RLR_LEXICAL_MAX_LIMIT)
+// pairs of every query unpacked into `sink`, on the workspace's stream.  No synchronisation.  too_many_terms[q] = 1: the
+// query has more unique known terms than the batched kernel takes; it was left without pairs (score it alone).
+int32_t lexical_batch_enqueue(rlr_lexical *lx, uint32_t nq, const char *tokens, const uint64_t *offsets, uint32_t limit,
+                              const LexBatchSink &sink, uint8_t *too_many_terms, LexBatchPending *out);
+// drains the workspace's stream, hands it back and drops the readers' lock (also after a failed enqueue)
+void lexical_batch_finish(LexBatchPending *p, bool ok);
+// (index.hip) query q's keys at d_sel[q * sel_stride], count at d_count[q * count_stride]; no error check inside
+void launch_lex_unpack_batch(const uint64_t *d_sel, uint32_t sel_stride, const uint32_t *d_count, uint32_t count_stride,
+                             uint32_t nq, uint32_t limit, const LexBatchSink &sink, void *stream);
+
+// index.hip: the cosine side, blend and MMR of nq hybrid searches at once.  `queries`: nq prepared (normalised, dim-long)
+// queries; `need`, `k`, `lambda`, `diversify`, weights, `n_lex_bound` as for search_hybrid_begin.  lex_launch (may be null:
+// no lexical pairs) is called once the workspace exists, before the cosine batch: it enqueues the BM25 chain into the sink
+// on its own stream and returns the event to join (*ready).  Results of query q at [q * k_cap, ...) with k_cap =
+// diversify ? max(min(max(k, 1), need), 1) : need; status[q] != 0: not decided here (1 overflow, 2 fetch boundary) --
+// the caller re-runs that query alone.  Two host synchronisations: the cosine batch and the results.
+int32_t search_hybrid_batch(rlr_index *ix, const float *queries, uint32_t nq, uint32_t need, uint32_t k, float lambda,
+                            int32_t diversify, float w_embedding, float w_lexical, uint32_t n_lex_bound,
+                            int32_t (*lex_launch)(void *, const LexBatchSink *, void **ready), void *lex_arg, uint64_t *rows_out,
+                            float *cos_out, float *score_out, float *lex_out, uint32_t *n_out, uint32_t *status);
 
 } // namespace rlr

@@ -299,6 +299,65 @@ class RagEngine:
             out.append(self._results(view, int(n_out[i])))
         return out
 
+    # -- many query texts at once (oracle: search / search_with_diversity with query_text, per query) -------------
+    def search_text_batch(self, query_embeddings, query_texts: Sequence[str], top_k: int, diversity_factor: float = 0.0,
+                          weights: Optional[QueryWeights] = None, stage: int = 0, return_info: bool = False):
+        """`search_with_diversity(q, top_k, diversity_factor, weights, query_text=t)` (diversity 0: `search(q, top_k,
+        weights, stage=stage, query_text=t)`) for every (q, t) pair, bit for bit, through the batched kernels.  Returns
+        one result list per query, and with return_info also a dict of how the queries were served."""
+        q = _f32(query_embeddings)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        nq, dq = q.shape
+        if len(query_texts) != nq:
+            raise ValueError(f"{nq} query embeddings but {len(query_texts)} query texts")
+        toks = [" ".join(tokenize(t)).encode("utf-8") for t in query_texts]
+        offsets = np.zeros(nq + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum([len(t) for t in toks], dtype=np.uint64) if nq else []
+        blob = b"".join(toks)
+        cap = max(3 * max(top_k, 1), top_k + 10)   # the most hits a query can have (stage 1 or the MMR pool's cut)
+        hits = (N.SearchHitC * (cap * max(nq, 1)))()
+        n_out = np.zeros(max(nq, 1), dtype=np.uint32)
+        info = N.TextBatchInfoC()
+        wc = weights.to_c() if weights is not None else None
+        N.check(N.lib().rlr_engine_search_text_batch(
+            self.index.handle, self.lexical._h, q.ctypes.data_as(N.f32p), dq, nq, blob, offsets.ctypes.data_as(N.u64p),
+            top_k, float(diversity_factor), stage, C.byref(wc) if wc is not None else None, hits, cap,
+            n_out.ctypes.data_as(N.u32p), C.byref(info)))
+        out = []
+        for i in range(nq):
+            view = (N.SearchHitC * cap).from_buffer(hits, i * cap * C.sizeof(N.SearchHitC))
+            out.append(self._results(view, int(n_out[i])))
+        if return_info:
+            return out, {name: int(getattr(info, name)) for name, _ in N.TextBatchInfoC._fields_}
+        return out
+
+    def search_documents_batch(self, requests: Sequence[SearchRequest]) -> List[List[SearchResult]]:
+        """search_documents for every request, grouped by (top_k, diversity, weights) after its caps and clamps and run
+        through search_text_batch; a request without text is scored with no query terms."""
+        groups: Dict[tuple, List[int]] = {}
+        keyed = []
+        for i, r in enumerate(requests):
+            if r.lexical:
+                raise ValueError("search_documents_batch: requests carry caller-computed lexical pairs; "
+                                 "use search_documents")
+            top_k = min(r.top_k if r.top_k is not None else N.DEFAULT_TOP_K, N.MAX_TOP_K)
+            div = r.diversity_factor if r.diversity_factor is not None else N.DEFAULT_DIVERSITY
+            div = min(max(div, 0.0), 1.0)
+            w = r.weights
+            wkey = None if w is None else (w.embedding, w.lexical, w.reranker, w.initial)
+            key = (top_k, div, wkey)
+            keyed.append(key)
+            groups.setdefault(key, []).append(i)
+        out: List[List[SearchResult]] = [[] for _ in requests]
+        for (top_k, div, _), members in groups.items():
+            w = requests[members[0]].weights
+            emb = np.stack([_f32(requests[i].query_embedding).ravel() for i in members])
+            texts = [requests[i].query or "" for i in members]
+            for i, res in zip(members, self.search_text_batch(emb, texts, top_k, div, w)):
+                out[i] = res
+        return out
+
     # -- RagEngine::get_embedding_candidates (rag_engine.rs:415-461) -----------------------
     def get_embedding_candidates(self, query_embedding, count: int) -> List[Tuple[str, float]]:
         q = _f32(query_embedding).ravel()

@@ -1,0 +1,317 @@
+"""rlr_engine_search_text_batch (RagEngine.search_text_batch / search_documents_batch): many query texts at once through the
+batched BM25, blend and MMR kernels.  Every query must come back bit-identical to the oracle (the reference's search /
+search_with_diversity given LexicalIndex::score's pairs) and to rlr_engine_search_text called alone, on every cosine path,
+with the counters saying how the queries were served."""
+import ctypes as C
+import importlib
+import threading
+
+import numpy as np
+import pytest
+
+from oracle import lexical as OL
+
+pytestmark = pytest.mark.gpu
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+VOCAB = [f"w{i:03d}x" for i in range(400)] + ["common", "frequent", "the", "of", "né", "Straße", "ÉTÉ"]
+
+
+def make_texts(n, seed, lo=3, hi=40, common_every=0):
+    rng = np.random.default_rng(seed)
+    zipf = 1.0 / np.arange(1, len(VOCAB) + 1)
+    zipf /= zipf.sum()
+    texts = []
+    for i in range(n):
+        m = int(rng.integers(lo, hi))
+        words = list(rng.choice(VOCAB, size=m, p=zipf))
+        if common_every and i % common_every == 0:
+            words.append("ubiquitous")
+        texts.append(" ".join(words) + (", " if i % 3 else " - "))
+    return texts
+
+
+def query_texts():
+    many = " ".join(f"w{i:03d}x" for i in range(20, 44))                 # 24 unique terms: more than one 16-term launch
+    return (["w000x w001x common", "w017x frequent", "the of w002x w003x w004x", "w005x", "nothing known here", "",
+             "w000x w000x w000x w010x", many, "w399x", "w250x w251x w252x", "common the of frequent", "né Straße été",
+             "w000x w001x common", "W003X; w004x", "w100x w200x w300x", "w007x w008x", "zzz w009x", "of"]
+            + [f"w{i:03d}x w{i + 1:03d}x" for i in range(30, 52)])
+
+
+def same(got, want, ctx):
+    assert [g.row for g in got] == [w.row for w in want], ctx
+    for f in ("score", "embedding_score", "lexical_score", "initial_score"):
+        assert np.array_equal(bits([getattr(g, f) for g in got]), bits([getattr(w, f) for w in want])), (ctx, f)
+
+
+def singles(eng, qs, texts, k, lam, w=None, stage=0):
+    if lam == 0.0:
+        return [eng.search(q, k, weights=w, stage=stage, query_text=t) for q, t in zip(qs, texts)]
+    return [eng.search_with_diversity(q, k, lam, weights=w, query_text=t) for q, t in zip(qs, texts)]
+
+
+@pytest.fixture(scope="module")
+def corpus(rlr, oracle):
+    n, dim = 5000, 128
+    texts = make_texts(n, seed=31, lo=4, hi=25)
+    rows = oracle.synth_rows(n, dim, seed=32)
+    rows[100:140] = rows[7]                      # exact duplicates: cosine ties across lexical and non-lexical rows
+    rows[2000, 5] = np.nan                       # a NaN row scores NaN and orders last
+    eng = rlr.RagEngine(dim)
+    eng.add_document("d", texts, rows)
+    stored = eng.index.fetch_rows(np.arange(n))
+    o = OL.LexicalIndex()
+    for r, t in enumerate(texts):
+        o.add_chunk(r, t, rank=r)
+    qt = query_texts()
+    qs = np.stack([oracle.synth_query(dim, seed=300 + i) for i in range(len(qt))])
+    qs[12] = qs[0]                               # the same query twice
+    qs[5] = rows[7]                              # a query equal to a stored row
+    yield dict(eng=eng, stored=stored, o=o, qs=qs, texts=qt, n=n, dim=dim, rows=rows)
+    eng.close()
+
+
+def oracle_results(oracle, cx, q, text, k, lam, stage, wts, cache):
+    w_e, w_l = wts if wts else (0.7, 0.3)
+    k_eff = k if lam == 0.0 else max(3 * k, k + 10)
+    limit = 5 * max(k_eff, 1)
+    key = (text, limit)
+    if key not in cache:
+        cache[key] = [(c, float(s)) for c, s in cx["o"].score(text, limit, keep_zero=False)]
+    pairs = cache[key]
+    if lam == 0.0:
+        return oracle.search(cx["stored"], q, k, w_e, w_l, lex=pairs, stage=stage)
+    return oracle.search_with_diversity(cx["stored"], q, k, lam, w_e, w_l, lex=pairs)
+
+
+def check_oracle(rlr, oracle, cx, k, lam, stage=0, wts=None, cache=None):
+    eng = cx["eng"]
+    w = rlr.QueryWeights(embedding=wts[0], lexical=wts[1]) if wts else None
+    got, info = eng.search_text_batch(cx["qs"], cx["texts"], k, lam, weights=w, stage=stage, return_info=True)
+    assert len(got) == len(cx["texts"])
+    for i, (q, text) in enumerate(zip(cx["qs"], cx["texts"])):
+        wr, wc, we, wl = oracle_results(oracle, cx, q, text, k, lam, stage, wts, cache)
+        ctx = (i, text, k, lam, stage, wts)
+        assert [g.row for g in got[i]] == list(wr), ctx
+        assert np.array_equal(bits([g.score for g in got[i]]), bits(wc)), ctx
+        assert np.array_equal(bits([g.initial_score for g in got[i]]), bits(wc)), ctx
+        assert np.array_equal(bits([g.embedding_score for g in got[i]]), bits(we)), ctx
+        assert np.array_equal(bits([g.lexical_score for g in got[i]]), bits(wl)), ctx
+    assert info["n_batched"] + info["n_single"] == len(cx["texts"])
+    assert info["n_single"] == info["n_single_lexical"] + info["n_single_blend"] + info["n_single_shape"]
+    return info
+
+
+def test_oracle_parity_default_weights(rlr, oracle, corpus):
+    cache = {}
+    for k in (0, 5, 10, 25, 100):
+        for lam in (0.0, 0.3, 0.7, 1.0):
+            for stage in ((0, 1) if lam == 0.0 else (0,)):
+                info = check_oracle(rlr, oracle, corpus, k, lam, stage, cache=cache)
+                # every query is served by the batched kernels but for the blend's designed hand-back (a rounding tie at
+                # the fetch boundary); a loop over single calls counts nothing here
+                assert info["n_single_shape"] == 0 and info["n_single_lexical"] == 0, (k, lam, stage, info)
+                assert info["n_batched"] >= len(corpus["texts"]) - 4, (k, lam, stage, info)
+
+
+def test_oracle_parity_weights_and_big_pools(rlr, oracle, corpus):
+    cache = {}
+    for wts in ((1.0, 0.0), (0.25, 0.75)):
+        for lam in (0.0, 0.3):
+            info = check_oracle(rlr, oracle, corpus, 10, lam, wts=wts, cache=cache)
+            assert info["n_single_shape"] == 0, (wts, lam, info)
+    for lam in (0.0, 0.3):
+        info = check_oracle(rlr, oracle, corpus, 10, lam, wts=(0.0, 1.0), cache=cache)   # w_e = 0: the single path
+        assert info["n_single_shape"] == len(corpus["texts"]) and info["n_batched"] == 0
+    info = check_oracle(rlr, oracle, corpus, 400, 0.5, cache=cache)                       # pool 1200 > 1024
+    assert info["n_single_shape"] == len(corpus["texts"])
+
+
+def test_lexical_index_ahead_of_embeddings(rlr, oracle):
+    n, dim = 3000, 64
+    texts = make_texts(n, seed=51, lo=4, hi=25)
+    rows = oracle.synth_rows(n, dim, seed=52)
+    eng = rlr.RagEngine(dim)
+    eng.add_document("d", texts, rows)
+    stored = eng.index.fetch_rows(np.arange(n))
+    o = OL.LexicalIndex()
+    for r, t in enumerate(texts):
+        o.add_chunk(r, t, rank=r)
+    eng.lexical.add_chunk(n + 3, "zzzrare zzzrare zzzrare w399x")
+    o.add_chunk(n + 3, "zzzrare zzzrare zzzrare w399x", rank=n + 3)
+    tx = ["zzzrare w399x", "w399x", "zzzrare", "w001x zzzrare"]
+    qs = np.stack([oracle.synth_query(dim, seed=60 + i) for i in range(len(tx))])
+    for lam in (0.0, 0.3):
+        got, info = eng.search_text_batch(qs, tx, 10, lam, return_info=True)
+        assert info["n_batched"] + info["n_single_blend"] == len(tx)
+        for i, t in enumerate(tx):
+            k_eff = 10 if lam == 0.0 else 30
+            pairs = [(c, float(s)) for c, s in o.score(t, 5 * k_eff, keep_zero=False)]
+            if "zzzrare" in t:
+                assert pairs[0][0] == n + 3          # the chunk without an embedding holds the largest BM25 score
+            if lam == 0.0:
+                wr, wc, we, wl = oracle.search(stored, qs[i], 10, lex=pairs)
+            else:
+                wr, wc, we, wl = oracle.search_with_diversity(stored, qs[i], 10, lam, lex=pairs)
+            assert [g.row for g in got[i]] == list(wr) and n + 3 not in wr, (t, lam)
+            assert np.array_equal(bits([g.score for g in got[i]]), bits(wc)), (t, lam)
+            assert np.array_equal(bits([g.lexical_score for g in got[i]]), bits(wl)), (t, lam)
+    eng.close()
+
+
+def _path_engine(rlr, oracle, dim, dtype="f32", n=4000, seed=71):
+    texts = make_texts(n, seed=seed, lo=4, hi=25)
+    rows = oracle.synth_rows(n, dim, seed=seed + 1)
+    eng = rlr.RagEngine(dim, dtype)
+    eng.add_document("d", texts, rows)
+    return eng
+
+
+@pytest.mark.parametrize("path", ["gemm", "scan_multi", "f16", "image"])
+def test_same_as_singles_on_every_cosine_path(rlr, oracle, monkeypatch, path):
+    """The cosine side of the batch on each path of the index' batched top-k, the path proven by the profile counters.
+    5000 rows (batches need >= 4096) of 256 elements (the f32 shared scan needs rows of 256 / 512 / 768 / 1024)."""
+    dim = 256
+    monkeypatch.setenv("RLR_BATCH_MIN", "2")  # (read at creation: batches of this small corpus take the batched paths)
+    eng = _path_engine(rlr, oracle, dim, "f16" if path == "f16" else "f32", n=5000)
+    if path == "image":
+        eng.index.enable_batch_image(True)
+    tx = query_texts()
+    qs = np.stack([oracle.synth_query(dim, seed=400 + i) for i in range(len(tx))])
+    # the shared f32 scan serves 2..8 queries; GEMM / image / binary16 batches of 40
+    sizes = (2, 5, 8) if path == "scan_multi" else (len(tx),)
+    for nb in sizes:
+        for k, lam, stage in ((10, 0.0, 0), (10, 0.3, 0), (25, 0.7, 0), (5, 0.0, 1)):
+            eng.index.profile_enable(True)
+            eng.index.profile_read(reset=True)
+            got, info = eng.search_text_batch(qs[:nb], tx[:nb], k, lam, stage=stage, return_info=True)
+            p = eng.index.profile_read()
+            eng.index.profile_enable(False)
+            ctx = (path, nb, k, lam, stage, info, p)
+            assert info["n_batched"] + info["n_single_blend"] == nb and info["n_batched"] > 0, ctx
+            # one batched top-k served the cosine side (a query re-run alone afterwards adds single-query scans only)
+            assert p.n_batches == 1 and p.n_batch_queries == nb and p.n_f16_range_fallbacks == 0, ctx
+            if path == "gemm":     # >= 16 f32 queries without the image: the GEMM over the f32 rows
+                assert p.n_batches_without_image == 1, ctx
+            else:                  # image: the GEMM over the binary16 image; f16 rows; the shared scan (< 16 queries)
+                assert p.n_batches_without_image == 0, ctx
+            want = singles(eng, qs[:nb], tx[:nb], k, lam, stage=stage)
+            for i in range(nb):
+                same(got[i], want[i], (path, nb, k, lam, stage, i))
+    eng.close()
+
+
+def test_more_queries_than_one_sub_batch(rlr, oracle):
+    """300 queries: two sub-batches (256 + 44), the second one's tokens found through token_offsets + 256"""
+    dim = 64
+    eng = _path_engine(rlr, oracle, dim, n=3000, seed=97)
+    base = query_texts()
+    tx = [base[i % len(base)] + f" w{(7 * i) % 400:03d}x" for i in range(300)]
+    qs = np.stack([oracle.synth_query(dim, seed=700 + i) for i in range(len(tx))])
+    for k, lam in ((10, 0.3), (5, 0.0)):
+        got, info = eng.search_text_batch(qs, tx, k, lam, return_info=True)
+        assert info["n_batched"] + info["n_single"] == len(tx) and info["n_single_shape"] == 0, info
+        want = singles(eng, qs, tx, k, lam)
+        for i in range(len(tx)):
+            same(got[i], want[i], (k, lam, i))
+    eng.close()
+
+
+def test_sampled_selection_regime(rlr, oracle):
+    """> 8192 touched rows per query: the batched radix selection, bit for bit with the single calls (whose BM25 goes through
+    the sampled selection)"""
+    n, dim = 150_000, 32
+    texts = make_texts(n, seed=81, lo=3, hi=10, common_every=2)   # 75 000 chunks hold "ubiquitous"
+    rows = oracle.synth_rows(n, dim, seed=82)
+    eng = rlr.RagEngine(dim)
+    eng.add_document("d", texts, rows)
+    tx = ["ubiquitous", "ubiquitous w000x", "the of common", "w001x ubiquitous w002x", "w300x", "frequent"]
+    qs = np.stack([oracle.synth_query(dim, seed=90 + i) for i in range(len(tx))])
+    for k, lam in ((10, 0.0), (10, 0.3), (100, 0.0)):
+        got, info = eng.search_text_batch(qs, tx, k, lam, return_info=True)
+        want = singles(eng, qs, tx, k, lam)
+        for i in range(len(tx)):
+            same(got[i], want[i], (k, lam, i))
+        assert info["n_single_lexical"] == 0 and info["n_single_shape"] == 0, info
+    eng.close()
+
+
+def test_concurrent_batches_and_singles(rlr, oracle):
+    dim = 64
+    eng = _path_engine(rlr, oracle, dim, n=3000, seed=91)
+    tx = query_texts()
+    qs = np.stack([oracle.synth_query(dim, seed=500 + i) for i in range(len(tx))])
+    jobs = [("batch", 10, 0.3), ("single", 10, 0.3), ("batch", 10, 0.0), ("single", 5, 0.0)]
+    serial = {}
+    for kind, k, lam in jobs:
+        serial[(kind, k, lam)] = (eng.search_text_batch(qs, tx, k, lam) if kind == "batch" else singles(eng, qs, tx, k, lam))
+    errors = []
+
+    def worker(j):
+        try:
+            for rep in range(3):
+                kind, k, lam = jobs[(j + rep) % len(jobs)]
+                res = eng.search_text_batch(qs, tx, k, lam) if kind == "batch" else singles(eng, qs, tx, k, lam)
+                for i in range(len(tx)):
+                    same(res[i], serial[(kind, k, lam)][i], (j, rep, kind, k, lam, i))
+        except Exception as e:  # noqa: BLE001 (re-raised in the main thread)
+            errors.append(e)
+
+    ts = [threading.Thread(target=worker, args=(j,)) for j in range(4)]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join()
+    assert not errors, errors[0]
+    eng.close()
+
+
+def test_bad_arguments_are_rejected_and_leave_the_engine_usable(rlr, oracle):
+    N = importlib.import_module("rust-local-rag_amd._native")
+    dim = 64
+    eng = _path_engine(rlr, oracle, dim, n=2000, seed=95)
+    tx = ["w000x common", "w001x", "the of"]
+    qs = np.ascontiguousarray(np.stack([oracle.synth_query(dim, seed=600 + i) for i in range(3)]), np.float32)
+    toks = [t.encode() for t in tx]
+    blob = b"".join(toks)
+    offs = np.array([0, len(toks[0]), len(toks[0]) + len(toks[1]), len(blob)], np.uint64)
+    cap = 30
+    hits = (N.SearchHitC * (cap * 3))()
+    n_out = np.zeros(3, np.uint32)
+    L = N.lib()
+
+    def call(lex=eng.lexical._h, offsets=offs, c=cap, k=10, lam=0.3):
+        return L.rlr_engine_search_text_batch(eng.index.handle, lex, qs.ctypes.data_as(N.f32p), dim, 3, blob,
+                                              offsets.ctypes.data_as(N.u64p), k, lam, 0, None, hits, c,
+                                              n_out.ctypes.data_as(N.u32p), None)
+    assert call(lex=None) == N.RLR_E_INVALID
+    bad = offs.copy()
+    bad[2] = bad[1] - 1
+    assert call(offsets=bad) == N.RLR_E_INVALID
+    assert call(c=9) == N.RLR_E_INVALID                  # 10 hits per query do not fit
+    assert call(c=29, k=10, lam=0.0) == N.RLR_OK         # (10 of them do at lambda 0)
+    got = eng.search_text_batch(qs, tx, 10, 0.3)
+    want = singles(eng, qs, tx, 10, 0.3)
+    for i in range(3):
+        same(got[i], want[i], i)
+    eng.close()
+
+
+def test_search_documents_batch(rlr, oracle, corpus):
+    eng = corpus["eng"]
+    reqs = [rlr.SearchRequest(corpus["qs"][i], top_k=k, diversity_factor=d, query=t)
+            for i, (k, d, t) in enumerate([(None, None, "w000x common"), (10, 0.0, "w017x"), (500, 2.0, "the of"),
+                                           (None, None, None), (10, 0.0, "w005x w006x"), (7, -1.0, "frequent")])]
+    got = eng.search_documents_batch(reqs)
+    for i, r in enumerate(reqs):
+        same(got[i], eng.search_documents(r), i)   # the request as it stands: no text takes search_documents' other path
+        want = eng.search_documents(rlr.SearchRequest(r.query_embedding, r.top_k, r.diversity_factor, None, [],
+                                                      r.query if r.query is not None else ""))
+        same(got[i], want, i)
+    with pytest.raises(ValueError):
+        eng.search_documents_batch([rlr.SearchRequest(corpus["qs"][0], lexical=[("x", 1.0)])])
