@@ -93,6 +93,20 @@ int32_t rlr_lexical_segments(rlr_lexical *lex, uint64_t *main_postings, uint64_t
 int32_t rlr_lexical_score(rlr_lexical *lex, const char *query_tokens, size_t len, uint32_t limit,
                           uint64_t *rows_out, float *scores_out, uint32_t *n_out);
 
+/* rlr_lexical_score for `n_queries` queries at once, through the batched BM25 kernels that
+ * rlr_engine_search_text_batch runs (a direct view of them: no embedding index involved).  Query q's
+ * tokens are tokens[token_offsets[q] .. token_offsets[q + 1]); its pairs go to rows_out / scores_out
+ * [q * limit, ...), their count to n_out[q] -- exactly what rlr_lexical_score(lex, tokens_q, len_q,
+ * limit, ...) returns: the same rows, order (score desc, row asc) and score bits.  `limit` must be
+ * 1 .. RLR_LEXICAL_MAX_LIMIT (no "0 = all" here).  Queries with more unique known terms than the
+ * batched kernel takes are scored by rlr_lexical_score and counted in *n_single.
+ * max_lexical_out[q] (may be null): max(scores of q, f32::EPSILON), the blend's normalisation input
+ * (rag_engine.rs:515-519) as the batched unpack computes it.  n_single may be null. */
+int32_t rlr_lexical_score_batch(rlr_lexical *lex, uint32_t n_queries, const char *tokens,
+                                const uint64_t *token_offsets, uint32_t limit, uint64_t *rows_out,
+                                float *scores_out, uint32_t *n_out, float *max_lexical_out,
+                                uint32_t *n_single);
+
 /* Convenience tokenizer for hosts without Unicode tables: exact for ASCII text; every
  * non-ASCII code point is treated as alphanumeric and left unchanged (the reference would
  * split at non-ASCII punctuation and lower-case non-ASCII letters).  Writes the space-joined

@@ -2068,3 +2068,119 @@ void lexical_batch_finish(LexBatchPending *p, bool ok)
 }
 
 } // namespace rlr
+
+// ---- rlr_lexical_score_batch: the batched BM25 chain on its own ------------------------------------------------------
+namespace {
+struct LexBatchHeader { // index.hip's HybridLexHeader, as lex_unpack_batch_kernel writes it
+    uint32_t n_lex;
+    float max_lex;
+};
+static_assert(sizeof(LexBatchHeader) == 8, "two 32-bit words per query");
+
+struct SinkBuffers { // the device side of one call's LexBatchSink
+    uint32_t *rows = nullptr;
+    float *scores = nullptr;
+    LexBatchHeader *headers = nullptr;
+    ~SinkBuffers()
+    {
+        void *dev[] = {rows, scores, headers};
+        for (void *p : dev)
+            if (p)
+                (void)hipFree(p);
+    }
+};
+} // namespace
+
+extern "C" int32_t rlr_lexical_score_batch(rlr_lexical *lx, uint32_t nq, const char *tokens, const uint64_t *offsets,
+                                           uint32_t limit, uint64_t *rows_out, float *scores_out, uint32_t *n_out,
+                                           float *max_lexical_out, uint32_t *n_single)
+{
+    if (n_single)
+        *n_single = 0;
+    if (!lx)
+        return set_error(RLR_E_INVALID, "lexical handle is null");
+    if (limit == 0 || limit > kMaxLimit)
+        return set_error(RLR_E_INVALID, "limit %u is outside 1..%u", limit, kMaxLimit);
+    if (nq == 0)
+        return RLR_OK;
+    if (!offsets || !rows_out || !scores_out || !n_out)
+        return set_error(RLR_E_INVALID, "null argument");
+    for (uint32_t q = 0; q < nq; ++q)
+        if (offsets[q + 1] < offsets[q])
+            return set_error(RLR_E_INVALID, "token_offsets decrease at query %u", q);
+    if (offsets[nq] > offsets[0] && !tokens)
+        return set_error(RLR_E_INVALID, "tokens is null");
+    LEX_HIP(hipSetDevice(lx->device));
+    // sub-batches of the engine's size (one grid row of bm25_batch_kernel per query)
+    constexpr uint32_t kSub = 256;
+    const uint32_t sub = std::min(nq, kSub);
+    SinkBuffers buf;
+    LEX_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&buf.rows), static_cast<size_t>(sub) * limit * sizeof(uint32_t)));
+    LEX_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&buf.scores), static_cast<size_t>(sub) * limit * sizeof(float)));
+    LEX_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&buf.headers), sub * sizeof(LexBatchHeader)));
+    rlr::LexBatchSink sink;
+    sink.d_rows = buf.rows;
+    sink.d_scores = buf.scores;
+    sink.d_headers = buf.headers;
+    sink.bound = limit;
+    sink.n_index_rows = 0xFFFFFFFFu; // no embedding index: no pair is marked
+    std::vector<uint32_t> h_rows(static_cast<size_t>(sub) * limit);
+    std::vector<float> h_scores(h_rows.size());
+    std::vector<LexBatchHeader> h_hdr(sub);
+    std::vector<uint8_t> many(sub);
+    std::vector<uint64_t> keys;
+    std::vector<uint32_t> redo;
+    for (uint32_t q0 = 0; q0 < nq; q0 += sub) {
+        const uint32_t m = std::min(sub, nq - q0);
+        rlr::LexBatchPending lp;
+        int32_t st = rlr::lexical_batch_enqueue(lx, m, tokens, offsets + q0, limit, sink, many.data(), &lp);
+        if (st == RLR_OK && hipEventSynchronize(static_cast<hipEvent_t>(lp.ready)) != hipSuccess)
+            st = set_error(RLR_E_HIP, "lexical batch did not complete");
+        if (st == RLR_OK &&
+            (hipMemcpy(h_hdr.data(), buf.headers, m * sizeof(LexBatchHeader), hipMemcpyDeviceToHost) != hipSuccess ||
+             hipMemcpy(h_rows.data(), buf.rows, static_cast<size_t>(m) * limit * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess ||
+             hipMemcpy(h_scores.data(), buf.scores, static_cast<size_t>(m) * limit * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess))
+            st = set_error(RLR_E_HIP, "lexical batch: copy to the host failed");
+        rlr::lexical_batch_finish(&lp, st == RLR_OK);
+        if (st != RLR_OK)
+            return st;
+        for (uint32_t q = 0; q < m; ++q) {
+            const uint32_t g = q0 + q;
+            if (many[q]) {
+                redo.push_back(g);
+                continue;
+            }
+            // the unpack keeps the keys in any order (the radix collect does not sort): order them as rlr_lexical_score does
+            const uint32_t n = std::min(h_hdr[q].n_lex, limit);
+            const size_t b = static_cast<size_t>(q) * limit;
+            keys.resize(n);
+            for (uint32_t i = 0; i < n; ++i)
+                keys[i] = pack_result(h_scores[b + i], h_rows[b + i]);
+            std::sort(keys.begin(), keys.end(), [](uint64_t a, uint64_t c) { return a > c; });
+            const size_t o = static_cast<size_t>(g) * limit;
+            for (uint32_t i = 0; i < n; ++i) {
+                uint32_t row;
+                unpack_result(keys[i], &scores_out[o + i], &row);
+                rows_out[o + i] = row;
+            }
+            n_out[g] = n;
+            if (max_lexical_out)
+                max_lexical_out[g] = h_hdr[q].max_lex;
+        }
+    }
+    // the queries the batched kernel does not take: alone (after the batch dropped the readers' lock)
+    for (uint32_t g : redo) {
+        const size_t o = static_cast<size_t>(g) * limit;
+        LEX_TRY(rlr_lexical_score(lx, tokens ? tokens + offsets[g] : nullptr, static_cast<size_t>(offsets[g + 1] - offsets[g]), limit,
+                                  rows_out + o, scores_out + o, &n_out[g]));
+        if (max_lexical_out) {
+            float mx = 0.0f; // fold(0.0, f32::max), floored at f32::EPSILON (rag_engine.rs:515-519)
+            for (uint32_t i = 0; i < n_out[g]; ++i)
+                mx = std::fmax(mx, scores_out[o + i]);
+            max_lexical_out[g] = mx >= 1.1920929e-07f ? mx : 1.1920929e-07f;
+        }
+    }
+    if (n_single)
+        *n_single = static_cast<uint32_t>(redo.size());
+    return RLR_OK;
+}

@@ -315,3 +315,73 @@ def test_search_documents_batch(rlr, oracle, corpus):
         same(got[i], want, i)
     with pytest.raises(ValueError):
         eng.search_documents_batch([rlr.SearchRequest(corpus["qs"][0], lexical=[("x", 1.0)])])
+
+
+def test_ingest_loop_appends_replacements_and_removals(rlr, oracle):
+    """The product's ingest loop: a search after every add_document (every document after the first lands in the appended
+    posting segment), a document re-added (its old rows removed -- a compaction of the appended segment on the device --
+    then appended again), the first document removed (a compaction of the main segment, which empties it) and one more
+    added.  In every state the batch equals the oracle (lexical oracle rebuilt from the engine's chunks in row order) and the
+    single calls, with BM25 weighted up as well as at the defaults; a query of 129 unique known terms is handed back."""
+    dim = 64
+    eng = rlr.RagEngine(dim)
+    sizes = {"d0": 1500, "d1": 400, "d2": 700, "d3": 300, "d4": 900, "d5": 250}
+    docs = {name: (make_texts(n, seed=1000 + i, lo=4, hi=25) + [f"marker{name} w000x"],
+                   oracle.synth_rows(n + 1, dim, seed=2000 + i)) for i, (name, n) in enumerate(sizes.items())}
+    tx = query_texts()[:20] + ["markerd0 w000x", "markerd1", "markerd2 markerd4 common", "markerd5 w001x"]
+    qs = np.stack([oracle.synth_query(dim, seed=3000 + i) for i in range(len(tx))])
+
+    def check_state(state):
+        o = OL.LexicalIndex()
+        for r, ch in enumerate(eng._chunks):
+            o.add_chunk(r, ch.text, rank=r)
+        cx = dict(o=o, stored=eng.index.fetch_rows(np.arange(len(eng))))
+        cache = {}
+        for k, lam, wts in ((10, 0.0, None), (10, 0.3, None), (10, 0.0, (0.25, 0.75)), (8, 0.5, (0.25, 0.75))):
+            w = rlr.QueryWeights(embedding=wts[0], lexical=wts[1]) if wts else None
+            got, info = eng.search_text_batch(qs, tx, k, lam, weights=w, return_info=True)
+            assert info["n_single_shape"] == 0 and info["n_batched"] + info["n_single"] == len(tx), (state, info)
+            want = singles(eng, qs, tx, k, lam, w)
+            for i, (q, text) in enumerate(zip(qs, tx)):
+                ctx = (state, i, text, k, lam, wts)
+                wr, wc, we, wl = oracle_results(oracle, cx, q, text, k, lam, 0, wts, cache)
+                assert [g.row for g in got[i]] == list(wr), ctx
+                assert np.array_equal(bits([g.score for g in got[i]]), bits(wc)), ctx
+                assert np.array_equal(bits([g.embedding_score for g in got[i]]), bits(we)), ctx
+                assert np.array_equal(bits([g.lexical_score for g in got[i]]), bits(wl)), ctx
+                same(got[i], want[i], ctx)
+        return o
+
+    for name in ("d0", "d1", "d2", "d3", "d4"):
+        eng.add_document(name, *docs[name])
+        check_state(("add", name))
+        seg = eng.lexical.segments()
+        assert seg["full_rebuilds"] == 1, (name, seg)
+        assert (seg["appended_postings"] > 0) == (name != "d0"), (name, seg)
+    # re-add d1: its rows leave the appended segment (device compaction), the new ones are appended
+    before = eng.lexical.segments()
+    eng.add_document("d1", *docs["d1"])
+    o = check_state(("re-add", "d1"))
+    seg = eng.lexical.segments()
+    assert seg["full_rebuilds"] == 1 and seg["appended_postings"] == before["appended_postings"], seg
+    assert seg["append_rebuilds"] == before["append_rebuilds"] + 1, seg
+    # a query of 129 unique known terms goes to the single path and still matches
+    known = sorted(t for t in o.term_postings if t.startswith("w"))[:129]
+    assert len(known) == 129
+    tx129 = tx[:3] + [" ".join(known)]
+    got, info = eng.search_text_batch(qs[:4], tx129, 10, 0.3, return_info=True)
+    assert info["n_single_shape"] == 1, info
+    want = singles(eng, qs[:4], tx129, 10, 0.3)
+    for i in range(4):
+        same(got[i], want[i], ("129 terms", i))
+    # remove d0, the whole main segment: compacted on the device, every remaining row in the appended segment
+    before = eng.lexical.segments()
+    eng.remove_document("d0")
+    check_state(("remove", "d0"))
+    seg = eng.lexical.segments()
+    assert seg["full_rebuilds"] == 1 and seg["append_rebuilds"] == before["append_rebuilds"], seg
+    assert seg["main_postings"] == 0 and seg["appended_postings"] == eng.lexical.info()["n_postings"], seg
+    eng.add_document("d5", *docs["d5"])
+    check_state(("add", "d5"))
+    assert eng.lexical.segments()["full_rebuilds"] == 1
+    eng.close()
