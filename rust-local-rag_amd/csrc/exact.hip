@@ -380,51 +380,6 @@ __device__ inline float gram_entry(float dot)
     return finite_f(dot) ? dot : -__builtin_inff();
 }
 
-// gram[i][j] = dot_ref(pool_i, pool_j), one lane per pair (j <= i computed, mirrored):
-// a*b is commutative and the summation order is the same, so dot(i,j) == dot(j,i) bitwise.
-__global__ __launch_bounds__(64) void gram_kernel(const float *__restrict__ pool, uint32_t P, uint32_t dim,
-                                                  float *__restrict__ gram)
-{
-    // blockIdx.z = query of a batch (pool and gram are P-strided per query)
-    pool += static_cast<size_t>(blockIdx.z) * P * dim;
-    gram += static_cast<size_t>(blockIdx.z) * P * P;
-    const uint32_t i = blockIdx.y;
-    const uint32_t j = blockIdx.x * 64 + threadIdx.x;
-    if (j > i || i >= P)
-        return;
-    const float *a = pool + static_cast<size_t>(i) * dim;
-    const float *b = pool + static_cast<size_t>(j) * dim;
-    float s = 0.0f;
-    uint32_t c = 0;
-    if ((dim & 3u) == 0) {
-        const float4 *a4 = reinterpret_cast<const float4 *>(a);
-        const float4 *b4 = reinterpret_cast<const float4 *>(b);
-        for (; c + 16 <= dim; c += 16) {
-            float4 x[4], y[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                x[u] = a4[c / 4 + u];
-                y[u] = b4[c / 4 + u];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                float p;
-                p = x[u].x * y[u].x; s = s + p;
-                p = x[u].y * y[u].y; s = s + p;
-                p = x[u].z * y[u].z; s = s + p;
-                p = x[u].w * y[u].w; s = s + p;
-            }
-        }
-    }
-    for (; c < dim; ++c) {
-        float p = a[c] * b[c];
-        s = s + p;
-    }
-    s = gram_entry(s);
-    gram[static_cast<size_t>(i) * P + j] = s;
-    gram[static_cast<size_t>(j) * P + i] = s;
-}
-
 // One staged float4 of a pool row (the vector path: dim % 4 == 0): rows as dense f32 (SRC 0, row = pool index), through the
 // index (SRC 1 f32, SRC 2 binary16 widened exactly; row = index row).  Unconditional -- the caller clamps row and column
 // into range and discards what it did not want -- so that a thread's loads are all in flight together: behind a
@@ -743,140 +698,6 @@ __device__ __forceinline__ void emit_empty_block(const MmrEmit &emit)
     emit.h_out[4 * emit.k_cap + 3] = kBlockDone;
 }
 
-// Register-resident greedy MMR for pools of <= 64*J candidates: lane l owns candidates l, l+64, ...
-// with their relevance, running max-similarity and current position in the reference's
-// `remaining` vector held in VGPRs.  A step is one batch of independent L2 loads of the last
-// pick's Gram row, a handful of VALU ops, a DPP wavefront max over the MMR values and a DPP
-// wavefront min over the positions of the lanes that hold that max ("first in visiting order
-// wins" under the reference's strict `>`), and the swap_remove position update -- no LDS, no
-// barriers.  ~0.3 us per pick instead of ~2.2 us for the LDS version.
-template <int J>
-__global__ __launch_bounds__(256) void mmr_greedy_reg_kernel(const float *__restrict__ gram,
-                                                             const float *__restrict__ scores, uint32_t P, uint32_t k,
-                                                             float lambda, uint32_t *__restrict__ out_order,
-                                                             float *__restrict__ out_mmr, uint32_t *__restrict__ out_n,
-                                                             const uint32_t *__restrict__ sizes, MmrEmit emit)
-{
-    // batch: blockIdx.x = query; arrays are strided by the launch-wide P, the pool size is sizes[q]
-    {
-        const uint32_t stride = P;
-        gram += static_cast<size_t>(blockIdx.x) * stride * stride;
-        scores += static_cast<size_t>(blockIdx.x) * stride;
-        out_order += static_cast<size_t>(blockIdx.x) * stride;
-        out_mmr += static_cast<size_t>(blockIdx.x) * stride;
-        out_n += blockIdx.x;
-    }
-    const uint32_t g_stride = P;
-    if (sizes)
-        P = sizes[blockIdx.x];
-    if (P == 0) {
-        if (threadIdx.x == 0) {
-            *out_n = 0;
-            if (emit.h_out) // (an unusable pool arrives here as size 0 with its status in info[1])
-                emit_empty_block(emit);
-        }
-        return;
-    }
-    // The Gram matrix was just written by other CUs (possibly other XCDs): its first touch from
-    // this CU is an Infinity-Cache/HBM miss (~0.4 us), and every pick reads a different row, so
-    // the greedy chain would pay that miss 99 times.  All four waves first sweep the matrix
-    // (P*P*4 bytes, 360 KB at P = 300) into this XCD's L2; the chain's loads then hit L2.
-    {
-        const float4 *g4 = reinterpret_cast<const float4 *>(gram);
-        const uint32_t n4 = (P * g_stride) / 4;
-        float warm = 0.0f;
-        for (uint32_t i = threadIdx.x * 8; i < n4; i += 256 * 8) // one 128-B line per thread and step
-            warm += g4[i].x;
-        asm volatile("" ::"v"(warm));
-    }
-    __syncthreads();
-    if (threadIdx.x >= 64)
-        return;
-    const uint32_t lane = threadIdx.x;
-    // The loop body is written branch-free (selects, no `continue`): with branches hipcc builds a saveexec / branch
-    // ladder per candidate, and one wave alone on its SIMD pays every one of those at ~5 cycles per instruction -- the
-    // chain took 1.07 us per pick, about two thirds of it control flow.  There are no per-candidate flags either
-    // (hipcc packs bool arrays into bytes and unpacks them every pick): a slot that is empty or already picked carries
-    // t0 = NaN, so its MMR value is never finite and never a candidate, and position ~0, which no live position
-    // equals; a relevance that is not finite makes t0, hence the MMR value, non-finite by itself (`rel.is_finite()`).
-    float t0[J], ms[J];          // (1 - lambda) * relevance (loop invariant; NaN = not selectable), running max similarity
-    uint32_t pos[J], idx[J];     // position in the reference's `remaining` (~0 = gone); clamped Gram column of the candidate
-    const float one_minus = 1.0f - lambda;
-    const float nan_f = __builtin_bit_cast(float, 0x7FC00000u);
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-        const uint32_t c = lane + 64 * j;
-        idx[j] = min(c, P - 1);
-        const float r = scores[idx[j]];
-        // selected.push(remaining.swap_remove(0)): candidate 0 goes first, the last one takes slot 0
-        const bool usable = (c < P) & (c != 0);
-        t0[j] = usable ? one_minus * r : nan_f;
-        ms[j] = 0.0f;
-        pos[j] = usable ? ((c == P - 1) ? 0u : c) : 0xFFFFFFFFu;
-    }
-    uint32_t n_rem = P - 1, n_sel = 1, last = 0;
-    if (lane == 0) {
-        out_order[0] = 0;
-        out_mmr[0] = nan_f;
-    }
-    const float neg_inf = -__builtin_inff();
-    while (n_sel < k && n_rem > 0) {
-        const float *g_last = gram + static_cast<size_t>(last) * g_stride;
-        float sim[J];
-#pragma unroll
-        for (int j = 0; j < J; ++j)
-            sim[j] = g_last[idx[j]]; // empty slots load a valid (clamped) column and ignore it
-        float best_m = neg_inf;
-        uint32_t best_pos = 0xFFFFFFFFu;
-        float raw[J];
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-            // `if sim.is_finite() { max_sim = max_sim.max(sim) }` on a max_sim that starts at +0.0 and is never NaN
-            const bool raise = finite_f(sim[j]) & (sim[j] > ms[j]);
-            ms[j] = raise ? sim[j] : ms[j];
-            const float t1 = lambda * ms[j];
-            const float m0 = t0[j] - t1;
-            raw[j] = m0;                            // what the reference logs for the winner (sign of zero included)
-            // (-0 and +0 compare equal in the reference, and so they do in the float compares below)
-            const bool better = finite_f(m0) & ((m0 > best_m) | ((m0 == best_m) & (pos[j] < best_pos)));
-            best_m = better ? m0 : best_m;
-            best_pos = better ? pos[j] : best_pos;
-        }
-        const float wm = wave_max_f32_no_nan(best_m); // best_m is -inf or a finite MMR value
-        if (wm == neg_inf) // no finite candidate left
-            break;
-        const uint32_t wp = wave_min_u32(best_m == wm ? best_pos : 0xFFFFFFFFu);
-        uint32_t win = 0;
-        float win_raw = 0.0f;
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-            const bool hit = pos[j] == wp;
-            win = hit ? lane + 64 * j + 1 : win;
-            win_raw = hit ? raw[j] : win_raw;
-            t0[j] = hit ? nan_f : t0[j];
-            // swap_remove(best_idx): the winner leaves, the candidate in the last slot moves into the freed one
-            pos[j] = hit ? 0xFFFFFFFFu : (pos[j] == n_rem - 1 ? wp : pos[j]);
-        }
-        // exactly one lane holds the winner: broadcast its candidate index
-        const unsigned long long ball = __ballot(win != 0);
-        const int src = __builtin_ctzll(ball);
-        last = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(win), src)) - 1;
-        const float wm_raw = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, win_raw), src));
-        if (lane == 0) {
-            out_order[n_sel] = last;
-            out_mmr[n_sel] = wm_raw;
-        }
-        n_sel++;
-        n_rem--;
-    }
-    if (lane == 0)
-        *out_n = n_sel;
-    if (emit.h_out) { // the picks straight into the caller's (pinned) result block
-        __threadfence(); // lane 0's out_order stores, read back by all lanes
-        emit_result_block(emit, n_sel, lane, [&](uint32_t i) { return out_order[i]; });
-    }
-}
-
 // max over a lane's J values that skips NaN, never below -inf: v_max3_f32 returns the largest non-NaN operand (all values
 // here are quiet NaNs or numbers), a tree two operands wide per step instead of a compare-and-select chain
 template <int J>
@@ -892,13 +713,17 @@ __device__ inline float lane_max_skip_nan(const float (&v)[J])
     return best;
 }
 
-// The same chain with the tie-break taken off the common path.
+// Register-resident greedy MMR for pools of <= 64*J candidates: lane l owns candidates l, l+64, ... with their relevance
+// and running max-similarity held in VGPRs.  A step is one batch of independent L2 loads of the last pick's Gram row, a
+// handful of VALU ops and a DPP wavefront max over the MMR values -- no barriers; ~2.2 us per pick for the LDS version
+// (mmr_greedy_kernel).
 //
-// A pick of the register-resident kernel above is ~190 instructions of one wave alone on its SIMD -- an issue slot every
-// four cycles whatever the instruction, eight when it depends on the one before -- plus the L2 round trip of its Gram-row
-// loads: 0.60 us.  About a third of those instructions keep every candidate's position in the reference's `remaining`
-// vector (swap_remove moves the last entry into the freed slot) and run a second wavefront reduction over positions --
-// needed only when two candidates hold the same maximal MMR value ("first in visiting order wins" under the strict `>`).
+// The tie-break is taken off the common path.  With every candidate's position in the reference's `remaining` vector kept
+// in registers too (swap_remove moves the last entry into the freed slot) and a second wavefront reduction over the
+// positions, a pick was ~190 instructions of one wave alone on its SIMD -- an issue slot every four cycles whatever the
+// instruction, eight when it depends on the one before -- plus the L2 round trip of its Gram-row loads: 0.60 us, about a
+// third of it for the positions, which are needed only when two candidates hold the same maximal MMR value ("first in
+// visiting order wins" under the strict `>`; that kernel was removed after the comparison).
 // Here the wave counts the holders of the maximum (one compare and one ballot per slot); a single holder is the pick, and
 // only a tie replays the removals logged so far on a copy of `remaining` in LDS (lane 0, incrementally: each removal is
 // replayed once) and takes the lowest position among the tied.  Non-finite values never reach the compares: a relevance
@@ -937,7 +762,10 @@ __global__ __launch_bounds__(256) void mmr_greedy_lazy_kernel(const float *__res
         }
         return;
     }
-    // (the L2 warm-up of mmr_greedy_reg_kernel: every pick reads a different row of a matrix other CUs just wrote)
+    // The Gram matrix was just written by other CUs (possibly other XCDs): its first touch from
+    // this CU is an Infinity-Cache/HBM miss (~0.4 us), and every pick reads a different row, so
+    // the greedy chain would pay that miss 99 times.  All four waves first sweep the matrix
+    // (P*P*4 bytes, 360 KB at P = 300) into this XCD's L2; the chain's loads then hit L2.
     {
         const float4 *g4 = reinterpret_cast<const float4 *>(gram);
         const uint32_t n4 = (P * g_stride) / 4;
@@ -954,6 +782,11 @@ __global__ __launch_bounds__(256) void mmr_greedy_lazy_kernel(const float *__res
         s_rem[c] = static_cast<uint16_t>(c);
         s_posof[c] = static_cast<uint16_t>(c);
     }
+    // The loop body is written branch-free (selects, no `continue`): with branches hipcc builds a saveexec / branch
+    // ladder per candidate, and one wave alone on its SIMD pays every one of those at ~5 cycles per instruction -- the
+    // chain took 1.07 us per pick, about two thirds of it control flow.  There are no per-candidate flags either
+    // (hipcc packs bool arrays into bytes and unpacks them every pick): a slot that is empty or already picked carries
+    // t0 = NaN, so its MMR value is never finite and never a candidate.
     float t0[J], ms[J];  // (1 - lambda) * relevance (loop invariant; NaN = not selectable), running max similarity
     uint32_t idx[J];     // clamped Gram column of the candidate
     const float one_minus = 1.0f - lambda;
@@ -1305,12 +1138,12 @@ typedef float v32f __attribute__((ext_vector_type(32)));
 // kernel's 3.3).  The row pair's one tile below the diagonal is computed twice, everything else once; all waves of a pool run
 // on one XCD (its rows come from HBM once).
 // UPR = 16-byte units per row and chunk: the K chunk is 8 UPR binary16 elements (UPR = 4: 7.7 KB of LDS per wave, five waves per SIMD
-// fit; UPR = 8: 13.8 KB, 2.75 per SIMD -- RLR_GRAM_CHUNK=64 selects it for A/B runs).
-template <int UPR>
+// fit; UPR = 8 would be 13.8 KB, 2.75 per SIMD).
 __global__ __launch_bounds__(64) void gram_mfma_f32_kernel(const unsigned char *__restrict__ rows, uint32_t pitch_bytes,
                                                            const uint32_t *__restrict__ list, uint32_t P, uint32_t n_pools,
                                                            uint32_t jobs_per_pool, float *__restrict__ gram)
 {
+    constexpr int UPR = 4;
     constexpr int kGmPitch = UPR * 16 + 16; // bytes per staged row: 16-byte reads of consecutive rows land in different slots
     constexpr int kPer = 96 * UPR / 64;     // 16-byte units per lane and chunk
     __shared__ __attribute__((aligned(16))) unsigned char s_rows[96 * kGmPitch]; // rows 0..63: A (2p, 2p + 1), 64..95: B (J)
@@ -1399,8 +1232,7 @@ static hipError_t launch_gram_src(const float *pool, uint32_t P, uint32_t dim, f
         // 16 x 16 (one pair per thread): 31 -> 17 us at 768-d.  The small tile wins until its blocks outnumber the
         // CUs about six times (measured: 800-row pools still, 1024-row pools no longer; 7 pools of 300 still).
         const uint32_t nb1 = (P + 15) / 16;
-        static const bool short_chunks = getenv("RLR_GRAM_SHORT_CHUNKS") != nullptr;
-        if (static_cast<uint64_t>(nb1) * (nb1 + 1) / 2 * n_queries <= 512 && !short_chunks) {
+        if (static_cast<uint64_t>(nb1) * (nb1 + 1) / 2 * n_queries <= 512) {
             // at most two blocks per CU: 384 columns per chunk, two rounds of loads per 768-d pool instead of six (10.3 against
             // 11.9 us; before the staged loads were batched -- gram_load4 -- the same pool took 17.9)
             hipLaunchKernelGGL((gram_tiled_kernel<1, SRC, 384>), dim3(nb1 * (nb1 + 1) / 2, 1, n_queries), dim3(256), 0, s, pool, P,
@@ -1421,11 +1253,6 @@ hipError_t launch_gram(const float *pool, uint32_t P, uint32_t dim, float *gram,
 {
     if (P == 0 || n_queries == 0)
         return hipSuccess;
-    static const bool naive = getenv("RLR_GRAM_NAIVE") != nullptr;
-    if (naive) {
-        hipLaunchKernelGGL(gram_kernel, dim3((P + 63) / 64, P, n_queries), dim3(64), 0, s, pool, P, dim, gram);
-        return hipGetLastError();
-    }
     return launch_gram_src<0>(pool, P, dim, gram, n_queries, nullptr, 0, nullptr, s);
 }
 
@@ -1437,20 +1264,14 @@ hipError_t launch_gram_rows(const void *rows, uint32_t pitch16, uint32_t dim, in
         return hipSuccess;
     if (dtype == RLR_F16) {
         // enough pools to fill the chip (two 32 x 32 tiles per wave, 1024 k-steps each): the f32 matrix cores
-        static const bool valu_only = getenv("RLR_GRAM_VALU") != nullptr;
-        if (n_queries >= 16 && !valu_only) {
+        if (n_queries >= 16) {
             const uint32_t nb = (P + 31) / 32;
             uint32_t jobs_per_pool = 0;
             for (uint32_t pr = 0; 2 * pr < nb; ++pr)
                 jobs_per_pool += nb - 2 * pr;
             const uint32_t pools8 = (n_queries + 7) / 8 * 8;
-            static const bool wide_chunk = getenv("RLR_GRAM_CHUNK") && atoi(getenv("RLR_GRAM_CHUNK")) == 64;
-            if (wide_chunk)
-                hipLaunchKernelGGL(gram_mfma_f32_kernel<8>, dim3(pools8 * jobs_per_pool), dim3(64), 0, s, static_cast<const unsigned char *>(rows),
-                                   pitch16 * 16u, list, P, n_queries, jobs_per_pool, gram);
-            else
-                hipLaunchKernelGGL(gram_mfma_f32_kernel<4>, dim3(pools8 * jobs_per_pool), dim3(64), 0, s, static_cast<const unsigned char *>(rows),
-                                   pitch16 * 16u, list, P, n_queries, jobs_per_pool, gram);
+            hipLaunchKernelGGL(gram_mfma_f32_kernel, dim3(pools8 * jobs_per_pool), dim3(64), 0, s, static_cast<const unsigned char *>(rows),
+                               pitch16 * 16u, list, P, n_queries, jobs_per_pool, gram);
             return hipGetLastError();
         }
         return launch_gram_src<2>(nullptr, P, dim, gram, n_queries, rows, pitch16, list, s);
@@ -1467,18 +1288,9 @@ hipError_t launch_mmr_greedy(const float *gram, const float *scores, uint32_t P,
     const MmrEmit emit = emit_in ? *emit_in : MmrEmit{};
     if (emit.h_out && (n_queries != 1 || P == 0 || P > 1024))
         return hipErrorInvalidValue; // the emit tail exists in the register-resident single-pool kernel only
-    // RLR_MMR_GREEDY=reg: every candidate's position kept in registers (the kernel before the lazy tie-break)
-    static const char *g_env = getenv("RLR_MMR_GREEDY");
-    static const bool reg = g_env && !strcmp(g_env, "reg");
 #define RLR_MMR_REG(JV)                                                                                          \
-    do {                                                                                                         \
-        if (reg)                                                                                                 \
-            hipLaunchKernelGGL(mmr_greedy_reg_kernel<JV>, dim3(n_queries), dim3(256), 0, s, gram, scores, P, k, lambda, \
-                               out_order, out_mmr, out_n, sizes, emit);                                          \
-        else                                                                                                     \
-            hipLaunchKernelGGL(mmr_greedy_lazy_kernel<JV>, dim3(n_queries), dim3(256), 0, s, gram, scores, P, k, lambda, \
-                               out_order, out_mmr, out_n, sizes, emit);                                          \
-    } while (0)
+    hipLaunchKernelGGL(mmr_greedy_lazy_kernel<JV>, dim3(n_queries), dim3(256), 0, s, gram, scores, P, k, lambda, \
+                       out_order, out_mmr, out_n, sizes, emit)
     if (P == 0 || (P > 1024 && n_queries == 1 && !sizes))
         hipLaunchKernelGGL(mmr_greedy_kernel, dim3(1), dim3(64), lds, s, gram, scores, P, k, lambda, out_order, out_mmr,
                            out_n);

@@ -106,10 +106,6 @@ struct GemmArgs {
     float *scores;               // materialise mode: [query][score_stride], column = row - row_begin
     size_t score_stride;
     uint32_t *sync;              // gemm8, several query blocks: 256 zeroed words, one arrival counter per sibling group (or null)
-    uint32_t sync_every;         // ... and the siblings meet before every sync_every-th unit
-    uint32_t a_nt_shared;        // (experiment, RLR_GEMM8_A_NT=1) row half-tiles streamed `nt` even when sibling workgroups share them:
-                                 // config 5's share fetched 1.36 x (meeting every unit) / 1.50 x (every 2nd) the image against
-                                 // 1.22 x / 1.28 x without -- the siblings are not tight enough for evict-first lines; off
 };
 
 // ---- epilogue shared by the GEMM kernels: D layout is col = lane & 15 (query), row = 4*(lane >> 4) + reg
@@ -456,10 +452,10 @@ __device__ __forceinline__ void lds_write_b32(uint32_t addr, uint32_t v)
     asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory");
 }
 
-// VAR (RLR_GEMM8_VARIANT, same-box A/B): bit 0 = s_setprio pair around each MFMA cluster (+2-5 % time: off), bit 1 = no
-// sched_barrier behind the phase's lgkmcnt(0) (-1 %), bit 2 = non-temporal DMA for the once-read row half-tiles
-// (-2.5 % at 256 queries; only used while a row tile has one reader).  Built: 6 (default) and 0.
-template <bool MATERIALISE, int VAR>
+// Schedule choices from same-box A/Bs: no s_setprio pair around the MFMA clusters (it cost 2-5 %), no sched_barrier behind
+// a phase's lgkmcnt(0) (1 % faster without), non-temporal DMA for row half-tiles that are read once (2.5 % faster at 256
+// queries).
+template <bool MATERIALISE>
 __global__ __launch_bounds__(512) void gemm8_kernel(const GemmArgs a, const char *__restrict__ image, uint32_t n_tiles)
 {
     __shared__ __attribute__((aligned(1024))) char lds[kG8LdsBytes];
@@ -500,7 +496,7 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const GemmArgs a, const char
     // on) until all nqb have arrived -- or 512 polls have passed (64 were not enough: siblings legitimately differ by a unit's epilogue, and workgroups
     // that gave up let the traffic climb back to 2.1 x): a sibling that never comes (a grid that is not fully resident, e.g. two
     // batched searches on the device at once) costs a few hundred microseconds ONCE -- the workgroup then stops meeting -- never a hang.
-    const uint32_t kSyncEvery = a.sync_every ? a.sync_every : 4u;
+    constexpr uint32_t kSyncEvery = 4;
     const bool sib_sync = a.sync != nullptr && nqb > 1 && nqb <= J && (J % nqb) == 0;
     const uint32_t *sync_word = sib_sync ? a.sync + xcd * 32 + j / nqb : nullptr;
     bool meeting = sib_sync; // (wave-uniform; only wave 0 uses it)
@@ -524,8 +520,9 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const GemmArgs a, const char
         const uint32_t second = is_a ? 8192u : 16384u;
         // non-temporal only while a row tile has ONE reader (<= 256 queries).  With several query blocks the units of a tile run
         // side by side on one XCD and their 2nd..n-th read is meant to hit its L2: streamed with `nt` the lines are gone before the
-        // siblings arrive -- config 5's share fetched the image 3.2 times per batch (rocprofv3 FETCH_SIZE, profiles/r03_c5_share_*)
-        if ((VAR & 4) && is_a && (nqb == 1 || a.a_nt_shared)) {
+        // siblings arrive -- config 5's share fetched the image 3.2 times per batch (rocprofv3 FETCH_SIZE, profiles/r03_c5_share_*);
+        // with the siblings meeting as above it was still 1.36-1.50 x against 1.22-1.28 x without `nt`
+        if (is_a && nqb == 1) {
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + tid * 16),
                                              (__attribute__((address_space(3))) void *)(dst), 16, 0, 2);
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + second + tid * 16),
@@ -610,11 +607,8 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const GemmArgs a, const char
     if (WAIT) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");                                              \
     RLR_FENCE();                                                                                             \
     __builtin_amdgcn_s_barrier();                                                                            \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                      \
-    if (!(VAR & 2)) __builtin_amdgcn_sched_barrier(0);                                                       \
-    if (VAR & 1) __builtin_amdgcn_s_setprio(1);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #define RLR_PHASE_TAIL()                                                                                     \
-    if (VAR & 1) __builtin_amdgcn_s_setprio(0);                                                              \
     RLR_FENCE();                                                                                             \
     __builtin_amdgcn_s_barrier();                                                                            \
     RLR_FENCE();
@@ -1107,41 +1101,6 @@ __global__ __launch_bounds__(1024) void batch_band_kernel(uint64_t *__restrict__
     }
 }
 
-__global__ __launch_bounds__(1024) void batch_tighten_kernel(uint64_t *__restrict__ cand, uint32_t cand_stride,
-                                                             SelectState *__restrict__ st, uint32_t k, float two_eps,
-                                                             float *__restrict__ tau)
-{
-    __shared__ uint64_t s_c[kFinCap];
-    __shared__ uint32_t s_keep;
-    const uint32_t q = blockIdx.x;
-    const uint32_t n_raw = st[q].n_cand;
-    if (n_raw > st[q].cap || n_raw > kFinCap || n_raw < k)
-        return; // the old threshold stays; the finish flags the query if the list ends up unusable
-    uint32_t n_pad = 1;
-    while (n_pad < n_raw)
-        n_pad <<= 1;
-    uint64_t *c = cand + static_cast<size_t>(q) * cand_stride;
-    for (uint32_t i = threadIdx.x; i < n_pad; i += 1024)
-        s_c[i] = i < n_raw ? c[i] : 0ull;
-    if (threadIdx.x == 0)
-        s_keep = 0;
-    __syncthreads();
-    bitonic_desc_lds(s_c, n_pad, 1024);
-    const float fk = key_score(static_cast<uint32_t>(s_c[k - 1] >> 32));
-    const uint32_t key_lo = score_key(fk - two_eps);
-    for (uint32_t i = threadIdx.x; i < n_raw; i += 1024)
-        if (static_cast<uint32_t>(s_c[i] >> 32) >= key_lo)
-            atomicMax(&s_keep, i + 1);
-    __syncthreads();
-    const uint32_t keep = s_keep;
-    for (uint32_t i = threadIdx.x; i < keep; i += 1024)
-        c[i] = s_c[i];
-    if (threadIdx.x == 0) {
-        st[q].n_cand = keep;
-        tau[q] = key_lo == 0 ? -__builtin_inff() : key_score(key_lo);
-    }
-}
-
 __global__ __launch_bounds__(1024) void batch_emit_kernel(const uint64_t *__restrict__ cand, uint32_t cand_stride,
                                                           const SelectState *__restrict__ st, uint32_t k,
                                                           uint64_t *__restrict__ out)
@@ -1243,8 +1202,6 @@ hipError_t launch_gemm_nominate(const void *rows, uint32_t pitch16, uint32_t dim
     a.scores = scores;
     a.score_stride = score_stride;
     a.sync = nullptr;
-    a.sync_every = 4;
-    a.a_nt_shared = 0;
     const uint32_t n_rt = (row_end - row_begin + kBM - 1) / kBM;
     const uint32_t grid = ((n_rt + 7) / 8) * 8 * a.n_qblocks;
     const bool mat = scores != nullptr;
@@ -1268,33 +1225,17 @@ hipError_t launch_gemm_nominate(const void *rows, uint32_t pitch16, uint32_t dim
         const uint32_t n_units = n_rt * a.n_qblocks;
         const uint32_t g8 = std::max<uint32_t>(8, std::min<uint32_t>(persistent_grid(), (n_units + 7) / 8 * 8));
         const char *img = static_cast<const char *>(image);
-        static const bool no_sync = getenv("RLR_GEMM8_NO_SIBLING_SYNC") != nullptr;
         // sibling groups only exist on a grid of one workgroup per CU (all of them resident at once)
-        if (sync_ws && a.n_qblocks > 1 && g8 == persistent_grid() && !no_sync) {
+        if (sync_ws && a.n_qblocks > 1 && g8 == persistent_grid()) {
             const hipError_t e = hipMemsetAsync(sync_ws, 0, 256 * sizeof(uint32_t), s);
             if (e != hipSuccess)
                 return e;
             a.sync = sync_ws;
-            static const uint32_t every = getenv("RLR_GEMM8_SYNC_EVERY") ? static_cast<uint32_t>(std::max(1, atoi(getenv("RLR_GEMM8_SYNC_EVERY")))) : 4u;
-            a.sync_every = every;
         }
-        static const bool a_nt = getenv("RLR_GEMM8_A_NT") != nullptr;
-        a.a_nt_shared = a_nt ? 1u : 0u;
-        static const int var = [] {
-            const char *v = getenv("RLR_GEMM8_VARIANT");
-            return v ? static_cast<int>(strtol(v, nullptr, 0)) : 6; // same-box A/B: 6 is 2-4 % faster than 0, 1 is slower
-        }();
-#define RLR_G8(VAR)                                                                                           \
-    if (mat)                                                                                                  \
-        hipLaunchKernelGGL((gemm8_kernel<true, VAR>), dim3(g8), dim3(512), 0, s, a, img, n_rt);               \
-    else                                                                                                      \
-        hipLaunchKernelGGL((gemm8_kernel<false, VAR>), dim3(g8), dim3(512), 0, s, a, img, n_rt)
-        if (var == 0) {
-            RLR_G8(0);
-        } else {
-            RLR_G8(6);
-        }
-#undef RLR_G8
+        if (mat)
+            hipLaunchKernelGGL((gemm8_kernel<true>), dim3(g8), dim3(512), 0, s, a, img, n_rt);
+        else
+            hipLaunchKernelGGL((gemm8_kernel<false>), dim3(g8), dim3(512), 0, s, a, img, n_rt);
         return hipGetLastError();
     }
     if (dtype == RLR_F16) {
@@ -1370,11 +1311,7 @@ hipError_t launch_batch_finish(const void *rows, uint32_t pitch16, uint32_t dim,
                                SelectState *st, uint32_t k, float two_eps, uint64_t *out, uint32_t *status,
                                hipStream_t s)
 {
-    static const bool fused = [] {
-        const char *v = getenv("RLR_BATCH_FINISH_FUSED"); // A/B switch: the one-kernel finish
-        return v && v[0] == '1';
-    }();
-    if (!fused && batch_rescore_fits(pitch16, dim, dtype)) {
+    if (batch_rescore_fits(pitch16, dim, dtype)) {
         hipLaunchKernelGGL(batch_band_kernel, dim3(n_queries), dim3(1024), 0, s, cand, cand_stride, st, k, two_eps, status);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess)
@@ -1386,7 +1323,7 @@ hipError_t launch_batch_finish(const void *rows, uint32_t pitch16, uint32_t dim,
         hipLaunchKernelGGL(batch_emit_kernel, dim3(n_queries), dim3(1024), 0, s, cand, cand_stride, st, k, out);
         return hipGetLastError();
     }
-    // rows too large for the staged layout (or RLR_BATCH_FINISH_FUSED=1): the one-kernel finish
+    // rows too large for the staged layout: the one-kernel finish
     const size_t lds = static_cast<size_t>(dim) * sizeof(float);
     const float4 *r4 = static_cast<const float4 *>(rows);
     if (dtype == RLR_F16)
@@ -1395,13 +1332,6 @@ hipError_t launch_batch_finish(const void *rows, uint32_t pitch16, uint32_t dim,
     else
         hipLaunchKernelGGL(batch_finish_kernel<false>, dim3(n_queries), dim3(256), lds, s, r4, pitch16, dim, queries,
                            q_pitch, cand, cand_stride, st, k, two_eps, out, status);
-    return hipGetLastError();
-}
-
-hipError_t launch_batch_tighten(uint64_t *cand, uint32_t cand_stride, SelectState *st, uint32_t n_queries, uint32_t k,
-                                float two_eps, float *tau, hipStream_t s)
-{
-    hipLaunchKernelGGL(batch_tighten_kernel, dim3(n_queries), dim3(1024), 0, s, cand, cand_stride, st, k, two_eps, tau);
     return hipGetLastError();
 }
 

@@ -87,15 +87,6 @@ uint32_t next_pow2(uint32_t v)
     return p;
 }
 
-// The allocation behind an index's row matrix.  Where the rows land in physical memory moves the streaming rate of the scan by
-// up to 1.5 %, so the policy is explicit: see rows_alloc.
-struct RowBlock {
-    void *raw = nullptr;     // what hipFree / hipMemAddressFree takes
-    size_t raw_bytes = 0;
-    std::vector<hipMemGenericAllocationHandle_t> handles; // virtual-memory form: one physical allocation per slab
-    size_t slab = 0;
-};
-
 // how long the recent waits of one kind took (the hybrid wait sleeps through most of that before it polls)
 struct WaitEma {
     double us = 0.0;
@@ -187,7 +178,6 @@ struct rlr_index {
     uint64_t n_rows = 0;
     uint64_t cap_rows = 0;
     void *d_rows = nullptr;
-    RowBlock rows_block;      // how d_rows was obtained (rows_alloc / rows_free)
     int n_cu = 256;
     int scan_variant = 0;
     int fused_tail = -1;         // select -> re-score -> sort behind the scan in two launches (tail.hip): RLR_TAIL=1 always, 0 never
@@ -356,12 +346,8 @@ int32_t ctx_acquire(rlr_index *ix, Ctx **out)
         std::unique_lock<std::mutex> lk(ix->mu);
         for (;;) {
             if (!ix->free_ctx.empty()) {
-                static const bool rotate = getenv("RLR_CTX_ROTATE") != nullptr; // (experiment: cycle through the contexts)
-                Ctx *c = rotate ? ix->free_ctx.front() : ix->free_ctx.back();
-                if (rotate)
-                    ix->free_ctx.erase(ix->free_ctx.begin());
-                else
-                    ix->free_ctx.pop_back();
+                Ctx *c = ix->free_ctx.back(); // the most recently released one
+                ix->free_ctx.pop_back();
                 lk.unlock();
                 if (c->hist_dirty) { // a previous call failed half way: restore the zero-histogram invariant
                     (void)hipStreamSynchronize(c->stream);
@@ -449,294 +435,6 @@ int32_t check_handle(const rlr_index *ix)
     return RLR_OK;
 }
 
-// RLR_ROWS_ALLOC (experiment switch; the default is chosen in DESIGN.md section 5):
-//   "plain"          hipMalloc(bytes)
-//   "align:<MiB>"    hipMalloc(bytes + A), base rounded up to A
-//   "round:<MiB>"    hipMalloc(bytes rounded up to a multiple of A)
-//   "vmm:<MiB>"      one virtual range (hipMemAddressReserve, aligned to the slab size) backed by separate physical
-//                    allocations of <MiB> each (hipMemCreate + hipMemMap)
-void rows_free(RowBlock *b)
-{
-    if (!b->handles.empty()) {
-        (void)hipMemUnmap(b->raw, b->raw_bytes);
-        for (auto h : b->handles)
-            (void)hipMemRelease(h);
-        (void)hipMemAddressFree(b->raw, b->raw_bytes);
-    } else if (b->raw) {
-        (void)hipFree(b->raw);
-    }
-    *b = RowBlock();
-}
-
-// Time of the scan kernel this index's searches launch over the rows at `base` (a slab of a fresh allocation: the
-// content is irrelevant), best of `reps` launches after one warm-up, in ms; < 0 on error.
-float slab_scan_ms(const rlr_index *ix, const void *base, size_t bytes, float *d_scratch, hipEvent_t ev0, hipEvent_t ev1, int reps)
-{
-    ScanArgs sa;
-    sa.rows = base;
-    sa.n_rows = static_cast<uint32_t>(bytes / row_bytes(ix));
-    sa.scores = d_scratch;
-    sa.query = d_scratch + sa.n_rows; // zeros
-    sa.hist = nullptr;
-    sa.dim = ix->dim;
-    sa.pitch16 = ix->pitch16;
-    sa.dtype = ix->dtype;
-    sa.n_cu = ix->n_cu;
-    sa.variant = ix->scan_variant;
-    float best = -1.0f;
-    for (int i = 0; i <= reps; ++i) {
-        if (hipEventRecord(ev0, nullptr) != hipSuccess || launch_scan(sa, nullptr) != hipSuccess ||
-            hipEventRecord(ev1, nullptr) != hipSuccess || hipEventSynchronize(ev1) != hipSuccess)
-            return -1.0f;
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev0, ev1) != hipSuccess)
-            return -1.0f;
-        if (i > 0 && (best < 0 || ms < best))
-            best = ms;
-    }
-    return best;
-}
-
-// "select" (an experiment that did NOT become the default): the row matrix on 1 GiB physical slabs behind one virtual range,
-// the slabs chosen by measurement.  In the steady state the scan kernel streams a 1 GiB slab at 0.897-0.902 of the HBM peak or
-// at 0.883-0.890, the same slabs every time, in runs of consecutive allocations (scratch/slab_scan.py, slab_content.py) -- so:
-// map the slabs, time the scan kernel over each, swap every slab more than 0.7 % slower than the best for a fresh allocation
-// (holding on to the rejects so the driver cannot hand the same memory back).  What it buys: nothing reliable.  During the
-// first seconds after the mapping a slab's rate moves between the two grades from one measurement to the next, so the
-// selection sorts noise; and a whole 10 M-row scan runs ~2 % below the mean of its slabs whatever they are (0.867 over slabs
-// that average 0.892).  Six selected indexes in one process: 0.872 .. 0.883; six from hipMalloc: 0.869 .. 0.887
-// (scratch/alloc_spread.py).  Kept behind RLR_ROWS_ALLOC=select for whoever wants to look again; DESIGN.md section 5.
-hipError_t rows_alloc_select(const rlr_index *ix, size_t bytes, RowBlock *b, void **base)
-{
-    hipMemAllocationProp prop = {};
-    prop.type = hipMemAllocationTypePinned;
-    prop.location.type = hipMemLocationTypeDevice;
-    prop.location.id = ix->device;
-    size_t gran = 0;
-    hipError_t e = hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended);
-    if (e != hipSuccess || gran == 0)
-        return e == hipSuccess ? hipErrorNotSupported : e;
-    const size_t slab = ((1ull << 30) + gran - 1) / gran * gran;
-    const size_t n_slabs = (bytes + slab - 1) / slab;
-    const size_t total = n_slabs * slab;
-    *b = RowBlock();
-    e = hipMemAddressReserve(&b->raw, total, slab, nullptr, 0);
-    if (e != hipSuccess)
-        return e;
-    b->raw_bytes = total;
-    b->slab = slab;
-    hipMemAccessDesc acc = {};
-    acc.location = prop.location;
-    acc.flags = hipMemAccessFlagsProtReadWrite;
-    auto place = [&](size_t pos, hipMemGenericAllocationHandle_t h) -> hipError_t {
-        char *at = static_cast<char *>(b->raw) + pos * slab;
-        hipError_t pe = hipMemMap(at, slab, 0, h, 0);
-        if (pe == hipSuccess)
-            pe = hipMemSetAccess(at, slab, &acc, 1);
-        return pe;
-    };
-    size_t mapped = 0;
-    for (; mapped < n_slabs && e == hipSuccess; ++mapped) {
-        hipMemGenericAllocationHandle_t h;
-        e = hipMemCreate(&h, slab, &prop, 0);
-        if (e != hipSuccess)
-            break;
-        b->handles.push_back(h);
-        e = place(mapped, h);
-    }
-    if (e != hipSuccess) {
-        for (size_t i = 0; i < b->handles.size(); ++i) {
-            if (i < mapped)
-                (void)hipMemUnmap(static_cast<char *>(b->raw) + i * slab, slab);
-            (void)hipMemRelease(b->handles[i]);
-        }
-        (void)hipMemAddressFree(b->raw, total);
-        *b = RowBlock();
-        (void)hipGetLastError();
-        return e;
-    }
-    *base = b->raw;
-    // ---- selection (best effort: any failure from here on keeps the slabs as they are) ----
-    static const bool no_select = getenv("RLR_ROWS_NO_SELECT") != nullptr;
-    const size_t slab_rows = slab / row_bytes(ix);
-    float *d_scratch = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    std::vector<hipMemGenericAllocationHandle_t> rejects;
-    if (!no_select && n_slabs >= 2 && slab_rows >= 4096 &&
-        rlr::dev_malloc(reinterpret_cast<void **>(&d_scratch), (slab_rows + ix->q_pitch + 64) * sizeof(float)) == hipSuccess &&
-        hipMemset(d_scratch, 0, (slab_rows + ix->q_pitch + 64) * sizeof(float)) == hipSuccess &&
-        hipStreamSynchronize(nullptr) == hipSuccess && hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess) {
-        std::vector<float> ms(n_slabs, -1.0f);
-        float best = -1.0f;
-        bool ok = true;
-        for (size_t i = 0; i < n_slabs && ok; ++i) {
-            ms[i] = slab_scan_ms(ix, static_cast<char *>(b->raw) + i * slab, slab, d_scratch, ev0, ev1, 3);
-            ok = ms[i] > 0;
-            if (ok && (best < 0 || ms[i] < best))
-                best = ms[i];
-        }
-        size_t budget = std::min<size_t>(2 * n_slabs, 96); // fresh slabs to try in all
-        uint32_t swapped = 0, tried = 0;
-        for (size_t i = 0; i < n_slabs && ok && budget > 0; ++i) {
-            for (int attempt = 0; attempt < 4 && ms[i] > best * 1.007f && budget > 0; ++attempt) {
-                size_t free_b = 0, total_b = 0;
-                if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < 3 * slab)
-                    budget = 1; // (this is the last try)
-                hipMemGenericAllocationHandle_t h;
-                if (hipMemCreate(&h, slab, &prop, 0) != hipSuccess) {
-                    (void)hipGetLastError();
-                    budget = 0;
-                    break;
-                }
-                budget--;
-                tried++;
-                char *at = static_cast<char *>(b->raw) + i * slab;
-                if (hipMemUnmap(at, slab) != hipSuccess || place(i, h) != hipSuccess) {
-                    // (cannot happen on a healthy runtime; the position must not stay unmapped)
-                    (void)hipGetLastError();
-                    (void)hipMemRelease(h);
-                    ok = place(i, b->handles[i]) == hipSuccess;
-                    budget = 0;
-                    break;
-                }
-                const float t = slab_scan_ms(ix, at, slab, d_scratch, ev0, ev1, 3);
-                if (t > 0 && t < ms[i]) { // better than what was here: keep it, hold the old one until the end
-                    rejects.push_back(b->handles[i]);
-                    b->handles[i] = h;
-                    ms[i] = t;
-                    swapped++;
-                    if (t < best)
-                        best = t;
-                } else { // no better: put the old one back, hold the new one until the end
-                    (void)hipMemUnmap(at, slab);
-                    ok = place(i, b->handles[i]) == hipSuccess;
-                    rejects.push_back(h);
-                }
-            }
-        }
-        if (getenv("RLR_ROWS_ALLOC_LOG")) {
-            float worst = 0;
-            for (float t : ms)
-                worst = std::max(worst, t);
-            fprintf(stderr, "rlr rows: %zu slabs of %zu MiB, %u fresh slabs tried, %u swapped in; slab scan best %.4f ms worst %.4f ms\n",
-                    n_slabs, slab >> 20, tried, swapped, best, worst);
-        }
-        if (!ok) { // a position could not be re-mapped: give up on this block altogether
-            for (auto h : rejects)
-                (void)hipMemRelease(h);
-            if (ev0) (void)hipEventDestroy(ev0);
-            if (ev1) (void)hipEventDestroy(ev1);
-            (void)hipFree(d_scratch);
-            rows_free(b);
-            return hipErrorUnknown;
-        }
-    }
-    for (auto h : rejects)
-        (void)hipMemRelease(h);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (d_scratch) (void)hipFree(d_scratch);
-    (void)hipGetLastError();
-    if (rlr::poison_mode()) {
-        (void)hipMemset(b->raw, 0xFF, total);
-        (void)hipDeviceSynchronize();
-    }
-    return hipSuccess;
-}
-
-hipError_t rows_alloc(const rlr_index *ix, size_t bytes, RowBlock *b, void **base)
-{
-    const int device = ix->device;
-    static const std::string policy = [] {
-        const char *v = getenv("RLR_ROWS_ALLOC");
-        return std::string(v ? v : "plain");
-    }();
-    const char *v = getenv("RLR_ROWS_ALLOC_NOW"); // (re-read per call: the placement experiment creates several indexes in one process)
-    const std::string pol = v ? std::string(v) : policy;
-    const size_t colon = pol.find(':');
-    const std::string kind = pol.substr(0, colon);
-    const size_t mib = colon == std::string::npos ? 0 : static_cast<size_t>(strtoull(pol.c_str() + colon + 1, nullptr, 10));
-    const size_t A = std::max<size_t>(mib, 2) << 20;
-    *b = RowBlock();
-    hipError_t e = hipSuccess;
-    // ("auto" = "select" from 2 GiB: NOT the default -- see the note above rows_alloc_select)
-    if (kind == "select" || (kind == "auto" && bytes >= (2ull << 30))) {
-        e = rows_alloc_select(ix, bytes, b, base);
-        if (e == hipSuccess)
-            return e;
-        (void)hipGetLastError();
-        *b = RowBlock(); // (no virtual-memory API, or out of memory for the slab rounding: the plain allocation below)
-    }
-    if (kind == "align") {
-        e = rlr::dev_malloc(&b->raw, bytes + A);
-        if (e != hipSuccess)
-            return e;
-        b->raw_bytes = bytes + A;
-        *base = reinterpret_cast<void *>((reinterpret_cast<uintptr_t>(b->raw) + A - 1) / A * A);
-        return hipSuccess;
-    }
-    if (kind == "round") {
-        const size_t r = (bytes + A - 1) / A * A;
-        e = rlr::dev_malloc(&b->raw, r);
-        b->raw_bytes = r;
-        *base = b->raw;
-        return e;
-    }
-    if (kind == "vmm") {
-        hipMemAllocationProp prop = {};
-        prop.type = hipMemAllocationTypePinned;
-        prop.location.type = hipMemLocationTypeDevice;
-        prop.location.id = device;
-        size_t gran = 0;
-        e = hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended);
-        if (e != hipSuccess)
-            return e;
-        const size_t slab = (A + gran - 1) / gran * gran;
-        const size_t total = (bytes + slab - 1) / slab * slab;
-        e = hipMemAddressReserve(&b->raw, total, slab, nullptr, 0);
-        if (e != hipSuccess)
-            return e;
-        b->raw_bytes = total;
-        b->slab = slab;
-        for (size_t off = 0; off < total && e == hipSuccess; off += slab) {
-            hipMemGenericAllocationHandle_t h;
-            e = hipMemCreate(&h, slab, &prop, 0);
-            if (e != hipSuccess)
-                break;
-            b->handles.push_back(h);
-            e = hipMemMap(static_cast<char *>(b->raw) + off, slab, 0, h, 0);
-        }
-        if (e == hipSuccess) {
-            hipMemAccessDesc acc = {};
-            acc.location = prop.location;
-            acc.flags = hipMemAccessFlagsProtReadWrite;
-            e = hipMemSetAccess(b->raw, total, &acc, 1);
-        }
-        if (e != hipSuccess) {
-            // (partial mappings: unmap what was mapped, release, free the range)
-            for (size_t i = 0; i < b->handles.size(); ++i) {
-                (void)hipMemUnmap(static_cast<char *>(b->raw) + i * slab, slab);
-                (void)hipMemRelease(b->handles[i]);
-            }
-            b->handles.clear();
-            (void)hipMemAddressFree(b->raw, total);
-            *b = RowBlock();
-            (void)hipGetLastError();
-            return e;
-        }
-        if (rlr::poison_mode()) {
-            (void)hipMemset(b->raw, 0xFF, total);
-            (void)hipDeviceSynchronize();
-        }
-        *base = b->raw;
-        return hipSuccess;
-    }
-    e = rlr::dev_malloc(&b->raw, bytes);
-    b->raw_bytes = bytes;
-    *base = b->raw;
-    return e;
-}
-
 int32_t ensure_rows(rlr_index *ix, uint64_t want_rows)
 {
     if (want_rows <= ix->cap_rows)
@@ -746,11 +444,10 @@ int32_t ensure_rows(rlr_index *ix, uint64_t want_rows)
     uint64_t cap = std::max<uint64_t>(want_rows, ix->cap_rows + ix->cap_rows / 2);
     cap = std::max<uint64_t>(cap, 1024);
     void *n = nullptr;
-    RowBlock nb;
-    hipError_t e = rows_alloc(ix, cap * row_bytes(ix), &nb, &n);
+    hipError_t e = rlr::dev_malloc(&n, cap * row_bytes(ix));
     if (e != hipSuccess && cap > want_rows) {
         cap = want_rows;
-        e = rows_alloc(ix, cap * row_bytes(ix), &nb, &n);
+        e = rlr::dev_malloc(&n, cap * row_bytes(ix));
     }
     if (e != hipSuccess)
         return fail(RLR_E_OOM, "allocation of %llu rows x %zu B failed: %s",
@@ -760,17 +457,14 @@ int32_t ensure_rows(rlr_index *ix, uint64_t want_rows)
         if (ce == hipSuccess)
             ce = hipStreamSynchronize(nullptr); // a device-to-device copy may return before it has run
         if (ce != hipSuccess) {
-            rows_free(&nb);
+            (void)hipFree(n);
             return fail(RLR_E_HIP, "moving the rows into the larger allocation failed: %s", hipGetErrorString(ce));
         }
     }
-    rows_free(&ix->rows_block);
-    ix->rows_block = std::move(nb);
+    if (ix->d_rows)
+        (void)hipFree(ix->d_rows);
     ix->d_rows = n;
     ix->cap_rows = cap;
-    if (getenv("RLR_ROWS_ALLOC_LOG"))
-        fprintf(stderr, "rlr rows: base %p bytes %zu (raw %p, %zu slabs of %zu)\n", n, static_cast<size_t>(cap * row_bytes(ix)),
-                ix->rows_block.raw, ix->rows_block.handles.size(), ix->rows_block.slab);
     return RLR_OK;
 }
 
@@ -1073,8 +767,7 @@ hipError_t stage_queries_for_scans(const rlr_index *ix, Ctx *c, const float *h_q
 
 hipError_t upload_queries(Ctx *c, const float *h_q, size_t q_bytes, hipStream_t s)
 {
-    static const bool by_copy = getenv("RLR_QUERY_MEMCPY") != nullptr; // (A/B)
-    if (by_copy || q_bytes > (64u << 10) || (q_bytes & 15) || (reinterpret_cast<uintptr_t>(h_q) & 15))
+    if (q_bytes > (64u << 10) || (q_bytes & 15) || (reinterpret_cast<uintptr_t>(h_q) & 15))
         return hipMemcpyAsync(c->d_query, h_q, q_bytes, hipMemcpyHostToDevice, s);
     const uint32_t n16 = static_cast<uint32_t>(q_bytes / 16);
     hipLaunchKernelGGL(rlr::stage_query_kernel, dim3(std::min<uint32_t>((n16 + 255) / 256, 8)), dim3(256), 0, s,
@@ -1723,15 +1416,6 @@ __global__ __launch_bounds__(1024) void hybrid_pool_batch_kernel(const uint64_t 
         sizes[q] = info[2 * q];
 }
 
-// the first info[0] candidates in their sorted order (no diversification) -> pinned host memory: hybrid_emit_body, below
-// hybrid_pool_kernel's helpers; this launch only exists for RLR_HYBRID_EMIT=split (the blend kernel emits by itself)
-__global__ __launch_bounds__(256) void hybrid_emit_kernel(const uint32_t *__restrict__ list, const float *__restrict__ comb,
-                                                          const float *__restrict__ cosv, const float *__restrict__ lexv,
-                                                          const uint32_t *__restrict__ info, uint32_t k_cap,
-                                                          uint32_t *__restrict__ h_out)
-{
-    hybrid_emit_body(list, comb, cosv, lexv, info[1] ? 0u : min(info[0], k_cap), info[1], k_cap, h_out);
-}
 } // namespace rlr
 
 namespace {
@@ -1850,10 +1534,6 @@ hipError_t enqueue_query_scan(rlr_index *ix, Ctx *c, uint32_t qi, bool timed)
     sa.n_cu = ix->n_cu;
     sa.variant = ix->scan_variant;
     sa.query_host = c->h_q_kq ? c->h_q_kq + static_cast<size_t>(qi) * ix->q_pitch : nullptr;
-    static const bool variant_dyn = getenv("RLR_SCAN_VARIANT_DYN") != nullptr; // (experiments: the variant re-read per launch)
-    if (variant_dyn)
-        if (const char *v = getenv("RLR_SCAN_VARIANT"))
-            sa.variant = static_cast<int>(strtol(v, nullptr, 0));
     const bool q8 = scan_over_q8(ix);
     const bool img = !q8 && scan_over_image(ix, c);
     if (q8)
@@ -1993,15 +1673,14 @@ int32_t big_query(rlr_index *ix, Ctx *c, uint32_t qi, const SearchPlan &p, uint3
     h.cap = cap;
     RLR_HIP(hipMemcpyAsync(st, &h, sizeof(h), hipMemcpyHostToDevice, s));
     RLR_HIP(launch_collect(c->d_scores, n, st, c->d_cand, ix->n_cu, s));
-    static const bool old_finish = getenv("RLR_BIG_QUERY_SORT") != nullptr; // A/B and test switch: the global bitonic sort
     hipError_t e = hipSuccess;
-    const bool second_level = !old_finish && p.k <= kLdsSortCap;
+    const bool second_level = p.k <= kLdsSortCap;
     // (the staged kernel writes the n_cand keys only; the global sort below needs the zero padding up to `cap` that the
     // one-lane kernel writes)
     const bool staged = second_level && launch_rescore_staged(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, dq, c->d_cand, st,
                                                               c->d_packed, cap, nullptr, s, &e);
     RLR_HIP(e);
-    if (!staged) // rows too large for the staged layout, k beyond the one-workgroup finish, or the switch
+    if (!staged) // rows too large for the staged layout, or k beyond the one-workgroup finish
         RLR_HIP(launch_rescore(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, dq, c->d_cand, st, c->d_packed, cap, s));
     if (second_level) {
         // second level: the exact keys are selected and sorted by one workgroup
@@ -2017,12 +1696,6 @@ int32_t big_query(rlr_index *ix, Ctx *c, uint32_t qi, const SearchPlan &p, uint3
 
 // ---- batched (matrix-core) pipeline ---------------------------------------------------
 constexpr uint32_t kBatchMaxQueries = 1024; // queries per batched pipeline run (bounds the workspace)
-
-bool env_is_one(const char *name)
-{
-    const char *v = getenv(name);
-    return v && v[0] == '1';
-}
 
 // 2..8 queries over f32 rows of these shapes share one VALU scan (scan_multi_kernel) in run_batched.  `coalesced`: the
 // queries are a group of concurrent single-query calls (rlr_index_set_coalescing) -- those also share one pass over
@@ -2040,7 +1713,7 @@ bool batch_eligible(const rlr_index *ix, uint32_t nq, uint32_t k, bool f16_ok = 
     if (nq < 2 || ix->dim % 128 != 0 || ix->n_rows < 4096 || k * 8 > batch_finish_capacity())
         return false;
     // operands beyond binary16 range: only the f32 shared scan may nominate
-    if (!f16_ok && !(batch_multi_shape(ix, nq, coalesced) && !(ix->image_enabled && ix->d_image) && !env_is_one("RLR_NO_MULTI_SCAN")))
+    if (!f16_ok && !(batch_multi_shape(ix, nq, coalesced) && !(ix->image_enabled && ix->d_image)))
         return false;
     if (ix->batch_min > 0)
         return nq >= ix->batch_min;
@@ -2076,24 +1749,17 @@ int32_t run_batched(rlr_index *ix, Ctx *c, uint32_t q0, uint32_t nq, const Searc
     const uint32_t n_qblocks = (nq + 255) / 256;
     // 2..8 queries over f32 rows: one VALU pass over the rows for all of them (scan_multi_kernel) instead of the
     // matrix-core pipeline -- about the cost of a single scan, scores in wavefront order (the tight f32 band)
-    const bool use_multi = batch_multi_shape(ix, nq, coalesced) && !(ix->image_enabled && ix->d_image) && !env_is_one("RLR_NO_MULTI_SCAN");
+    const bool use_multi = batch_multi_shape(ix, nq, coalesced) && !(ix->image_enabled && ix->d_image);
     const float eps_nom = use_multi ? 0.5f * p.two_eps : nomination_eps(ix->dim, ix->dtype, p.scale, p.norm_sum);
     const float two_eps = 2.0f * eps_nom;
     // Sample rows [0, S): the floor for the rest of the corpus is the sample's rank-th score, and S is large enough that
     // the expected number of later rows above it (rank * N / S) stays well inside the per-query candidate capacity.
     // rank = k needs no check afterwards (k sample rows sit at or above the floor) but a sample of k * N * 2.5 / capacity
-    // rows -- so large that a quarter of it used to be materialised and the rest run as a separate "bootstrap" launch with
-    // a per-query sort to tighten the floor (0.2 ms of a 4.4 ms batch of 256, 1.2 of 13.9 at 1024 x 308).  rank = k / 4
-    // gives the same floor from the quarter alone: the count of rows above it spreads more (relative deviation
-    // 1 / sqrt(rank): 3.3 k +- 0.65 k at rank 25 against a capacity of 8192), and the finish hands a query back when its
-    // k-th nominated score lies under the floor's rank (batch_band_kernel; essentially never: it takes fewer than k rows
-    // where ~3 k are expected).  RLR_BATCH_RANK_DIV=1 restores rank = k with the bootstrap.
-    static const uint32_t rank_div = [] {
-        const char *v = getenv("RLR_BATCH_RANK_DIV");
-        const long d = v ? strtol(v, nullptr, 10) : 4;
-        return static_cast<uint32_t>(d >= 1 && d <= 64 ? d : 4);
-    }();
-    uint32_t rank = std::max<uint32_t>(std::min<uint32_t>(p.k, 16), p.k / rank_div);
+    // rows, four times what rank = k / 4 has to materialise and radix-select per query.  With rank = k / 4 the count of
+    // rows above the floor spreads more (relative deviation 1 / sqrt(rank): 3.3 k +- 0.65 k at rank 25 against a capacity
+    // of 8192), and the finish hands a query back when its k-th nominated score lies under the floor's rank
+    // (batch_band_kernel; essentially never: it takes fewer than k rows where ~3 k are expected).
+    uint32_t rank = std::max<uint32_t>(std::min<uint32_t>(p.k, 16), p.k / 4);
     uint64_t S = (static_cast<uint64_t>(rank) * n * 5 / 2 + fin_cap - 1) / fin_cap;
     S = std::max<uint64_t>(S, std::min<uint64_t>(n, 65536));
     S = (S + 255) / 256 * 256;
@@ -2111,16 +1777,6 @@ int32_t run_batched(rlr_index *ix, Ctx *c, uint32_t q0, uint32_t nq, const Searc
         if (forced) // tests: a rank low enough that queries ARE handed back (too few candidates, or a band below the floor)
             rank = std::min<uint32_t>(p.k, forced);
     }
-    // Bootstrap: materialising and radix-selecting S rows per query costs 4 passes over nq x S floats
-    // (2.4 GB for 1024 queries x 587 k rows).  When S is large, only a quarter of it (S1) goes that way;
-    // its threshold filters the rows [S1, S) in the GEMM epilogue (about 3 k extra candidates), one sort
-    // per query tightens the threshold to the k-th score of all S rows, and the main pass starts from the
-    // same threshold the full-size sample would have given.
-    const uint64_t S2 = S;
-    uint64_t S1 = std::max<uint64_t>(65536, (S2 / 4 + 255) / 256 * 256);
-    const bool bootstrap = rank_div == 1 && S2 < n && S1 * 2 <= S2 && !getenv("RLR_BATCH_NO_BOOTSTRAP");
-    if (bootstrap)
-        S = S1;
     const uint64_t s_stride = (S + 3) / 4 * 4;
 
     // workspace
@@ -2201,15 +1857,7 @@ int32_t run_batched(rlr_index *ix, Ctx *c, uint32_t q0, uint32_t nq, const Searc
     RLR_HIP(launch_batch_select(c->d_sample, static_cast<uint32_t>(S), s_stride, nq, c->d_bhist, c->d_bstate, two_eps,
                                 c->d_tau, c->d_bcand, fin_cap, ix->n_cu, s));
     if (timed) RLR_HIP(hipEventRecord(c->bev[2], s));
-    uint32_t rest_begin = static_cast<uint32_t>(S);
-    if (bootstrap) {
-        // 2b. rows [S1, S2) against the small sample's threshold, then tighten it
-        RLR_HIP(launch_gemm_nominate(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, static_cast<uint32_t>(S1),
-                                     static_cast<uint32_t>(S2), c->d_qfrag, nq, c->d_tau, c->d_bcand, fin_cap, c->d_bstate,
-                                     nullptr, 0, image, s, c->d_gsync));
-        RLR_HIP(launch_batch_tighten(c->d_bcand, fin_cap, c->d_bstate, nq, p.k, two_eps, c->d_tau, s));
-        rest_begin = static_cast<uint32_t>(S2);
-    }
+    const uint32_t rest_begin = static_cast<uint32_t>(S);
     // 3. the rest of the corpus, filtered in the GEMM epilogue
     if (timed) RLR_HIP(hipEventRecord(c->bev[4], s));
     RLR_HIP(launch_gemm_nominate(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, rest_begin, n, c->d_qfrag, nq,
@@ -2509,7 +2157,7 @@ constexpr int kCoalesceInflight = 1; // coalescer pipelines per index (DESIGN.md
 // Would two concurrent single-query calls with this k share a pass?  (Everything else runs today's path at once.)
 bool coalesce_eligible(const rlr_index *ix, uint32_t k)
 {
-    return !ix->image_enabled && !ix->q8_enabled && batch_multi_shape(ix, 2, true) && !env_is_one("RLR_NO_MULTI_SCAN") &&
+    return !ix->image_enabled && !ix->q8_enabled && batch_multi_shape(ix, 2, true) &&
            batch_eligible(ix, 2, std::min<uint64_t>(k, ix->n_rows), true, true);
 }
 
@@ -2757,7 +2405,7 @@ int32_t rlr_index_destroy(rlr_index *ix)
     (void)hipDeviceSynchronize();
     for (Ctx *c : ix->free_ctx)
         ctx_free(c);
-    rows_free(&ix->rows_block);
+    if (ix->d_rows) (void)hipFree(ix->d_rows);
     ix->d_rows = nullptr;
     if (ix->d_q8) (void)hipFree(ix->d_q8);
     if (ix->d_q8_scale) (void)hipFree(ix->d_q8_scale);
@@ -3400,8 +3048,7 @@ int32_t rlr_search_diverse(rlr_index *ix, const float *query, uint32_t pool, uin
     const bool timed = ix->profiling;
     RLR_HIP(stage_queries_for_scans(ix, c, h_q, q_bytes, s));
     uint64_t *d_meta = c->d_out + fetch;
-    static const bool two_launches = getenv("RLR_POOL_AFTER_SORT") != nullptr; // A/B: sort_emit, then the pool from its output
-    const bool from_candidates = fetch <= 512 && !two_launches;                // (the band of a larger fetch rarely fits 1024)
+    const bool from_candidates = fetch <= 512; // (the band of a larger fetch rarely fits 1024)
     const PoolArgs pa{fetch, need, n, w_embedding, w_lexical, c->d_list, d_comb, d_cos, d_info};
     bool pool_done = false; // (the fused tail's finish builds the pool itself: one launch and ~13 us of config 2's chain less)
     RLR_HIP(enqueue_query(ix, c, 0, p, c->d_out, d_meta, timed, /*emit=*/!from_candidates, from_candidates ? &pa : nullptr,
@@ -3657,8 +3304,7 @@ static int32_t hybrid_finish_impl(HybridTicket *ticket, const HybridLexSrc &src,
     }
     RLR_HIP(launch_score_rows(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_query, d_lrow, n_lex, d_lcos, s,
                               src.dev ? &d_hdr->n_lex : nullptr, n));
-    static const bool emit_split = getenv("RLR_HYBRID_EMIT") && !strcmp(getenv("RLR_HYBRID_EMIT"), "split"); // (A/B: its own launch)
-    const bool pool_emits = !t->diversify && !emit_split;
+    const bool pool_emits = !t->diversify; // (without diversification the blend kernel emits by itself)
     hipLaunchKernelGGL(hybrid_pool_kernel, dim3(1), dim3(1024), 0, s, c->d_out, t->fetch, t->need, n, t->w_e, t->w_l, d_lrow,
                        d_lscore, d_lcos, d_hdr, d_cand, c->d_list, d_comb, d_cos, d_lexv, d_info, k_cap,
                        pool_emits ? h_out : static_cast<uint32_t *>(nullptr));
@@ -3674,9 +3320,6 @@ static int32_t hybrid_finish_impl(HybridTicket *ticket, const HybridLexSrc &src,
         emit.k_cap = k_cap;
         emit.h_out = h_out;
         RLR_HIP(launch_mmr_greedy(d_gram, d_comb, P, t->k, t->lambda, d_order, d_mmr, d_nsel, d_info, 1, s, &emit));
-    } else if (!pool_emits) {
-        hipLaunchKernelGGL(hybrid_emit_kernel, dim3(1), dim3(256), 0, s, c->d_list, d_comb, d_cos, d_lexv, d_info, k_cap, h_out);
-        RLR_HIP(hipGetLastError());
     }
     if (t->timed) RLR_HIP(hipEventRecord(c->bev[1], s));
     if (t->timed) {
@@ -4137,38 +3780,27 @@ int32_t rlr_index_probe_bandwidth(rlr_index *ix, int32_t mode, uint32_t reps, do
     };
     if (mode == 0) {
         RLR_HIP(rlr::dev_malloc(&scratch, static_cast<size_t>(ix->n_cu) * 8 * 256 * sizeof(float)));
-        // (experiments: RLR_PROBE_SHAPE pins the launch shape, RLR_PROBE_OFF_MIB / RLR_PROBE_LEN_MIB a sub-range of the rows)
-        const char *es = getenv("RLR_PROBE_SHAPE"), *eo = getenv("RLR_PROBE_OFF_MIB"), *el = getenv("RLR_PROBE_LEN_MIB");
-        size_t off = eo ? static_cast<size_t>(strtoull(eo, nullptr, 10)) << 20 : 0;
-        size_t len = el ? static_cast<size_t>(strtoull(el, nullptr, 10)) << 20 : bytes;
-        off = std::min(off, bytes - (1u << 20));
-        len = std::min(len, bytes - off);
-        moved = len / 1024 * 1024;
-        const char *base = static_cast<const char *>(ix->d_rows) + off;
-        for (int shape = es ? atoi(es) : 0; shape < (es ? atoi(es) + 1 : 3) && st == RLR_OK; ++shape)
-            st = timed([&] { return launch_probe_read(base, len, static_cast<float *>(scratch), ix->n_cu, shape, s); });
+        moved = bytes / 1024 * 1024;
+        for (int shape = 0; shape < 3 && st == RLR_OK; ++shape)
+            st = timed([&] { return launch_probe_read(ix->d_rows, bytes, static_cast<float *>(scratch), ix->n_cu, shape, s); });
     } else if (mode >= 2) {
         // diagnostic: the scan kernel itself over the rows with a zero query, scores into a scratch array, without (2) or
         // with (3) the digit-1 histogram it accumulates in LDS and flushes with global atomics
         const size_t sc_bytes = (static_cast<size_t>(ix->n_rows) + 2 * kHistBins + ix->q_pitch) * sizeof(float);
         RLR_HIP(rlr::dev_malloc(&scratch, sc_bytes));
         RLR_HIP(hipMemsetAsync(scratch, 0, sc_bytes, s));
-        const char *eo = getenv("RLR_PROBE_OFF_MIB"), *el = getenv("RLR_PROBE_LEN_MIB"); // (experiments: a sub-range of the rows)
-        const uint64_t row_lo = eo ? std::min<uint64_t>((strtoull(eo, nullptr, 10) << 20) / row_bytes(ix), ix->n_rows - 1) : 0;
-        const uint64_t row_n = el ? std::min<uint64_t>((strtoull(el, nullptr, 10) << 20) / row_bytes(ix), ix->n_rows - row_lo)
-                                  : ix->n_rows - row_lo;
         ScanArgs sa;
-        sa.rows = static_cast<const char *>(ix->d_rows) + row_lo * row_bytes(ix);
+        sa.rows = ix->d_rows;
         sa.scores = static_cast<float *>(scratch);
         sa.hist = mode == 3 ? reinterpret_cast<uint32_t *>(sa.scores + ix->n_rows) : nullptr;
         sa.query = sa.scores + ix->n_rows + 2 * kHistBins;
-        sa.n_rows = static_cast<uint32_t>(row_n);
+        sa.n_rows = static_cast<uint32_t>(ix->n_rows);
         sa.dim = ix->dim;
         sa.pitch16 = ix->pitch16;
         sa.dtype = ix->dtype;
         sa.n_cu = ix->n_cu;
         sa.variant = ix->scan_variant;
-        moved = static_cast<size_t>(row_n) * ix->dim * (ix->dtype == RLR_F16 ? 2 : 4);
+        moved = static_cast<size_t>(ix->n_rows) * ix->dim * (ix->dtype == RLR_F16 ? 2 : 4);
         st = timed([&] { return launch_scan(sa, s); });
     } else {
         const size_t half = std::min<size_t>(bytes / 2, 4ull << 30) & ~static_cast<size_t>(255);

@@ -10,8 +10,7 @@
 //                      posting adds its BM25 contribution to its row's accumulator in query-term order (the f32 sum
 //                      order of the reference -- deterministic), the accumulators of a workgroup's rows in LDS; rows
 //                      whose sum becomes positive are appended to a compact "touched" list.  (bm25_terms_kernel: the
-//                      same with the accumulators in device memory, for indexes beyond a few million rows;
-//                      bm25_term_kernel: one launch per term, an A/B switch);
+//                      same with the accumulators in device memory, for indexes beyond a few million rows);
 //   <= 8192 postings   lex_sort_kernel: packed (score, row) keys sorted in LDS;
 //   more, limit <= 4096  sampled selection, 3 launches: lex_sample_kernel (threshold key from a strided sample),
 //                      lex_filter_kernel (one pass, ~1.5 limit candidates), lex_final_kernel (exact limit-th key
@@ -95,37 +94,6 @@ __device__ inline uint32_t wave_append_slot(bool flag, uint32_t *counter)
         base = atomicAdd(counter, static_cast<uint32_t>(__popcll(mask)));
     base = __shfl(base, leader);
     return base + static_cast<uint32_t>(__popcll(mask & ((1ull << lane) - 1ull)));
-}
-
-// LexicalIndex::score inner loop, rag_engine.rs:2200-2213, for the postings of one term
-__global__ __launch_bounds__(256) void bm25_term_kernel(const uint32_t *__restrict__ post_row,
-                                                        const uint32_t *__restrict__ post_tf, uint32_t cnt,
-                                                        const uint32_t *__restrict__ doc_len, float avg, float idf,
-                                                        float *__restrict__ scores, uint32_t *__restrict__ touched,
-                                                        LexControl *__restrict__ ctl)
-{
-    const uint32_t stride = gridDim.x * 256;
-    for (uint32_t i0 = blockIdx.x * 256; i0 < cnt; i0 += stride) {
-        const uint32_t i = i0 + threadIdx.x;
-        bool first_touch = false;
-        uint32_t row = 0;
-        if (i < cnt) {
-            row = post_row[i];
-            const float dl = static_cast<float>(doc_len[row]);
-            const float tf = static_cast<float>(post_tf[i]);
-            const float denom = tf + kK1 * ((1.0f - kB) + kB * (dl / avg));
-            if (dl != 0.0f && denom != 0.0f) {
-                const float sc = idf * (tf * (kK1 + 1.0f)) / denom;
-                const float old = scores[row];
-                const float now = old + sc; // `*scores.entry(doc).or_insert(0.0) += score`
-                scores[row] = now;
-                first_touch = old == 0.0f && now > 0.0f;
-            }
-        }
-        const uint32_t slot = wave_append_slot(first_touch, &ctl->n_touched);
-        if (first_touch)
-            touched[slot] = row;
-    }
 }
 
 // bitonic sort (descending) of n_pad keys in LDS, n_pad a power of two <= kMaxLimit
@@ -1741,7 +1709,6 @@ int32_t lexical_enqueue(rlr_lexical *lx, const char *query_tokens, size_t len, u
     LexControl *ctl_next = ws->d_ctl + (ws->ctl_cur ^ 1u);
     ws->ctl_cur ^= 1u;
     const uint32_t max_blocks = static_cast<uint32_t>(lx->n_cu) * 8;
-    static const bool per_term = getenv("RLR_LEX_PER_TERM") != nullptr; // (A/B switch: one launch per term and segment)
     // workgroups of the row-partitioned kernel: one per CU while each still owns a few hundred rows
     const uint32_t row_wgs = std::max<uint32_t>(1u, std::min<uint32_t>(static_cast<uint32_t>(lx->n_cu), static_cast<uint32_t>(n_rows / 256)));
     TermBatch tb{};
@@ -1769,29 +1736,14 @@ int32_t lexical_enqueue(rlr_lexical *lx, const char *query_tokens, size_t len, u
         // the term's postings in the main segment, then in the appended one (a row is in exactly one of them)
         const uint32_t cnt_m = t < lx->main_df.size() ? lx->main_df[t] : 0u;
         const uint32_t cnt_d = lx->dterm_off.empty() ? 0u : static_cast<uint32_t>(lx->dterm_off[t + 1] - lx->dterm_off[t]);
-        if (!per_term) {
-            const uint32_t at = tb.n_terms++;
-            tb.cnt_m[at] = cnt_m;
-            tb.off_m[at] = cnt_m ? lx->term_off[t] : 0;
-            tb.cnt_d[at] = cnt_d;
-            tb.off_d[at] = cnt_d ? lx->dterm_off[t] : 0;
-            tb.idf[at] = idf;
-            if (tb.n_terms == kTermsPerLaunch)
-                flush_terms(); // (more than 16 terms: the next launch continues in term order)
-            continue;
-        }
-        if (cnt_m) {
-            const uint64_t off = lx->term_off[t];
-            const uint32_t blocks = std::min<uint32_t>((cnt_m + 255) / 256, max_blocks);
-            hipLaunchKernelGGL(bm25_term_kernel, dim3(blocks), dim3(256), 0, s, lx->d_post_row + off, lx->d_post_tf + off, cnt_m,
-                               lx->d_doc_len, avg, idf, ws->d_scores, ws->d_touched, ctl);
-        }
-        if (cnt_d) {
-            const uint64_t off = lx->dterm_off[t];
-            const uint32_t blocks = std::min<uint32_t>((cnt_d + 255) / 256, max_blocks);
-            hipLaunchKernelGGL(bm25_term_kernel, dim3(blocks), dim3(256), 0, s, lx->d_dpost_row + off, lx->d_dpost_tf + off,
-                               cnt_d, lx->d_doc_len, avg, idf, ws->d_scores, ws->d_touched, ctl);
-        }
+        const uint32_t at = tb.n_terms++;
+        tb.cnt_m[at] = cnt_m;
+        tb.off_m[at] = cnt_m ? lx->term_off[t] : 0;
+        tb.cnt_d[at] = cnt_d;
+        tb.off_d[at] = cnt_d ? lx->dterm_off[t] : 0;
+        tb.idf[at] = idf;
+        if (tb.n_terms == kTermsPerLaunch)
+            flush_terms(); // (more than 16 terms: the next launch continues in term order)
     }
     flush_terms();
     LEX_HIP(hipGetLastError());

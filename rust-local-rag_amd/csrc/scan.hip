@@ -602,15 +602,6 @@ ScanPlan plan_scan(const ScanArgs &a)
     return p;
 }
 
-bool kq_enabled()
-{
-    static const bool on = [] {
-        const char *v = getenv("RLR_SCAN_KQ"); // the query in the kernel arguments (ScanArgs::query_host); "0" turns it off
-        return !(v && v[0] == '0');
-    }();
-    return on;
-}
-
 template <int CH>
 hipError_t launch_fixed_kq(const ScanArgs &a, const ScanPlan &p, hipStream_t s)
 {
@@ -634,7 +625,7 @@ template <int CH, bool F16>
 hipError_t launch_fixed(const ScanArgs &a, const ScanPlan &p, hipStream_t s)
 {
     if constexpr (!F16 && CH <= 3) {
-        if (a.query_host && p.nt && kq_enabled())
+        if (a.query_host && p.nt)
             return launch_fixed_kq<CH>(a, p, s);
     }
     const float4 *rows = static_cast<const float4 *>(a.rows);
@@ -727,7 +718,7 @@ bool launch_packed(const ScanArgs &a, const ScanPlan &p, hipStream_t s, hipError
 bool launch_scan_takes_host_query(const ScanArgs &a)
 {
     int ch = 0;
-    if (!a.query_host || a.n_rows == 0 || a.dtype != RLR_F32 || !fixed_shape(a, &ch) || ch > 3 || !kq_enabled())
+    if (!a.query_host || a.n_rows == 0 || a.dtype != RLR_F32 || !fixed_shape(a, &ch) || ch > 3)
         return false;
     return plan_scan(a).nt;
 }

@@ -440,9 +440,8 @@ hipError_t launch_batch_select(const float *scores, uint32_t n, size_t score_str
                                hipStream_t s)
 {
     // one workgroup per query while the queries alone fill the chip and a sample stays L2-sized: three passes over its own
-    // 4 n bytes with every counter in LDS (RLR_BATCH_SELECT_SPLIT=1: the five-launch form)
-    static const bool split = getenv("RLR_BATCH_SELECT_SPLIT") != nullptr;
-    if (!split && q_count >= 64 && n <= (1u << 20) && (score_stride % 4) == 0) {
+    // 4 n bytes with every counter in LDS; else the five-launch form
+    if (q_count >= 64 && n <= (1u << 20) && (score_stride % 4) == 0) {
         hipLaunchKernelGGL(batch_select_fused_kernel, dim3(q_count), dim3(1024), 0, s, scores, n, score_stride, st, two_eps, tau_out,
                            cand, cand_stride);
         return hipGetLastError();

@@ -1,9 +1,8 @@
 """Which part of the scan is placement-sensitive?  Six 10 M x 768 f32 indexes in one process: the real scan (events), the read
-probe in the scan's shape, the scan kernel without and with its histogram flush into fresh scratch buffers."""
+probe, the scan kernel without and with its histogram flush into fresh scratch buffers."""
 import importlib, json, os, sys
 import numpy as np
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
-os.environ["RLR_PROBE_SHAPE"] = "0"
 rlr = importlib.import_module("rust-local-rag_amd")
 n, dim = 10_000_000, 768
 rng = np.random.default_rng(3)

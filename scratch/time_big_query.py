@@ -1,5 +1,4 @@
-"""the large-candidate path (guard band > 4096 entries): dense cluster around the query, 8-bit nomination.
-RLR_BIG_QUERY_SORT=1 selects the old finish (one-lane re-score + global bitonic sort)."""
+"""the large-candidate path (guard band > 4096 entries): dense cluster around the query, 8-bit nomination."""
 import importlib, sys, time, os
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

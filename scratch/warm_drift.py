@@ -1,5 +1,5 @@
 """Does the scan rate drift while the device warms up?  One 10 M x 768 f32 index, back-to-back searches for 20 s, the scan stage's
-fraction of the HBM peak (HIP events) averaged per second.  RLR_ROWS_ALLOC_NOW picks the allocation policy."""
+fraction of the HBM peak (HIP events) averaged per second."""
 import importlib, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -18,4 +18,4 @@ for sec in range(int(os.environ.get("RLR_DRIFT_S", "20"))):
         ix.search_topk(qs[i % 64], 100); i += 1
     p = ix.profile_read()
     out.append(round(n * dim * 4 / (p.scan_ms / p.n_scan_launches * 1e-3) / 8e12, 4))
-print(json.dumps({"policy": os.environ.get("RLR_ROWS_ALLOC_NOW", "default"), "frac_per_second": out}))
+print(json.dumps({"frac_per_second": out}))

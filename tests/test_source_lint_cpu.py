@@ -2,7 +2,8 @@
 * device memory the library allocates must come from rlr::dev_malloc, so that RLR_POISON_ALLOC=1 covers every buffer;
 * a null-stream fill / device-to-device copy of device memory may return before it has run and is NOT ordered
   against the non-blocking streams searches run on (the histogram defect of round 1), so each one must be followed
-  by an explicit wait before the function goes on, or be issued Async on the consumer's own stream."""
+  by an explicit wait before the function goes on, or be issued Async on the consumer's own stream.
+And one for a class of code no test would run: an environment switch that nothing sets (the last test)."""
 import glob
 import os
 import re
@@ -45,3 +46,32 @@ def test_null_stream_fills_and_device_copies_are_followed_by_a_wait():
             if not any(w in window for w in waits):
                 loose.append((os.path.basename(path), i + 1, code.strip()))
     assert not loose, loose
+
+
+# launch-shape overrides: each parametrises one kernel rather than selecting a second implementation, and the sweep
+# scripts under scratch/ depend on them
+LAUNCH_SHAPE_OVERRIDES = {"RLR_SCAN_VARIANT", "RLR_SCAN_IMAGE_VARIANT", "RLR_Q8_VARIANT", "RLR_SCAN_MULTI_VARIANT"}
+
+
+def test_every_environment_switch_is_documented_and_exercised():
+    """An environment switch is a second code path.  One stays in the library only while something runs it: a test,
+    bench.py, a tool -- or it is one of the launch-shape overrides above.  Every quoted "RLR_..." literal in csrc/ is a
+    name handed to getenv, directly or through a helper (the RLR_ macros and enumerators are never quoted)."""
+    switches = set()
+    for path in SOURCES + sorted(glob.glob(os.path.join(ROOT, "rust-local-rag_amd", "csrc", "*.h"))):
+        for line in _lines(path):
+            switches.update(re.findall(r'"(RLR_[A-Z0-9_]+)"', line.split("//")[0]))
+    assert switches, "no getenv names found: the pattern above no longer matches how csrc/ reads its switches"
+    with open(os.path.join(ROOT, "INTEGRATION.md")) as f:
+        documented = set(re.findall(r"RLR_[A-Z0-9_]+", f.read()))
+    users = [p for p in glob.glob(os.path.join(ROOT, "tests", "**", "*.py"), recursive=True)
+             if os.path.abspath(p) != os.path.abspath(__file__)]
+    users += [os.path.join(ROOT, "bench.py")] + glob.glob(os.path.join(ROOT, "tools", "**", "*.py"), recursive=True)
+    exercised = set()
+    for p in users:
+        with open(p) as f:
+            exercised.update(re.findall(r"RLR_[A-Z0-9_]+", f.read()))
+    undocumented = sorted(switches - documented)
+    unexercised = sorted(switches - exercised - LAUNCH_SHAPE_OVERRIDES)
+    assert not undocumented, f"not in INTEGRATION.md: {undocumented}"
+    assert not unexercised, f"set or read by no test, bench.py or tool: {unexercised}"
