@@ -667,23 +667,23 @@ __device__ __forceinline__ void emit_result_block(const MmrEmit &emit, uint32_t 
         const uint32_t w0 = emit.list[o], w1 = __builtin_bit_cast(uint32_t, emit.cosv[o]);
         const uint32_t w2 = __builtin_bit_cast(uint32_t, emit.comb[o]);
         const uint32_t w3 = emit.lexv ? __builtin_bit_cast(uint32_t, emit.lexv[o]) : 0u;
-        emit.h_out[i] = w0;
-        emit.h_out[emit.k_cap + i] = w1;
-        emit.h_out[2 * emit.k_cap + i] = w2;
-        emit.h_out[3 * emit.k_cap + i] = w3;
-        chk += result_chk_term(w0, i) + result_chk_term(w1, emit.k_cap + i) + result_chk_term(w2, 2 * emit.k_cap + i) +
-               result_chk_term(w3, 3 * emit.k_cap + i);
+        emit.h_out[block_value(emit.k_cap, kBlockRow, i)] = w0;
+        emit.h_out[block_value(emit.k_cap, kBlockCos, i)] = w1;
+        emit.h_out[block_value(emit.k_cap, kBlockComb, i)] = w2;
+        emit.h_out[block_value(emit.k_cap, kBlockLex, i)] = w3;
+        chk += result_chk_term(w0, block_value(emit.k_cap, kBlockRow, i)) + result_chk_term(w1, block_value(emit.k_cap, kBlockCos, i)) +
+               result_chk_term(w2, block_value(emit.k_cap, kBlockComb, i)) + result_chk_term(w3, block_value(emit.k_cap, kBlockLex, i));
     }
     __threadfence_system();
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1)
         chk += static_cast<uint32_t>(__shfl_xor(static_cast<int>(chk), off));
     if (lane == 0) {
-        emit.h_out[4 * emit.k_cap] = n;
-        emit.h_out[4 * emit.k_cap + 1] = status;
-        emit.h_out[4 * emit.k_cap + 2] = block_chk_tail(chk, n, status, emit.k_cap);
+        emit.h_out[block_n(emit.k_cap)] = n;
+        emit.h_out[block_status(emit.k_cap)] = status;
+        emit.h_out[block_chk(emit.k_cap)] = block_chk_tail(chk, n, status, emit.k_cap);
         __threadfence_system();
-        emit.h_out[4 * emit.k_cap + 3] = kBlockDone;
+        emit.h_out[block_done(emit.k_cap)] = kBlockDone;
     }
 }
 
@@ -691,11 +691,11 @@ __device__ __forceinline__ void emit_result_block(const MmrEmit &emit, uint32_t 
 __device__ __forceinline__ void emit_empty_block(const MmrEmit &emit)
 {
     const uint32_t status = emit.info[1];
-    emit.h_out[4 * emit.k_cap] = 0;
-    emit.h_out[4 * emit.k_cap + 1] = status;
-    emit.h_out[4 * emit.k_cap + 2] = block_chk_tail(0u, 0u, status, emit.k_cap);
+    emit.h_out[block_n(emit.k_cap)] = 0;
+    emit.h_out[block_status(emit.k_cap)] = status;
+    emit.h_out[block_chk(emit.k_cap)] = block_chk_tail(0u, 0u, status, emit.k_cap);
     __threadfence_system();
-    emit.h_out[4 * emit.k_cap + 3] = kBlockDone;
+    emit.h_out[block_done(emit.k_cap)] = kBlockDone;
 }
 
 // max over a lane's J values that skips NaN, never below -inf: v_max3_f32 returns the largest non-NaN operand (all values

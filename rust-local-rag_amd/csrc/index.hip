@@ -684,23 +684,41 @@ int32_t wait_polling(Complete &&complete, hipStream_t s, WaitEma *c, uint32_t ke
     return RLR_OK;
 }
 
-// The result block of a fused search -> MMR call (sort_emit.h: [4 x k_cap values] n status checksum done).
+// The result block of a fused search -> MMR call (sort_emit.h).
 int32_t wait_block(const volatile uint32_t *h_out, uint32_t k_cap, hipStream_t s, WaitEma *c)
 {
     return wait_polling(
         [&]() {
-            if (h_out[4 * k_cap + 3] != kBlockDone)
+            if (h_out[block_done(k_cap)] != kBlockDone)
                 return false;
-            const uint32_t n = h_out[4 * k_cap], status = h_out[4 * k_cap + 1];
+            const uint32_t n = h_out[block_n(k_cap)], status = h_out[block_status(k_cap)];
             if (n > k_cap)
                 return false;
             uint32_t chk = 0;
-            for (uint32_t b = 0; b < 4; ++b)
+            for (uint32_t b = 0; b < kBlockPlanes; ++b)
                 for (uint32_t i = 0; i < n; ++i)
-                    chk += result_chk_term(h_out[b * k_cap + i], b * k_cap + i);
-            return block_chk_tail(chk, n, status, k_cap) == h_out[4 * k_cap + 2];
+                    chk += result_chk_term(h_out[block_value(k_cap, b, i)], block_value(k_cap, b, i));
+            return block_chk_tail(chk, n, status, k_cap) == h_out[block_chk(k_cap)];
         },
         s, c, 0x40000000u);
+}
+
+// The host reader of a complete block: its n picks into the caller's arrays (lex_out may be null), its status returned.
+uint32_t read_block(const uint32_t *h_out, uint32_t k_cap, uint64_t *rows_out, float *cos_out, float *score_out, float *lex_out,
+                    uint32_t *n_out)
+{
+    const uint32_t n = h_out[block_n(k_cap)], status = h_out[block_status(k_cap)];
+    if (status != 0)
+        return status;
+    for (uint32_t i = 0; i < n; ++i) {
+        rows_out[i] = h_out[block_value(k_cap, kBlockRow, i)];
+        cos_out[i] = __builtin_bit_cast(float, h_out[block_value(k_cap, kBlockCos, i)]);
+        score_out[i] = __builtin_bit_cast(float, h_out[block_value(k_cap, kBlockComb, i)]);
+        if (lex_out)
+            lex_out[i] = __builtin_bit_cast(float, h_out[block_value(k_cap, kBlockLex, i)]);
+    }
+    *n_out = n;
+    return 0;
 }
 
 // The completion words of nq single-query pipelines (sort_emit.h: count | checksum << 32, written last).  res != null:
@@ -1185,23 +1203,23 @@ __device__ inline void hybrid_emit_body(const uint32_t *list, const float *comb,
     for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
         const uint32_t w0 = list[i], w1 = __builtin_bit_cast(uint32_t, cosv[i]), w2 = __builtin_bit_cast(uint32_t, comb[i]);
         const uint32_t w3 = __builtin_bit_cast(uint32_t, lexv[i]);
-        h_out[i] = w0;
-        h_out[k_cap + i] = w1;
-        h_out[2 * k_cap + i] = w2;
-        h_out[3 * k_cap + i] = w3;
-        chk += result_chk_term(w0, i) + result_chk_term(w1, k_cap + i) + result_chk_term(w2, 2 * k_cap + i) +
-               result_chk_term(w3, 3 * k_cap + i);
+        h_out[block_value(k_cap, kBlockRow, i)] = w0;
+        h_out[block_value(k_cap, kBlockCos, i)] = w1;
+        h_out[block_value(k_cap, kBlockComb, i)] = w2;
+        h_out[block_value(k_cap, kBlockLex, i)] = w3;
+        chk += result_chk_term(w0, block_value(k_cap, kBlockRow, i)) + result_chk_term(w1, block_value(k_cap, kBlockCos, i)) +
+               result_chk_term(w2, block_value(k_cap, kBlockComb, i)) + result_chk_term(w3, block_value(k_cap, kBlockLex, i));
     }
     if (chk)
         atomicAdd(&s_chk, chk);
     __threadfence_system();
     __syncthreads();
     if (threadIdx.x == 0) { // (the greedy kernel's emit tail writes the same four words)
-        h_out[4 * k_cap] = n;
-        h_out[4 * k_cap + 1] = status;
-        h_out[4 * k_cap + 2] = block_chk_tail(s_chk, n, status, k_cap);
+        h_out[block_n(k_cap)] = n;
+        h_out[block_status(k_cap)] = status;
+        h_out[block_chk(k_cap)] = block_chk_tail(s_chk, n, status, k_cap);
         __threadfence_system();
-        h_out[4 * k_cap + 3] = kBlockDone;
+        h_out[block_done(k_cap)] = kBlockDone;
     }
 }
 
@@ -1444,21 +1462,34 @@ bool scan_over_q8(const rlr_index *ix)
     return ix->q8_enabled && ix->d_q8 && !ix->q8_has_inf;
 }
 
-bool scans_take_host_query(const rlr_index *ix, const Ctx *c, const float *h_q)
+// bytes per element the single-query nomination scan streams (profile accounting)
+uint64_t scan_bytes_per_element(const rlr_index *ix, const Ctx *c)
 {
-    if (scan_over_q8(ix) || scan_over_image(ix, c) || ix->n_rows == 0)
-        return false;
+    return scan_over_q8(ix) ? 1 : (ix->dtype == RLR_F16 || scan_over_image(ix, c)) ? 2 : 4;
+}
+
+// a scan over the index' rows (query_host stays null: the caller sets it where the query may travel in the arguments)
+ScanArgs scan_args(const rlr_index *ix, const float *query, float *scores, uint32_t *hist)
+{
     ScanArgs sa;
     sa.rows = ix->d_rows;
-    sa.query = nullptr;
-    sa.scores = nullptr;
-    sa.hist = nullptr;
+    sa.query = query;
+    sa.scores = scores;
+    sa.hist = hist;
     sa.n_rows = static_cast<uint32_t>(ix->n_rows);
     sa.dim = ix->dim;
     sa.pitch16 = ix->pitch16;
     sa.dtype = ix->dtype;
     sa.n_cu = ix->n_cu;
     sa.variant = ix->scan_variant;
+    return sa;
+}
+
+bool scans_take_host_query(const rlr_index *ix, const Ctx *c, const float *h_q)
+{
+    if (scan_over_q8(ix) || scan_over_image(ix, c) || ix->n_rows == 0)
+        return false;
+    ScanArgs sa = scan_args(ix, nullptr, nullptr, nullptr);
     sa.query_host = h_q;
     return launch_scan_takes_host_query(sa);
 }
@@ -1502,6 +1533,280 @@ int32_t check_hist_assert(Ctx *c)
     return RLR_OK;
 }
 
+// ---- the frame every search entry point is built on ----------------------------------------------------------------
+// The plan of a call: k clamped to the rows, the band factors of its queries, the guard bands (the one place that knows
+// the rule: the caller's guard_eps, or the default for this dim, times the operands' scale) and the candidate capacity.
+SearchPlan make_plan(const rlr_index *ix, const float *queries, uint32_t nq, uint32_t k, float guard_eps, bool unordered = false)
+{
+    SearchPlan p;
+    p.k = static_cast<uint32_t>(std::min<uint64_t>(k, ix->n_rows));
+    plan_bands(ix, queries, nq, &p);
+    const float eps = (guard_eps >= 0.0f ? guard_eps : rlr_default_guard_eps(ix->dim)) * p.scale;
+    p.two_eps = 2.0f * eps;
+    p.two_eps_img = image_two_eps(ix, eps, p);
+    p.cap = kLdsSortCap;
+    p.unordered = unordered;
+    return p;
+}
+
+// nq dim-long queries -> h_q, q_pitch floats each, zero padded
+void pad_queries(const rlr_index *ix, const float *queries, uint32_t nq, float *h_q)
+{
+    if (ix->q_pitch != ix->dim)
+        std::memset(h_q, 0, static_cast<size_t>(nq) * ix->q_pitch * sizeof(float));
+    for (uint32_t q = 0; q < nq; ++q)
+        std::memcpy(h_q + static_cast<size_t>(q) * ix->q_pitch, queries + static_cast<size_t>(q) * ix->dim, ix->dim * sizeof(float));
+}
+
+// The queries of a call that enqueues single-query pipelines, staged in pinned memory (h_q), their norms for the 8-bit
+// band; from here on the context's histograms count as in use until the call has seen every pipeline finish.
+void stage_queries(const rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, float *h_q)
+{
+    pad_queries(ix, queries, nq, h_q);
+    stage_query_norms(ix, c, queries, nq);
+    c->hist_dirty = true;
+}
+
+// the completion words a polling wait watches (sort_emit.h): pre-set before the first enqueue, replaced by each
+// pipeline's last store
+void arm_meta(uint64_t *h_meta, uint32_t nq)
+{
+    if (wait_mode() != kWaitBlock)
+        for (uint32_t q = 0; q < nq; ++q)
+            h_meta[q] = kMetaPending;
+}
+
+// c->ev[0] .. c->ev[3] of a timed single-query pipeline: scan | select | re-score + sort, added to *t
+struct StageMs {
+    double scan = 0, select = 0, rescore = 0, total = 0;
+};
+
+hipError_t add_stage_ms(Ctx *c, StageMs *t)
+{
+    float a = 0, b = 0, d = 0;
+    hipError_t e = hipEventElapsedTime(&a, c->ev[0], c->ev[1]);
+    if (e == hipSuccess)
+        e = hipEventElapsedTime(&b, c->ev[1], c->ev[2]);
+    if (e == hipSuccess)
+        e = hipEventElapsedTime(&d, c->ev[2], c->ev[3]);
+    t->scan += a;
+    t->select += b;
+    t->rescore += d;
+    t->total += a + b + d;
+    return e;
+}
+
+// profile bookkeeping of an MMR call: c->ev[0] .. c->ev[1] bracket gather + Gram + greedy on the context's stream
+void note_mmr(rlr_index *ix, Ctx *c, uint32_t n_queries)
+{
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    ix->prof.n_mmr += n_queries;
+    ix->prof.mmr_ms += ms;
+}
+
+// Profile bookkeeping of a search call that has synchronised: nq queries, their candidates and large-candidate retries.
+// timed: the pipelines recorded their events -- read here once, or already summed per query by the caller (*summed);
+// mmr_chain: c->bev[0] .. c->bev[1] bracket the blend / Gram / greedy chain of a fused search -> MMR call.
+// A failed event read leaves its times zero; the counters are kept either way and the failure is the return value (the
+// fused paths, whose results are complete by then, ignore it as they always have).
+int32_t note_search(rlr_index *ix, Ctx *c, uint32_t nq, uint64_t n_candidates, uint64_t n_retries, bool timed,
+                    bool mmr_chain = false, const StageMs *summed = nullptr)
+{
+    StageMs t;
+    float mmr_ms = 0;
+    hipError_t e = hipSuccess;
+    if (timed && summed)
+        t = *summed;
+    else if (timed)
+        e = add_stage_ms(c, &t);
+    if (timed && mmr_chain && hipEventElapsedTime(&mmr_ms, c->bev[0], c->bev[1]) != hipSuccess)
+        mmr_ms = 0;
+    std::unique_lock<std::mutex> lk(ix->mu);
+    ix->prof.n_searches += nq;
+    ix->prof.n_candidates += n_candidates;
+    ix->prof.n_retries += n_retries;
+    if (timed) {
+        ix->prof.n_scan_launches += nq;
+        ix->prof.scan_ms += t.scan;
+        ix->prof.select_ms += t.select;
+        ix->prof.rescore_ms += t.rescore;
+        ix->prof.total_ms += t.total + mmr_ms;
+        ix->prof.scan_bytes += static_cast<uint64_t>(nq) * ix->n_rows * ix->dim * scan_bytes_per_element(ix, c);
+        if (mmr_chain) {
+            ix->prof.n_mmr += nq;
+            ix->prof.mmr_ms += mmr_ms;
+        }
+    }
+    lk.unlock();
+    RLR_HIP(e);
+    return RLR_OK;
+}
+
+// From the first enqueue on, work may be running on `s` (and, for a batched text search, on the stream that records
+// `also`): an exit that has not seen it finish drains it before the lease hands the context back.
+struct StreamDrain {
+    hipStream_t s;
+    hipEvent_t also = nullptr;
+    bool armed = true;
+    ~StreamDrain()
+    {
+        if (also)
+            (void)hipEventSynchronize(also);
+        if (armed)
+            (void)hipStreamSynchronize(s);
+    }
+};
+
+// ---- workspace layouts ---------------------------------------------------------------------------------------------
+// A cursor over a base pointer that hands out regions in declaration order.  Each layout below is ONE list of regions, a
+// member per region initialised by its take(): built over null bases it only measures (what grow() / pin_reserve() are
+// asked for), built again over the buffers it yields every pointer -- the size and the pointers cannot disagree.  Region
+// order and sizes are what the kernels and copies have always used; what a layout relies on is said next to it.
+struct Carver {
+    char *base;
+    size_t bytes = 0;
+    explicit Carver(void *b) : base(static_cast<char *>(b)) {}
+    template <typename T>
+    T *take(uint64_t count)
+    {
+        T *p = base ? reinterpret_cast<T *>(base + bytes) : nullptr;
+        bytes += static_cast<size_t>(count) * sizeof(T);
+        return p;
+    }
+    uint64_t floats() const { return bytes / sizeof(float); } // c->d_pool is grown in floats; every region is whole words
+};
+
+// The results of an MMR call over m pools of P: order | mmr | n, contiguous on the device and in pinned memory -- one
+// copy of words() words moves them.
+struct MmrResults {
+    uint32_t *order;
+    float *mmr;
+    uint32_t *n;
+    MmrResults(Carver &w, uint64_t m, uint64_t P)
+        : order(w.take<uint32_t>(m * P)), mmr(w.take<float>(m * P)), n(w.take<uint32_t>(m)) {}
+    static uint64_t words(uint64_t m, uint64_t P) { return 2 * m * P + m; }
+};
+
+// Device side (c->d_pool) of an MMR call over m pools of P.
+struct MmrWs {
+    uint64_t m, P, unused_head; // floats in front that no kernel reads (the single-pool call once gathered its pool there)
+    Carver d;
+    float *head = d.take<float>(unused_head), *gram = d.take<float>(m * P * P), *scores = d.take<float>(m * P);
+    MmrResults res{d, m, P};
+    uint32_t *sizes = d.take<uint32_t>(m), *pad = d.take<uint32_t>(8);
+    MmrWs(float *base, uint32_t m_, uint32_t P_, uint64_t head_ = 0) : m(m_), P(P_), unused_head(head_), d(base) {}
+};
+
+// Pinned side (c->h_pin) of a batched MMR call: the row list upload_list stages at the head of the buffer | scores |
+// sizes | the results.  Reserved as a whole BEFORE upload_list enqueues its copy, so that the buffer
+// is never reallocated under a transfer.
+struct MmrStaging {
+    uint64_t m, P;
+    Carver h;
+    char *list = h.take<char>(m * P * 8 + 64);
+    float *scores = h.take<float>(m * P);
+    uint32_t *sizes = h.take<uint32_t>(m + 4);
+    MmrResults res{h, m, P};
+    char *pad = h.take<char>(64);
+    MmrStaging(void *base, uint32_t m_, uint32_t P_) : m(m_), P(P_), h(base) {}
+};
+
+// rlr_search_diverse: device (c->d_pool) and pinned (c->h_pin: the staged query | the result block).
+struct DiverseWs {
+    uint64_t P, dim, q_pitch, k_cap;
+    Carver d, h;
+    float *unused = d.take<float>(P * dim); // (the Gram kernel reads the pool rows in place)
+    float *gram = d.take<float>(P * P), *comb = d.take<float>(P), *cos = d.take<float>(P);
+    uint32_t *order = d.take<uint32_t>(P);
+    float *mmr = d.take<float>(P);
+    uint32_t *nsel = d.take<uint32_t>(1), *info = d.take<uint32_t>(7);
+    float *h_q = h.take<float>(q_pitch);
+    uint32_t *h_out = h.take<uint32_t>(block_words(static_cast<uint32_t>(k_cap)));
+    char *h_pad = h.take<char>(64);
+    DiverseWs(float *d_base, void *h_base, const rlr_index *ix, uint32_t P_, uint32_t k_cap_)
+        : P(P_), dim(ix->dim), q_pitch(ix->q_pitch), k_cap(k_cap_), d(d_base), h(h_base) {}
+};
+
+// A hybrid search: hybrid_begin_impl lays it out, the ticket carries it to hybrid_finish_impl.  Header, lexical rows and
+// scores are adjacent on the device and in pinned memory (h_lex): host-supplied pairs travel in one copy.
+struct HybridWs {
+    uint64_t P, n_lex_bound, q_pitch, k_cap;
+    Carver d, h;
+    float *gram = d.take<float>(P * P), *comb = d.take<float>(P), *cos = d.take<float>(P), *lexv = d.take<float>(P);
+    uint32_t *order = d.take<uint32_t>(P);
+    float *mmr = d.take<float>(P);
+    uint32_t *nsel = d.take<uint32_t>(1), *info = d.take<uint32_t>(7);
+    HybridLexHeader *hdr = d.take<HybridLexHeader>(1);
+    uint32_t *lrow = d.take<uint32_t>(2 * n_lex_bound); // the rows, then their scores: lscore()
+    float *lcos = d.take<float>(n_lex_bound);
+    float *cand = d.take<float>(3ull * kHybridSlots);                                    // blend candidates: combined | cos | lex
+    float *h_q = h.take<float>(q_pitch);
+    uint32_t *h_lex = h.take<uint32_t>(2 + 2 * n_lex_bound), *h_out = h.take<uint32_t>(block_words(static_cast<uint32_t>(k_cap)));
+    char *h_pad = h.take<char>(64);
+    HybridWs(float *d_base, void *h_base, uint32_t q_pitch_, uint32_t P_, uint32_t bound, uint32_t k_cap_)
+        : P(P_), n_lex_bound(bound), q_pitch(q_pitch_), k_cap(k_cap_), d(d_base), h(h_base) {}
+    HybridWs() : HybridWs(nullptr, nullptr, 0, 0, 0, 0) {}
+    // The scores of n_lex pairs sit right behind their rows.  Pairs left on the device by the BM25 kernels use every slot
+    // (n_lex = n_lex_bound: the LexSink of begin and the blend of finish agree by construction); host-supplied pairs
+    // (n_lex <= n_lex_bound) are packed the same way in h_lex, so that header | rows | scores is one copy.
+    float *lscore(uint32_t n_lex) const { return reinterpret_cast<float *>(lrow + n_lex); }
+    static float *h_lscore(uint32_t *h_lex, uint32_t n_lex) { return reinterpret_cast<float *>(h_lex + 2 + n_lex); }
+    static size_t lex_copy_bytes(uint32_t n_lex) { return sizeof(HybridLexHeader) + static_cast<size_t>(n_lex) * 8; }
+};
+
+// The per-query results of search_hybrid_batch (Q x P each, then per-query words): the same list on the device and in
+// pinned memory, moved in one copy of words() words.
+struct HybridBatchRes {
+    uint32_t *list;
+    float *comb, *cos, *lexv;
+    uint32_t *order;
+    float *mmr;
+    uint32_t *nsel, *sizes, *info;
+    HybridBatchRes(Carver &w, uint64_t Q, uint64_t P)
+        : list(w.take<uint32_t>(Q * P)), comb(w.take<float>(Q * P)), cos(w.take<float>(Q * P)), lexv(w.take<float>(Q * P)),
+          order(w.take<uint32_t>(Q * P)), mmr(w.take<float>(Q * P)), nsel(w.take<uint32_t>(Q)), sizes(w.take<uint32_t>(Q)),
+          info(w.take<uint32_t>(2 * Q)) {}
+    static uint64_t words(uint64_t Q, uint64_t P) { return 6 * Q * P + 4 * Q; }
+};
+
+// search_hybrid_batch, device side (c->d_pool)
+struct HybridBatchWs {
+    uint64_t Q, fetch, P, bound, q_pitch, gram_floats;
+    Carver d;
+    uint64_t *packed = d.take<uint64_t>(Q * fetch); // the fetched keys of every query
+    float *q = d.take<float>(Q * q_pitch);
+    uint32_t *lrow = d.take<uint32_t>(Q * bound);
+    float *lscore = d.take<float>(Q * bound), *lcos = d.take<float>(Q * bound);
+    HybridLexHeader *hdr = d.take<HybridLexHeader>(Q);
+    float *cand = d.take<float>(Q * 3 * kHybridSlots);
+    HybridBatchRes res{d, Q, P};
+    float *gram = d.take<float>(gram_floats);
+    HybridBatchWs(float *base, const rlr_index *ix, uint64_t Q_, uint32_t fetch_, uint32_t P_, uint32_t bound_, bool diversify)
+        : Q(Q_), fetch(fetch_), P(P_), bound(bound_), q_pitch(ix->q_pitch), gram_floats(diversify ? Q_ * P_ * P_ : 0), d(base) {}
+};
+
+// search_hybrid_batch, pinned side (c->h_pin): fetched keys | queries | the results.  Laid out only once the cosine batch,
+// which stages through the same buffer, is back.
+struct HybridBatchPin {
+    uint64_t Q, fetch, P, q_pitch;
+    Carver h;
+    uint64_t *packed = h.take<uint64_t>(Q * fetch);
+    float *q = h.take<float>(Q * q_pitch);
+    HybridBatchRes res{h, Q, P};
+    char *pad = h.take<char>(64);
+    HybridBatchPin(void *base, const rlr_index *ix, uint64_t Q_, uint32_t fetch_, uint32_t P_)
+        : Q(Q_), fetch(fetch_), P(P_), q_pitch(ix->q_pitch), h(base) {}
+};
+
+// the greedy kernel writes the picks of a fused search into the pinned block itself
+rlr::MmrEmit mmr_emit(const uint32_t *list, const float *comb, const float *cosv, const float *lexv, const uint32_t *info,
+                      uint32_t k_cap, uint32_t *h_out)
+{
+    return rlr::MmrEmit{list, comb, cosv, lexv, info, k_cap, h_out};
+}
+
 // Enqueue the whole pipeline for query `qi` on the context's stream:
 //   scan (+digit-1 histogram) -> the tail in two launches (tail.hip), or in its split form: digit-2 histogram (bin search
 //   folded in) -> collect (bin search folded in) -> LDS-staged reference-order re-score -> sort + emit; either way the
@@ -1522,17 +1827,7 @@ hipError_t enqueue_query_scan(rlr_index *ix, Ctx *c, uint32_t qi, bool timed)
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (timed && (e = hipEventRecord(c->ev[0], s)) != hipSuccess) return e;
-    ScanArgs sa;
-    sa.rows = ix->d_rows;
-    sa.query = dq;
-    sa.scores = c->d_scores;
-    sa.hist = hist1;
-    sa.n_rows = n;
-    sa.dim = ix->dim;
-    sa.pitch16 = ix->pitch16;
-    sa.dtype = ix->dtype;
-    sa.n_cu = ix->n_cu;
-    sa.variant = ix->scan_variant;
+    ScanArgs sa = scan_args(ix, dq, c->d_scores, hist1);
     sa.query_host = c->h_q_kq ? c->h_q_kq + static_cast<size_t>(qi) * ix->q_pitch : nullptr;
     const bool q8 = scan_over_q8(ix);
     const bool img = !q8 && scan_over_image(ix, c);
@@ -1651,20 +1946,8 @@ int32_t big_query(rlr_index *ix, Ctx *c, uint32_t qi, const SearchPlan &p, uint3
     }
     SelectState *st = c->d_state + qi;
     const float *dq = c->d_query + static_cast<size_t>(qi) * ix->q_pitch;
-    if (rescan) {
-        ScanArgs sa;
-        sa.rows = ix->d_rows;
-        sa.query = dq;
-        sa.scores = c->d_scores;
-        sa.hist = nullptr;
-        sa.n_rows = n;
-        sa.dim = ix->dim;
-        sa.pitch16 = ix->pitch16;
-        sa.dtype = ix->dtype;
-        sa.n_cu = ix->n_cu;
-        sa.variant = ix->scan_variant;
-        RLR_HIP(launch_scan(sa, s));
-    }
+    if (rescan)
+        RLR_HIP(launch_scan(scan_args(ix, dq, c->d_scores, nullptr), s));
     // key_lo is still valid in the state; reset the counter and the capacity
     SelectState h;
     RLR_HIP(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, s));
@@ -1723,8 +2006,7 @@ bool batch_eligible(const rlr_index *ix, uint32_t nq, uint32_t k, bool f16_ok = 
     // ~0.8 ms for the sample, the per-query selects and the finish kernels.
     const double row_bytes = static_cast<double>(ix->n_rows) * ix->dim * (ix->dtype == RLR_F16 ? 2.0 : 4.0);
     // the single-query scan streams the 8-bit copy / the binary16 image when those are switched on
-    const double scan_bytes = static_cast<double>(ix->n_rows) * ix->dim *
-                              (scan_over_q8(ix) ? 1.0 : (scan_over_image(ix, nullptr) || ix->dtype == RLR_F16) ? 2.0 : 4.0);
+    const double scan_bytes = static_cast<double>(ix->n_rows) * ix->dim * static_cast<double>(scan_bytes_per_element(ix, nullptr));
     const double t_single = 60e-6 + scan_bytes / 6.2e12;
     const bool image = ix->image_enabled && ix->d_image;
     // (over the image, batches of <= 128 queries take the resident-query kernel: ~5 TB/s of binary16)
@@ -1829,17 +2111,7 @@ int32_t run_batched(rlr_index *ix, Ctx *c, uint32_t q0, uint32_t nq, const Searc
     const void *image = use_image ? ix->d_image : nullptr;
     // the image stores k in natural order (like binary16 rows); only the direct f32-row loads permute it
     if (use_multi) {
-        ScanArgs sa;
-        sa.rows = ix->d_rows;
-        sa.query = dq;
-        sa.scores = c->d_sample;
-        sa.hist = nullptr;
-        sa.n_rows = n;
-        sa.dim = ix->dim;
-        sa.pitch16 = ix->pitch16;
-        sa.dtype = ix->dtype;
-        sa.n_cu = ix->n_cu;
-        sa.variant = ix->scan_variant;
+        const ScanArgs sa = scan_args(ix, dq, c->d_sample, nullptr);
         hipError_t e = hipSuccess;
         // (binary16 rows: the same band -- the widening is exact and the products and sums are f32 as in the single-query scan)
         if (!(ix->dtype == RLR_F16 ? launch_scan_multi_f16(sa, ix->q_pitch, nq, s_stride, s, &e)
@@ -1917,14 +2189,7 @@ int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uin
 {
     if (n_handed_back)
         *n_handed_back = 0;
-    const uint32_t n = static_cast<uint32_t>(ix->n_rows);
-    SearchPlan p;
-    p.k = std::min<uint32_t>(k_req, n);
-    plan_bands(ix, queries, nq, &p);
-    const float eps = (guard_eps >= 0.0f ? guard_eps : rlr_default_guard_eps(ix->dim)) * p.scale;
-    p.two_eps = 2.0f * eps;
-    p.two_eps_img = image_two_eps(ix, eps, p);
-    p.cap = kLdsSortCap;
+    const SearchPlan p = make_plan(ix, queries, nq, k_req, guard_eps);
     *plan_out = p;
     if (h_results)
         *h_results = nullptr;
@@ -1942,14 +2207,8 @@ int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uin
     float *h_q = static_cast<float *>(c->h_pin);
     uint64_t *h_res = reinterpret_cast<uint64_t *>(static_cast<char *>(c->h_pin) + q_bytes);
     uint64_t *h_meta = h_res + n_res;
-    if (ix->q_pitch != ix->dim)
-        std::memset(h_q, 0, q_bytes);
-    for (uint32_t q = 0; q < nq; ++q)
-        std::memcpy(h_q + static_cast<size_t>(q) * ix->q_pitch, queries + static_cast<size_t>(q) * ix->dim,
-                    ix->dim * sizeof(float));
-    stage_query_norms(ix, c, queries, nq);
+    stage_queries(ix, c, queries, nq, h_q);
     hipStream_t s = c->stream;
-    c->hist_dirty = true; // cleared when every enqueued pipeline has run to its histogram-clearing stage
     const bool batched = batch_eligible(ix, nq, p.k, p.f16_ok, coalesced);
     if (!batched)
         count_f16_fallbacks(ix, p, nq, batch_eligible(ix, nq, p.k));
@@ -1960,7 +2219,7 @@ int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uin
         RLR_HIP(stage_queries_for_scans(ix, c, h_q, q_bytes, s));
 
     const bool timed = ix->profiling;
-    double scan_ms = 0, select_ms = 0, rescore_ms = 0, total_ms = 0;
+    StageMs per_query_ms; // (profiling several queries: summed query by query)
     uint64_t n_cand_total = 0, n_retry = 0;
     auto fetch_results = [&](size_t first, size_t count) -> int32_t { // packed results -> pinned host
         if (!d_out_user && count)
@@ -2000,10 +2259,7 @@ int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uin
         c->hist_dirty = false;
         if (h_results)
             *h_results = h_res;
-        std::lock_guard<std::mutex> lk(ix->mu);
-        ix->prof.n_searches += nq;
-        ix->prof.n_retries += n_retry;
-        return RLR_OK;
+        return note_search(ix, c, nq, 0, n_retry, /*timed=*/false);
     }
 
     // Host-bound results: the last kernel of each pipeline writes its k packed results and the candidate
@@ -2011,9 +2267,7 @@ int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uin
     const bool host_direct = !d_out_user;
     uint64_t *q_out = host_direct ? h_res : d_out;
     uint64_t *q_meta = h_meta; // the candidate count always goes straight to the host (the overflow check needs it)
-    if (wait_mode() != kWaitBlock)
-        for (uint32_t q = 0; q < nq; ++q)
-            h_meta[q] = kMetaPending; // each pipeline's last store replaces it (sort_emit.h): what the wait below polls
+    arm_meta(h_meta, nq);
     if (!timed || nq == 1) {
         // (with profiling on, a single query's four events are read after the one final sync)
         for (uint32_t q = 0; q < nq; ++q)
@@ -2023,14 +2277,7 @@ int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uin
         for (uint32_t q = 0; q < nq; ++q) {
             RLR_HIP(enqueue_query(ix, c, q, p, q_out + static_cast<size_t>(q) * p.k, q_meta + q, true));
             RLR_HIP(hipStreamSynchronize(s));
-            float a = 0, b = 0, d = 0;
-            RLR_HIP(hipEventElapsedTime(&a, c->ev[0], c->ev[1]));
-            RLR_HIP(hipEventElapsedTime(&b, c->ev[1], c->ev[2]));
-            RLR_HIP(hipEventElapsedTime(&d, c->ev[2], c->ev[3]));
-            scan_ms += a;
-            select_ms += b;
-            rescore_ms += d;
-            total_ms += a + b + d;
+            RLR_HIP(add_stage_ms(c, &per_query_ms));
         }
     }
     if (timed)
@@ -2039,16 +2286,6 @@ int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uin
         RLR_TRY(wait_results(h_meta, host_direct ? h_res : nullptr, nq, p.k, std::min<uint32_t>(p.cap, kLdsSortCap), s,
                              &c->wait_ema));
     RLR_TRY(check_hist_assert(c));
-    if (timed && nq == 1) {
-        float a = 0, b = 0, d = 0;
-        RLR_HIP(hipEventElapsedTime(&a, c->ev[0], c->ev[1]));
-        RLR_HIP(hipEventElapsedTime(&b, c->ev[1], c->ev[2]));
-        RLR_HIP(hipEventElapsedTime(&d, c->ev[2], c->ev[3]));
-        scan_ms += a;
-        select_ms += b;
-        rescore_ms += d;
-        total_ms += a + b + d;
-    }
     // band overflow -> large-candidate path (rare: massive exact ties, or k > 4096)
     bool refetch = false;
     for (uint32_t q = 0; q < nq; ++q) {
@@ -2065,21 +2302,24 @@ int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uin
     c->hist_dirty = false;
     if (h_results)
         *h_results = h_res;
-    {
-        std::lock_guard<std::mutex> lk(ix->mu);
-        ix->prof.n_searches += nq;
-        ix->prof.n_candidates += n_cand_total;
-        ix->prof.n_retries += n_retry;
-        if (timed) {
-            ix->prof.n_scan_launches += nq;
-            ix->prof.scan_ms += scan_ms;
-            ix->prof.select_ms += select_ms;
-            ix->prof.rescore_ms += rescore_ms;
-            ix->prof.total_ms += total_ms;
-            ix->prof.scan_bytes += static_cast<uint64_t>(nq) * ix->n_rows * ix->dim *
-                                   (scan_over_q8(ix) ? 1 : (ix->dtype == RLR_F16 || scan_over_image(ix, c)) ? 2 : 4);
-        }
-    }
+    // (a single profiled query's events are read here, after the one final synchronisation)
+    return note_search(ix, c, nq, n_cand_total, n_retry, timed, /*mmr_chain=*/false, nq > 1 ? &per_query_ms : nullptr);
+}
+
+// c->d_list / c->d_vals for n rows (at least 1024)
+int32_t reserve_list(Ctx *c, uint32_t n)
+{
+    if (c->list_cap >= n && c->d_list)
+        return RLR_OK;
+    if (c->d_list) (void)hipFree(c->d_list);
+    if (c->d_vals) (void)hipFree(c->d_vals);
+    c->d_list = nullptr;
+    c->d_vals = nullptr;
+    c->list_cap = 0;
+    const uint32_t cap = std::max<uint32_t>(next_pow2(n), 1024);
+    RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_list), static_cast<size_t>(cap) * sizeof(uint32_t)));
+    RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_vals), static_cast<size_t>(cap) * sizeof(float)));
+    c->list_cap = cap;
     return RLR_OK;
 }
 
@@ -2087,17 +2327,7 @@ int32_t upload_list(rlr_index *ix, Ctx *c, const uint64_t *rows, uint32_t n, uin
 {
     if (bound == ~0ull)
         bound = ix->n_rows;
-    if (c->list_cap < n || !c->d_list) {
-        if (c->d_list) (void)hipFree(c->d_list);
-        if (c->d_vals) (void)hipFree(c->d_vals);
-        c->d_list = nullptr;
-        c->d_vals = nullptr;
-        c->list_cap = 0;
-        const uint32_t cap = std::max<uint32_t>(next_pow2(n), 1024);
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_list), static_cast<size_t>(cap) * sizeof(uint32_t)));
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_vals), static_cast<size_t>(cap) * sizeof(float)));
-        c->list_cap = cap;
-    }
+    RLR_TRY(reserve_list(c, n));
     RLR_TRY(pin_reserve(c, static_cast<size_t>(n) * 8 + 64));
     uint32_t *h = static_cast<uint32_t *>(c->h_pin);
     for (uint32_t i = 0; i < n; ++i) {
@@ -2678,34 +2908,21 @@ int32_t rlr_search_topk_device_begin(rlr_index *ix, const float *queries, uint32
     RLR_TRY(ctx_acquire(ix, &c));
     CtxLease lease(ix);
     lease.c = c; // released on every error path below
-    SearchPlan p;
-    p.k = k;
-    plan_bands(ix, queries, n_queries, &p);
-    p.two_eps = 2.0f * (guard_eps >= 0.0f ? guard_eps : rlr_default_guard_eps(ix->dim)) * p.scale;
-    p.two_eps_img = image_two_eps(ix, p.two_eps * 0.5f, p);
-    p.cap = kLdsSortCap;
+    const SearchPlan p = make_plan(ix, queries, n_queries, k, guard_eps);
     RLR_TRY(ctx_prepare(ix, c, n_queries, p));
     count_f16_fallbacks(ix, p, n_queries, false);
     const size_t q_bytes = static_cast<size_t>(n_queries) * ix->q_pitch * sizeof(float);
     RLR_TRY(pin_reserve(c, q_bytes + (static_cast<size_t>(n_queries) * k + n_queries) * sizeof(uint64_t)));
     float *h_q = static_cast<float *>(c->h_pin);
     uint64_t *h_meta = reinterpret_cast<uint64_t *>(static_cast<char *>(c->h_pin) + q_bytes) + static_cast<size_t>(n_queries) * k;
-    if (ix->q_pitch != ix->dim)
-        std::memset(h_q, 0, q_bytes);
-    for (uint32_t q = 0; q < n_queries; ++q)
-        std::memcpy(h_q + static_cast<size_t>(q) * ix->q_pitch, queries + static_cast<size_t>(q) * ix->dim,
-                    ix->dim * sizeof(float));
-    stage_query_norms(ix, c, queries, n_queries);
+    stage_queries(ix, c, queries, n_queries, h_q);
     // The pipelines go on the CALLER's stream: whatever it queues next (all-gather, merge) is ordered behind
     // them by the stream itself.  (A cross-stream event wait was measured first: +20 us per step.)  The
     // context's own stream is idle -- every earlier use of this context ended with a synchronisation.
     hipStream_t own = c->stream;
     c->stream = static_cast<hipStream_t>(stream);
     hipStream_t s = c->stream;
-    c->hist_dirty = true;
-    if (wait_mode() != kWaitBlock)
-        for (uint32_t q = 0; q < n_queries; ++q)
-            h_meta[q] = kMetaPending; // (what _end polls instead of the stream's completion signal)
+    arm_meta(h_meta, n_queries); // (what _end polls instead of the stream's completion signal)
     hipError_t e = stage_queries_for_scans(ix, c, h_q, q_bytes, s);
     uint64_t *out = static_cast<uint64_t *>(d_packed_out);
     for (uint32_t q = 0; q < n_queries && e == hipSuccess; ++q)
@@ -2751,27 +2968,7 @@ int32_t rlr_search_topk_device_end(rlr_index *ix, void *ticket, uint32_t *n_over
         over += nc > kLdsSortCap;
     }
     c->hist_dirty = false;
-    float t_scan = 0, t_sel = 0, t_res = 0;
-    if (c->pending_timed) {
-        RLR_HIP(hipEventElapsedTime(&t_scan, c->ev[0], c->ev[1]));
-        RLR_HIP(hipEventElapsedTime(&t_sel, c->ev[1], c->ev[2]));
-        RLR_HIP(hipEventElapsedTime(&t_res, c->ev[2], c->ev[3]));
-    }
-    {
-        std::lock_guard<std::mutex> lk(ix->mu);
-        ix->prof.n_searches += c->pending_q;
-        ix->prof.n_candidates += n_cand;
-        ix->prof.n_retries += over;
-        if (c->pending_timed) {
-            ix->prof.n_scan_launches += c->pending_q;
-            ix->prof.scan_ms += t_scan;
-            ix->prof.select_ms += t_sel;
-            ix->prof.rescore_ms += t_res;
-            ix->prof.total_ms += t_scan + t_sel + t_res;
-            ix->prof.scan_bytes += static_cast<uint64_t>(c->pending_q) * ix->n_rows * ix->dim *
-                                   (scan_over_q8(ix) ? 1 : (ix->dtype == RLR_F16 || scan_over_image(ix, c)) ? 2 : 4);
-        }
-    }
+    RLR_TRY(note_search(ix, c, c->pending_q, n_cand, over, c->pending_timed));
     c->pending_q = 0;
     c->pending_timed = false;
     if (n_overflow_out)
@@ -2910,16 +3107,6 @@ int32_t rlr_fetch_rows(rlr_index *ix, const uint64_t *rows, uint32_t n, float *o
     return RLR_OK;
 }
 
-// profile bookkeeping of an MMR call: c->ev[0] .. c->ev[1] bracket gather + Gram + greedy on the context's stream
-static void note_mmr(rlr_index *ix, Ctx *c, uint32_t n_queries)
-{
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
-    std::lock_guard<std::mutex> lk(ix->mu);
-    ix->prof.n_mmr += n_queries;
-    ix->prof.mmr_ms += ms;
-}
-
 // one pool of up to 4096 candidates; d_matrix != null: pool_rows are slots of that staged matrix (see mmr_batch_impl)
 static int32_t mmr_single_impl(rlr_index *ix, const uint64_t *pool_rows, const float *pool_scores, uint32_t P, uint32_t k,
                                float lambda, uint32_t *order_out, float *mmr_out, uint32_t *n_out, const void *d_matrix,
@@ -2941,34 +3128,27 @@ static int32_t mmr_single_impl(rlr_index *ix, const uint64_t *pool_rows, const f
     Ctx *c = lease.c;
     hipStream_t s = c->stream;
     RLR_TRY(upload_list(ix, c, pool_rows, P, d_matrix ? n_matrix : ~0ull));
-    // pool (P x dim) followed by gram (P x P), scores (P), order (P), mmr (P), n (1)
-    const uint64_t floats = static_cast<uint64_t>(P) * ix->dim + static_cast<uint64_t>(P) * P + 3ull * P + 4;
-    RLR_TRY(grow(&c->d_pool, &c->pool_cap, floats));
-    float *d_pool = c->d_pool;
-    float *d_gram = d_pool + static_cast<uint64_t>(P) * ix->dim;
-    float *d_sc = d_gram + static_cast<uint64_t>(P) * P;
-    uint32_t *d_order = reinterpret_cast<uint32_t *>(d_sc + P);
-    float *d_mmr = d_sc + 2ull * P;
-    uint32_t *d_n = reinterpret_cast<uint32_t *>(d_sc + 3ull * P);
+    const uint64_t head = static_cast<uint64_t>(P) * ix->dim;
+    RLR_TRY(grow(&c->d_pool, &c->pool_cap, MmrWs(nullptr, 1, P, head).d.floats()));
+    const MmrWs ws(c->d_pool, 1, P, head);
     const bool timed = ix->profiling;
-    RLR_HIP(hipMemcpyAsync(d_sc, pool_scores, static_cast<size_t>(P) * sizeof(float), hipMemcpyHostToDevice, s));
+    RLR_HIP(hipMemcpyAsync(ws.scores, pool_scores, static_cast<size_t>(P) * sizeof(float), hipMemcpyHostToDevice, s));
     if (timed) RLR_HIP(hipEventRecord(c->ev[0], s));
-    RLR_HIP(launch_gram_rows(d_matrix ? d_matrix : ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_list, P, d_gram, 1, s));
-    RLR_HIP(launch_mmr_greedy(d_gram, d_sc, P, k, lambda, d_order, d_mmr, d_n, nullptr, 1, s));
+    RLR_HIP(launch_gram_rows(d_matrix ? d_matrix : ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_list, P, ws.gram, 1, s));
+    RLR_HIP(launch_mmr_greedy(ws.gram, ws.scores, P, k, lambda, ws.res.order, ws.res.mmr, ws.res.n, nullptr, 1, s));
     if (timed) RLR_HIP(hipEventRecord(c->ev[1], s));
-    // one D2H: order | mmr | n are contiguous
-    RLR_TRY(pin_reserve(c, (2ull * P + 4) * 4));
-    RLR_HIP(hipMemcpyAsync(c->h_pin, d_order, (2ull * P + 1) * 4, hipMemcpyDeviceToHost, s));
+    RLR_TRY(pin_reserve(c, (MmrResults::words(1, P) + 3) * 4));
+    Carver pin(c->h_pin); // (upload_list's copy out of it is ahead on the stream)
+    const MmrResults h(pin, 1, P);
+    RLR_HIP(hipMemcpyAsync(h.order, ws.res.order, MmrResults::words(1, P) * 4, hipMemcpyDeviceToHost, s));
     RLR_HIP(hipStreamSynchronize(s));
     if (timed)
         note_mmr(ix, c, 1);
-    const uint32_t *h_order = static_cast<const uint32_t *>(c->h_pin);
-    const float *h_mmr = reinterpret_cast<const float *>(h_order + P);
-    const uint32_t n_sel = h_order[2 * P];
+    const uint32_t n_sel = h.n[0];
     for (uint32_t i = 0; i < n_sel; ++i) {
-        order_out[i] = h_order[i];
+        order_out[i] = h.order[i];
         if (mmr_out)
-            mmr_out[i] = h_mmr[i];
+            mmr_out[i] = h.mmr[i];
     }
     *n_out = n_sel;
     return RLR_OK;
@@ -3009,47 +3189,24 @@ int32_t rlr_search_diverse(rlr_index *ix, const float *query, uint32_t pool, uin
     RLR_TRY(ctx_acquire(ix, &lease.c));
     Ctx *c = lease.c;
     hipStream_t s = c->stream;
-    SearchPlan p;
-    p.k = fetch;
-    plan_bands(ix, query, 1, &p);
-    const float eps = (guard_eps >= 0.0f ? guard_eps : rlr_default_guard_eps(ix->dim)) * p.scale;
-    p.two_eps = 2.0f * eps;
-    p.two_eps_img = image_two_eps(ix, eps, p);
-    count_f16_fallbacks(ix, p, 1, false);
-    p.cap = kLdsSortCap;
+    const SearchPlan p = make_plan(ix, query, 1, fetch, guard_eps);
     RLR_TRY(ctx_prepare(ix, c, 1, p));
+    count_f16_fallbacks(ix, p, 1, false);
     const uint32_t P = need;
-    const uint32_t k_cap = std::max<uint32_t>(std::min<uint32_t>(std::max<uint32_t>(k, 1u), P), 1u);
-    // workspace: pool P x dim | gram P x P | combined P | cos P | order P | mmr P | n_sel, info[2]
-    const uint64_t floats = static_cast<uint64_t>(P) * ix->dim + static_cast<uint64_t>(P) * P + 4ull * P + 8;
-    RLR_TRY(grow(&c->d_pool, &c->pool_cap, floats));
-    if (c->list_cap < P || !c->d_list) {
-        const uint64_t zero = 0;
-        RLR_TRY(upload_list(ix, c, &zero, 1)); // (allocates the list for >= 1024 rows)
-    }
-    float *d_pool = c->d_pool;
-    float *d_gram = d_pool + static_cast<uint64_t>(P) * ix->dim;
-    float *d_comb = d_gram + static_cast<uint64_t>(P) * P;
-    float *d_cos = d_comb + P;
-    uint32_t *d_order = reinterpret_cast<uint32_t *>(d_cos + P);
-    float *d_mmr = d_cos + 2ull * P;
-    uint32_t *d_nsel = reinterpret_cast<uint32_t *>(d_cos + 3ull * P);
-    uint32_t *d_info = d_nsel + 1;
-    const size_t q_bytes = static_cast<size_t>(ix->q_pitch) * sizeof(float);
-    const size_t out_words = 4ull * k_cap + 4;
-    RLR_TRY(pin_reserve(c, q_bytes + out_words * 4 + 64));
-    float *h_q = static_cast<float *>(c->h_pin);
-    uint32_t *h_out = reinterpret_cast<uint32_t *>(static_cast<char *>(c->h_pin) + q_bytes);
-    h_out[4 * k_cap + 3] = kBlockPending; // (the greedy kernel's last store replaces it: what the wait below polls)
-    std::memset(h_q, 0, q_bytes);
-    std::memcpy(h_q, query, ix->dim * sizeof(float));
-    stage_query_norms(ix, c, query, 1);
-    c->hist_dirty = true;
+    const uint32_t k_cap = rlr::result_k_cap(k, P, true);
+    const DiverseWs sizes(nullptr, nullptr, ix, P, k_cap);
+    RLR_TRY(grow(&c->d_pool, &c->pool_cap, sizes.d.floats()));
+    RLR_TRY(reserve_list(c, P));
+    RLR_TRY(pin_reserve(c, sizes.h.bytes));
+    const DiverseWs ws(c->d_pool, c->h_pin, ix, P, k_cap);
+    uint32_t *h_out = ws.h_out;
+    h_out[block_done(k_cap)] = kBlockPending; // (the greedy kernel's last store replaces it: what the wait below polls)
+    stage_queries(ix, c, query, 1, ws.h_q);
     const bool timed = ix->profiling;
-    RLR_HIP(stage_queries_for_scans(ix, c, h_q, q_bytes, s));
+    RLR_HIP(stage_queries_for_scans(ix, c, ws.h_q, static_cast<size_t>(ix->q_pitch) * sizeof(float), s));
     uint64_t *d_meta = c->d_out + fetch;
     const bool from_candidates = fetch <= 512; // (the band of a larger fetch rarely fits 1024)
-    const PoolArgs pa{fetch, need, n, w_embedding, w_lexical, c->d_list, d_comb, d_cos, d_info};
+    const PoolArgs pa{fetch, need, n, w_embedding, w_lexical, c->d_list, ws.comb, ws.cos, ws.info};
     bool pool_done = false; // (the fused tail's finish builds the pool itself: one launch and ~13 us of config 2's chain less)
     RLR_HIP(enqueue_query(ix, c, 0, p, c->d_out, d_meta, timed, /*emit=*/!from_candidates, from_candidates ? &pa : nullptr,
                           &pool_done));
@@ -3061,15 +3218,9 @@ int32_t rlr_search_diverse(rlr_index *ix, const float *query, uint32_t pool, uin
             hipLaunchKernelGGL(rlr::pool_prepare_kernel<false>, dim3(1), dim3(1024), 0, s, c->d_out, c->d_state, pa);
         RLR_HIP(hipGetLastError());
     }
-    RLR_HIP(launch_gram_rows(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_list, P, d_gram, 1, s));
-    rlr::MmrEmit emit; // the greedy kernel writes the picks into the pinned block itself
-    emit.list = c->d_list;
-    emit.comb = d_comb;
-    emit.cosv = d_cos;
-    emit.info = d_info;
-    emit.k_cap = k_cap;
-    emit.h_out = h_out;
-    RLR_HIP(launch_mmr_greedy(d_gram, d_comb, P, k, lambda, d_order, d_mmr, d_nsel, d_info, 1, s, &emit));
+    RLR_HIP(launch_gram_rows(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_list, P, ws.gram, 1, s));
+    const rlr::MmrEmit emit = mmr_emit(c->d_list, ws.comb, ws.cos, nullptr, ws.info, k_cap, h_out);
+    RLR_HIP(launch_mmr_greedy(ws.gram, ws.comb, P, k, lambda, ws.order, ws.mmr, ws.nsel, ws.info, 1, s, &emit));
     if (timed) RLR_HIP(hipEventRecord(c->bev[1], s));
     if (timed)
         RLR_HIP(hipStreamSynchronize(s)); // (the events are read below)
@@ -3077,36 +3228,8 @@ int32_t rlr_search_diverse(rlr_index *ix, const float *query, uint32_t pool, uin
         RLR_TRY(wait_block(h_out, k_cap, s, &c->wait_ema));
     RLR_TRY(check_hist_assert(c));
     c->hist_dirty = false;
-    const uint32_t n_sel = h_out[4 * k_cap], status = h_out[4 * k_cap + 1];
-    {
-        std::lock_guard<std::mutex> lk(ix->mu);
-        ix->prof.n_searches += 1;
-        if (timed) {
-            float a = 0, b = 0, d = 0, m = 0;
-            (void)hipEventElapsedTime(&a, c->ev[0], c->ev[1]);
-            (void)hipEventElapsedTime(&b, c->ev[1], c->ev[2]);
-            (void)hipEventElapsedTime(&d, c->ev[2], c->ev[3]);
-            (void)hipEventElapsedTime(&m, c->bev[0], c->bev[1]);
-            ix->prof.n_scan_launches += 1;
-            ix->prof.scan_ms += a;
-            ix->prof.select_ms += b;
-            ix->prof.rescore_ms += d;
-            ix->prof.total_ms += a + b + d + m;
-            ix->prof.scan_bytes += ix->n_rows * ix->dim * (scan_over_q8(ix) ? 1 : (ix->dtype == RLR_F16 || scan_over_image(ix, c)) ? 2 : 4);
-            ix->prof.n_mmr += 1;
-            ix->prof.mmr_ms += m;
-        }
-    }
-    if (status != 0) {
-        *fallback = static_cast<int32_t>(status);
-        return RLR_OK;
-    }
-    for (uint32_t i = 0; i < n_sel; ++i) {
-        rows_out[i] = h_out[i];
-        cos_out[i] = __builtin_bit_cast(float, h_out[k_cap + i]);
-        score_out[i] = __builtin_bit_cast(float, h_out[2 * k_cap + i]);
-    }
-    *n_out = n_sel;
+    (void)note_search(ix, c, 1, 0, 0, timed, /*mmr_chain=*/true);
+    *fallback = static_cast<int32_t>(read_block(h_out, k_cap, rows_out, cos_out, score_out, nullptr, n_out));
     return RLR_OK;
 }
 
@@ -3130,11 +3253,14 @@ namespace rlr {
 struct HybridTicket {
     rlr_index *ix;
     CtxLease lease;
-    uint32_t n, need, fetch, n_lex_bound, k, k_cap;
+    uint32_t n, need, fetch, k, k_cap;
     float lambda, w_e, w_l;
     int32_t diversify;
     bool timed;
-    size_t q_bytes, lex_bytes_cap;
+    // begin hands the lexical side of it to the BM25 kernels (LexSink), finish blends from the same object.  It points into
+    // c->d_pool and c->h_pin: the ticket holds the context's lease, and nothing may grow() / pin_reserve() on this context
+    // between begin and finish.
+    HybridWs ws;
     explicit HybridTicket(rlr_index *i) : ix(i), lease(i) {}
 };
 
@@ -3169,30 +3295,21 @@ static int32_t hybrid_begin_impl(rlr_index *ix, const float *query, uint32_t nee
     RLR_TRY(ctx_acquire(ix, &t->lease.c));
     Ctx *c = t->lease.c;
     hipStream_t s = c->stream;
-    SearchPlan p;
-    p.k = fetch;
-    plan_bands(ix, query, 1, &p);
-    const float eps = (guard_eps >= 0.0f ? guard_eps : rlr_default_guard_eps(ix->dim)) * p.scale;
-    p.two_eps = 2.0f * eps;
-    p.two_eps_img = image_two_eps(ix, eps, p);
-    count_f16_fallbacks(ix, p, 1, false);
-    p.cap = kLdsSortCap;
-    p.unordered = true; // the blend orders fetched and lexical rows together: it needs the fetched SET and its minimum
+    // unordered: the blend orders fetched and lexical rows together -- it needs the fetched SET and its minimum
+    const SearchPlan p = make_plan(ix, query, 1, fetch, guard_eps, /*unordered=*/true);
     RLR_TRY(ctx_prepare(ix, c, 1, p));
+    count_f16_fallbacks(ix, p, 1, false);
     const uint32_t P = need;
-    const uint32_t k_cap = diversify ? std::max<uint32_t>(std::min<uint32_t>(std::max<uint32_t>(k, 1u), P), 1u) : P;
-    // workspace (4-byte words): gram P x P | combined P | cos P | lex P | order P | mmr P | n_sel, info[2], pad |
-    //                           header[2] | lexical rows | scores | cosines (bound each) | candidate combined / cos / lex
-    const uint64_t words = static_cast<uint64_t>(P) * P + 5ull * P + 8 + 2 + 3ull * n_lex_bound + 3ull * kHybridSlots;
-    RLR_TRY(grow(&c->d_pool, &c->pool_cap, words));
-    if (c->list_cap < P || !c->d_list) {
-        const uint64_t zero = 0;
-        RLR_TRY(upload_list(ix, c, &zero, 1)); // (allocates the list for >= 1024 rows)
-    }
+    const uint32_t k_cap = result_k_cap(k, P, diversify != 0);
+    const HybridWs sizes(nullptr, nullptr, ix->q_pitch, P, n_lex_bound, k_cap);
+    RLR_TRY(grow(&c->d_pool, &c->pool_cap, sizes.d.floats()));
+    RLR_TRY(reserve_list(c, P));
+    RLR_TRY(pin_reserve(c, sizes.h.bytes));
+    t->ws = HybridWs(c->d_pool, c->h_pin, ix->q_pitch, P, n_lex_bound, k_cap);
+    const HybridWs &ws = t->ws;
     t->n = n;
     t->need = need;
     t->fetch = fetch;
-    t->n_lex_bound = n_lex_bound;
     t->k = k;
     t->k_cap = k_cap;
     t->lambda = lambda;
@@ -3200,37 +3317,19 @@ static int32_t hybrid_begin_impl(rlr_index *ix, const float *query, uint32_t nee
     t->w_l = w_lexical;
     t->diversify = diversify;
     t->timed = ix->profiling;
-    t->q_bytes = static_cast<size_t>(ix->q_pitch) * sizeof(float);
-    t->lex_bytes_cap = 8 + static_cast<size_t>(n_lex_bound) * 8; // header | rows | scores, one copy
-    RLR_TRY(pin_reserve(c, t->q_bytes + t->lex_bytes_cap + (4ull * k_cap + 4) * 4 + 64));
-    float *h_q = static_cast<float *>(c->h_pin);
-    std::memset(h_q, 0, t->q_bytes);
-    std::memcpy(h_q, query, ix->dim * sizeof(float));
-    stage_query_norms(ix, c, query, 1);
-    c->hist_dirty = true;
-    // from here on work may be queued on `s`: an error exit drains it before the lease hands the context back
-    struct Drain {
-        hipStream_t s;
-        bool armed = true;
-        ~Drain()
-        {
-            if (armed)
-                (void)hipStreamSynchronize(s);
-        }
-    } drain{s};
-    RLR_HIP(stage_queries_for_scans(ix, c, h_q, t->q_bytes, s));
+    stage_queries(ix, c, query, 1, ws.h_q);
+    StreamDrain drain{s};
+    RLR_HIP(stage_queries_for_scans(ix, c, ws.h_q, static_cast<size_t>(ix->q_pitch) * sizeof(float), s));
     uint64_t *d_meta = c->d_out + fetch;
     // the scan first; then whatever the caller runs beside it (the BM25 chain on its own stream: about as long as scan +
     // select + re-score + sort, so it must not wait for the host to have launched those -- it used to start 39 us behind the
     // scan and was the critical path by as much); then the four launches that wait for the scan anyway
     RLR_HIP(enqueue_query_scan(ix, c, 0, t->timed));
     if (behind_scan) {
-        // (the lexical side of the workspace as hybrid_finish_impl lays it out for pairs that stay on the device)
-        uint32_t *d_nsel = reinterpret_cast<uint32_t *>(c->d_pool + static_cast<uint64_t>(P) * P + 5ull * P);
-        LexSink sink;
-        sink.d_header = d_nsel + 8;
-        sink.d_rows = d_nsel + 10;
-        sink.d_scores = reinterpret_cast<float *>(sink.d_rows + n_lex_bound);
+        LexSink sink; // (pairs that stay on the device fill every slot)
+        sink.d_header = ws.hdr;
+        sink.d_rows = ws.lrow;
+        sink.d_scores = ws.lscore(n_lex_bound);
         sink.n_bound = n_lex_bound;
         sink.n_index_rows = n;
         RLR_TRY(behind_scan(behind_scan_arg, &sink));
@@ -3252,41 +3351,20 @@ static int32_t hybrid_finish_impl(HybridTicket *ticket, const HybridLexSrc &src,
     hipStream_t s = c->stream;
     *n_out = 0;
     *fallback = 0;
-    // whatever goes wrong from here on: the enqueued work may still be running on `s` when the context goes back
-    struct Drain {
-        hipStream_t s;
-        bool armed = true;
-        ~Drain()
-        {
-            if (armed)
-                (void)hipStreamSynchronize(s);
-        }
-    } drain{s};
-    const uint32_t n_lex = src.dev ? t->n_lex_bound : src.n_host;
-    if (n_lex > t->n_lex_bound || !rows_out || !cos_out || !score_out || !lex_out)
+    StreamDrain drain{s};
+    const HybridWs &ws = t->ws;
+    const uint32_t n_lex = src.dev ? static_cast<uint32_t>(ws.n_lex_bound) : src.n_host;
+    if (n_lex > ws.n_lex_bound || !rows_out || !cos_out || !score_out || !lex_out)
         return fail(RLR_E_INVALID, "hybrid search: bad arguments");
     const uint32_t P = t->need, k_cap = t->k_cap, n = t->n;
-    float *d_gram = c->d_pool;
-    float *d_comb = d_gram + static_cast<uint64_t>(P) * P;
-    float *d_cos = d_comb + P;
-    float *d_lexv = d_cos + P;
-    uint32_t *d_order = reinterpret_cast<uint32_t *>(d_lexv + P);
-    float *d_mmr = d_lexv + 2ull * P;
-    uint32_t *d_nsel = reinterpret_cast<uint32_t *>(d_lexv + 3ull * P);
-    uint32_t *d_info = d_nsel + 1;
-    HybridLexHeader *d_hdr = reinterpret_cast<HybridLexHeader *>(d_nsel + 8);
-    uint32_t *d_lrow = d_nsel + 10;
-    float *d_lscore = reinterpret_cast<float *>(d_lrow + n_lex);
-    float *d_lcos = d_lscore + t->n_lex_bound;
-    float *d_cand = d_lcos + t->n_lex_bound;
-    uint32_t *h_lex = reinterpret_cast<uint32_t *>(static_cast<char *>(c->h_pin) + t->q_bytes);
-    uint32_t *h_out = reinterpret_cast<uint32_t *>(static_cast<char *>(c->h_pin) + t->q_bytes + t->lex_bytes_cap);
-    h_out[4 * k_cap + 3] = kBlockPending; // (the last kernel's last store replaces it: what the wait below polls)
+    float *d_lscore = ws.lscore(n_lex);
+    uint32_t *h_lex = ws.h_lex, *h_out = ws.h_out;
+    h_out[block_done(k_cap)] = kBlockPending; // (the last kernel's last store replaces it: what the wait below polls)
     if (src.dev) { // the BM25 kernels ran beside the scan on their own stream: join, then unpack their result
         RLR_HIP(hipStreamWaitEvent(s, static_cast<hipEvent_t>(src.dev->ready), 0));
         if (!src.dev->unpacked) { // (begin's LexSink: the scoring stream has done it in front of `ready`)
             hipLaunchKernelGGL(lex_unpack_kernel, dim3(1), dim3(1024), 0, s, src.dev->d_packed, src.dev->d_count,
-                               std::min(n_lex, src.dev->limit), n, d_lrow, d_lscore, d_hdr);
+                               std::min(n_lex, src.dev->limit), n, ws.lrow, d_lscore, ws.hdr);
             RLR_HIP(hipGetLastError());
         }
     } else {
@@ -3298,28 +3376,20 @@ static int32_t hybrid_finish_impl(HybridTicket *ticket, const HybridLexSrc &src,
         for (uint32_t i = 0; i < n_lex; ++i)
             h_lex[2 + i] = static_cast<uint32_t>(src.h_rows[i]);
         if (n_lex)
-            std::memcpy(h_lex + 2 + n_lex, src.h_scores, static_cast<size_t>(n_lex) * sizeof(float));
-        // header, rows, scores are adjacent on both sides
-        RLR_HIP(hipMemcpyAsync(d_hdr, h_lex, 8 + static_cast<size_t>(n_lex) * 8, hipMemcpyHostToDevice, s));
+            std::memcpy(HybridWs::h_lscore(h_lex, n_lex), src.h_scores, static_cast<size_t>(n_lex) * sizeof(float));
+        RLR_HIP(hipMemcpyAsync(ws.hdr, h_lex, HybridWs::lex_copy_bytes(n_lex), hipMemcpyHostToDevice, s));
     }
-    RLR_HIP(launch_score_rows(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_query, d_lrow, n_lex, d_lcos, s,
-                              src.dev ? &d_hdr->n_lex : nullptr, n));
+    RLR_HIP(launch_score_rows(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_query, ws.lrow, n_lex, ws.lcos, s,
+                              src.dev ? &ws.hdr->n_lex : nullptr, n));
     const bool pool_emits = !t->diversify; // (without diversification the blend kernel emits by itself)
-    hipLaunchKernelGGL(hybrid_pool_kernel, dim3(1), dim3(1024), 0, s, c->d_out, t->fetch, t->need, n, t->w_e, t->w_l, d_lrow,
-                       d_lscore, d_lcos, d_hdr, d_cand, c->d_list, d_comb, d_cos, d_lexv, d_info, k_cap,
+    hipLaunchKernelGGL(hybrid_pool_kernel, dim3(1), dim3(1024), 0, s, c->d_out, t->fetch, t->need, n, t->w_e, t->w_l, ws.lrow,
+                       d_lscore, ws.lcos, ws.hdr, ws.cand, c->d_list, ws.comb, ws.cos, ws.lexv, ws.info, k_cap,
                        pool_emits ? h_out : static_cast<uint32_t *>(nullptr));
     RLR_HIP(hipGetLastError());
     if (t->diversify) {
-        RLR_HIP(launch_gram_rows(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_list, P, d_gram, 1, s));
-        MmrEmit emit; // the greedy kernel writes the picks into the pinned block itself
-        emit.list = c->d_list;
-        emit.comb = d_comb;
-        emit.cosv = d_cos;
-        emit.lexv = d_lexv;
-        emit.info = d_info;
-        emit.k_cap = k_cap;
-        emit.h_out = h_out;
-        RLR_HIP(launch_mmr_greedy(d_gram, d_comb, P, t->k, t->lambda, d_order, d_mmr, d_nsel, d_info, 1, s, &emit));
+        RLR_HIP(launch_gram_rows(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_list, P, ws.gram, 1, s));
+        const MmrEmit emit = mmr_emit(c->d_list, ws.comb, ws.cos, ws.lexv, ws.info, k_cap, h_out);
+        RLR_HIP(launch_mmr_greedy(ws.gram, ws.comb, P, t->k, t->lambda, ws.order, ws.mmr, ws.nsel, ws.info, 1, s, &emit));
     }
     if (t->timed) RLR_HIP(hipEventRecord(c->bev[1], s));
     if (t->timed) {
@@ -3331,37 +3401,8 @@ static int32_t hybrid_finish_impl(HybridTicket *ticket, const HybridLexSrc &src,
     }
     RLR_TRY(check_hist_assert(c));
     c->hist_dirty = false;
-    const uint32_t n_sel = h_out[4 * k_cap], status = h_out[4 * k_cap + 1];
-    {
-        std::lock_guard<std::mutex> lk(ix->mu);
-        ix->prof.n_searches += 1;
-        if (t->timed) {
-            float a = 0, b = 0, d = 0, m = 0;
-            (void)hipEventElapsedTime(&a, c->ev[0], c->ev[1]);
-            (void)hipEventElapsedTime(&b, c->ev[1], c->ev[2]);
-            (void)hipEventElapsedTime(&d, c->ev[2], c->ev[3]);
-            (void)hipEventElapsedTime(&m, c->bev[0], c->bev[1]);
-            ix->prof.n_scan_launches += 1;
-            ix->prof.scan_ms += a;
-            ix->prof.select_ms += b;
-            ix->prof.rescore_ms += d;
-            ix->prof.total_ms += a + b + d + m;
-            ix->prof.scan_bytes += ix->n_rows * ix->dim * (scan_over_q8(ix) ? 1 : (ix->dtype == RLR_F16 || scan_over_image(ix, c)) ? 2 : 4);
-            ix->prof.n_mmr += 1;
-            ix->prof.mmr_ms += m;
-        }
-    }
-    if (status != 0) {
-        *fallback = static_cast<int32_t>(status);
-        return RLR_OK;
-    }
-    for (uint32_t i = 0; i < n_sel; ++i) {
-        rows_out[i] = h_out[i];
-        cos_out[i] = __builtin_bit_cast(float, h_out[k_cap + i]);
-        score_out[i] = __builtin_bit_cast(float, h_out[2 * k_cap + i]);
-        lex_out[i] = __builtin_bit_cast(float, h_out[3 * k_cap + i]);
-    }
-    *n_out = n_sel;
+    (void)note_search(ix, c, 1, 0, 0, t->timed, /*mmr_chain=*/true);
+    *fallback = static_cast<int32_t>(read_block(h_out, k_cap, rows_out, cos_out, score_out, lex_out, n_out));
     return RLR_OK;
 }
 
@@ -3426,55 +3467,24 @@ int32_t search_hybrid_batch(rlr_index *ix, const float *queries, uint32_t nq, ui
     RLR_TRY(ctx_acquire(ix, &lease.c));
     Ctx *c = lease.c;
     hipStream_t s = c->stream;
-    const uint32_t P = need, B = n_lex_bound, qp = ix->q_pitch;
-    const uint32_t k_cap = diversify ? std::max<uint32_t>(std::min<uint32_t>(std::max<uint32_t>(k, 1u), P), 1u) : P;
-    // workspace (4-byte words): fetched keys nq x fetch (u64) | queries nq x q_pitch | lexical rows, scores, cosines nq x B
-    // each | headers nq x 2 | blend candidates nq x 3 x kHybridSlots | results: list, combined, cos, lex, order, mmr nq x P
-    // each, n_sel nq, sizes nq, info 2 nq | gram nq x P x P (diversify)
+    const uint32_t P = need, B = n_lex_bound;
+    const uint32_t k_cap = result_k_cap(k, P, diversify != 0);
     const uint64_t Q = nq;
-    const uint64_t o_q = 2 * Q * fetch, o_lrow = o_q + Q * qp, o_lsc = o_lrow + Q * B, o_lcos = o_lsc + Q * B;
-    const uint64_t o_hdr = o_lcos + Q * B, o_cand = o_hdr + 2 * Q, o_res = o_cand + Q * 3 * kHybridSlots;
-    const uint64_t res_words = 6 * Q * P + 4 * Q, o_gram = o_res + res_words;
-    const uint64_t words = o_gram + (diversify ? Q * P * P : 0);
-    RLR_TRY(grow(&c->d_pool, &c->pool_cap, words));
-    float *w = c->d_pool;
-    uint64_t *d_packed = reinterpret_cast<uint64_t *>(w);
-    float *d_q = w + o_q;
-    uint32_t *d_lrow = reinterpret_cast<uint32_t *>(w + o_lrow);
-    float *d_lscore = w + o_lsc, *d_lcos = w + o_lcos;
-    HybridLexHeader *d_hdr = reinterpret_cast<HybridLexHeader *>(w + o_hdr);
-    float *d_cand = w + o_cand;
-    uint32_t *d_list = reinterpret_cast<uint32_t *>(w + o_res);
-    float *d_comb = w + o_res + Q * P, *d_cos = w + o_res + 2 * Q * P, *d_lexv = w + o_res + 3 * Q * P;
-    uint32_t *d_order = reinterpret_cast<uint32_t *>(w + o_res + 4 * Q * P);
-    float *d_mmr = w + o_res + 5 * Q * P;
-    uint32_t *d_nsel = reinterpret_cast<uint32_t *>(w + o_res + 6 * Q * P);
-    uint32_t *d_sizes = d_nsel + Q, *d_info = d_nsel + 2 * Q;
-    float *d_gram = w + o_gram;
+    RLR_TRY(grow(&c->d_pool, &c->pool_cap, HybridBatchWs(nullptr, ix, Q, fetch, P, B, diversify != 0).d.floats()));
+    const HybridBatchWs ws(c->d_pool, ix, Q, fetch, P, B, diversify != 0);
     // whatever goes wrong from here on: the BM25 chain (another stream, writing into this workspace) and this stream must
     // be drained before the context goes back
-    struct Drain {
-        hipStream_t s;
-        hipEvent_t lex_ready = nullptr;
-        bool armed = true;
-        ~Drain()
-        {
-            if (lex_ready)
-                (void)hipEventSynchronize(lex_ready);
-            if (armed)
-                (void)hipStreamSynchronize(s);
-        }
-    } drain{s};
+    StreamDrain drain{s};
     // 1. the BM25 chain on the lexical index' stream, into this workspace
     LexBatchSink sink;
-    sink.d_rows = d_lrow;
-    sink.d_scores = d_lscore;
-    sink.d_headers = d_hdr;
+    sink.d_rows = ws.lrow;
+    sink.d_scores = ws.lscore;
+    sink.d_headers = ws.hdr;
     sink.bound = B;
     sink.n_index_rows = n;
     void *ready = nullptr;
     RLR_TRY(lex_launch(lex_arg, &sink, &ready));
-    drain.lex_ready = static_cast<hipEvent_t>(ready);
+    drain.also = static_cast<hipEvent_t>(ready);
     // 2. beside it: the fetch of every query, the batched top-k (GEMM / shared scan / per-query pipeline as the planner picks);
     //    its overflow handling needs the host, hence the first synchronisation
     SearchPlan p;
@@ -3486,48 +3496,42 @@ int32_t search_hybrid_batch(rlr_index *ix, const float *queries, uint32_t nq, ui
     // too small for a shared pass -- write their results straight into pinned host memory, not into c->d_out, so the host
     // copy is the one place every path leaves them; Q x fetch x 8 bytes each way)
     std::vector<uint64_t> fetched(h, h + Q * fetch); // (the pinned buffer is re-laid out below)
-    const size_t b_packed = Q * fetch * 8, b_q = Q * qp * 4, b_res = res_words * 4;
-    RLR_TRY(pin_reserve(c, b_packed + b_q + b_res + 64));
-    char *hp = static_cast<char *>(c->h_pin);
-    std::memcpy(hp, fetched.data(), b_packed);
-    float *h_q = reinterpret_cast<float *>(hp + b_packed);
-    std::memset(h_q, 0, b_q);
-    for (uint32_t q = 0; q < nq; ++q)
-        std::memcpy(h_q + static_cast<size_t>(q) * qp, queries + static_cast<size_t>(q) * ix->dim, ix->dim * sizeof(float));
-    RLR_HIP(hipMemcpyAsync(d_packed, hp, b_packed, hipMemcpyHostToDevice, s));
-    RLR_HIP(hipMemcpyAsync(d_q, h_q, b_q, hipMemcpyHostToDevice, s));
+    RLR_TRY(pin_reserve(c, HybridBatchPin(nullptr, ix, Q, fetch, P).h.bytes));
+    const HybridBatchPin pin(c->h_pin, ix, Q, fetch, P);
+    const size_t b_packed = Q * fetch * sizeof(uint64_t), b_q = Q * ix->q_pitch * sizeof(float);
+    std::memcpy(pin.packed, fetched.data(), b_packed);
+    pad_queries(ix, queries, nq, pin.q);
+    RLR_HIP(hipMemcpyAsync(ws.packed, pin.packed, b_packed, hipMemcpyHostToDevice, s));
+    RLR_HIP(hipMemcpyAsync(ws.q, pin.q, b_q, hipMemcpyHostToDevice, s));
     // 3. join the BM25 chain; exact cosines of the lexical rows, blend, order, cut -- one workgroup per query
     RLR_HIP(hipStreamWaitEvent(s, static_cast<hipEvent_t>(ready), 0));
-    RLR_HIP(launch_score_rows_batch(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, d_q, qp, nq, d_lrow, B, d_lcos,
-                                    reinterpret_cast<const uint32_t *>(d_hdr), 2, n, s));
-    hipLaunchKernelGGL(hybrid_pool_batch_kernel, dim3(nq), dim3(1024), 0, s, d_packed, fetch, P, n, w_embedding, w_lexical, B,
-                       d_lrow, d_lscore, d_lcos, d_hdr, d_cand, d_list, d_comb, d_cos, d_lexv, d_info, d_sizes);
+    RLR_HIP(launch_score_rows_batch(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, ws.q, ix->q_pitch, nq, ws.lrow, B, ws.lcos,
+                                    reinterpret_cast<const uint32_t *>(ws.hdr), 2, n, s));
+    const HybridBatchRes &d = ws.res, &r = pin.res;
+    hipLaunchKernelGGL(hybrid_pool_batch_kernel, dim3(nq), dim3(1024), 0, s, ws.packed, fetch, P, n, w_embedding, w_lexical, B,
+                       ws.lrow, ws.lscore, ws.lcos, ws.hdr, ws.cand, d.list, d.comb, d.cos, d.lexv, d.info, d.sizes);
     RLR_HIP(hipGetLastError());
     // 4. MMR over every pool at once
     if (diversify) {
-        RLR_HIP(launch_gram_rows(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, d_list, P, d_gram, nq, s));
-        RLR_HIP(launch_mmr_greedy(d_gram, d_comb, P, k, lambda, d_order, d_mmr, d_nsel, d_sizes, nq, s));
+        RLR_HIP(launch_gram_rows(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, d.list, P, ws.gram, nq, s));
+        RLR_HIP(launch_mmr_greedy(ws.gram, d.comb, P, k, lambda, d.order, d.mmr, d.nsel, d.sizes, nq, s));
     }
-    uint32_t *h_res = reinterpret_cast<uint32_t *>(hp + b_packed + b_q);
-    RLR_HIP(hipMemcpyAsync(h_res, d_list, b_res, hipMemcpyDeviceToHost, s));
+    RLR_HIP(hipMemcpyAsync(r.list, d.list, HybridBatchRes::words(Q, P) * 4, hipMemcpyDeviceToHost, s));
     RLR_HIP(hipStreamSynchronize(s));
     drain.armed = false;
-    const uint32_t *h_list = h_res, *h_order = h_res + 4 * Q * P, *h_nsel = h_res + 6 * Q * P, *h_info = h_nsel + 2 * Q;
-    const float *h_comb = reinterpret_cast<const float *>(h_res + Q * P), *h_cos = reinterpret_cast<const float *>(h_res + 2 * Q * P);
-    const float *h_lex = reinterpret_cast<const float *>(h_res + 3 * Q * P);
     for (uint32_t q = 0; q < nq; ++q) {
-        status[q] = h_info[2 * q + 1];
+        status[q] = r.info[2 * q + 1];
         n_out[q] = 0;
         if (status[q])
             continue;
         const size_t base = static_cast<size_t>(q) * P, ob = static_cast<size_t>(q) * k_cap;
-        const uint32_t cnt = std::min<uint32_t>(diversify ? h_nsel[q] : h_info[2 * q], k_cap);
+        const uint32_t cnt = std::min<uint32_t>(diversify ? r.nsel[q] : r.info[2 * q], k_cap);
         for (uint32_t i = 0; i < cnt; ++i) {
-            const size_t o = base + (diversify ? h_order[base + i] : i);
-            rows_out[ob + i] = h_list[o];
-            cos_out[ob + i] = h_cos[o];
-            score_out[ob + i] = h_comb[o];
-            lex_out[ob + i] = h_lex[o];
+            const size_t o = base + (diversify ? r.order[base + i] : i);
+            rows_out[ob + i] = r.list[o];
+            cos_out[ob + i] = r.cos[o];
+            score_out[ob + i] = r.comb[o];
+            lex_out[ob + i] = r.lexv[o];
         }
         n_out[q] = cnt;
     }
@@ -3603,12 +3607,7 @@ static int32_t mmr_batch_impl(rlr_index *ix, const uint64_t *pool_rows, const fl
         for (uint32_t q = 0; q < m; ++q)
             if (pool_sizes[q0 + q] > P)
                 return fail(RLR_E_INVALID, "pool_sizes[%u] = %u exceeds P = %u", q0 + q, pool_sizes[q0 + q], P);
-        // pinned staging layout: [row list (upload_list)] [scores] [sizes] [results]; reserve it all
-        // BEFORE upload_list enqueues its copy so the buffer is never reallocated under a transfer
-        const size_t list_bytes = static_cast<size_t>(n_list) * 8 + 64;
-        const size_t in_bytes = static_cast<size_t>(n_list) * 4 + static_cast<size_t>(m + 4) * 4;
-        const size_t out_bytes = (2ull * n_list + m) * 4;
-        RLR_TRY(pin_reserve(c, list_bytes + in_bytes + out_bytes + 64));
+        RLR_TRY(pin_reserve(c, MmrStaging(nullptr, m, P).h.bytes));
         if (pool_rows) {
             // unused slots (j >= pool_sizes[q]) gather row 0: never read by the greedy kernel
             bool all_full = true;
@@ -3624,45 +3623,31 @@ static int32_t mmr_batch_impl(rlr_index *ix, const uint64_t *pool_rows, const fl
             }
             RLR_TRY(upload_list(ix, c, src_rows, n_list, d_matrix ? n_matrix : ~0ull));
         }
-        const uint64_t pool_floats = 0; // (the pool rows are read in place)
-        const uint64_t floats = pool_floats + static_cast<uint64_t>(m) * P * P + 3ull * n_list + 2ull * m + 8;
-        RLR_TRY(grow(&c->d_pool, &c->pool_cap, floats));
-        float *d_pool = c->d_pool;
-        float *d_gram = d_pool + pool_floats;
-        float *d_sc = d_gram + static_cast<uint64_t>(m) * P * P;
-        uint32_t *d_order = reinterpret_cast<uint32_t *>(d_sc + n_list);
-        float *d_mmr = d_sc + 2ull * n_list;
-        uint32_t *d_n = reinterpret_cast<uint32_t *>(d_sc + 3ull * n_list);
-        uint32_t *d_sizes = d_n + m;
-        char *h_base = static_cast<char *>(c->h_pin) + list_bytes;
-        float *h_sc = reinterpret_cast<float *>(h_base);
-        uint32_t *h_sizes = reinterpret_cast<uint32_t *>(h_sc + n_list);
-        std::memcpy(h_sc, pool_scores + static_cast<size_t>(q0) * P, static_cast<size_t>(n_list) * sizeof(float));
-        std::memcpy(h_sizes, pool_sizes + q0, m * sizeof(uint32_t));
-        RLR_HIP(hipMemcpyAsync(d_sc, h_sc, static_cast<size_t>(n_list) * sizeof(float), hipMemcpyHostToDevice, s));
-        RLR_HIP(hipMemcpyAsync(d_sizes, h_sizes, m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        RLR_TRY(grow(&c->d_pool, &c->pool_cap, MmrWs(nullptr, m, P).d.floats()));
+        const MmrWs ws(c->d_pool, m, P);
+        const MmrStaging h(c->h_pin, m, P);
+        std::memcpy(h.scores, pool_scores + static_cast<size_t>(q0) * P, static_cast<size_t>(n_list) * sizeof(float));
+        std::memcpy(h.sizes, pool_sizes + q0, m * sizeof(uint32_t));
+        RLR_HIP(hipMemcpyAsync(ws.scores, h.scores, static_cast<size_t>(n_list) * sizeof(float), hipMemcpyHostToDevice, s));
+        RLR_HIP(hipMemcpyAsync(ws.sizes, h.sizes, m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         const bool timed = ix->profiling;
         if (timed) RLR_HIP(hipEventRecord(c->ev[0], s));
         if (pool_rows) // the Gram kernel reads the index rows through the list: no gathered copy
-            RLR_HIP(launch_gram_rows(d_matrix ? d_matrix : ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_list, P, d_gram, m, s));
+            RLR_HIP(launch_gram_rows(d_matrix ? d_matrix : ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_list, P, ws.gram, m, s));
         else
-            RLR_HIP(launch_gram(d_values + static_cast<size_t>(q0) * P * ix->dim, P, ix->dim, d_gram, m, s));
-        RLR_HIP(launch_mmr_greedy(d_gram, d_sc, P, k, lambda, d_order, d_mmr, d_n, d_sizes, m, s));
+            RLR_HIP(launch_gram(d_values + static_cast<size_t>(q0) * P * ix->dim, P, ix->dim, ws.gram, m, s));
+        RLR_HIP(launch_mmr_greedy(ws.gram, ws.scores, P, k, lambda, ws.res.order, ws.res.mmr, ws.res.n, ws.sizes, m, s));
         if (timed) RLR_HIP(hipEventRecord(c->ev[1], s));
-        // results: order | mmr | n are contiguous
-        uint32_t *h_res = reinterpret_cast<uint32_t *>(h_sizes + m + 4);
-        RLR_HIP(hipMemcpyAsync(h_res, d_order, (2ull * n_list + m) * 4, hipMemcpyDeviceToHost, s));
+        RLR_HIP(hipMemcpyAsync(h.res.order, ws.res.order, MmrResults::words(m, P) * 4, hipMemcpyDeviceToHost, s));
         RLR_HIP(hipStreamSynchronize(s));
         if (timed)
             note_mmr(ix, c, m);
-        const float *h_mmr = reinterpret_cast<const float *>(h_res + n_list);
-        const uint32_t *h_n = h_res + 2ull * n_list;
         for (uint32_t q = 0; q < m; ++q) {
-            const uint32_t ns = h_n[q];
+            const uint32_t ns = h.res.n[q];
             n_out[q0 + q] = ns;
-            std::memcpy(order_out + static_cast<size_t>(q0 + q) * P, h_res + static_cast<size_t>(q) * P, ns * sizeof(uint32_t));
+            std::memcpy(order_out + static_cast<size_t>(q0 + q) * P, h.res.order + static_cast<size_t>(q) * P, ns * sizeof(uint32_t));
             if (mmr_out)
-                std::memcpy(mmr_out + static_cast<size_t>(q0 + q) * P, h_mmr + static_cast<size_t>(q) * P, ns * sizeof(float));
+                std::memcpy(mmr_out + static_cast<size_t>(q0 + q) * P, h.res.mmr + static_cast<size_t>(q) * P, ns * sizeof(float));
         }
     }
     return RLR_OK;
@@ -3789,17 +3774,9 @@ int32_t rlr_index_probe_bandwidth(rlr_index *ix, int32_t mode, uint32_t reps, do
         const size_t sc_bytes = (static_cast<size_t>(ix->n_rows) + 2 * kHistBins + ix->q_pitch) * sizeof(float);
         RLR_HIP(rlr::dev_malloc(&scratch, sc_bytes));
         RLR_HIP(hipMemsetAsync(scratch, 0, sc_bytes, s));
-        ScanArgs sa;
-        sa.rows = ix->d_rows;
-        sa.scores = static_cast<float *>(scratch);
-        sa.hist = mode == 3 ? reinterpret_cast<uint32_t *>(sa.scores + ix->n_rows) : nullptr;
-        sa.query = sa.scores + ix->n_rows + 2 * kHistBins;
-        sa.n_rows = static_cast<uint32_t>(ix->n_rows);
-        sa.dim = ix->dim;
-        sa.pitch16 = ix->pitch16;
-        sa.dtype = ix->dtype;
-        sa.n_cu = ix->n_cu;
-        sa.variant = ix->scan_variant;
+        float *sc = static_cast<float *>(scratch);
+        const ScanArgs sa = scan_args(ix, sc + ix->n_rows + 2 * kHistBins, sc,
+                                      mode == 3 ? reinterpret_cast<uint32_t *>(sc + ix->n_rows) : nullptr);
         moved = static_cast<size_t>(ix->n_rows) * ix->dim * (ix->dtype == RLR_F16 ? 2 : 4);
         st = timed([&] { return launch_scan(sa, s); });
     } else {

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <vector>
 
 struct rlr_lexical;
@@ -102,11 +103,18 @@ void lexical_batch_finish(LexBatchPending *p, bool ok);
 void launch_lex_unpack_batch(const uint64_t *d_sel, uint32_t sel_stride, const uint32_t *d_count, uint32_t count_stride,
                              uint32_t nq, uint32_t limit, const LexBatchSink &sink, void *stream);
 
+// The most results a fused search returns -- MMR picks k (at least one) of the `need` pool rows, a search
+// without diversification returns the pool.
+inline uint32_t result_k_cap(uint32_t k, uint32_t need, bool diversify)
+{
+    return diversify ? std::max<uint32_t>(std::min<uint32_t>(std::max<uint32_t>(k, 1u), need), 1u) : need;
+}
+
 // index.hip: the cosine side, blend and MMR of nq hybrid searches at once.  `queries`: nq prepared (normalised, dim-long)
 // queries; `need`, `k`, `lambda`, `diversify`, weights, `n_lex_bound` as for search_hybrid_begin.  lex_launch (may be null:
 // no lexical pairs) is called once the workspace exists, before the cosine batch: it enqueues the BM25 chain into the sink
 // on its own stream and returns the event to join (*ready).  Results of query q at [q * k_cap, ...) with k_cap =
-// diversify ? max(min(max(k, 1), need), 1) : need; status[q] != 0: not decided here (1 overflow, 2 fetch boundary) --
+// result_k_cap(k, need, diversify); status[q] != 0: not decided here (1 overflow, 2 fetch boundary) --
 // the caller re-runs that query alone.  Two host synchronisations: the cosine batch and the results.
 int32_t search_hybrid_batch(rlr_index *ix, const float *queries, uint32_t nq, uint32_t need, uint32_t k, float lambda,
                             int32_t diversify, float w_embedding, float w_lexical, uint32_t n_lex_bound,

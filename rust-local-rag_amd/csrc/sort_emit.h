@@ -182,9 +182,18 @@ __device__ inline void sort_emit_body(const uint64_t *packed, uint32_t n_raw, ui
 // checksum covers the 4 x n value words plus n and status, with the same term as above.
 constexpr uint32_t kBlockPending = 0xFFFFFFFFu, kBlockDone = 1u;
 
+// Word offsets inside the block -- the only place that knows them (a value's offset is also its checksum position).
+enum BlockPlane : uint32_t { kBlockRow = 0, kBlockCos = 1, kBlockComb = 2, kBlockLex = 3, kBlockPlanes = 4 };
+__host__ __device__ constexpr uint32_t block_value(uint32_t k_cap, uint32_t plane, uint32_t i) { return plane * k_cap + i; }
+__host__ __device__ constexpr uint32_t block_n(uint32_t k_cap) { return kBlockPlanes * k_cap; }
+__host__ __device__ constexpr uint32_t block_status(uint32_t k_cap) { return kBlockPlanes * k_cap + 1; }
+__host__ __device__ constexpr uint32_t block_chk(uint32_t k_cap) { return kBlockPlanes * k_cap + 2; }
+__host__ __device__ constexpr uint32_t block_done(uint32_t k_cap) { return kBlockPlanes * k_cap + 3; }
+__host__ __device__ constexpr uint32_t block_words(uint32_t k_cap) { return kBlockPlanes * k_cap + 4; }
+
 __host__ __device__ inline uint32_t block_chk_tail(uint32_t chk_values, uint32_t n, uint32_t status, uint32_t k_cap)
 {
-    return chk_values + result_chk_term(n, 4 * k_cap) + result_chk_term(status, 4 * k_cap + 1);
+    return chk_values + result_chk_term(n, block_n(k_cap)) + result_chk_term(status, block_status(k_cap));
 }
 
 } // namespace rlr

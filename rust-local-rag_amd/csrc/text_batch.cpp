@@ -54,7 +54,8 @@ int32_t rlr_engine_search_text_batch(rlr_index *idx, rlr_lexical *lex, const flo
         return st;
     const uint64_t initial_k = std::min<uint64_t>(N, static_cast<uint64_t>(k_seen) * 3);             // :544
     const uint64_t need = (diversify || !stage) ? std::min<uint64_t>(initial_k, k_seen) : initial_k; // :667-698
-    const uint64_t n_res = diversify ? std::min<uint64_t>(std::max<uint32_t>(top_k, 1u), need) : need;
+    // (need <= N, and an index holds fewer than 2^32 rows)
+    const uint64_t n_res = rlr::result_k_cap(top_k, static_cast<uint32_t>(need), diversify);
     if (!out || cap < n_res)
         return RLR_E_INVALID; // (cap below the result count of a query)
     auto tok = [&](uint32_t q) { return tokens ? tokens + token_offsets[q] : nullptr; };
@@ -83,7 +84,7 @@ int32_t rlr_engine_search_text_batch(rlr_index *idx, rlr_lexical *lex, const flo
     }
     constexpr uint32_t kSubBatch = 256; // one GEMM query block
     const uint32_t nd = static_cast<uint32_t>(need);
-    const uint32_t k_cap = diversify ? static_cast<uint32_t>(std::min<uint64_t>(std::max<uint32_t>(top_k, 1u), nd)) : nd;
+    const uint32_t k_cap = static_cast<uint32_t>(n_res);
     // (the Gram matrices of a sub-batch stay below 256 MB)
     const uint64_t gram_q = diversify ? std::max<uint64_t>(1, (64ull << 20) / (static_cast<uint64_t>(nd) * nd)) : kSubBatch;
     const uint32_t sub = static_cast<uint32_t>(std::max<uint64_t>(2, std::min<uint64_t>(kSubBatch, gram_q)));
