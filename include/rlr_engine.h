@@ -125,6 +125,33 @@ int32_t rlr_engine_search_text_batch(rlr_index *idx, rlr_lexical *lex, const flo
                                      const rlr_query_weights *weights, rlr_search_hit *out, uint32_t cap,
                                      uint32_t *n_out, rlr_text_batch_info *info);
 
+/* ---- the same searches inside a set of rows (rlr_filter, include/rlr_gpu.h: "search only in these documents") ----
+ * search_F is the reference's search over the corpus that holds only the rows of the filter F, in ascending row order,
+ * with the rows mapped back to index rows.  Two choices are made here and hold for all three entry points:
+ *   - N is |F| everywhere the reference uses the corpus size: top_k is clamped to |F|, initial_k = min(|F|, 3 * top_k),
+ *     the MMR pool is min(|F|, max(3 * top_k, top_k + 10)), and |F| = 0 returns no hits with RLR_OK (:476-478);
+ *   - the lexical term keeps the statistics of the WHOLE lexical index (total_docs, average length, df, idf): the
+ *     filter restricts candidates, not corpus statistics.  The lexical candidates of _search_text_filtered are the
+ *     limit = 5 * k_eff best rows of F with bm25 > 0 by (bm25 desc, row asc) (rlr_lexical_score_filtered), and
+ *     max_lexical (:515-519) is taken over that list.
+ * (lex_rows given to the first two that lie outside F are not candidates, exactly as rows beyond the corpus are not in
+ * rlr_engine_search; like those they still count towards max_lexical.)  Blend, pool sizing, tie widening and fall-backs
+ * are the code of the unfiltered and sharded engines (csrc/engine_host.h) over rlr_search_topk_filtered,
+ * rlr_score_rows and rlr_mmr_select; _search_text_filtered runs rlr_lexical_score_filtered and then one of the other
+ * two (two host synchronisations: the fused one-enqueue hybrid path takes no filter).  A stale filter, or one of another
+ * index: RLR_E_INVALID. */
+int32_t rlr_engine_search_filtered(rlr_index *idx, const rlr_filter *f, const float *query_raw, uint32_t dq, uint32_t top_k,
+                                   const rlr_query_weights *weights, const uint64_t *lex_rows, const float *lex_scores,
+                                   uint32_t n_lex, int32_t stage, rlr_search_hit *out, uint32_t cap, uint32_t *n_out);
+int32_t rlr_engine_search_with_diversity_filtered(rlr_index *idx, const rlr_filter *f, const float *query_raw, uint32_t dq,
+                                                  uint32_t top_k, float diversity_factor, const rlr_query_weights *weights,
+                                                  const uint64_t *lex_rows, const float *lex_scores, uint32_t n_lex,
+                                                  rlr_search_hit *out, uint32_t cap, uint32_t *n_out);
+int32_t rlr_engine_search_text_filtered(rlr_index *idx, rlr_lexical *lex, const rlr_filter *f, const float *query_raw,
+                                        uint32_t dq, const char *query_tokens, size_t tokens_len, uint32_t top_k,
+                                        float diversity_factor, int32_t stage, const rlr_query_weights *weights,
+                                        rlr_search_hit *out, uint32_t cap, uint32_t *n_out);
+
 /* Additive batched entry point (the reference has no batched API; its oracle is "loop
  * search_with_diversity over the batch"): n_queries raw query embeddings,
  * no lexical candidates.  Hits of query q start at out[q * cap]; n_out[q] = their count.

@@ -340,6 +340,43 @@ typedef struct rlr_multi_stats_t {
 } rlr_multi_stats_t;
 int32_t rlr_multi_stats(rlr_multi *m, rlr_multi_stats_t *out, int32_t reset);
 
+/* ---- row filters: search inside a set of rows ("only in these documents") ------------------ */
+/* A filter F is a set of row numbers of ONE index, fixed when it is made.  A filtered search is the reference's search
+ * over the corpus that holds only the rows of F in ascending row order, with the row numbers mapped back to index rows:
+ * N is |F| wherever the reference uses the corpus size (k is clamped to |F|, initial_k = min(|F|, 3k), the MMR pool is
+ * min(|F|, max(3k, k + 10)), |F| = 0 returns no result with RLR_OK, rag_engine.rs:476-478), the order stays (score desc,
+ * row asc) with NaN last, scores stay bit-identical to the reference-order dot product.  Over-fetching and filtering on
+ * the host gives none of this: a rare document may have no chunk among the best 10 000 rows.
+ *   rlr_filter_create_rows    rows in any order, duplicates ignored; a row >= the index size: RLR_E_RANGE
+ *   rlr_filter_create_ranges  the union of [first[i], first[i] + count[i]) (a document is a contiguous run of rows:
+ *                             append adds at the end, rlr_index_delete_rows compacts stably); ranges may overlap, an
+ *                             empty range is ignored, one that leaves the index: RLR_E_RANGE
+ * The filter keeps one bit per index row on the device (tail bits of the last word zero), the allowed rows as an
+ * ascending list, and their count.  It is immutable and may be shared by any number of concurrent searches; destroying
+ * one while a search uses it is the caller's error, as with index mutators.  Every call that changes which rows the
+ * index holds (upload, append, delete_rows, fill_synthetic, load_json) makes the filters made before it STALE: every
+ * filtered call with a stale filter returns RLR_E_INVALID before any GPU work (deletion renumbers rows; a silently
+ * stale filter would return other documents).  Without a usable device: RLR_E_NO_DEVICE.
+ * rlr_filter_info: any pointer may be null.  *path = how searches with this filter run: 0 = list path (few allowed rows:
+ * reference-order scores of every allowed row, then a select / sort), 1 = masked scan (a scan kernel that reads the
+ * mask word of 64 rows and never requests the bytes of a masked row, then the unfiltered tail).  The choice is made
+ * once, from the number of allowed rows ("Row filters", has the measured crossover). */
+typedef struct rlr_filter rlr_filter;
+int32_t rlr_filter_create_rows(rlr_index *idx, const uint64_t *rows, uint64_t n, rlr_filter **out);
+int32_t rlr_filter_create_ranges(rlr_index *idx, const uint64_t *first, const uint64_t *count, uint32_t n_ranges,
+                                 rlr_filter **out);
+int32_t rlr_filter_destroy(rlr_filter *f);
+int32_t rlr_filter_info(const rlr_filter *f, uint64_t *index_rows, uint64_t *n_allowed, int32_t *path, int32_t *stale);
+/* Measurement hook (tools/bench_filtered.py times both paths at the same number of allowed rows to place the
+ * crossover): make this filter take `path` (0 / 1) from now on.  Results do not depend on the path.  Mutator-class:
+ * not concurrent with searches that use the filter. */
+int32_t rlr_filter_set_path(rlr_filter *f, int32_t path);
+/* rlr_search_topk over the rows of `f`: same arguments and result contract, k clamped to the allowed rows.  Queries
+ * run one by one over the master rows: the matrix-core batch, the coalescer and the nomination copies
+ * (rlr_index_enable_batch_image) are not used. */
+int32_t rlr_search_topk_filtered(rlr_index *idx, const rlr_filter *f, const float *queries, uint32_t n_queries,
+                                 uint32_t k, float guard_eps, uint64_t *rows_out, float *cos_out, uint32_t *n_out);
+
 /* ---- coalescing of concurrent single-query searches ----------------------- */
 /* Serve concurrent single-query rlr_search_topk calls on this index from shared passes over the rows.
  * max_group 0 or 1: off (the default).  2..8: at most this many queries share one pass.

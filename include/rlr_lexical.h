@@ -93,6 +93,16 @@ int32_t rlr_lexical_segments(rlr_lexical *lex, uint64_t *main_postings, uint64_t
 int32_t rlr_lexical_score(rlr_lexical *lex, const char *query_tokens, size_t len, uint32_t limit,
                           uint64_t *rows_out, float *scores_out, uint32_t *n_out);
 
+/* rlr_lexical_score restricted to the rows of a filter (rlr_filter_create_*, include/rlr_gpu.h; it must live on the
+ * device of `lex` and be current, RLR_E_INVALID otherwise).  The filter restricts the CANDIDATES, not the corpus
+ * statistics: total_docs, the average length, df and idf stay those of the whole lexical index -- the conventional
+ * meaning of a search filter, and one lexical index per corpus.  The result is the min(limit, ...) best rows of the
+ * filter with bm25 > 0 by (bm25 desc, row asc): what rlr_lexical_score would return with limit = "all", reduced to
+ * the filter's rows and then truncated; score bits unchanged (masked rows are never accumulated, an allowed row's
+ * f32 sum keeps the term order).  Rows of the lexical index at or beyond the filter's index size count as masked. */
+int32_t rlr_lexical_score_filtered(rlr_lexical *lex, const rlr_filter *f, const char *query_tokens, size_t len,
+                                   uint32_t limit, uint64_t *rows_out, float *scores_out, uint32_t *n_out);
+
 /* rlr_lexical_score for `n_queries` queries at once, through the batched BM25 kernels that
  * rlr_engine_search_text_batch runs (a direct view of them: no embedding index involved).  Query q's
  * tokens are tokens[token_offsets[q] .. token_offsets[q + 1]); its pairs go to rows_out / scores_out

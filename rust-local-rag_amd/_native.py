@@ -142,6 +142,12 @@ PROTOTYPES = [
     ("rlr_index_row_bytes", C.c_int32, [_H, u32p]),
     ("rlr_mmr_select_staged", C.c_int32, [_H, C.c_void_p, C.c_uint64, u64p, f32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32,
                                           C.c_float, u32p, f32p, u32p]),
+    ("rlr_filter_create_rows", C.c_int32, [_H, u64p, C.c_uint64, C.POINTER(_H)]),
+    ("rlr_filter_create_ranges", C.c_int32, [_H, u64p, u64p, C.c_uint32, C.POINTER(_H)]),
+    ("rlr_filter_destroy", C.c_int32, [_H]),
+    ("rlr_filter_info", C.c_int32, [_H, u64p, u64p, i32p, i32p]),
+    ("rlr_filter_set_path", C.c_int32, [_H, C.c_int32]),
+    ("rlr_search_topk_filtered", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, C.c_float, u64p, f32p, u32p]),
     ("rlr_index_set_coalescing", C.c_int32, [_H, C.c_uint32, C.c_uint32]),
     ("rlr_index_coalesce_stats", C.c_int32, [_H, C.POINTER(CoalesceStatsC), C.c_int32]),
     ("rlr_profile_enable", C.c_int32, [_H, C.c_int32]),
@@ -161,6 +167,14 @@ PROTOTYPES = [
     ("rlr_engine_search_text_batch", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, C.c_char_p, u64p, C.c_uint32,
                                                  C.c_float, C.c_int32, C.POINTER(QueryWeightsC), C.POINTER(SearchHitC),
                                                  C.c_uint32, u32p, C.POINTER(TextBatchInfoC)]),
+    ("rlr_engine_search_filtered", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, C.POINTER(QueryWeightsC), u64p, f32p,
+                                               C.c_uint32, C.c_int32, C.POINTER(SearchHitC), C.c_uint32, u32p]),
+    ("rlr_engine_search_with_diversity_filtered", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, C.c_float,
+                                                              C.POINTER(QueryWeightsC), u64p, f32p, C.c_uint32,
+                                                              C.POINTER(SearchHitC), C.c_uint32, u32p]),
+    ("rlr_engine_search_text_filtered", C.c_int32, [_H, _H, _H, f32p, C.c_uint32, C.c_char_p, C.c_size_t, C.c_uint32,
+                                                    C.c_float, C.c_int32, C.POINTER(QueryWeightsC), C.POINTER(SearchHitC),
+                                                    C.c_uint32, u32p]),
     ("rlr_engine_search_with_diversity_batch", C.c_int32, [_H, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
                                                            C.POINTER(QueryWeightsC), C.POINTER(SearchHitC), C.c_uint32,
                                                            u32p]),
@@ -190,6 +204,7 @@ PROTOTYPES = [
     ("rlr_lexical_info", C.c_int32, [_H, u64p, u64p, u64p, u64p]),
     ("rlr_lexical_segments", C.c_int32, [_H, u64p, u64p, u64p, u64p, u64p]),
     ("rlr_lexical_score", C.c_int32, [_H, C.c_char_p, C.c_size_t, C.c_uint32, u64p, f32p, u32p]),
+    ("rlr_lexical_score_filtered", C.c_int32, [_H, _H, C.c_char_p, C.c_size_t, C.c_uint32, u64p, f32p, u32p]),
     ("rlr_lexical_score_batch", C.c_int32, [_H, C.c_uint32, C.c_char_p, u64p, C.c_uint32, u64p, f32p, u32p, f32p, u32p]),
     ("rlr_tokenize_ascii", C.c_int32, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
 ]

@@ -63,6 +63,8 @@ struct SingleBackend {
     rlr_index *idx;
     uint64_t n_rows = 0;
     uint32_t dim = 0;
+    bool holds(uint64_t row) const { return row < n_rows; }
+    void first_rows(uint64_t take, uint64_t *rows) const { first_rows_dense(take, rows); }
     int32_t topk(const float *queries, uint32_t nq, uint32_t k, uint64_t *rows, float *cos, uint32_t *n) const
     {
         return rlr_search_topk(idx, queries, nq, k, -1.0f, rows, cos, n);

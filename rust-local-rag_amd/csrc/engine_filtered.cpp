@@ -1,0 +1,148 @@
+// engine_filtered.cpp -- rlr_engine_search_filtered / _search_with_diversity_filtered / _search_text_filtered
+// (include/rlr_engine.h): RagEngine::search / search_with_diversity inside a row filter.  The corpus the reference's
+// code sees is the filter's rows in ascending order: the host half is engine_host.h over a backend whose candidate
+// universe is the filter -- its size where the reference uses the corpus size, its bit where a lexical pair is checked
+// against the corpus, its first rows where w_embedding == 0 enumerates rows -- and whose top-k is
+// rlr_search_topk_filtered.  score_rows and mmr are the unfiltered ones: the rows they are given are allowed rows already.
+// A translation unit of its own, as text_batch.cpp is: engine.cpp stays free of the filtered device entry points.
+// Compiled with -ffp-contract=off like engine.cpp.
+#include "../../include/rlr_engine.h"
+#include "../../include/rlr_lexical.h"
+#include "engine_host.h"
+#include "filter_internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+using namespace rlr_host;
+
+namespace {
+
+struct FilteredBackend {
+    rlr_index *idx;
+    const rlr_filter *f;
+    rlr::FilterView v;
+    uint64_t n_rows = 0; // |F|
+    uint32_t dim = 0;
+    bool holds(uint64_t row) const { return row < v.index_rows && ((v.h_mask[row >> 6] >> (row & 63)) & 1ull); }
+    void first_rows(uint64_t take, uint64_t *rows) const
+    {
+        uint64_t at = 0;
+        const uint64_t n_words = (v.index_rows + 63) / 64;
+        for (uint64_t w = 0; w < n_words && at < take; ++w)
+            for (uint64_t m = v.h_mask[w]; m && at < take; m &= m - 1)
+                rows[at++] = w * 64 + static_cast<uint64_t>(__builtin_ctzll(m));
+    }
+    int32_t topk(const float *queries, uint32_t nq, uint32_t k, uint64_t *rows, float *cos, uint32_t *n) const
+    {
+        return rlr_search_topk_filtered(idx, f, queries, nq, k, -1.0f, rows, cos, n);
+    }
+    int32_t score_rows(const float *query, const uint64_t *rows, uint32_t n, float *cos) const
+    {
+        return rlr_score_rows(idx, query, rows, n, cos);
+    }
+    int32_t mmr(const uint64_t *pool_rows, const float *pool_scores, const uint32_t *pool_sizes, uint32_t nq, uint32_t P,
+                uint32_t k, float lambda, uint32_t *order, uint32_t *n_sel) const
+    {
+        if (nq == 1)
+            return rlr_mmr_select(idx, pool_rows, pool_scores, pool_sizes[0], k, lambda, order, nullptr, n_sel);
+        return rlr_mmr_select_batch(idx, pool_rows, pool_scores, pool_sizes, nq, P, k, lambda, order, nullptr, n_sel);
+    }
+};
+
+int32_t filtered_backend(rlr_index *idx, const rlr_filter *f, FilteredBackend *be)
+{
+    be->idx = idx;
+    be->f = f;
+    int32_t st = rlr::filter_view(f, &be->v); // (null, stale)
+    if (st != RLR_OK)
+        return st;
+    uint64_t n = 0;
+    st = rlr_index_info(idx, &n, &be->dim, nullptr, nullptr);
+    be->n_rows = be->v.n_allowed;
+    return st;
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t rlr_engine_search_filtered(rlr_index *idx, const rlr_filter *f, const float *query_raw, uint32_t dq, uint32_t top_k,
+                                   const rlr_query_weights *weights, const uint64_t *lex_rows, const float *lex_scores,
+                                   uint32_t n_lex, int32_t stage, rlr_search_hit *out, uint32_t cap, uint32_t *n_out)
+{
+    if (!idx || !f || !n_out || (!query_raw && dq) || (n_lex && (!lex_rows || !lex_scores)))
+        return RLR_E_INVALID;
+    *n_out = 0;
+    FilteredBackend be;
+    int32_t st = filtered_backend(idx, f, &be);
+    if (st != RLR_OK)
+        return st;
+    rlr_resolved_weights w;
+    rlr_resolve_weights(weights, &w);
+    std::vector<Cand> res;
+    st = generic_search(be, query_raw, dq, top_k, w, lex_rows, lex_scores, n_lex, stage, res);
+    if (st != RLR_OK)
+        return st;
+    if (!res.empty() && !out)
+        return RLR_E_INVALID;
+    emit(res, out, cap, n_out);
+    return RLR_OK;
+}
+
+int32_t rlr_engine_search_with_diversity_filtered(rlr_index *idx, const rlr_filter *f, const float *query_raw, uint32_t dq,
+                                                  uint32_t top_k, float diversity_factor, const rlr_query_weights *weights,
+                                                  const uint64_t *lex_rows, const float *lex_scores, uint32_t n_lex,
+                                                  rlr_search_hit *out, uint32_t cap, uint32_t *n_out)
+{
+    if (!idx || !f || !n_out || (!query_raw && dq) || (n_lex && (!lex_rows || !lex_scores)))
+        return RLR_E_INVALID;
+    *n_out = 0;
+    if (diversity_factor < 0.0f) diversity_factor = 0.0f; // f32::clamp(0.0, 1.0) (:725); NaN takes the MMR branch
+    if (diversity_factor > 1.0f) diversity_factor = 1.0f;
+    FilteredBackend be;
+    int32_t st = filtered_backend(idx, f, &be);
+    if (st != RLR_OK)
+        return st;
+    rlr_resolved_weights w;
+    rlr_resolve_weights(weights, &w);
+    std::vector<Cand> picked;
+    st = generic_search_with_diversity(be, query_raw, dq, top_k, diversity_factor, w, lex_rows, lex_scores, n_lex, picked);
+    if (st != RLR_OK)
+        return st;
+    if (!picked.empty() && !out)
+        return RLR_E_INVALID;
+    emit(picked, out, cap, n_out);
+    return RLR_OK;
+}
+
+int32_t rlr_engine_search_text_filtered(rlr_index *idx, rlr_lexical *lex, const rlr_filter *f, const float *query_raw,
+                                        uint32_t dq, const char *query_tokens, size_t tokens_len, uint32_t top_k,
+                                        float diversity_factor, int32_t stage, const rlr_query_weights *weights,
+                                        rlr_search_hit *out, uint32_t cap, uint32_t *n_out)
+{
+    if (!idx || !lex || !f || !n_out || (!query_raw && dq) || (tokens_len && !query_tokens))
+        return RLR_E_INVALID;
+    *n_out = 0;
+    float lambda = diversity_factor;
+    if (lambda < 0.0f) lambda = 0.0f;
+    if (lambda > 1.0f) lambda = 1.0f;
+    const bool diversify = !(lambda == 0.0f);
+    // the sizes rlr_engine_search_text works with: `search` sees top_k (or the pool) and asks BM25 for five times that (:505)
+    const uint32_t k_seen = std::max<uint32_t>(diversify ? pool_size_of(top_k) : top_k, 1u);
+    const uint32_t limit = static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(k_seen) * 5, 0xFFFFFFFFull));
+    const uint32_t lcap = std::min<uint32_t>(limit, RLR_LEXICAL_MAX_LIMIT);
+    std::vector<uint64_t> lrows(lcap);
+    std::vector<float> lscores(lcap);
+    uint32_t n_lex = 0;
+    const int32_t st = rlr_lexical_score_filtered(lex, f, query_tokens, tokens_len, limit, lrows.data(), lscores.data(), &n_lex);
+    if (st != RLR_OK)
+        return st;
+    return diversify ? rlr_engine_search_with_diversity_filtered(idx, f, query_raw, dq, top_k, diversity_factor, weights,
+                                                                 lrows.data(), lscores.data(), n_lex, out, cap, n_out)
+                     : rlr_engine_search_filtered(idx, f, query_raw, dq, top_k, weights, lrows.data(), lscores.data(), n_lex,
+                                                  stage, out, cap, n_out);
+}
+
+} // extern "C"

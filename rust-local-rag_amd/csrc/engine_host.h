@@ -6,6 +6,11 @@
 //
 // A backend provides (all rows are GLOBAL row numbers):
 //   uint64_t n_rows;  uint32_t dim;
+//        -- n_rows: the size of the candidate universe, the reference's corpus size N (k clamps, initial_k, the pool)
+//   bool holds(uint64_t row) const;
+//        -- is `row` part of the universe?  (a whole index: row < n_rows; a row filter: its bit)
+//   void first_rows(uint64_t take, uint64_t *rows) const;
+//        -- the first `take` (<= n_rows) rows of the universe in ascending order (a whole index: 0 .. take - 1)
 //   int32_t topk(const float *queries, uint32_t nq, uint32_t k, uint64_t *rows, float *cos, uint32_t *n) const;
 //        -- per query the k best rows by reference-order cosine, (cos desc, row asc), NaN last
 //   int32_t score_rows(const float *query, const uint64_t *rows, uint32_t n, float *cos) const;
@@ -108,7 +113,9 @@ struct LexPrep {
     }
 };
 
-inline LexPrep prepare_lexical(uint64_t N, const uint64_t *lex_rows, const float *lex_scores, uint32_t n_lex)
+// `holds(row)`: is the row part of the corpus that is searched (pairs outside it are no candidates, but count for max_lexical)
+template <typename Holds>
+inline LexPrep prepare_lexical_in(Holds holds, const uint64_t *lex_rows, const float *lex_scores, uint32_t n_lex)
 {
     LexPrep p;
     float max_lex = 0.0f;
@@ -116,7 +123,7 @@ inline LexPrep prepare_lexical(uint64_t N, const uint64_t *lex_rows, const float
     order.reserve(n_lex);
     for (uint32_t i = 0; i < n_lex; ++i) {
         max_lex = std::fmax(max_lex, lex_scores[i]);
-        if (lex_rows[i] < N)
+        if (holds(lex_rows[i]))
             order.push_back(i);
     }
     if (max_lex >= 1.1920929e-07f)
@@ -131,6 +138,18 @@ inline LexPrep prepare_lexical(uint64_t N, const uint64_t *lex_rows, const float
         p.scores.push_back(lex_scores[order[i]]);
     }
     return p;
+}
+
+inline LexPrep prepare_lexical(uint64_t N, const uint64_t *lex_rows, const float *lex_scores, uint32_t n_lex)
+{
+    return prepare_lexical_in([N](uint64_t row) { return row < N; }, lex_rows, lex_scores, n_lex);
+}
+
+// what a backend over a whole index (rows 0 .. n_rows - 1) answers for the two universe hooks
+inline void first_rows_dense(uint64_t take, uint64_t *rows)
+{
+    for (uint64_t r = 0; r < take; ++r)
+        rows[r] = r;
 }
 
 
@@ -175,19 +194,18 @@ int32_t blend_search(const B &be, const std::vector<float> &q, uint64_t need, co
         // (row asc) picks the lowest rows; no scan needed, only their cosines for reporting.
         const uint64_t take = std::min<uint64_t>(N, need + lrows.size());
         std::vector<uint64_t> rows(take);
-        for (uint64_t r = 0; r < take; ++r)
-            rows[r] = r;
+        be.first_rows(take, rows.data());
         std::vector<float> cosv(take);
         st = be.score_rows(q.data(), rows.data(), static_cast<uint32_t>(take), cosv.data());
         if (st != RLR_OK)
             return st;
         for (uint64_t r = 0; r < take; ++r) {
             float l = 0.0f;
-            (void)lex.find(r, &l);
-            cands.push_back({r, combine(w, cosv[r], l), cosv[r], l});
+            (void)lex.find(rows[r], &l);
+            cands.push_back({rows[r], combine(w, cosv[r], l), cosv[r], l});
         }
         for (size_t i = 0; i < lrows.size(); ++i)
-            if (lrows[i] >= take) {
+            if (take == 0 || lrows[i] > rows[take - 1]) { // (the rows are ascending: a lexical row beyond the ones taken)
                 const float l = lex.scores[i] / lex.max_lex;
                 cands.push_back({lrows[i], combine(w, lcos[i], l), lcos[i], l});
             }
@@ -259,7 +277,7 @@ int32_t generic_search(const B &be, const float *query_raw, uint32_t dq, uint32_
     if (be.n_rows == 0) // :476-478
         return RLR_OK;
     const std::vector<float> q = prepare_query(query_raw, dq, be.dim);
-    const LexPrep lex = prepare_lexical(be.n_rows, lex_rows, lex_scores, n_lex);
+    const LexPrep lex = prepare_lexical_in([&be](uint64_t row) { return be.holds(row); }, lex_rows, lex_scores, n_lex);
     return blend_search(be, q, need_of(be.n_rows, top_k, stage), w, lex, result);
 }
 

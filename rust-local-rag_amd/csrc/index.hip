@@ -12,6 +12,7 @@
 #include "sort_emit.h"
 #include "pool_prepare.h"
 #include "lexical_internal.h"
+#include "filter_internal.h"
 
 #include <algorithm>
 #include <atomic>
@@ -228,6 +229,21 @@ struct rlr_index {
     int co_running = 0;               // coalescer pipelines in flight (co_mu)
     std::vector<std::shared_ptr<CoalesceGroup>> co_pending; // groups waiting for a slot, oldest first (co_mu)
     rlr_coalesce_stats co_stats{};    // (co_mu)
+    // bumped by every call that changes which rows the index holds (upload, append, delete_rows, fill_synthetic; load_json
+    // goes through upload): a row filter records it at creation and is refused as stale once it has moved on
+    std::atomic<uint64_t> mutations{0};
+};
+
+// A set of rows of one index, fixed at creation (rlr_filter_create_*): one bit per index row on the device (tail bits of
+// the last word zero) and on the host (the check that no returned row is masked, the engine's row enumeration), the
+// allowed rows as an ascending list on the device (the list path, and the exact fall-back of the masked scan), the count.
+struct rlr_filter {
+    rlr_index *ix = nullptr;
+    uint64_t index_rows = 0, n_allowed = 0, mutations = 0;
+    int32_t path = 0; // 0: list path, 1: masked scan
+    uint64_t *d_mask = nullptr;
+    uint32_t *d_list = nullptr;
+    std::vector<uint64_t> h_mask;
 };
 
 namespace {
@@ -1105,6 +1121,17 @@ __global__ void emit_kernel(const uint64_t *__restrict__ packed, uint32_t n, uin
         out[i] = i < n ? packed[i] : 0ull;
 }
 
+// The list path of a filtered search: the reference-order scores of the filter's rows as sortable keys, zero padding up
+// to the power of two the sort / select behind it works on; the count goes where topk_global_kernel reads it.
+__global__ __launch_bounds__(256) void pack_list_kernel(const float *__restrict__ vals, const uint32_t *__restrict__ list, uint32_t n,
+                                                        uint64_t *__restrict__ packed, uint32_t n_pad, SelectState *__restrict__ st)
+{
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n_pad; i += gridDim.x * 256)
+        packed[i] = i < n ? pack_result(vals[i], list[i]) : 0ull;
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        st->n_cand = n;
+}
+
 // ---- search -> MMR without a host round trip (rlr_search_diverse): pool_prepare.h ---------------------------
 template <bool FROM_CANDIDATES>
 __global__ __launch_bounds__(1024) void pool_prepare_kernel(const uint64_t *__restrict__ packed, const SelectState *__restrict__ st,
@@ -1845,7 +1872,8 @@ hipError_t enqueue_query_scan(rlr_index *ix, Ctx *c, uint32_t qi, bool timed)
 // pool != nullptr (with emit == false): a diversified search -- when the fused tail runs, its finish builds the MMR pool in
 // the same launch and *pool_done = true; otherwise the caller launches pool_prepare_kernel itself.
 hipError_t enqueue_query_rest(rlr_index *ix, Ctx *c, uint32_t qi, const SearchPlan &p, uint64_t *d_out_q, uint64_t *d_meta_q,
-                              bool timed, bool emit = true, const PoolArgs *pool = nullptr, bool *pool_done = nullptr)
+                              bool timed, bool emit = true, const PoolArgs *pool = nullptr, bool *pool_done = nullptr,
+                              bool master_scan = false)
 {
     if (pool_done)
         *pool_done = false;
@@ -1855,8 +1883,9 @@ hipError_t enqueue_query_rest(rlr_index *ix, Ctx *c, uint32_t qi, const SearchPl
     uint32_t *hist1 = c->d_hist, *hist2 = c->d_hist + kHistBins;
     SelectState *st = c->d_state + qi;
     const float *dq = c->d_query + static_cast<size_t>(qi) * ix->q_pitch;
-    const bool q8 = scan_over_q8(ix);
-    const bool img = !q8 && scan_over_image(ix, c);
+    // (master_scan: the scores in front of this tail came from the master rows whatever copies the index keeps -- the masked scan)
+    const bool q8 = !master_scan && scan_over_q8(ix);
+    const bool img = !master_scan && !q8 && scan_over_image(ix, c);
     const float band = q8 ? q8_two_eps(ix, qi < c->q_norm.size() ? c->q_norm[qi] : 1.0f, p.two_eps * 0.5f)
                           : (img ? p.two_eps_img : p.two_eps);
     // Up to a few million rows the k-th score's digit-1 bin holds a few hundred scores and the tail's one-pass (DIRECT)
@@ -2374,6 +2403,180 @@ int32_t search_topk_host(rlr_index *ix, const float *queries, uint32_t n_queries
     return RLR_OK;
 }
 
+// ---- filtered search (rlr_search_topk_filtered) ---------------------------------------------------------------------
+// Fewer allowed rows than this: the list path (reference-order scores of every allowed row, then a sort or a select).
+// From here on: the masked scan and the unfiltered tail.  Measured on the MI355X at 1 M x 768 f32, k = 100, scattered rows
+// (tools/bench_filtered.py, DESIGN.md "Row filters"): list / scan 42 / 50 us at 256 rows, 56 / 60 at 8192, 69 / 66 at
+// 16 384, 134 / 87 at 65 536 -- the crossover lies near 12 k rows; rounded down to a power of two.
+constexpr uint64_t kFilterListMax = 8192;
+
+int32_t check_filter(const rlr_index *ix, const rlr_filter *f)
+{
+    if (!f)
+        return fail(RLR_E_INVALID, "null filter handle");
+    if (f->ix != ix)
+        return fail(RLR_E_INVALID, "the filter was made for another index");
+    if (f->mutations != ix->mutations.load(std::memory_order_acquire))
+        return fail(RLR_E_INVALID, "stale filter: the index was mutated after the filter was made (rows may have been renumbered)");
+    return RLR_OK;
+}
+
+int32_t reserve_cand(Ctx *c, uint32_t cap)
+{
+    if (c->cand_cap >= cap)
+        return RLR_OK;
+    if (c->d_cand) (void)hipFree(c->d_cand);
+    if (c->d_packed) (void)hipFree(c->d_packed);
+    c->d_cand = nullptr;
+    c->d_packed = nullptr;
+    c->cand_cap = 0;
+    RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_cand), static_cast<size_t>(cap) * sizeof(uint32_t)));
+    RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_packed), static_cast<size_t>(cap) * sizeof(uint64_t)));
+    c->cand_cap = cap;
+    return RLR_OK;
+}
+
+// The list path, and the exact fall-back of the masked scan: every allowed row scored in reference order (no nomination,
+// no band), the keys sorted -- or, for k <= 4096, the k best selected and sorted by one workgroup.  The query is in
+// c->d_query; p.k <= n_allowed.  The k packed results end up in h_res.
+int32_t filtered_exact(rlr_index *ix, Ctx *c, const rlr_filter *f, const SearchPlan &p, uint64_t *h_res)
+{
+    hipStream_t s = c->stream;
+    const uint32_t n = static_cast<uint32_t>(f->n_allowed);
+    const uint32_t cap = next_pow2(std::max<uint32_t>(n, p.k));
+    RLR_TRY(reserve_list(c, n));
+    RLR_TRY(reserve_cand(c, cap));
+    SelectState *st = c->d_state;
+    RLR_HIP(launch_score_rows(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_query, f->d_list, n, c->d_vals, s));
+    hipLaunchKernelGGL(rlr::pack_list_kernel, dim3(std::min<uint32_t>((cap + 255) / 256, 1024)), dim3(256), 0, s, c->d_vals,
+                       f->d_list, n, c->d_packed, cap, st);
+    RLR_HIP(hipGetLastError());
+    if (p.k <= kLdsSortCap) {
+        hipLaunchKernelGGL(rlr::topk_global_kernel, dim3(1), dim3(1024), 0, s, c->d_packed, st, cap, c->d_out, p.k);
+    } else {
+        RLR_HIP(launch_sort_desc(c->d_packed, cap, s));
+        hipLaunchKernelGGL(rlr::emit_kernel, dim3((p.k + 255) / 256), dim3(256), 0, s, c->d_packed, n, c->d_out, p.k);
+    }
+    RLR_HIP(hipGetLastError());
+    RLR_HIP(hipMemcpyAsync(h_res, c->d_out, static_cast<size_t>(p.k) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    RLR_HIP(hipStreamSynchronize(s));
+    return RLR_OK;
+}
+
+// One query over the rows of `f` (n_allowed > 0, k > 0).  Filtered calls scan the master rows and never use the
+// nomination copies, the matrix-core batch or the coalescer.
+int32_t filtered_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *query, uint32_t k, float guard_eps,
+                       uint64_t *rows_out, float *cos_out, uint32_t *n_out)
+{
+    // k is clamped to the allowed rows BEFORE the plan: the histogram of a masked scan counts n_allowed scores
+    const SearchPlan p = make_plan(ix, query, 1, static_cast<uint32_t>(std::min<uint64_t>(k, f->n_allowed)), guard_eps);
+    RLR_TRY(ctx_prepare(ix, c, 1, p));
+    const size_t q_bytes = static_cast<size_t>(ix->q_pitch) * sizeof(float);
+    RLR_TRY(pin_reserve(c, q_bytes + (static_cast<size_t>(p.k) + 1) * sizeof(uint64_t)));
+    float *h_q = static_cast<float *>(c->h_pin);
+    uint64_t *h_res = reinterpret_cast<uint64_t *>(static_cast<char *>(c->h_pin) + q_bytes);
+    uint64_t *h_meta = h_res + p.k;
+    stage_queries(ix, c, query, 1, h_q);
+    hipStream_t s = c->stream;
+    c->h_q_kq = nullptr;
+    RLR_HIP(upload_queries(c, h_q, q_bytes, s));
+    const bool timed = ix->profiling;
+    uint64_t n_cand = 0, n_retry = 0;
+    if (f->path == 0) {
+        RLR_TRY(filtered_exact(ix, c, f, p, h_res));
+    } else {
+        arm_meta(h_meta, 1);
+        if (c->h_assert) {
+            hipLaunchKernelGGL(rlr::hist_assert_zero_kernel, dim3(4), dim3(256), 0, s, c->d_hist, 2u * kHistBins, c->h_assert);
+            RLR_HIP(hipGetLastError());
+        }
+        if (timed)
+            RLR_HIP(hipEventRecord(c->ev[0], s));
+        RLR_HIP(launch_scan_masked(scan_args(ix, c->d_query, c->d_scores, c->d_hist), f->d_mask, f->n_allowed, s));
+        if (timed)
+            RLR_HIP(hipEventRecord(c->ev[1], s));
+        RLR_HIP(enqueue_query_rest(ix, c, 0, p, h_res, h_meta, timed, true, nullptr, nullptr, /*master_scan=*/true));
+        if (timed)
+            RLR_HIP(hipStreamSynchronize(s));
+        else
+            RLR_TRY(wait_results(h_meta, h_res, 1, p.k, std::min<uint32_t>(p.cap, kLdsSortCap), s, &c->wait_ema));
+        RLR_TRY(check_hist_assert(c));
+        n_cand = static_cast<uint32_t>(h_meta[0]);
+        if (n_cand > p.cap || n_cand > kLdsSortCap) {
+            // band overflow (massive ties, k > 4096): the large-candidate path over the masked scores still resident
+            n_retry++;
+            RLR_TRY(big_query(ix, c, 0, p, static_cast<uint32_t>(n_cand), /*rescan=*/false, h_res));
+        }
+        // A masked row must never be returned.  Its sentinel keeps it out of every collect whose threshold key is above
+        // 0; a threshold of 0 (k reaches allowed rows whose own nomination score is NaN) lets it in, and re-scored from
+        // its real values it can rank anywhere.  So every returned row is tested against the host copy of the mask --
+        // if none is masked the result is the right one -- and a failed test takes the exact path.
+        bool leaked = false;
+        for (uint32_t i = 0; i < p.k && !leaked; ++i) {
+            const uint32_t row = 0xFFFFFFFFu - static_cast<uint32_t>(h_res[i]);
+            leaked = row >= f->index_rows || !((f->h_mask[row >> 6] >> (row & 63)) & 1ull);
+        }
+        if (leaked) {
+            n_retry++;
+            RLR_TRY(filtered_exact(ix, c, f, p, h_res));
+        }
+    }
+    c->hist_dirty = false;
+    *n_out = p.k;
+    unpack_results(h_res, p.k, rows_out, cos_out);
+    return note_search(ix, c, 1, n_cand, n_retry, timed && f->path != 0);
+}
+
+int32_t filter_finish(rlr_index *ix, std::vector<uint64_t> &&mask, rlr_filter **out)
+{
+    std::unique_ptr<rlr_filter> f(new (std::nothrow) rlr_filter());
+    if (!f)
+        return fail(RLR_E_OOM, "host allocation failed");
+    f->ix = ix;
+    f->index_rows = ix->n_rows;
+    f->mutations = ix->mutations.load(std::memory_order_acquire);
+    f->h_mask = std::move(mask);
+    std::vector<uint32_t> list;
+    for (size_t w = 0; w < f->h_mask.size(); ++w)
+        for (uint64_t m = f->h_mask[w]; m; m &= m - 1)
+            list.push_back(static_cast<uint32_t>(w * 64 + static_cast<uint32_t>(__builtin_ctzll(m))));
+    f->n_allowed = list.size();
+    f->path = f->n_allowed < kFilterListMax ? 0 : 1;
+    CtxLease lease(ix);
+    RLR_TRY(ctx_acquire(ix, &lease.c));
+    hipStream_t s = lease.c->stream;
+    const size_t mask_bytes = std::max<size_t>(f->h_mask.size(), 1) * sizeof(uint64_t);
+    const size_t list_bytes = std::max<size_t>(list.size(), 1) * sizeof(uint32_t);
+    hipError_t e = rlr::dev_malloc(reinterpret_cast<void **>(&f->d_mask), mask_bytes);
+    if (e == hipSuccess)
+        e = rlr::dev_malloc(reinterpret_cast<void **>(&f->d_list), list_bytes);
+    // uploaded on a stream and waited for: the searches that read them run on other, non-blocking streams
+    if (e == hipSuccess && !f->h_mask.empty())
+        e = hipMemcpyAsync(f->d_mask, f->h_mask.data(), f->h_mask.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && !list.empty())
+        e = hipMemcpyAsync(f->d_list, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        if (f->d_mask) (void)hipFree(f->d_mask);
+        if (f->d_list) (void)hipFree(f->d_list);
+        return fail(e == hipErrorOutOfMemory ? RLR_E_OOM : RLR_E_HIP, "filter upload failed: %s", hipGetErrorString(e));
+    }
+    *out = f.release();
+    return RLR_OK;
+}
+
+int32_t filter_create_check(rlr_index *ix, rlr_filter **out)
+{
+    if (!out)
+        return fail(RLR_E_INVALID, "out is null");
+    *out = nullptr;
+    if (rlr_device_count() <= 0)
+        return fail(RLR_E_NO_DEVICE, "no HIP device is visible (this library has no CPU path)");
+    RLR_TRY(check_handle(ix));
+    return use_device(ix);
+}
+
 // ---- coalescer: concurrent single-query calls served from shared passes (rlr_index_set_coalescing) ----------------
 // A caller that finds no coalescer pipeline running and nothing pending runs today's single-query pipeline at once
 // (after linger_us, if set, as the leader of a group others may join meanwhile).  A caller that arrives while one runs
@@ -2666,6 +2869,7 @@ int32_t rlr_index_reserve(rlr_index *ix, uint64_t n_rows)
 int32_t rlr_index_upload(rlr_index *ix, const float *rows, uint64_t n_rows, int32_t normalize_on_device)
 {
     RLR_TRY(check_handle(ix));
+    ix->mutations.fetch_add(1, std::memory_order_acq_rel); // (row filters made before this call are stale from here on)
     if (n_rows && !rows)
         return fail(RLR_E_INVALID, "rows is null");
     RLR_TRY(use_device(ix));
@@ -2682,6 +2886,7 @@ int32_t rlr_index_append(rlr_index *ix, const float *rows, uint64_t n_rows, int3
                          uint64_t *first_row_out)
 {
     RLR_TRY(check_handle(ix));
+    ix->mutations.fetch_add(1, std::memory_order_acq_rel); // (row filters made before this call are stale from here on)
     if (n_rows && !rows)
         return fail(RLR_E_INVALID, "rows is null");
     RLR_TRY(use_device(ix));
@@ -2701,6 +2906,7 @@ int32_t rlr_index_delete_rows(rlr_index *ix, const uint64_t *rows, uint64_t n)
         return RLR_OK;
     if (!rows)
         return fail(RLR_E_INVALID, "rows is null");
+    ix->mutations.fetch_add(1, std::memory_order_acq_rel); // (deletion renumbers rows: a filter made before it names other rows now)
     RLR_TRY(use_device(ix));
     const uint64_t N = ix->n_rows;
     std::vector<uint8_t> dead(N, 0);
@@ -2799,6 +3005,7 @@ int32_t rlr_index_enable_batch_image(rlr_index *ix, int32_t enable)
 int32_t rlr_index_fill_synthetic(rlr_index *ix, uint64_t n_rows, uint64_t row0, uint64_t seed, uint32_t n_clusters)
 {
     RLR_TRY(check_handle(ix));
+    ix->mutations.fetch_add(1, std::memory_order_acq_rel); // (row filters made before this call are stale from here on)
     RLR_TRY(use_device(ix));
     ix->n_rows = 0;
     RLR_TRY(ensure_rows(ix, n_rows));
@@ -2848,6 +3055,99 @@ int32_t rlr_search_topk(rlr_index *ix, const float *queries, uint32_t n_queries,
     if (n_queries == 1 && ix->co_max.load(std::memory_order_relaxed) >= 2 && coalesce_eligible(ix, k))
         return coalesced_search(ix, queries, k, guard_eps, rows_out, cos_out, n_out);
     return search_topk_host(ix, queries, n_queries, k, guard_eps, rows_out, cos_out, n_out);
+}
+
+int32_t rlr_filter_create_rows(rlr_index *ix, const uint64_t *rows, uint64_t n, rlr_filter **out)
+{
+    RLR_TRY(filter_create_check(ix, out));
+    if (n && !rows)
+        return fail(RLR_E_INVALID, "rows is null");
+    std::vector<uint64_t> mask((ix->n_rows + 63) / 64, 0);
+    for (uint64_t i = 0; i < n; ++i) {
+        if (rows[i] >= ix->n_rows)
+            return fail(RLR_E_RANGE, "row %llu out of range (index holds %llu rows)", static_cast<unsigned long long>(rows[i]),
+                        static_cast<unsigned long long>(ix->n_rows));
+        mask[rows[i] >> 6] |= 1ull << (rows[i] & 63);
+    }
+    return filter_finish(ix, std::move(mask), out);
+}
+
+int32_t rlr_filter_create_ranges(rlr_index *ix, const uint64_t *first, const uint64_t *count, uint32_t n_ranges, rlr_filter **out)
+{
+    RLR_TRY(filter_create_check(ix, out));
+    if (n_ranges && (!first || !count))
+        return fail(RLR_E_INVALID, "first / count is null");
+    std::vector<uint64_t> mask((ix->n_rows + 63) / 64, 0);
+    for (uint32_t i = 0; i < n_ranges; ++i) {
+        if (count[i] == 0)
+            continue;
+        if (first[i] >= ix->n_rows || count[i] > ix->n_rows - first[i])
+            return fail(RLR_E_RANGE, "range [%llu, +%llu) out of range (index holds %llu rows)",
+                        static_cast<unsigned long long>(first[i]), static_cast<unsigned long long>(count[i]),
+                        static_cast<unsigned long long>(ix->n_rows));
+        const uint64_t lo = first[i], hi = first[i] + count[i]; // [lo, hi)
+        for (uint64_t w = lo >> 6; w <= (hi - 1) >> 6; ++w) {
+            const uint64_t b0 = std::max<uint64_t>(lo, w * 64) - w * 64, b1 = std::min<uint64_t>(hi, w * 64 + 64) - w * 64; // bits [b0, b1)
+            const uint64_t upto = b1 == 64 ? ~0ull : (1ull << b1) - 1ull;
+            mask[w] |= upto & ~((1ull << b0) - 1ull);
+        }
+    }
+    return filter_finish(ix, std::move(mask), out);
+}
+
+int32_t rlr_filter_destroy(rlr_filter *f)
+{
+    if (!f)
+        return RLR_OK;
+    if (f->ix)
+        (void)hipSetDevice(f->ix->device);
+    if (f->d_mask) (void)hipFree(f->d_mask);
+    if (f->d_list) (void)hipFree(f->d_list);
+    delete f;
+    return RLR_OK;
+}
+
+int32_t rlr_filter_info(const rlr_filter *f, uint64_t *index_rows, uint64_t *n_allowed, int32_t *path, int32_t *stale)
+{
+    if (!f)
+        return fail(RLR_E_INVALID, "null filter handle");
+    if (index_rows) *index_rows = f->index_rows;
+    if (n_allowed) *n_allowed = f->n_allowed;
+    if (path) *path = f->path;
+    if (stale) *stale = f->mutations != f->ix->mutations.load(std::memory_order_acquire) ? 1 : 0;
+    return RLR_OK;
+}
+
+int32_t rlr_filter_set_path(rlr_filter *f, int32_t path)
+{
+    if (!f || (path != 0 && path != 1))
+        return fail(RLR_E_INVALID, "null filter handle, or a path other than 0 / 1");
+    f->path = path;
+    return RLR_OK;
+}
+
+int32_t rlr_search_topk_filtered(rlr_index *ix, const rlr_filter *f, const float *queries, uint32_t n_queries, uint32_t k,
+                                 float guard_eps, uint64_t *rows_out, float *cos_out, uint32_t *n_out)
+{
+    RLR_TRY(check_handle(ix));
+    RLR_TRY(check_filter(ix, f)); // (a stale filter is refused before any GPU work)
+    if (n_queries && (!queries || !n_out))
+        return fail(RLR_E_INVALID, "queries / n_out is null");
+    if (n_queries && k && (!rows_out || !cos_out))
+        return fail(RLR_E_INVALID, "output buffers are null");
+    RLR_TRY(use_device(ix));
+    for (uint32_t q = 0; q < n_queries; ++q)
+        n_out[q] = 0;
+    if (f->n_allowed == 0 || k == 0 || n_queries == 0)
+        return RLR_OK;
+    CtxLease lease(ix);
+    RLR_TRY(ctx_acquire(ix, &lease.c));
+    StreamDrain drain{lease.c->stream};
+    for (uint32_t q = 0; q < n_queries; ++q) // query by query: no matrix-core batch, no coalesced group
+        RLR_TRY(filtered_query(ix, lease.c, f, queries + static_cast<size_t>(q) * ix->dim, k, guard_eps,
+                               rows_out + static_cast<size_t>(q) * k, cos_out + static_cast<size_t>(q) * k, &n_out[q]));
+    drain.armed = false;
+    return RLR_OK;
 }
 
 int32_t rlr_search_topk_device(rlr_index *ix, const float *queries, uint32_t n_queries, uint32_t k, float guard_eps,
@@ -3844,3 +4144,18 @@ int32_t rlr_profile_read(rlr_index *ix, rlr_profile *out, int32_t reset)
 }
 
 } // extern "C"
+
+namespace rlr {
+int32_t filter_view(const rlr_filter *f, FilterView *out)
+{
+    if (!f)
+        return fail(RLR_E_INVALID, "null filter handle");
+    RLR_TRY(check_filter(f->ix, f));
+    out->h_mask = f->h_mask.data();
+    out->d_mask = f->d_mask;
+    out->index_rows = f->index_rows;
+    out->n_allowed = f->n_allowed;
+    out->device = f->ix->device;
+    return RLR_OK;
+}
+} // namespace rlr

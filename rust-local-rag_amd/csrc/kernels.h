@@ -37,6 +37,10 @@ struct ScanArgs {
 };
 hipError_t launch_scan(const ScanArgs &a, hipStream_t stream);
 bool launch_scan_takes_host_query(const ScanArgs &a);
+// the same scan over the rows a filter allows: `mask` holds one bit per row (ceil(n_rows / 64) words, tail bits zero),
+// n_allowed of them set (it only picks the launch shape); masked rows are not read, score NaN (score_key 0) and are not
+// counted in `hist`.  The query comes from a.query.
+hipError_t launch_scan_masked(const ScanArgs &a, const uint64_t *mask, uint64_t n_allowed, hipStream_t stream);
 // one pass over the rows for 2..8 queries (a.query = n_queries x q_pitch floats, a.scores = n_queries x score_stride);
 // false when the shape is not served (then nothing was launched)
 bool launch_scan_multi(const ScanArgs &a, uint32_t q_pitch, uint32_t n_queries, size_t score_stride, hipStream_t s,

@@ -28,6 +28,7 @@
 #include "kernels.h"
 #include "lds_select.h"
 #include "lexical_internal.h"
+#include "filter_internal.h"
 
 #include <algorithm>
 #include <atomic>
@@ -144,11 +145,23 @@ __device__ inline uint32_t lower_bound_rows(const uint32_t *__restrict__ rows, u
     return lo;
 }
 
+// A row filter on the accumulate kernels (rlr_lexical_score_filtered): MASKED instantiations skip the postings of rows
+// the filter does not allow -- rows at or beyond `mask_rows`, the index size the filter was made for, included.  A masked
+// row is never added to, so it never enters the touched list: the selection kernels see exactly the allowed touched rows
+// (their min(limit, n_touched) is the allowed count), and the clean-up that restores the dense accumulator through that
+// list has nothing else to restore.  An allowed row's sum is the unfiltered one, term by term.
+__device__ inline bool lex_row_allowed(const uint64_t *__restrict__ mask, uint32_t mask_rows, uint32_t row)
+{
+    return row < mask_rows && ((mask[row >> 6] >> (row & 63)) & 1ull);
+}
+
+template <bool MASKED>
 __global__ __launch_bounds__(256) void bm25_terms_kernel(TermBatch tb, const uint32_t *__restrict__ post_row,
                                                          const uint32_t *__restrict__ post_tf, const uint32_t *__restrict__ dpost_row,
                                                          const uint32_t *__restrict__ dpost_tf, const uint32_t *__restrict__ doc_len,
                                                          uint32_t n_rows, float avg, float *__restrict__ scores,
-                                                         uint32_t *__restrict__ touched, LexControl *__restrict__ ctl)
+                                                         uint32_t *__restrict__ touched, LexControl *__restrict__ ctl,
+                                                         const uint64_t *__restrict__ mask, uint32_t mask_rows)
 {
     __shared__ uint32_t s_range[kTermsPerLaunch][4]; // [term][main lo, main hi, appended lo, appended hi]
     const uint32_t r0 = static_cast<uint32_t>(static_cast<uint64_t>(blockIdx.x) * n_rows / gridDim.x);
@@ -176,7 +189,7 @@ __global__ __launch_bounds__(256) void bm25_terms_kernel(TermBatch tb, const uin
                 const uint32_t i = i0 + threadIdx.x;
                 bool first_touch = false;
                 uint32_t row = 0;
-                if (i < hi) {
+                if (i < hi && (!MASKED || lex_row_allowed(mask, mask_rows, rows[i]))) {
                     row = rows[i];
                     const float dl = static_cast<float>(doc_len[row]);
                     const float tf = static_cast<float>(tfs[i]);
@@ -227,11 +240,13 @@ __device__ inline uint32_t wave_lower_bound_rows(const uint32_t *__restrict__ ro
     const bool below = i < hi && rows[i] < key;
     return lo + static_cast<uint32_t>(__popcll(__ballot(below)));
 }
+template <bool MASKED>
 __global__ __launch_bounds__(256) void bm25_terms_lds_kernel(TermBatch tb, const uint32_t *__restrict__ post_row,
                                                              const uint32_t *__restrict__ post_tf, const uint32_t *__restrict__ dpost_row,
                                                              const uint32_t *__restrict__ dpost_tf, const uint32_t *__restrict__ doc_len,
                                                              uint32_t n_rows, float avg, float *__restrict__ scores,
-                                                             uint32_t *__restrict__ touched, LexControl *__restrict__ ctl)
+                                                             uint32_t *__restrict__ touched, LexControl *__restrict__ ctl,
+                                                             const uint64_t *__restrict__ mask, uint32_t mask_rows)
 {
     __shared__ uint32_t s_range[kTermsPerLaunch][4]; // [term][main lo, main hi, appended lo, appended hi]
     __shared__ float s_sc[kLdsRows], s_dl[kLdsRows], s_nk[kLdsRows];
@@ -348,7 +363,7 @@ __global__ __launch_bounds__(256) void bm25_terms_lds_kernel(TermBatch tb, const
         seek(t2, seg2, j0);
         uint32_t row2 = 0, tfw2 = 0;
         const bool ok2 = fetch(t2, seg2, j0, &row2, &tfw2); // on its way while this chunk is added
-        if (ok) {
+        if (ok && (!MASKED || lex_row_allowed(mask, mask_rows, row))) {
             const uint32_t r = row - r0;
             const float dl = s_dl[r];
             const float tf = static_cast<float>(tfw);
@@ -1522,7 +1537,17 @@ int32_t rlr_lexical_segments(rlr_lexical *lx, uint64_t *main_postings, uint64_t 
 
 // first_attempt = 1: skip the sampled selection (a fused search already saw it hand this query back)
 static int32_t lexical_score_from(rlr_lexical *lx, const char *query_tokens, size_t len, uint32_t limit, uint64_t *rows_out,
-                                  float *scores_out, uint32_t *n_out, int first_attempt);
+                                  float *scores_out, uint32_t *n_out, int first_attempt, const uint64_t *d_mask = nullptr,
+                                  uint32_t mask_rows = 0);
+
+extern "C++" {
+namespace rlr {
+// lexical_enqueue with an optional row filter: d_mask (null: none) holds one bit per row below mask_rows
+static int32_t lexical_enqueue_masked(rlr_lexical *lx, const char *query_tokens, size_t len, uint32_t limit, LexPending *out,
+                                      bool need_sorted, bool exact_passes, const LexSink *sink, const uint64_t *d_mask,
+                                      uint32_t mask_rows);
+} // namespace rlr
+} // extern "C++"
 
 int32_t rlr_lexical_score(rlr_lexical *lx, const char *query_tokens, size_t len, uint32_t limit, uint64_t *rows_out,
                           float *scores_out, uint32_t *n_out)
@@ -1542,8 +1567,26 @@ int32_t lexical_score_exact(rlr_lexical *lx, const char *query_tokens, size_t le
 } // namespace rlr
 } // extern "C++"
 
+int32_t rlr_lexical_score_filtered(rlr_lexical *lx, const rlr_filter *f, const char *query_tokens, size_t len, uint32_t limit,
+                                   uint64_t *rows_out, float *scores_out, uint32_t *n_out)
+{
+    if (!lx)
+        return set_error(RLR_E_INVALID, "lexical handle is null");
+    if (!n_out)
+        return set_error(RLR_E_INVALID, "n_out is null");
+    *n_out = 0;
+    rlr::FilterView v;
+    LEX_TRY(rlr::filter_view(f, &v)); // (null or stale: refused before any GPU work)
+    if (v.device != lx->device)
+        return set_error(RLR_E_INVALID, "the filter lives on device %d, the lexical index on device %d", v.device, lx->device);
+    if (v.n_allowed == 0)
+        return RLR_OK;
+    return lexical_score_from(lx, query_tokens, len, limit, rows_out, scores_out, n_out, 0, v.d_mask,
+                              static_cast<uint32_t>(v.index_rows));
+}
+
 static int32_t lexical_score_from(rlr_lexical *lx, const char *query_tokens, size_t len, uint32_t limit, uint64_t *rows_out,
-                                  float *scores_out, uint32_t *n_out, int first_attempt)
+                                  float *scores_out, uint32_t *n_out, int first_attempt, const uint64_t *d_mask, uint32_t mask_rows)
 {
     if (!lx)
         return set_error(RLR_E_INVALID, "lexical handle is null");
@@ -1554,7 +1597,8 @@ static int32_t lexical_score_from(rlr_lexical *lx, const char *query_tokens, siz
         return set_error(RLR_E_INVALID, "query_tokens is null");
     for (int attempt = first_attempt; attempt < 2; ++attempt) {
         rlr::LexPending p;
-        LEX_TRY(rlr::lexical_enqueue(lx, query_tokens, len, limit, &p, /*need_sorted=*/true, /*exact_passes=*/attempt == 1));
+        LEX_TRY(rlr::lexical_enqueue_masked(lx, query_tokens, len, limit, &p, /*need_sorted=*/true, /*exact_passes=*/attempt == 1,
+                                            nullptr, d_mask, mask_rows));
         if (p.limit == 0) // empty index, no tokens, or no term of the query is known (:2170-2177, :2196)
             return RLR_OK;
         int32_t st = RLR_OK;
@@ -1632,6 +1676,13 @@ static double sampled_candidates(uint32_t limit, uint64_t n, uint32_t s)
 
 int32_t lexical_enqueue(rlr_lexical *lx, const char *query_tokens, size_t len, uint32_t limit, LexPending *out,
                         bool need_sorted, bool exact_passes, const LexSink *sink)
+{
+    return lexical_enqueue_masked(lx, query_tokens, len, limit, out, need_sorted, exact_passes, sink, nullptr, 0);
+}
+
+static int32_t lexical_enqueue_masked(rlr_lexical *lx, const char *query_tokens, size_t len, uint32_t limit, LexPending *out,
+                                      bool need_sorted, bool exact_passes, const LexSink *sink, const uint64_t *d_mask,
+                                      uint32_t mask_rows)
 {
     *out = LexPending{};
     out->lx = lx;
@@ -1719,14 +1770,18 @@ int32_t lexical_enqueue(rlr_lexical *lx, const char *query_tokens, size_t len, u
                                  : static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(max_blocks, (n_rows + 255) / 256)));
     const bool terms_lds = !lx->terms_global && (n_rows + lds_wgs - 1) / lds_wgs + 1 <= kLdsRows;
     auto flush_terms = [&]() {
-        if (tb.n_terms && terms_lds)
-            hipLaunchKernelGGL(bm25_terms_lds_kernel, dim3(lds_wgs), dim3(256), 0, s, tb, lx->d_post_row, lx->d_post_tf,
-                               lx->d_dpost_row, lx->d_dpost_tf, lx->d_doc_len, static_cast<uint32_t>(n_rows), avg, ws->d_scores,
-                               ws->d_touched, ctl);
+#define RLR_LEX_TERMS_ARGS                                                                                                   \
+    tb, lx->d_post_row, lx->d_post_tf, lx->d_dpost_row, lx->d_dpost_tf, lx->d_doc_len, static_cast<uint32_t>(n_rows), avg,      \
+        ws->d_scores, ws->d_touched, ctl, d_mask, mask_rows
+        if (tb.n_terms && terms_lds && d_mask)
+            hipLaunchKernelGGL(bm25_terms_lds_kernel<true>, dim3(lds_wgs), dim3(256), 0, s, RLR_LEX_TERMS_ARGS);
+        else if (tb.n_terms && terms_lds)
+            hipLaunchKernelGGL(bm25_terms_lds_kernel<false>, dim3(lds_wgs), dim3(256), 0, s, RLR_LEX_TERMS_ARGS);
+        else if (tb.n_terms && d_mask)
+            hipLaunchKernelGGL(bm25_terms_kernel<true>, dim3(row_wgs), dim3(256), 0, s, RLR_LEX_TERMS_ARGS);
         else if (tb.n_terms)
-            hipLaunchKernelGGL(bm25_terms_kernel, dim3(row_wgs), dim3(256), 0, s, tb, lx->d_post_row, lx->d_post_tf, lx->d_dpost_row,
-                               lx->d_dpost_tf, lx->d_doc_len, static_cast<uint32_t>(n_rows), avg, ws->d_scores, ws->d_touched,
-                               ctl);
+            hipLaunchKernelGGL(bm25_terms_kernel<false>, dim3(row_wgs), dim3(256), 0, s, RLR_LEX_TERMS_ARGS);
+#undef RLR_LEX_TERMS_ARGS
         tb.n_terms = 0;
     };
     for (uint32_t t : terms) {

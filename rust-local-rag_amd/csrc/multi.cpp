@@ -687,6 +687,8 @@ struct MultiBackend {
     rlr_multi *m;
     uint64_t n_rows;
     uint32_t dim;
+    bool holds(uint64_t row) const { return row < n_rows; }
+    void first_rows(uint64_t take, uint64_t *rows) const { rlr_host::first_rows_dense(take, rows); }
     int32_t topk(const float *queries, uint32_t nq, uint32_t k, uint64_t *rows, float *cos, uint32_t *n) const
     {
         return rlr_multi_search_topk(m, queries, nq, k, -1.0f, rows, cos, n);

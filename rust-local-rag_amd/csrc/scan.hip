@@ -526,6 +526,181 @@ __global__ __launch_bounds__(256) void scan_generic_kernel(const float4 *__restr
     }
 }
 
+// ---------------------------------------------------------------------------
+// Masked kernels (row filters): a wave owns a UNIT of `unit` consecutive rows (8, 16, 32 or 64: a slice of ONE 64-bit word
+// of the filter's bitmask), reads the word through a wave-uniform address and walks the unit's set bits (count trailing
+// zeros, clear the lowest), R allowed rows in flight at a time.  Every branch on the mask is wave-uniform, and the bytes
+// of a masked row are never requested from HBM: the kernel's traffic is the allowed rows plus one bit per row.  An
+// allowed row is scored exactly as the unmasked kernels score it (per-lane fmaf partials, the DPP wave sum), so the
+// guard band is the same.  Masked rows leave as NaN -- score_key 0, the class that orders last -- in the same coalesced
+// store as the unit's scores, and only allowed rows are counted in the digit-1 histogram: the tail then finds the k-th
+// key among allowed rows.
+// ---------------------------------------------------------------------------
+// the unit's bits of its mask word, bit i = row0 + i (row0 a multiple of unit, nr = rows of the unit inside the matrix)
+__device__ inline uint64_t mask_bits(const uint64_t *__restrict__ mask, uint32_t row0, uint32_t unit, uint32_t nr)
+{
+    const uint64_t w = mask[row0 >> 6] >> (row0 & 63);
+    uint64_t u = (static_cast<uint64_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(w >> 32))) << 32) |
+                 static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(w & 0xFFFFFFFFu)));
+    const uint32_t take = min(unit, nr); // (the filter keeps the tail bits of its last word zero; a row past the matrix is never read either way)
+    if (take < 64)
+        u &= (1ull << take) - 1ull;
+    return u;
+}
+
+__device__ inline void masked_store(float *__restrict__ scores, uint32_t *s_hist, bool hist, uint32_t row0, uint32_t nr,
+                                    uint64_t word, int lane, float mine)
+{
+    if (static_cast<uint32_t>(lane) < nr) {
+        scores[row0 + lane] = mine;
+        if (hist && ((word >> lane) & 1ull))
+            atomicAdd(&s_hist[score_key(mine) >> 21], 1u);
+    }
+}
+
+// f32 rows of CH KiB (768-d: CH = 3), the query in registers
+template <int CH, int R>
+__global__ __launch_bounds__(256) void scan_masked_fixed_kernel(const float4 *__restrict__ rows, const float *__restrict__ query,
+                                                                const uint64_t *__restrict__ mask, float *__restrict__ scores,
+                                                                uint32_t *__restrict__ g_hist, uint32_t n_rows, uint32_t unit)
+{
+    constexpr int P16 = CH * 64;
+    __shared__ uint32_t s_hist[kHistBins];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    for (int i = tid; i < kHistBins; i += 256)
+        s_hist[i] = 0;
+    __syncthreads();
+    float4 qv[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c)
+        qv[c] = reinterpret_cast<const float4 *>(query)[c * 64 + lane];
+
+    const float masked = __builtin_bit_cast(float, 0x7FC00000u);
+    const uint32_t n_groups = (n_rows + unit - 1) / unit;
+    const uint32_t n_waves = gridDim.x * 4;
+    for (uint32_t g = blockIdx.x * 4 + wave; g < n_groups; g += n_waves) {
+        const uint32_t row0 = g * unit;
+        const uint32_t nr = min(unit, n_rows - row0);
+        const uint64_t word = mask_bits(mask, row0, unit, nr);
+        float mine = masked;
+        uint64_t rem = word;
+        while (rem) { // (uniform)
+            uint32_t bit[R];
+            float4 x[R][CH];
+            int m = 0;
+#pragma unroll
+            for (int rr = 0; rr < R; ++rr) {
+                bit[rr] = 0;
+                if (rem) { // (uniform)
+                    bit[rr] = static_cast<uint32_t>(__builtin_ctzll(rem));
+                    rem &= rem - 1;
+                    m = rr + 1;
+                    const float4 *p = rows + static_cast<size_t>(row0 + bit[rr]) * P16 + lane;
+#pragma unroll
+                    for (int c = 0; c < CH; ++c)
+                        x[rr][c] = ld16<true>(p + c * 64);
+                }
+            }
+#pragma unroll
+            for (int rr = 0; rr < R; ++rr) {
+                if (rr < m) { // (uniform)
+                    float acc = 0.0f;
+#pragma unroll
+                    for (int c = 0; c < CH; ++c)
+                        acc = dot4(x[rr][c], qv[c], acc);
+                    const float tot = wave_sum(acc);
+                    if (static_cast<uint32_t>(lane) == bit[rr])
+                        mine = tot;
+                }
+            }
+        }
+        masked_store(scores, s_hist, g_hist != nullptr, row0, nr, word, lane, mine);
+    }
+    if (g_hist) {
+        __syncthreads();
+        hist_flush(s_hist, g_hist);
+    }
+}
+
+// any dim and pitch, f32 or binary16 rows, the query in LDS (the shape of scan_generic_kernel)
+template <int R, bool F16>
+__global__ __launch_bounds__(256) void scan_masked_generic_kernel(const float4 *__restrict__ rows, const float *__restrict__ query,
+                                                                  const uint64_t *__restrict__ mask, float *__restrict__ scores,
+                                                                  uint32_t *__restrict__ g_hist, uint32_t n_rows,
+                                                                  uint32_t pitch16, uint32_t unit)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+    uint32_t *s_hist = reinterpret_cast<uint32_t *>(s_raw);
+    float4 *s_q = reinterpret_cast<float4 *>(s_raw + kHistBins * sizeof(uint32_t));
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t qf4 = F16 ? 2 * pitch16 : pitch16;
+    for (uint32_t i = tid; i < qf4; i += 256)
+        s_q[i] = reinterpret_cast<const float4 *>(query)[i];
+    for (int i = tid; i < kHistBins; i += 256)
+        s_hist[i] = 0;
+    __syncthreads();
+
+    const float masked = __builtin_bit_cast(float, 0x7FC00000u);
+    const uint32_t n_groups = (n_rows + unit - 1) / unit;
+    const uint32_t n_waves = gridDim.x * 4;
+    for (uint32_t g = blockIdx.x * 4 + wave; g < n_groups; g += n_waves) {
+        const uint32_t row0 = g * unit;
+        const uint32_t nr = min(unit, n_rows - row0);
+        const uint64_t word = mask_bits(mask, row0, unit, nr);
+        float mine = masked;
+        uint64_t rem = word;
+        while (rem) { // (uniform)
+            uint32_t bit[R];
+            const float4 *p[R];
+            float acc[R];
+#pragma unroll
+            for (int rr = 0; rr < R; ++rr) {
+                // fewer than R bits left: the last allowed row once more (same address, same score, same lane)
+                if (rem || rr == 0) {
+                    bit[rr] = static_cast<uint32_t>(__builtin_ctzll(rem));
+                    rem &= rem - 1;
+                } else {
+                    bit[rr] = bit[rr - 1];
+                }
+                acc[rr] = 0.0f;
+                p[rr] = rows + static_cast<size_t>(row0 + bit[rr]) * pitch16;
+            }
+            for (uint32_t c = lane; c < pitch16; c += 64) {
+                float4 x[R];
+#pragma unroll
+                for (int rr = 0; rr < R; ++rr)
+                    x[rr] = ld16<true>(p[rr] + c);
+                if constexpr (F16) {
+                    const float4 q0 = s_q[2 * c], q1 = s_q[2 * c + 1];
+#pragma unroll
+                    for (int rr = 0; rr < R; ++rr)
+                        acc[rr] = dot8h(x[rr], q0, q1, acc[rr]);
+                } else {
+                    const float4 q0 = s_q[c];
+#pragma unroll
+                    for (int rr = 0; rr < R; ++rr)
+                        acc[rr] = dot4(x[rr], q0, acc[rr]);
+                }
+            }
+#pragma unroll
+            for (int rr = 0; rr < R; ++rr) {
+                const float tot = wave_sum(acc[rr]);
+                if (static_cast<uint32_t>(lane) == bit[rr])
+                    mine = tot;
+            }
+        }
+        masked_store(scores, s_hist, g_hist != nullptr, row0, nr, word, lane, mine);
+    }
+    if (g_hist) {
+        __syncthreads();
+        hist_flush(s_hist, g_hist);
+    }
+}
+
 struct ScanPlan {
     uint32_t group_rows;
     uint32_t blocks;
@@ -769,6 +944,43 @@ hipError_t launch_scan(const ScanArgs &a, hipStream_t s)
     else
         hipLaunchKernelGGL((scan_generic_kernel<2, false>), dim3(p.blocks), dim3(256), lds, s, rows,
                            a.query, a.scores, a.hist, a.n_rows, p.group_rows, a.pitch16);
+    return hipGetLastError();
+}
+
+// The scan over the rows a filter allows (mask: one bit per row, ceil(n_rows / 64) words, tail bits zero; n_allowed of
+// them set).  The query is read from device memory (a.query; query_host is not used).  768-d f32 rows take the fixed
+// kernel with the query in registers, every other shape the generic one.
+// Launch shape, measured on the MI355X at 1 M x 768 f32 (kernel times, DESIGN.md "Row filters"; unit x workgroups per CU):
+//   a quarter of the rows or more allowed: the unfiltered scan's own shape -- 8-row units, ONE workgroup per CU, four rows
+//   in flight per wave: 466 us with every row allowed where the unfiltered kernel takes 452 (64-row units leave the
+//   15 625 words of 1 M rows unevenly spread over the waves: 457 against 431 at one workgroup per CU, 485 against 432 at four);
+//   fewer: a unit holds few allowed rows and a wave has one or two in flight, so the latency is covered by the number of
+//   waves instead -- 16-row units, four workgroups per CU: 13 us for 10 000 contiguous rows, 12 us for 1000, where the
+//   dense shape takes 29 and 27 (and 64-row units 23 and 22: a contiguous range then lives in a handful of waves).
+hipError_t launch_scan_masked(const ScanArgs &a, const uint64_t *mask, uint64_t n_allowed, hipStream_t s)
+{
+    if (a.n_rows == 0)
+        return hipSuccess;
+    const bool fixed = a.dtype == RLR_F32 && a.pitch16 == 192 && a.dim == 768;
+    const bool dense = fixed && n_allowed * 4 >= a.n_rows;
+    const uint32_t unit = dense ? 8u : 16u;
+    const uint32_t wgs = dense ? 1u : 4u;
+    const uint32_t n_groups = (a.n_rows + unit - 1) / unit;
+    const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((n_groups + 3) / 4, static_cast<uint32_t>(a.n_cu) * wgs));
+    const float4 *rows = static_cast<const float4 *>(a.rows);
+    if (fixed) {
+        hipLaunchKernelGGL((scan_masked_fixed_kernel<3, 4>), dim3(blocks), dim3(256), 0, s, rows, a.query, mask, a.scores,
+                           a.hist, a.n_rows, unit);
+        return hipGetLastError();
+    }
+    const uint32_t qf4 = a.dtype == RLR_F16 ? 2 * a.pitch16 : a.pitch16;
+    const size_t lds = kHistBins * sizeof(uint32_t) + static_cast<size_t>(qf4) * 16;
+    if (a.dtype == RLR_F16)
+        hipLaunchKernelGGL((scan_masked_generic_kernel<2, true>), dim3(blocks), dim3(256), lds, s, rows, a.query, mask,
+                           a.scores, a.hist, a.n_rows, a.pitch16, unit);
+    else
+        hipLaunchKernelGGL((scan_masked_generic_kernel<2, false>), dim3(blocks), dim3(256), lds, s, rows, a.query, mask,
+                           a.scores, a.hist, a.n_rows, a.pitch16, unit);
     return hipGetLastError();
 }
 

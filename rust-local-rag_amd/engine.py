@@ -21,7 +21,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as N
-from .index import GpuIndex, _f32
+from .index import GpuIndex, RowFilter, _f32
 from .lexical import LexicalIndex, tokenize
 
 
@@ -119,6 +119,25 @@ class SearchRequest:  # mcp_server.rs:17-31
     weights: Optional[QueryWeights] = None
     lexical: Sequence[Tuple[str, float]] = field(default_factory=list)
     query: Optional[str] = None   # the query text (mcp_server.rs:19); scored by the GPU LexicalIndex when given
+    documents: Optional[Sequence[str]] = None  # search only inside these documents (None: the whole corpus; []: nothing)
+
+
+def document_ranges(chunks: Sequence[DocumentChunk], documents) -> List[Tuple[int, int]]:
+    """The rows of `documents` in a row -> chunk table as (first, count) runs, ascending.  A document is one run as a
+    rule (add_document appends, removal compacts stably); unknown names contribute no rows."""
+    want = set(documents)
+    runs: List[Tuple[int, int]] = []
+    start = None
+    for r, ch in enumerate(chunks):
+        if ch.document_name in want:
+            if start is None:
+                start = r
+        elif start is not None:
+            runs.append((start, r - start))
+            start = None
+    if start is not None:
+        runs.append((start, len(chunks) - start))
+    return runs
 
 
 class RagEngine:
@@ -138,10 +157,30 @@ class RagEngine:
         self.dim = dim
         self._chunks: List[DocumentChunk] = []       # row -> chunk
         self._row_of: Dict[str, int] = {}            # chunk_id -> row
+        self._filters: Dict[frozenset, RowFilter] = {}  # documents -> their rows as a filter; dropped by every mutation
 
     def close(self) -> None:
+        self._drop_filters()
         self.index.close()
         self.lexical.close()
+
+    # -- document scopes -----------------------------------------------------------------------
+    def _drop_filters(self) -> None:
+        for f in self._filters.values():
+            f.close()
+        self._filters = {}
+
+    def _filter_for(self, documents: Sequence[str]) -> RowFilter:
+        """the rows of these documents as a RowFilter (cached until the next add_document / remove_document)"""
+        key = frozenset(documents)
+        f = self._filters.get(key)
+        if f is not None and f.info()["stale"]:  # (the index was replaced behind the engine: load_from_disk)
+            self._drop_filters()
+            f = None
+        if f is None:
+            f = self.index.filter_ranges(document_ranges(self._chunks, key))
+            self._filters[key] = f
+        return f
 
     # -- index mutation (sites rag_engine.rs:347-348, :358-384) --------------------------
     def add_document(self, document_name: str, texts: Sequence[str], embeddings, pages: Optional[Sequence[int]] = None,
@@ -158,11 +197,13 @@ class RagEngine:
             self._row_of[cid] = first + i
             self.lexical.add_chunk(first + i, text)   # lexical_index.add_chunk(&chunk.id, &chunk.text) :382
             ids.append(cid)
+        self._drop_filters()
         return ids
 
     def remove_document(self, document_name: str) -> int:
         dead = [r for r, ch in enumerate(self._chunks) if ch.document_name == document_name]
         if dead:
+            self._drop_filters()
             self.index.delete_rows(dead)  # chunks.retain(|_, c| c.document_name != filename)
             self.lexical.remove_rows(dead)
             dead_set = set(dead)
@@ -206,13 +247,29 @@ class RagEngine:
     # -- RagEngine::search (rag_engine.rs:470-701) -----------------------------------------
     def search(self, query_embedding, top_k: int, weights: Optional[QueryWeights] = None,
                lexical: Sequence[Tuple[str, float]] = (), stage: int = 0,
-               query_text: Optional[str] = None) -> List[SearchResult]:
-        """`lexical`: BM25 pairs computed by the caller, or `query_text`: scored by the GPU LexicalIndex."""
+               query_text: Optional[str] = None, documents: Optional[Sequence[str]] = None) -> List[SearchResult]:
+        """`lexical`: BM25 pairs computed by the caller, or `query_text`: scored by the GPU LexicalIndex.
+        `documents`: search only inside these documents -- the reference's search over the corpus that holds only their
+        chunks (None: the whole corpus; an empty list or unknown names: no rows, no results)."""
         q = _f32(query_embedding).ravel()
         cap = max(3 * max(top_k, 1), 1)
         hits = (N.SearchHitC * cap)()
         n = C.c_uint32()
         wc = weights.to_c() if weights is not None else None
+        if documents is not None:
+            f = self._filter_for(documents)
+            if query_text is not None:
+                tok = " ".join(tokenize(query_text)).encode("utf-8")
+                N.check(N.lib().rlr_engine_search_text_filtered(
+                    self.index.handle, self.lexical._h, f.handle, q.ctypes.data_as(N.f32p), q.size, tok, len(tok), top_k, 0.0,
+                    stage, C.byref(wc) if wc is not None else None, hits, cap, C.byref(n)))
+            else:
+                lr, ls, nl = self._lex(lexical, None, 5 * max(top_k, 1))
+                N.check(N.lib().rlr_engine_search_filtered(
+                    self.index.handle, f.handle, q.ctypes.data_as(N.f32p), q.size, top_k,
+                    C.byref(wc) if wc is not None else None, lr.ctypes.data_as(N.u64p), ls.ctypes.data_as(N.f32p), nl, stage,
+                    hits, cap, C.byref(n)))
+            return self._results(hits, n.value)
         if query_text is not None:
             # BM25 of the text beside the scan, blended on the device: one enqueue, one synchronisation
             tok = " ".join(tokenize(query_text)).encode("utf-8")
@@ -230,7 +287,9 @@ class RagEngine:
     def search_with_diversity(self, query_embedding, top_k: int, diversity_factor: float,
                               weights: Optional[QueryWeights] = None,
                               lexical: Sequence[Tuple[str, float]] = (),
-                              query_text: Optional[str] = None) -> List[SearchResult]:
+                              query_text: Optional[str] = None,
+                              documents: Optional[Sequence[str]] = None) -> List[SearchResult]:
+        """`documents`: as for search -- the MMR pool is then min(rows of the documents, max(3 top_k, top_k + 10))"""
         q = _f32(query_embedding).ravel()
         cap = max(3 * max(top_k, 1), top_k + 10)
         hits = (N.SearchHitC * cap)()
@@ -238,6 +297,20 @@ class RagEngine:
         lam = min(max(float(diversity_factor), 0.0), 1.0)
         k_eff = top_k if lam == 0.0 else max(3 * top_k, top_k + 10)  # the top_k `search` sees (:728-735)
         wc = weights.to_c() if weights is not None else None
+        if documents is not None:
+            f = self._filter_for(documents)
+            if query_text is not None:
+                tok = " ".join(tokenize(query_text)).encode("utf-8")
+                N.check(N.lib().rlr_engine_search_text_filtered(
+                    self.index.handle, self.lexical._h, f.handle, q.ctypes.data_as(N.f32p), q.size, tok, len(tok), top_k,
+                    float(diversity_factor), 0, C.byref(wc) if wc is not None else None, hits, cap, C.byref(n)))
+            else:
+                lr, ls, nl = self._lex(lexical, None, 5 * max(k_eff, 1))
+                N.check(N.lib().rlr_engine_search_with_diversity_filtered(
+                    self.index.handle, f.handle, q.ctypes.data_as(N.f32p), q.size, top_k, float(diversity_factor),
+                    C.byref(wc) if wc is not None else None, lr.ctypes.data_as(N.u64p), ls.ctypes.data_as(N.f32p), nl,
+                    hits, cap, C.byref(n)))
+            return self._results(hits, n.value)
         if query_text is not None:
             tok = " ".join(tokenize(query_text)).encode("utf-8")
             N.check(N.lib().rlr_engine_search_text(self.index.handle, self.lexical._h, q.ctypes.data_as(N.f32p), q.size, tok,
@@ -375,7 +448,7 @@ class RagEngine:
         div = request.diversity_factor if request.diversity_factor is not None else N.DEFAULT_DIVERSITY
         div = min(max(div, 0.0), 1.0)
         return self.search_with_diversity(request.query_embedding, top_k, div, request.weights, request.lexical,
-                                          request.query)
+                                          request.query, request.documents)
 
 
 def format_search_results(results: Sequence[SearchResult]) -> str:

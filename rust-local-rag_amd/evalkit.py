@@ -2,7 +2,8 @@
 GPU path, and the retrieval metrics the reference's harness computes from it.
 
 What is mirrored (behaviour, not code):
-  wire contract   POST /search  {"query": str, "top_k"?: int = 5, "diversity_factor"?: float = 0.3}
+  wire contract   POST /search  {"query": str, "top_k"?: int = 5, "diversity_factor"?: float = 0.3,
+                                 "documents"?: [str]  -- this build's addition: search only inside these documents}
                   -> 200 {"results": [SearchResult]}        src/mcp_server.rs:345-389
                   top_k capped at MAX_TOP_K = 100 (:364, :375), diversity clamped to [0, 1] (:376),
                   default weights (:378), engine error -> 500 (:384-387); a body without "query" is
@@ -129,13 +130,19 @@ class SearchService:
             return 422, {"error": "invalid type for `top_k`: expected usize"}
         if isinstance(div, bool) or not isinstance(div, (int, float)):
             return 422, {"error": "invalid type for `diversity_factor`: expected f32"}
+        scope = {}
+        if "documents" in body:  # optional: search only inside these documents ([]: nothing); absent: the whole corpus
+            docs = body["documents"]
+            if not isinstance(docs, list) or not all(isinstance(d, str) for d in docs):
+                return 422, {"error": "invalid type for `documents`: expected a sequence of strings"}
+            scope["documents"] = docs
         top_k = min(top_k, MAX_TOP_K)
         div = min(max(float(div), 0.0), 1.0)
         try:
             with self._lock:
                 q = self.embed(body["query"])
                 results = self.engine.search_with_diversity(q, top_k, div, None,
-                                                            query_text=body["query"] if self.use_lexical else None)
+                                                            query_text=body["query"] if self.use_lexical else None, **scope)
         except Exception as e:  # engine error -> INTERNAL_SERVER_ERROR (:384-387)
             return 500, {"error": f"Search error: {e}"}
         return 200, {"results": [r.to_json() for r in results]}

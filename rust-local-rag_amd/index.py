@@ -52,6 +52,49 @@ class Profile:
     n_f16_range_fallbacks: int = 0
 
 
+class RowFilter:
+    """A fixed set of rows of one GpuIndex (rlr_filter): made by GpuIndex.filter_rows / filter_ranges, passed as `filter=`
+    to the search calls.  Immutable; stale (every filtered call raises RLR_E_INVALID) once the index is mutated.  A
+    context manager; close() releases the device memory."""
+
+    def __init__(self, index: "GpuIndex", handle: C.c_void_p):
+        self._L = index._L
+        self._index = index  # (keeps the index alive as long as the filter)
+        self._h = handle
+
+    @property
+    def handle(self) -> C.c_void_p:
+        return self._h
+
+    def info(self) -> dict:
+        """index_rows, n_allowed, path ("list" / "scan": how searches with this filter run), stale"""
+        rows, allowed, path, stale = C.c_uint64(), C.c_uint64(), C.c_int32(), C.c_int32()
+        N.check(self._L.rlr_filter_info(self._h, C.byref(rows), C.byref(allowed), C.byref(path), C.byref(stale)))
+        return {"index_rows": int(rows.value), "n_allowed": int(allowed.value), "path": ("list", "scan")[path.value],
+                "stale": bool(stale.value)}
+
+    def set_path(self, path: str) -> None:
+        """measurement hook (tools/bench_filtered.py): "list" or "scan" from now on; results do not depend on it"""
+        N.check(self._L.rlr_filter_set_path(self._h, {"list": 0, "scan": 1}[path]))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h:
+            self._L.rlr_filter_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class GpuIndex:
     """Dense chunk-embedding matrix resident in HBM + the search entry points."""
 
@@ -121,16 +164,37 @@ class GpuIndex:
         flags = (1 if (on or single_query) else 0) | (2 if single_query else 0) | (4 if q8 else 0)
         N.check(self._L.rlr_index_enable_batch_image(self._h, flags))
 
+    # -- row filters -----------------------------------------------------------
+    def filter_rows(self, rows) -> RowFilter:
+        """the given rows (any order, duplicates ignored) as a RowFilter"""
+        rows = _u64(rows).ravel()
+        h = C.c_void_p()
+        N.check(self._L.rlr_filter_create_rows(self._h, _up(rows) if rows.size else None, rows.size, C.byref(h)))
+        return RowFilter(self, h)
+
+    def filter_ranges(self, ranges) -> RowFilter:
+        """the union of the (first, count) ranges as a RowFilter (a document is a contiguous run of rows)"""
+        r = _u64(list(ranges)).reshape(-1, 2) if len(ranges) else np.zeros((0, 2), np.uint64)
+        first, count = np.ascontiguousarray(r[:, 0]), np.ascontiguousarray(r[:, 1])
+        h = C.c_void_p()
+        N.check(self._L.rlr_filter_create_ranges(self._h, _up(first) if r.shape[0] else None,
+                                                 _up(count) if r.shape[0] else None, r.shape[0], C.byref(h)))
+        return RowFilter(self, h)
+
     # -- hot path ------------------------------------------------------------
-    def search_topk(self, queries, k: int, guard_eps: float = -1.0):
-        """queries: [Q, dim] (or [dim]) already normalised -> (rows u64 [Q,k'], cos f32 [Q,k'])"""
+    def search_topk(self, queries, k: int, guard_eps: float = -1.0, filter: "RowFilter | None" = None):
+        """queries: [Q, dim] (or [dim]) already normalised -> (rows u64 [Q,k'], cos f32 [Q,k']); filter: only these rows"""
         q = _f32(queries).reshape(-1, self.dim)
         nq = q.shape[0]
         rows = np.zeros((nq, max(k, 1)), dtype=np.uint64)
         cos = np.zeros((nq, max(k, 1)), dtype=np.float32)
         n_out = np.zeros(max(nq, 1), dtype=np.uint32)
-        N.check(self._L.rlr_search_topk(self._h, _fp(q), nq, k, guard_eps, _up(rows), _fp(cos),
-                                        n_out.ctypes.data_as(N.u32p)))
+        if filter is not None:
+            N.check(self._L.rlr_search_topk_filtered(self._h, filter.handle, _fp(q), nq, k, guard_eps, _up(rows), _fp(cos),
+                                                     n_out.ctypes.data_as(N.u32p)))
+        else:
+            N.check(self._L.rlr_search_topk(self._h, _fp(q), nq, k, guard_eps, _up(rows), _fp(cos),
+                                            n_out.ctypes.data_as(N.u32p)))
         kk = int(n_out[0]) if nq else 0
         return rows[:, :kk], cos[:, :kk]
 

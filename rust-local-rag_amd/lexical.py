@@ -91,18 +91,23 @@ class LexicalIndex:
         return dict(zip(("main_postings", "appended_postings", "full_rebuilds", "append_rebuilds", "select_retries"),
                         (x.value for x in v)))
 
-    def score(self, query: str, limit: int) -> Tuple[np.ndarray, np.ndarray]:
-        """LexicalIndex::score :2169-2225 -> (rows u64, scores f32), (score desc, row asc)"""
-        return self.score_tokens(tokenize(query), limit)
+    def score(self, query: str, limit: int, filter=None) -> Tuple[np.ndarray, np.ndarray]:
+        """LexicalIndex::score :2169-2225 -> (rows u64, scores f32), (score desc, row asc).  filter (a RowFilter of the
+        index whose rows these are): only its rows are candidates; the BM25 statistics stay those of the whole index"""
+        return self.score_tokens(tokenize(query), limit, filter)
 
-    def score_tokens(self, tokens: Sequence[str], limit: int) -> Tuple[np.ndarray, np.ndarray]:
+    def score_tokens(self, tokens: Sequence[str], limit: int, filter=None) -> Tuple[np.ndarray, np.ndarray]:
         b = self._joined(tokens)
         cap = self.MAX_LIMIT if limit == 0 else min(limit, self.MAX_LIMIT)
         rows = np.zeros(max(cap, 1), dtype=np.uint64)
         sc = np.zeros(max(cap, 1), dtype=np.float32)
         n = C.c_uint32()
-        N.check(self._L.rlr_lexical_score(self._h, b, len(b), limit, rows.ctypes.data_as(N.u64p),
-                                          sc.ctypes.data_as(N.f32p), C.byref(n)))
+        if filter is not None:
+            N.check(self._L.rlr_lexical_score_filtered(self._h, filter.handle, b, len(b), limit, rows.ctypes.data_as(N.u64p),
+                                                       sc.ctypes.data_as(N.f32p), C.byref(n)))
+        else:
+            N.check(self._L.rlr_lexical_score(self._h, b, len(b), limit, rows.ctypes.data_as(N.u64p),
+                                              sc.ctypes.data_as(N.f32p), C.byref(n)))
         return rows[: n.value], sc[: n.value]
 
     def score_batch(self, queries: Sequence[str], limit: int, return_info: bool = False):
