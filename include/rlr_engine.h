@@ -151,6 +151,18 @@ int32_t rlr_engine_search_text_filtered(rlr_index *idx, rlr_lexical *lex, const 
                                         uint32_t dq, const char *query_tokens, size_t tokens_len, uint32_t top_k,
                                         float diversity_factor, int32_t stage, const rlr_query_weights *weights,
                                         rlr_search_hit *out, uint32_t cap, uint32_t *n_out);
+/* rlr_engine_search_with_diversity_batch inside a filter: n_queries raw query embeddings, no lexical pairs; query q
+ * equals rlr_engine_search_with_diversity_filtered(query q, n_lex = 0), N = |F| everywhere.  Hits of query q start at
+ * out[q * cap]; n_out[q] = their count (every one 0 when |F| = 0).  The candidates come from ONE
+ * rlr_search_topk_filtered call -- chunks of up to 8 queries share one masked pass over f32 rows of 256 / 512 / 768 /
+ * 1024 elements; binary16 rows, other widths and other pitches run query by query -- and the MMR from
+ * rlr_mmr_select_batch.  Argument checks and error codes of rlr_engine_search_with_diversity_batch; a stale filter, or
+ * one of another index: RLR_E_INVALID before any GPU work.  Batched TEXT search inside a filter (a masked batched
+ * BM25) does not exist: callers with query text loop rlr_engine_search_text_filtered. */
+int32_t rlr_engine_search_with_diversity_batch_filtered(rlr_index *idx, const rlr_filter *f, const float *queries_raw,
+                                                        uint32_t dq, uint32_t n_queries, uint32_t top_k,
+                                                        float diversity_factor, const rlr_query_weights *weights,
+                                                        rlr_search_hit *out, uint32_t cap, uint32_t *n_out);
 
 /* Additive batched entry point (the reference has no batched API; its oracle is "loop
  * search_with_diversity over the batch"): n_queries raw query embeddings,

@@ -372,8 +372,12 @@ int32_t rlr_filter_info(const rlr_filter *f, uint64_t *index_rows, uint64_t *n_a
  * not concurrent with searches that use the filter. */
 int32_t rlr_filter_set_path(rlr_filter *f, int32_t path);
 /* rlr_search_topk over the rows of `f`: same arguments and result contract, k clamped to the allowed rows.  Queries
- * run one by one over the master rows: the matrix-core batch, the coalescer and the nomination copies
- * (rlr_index_enable_batch_image) are not used. */
+ * run over the master rows: the matrix-core batch, the coalescer and the nomination copies
+ * (rlr_index_enable_batch_image) are not used.  With n_queries >= 2, chunks of up to 8 queries share ONE masked pass
+ * over f32 rows of 256 / 512 / 768 / 1024 elements when a cost model over the allowed bytes (or RLR_BATCH_MIN) says
+ * so, and runs of queries on the list path share one synchronisation; binary16 rows, other widths and other pitches
+ * run one by one.  Results are those of n_queries single-query calls, bit for bit.  Profile counters of a shared
+ * pass: n_batches, n_batch_queries, n_batch_fallbacks (queries re-run by the single-query filtered path). */
 int32_t rlr_search_topk_filtered(rlr_index *idx, const rlr_filter *f, const float *queries, uint32_t n_queries,
                                  uint32_t k, float guard_eps, uint64_t *rows_out, float *cos_out, uint32_t *n_out);
 

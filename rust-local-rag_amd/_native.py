@@ -175,6 +175,9 @@ PROTOTYPES = [
     ("rlr_engine_search_text_filtered", C.c_int32, [_H, _H, _H, f32p, C.c_uint32, C.c_char_p, C.c_size_t, C.c_uint32,
                                                     C.c_float, C.c_int32, C.POINTER(QueryWeightsC), C.POINTER(SearchHitC),
                                                     C.c_uint32, u32p]),
+    ("rlr_engine_search_with_diversity_batch_filtered", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                                    C.c_float, C.POINTER(QueryWeightsC),
+                                                                    C.POINTER(SearchHitC), C.c_uint32, u32p]),
     ("rlr_engine_search_with_diversity_batch", C.c_int32, [_H, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
                                                            C.POINTER(QueryWeightsC), C.POINTER(SearchHitC), C.c_uint32,
                                                            u32p]),

@@ -1,4 +1,5 @@
-// engine_filtered.cpp -- rlr_engine_search_filtered / _search_with_diversity_filtered / _search_text_filtered
+// engine_filtered.cpp -- rlr_engine_search_filtered / _search_with_diversity_filtered / _search_text_filtered /
+// _search_with_diversity_batch_filtered
 // (include/rlr_engine.h): RagEngine::search / search_with_diversity inside a row filter.  The corpus the reference's
 // code sees is the filter's rows in ascending order: the host half is engine_host.h over a backend whose candidate
 // universe is the filter -- its size where the reference uses the corpus size, its bit where a lexical pair is checked
@@ -143,6 +144,39 @@ int32_t rlr_engine_search_text_filtered(rlr_index *idx, rlr_lexical *lex, const 
                                                                  lrows.data(), lscores.data(), n_lex, out, cap, n_out)
                      : rlr_engine_search_filtered(idx, f, query_raw, dq, top_k, weights, lrows.data(), lscores.data(), n_lex,
                                                   stage, out, cap, n_out);
+}
+
+int32_t rlr_engine_search_with_diversity_batch_filtered(rlr_index *idx, const rlr_filter *f, const float *queries_raw, uint32_t dq,
+                                                        uint32_t n_queries, uint32_t top_k, float diversity_factor,
+                                                        const rlr_query_weights *weights, rlr_search_hit *out, uint32_t cap,
+                                                        uint32_t *n_out)
+{
+    if (!idx || !f || !n_out || (n_queries && !queries_raw && dq) || (n_queries && cap && !out))
+        return RLR_E_INVALID;
+    for (uint32_t q = 0; q < n_queries; ++q)
+        n_out[q] = 0;
+    int32_t st = rlr::filter_check(idx, f); // a stale filter, or one of another index: before any GPU work
+    if (st != RLR_OK)
+        return st;
+    FilteredBackend be;
+    st = filtered_backend(idx, f, &be);
+    if (st != RLR_OK)
+        return st;
+    if (n_queries == 0)
+        return RLR_OK;
+    if (diversity_factor < 0.0f) diversity_factor = 0.0f;
+    if (diversity_factor > 1.0f) diversity_factor = 1.0f;
+    rlr_resolved_weights w;
+    rlr_resolve_weights(weights, &w);
+    std::vector<std::vector<Cand>> results;
+    // the queries' top-k is ONE rlr_search_topk_filtered call (chunks of up to 8 share a masked pass), the pools' MMR one
+    // rlr_mmr_select_batch
+    st = generic_search_with_diversity_batch(be, queries_raw, dq, n_queries, top_k, diversity_factor, w, results);
+    if (st != RLR_OK)
+        return st;
+    for (uint32_t q = 0; q < n_queries; ++q)
+        emit(results[q], out + static_cast<size_t>(q) * cap, cap, &n_out[q]);
+    return RLR_OK;
 }
 
 } // extern "C"

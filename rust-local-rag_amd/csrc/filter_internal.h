@@ -16,5 +16,7 @@ struct FilterView {
 
 // RLR_E_INVALID (message in rlr_last_error) for a null filter or one whose index has been mutated since it was made
 int32_t filter_view(const rlr_filter *f, FilterView *out);
+// the same, and RLR_E_INVALID for a filter that was made for another index than `ix`; no GPU work
+int32_t filter_check(const rlr_index *ix, const rlr_filter *f);
 
 } // namespace rlr

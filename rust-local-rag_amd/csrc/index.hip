@@ -2048,6 +2048,73 @@ bool batch_eligible(const rlr_index *ix, uint32_t nq, uint32_t k, bool f16_ok = 
     return nq * t_single > t_batch;
 }
 
+// The per-query workspace of a batched run of nq queries (select states, histograms, status words, fin_cap candidates and
+// s_stride sample scores each), the states armed for rank `rank` of n scored rows, histograms and status words cleared on
+// the context's stream.  Shared by run_batched and the filtered shared pass.
+int32_t batch_arm(Ctx *c, uint32_t nq, uint32_t fin_cap, uint64_t s_stride, uint32_t rank, uint64_t n)
+{
+    hipStream_t s = c->stream;
+    if (c->bq_cap < nq) {
+        (void)hipFree(c->d_tau);
+        (void)hipFree(c->d_bstate);
+        (void)hipFree(c->d_bhist);
+        (void)hipFree(c->d_bstatus);
+        if (c->h_batch) (void)hipHostFree(c->h_batch);
+        c->h_batch = nullptr;
+        c->d_tau = nullptr;
+        c->d_bstate = nullptr;
+        c->d_bhist = nullptr;
+        c->d_bstatus = nullptr;
+        c->bq_cap = 0;
+        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_tau), static_cast<size_t>(nq) * sizeof(float)));
+        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_bstate), static_cast<size_t>(nq) * sizeof(SelectState)));
+        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_bhist), static_cast<size_t>(nq) * 2 * kHistBins * sizeof(uint32_t)));
+        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_bstatus), static_cast<size_t>(nq) * sizeof(uint32_t)));
+        RLR_HIP(hipHostMalloc(&c->h_batch, static_cast<size_t>(nq) * (sizeof(SelectState) + sizeof(uint32_t)), hipHostMallocDefault));
+        c->bq_cap = nq;
+    }
+    RLR_TRY(grow(&c->d_bcand, &c->bcand_cap, static_cast<uint64_t>(nq) * fin_cap));
+    RLR_TRY(grow(&c->d_sample, &c->sample_cap, static_cast<uint64_t>(nq) * s_stride));
+    SelectState *h_st = static_cast<SelectState *>(c->h_batch);
+    for (uint32_t i = 0; i < nq; ++i) {
+        std::memset(&h_st[i], 0, sizeof(SelectState));
+        h_st[i].k = static_cast<uint32_t>(std::min<uint64_t>(rank, n));
+        h_st[i].cap = fin_cap;
+    }
+    RLR_HIP(hipMemcpyAsync(c->d_bstate, h_st, nq * sizeof(SelectState), hipMemcpyHostToDevice, s));
+    RLR_HIP(hipMemsetAsync(c->d_bhist, 0, static_cast<size_t>(nq) * 2 * kHistBins * sizeof(uint32_t), s));
+    RLR_HIP(hipMemsetAsync(c->d_bstatus, 0xFF, static_cast<size_t>(nq) * sizeof(uint32_t), s));
+    return RLR_OK;
+}
+
+// The end of a batched run: the per-query finish (band, reference-order re-score, order, emit) over the candidates the
+// select and the nomination left, then ONE copy of the status words (and of the results, when h_res_out is given) and one
+// synchronisation.  h_status[q] != 0: the finish handed query q back.  n_cand_out (optional): the candidates the select
+// collected per query (the rows at or above its floor), fetched with the same synchronisation.
+int32_t batch_finish(rlr_index *ix, Ctx *c, const float *dq, uint32_t nq, uint32_t k, float two_eps, uint64_t *d_out,
+                     std::vector<uint32_t> &h_status, uint64_t *h_res_out, std::vector<uint32_t> *n_cand_out = nullptr)
+{
+    hipStream_t s = c->stream;
+    uint32_t *h_stat = reinterpret_cast<uint32_t *>(static_cast<SelectState *>(c->h_batch) + c->bq_cap);
+    RLR_HIP(launch_batch_finish(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, dq, ix->q_pitch, nq, c->d_bcand, batch_finish_capacity(),
+                                c->d_bstate, k, two_eps, d_out, c->d_bstatus, s));
+    if (ix->profiling) RLR_HIP(hipEventRecord(c->ev[3], s));
+    RLR_HIP(hipMemcpyAsync(h_stat, c->d_bstatus, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (h_res_out) // the batch's results ride on the same synchronisation (queries handed back are fetched again by the caller)
+        RLR_HIP(hipMemcpyAsync(h_res_out, d_out, static_cast<size_t>(nq) * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    SelectState *h_st = static_cast<SelectState *>(c->h_batch);
+    if (n_cand_out)
+        RLR_HIP(hipMemcpyAsync(h_st, c->d_bstate, nq * sizeof(SelectState), hipMemcpyDeviceToHost, s));
+    RLR_HIP(hipStreamSynchronize(s));
+    h_status.assign(h_stat, h_stat + nq);
+    if (n_cand_out) {
+        n_cand_out->resize(nq);
+        for (uint32_t q = 0; q < nq; ++q)
+            (*n_cand_out)[q] = h_st[q].n_cand;
+    }
+    return RLR_OK;
+}
+
 // Runs queries [q0, q0+nq) (already staged in c->d_query) through the GEMM nomination pipeline
 // and leaves k packed results per query in d_out; h_status[q] != 0 marks queries the caller must
 // re-run through the single-query pipeline.
@@ -2099,42 +2166,12 @@ int32_t run_batched(rlr_index *ix, Ctx *c, uint32_t q0, uint32_t nq, const Searc
         RLR_HIP(rlr::dev_malloc(&c->d_qfrag, qfrag_bytes));
         c->qfrag_cap = qfrag_bytes;
     }
-    if (c->bq_cap < nq) {
-        (void)hipFree(c->d_tau);
-        (void)hipFree(c->d_bstate);
-        (void)hipFree(c->d_bhist);
-        (void)hipFree(c->d_bstatus);
-        if (c->h_batch) (void)hipHostFree(c->h_batch);
-        c->h_batch = nullptr;
-        c->d_tau = nullptr;
-        c->d_bstate = nullptr;
-        c->d_bhist = nullptr;
-        c->d_bstatus = nullptr;
-        c->bq_cap = 0;
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_tau), static_cast<size_t>(nq) * sizeof(float)));
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_bstate), static_cast<size_t>(nq) * sizeof(SelectState)));
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_bhist), static_cast<size_t>(nq) * 2 * kHistBins * sizeof(uint32_t)));
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_bstatus), static_cast<size_t>(nq) * sizeof(uint32_t)));
-        RLR_HIP(hipHostMalloc(&c->h_batch, static_cast<size_t>(nq) * (sizeof(SelectState) + sizeof(uint32_t)), hipHostMallocDefault));
-        c->bq_cap = nq;
-    }
     if (!c->d_gsync)
         RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_gsync), 256 * sizeof(uint32_t)));
-    RLR_TRY(grow(&c->d_bcand, &c->bcand_cap, static_cast<uint64_t>(nq) * fin_cap));
-    RLR_TRY(grow(&c->d_sample, &c->sample_cap, static_cast<uint64_t>(nq) * s_stride));
+    RLR_TRY(batch_arm(c, nq, fin_cap, s_stride, rank, S));
 
-    SelectState *h_st = static_cast<SelectState *>(c->h_batch);
-    uint32_t *h_stat = reinterpret_cast<uint32_t *>(h_st + c->bq_cap);
-    for (uint32_t i = 0; i < nq; ++i) {
-        std::memset(&h_st[i], 0, sizeof(SelectState));
-        h_st[i].k = std::min<uint32_t>(rank, static_cast<uint32_t>(S));
-        h_st[i].cap = fin_cap;
-    }
     const float *dq = c->d_query + static_cast<size_t>(q0) * ix->q_pitch;
     const bool timed = ix->profiling;
-    RLR_HIP(hipMemcpyAsync(c->d_bstate, h_st, nq * sizeof(SelectState), hipMemcpyHostToDevice, s));
-    RLR_HIP(hipMemsetAsync(c->d_bhist, 0, static_cast<size_t>(nq) * 2 * kHistBins * sizeof(uint32_t), s));
-    RLR_HIP(hipMemsetAsync(c->d_bstatus, 0xFF, static_cast<size_t>(nq) * sizeof(uint32_t), s));
     if (timed) RLR_HIP(hipEventRecord(c->bev[0], s));
     const bool use_image = ix->image_enabled && ix->d_image && gemm_image_usable(ix->dim);
     const void *image = use_image ? ix->d_image : nullptr;
@@ -2165,14 +2202,7 @@ int32_t run_batched(rlr_index *ix, Ctx *c, uint32_t q0, uint32_t nq, const Searc
                                  c->d_tau, c->d_bcand, fin_cap, c->d_bstate, nullptr, 0, image, s, c->d_gsync));
     if (timed) RLR_HIP(hipEventRecord(c->bev[3], s));
     // 4. per-query finish: band, reference-order re-score, order, emit
-    RLR_HIP(launch_batch_finish(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, dq, ix->q_pitch, nq, c->d_bcand, fin_cap,
-                                c->d_bstate, p.k, two_eps, d_out, c->d_bstatus, s));
-    if (timed) RLR_HIP(hipEventRecord(c->ev[3], s));
-    RLR_HIP(hipMemcpyAsync(h_stat, c->d_bstatus, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (h_res_out) // the batch's results ride on the same synchronisation (queries handed back are fetched again by the caller)
-        RLR_HIP(hipMemcpyAsync(h_res_out, d_out, static_cast<size_t>(nq) * p.k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    RLR_HIP(hipStreamSynchronize(s));
-    h_status.assign(h_stat, h_stat + nq);
+    RLR_TRY(batch_finish(ix, c, dq, nq, p.k, two_eps, d_out, h_status, h_res_out));
     uint64_t fallbacks = 0;
     for (uint32_t v : h_status)
         fallbacks += v != 0;
@@ -2409,6 +2439,8 @@ int32_t search_topk_host(rlr_index *ix, const float *queries, uint32_t n_queries
 // (tools/bench_filtered.py, DESIGN.md "Row filters"): list / scan 42 / 50 us at 256 rows, 56 / 60 at 8192, 69 / 66 at
 // 16 384, 134 / 87 at 65 536 -- the crossover lies near 12 k rows; rounded down to a power of two.
 constexpr uint64_t kFilterListMax = 8192;
+constexpr uint64_t kFilterListBatchEntries = 1u << 20; // list-path workspace of one run of queries: keys (queries x padded rows) at most
+constexpr uint64_t kFilterListBatchQueries = 256;    // ... and queries enqueued back to back behind one synchronisation at most
 
 int32_t check_filter(const rlr_index *ix, const rlr_filter *f)
 {
@@ -2439,6 +2471,27 @@ int32_t reserve_cand(Ctx *c, uint32_t cap)
 // The list path, and the exact fall-back of the masked scan: every allowed row scored in reference order (no nomination,
 // no band), the keys sorted -- or, for k <= 4096, the k best selected and sorted by one workgroup.  The query is in
 // c->d_query; p.k <= n_allowed.  The k packed results end up in h_res.
+int32_t filtered_exact_enqueue(rlr_index *ix, Ctx *c, const rlr_filter *f, const SearchPlan &p, uint32_t qi, float *d_vals,
+                               uint64_t *d_packed, uint32_t cap, uint64_t *d_out)
+{
+    hipStream_t s = c->stream;
+    const uint32_t n = static_cast<uint32_t>(f->n_allowed);
+    SelectState *st = c->d_state + qi;
+    RLR_HIP(launch_score_rows(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_query + static_cast<size_t>(qi) * ix->q_pitch,
+                              f->d_list, n, d_vals, s));
+    hipLaunchKernelGGL(rlr::pack_list_kernel, dim3(std::min<uint32_t>((cap + 255) / 256, 1024)), dim3(256), 0, s, d_vals,
+                       f->d_list, n, d_packed, cap, st);
+    RLR_HIP(hipGetLastError());
+    if (p.k <= kLdsSortCap) {
+        hipLaunchKernelGGL(rlr::topk_global_kernel, dim3(1), dim3(1024), 0, s, d_packed, st, cap, d_out, p.k);
+    } else {
+        RLR_HIP(launch_sort_desc(d_packed, cap, s));
+        hipLaunchKernelGGL(rlr::emit_kernel, dim3((p.k + 255) / 256), dim3(256), 0, s, d_packed, n, d_out, p.k);
+    }
+    RLR_HIP(hipGetLastError());
+    return RLR_OK;
+}
+
 int32_t filtered_exact(rlr_index *ix, Ctx *c, const rlr_filter *f, const SearchPlan &p, uint64_t *h_res)
 {
     hipStream_t s = c->stream;
@@ -2446,21 +2499,16 @@ int32_t filtered_exact(rlr_index *ix, Ctx *c, const rlr_filter *f, const SearchP
     const uint32_t cap = next_pow2(std::max<uint32_t>(n, p.k));
     RLR_TRY(reserve_list(c, n));
     RLR_TRY(reserve_cand(c, cap));
-    SelectState *st = c->d_state;
-    RLR_HIP(launch_score_rows(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_query, f->d_list, n, c->d_vals, s));
-    hipLaunchKernelGGL(rlr::pack_list_kernel, dim3(std::min<uint32_t>((cap + 255) / 256, 1024)), dim3(256), 0, s, c->d_vals,
-                       f->d_list, n, c->d_packed, cap, st);
-    RLR_HIP(hipGetLastError());
-    if (p.k <= kLdsSortCap) {
-        hipLaunchKernelGGL(rlr::topk_global_kernel, dim3(1), dim3(1024), 0, s, c->d_packed, st, cap, c->d_out, p.k);
-    } else {
-        RLR_HIP(launch_sort_desc(c->d_packed, cap, s));
-        hipLaunchKernelGGL(rlr::emit_kernel, dim3((p.k + 255) / 256), dim3(256), 0, s, c->d_packed, n, c->d_out, p.k);
-    }
-    RLR_HIP(hipGetLastError());
+    RLR_TRY(filtered_exact_enqueue(ix, c, f, p, 0, c->d_vals, c->d_packed, cap, c->d_out));
     RLR_HIP(hipMemcpyAsync(h_res, c->d_out, static_cast<size_t>(p.k) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     RLR_HIP(hipStreamSynchronize(s));
     return RLR_OK;
+}
+
+// is `row` an allowed row of `f`?  (the host copy of the mask: what every returned row is tested against)
+bool filter_holds(const rlr_filter *f, uint32_t row)
+{
+    return row < f->index_rows && ((f->h_mask[row >> 6] >> (row & 63)) & 1ull);
 }
 
 // One query over the rows of `f` (n_allowed > 0, k > 0).  Filtered calls scan the master rows and never use the
@@ -2512,10 +2560,8 @@ int32_t filtered_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *
         // its real values it can rank anywhere.  So every returned row is tested against the host copy of the mask --
         // if none is masked the result is the right one -- and a failed test takes the exact path.
         bool leaked = false;
-        for (uint32_t i = 0; i < p.k && !leaked; ++i) {
-            const uint32_t row = 0xFFFFFFFFu - static_cast<uint32_t>(h_res[i]);
-            leaked = row >= f->index_rows || !((f->h_mask[row >> 6] >> (row & 63)) & 1ull);
-        }
+        for (uint32_t i = 0; i < p.k && !leaked; ++i)
+            leaked = !filter_holds(f, 0xFFFFFFFFu - static_cast<uint32_t>(h_res[i]));
         if (leaked) {
             n_retry++;
             RLR_TRY(filtered_exact(ix, c, f, p, h_res));
@@ -2525,6 +2571,138 @@ int32_t filtered_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *
     *n_out = p.k;
     unpack_results(h_res, p.k, rows_out, cos_out);
     return note_search(ix, c, 1, n_cand, n_retry, timed && f->path != 0);
+}
+
+// ---- several queries inside one filter ------------------------------------------------------------------------------
+// Does a chunk of nq (2..8) queries over `f` take the shared masked pass (scan_masked_multi_kernel)?  The filter's path
+// must be the masked scan and the rows a shape the kernel serves; k (already clamped to the allowed rows) must leave the
+// finish its band.  RLR_BATCH_MIN decides when set.  Else a cost model over the ALLOWED bytes A, fitted to the calls
+// measured at 1 M x 768 f32, k = 100 (tools/bench_filtered.py --queries against the parent build, natural and with the
+// pass forced; DESIGN.md "Several queries inside one filter" has the table and what was NOT measured):
+//   one by one   per query 45 us of launches and its own synchronisation + A / 6.5 TB/s
+//                (measured 0.050 / 0.10 / 0.28 / 0.50 ms per query at 0.01 / 0.1 / 0.5 / 1.0 of the rows)
+//   shared       100 us for the batched select, the finish and the one synchronisation, 6 us per query and million rows
+//                (the select reads an n_rows-long score array per query, sentinels included, whatever the filter allows)
+//                and one pass at 6.5 / 6.0 / 4.1 TB/s for the Q = 2 / 4 / 8 instance (eight queries are VALU-bound)
+//                (measured 0.106 / 0.112 / 0.142 ms at 0.01, 0.55 / 0.62 / 0.88 with every row allowed)
+// and the shared pass must win by 10 %: two queries over a hundredth of the rows measured 3-5 % SLOWER shared and stay
+// one by one, as the model has it.
+bool filtered_batch_eligible(const rlr_index *ix, const rlr_filter *f, uint32_t nq, uint32_t k)
+{
+    if (nq < 2 || f->path != 1 || !batch_multi_shape(ix, nq) || k * 8 > batch_finish_capacity())
+        return false;
+    if (ix->batch_min > 0)
+        return nq >= ix->batch_min;
+    const double allowed_bytes = static_cast<double>(f->n_allowed) * ix->dim * 4.0;
+    const double t_single = 45e-6 + allowed_bytes / 6.5e12;
+    const double pass_rate = nq <= 2 ? 6.5e12 : nq <= 4 ? 6.0e12 : 4.1e12;
+    const double t_shared = 100e-6 + nq * (static_cast<double>(ix->n_rows) * 6e-12) + allowed_bytes / pass_rate;
+    return nq * t_single > 1.1 * t_shared;
+}
+
+// A chunk of m (2..8) queries over `f` through ONE masked pass: the queries staged and uploaded once, the pass into
+// c->d_sample (the "sample" is the whole score array: rank = k, as run_batched's use_multi branch), the batched select and
+// finish, one result copy and one synchronisation.  The hazards filtered_query closes are closed per query: a result
+// holding a masked row (k reached allowed rows whose nominated score is NaN: threshold key 0) and a query the finish
+// handed back (band overflow, mass ties) are re-run by filtered_query -- never by an unfiltered path.  c->d_hist is not
+// touched (the select's histograms are c->d_bhist, cleared in front of every use).
+int32_t filtered_batch(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *queries, uint32_t m, uint32_t k, float guard_eps,
+                       uint64_t *rows_out, float *cos_out, uint32_t *n_out)
+{
+    const SearchPlan p = make_plan(ix, queries, m, static_cast<uint32_t>(std::min<uint64_t>(k, f->n_allowed)), guard_eps);
+    RLR_TRY(ctx_prepare(ix, c, m, p));
+    const size_t q_bytes = static_cast<size_t>(m) * ix->q_pitch * sizeof(float);
+    const size_t n_res = static_cast<size_t>(m) * p.k;
+    RLR_TRY(pin_reserve(c, q_bytes + n_res * sizeof(uint64_t)));
+    float *h_q = static_cast<float *>(c->h_pin);
+    uint64_t *h_res = reinterpret_cast<uint64_t *>(static_cast<char *>(c->h_pin) + q_bytes);
+    stage_queries(ix, c, queries, m, h_q);
+    hipStream_t s = c->stream;
+    c->h_q_kq = nullptr;
+    RLR_HIP(upload_queries(c, h_q, q_bytes, s));
+    const uint64_t n = ix->n_rows;
+    const uint64_t s_stride = (n + 3) / 4 * 4;
+    const float two_eps = p.two_eps; // the summation-order band: 2 x (0.5 x two_eps), as run_batched's shared scan
+    RLR_TRY(batch_arm(c, m, batch_finish_capacity(), s_stride, p.k, n));
+    const bool timed = ix->profiling;
+    if (timed) RLR_HIP(hipEventRecord(c->bev[0], s));
+    hipError_t e = hipSuccess;
+    if (!launch_scan_masked_multi(scan_args(ix, c->d_query, c->d_sample, nullptr), f->d_mask, f->n_allowed, ix->q_pitch, m,
+                                  s_stride, s, &e))
+        return fail(RLR_E_INTERNAL, "masked multi-query scan refused a shape its gate accepted");
+    RLR_HIP(e);
+    if (timed) RLR_HIP(hipEventRecord(c->bev[1], s));
+    RLR_HIP(launch_batch_select(c->d_sample, static_cast<uint32_t>(n), s_stride, m, c->d_bhist, c->d_bstate, two_eps, c->d_tau,
+                                c->d_bcand, batch_finish_capacity(), ix->n_cu, s));
+    std::vector<uint32_t> status, n_cand;
+    RLR_TRY(batch_finish(ix, c, c->d_query, m, p.k, two_eps, c->d_out, status, h_res, &n_cand));
+    c->hist_dirty = false;
+    std::vector<uint32_t> redo;
+    uint64_t n_cand_total = 0; // of the queries served here, as filtered_query reports its own
+    for (uint32_t q = 0; q < m; ++q) {
+        bool back = status[q] != 0;
+        for (uint32_t i = 0; i < p.k && !back; ++i)
+            back = !filter_holds(f, 0xFFFFFFFFu - static_cast<uint32_t>(h_res[static_cast<size_t>(q) * p.k + i]));
+        if (back) {
+            redo.push_back(q);
+            continue;
+        }
+        n_out[q] = p.k;
+        n_cand_total += n_cand[q];
+        unpack_results(h_res + static_cast<size_t>(q) * p.k, p.k, rows_out + static_cast<size_t>(q) * k, cos_out + static_cast<size_t>(q) * k);
+    }
+    {
+        float scan_ms = 0;
+        if (timed)
+            (void)hipEventElapsedTime(&scan_ms, c->bev[0], c->bev[1]);
+        std::lock_guard<std::mutex> lk(ix->mu);
+        ix->prof.n_batches += 1;
+        ix->prof.n_batch_queries += m;
+        ix->prof.n_batch_fallbacks += redo.size();
+        ix->prof.n_searches += m - redo.size(); // (a query handed back is counted by filtered_query)
+        ix->prof.n_candidates += n_cand_total;
+        if (timed) {
+            ix->prof.scan_ms += scan_ms;
+            ix->prof.scan_bytes += f->n_allowed * ix->dim * 4;
+        }
+    }
+    // (from here on the pinned buffer and the context are filtered_query's)
+    for (uint32_t q : redo)
+        RLR_TRY(filtered_query(ix, c, f, queries + static_cast<size_t>(q) * ix->dim, k, guard_eps, rows_out + static_cast<size_t>(q) * k,
+                               cos_out + static_cast<size_t>(q) * k, &n_out[q]));
+    return RLR_OK;
+}
+
+// The list path for a run of m >= 2 queries: score -> pack -> select of every query enqueued back to back on per-query
+// slices of the workspace, then one result copy and one synchronisation.  Same kernels, same results as filtered_exact.
+int32_t filtered_list_batch(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *queries, uint32_t m, uint32_t k,
+                            float guard_eps, uint64_t *rows_out, float *cos_out, uint32_t *n_out)
+{
+    const SearchPlan p = make_plan(ix, queries, m, static_cast<uint32_t>(std::min<uint64_t>(k, f->n_allowed)), guard_eps);
+    RLR_TRY(ctx_prepare(ix, c, m, p));
+    const size_t q_bytes = static_cast<size_t>(m) * ix->q_pitch * sizeof(float);
+    const size_t n_res = static_cast<size_t>(m) * p.k;
+    RLR_TRY(pin_reserve(c, q_bytes + n_res * sizeof(uint64_t)));
+    float *h_q = static_cast<float *>(c->h_pin);
+    uint64_t *h_res = reinterpret_cast<uint64_t *>(static_cast<char *>(c->h_pin) + q_bytes);
+    stage_queries(ix, c, queries, m, h_q);
+    hipStream_t s = c->stream;
+    c->h_q_kq = nullptr;
+    RLR_HIP(upload_queries(c, h_q, q_bytes, s));
+    const uint32_t cap = next_pow2(std::max<uint32_t>(static_cast<uint32_t>(f->n_allowed), p.k));
+    RLR_TRY(reserve_list(c, m * cap));
+    RLR_TRY(reserve_cand(c, next_pow2(m * cap)));
+    for (uint32_t q = 0; q < m; ++q)
+        RLR_TRY(filtered_exact_enqueue(ix, c, f, p, q, c->d_vals + static_cast<size_t>(q) * cap, c->d_packed + static_cast<size_t>(q) * cap,
+                                       cap, c->d_out + static_cast<size_t>(q) * p.k));
+    RLR_HIP(hipMemcpyAsync(h_res, c->d_out, n_res * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    RLR_HIP(hipStreamSynchronize(s));
+    c->hist_dirty = false;
+    for (uint32_t q = 0; q < m; ++q) {
+        n_out[q] = p.k;
+        unpack_results(h_res + static_cast<size_t>(q) * p.k, p.k, rows_out + static_cast<size_t>(q) * k, cos_out + static_cast<size_t>(q) * k);
+    }
+    return note_search(ix, c, m, 0, 0, /*timed=*/false);
 }
 
 int32_t filter_finish(rlr_index *ix, std::vector<uint64_t> &&mask, rlr_filter **out)
@@ -3143,9 +3321,28 @@ int32_t rlr_search_topk_filtered(rlr_index *ix, const rlr_filter *f, const float
     CtxLease lease(ix);
     RLR_TRY(ctx_acquire(ix, &lease.c));
     StreamDrain drain{lease.c->stream};
-    for (uint32_t q = 0; q < n_queries; ++q) // query by query: no matrix-core batch, no coalesced group
-        RLR_TRY(filtered_query(ix, lease.c, f, queries + static_cast<size_t>(q) * ix->dim, k, guard_eps,
-                               rows_out + static_cast<size_t>(q) * k, cos_out + static_cast<size_t>(q) * k, &n_out[q]));
+    // Chunks of up to 8 queries share one masked pass where the gate says so (filtered_batch_eligible); on the list path
+    // runs of queries share one synchronisation; everything else -- binary16 rows, other widths and pitches, a last chunk
+    // of one query -- goes query by query.  No matrix-core batch, no coalesced group.
+    const uint32_t k_eff = static_cast<uint32_t>(std::min<uint64_t>(k, f->n_allowed));
+    const uint32_t list_run = static_cast<uint32_t>(std::min<uint64_t>(
+        kFilterListBatchQueries,
+        std::max<uint64_t>(1, kFilterListBatchEntries / next_pow2(std::max<uint32_t>(static_cast<uint32_t>(f->n_allowed), k_eff)))));
+    for (uint32_t q0 = 0; q0 < n_queries;) {
+        const float *qs = queries + static_cast<size_t>(q0) * ix->dim;
+        uint64_t *ro = rows_out + static_cast<size_t>(q0) * k;
+        float *co = cos_out + static_cast<size_t>(q0) * k;
+        uint32_t m = std::min<uint32_t>(8, n_queries - q0);
+        if (filtered_batch_eligible(ix, f, m, k_eff)) {
+            RLR_TRY(filtered_batch(ix, lease.c, f, qs, m, k, guard_eps, ro, co, n_out + q0));
+        } else if (f->path == 0 && (m = std::min(list_run, n_queries - q0)) >= 2) {
+            RLR_TRY(filtered_list_batch(ix, lease.c, f, qs, m, k, guard_eps, ro, co, n_out + q0));
+        } else {
+            m = 1;
+            RLR_TRY(filtered_query(ix, lease.c, f, qs, k, guard_eps, ro, co, &n_out[q0]));
+        }
+        q0 += m;
+    }
     drain.armed = false;
     return RLR_OK;
 }
@@ -4157,5 +4354,10 @@ int32_t filter_view(const rlr_filter *f, FilterView *out)
     out->n_allowed = f->n_allowed;
     out->device = f->ix->device;
     return RLR_OK;
+}
+
+int32_t filter_check(const rlr_index *ix, const rlr_filter *f)
+{
+    return check_filter(ix, f);
 }
 } // namespace rlr

@@ -45,7 +45,12 @@ hipError_t launch_scan_masked(const ScanArgs &a, const uint64_t *mask, uint64_t 
 // false when the shape is not served (then nothing was launched)
 bool launch_scan_multi(const ScanArgs &a, uint32_t q_pitch, uint32_t n_queries, size_t score_stride, hipStream_t s,
                        hipError_t *err);
-// the same over binary16 rows of C x 512 B (C = 1..4), f32 arithmetic on the exactly widened elements (coalesced
+// one MASKED pass for 2..8 queries (a document-scoped batch): launch_scan_multi's arguments and score layout,
+// launch_scan_masked's mask; masked rows leave as NaN in every query's array, no histogram.  f32 rows of 1..4 KiB
+// only -- binary16 rows, other widths and other pitches return false and keep the one-by-one masked scans.
+bool launch_scan_masked_multi(const ScanArgs &a, const uint64_t *mask, uint64_t n_allowed, uint32_t q_pitch, uint32_t n_queries,
+                              size_t score_stride, hipStream_t s, hipError_t *err);
+// launch_scan_multi over binary16 rows of C x 512 B (C = 1..4), f32 arithmetic on the exactly widened elements (coalesced
 // single-query calls only; see run_batched)
 bool launch_scan_multi_f16(const ScanArgs &a, uint32_t q_pitch, uint32_t n_queries, size_t score_stride, hipStream_t s,
                            hipError_t *err);

@@ -701,6 +701,99 @@ __global__ __launch_bounds__(256) void scan_masked_generic_kernel(const float4 *
     }
 }
 
+// ---------------------------------------------------------------------------
+// Masked multi-query kernel: 2..8 queries share ONE masked pass (a document-scoped batch).  The cross of the two kernels
+// above it: the row walk of scan_masked_fixed_kernel (a unit of one mask word, the word through a wave-uniform address,
+// ctz / clear-lowest over its set bits, R allowed rows in flight, every branch on the mask wave-uniform, a masked row's
+// bytes never requested) and the arithmetic of scan_multi_kernel (Q x CH float4 of queries per lane, slots at or beyond
+// n_queries zero; every loaded row feeds Q dot4 chains and Q DPP wave sums).  The per-lane partials and the reduction
+// are those of the single masked scan, so an allowed row's nominated score for a query is the one that scan stores and
+// the band is the summation-order band.  Scores go to Q arrays (stride score_stride); a masked row leaves as the NaN
+// sentinel in the same coalesced store; no histogram (the batched select behind it builds them).
+// f32 rows of CH KiB only: binary16 rows, other widths and other pitches keep the one-by-one masked scans.
+// Registers (the compiler's resource report for gfx950, __launch_bounds__(256); waves per SIMD the allocation allows):
+//            Q = 2       Q = 4       Q = 8
+//   CH = 1   36 -> 8     47 -> 8     65 -> 7
+//   CH = 2   60 -> 8     77 -> 6    114 -> 4
+//   CH = 3   84 -> 5    110 -> 4    161 -> 3
+//   CH = 4  108 -> 4    141 -> 3    208 -> 2
+// (no AGPRs, no scratch: the queries take Q x CH x 4 VGPRs, the R = 4 rows in flight 16 x CH.)  The sparse launch shape
+// wants four workgroups per CU, one wave of each per SIMD; launch_scan_masked_multi lowers that to what stays resident.
+// ---------------------------------------------------------------------------
+template <int CH, int Q>
+__global__ __launch_bounds__(256) void scan_masked_multi_kernel(const float4 *__restrict__ rows, const float *__restrict__ queries,
+                                                                uint32_t q_pitch, uint32_t n_queries,
+                                                                const uint64_t *__restrict__ mask, float *__restrict__ scores,
+                                                                size_t score_stride, uint32_t n_rows, uint32_t unit)
+{
+    constexpr int P16 = CH * 64;
+    constexpr int R = 4;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    float4 qv[Q][CH];
+#pragma unroll
+    for (int q = 0; q < Q; ++q)
+#pragma unroll
+        for (int c = 0; c < CH; ++c)
+            qv[q][c] = static_cast<uint32_t>(q) < n_queries
+                           ? reinterpret_cast<const float4 *>(queries + static_cast<size_t>(q) * q_pitch)[c * 64 + lane]
+                           : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+
+    const float masked = __builtin_bit_cast(float, 0x7FC00000u);
+    const uint32_t n_groups = (n_rows + unit - 1) / unit;
+    const uint32_t n_waves = gridDim.x * 4;
+    for (uint32_t g = blockIdx.x * 4 + wave; g < n_groups; g += n_waves) {
+        const uint32_t row0 = g * unit;
+        const uint32_t nr = min(unit, n_rows - row0);
+        const uint64_t word = mask_bits(mask, row0, unit, nr);
+        float mine[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q)
+            mine[q] = masked;
+        uint64_t rem = word;
+        while (rem) { // (uniform)
+            uint32_t bit[R];
+            float4 x[R][CH];
+            int m = 0;
+#pragma unroll
+            for (int rr = 0; rr < R; ++rr) {
+                bit[rr] = 0;
+                if (rem) { // (uniform)
+                    bit[rr] = static_cast<uint32_t>(__builtin_ctzll(rem));
+                    rem &= rem - 1;
+                    m = rr + 1;
+                    const float4 *p = rows + static_cast<size_t>(row0 + bit[rr]) * P16 + lane;
+#pragma unroll
+                    for (int c = 0; c < CH; ++c)
+                        x[rr][c] = ld16<true>(p + c * 64);
+                }
+            }
+#pragma unroll
+            for (int rr = 0; rr < R; ++rr) {
+                if (rr < m) { // (uniform)
+#pragma unroll
+                    for (int q = 0; q < Q; ++q) {
+                        float acc = 0.0f;
+#pragma unroll
+                        for (int c = 0; c < CH; ++c)
+                            acc = dot4(x[rr][c], qv[q][c], acc);
+                        const float tot = wave_sum(acc);
+                        if (static_cast<uint32_t>(lane) == bit[rr])
+                            mine[q] = tot;
+                    }
+                }
+            }
+        }
+        if (static_cast<uint32_t>(lane) < nr) {
+#pragma unroll
+            for (int q = 0; q < Q; ++q)
+                if (static_cast<uint32_t>(q) < n_queries)
+                    scores[static_cast<size_t>(q) * score_stride + row0 + lane] = mine[q];
+        }
+    }
+}
+
 struct ScanPlan {
     uint32_t group_rows;
     uint32_t blocks;
@@ -1093,6 +1186,50 @@ bool launch_scan_multi(const ScanArgs &a, uint32_t q_pitch, uint32_t n_queries, 
     }
 #undef RLR_MULTI_Q
 #undef RLR_MULTI
+    *err = hipGetLastError();
+    return true;
+}
+
+// 2..8 queries over the rows a filter allows (mask / n_allowed as launch_scan_masked takes them): f32 rows whose pitch
+// is a multiple of 1 KiB (256/512/768/1024-d); false otherwise (then nothing was launched).  The launch shape is the
+// policy launch_scan_masked measured -- 8-row units and one workgroup per CU from a quarter of the rows allowed, 16-row
+// units and four workgroups per CU below that -- with the four lowered to the workgroups whose registers fit a CU at once
+// (the table above scan_masked_multi_kernel: three for 768-d x 8 and 1024-d x 4 queries, two for 1024-d x 8).
+bool launch_scan_masked_multi(const ScanArgs &a, const uint64_t *mask, uint64_t n_allowed, uint32_t q_pitch, uint32_t n_queries,
+                              size_t score_stride, hipStream_t s, hipError_t *err)
+{
+    int ch = 0;
+    if (a.dtype != RLR_F32 || n_queries < 2 || n_queries > 8 || !fixed_shape(a, &ch) || ch > 4 || q_pitch < a.dim ||
+        score_stride < a.n_rows)
+        return false;
+    *err = hipSuccess;
+    if (a.n_rows == 0)
+        return true;
+    const bool dense = n_allowed * 4 >= a.n_rows;
+    const uint32_t unit = dense ? 8u : 16u;
+    const uint32_t q_inst = n_queries <= 2 ? 2u : n_queries <= 4 ? 4u : 8u;
+    const uint32_t resident = ch == 4 && q_inst == 8 ? 2u : (ch == 4 && q_inst == 4) || (ch == 3 && q_inst == 8) ? 3u : 4u;
+    const uint32_t wgs = dense ? 1u : resident;
+    const uint32_t n_groups = (a.n_rows + unit - 1) / unit;
+    const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((n_groups + 3) / 4, static_cast<uint32_t>(a.n_cu) * wgs));
+    const float4 *rows = static_cast<const float4 *>(a.rows);
+#define RLR_MASKED_MULTI(CHV, QV)                                                                                        \
+    hipLaunchKernelGGL((scan_masked_multi_kernel<CHV, QV>), dim3(blocks), dim3(256), 0, s, rows, a.query, q_pitch,       \
+                       n_queries, mask, a.scores, score_stride, a.n_rows, unit)
+#define RLR_MASKED_MULTI_Q(CHV)                                  \
+    do {                                                         \
+        if (n_queries <= 2) RLR_MASKED_MULTI(CHV, 2);            \
+        else if (n_queries <= 4) RLR_MASKED_MULTI(CHV, 4);       \
+        else RLR_MASKED_MULTI(CHV, 8);                           \
+    } while (0)
+    switch (ch) {
+    case 1: RLR_MASKED_MULTI_Q(1); break;
+    case 2: RLR_MASKED_MULTI_Q(2); break;
+    case 3: RLR_MASKED_MULTI_Q(3); break;
+    default: RLR_MASKED_MULTI_Q(4); break;
+    }
+#undef RLR_MASKED_MULTI_Q
+#undef RLR_MASKED_MULTI
     *err = hipGetLastError();
     return true;
 }

@@ -354,7 +354,11 @@ class RagEngine:
 
     # -- additive batched entry point (oracle: loop search_with_diversity over the batch) -------
     def search_with_diversity_batch(self, query_embeddings, top_k: int, diversity_factor: float,
-                                    weights: Optional[QueryWeights] = None) -> List[List[SearchResult]]:
+                                    weights: Optional[QueryWeights] = None,
+                                    documents: Optional[Sequence[str]] = None) -> List[List[SearchResult]]:
+        """`documents`: as for search_with_diversity -- every query searches only inside these documents (None: the
+        whole corpus; an empty list or unknown names: no rows, an empty list per query); chunks of up to 8 queries
+        share one masked pass over the documents' rows."""
         q = _f32(query_embeddings)
         if q.ndim == 1:
             q = q.reshape(1, -1)
@@ -363,9 +367,17 @@ class RagEngine:
         hits = (N.SearchHitC * (cap * max(nq, 1)))()
         n_out = np.zeros(max(nq, 1), dtype=np.uint32)
         wc = weights.to_c() if weights is not None else None
-        N.check(N.lib().rlr_engine_search_with_diversity_batch(
-            self.index.handle, q.ctypes.data_as(N.f32p), dq, nq, top_k, float(diversity_factor),
-            C.byref(wc) if wc is not None else None, hits, cap, n_out.ctypes.data_as(N.u32p)))
+        if documents is not None:
+            if not document_ranges(self._chunks, documents):
+                return [[] for _ in range(nq)]
+            f = self._filter_for(documents)
+            N.check(N.lib().rlr_engine_search_with_diversity_batch_filtered(
+                self.index.handle, f.handle, q.ctypes.data_as(N.f32p), dq, nq, top_k, float(diversity_factor),
+                C.byref(wc) if wc is not None else None, hits, cap, n_out.ctypes.data_as(N.u32p)))
+        else:
+            N.check(N.lib().rlr_engine_search_with_diversity_batch(
+                self.index.handle, q.ctypes.data_as(N.f32p), dq, nq, top_k, float(diversity_factor),
+                C.byref(wc) if wc is not None else None, hits, cap, n_out.ctypes.data_as(N.u32p)))
         out = []
         for i in range(nq):
             view = (N.SearchHitC * cap).from_buffer(hits, i * cap * C.sizeof(N.SearchHitC))
@@ -406,10 +418,11 @@ class RagEngine:
         return out
 
     def search_documents_batch(self, requests: Sequence[SearchRequest]) -> List[List[SearchResult]]:
-        """search_documents for every request, grouped by (top_k, diversity, weights) after its caps and clamps and run
-        through search_text_batch; a request without text is scored with no query terms."""
+        """search_documents for every request, grouped by (top_k, diversity, weights, documents) after its caps and
+        clamps.  Unscoped groups run through search_text_batch (a request without text is scored with no query terms);
+        scoped groups without query text through search_with_diversity_batch(documents=...); scoped requests WITH query
+        text one by one through search_documents (there is no batched BM25 inside a filter)."""
         groups: Dict[tuple, List[int]] = {}
-        keyed = []
         for i, r in enumerate(requests):
             if r.lexical:
                 raise ValueError("search_documents_batch: requests carry caller-computed lexical pairs; "
@@ -419,16 +432,25 @@ class RagEngine:
             div = min(max(div, 0.0), 1.0)
             w = r.weights
             wkey = None if w is None else (w.embedding, w.lexical, w.reranker, w.initial)
-            key = (top_k, div, wkey)
-            keyed.append(key)
-            groups.setdefault(key, []).append(i)
+            scope = None if r.documents is None else frozenset(r.documents)  # ([] is a scope: no rows)
+            groups.setdefault((top_k, div, wkey, scope), []).append(i)
         out: List[List[SearchResult]] = [[] for _ in requests]
-        for (top_k, div, _), members in groups.items():
+        for (top_k, div, _, scope), members in groups.items():
             w = requests[members[0]].weights
-            emb = np.stack([_f32(requests[i].query_embedding).ravel() for i in members])
-            texts = [requests[i].query or "" for i in members]
-            for i, res in zip(members, self.search_text_batch(emb, texts, top_k, div, w)):
-                out[i] = res
+            if scope is None:
+                emb = np.stack([_f32(requests[i].query_embedding).ravel() for i in members])
+                texts = [requests[i].query or "" for i in members]
+                for i, res in zip(members, self.search_text_batch(emb, texts, top_k, div, w)):
+                    out[i] = res
+                continue
+            plain = [i for i in members if not requests[i].query]
+            if plain:
+                emb = np.stack([_f32(requests[i].query_embedding).ravel() for i in plain])
+                for i, res in zip(plain, self.search_with_diversity_batch(emb, top_k, div, w, documents=sorted(scope))):
+                    out[i] = res
+            for i in members:
+                if requests[i].query:
+                    out[i] = self.search_documents(requests[i])
         return out
 
     # -- RagEngine::get_embedding_candidates (rag_engine.rs:415-461) -----------------------
