@@ -7,6 +7,7 @@
 // point fails with RLR_E_NO_DEVICE.
 #include "../../include/rlr_gpu.h"
 #include "common.h"
+#include "device_buffer.h"
 #include "kernels.h"
 #include "lds_select.h"
 #include "sort_emit.h"
@@ -99,47 +100,36 @@ struct Ctx {
     hipStream_t stream = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     // device
-    float *d_query = nullptr;      // q_cap x q_pitch floats
-    uint32_t q_cap = 0;
-    float *d_scores = nullptr;     // score_cap floats
-    uint64_t score_cap = 0;
-    uint32_t *d_hist = nullptr;    // 2 * kHistBins
-    SelectState *d_state = nullptr; // q_cap states
-    uint32_t *d_cand = nullptr;    // cand_cap
-    uint64_t *d_packed = nullptr;  // cand_cap (power of two)
-    uint32_t cand_cap = 0;
-    uint64_t *d_out = nullptr;     // out_cap packed results
-    uint64_t out_cap = 0;
-    uint32_t *d_list = nullptr;    // row lists (score_rows / fetch / mmr)
-    float *d_vals = nullptr;       // float outputs for lists / mmr
-    uint32_t list_cap = 0;
-    float *d_pool = nullptr;       // mmr pool P x dim, then gram P x P
-    uint64_t pool_cap = 0;         // floats
+    // (buffers named together grow together: reserve_group, device_buffer.h)
+    DevBuf<float> d_query;         // q x q_pitch floats, with d_state
+    DevBuf<float> d_scores;
+    DevBuf<uint32_t> d_hist;       // 2 * kHistBins
+    DevBuf<SelectState> d_state;   // q states
+    DevBuf<uint32_t> d_cand;       // with d_packed
+    DevBuf<uint64_t> d_packed;     // (a power of two)
+    DevBuf<uint64_t> d_out;        // packed results
+    DevBuf<uint32_t> d_list;       // row lists (score_rows / fetch / mmr), with d_vals
+    DevBuf<float> d_vals;          // float outputs for lists / mmr
+    DevBuf<float> d_pool;          // mmr pool P x dim, then gram P x P
     // batched (MFMA) path workspace
-    void *d_qfrag = nullptr;        // binary16 fragment-major queries
-    uint64_t qfrag_cap = 0;         // bytes
-    float *d_tau = nullptr;         // per-query nomination threshold
-    SelectState *d_bstate = nullptr;
-    uint32_t *d_bhist = nullptr;    // q x 2 x kHistBins
-    uint32_t *d_bstatus = nullptr;
-    uint32_t *d_gsync = nullptr;   // 256 words: sibling-group arrival counters of the persistent batched GEMM (gemm.hip)
-    void *h_batch = nullptr;       // pinned: SelectState[bq_cap] | status[bq_cap] (pageable staging makes the async copies synchronous)
-    uint32_t bq_cap = 0;            // queries the four arrays above are sized for
+    DevBuf<uint8_t> d_qfrag;        // binary16 fragment-major queries
+    DevBuf<float> d_tau;            // per-query nomination threshold; with d_bstate, d_bhist, d_bstatus and h_batch
+    DevBuf<SelectState> d_bstate;
+    DevBuf<uint32_t> d_bhist;       // q x 2 x kHistBins
+    DevBuf<uint32_t> d_bstatus;
+    DevBuf<uint32_t> d_gsync;      // 256 words: sibling-group arrival counters of the persistent batched GEMM (gemm.hip)
+    PinBuf h_batch;                // SelectState[q] | status[q] (pageable staging makes the async copies synchronous)
     bool no_f16 = false;            // this call's queries or the rows leave binary16 range: no binary16 nomination
-    uint64_t *d_bcand = nullptr;    // q x fin_cap packed candidates
-    uint64_t bcand_cap = 0;         // entries
-    float *d_sample = nullptr;      // q x S nominated scores of the sample rows
-    uint64_t sample_cap = 0;        // floats
+    DevBuf<uint64_t> d_bcand;       // q x fin_cap packed candidates
+    DevBuf<float> d_sample;         // q x S nominated scores of the sample rows
     hipEvent_t bev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    // pinned host
-    void *h_pin = nullptr;
-    size_t h_pin_bytes = 0;
+    PinBuf h_pin;                   // staging of a call's queries and results
     std::vector<float> q_norm; // ||q||_2 of the staged queries (band of the 8-bit nomination scan)
     WaitEma wait_ema;          // how long the last waits for a call's completion words took (wait_flags)
     const float *h_q_kq = nullptr; // set for the duration of a call whose scans take their query in the kernel arguments
                                    // (ScanArgs::query_host): the staged queries in pinned host memory, q_pitch floats each
     bool hist_dirty = false; // a pipeline was enqueued and did not complete: d_hist may hold counts
-    uint32_t *h_assert = nullptr; // RLR_POISON_ALLOC=1 only: pinned word the zero-histogram assertion kernel counts into
+    PinBuf h_assert;         // RLR_POISON_ALLOC=1 only: pinned word the zero-histogram assertion kernel counts into
     // rlr_search_topk_device_begin / _end
     hipStream_t pending_stream = nullptr;
     uint32_t pending_q = 0, pending_k = 0;
@@ -178,7 +168,7 @@ struct rlr_index {
     uint32_t q_pitch = 0;   // floats per staged query (row pitch in elements)
     uint64_t n_rows = 0;
     uint64_t cap_rows = 0;
-    void *d_rows = nullptr;
+    DevBuf<char> d_rows;    // cap_rows x row_bytes
     int n_cu = 256;
     int scan_variant = 0;
     int fused_tail = -1;         // select -> re-score -> sort behind the scan in two launches (tail.hip): RLR_TAIL=1 always, 0 never
@@ -206,14 +196,12 @@ struct rlr_index {
     bool image_scan = false;    // single queries nominate over the image too (half the bytes of f32 rows)
     // optional 8-bit nomination copy for single queries (q8.hip): a quarter of the f32 bytes
     bool q8_enabled = false;
-    void *d_q8 = nullptr;        // cap_rows x dim bytes
-    float *d_q8_scale = nullptr; // cap_rows
-    uint32_t *d_q8_stats = nullptr; // [0] max row error norm (float bits), [1] max scale (float bits), [2] an Inf row exists
-    uint64_t q8_cap_rows = 0;
+    DevBuf<uint8_t> d_q8;        // cap_rows x dim bytes, with d_q8_scale
+    DevBuf<float> d_q8_scale;    // cap_rows
+    DevBuf<uint32_t> d_q8_stats; // [0] max row error norm (float bits), [1] max scale (float bits), [2] an Inf row exists
     float q8_delta = 0.0f, q8_scale_max = 0.0f;
     bool q8_has_inf = false;
-    void *d_image = nullptr;
-    size_t image_cap = 0;       // bytes
+    DevBuf<uint8_t> d_image;
     std::mutex mu;
     std::condition_variable ctx_cv; // callers beyond ctx_cap wait here for a context to come back
     std::vector<Ctx *> free_ctx;
@@ -241,8 +229,8 @@ struct rlr_filter {
     rlr_index *ix = nullptr;
     uint64_t index_rows = 0, n_allowed = 0, mutations = 0;
     int32_t path = 0; // 0: list path, 1: masked scan
-    uint64_t *d_mask = nullptr;
-    uint32_t *d_list = nullptr;
+    DevBuf<uint64_t> d_mask;
+    DevBuf<uint32_t> d_list;
     std::vector<uint64_t> h_mask;
 };
 
@@ -287,35 +275,30 @@ int32_t use_device(const rlr_index *ix)
     return RLR_OK;
 }
 
-template <typename T>
-int32_t grow(T **p, uint64_t *cap, uint64_t want, bool keep = false)
+int32_t pin_reserve(Ctx *c, size_t bytes)
 {
-    if (*cap >= want && *p)
-        return RLR_OK;
-    T *n = nullptr;
-    RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&n), want * sizeof(T)));
-    if (keep && *p && *cap) {
-        RLR_HIP(hipMemcpy(n, *p, *cap * sizeof(T), hipMemcpyDeviceToDevice));
-        RLR_HIP(hipStreamSynchronize(nullptr)); // a device-to-device copy may return before it has run
-    }
-    if (*p)
-        (void)hipFree(*p);
-    *p = n;
-    *cap = want;
+    RLR_HIP(c->h_pin.reserve(std::max<size_t>(bytes, 1 << 16)));
     return RLR_OK;
 }
 
-int32_t pin_reserve(Ctx *c, size_t bytes)
+// c->d_query / c->d_state for nq queries
+int32_t reserve_queries(const rlr_index *ix, Ctx *c, uint32_t nq)
 {
-    if (c->h_pin_bytes >= bytes)
+    if (c->d_state.capacity() >= nq)
         return RLR_OK;
-    if (c->h_pin)
-        (void)hipHostFree(c->h_pin);
-    c->h_pin = nullptr;
-    c->h_pin_bytes = 0;
-    size_t want = std::max<size_t>(bytes, 1 << 16);
-    RLR_HIP(hipHostMalloc(&c->h_pin, want, hipHostMallocDefault));
-    c->h_pin_bytes = want;
+    RLR_HIP(reserve_group(Want{c->d_query, static_cast<size_t>(nq) * ix->q_pitch}, Want{c->d_state, nq}));
+    // the fused tail's counters (n_work, done, flags) are zero between two queries; on the context's stream, like the histograms
+    const hipError_t e = hipMemsetAsync(c->d_state.get(), 0, static_cast<size_t>(nq) * sizeof(SelectState), c->stream);
+    if (e != hipSuccess)
+        c->d_state.reset(); // (states that were never cleared: the next call rebuilds the group)
+    RLR_HIP(e);
+    return RLR_OK;
+}
+
+// c->d_cand / c->d_packed for cap candidates
+int32_t reserve_cand(Ctx *c, uint32_t cap)
+{
+    RLR_HIP(reserve_group(Want{c->d_cand, cap}, Want{c->d_packed, cap}));
     return RLR_OK;
 }
 
@@ -326,30 +309,9 @@ void ctx_free(Ctx *c)
     for (auto &e : c->ev)
         if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    (void)hipFree(c->d_query);
-    (void)hipFree(c->d_scores);
-    (void)hipFree(c->d_hist);
-    (void)hipFree(c->d_state);
-    (void)hipFree(c->d_cand);
-    (void)hipFree(c->d_packed);
-    (void)hipFree(c->d_out);
-    (void)hipFree(c->d_list);
-    (void)hipFree(c->d_vals);
-    (void)hipFree(c->d_pool);
-    (void)hipFree(c->d_qfrag);
-    (void)hipFree(c->d_tau);
-    (void)hipFree(c->d_bstate);
-    (void)hipFree(c->d_bhist);
-    (void)hipFree(c->d_bstatus);
-    (void)hipFree(c->d_gsync);
-    (void)hipFree(c->d_bcand);
-    (void)hipFree(c->d_sample);
     for (auto &e : c->bev)
         if (e) (void)hipEventDestroy(e);
-    if (c->h_pin) (void)hipHostFree(c->h_pin);
-    if (c->h_batch) (void)hipHostFree(c->h_batch);
-    if (c->h_assert) (void)hipHostFree(c->h_assert);
-    delete c;
+    delete c; // (the buffers free themselves)
 }
 
 // A free context, a new one while fewer than ctx_cap exist, else wait until a call hands one back.  The reference serves
@@ -368,8 +330,8 @@ int32_t ctx_acquire(rlr_index *ix, Ctx **out)
                 if (c->hist_dirty) { // a previous call failed half way: restore the zero-histogram invariant
                     (void)hipStreamSynchronize(c->stream);
                     // (on the context's own stream: the null stream does not order against a non-blocking one)
-                    if (hipMemsetAsync(c->d_hist, 0, 2 * kHistBins * sizeof(uint32_t), c->stream) == hipSuccess &&
-                        (!c->d_state || hipMemsetAsync(c->d_state, 0, static_cast<size_t>(c->q_cap) * sizeof(SelectState), c->stream) ==
+                    if (hipMemsetAsync(c->d_hist.get(), 0, 2 * kHistBins * sizeof(uint32_t), c->stream) == hipSuccess &&
+                        (!c->d_state.get() || hipMemsetAsync(c->d_state.get(), 0, c->d_state.capacity() * sizeof(SelectState), c->stream) ==
                                             hipSuccess))
                         c->hist_dirty = false;
                 }
@@ -402,17 +364,17 @@ int32_t ctx_acquire(rlr_index *ix, Ctx **out)
     for (int i = 0; i < 5 && e == hipSuccess; ++i)
         e = hipEventCreate(&c->bev[i]);
     if (e == hipSuccess)
-        e = rlr::dev_malloc(reinterpret_cast<void **>(&c->d_hist), 2 * kHistBins * sizeof(uint32_t));
+        e = c->d_hist.reserve(2 * kHistBins);
     // The zero-histogram invariant is established ON THE CONTEXT'S STREAM: a null-stream hipMemset of device
     // memory may return before it has run, and a non-blocking stream is not ordered against the null stream --
     // the first scan's histogram atomics could then land before the fill and be wiped (a rare wrong threshold
     // on the first search of a fresh context, caught by the multi-shard fuzz with five contexts starting at once).
     if (e == hipSuccess)
-        e = hipMemsetAsync(c->d_hist, 0, 2 * kHistBins * sizeof(uint32_t), c->stream);
+        e = hipMemsetAsync(c->d_hist.get(), 0, 2 * kHistBins * sizeof(uint32_t), c->stream);
     if (e == hipSuccess && rlr::poison_mode()) {
-        e = hipHostMalloc(reinterpret_cast<void **>(&c->h_assert), 64, hipHostMallocDefault);
+        e = c->h_assert.reserve(64);
         if (e == hipSuccess)
-            *c->h_assert = 0;
+            *static_cast<uint32_t *>(c->h_assert.get()) = 0;
     }
     if (e == hipSuccess)
         e = hipStreamSynchronize(c->stream);
@@ -459,27 +421,23 @@ int32_t ensure_rows(rlr_index *ix, uint64_t want_rows)
         return fail(RLR_E_INVALID, "an index shard holds at most 2^32-16 rows");
     uint64_t cap = std::max<uint64_t>(want_rows, ix->cap_rows + ix->cap_rows / 2);
     cap = std::max<uint64_t>(cap, 1024);
-    void *n = nullptr;
-    hipError_t e = rlr::dev_malloc(&n, cap * row_bytes(ix));
+    DevBuf<char> n;
+    hipError_t e = n.reserve(cap * row_bytes(ix));
     if (e != hipSuccess && cap > want_rows) {
         cap = want_rows;
-        e = rlr::dev_malloc(&n, cap * row_bytes(ix));
+        e = n.reserve(cap * row_bytes(ix));
     }
     if (e != hipSuccess)
         return fail(RLR_E_OOM, "allocation of %llu rows x %zu B failed: %s",
                     static_cast<unsigned long long>(cap), row_bytes(ix), hipGetErrorString(e));
-    if (ix->d_rows && ix->n_rows) {
-        hipError_t ce = hipMemcpy(n, ix->d_rows, ix->n_rows * row_bytes(ix), hipMemcpyDeviceToDevice);
+    if (ix->d_rows.get() && ix->n_rows) {
+        hipError_t ce = hipMemcpy(n.get(), ix->d_rows.get(), ix->n_rows * row_bytes(ix), hipMemcpyDeviceToDevice);
         if (ce == hipSuccess)
             ce = hipStreamSynchronize(nullptr); // a device-to-device copy may return before it has run
-        if (ce != hipSuccess) {
-            (void)hipFree(n);
+        if (ce != hipSuccess)
             return fail(RLR_E_HIP, "moving the rows into the larger allocation failed: %s", hipGetErrorString(ce));
-        }
     }
-    if (ix->d_rows)
-        (void)hipFree(ix->d_rows);
-    ix->d_rows = n;
+    ix->d_rows = std::move(n); // (frees the old rows)
     ix->cap_rows = cap;
     return RLR_OK;
 }
@@ -490,26 +448,18 @@ int32_t sync_q8(rlr_index *ix, uint64_t first_row)
 {
     if (!ix->q8_enabled)
         return RLR_OK;
-    const uint64_t want = std::max<uint64_t>(ix->cap_rows, ix->n_rows);
-    if (ix->q8_cap_rows < want || !ix->d_q8) {
-        if (ix->d_q8) (void)hipFree(ix->d_q8);
-        if (ix->d_q8_scale) (void)hipFree(ix->d_q8_scale);
-        ix->d_q8 = nullptr;
-        ix->d_q8_scale = nullptr;
-        ix->q8_cap_rows = 0;
-        RLR_HIP(rlr::dev_malloc(&ix->d_q8, std::max<uint64_t>(want, 1) * ix->dim));
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&ix->d_q8_scale), std::max<uint64_t>(want, 1) * sizeof(float)));
-        ix->q8_cap_rows = want;
+    const uint64_t want = std::max<uint64_t>(std::max<uint64_t>(ix->cap_rows, ix->n_rows), 1);
+    if (ix->d_q8_scale.capacity() < want) {
+        RLR_HIP(reserve_group(Want{ix->d_q8, want * ix->dim}, Want{ix->d_q8_scale, want}));
         first_row = 0;
     }
-    if (!ix->d_q8_stats)
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&ix->d_q8_stats), 4 * sizeof(uint32_t)));
+    RLR_HIP(ix->d_q8_stats.reserve(4));
     if (first_row == 0)
-        RLR_HIP(hipMemset(ix->d_q8_stats, 0, 4 * sizeof(uint32_t)));
-    RLR_HIP(launch_q8_build(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, static_cast<uint32_t>(first_row),
-                            static_cast<uint32_t>(ix->n_rows), ix->d_q8, ix->d_q8_scale, ix->d_q8_stats, nullptr));
+        RLR_HIP(hipMemset(ix->d_q8_stats.get(), 0, 4 * sizeof(uint32_t)));
+    RLR_HIP(launch_q8_build(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, static_cast<uint32_t>(first_row),
+                            static_cast<uint32_t>(ix->n_rows), ix->d_q8.get(), ix->d_q8_scale.get(), ix->d_q8_stats.get(), nullptr));
     uint32_t h[4] = {0, 0, 0, 0};
-    RLR_HIP(hipMemcpy(h, ix->d_q8_stats, sizeof(h), hipMemcpyDeviceToHost));
+    RLR_HIP(hipMemcpy(h, ix->d_q8_stats.get(), sizeof(h), hipMemcpyDeviceToHost));
     std::memcpy(&ix->q8_delta, &h[0], 4);
     std::memcpy(&ix->q8_scale_max, &h[1], 4);
     ix->q8_has_inf = h[2] != 0;
@@ -523,19 +473,14 @@ int32_t sync_image(rlr_index *ix, uint64_t first_row)
     if (!ix->image_enabled)
         return RLR_OK;
     const size_t need = image_bytes(ix->dim, std::max<uint64_t>(ix->cap_rows, ix->n_rows));
-    if (ix->image_cap < need) {
-        if (ix->d_image)
-            (void)hipFree(ix->d_image);
-        ix->d_image = nullptr;
-        ix->image_cap = 0;
-        RLR_HIP(rlr::dev_malloc(&ix->d_image, std::max<size_t>(need, 256)));
-        ix->image_cap = std::max<size_t>(need, 256);
+    if (ix->d_image.capacity() < need) {
+        RLR_HIP(ix->d_image.reserve(std::max<size_t>(need, 256)));
         first_row = 0; // fresh buffer: every tile has to be written
     }
     const uint32_t t0 = static_cast<uint32_t>(first_row / 256);
     const uint32_t t1 = static_cast<uint32_t>((ix->n_rows + 255) / 256);
-    RLR_HIP(launch_build_image(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, static_cast<uint32_t>(ix->n_rows), t0, t1,
-                               ix->d_image, nullptr));
+    RLR_HIP(launch_build_image(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, static_cast<uint32_t>(ix->n_rows), t0, t1,
+                               ix->d_image.get(), nullptr));
     RLR_HIP(hipStreamSynchronize(nullptr));
     return RLR_OK;
 }
@@ -560,14 +505,13 @@ int32_t ingest(rlr_index *ix, const float *rows, uint64_t n, uint64_t first, int
     if (n == 0)
         return RLR_OK;
     const uint64_t chunk_rows = std::max<uint64_t>(1, (64ull << 20) / (static_cast<uint64_t>(ix->dim) * 4));
-    float *d_stage = nullptr, *d_norm = nullptr;
+    DevBuf<float> stage, norm;
     const uint64_t cr = std::min(chunk_rows, n);
-    RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&d_stage), cr * ix->dim * sizeof(float)));
-    hipError_t e = rlr::dev_malloc(reinterpret_cast<void **>(&d_norm), cr * sizeof(float));
-    if (e != hipSuccess) {
-        (void)hipFree(d_stage);
+    RLR_HIP(stage.reserve(cr * ix->dim));
+    hipError_t e = norm.reserve(cr);
+    if (e != hipSuccess)
         return fail(RLR_E_OOM, "staging allocation failed");
-    }
+    float *const d_stage = stage.get(), *const d_norm = norm.get();
     int32_t st = RLR_OK;
     std::vector<float> h_norm;
     for (uint64_t r0 = 0; r0 < n && st == RLR_OK; r0 += cr) {
@@ -575,7 +519,7 @@ int32_t ingest(rlr_index *ix, const float *rows, uint64_t n, uint64_t first, int
         e = hipMemcpy(d_stage, rows + r0 * ix->dim, m * ix->dim * sizeof(float), hipMemcpyHostToDevice);
         if (e == hipSuccess)
             e = launch_normalize_store(d_stage, static_cast<uint32_t>(m), ix->dim, normalize,
-                                       static_cast<char *>(ix->d_rows) + (first + r0) * row_bytes(ix), ix->pitch16,
+                                       static_cast<char *>(ix->d_rows.get()) + (first + r0) * row_bytes(ix), ix->pitch16,
                                        ix->dtype, d_norm, nullptr);
         if (e == hipSuccess)
             e = hipStreamSynchronize(nullptr);
@@ -594,8 +538,6 @@ int32_t ingest(rlr_index *ix, const float *rows, uint64_t n, uint64_t first, int
         if (e != hipSuccess)
             st = fail(RLR_E_HIP, "row ingest failed: %s", hipGetErrorString(e));
     }
-    (void)hipFree(d_stage);
-    (void)hipFree(d_norm);
     return st;
 }
 
@@ -802,10 +744,10 @@ hipError_t stage_queries_for_scans(const rlr_index *ix, Ctx *c, const float *h_q
 hipError_t upload_queries(Ctx *c, const float *h_q, size_t q_bytes, hipStream_t s)
 {
     if (q_bytes > (64u << 10) || (q_bytes & 15) || (reinterpret_cast<uintptr_t>(h_q) & 15))
-        return hipMemcpyAsync(c->d_query, h_q, q_bytes, hipMemcpyHostToDevice, s);
+        return hipMemcpyAsync(c->d_query.get(), h_q, q_bytes, hipMemcpyHostToDevice, s);
     const uint32_t n16 = static_cast<uint32_t>(q_bytes / 16);
     hipLaunchKernelGGL(rlr::stage_query_kernel, dim3(std::min<uint32_t>((n16 + 255) / 256, 8)), dim3(256), 0, s,
-                       reinterpret_cast<const float4 *>(h_q), reinterpret_cast<float4 *>(c->d_query), n16);
+                       reinterpret_cast<const float4 *>(h_q), reinterpret_cast<float4 *>(c->d_query.get()), n16);
     return hipGetLastError();
 }
 
@@ -863,30 +805,10 @@ void plan_bands(const rlr_index *ix, const float *queries, uint32_t nq, SearchPl
 int32_t ctx_prepare(rlr_index *ix, Ctx *c, uint32_t nq, const SearchPlan &p)
 {
     c->no_f16 = !p.f16_ok;
-    if (c->q_cap < nq || !c->d_query) {
-        if (c->d_query) (void)hipFree(c->d_query);
-        if (c->d_state) (void)hipFree(c->d_state);
-        c->d_query = nullptr;
-        c->d_state = nullptr;
-        c->q_cap = 0;
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_query), static_cast<size_t>(nq) * ix->q_pitch * sizeof(float)));
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_state), static_cast<size_t>(nq) * sizeof(SelectState)));
-        // the fused tail's counters (n_work, done, flags) are zero between two queries; on the context's stream, like the histograms
-        RLR_HIP(hipMemsetAsync(c->d_state, 0, static_cast<size_t>(nq) * sizeof(SelectState), c->stream));
-        c->q_cap = nq;
-    }
-    RLR_TRY(grow(&c->d_scores, &c->score_cap, std::max<uint64_t>(ix->n_rows, 4)));
-    if (c->cand_cap < p.cap) {
-        if (c->d_cand) (void)hipFree(c->d_cand);
-        if (c->d_packed) (void)hipFree(c->d_packed);
-        c->d_cand = nullptr;
-        c->d_packed = nullptr;
-        c->cand_cap = 0;
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_cand), static_cast<size_t>(p.cap) * sizeof(uint32_t)));
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_packed), static_cast<size_t>(p.cap) * sizeof(uint64_t)));
-        c->cand_cap = p.cap;
-    }
-    RLR_TRY(grow(&c->d_out, &c->out_cap, static_cast<uint64_t>(nq) * p.k + nq)); // results + per-query counts
+    RLR_TRY(reserve_queries(ix, c, nq));
+    RLR_HIP(c->d_scores.reserve(std::max<uint64_t>(ix->n_rows, 4)));
+    RLR_TRY(reserve_cand(c, p.cap));
+    RLR_HIP(c->d_out.reserve(static_cast<uint64_t>(nq) * p.k + nq)); // results + per-query counts
     return RLR_OK;
 }
 
@@ -1468,7 +1390,7 @@ namespace {
 // f32 rows with an up-to-date image and the opt-in set: the nomination scan reads the binary16 image
 bool scan_over_image(const rlr_index *ix, const Ctx *c)
 {
-    return ix->image_scan && ix->image_enabled && ix->d_image && ix->dtype == RLR_F32 && !(c && c->no_f16);
+    return ix->image_scan && ix->image_enabled && ix->d_image.get() && ix->dtype == RLR_F32 && !(c && c->no_f16);
 }
 
 // ||q||_2 per staged query, rounded up (only the 8-bit nomination band needs it)
@@ -1486,7 +1408,7 @@ void stage_query_norms(const rlr_index *ix, Ctx *c, const float *queries, uint32
 // f32 rows with an up-to-date 8-bit copy: the nomination scan reads one byte per element
 bool scan_over_q8(const rlr_index *ix)
 {
-    return ix->q8_enabled && ix->d_q8 && !ix->q8_has_inf;
+    return ix->q8_enabled && ix->d_q8.get() && !ix->q8_has_inf;
 }
 
 // bytes per element the single-query nomination scan streams (profile accounting)
@@ -1499,7 +1421,7 @@ uint64_t scan_bytes_per_element(const rlr_index *ix, const Ctx *c)
 ScanArgs scan_args(const rlr_index *ix, const float *query, float *scores, uint32_t *hist)
 {
     ScanArgs sa;
-    sa.rows = ix->d_rows;
+    sa.rows = ix->d_rows.get();
     sa.query = query;
     sa.scores = scores;
     sa.hist = hist;
@@ -1552,9 +1474,10 @@ void count_f16_fallbacks(rlr_index *ix, const SearchPlan &p, uint32_t nq, bool b
 // after a synchronisation: did the zero-histogram assertion of a poisoned run fire?
 int32_t check_hist_assert(Ctx *c)
 {
-    if (c->h_assert && *c->h_assert) {
-        const uint32_t n = *c->h_assert;
-        *c->h_assert = 0;
+    uint32_t *h = static_cast<uint32_t *>(c->h_assert.get());
+    if (h && *h) {
+        const uint32_t n = *h;
+        *h = 0;
         return fail(RLR_E_INTERNAL, "zero-histogram invariant violated: %u non-zero bins in front of a scan", n);
     }
     return RLR_OK;
@@ -1688,7 +1611,7 @@ struct StreamDrain {
 
 // ---- workspace layouts ---------------------------------------------------------------------------------------------
 // A cursor over a base pointer that hands out regions in declaration order.  Each layout below is ONE list of regions, a
-// member per region initialised by its take(): built over null bases it only measures (what grow() / pin_reserve() are
+// member per region initialised by its take(): built over null bases it only measures (what reserve() / pin_reserve() are
 // asked for), built again over the buffers it yields every pointer -- the size and the pointers cannot disagree.  Region
 // order and sizes are what the kernels and copies have always used; what a layout relies on is said next to it.
 struct Carver {
@@ -1846,22 +1769,23 @@ hipError_t enqueue_query_scan(rlr_index *ix, Ctx *c, uint32_t qi, bool timed)
     hipStream_t s = c->stream;
     hipError_t e;
     const uint32_t n = static_cast<uint32_t>(ix->n_rows);
-    uint32_t *hist1 = c->d_hist;
-    const float *dq = c->d_query + static_cast<size_t>(qi) * ix->q_pitch;
+    uint32_t *hist1 = c->d_hist.get();
+    const float *dq = c->d_query.get() + static_cast<size_t>(qi) * ix->q_pitch;
 
     if (c->h_assert) {
-        hipLaunchKernelGGL(rlr::hist_assert_zero_kernel, dim3(4), dim3(256), 0, s, c->d_hist, 2u * kHistBins, c->h_assert);
+        hipLaunchKernelGGL(rlr::hist_assert_zero_kernel, dim3(4), dim3(256), 0, s, c->d_hist.get(), 2u * kHistBins,
+                           static_cast<uint32_t *>(c->h_assert.get()));
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (timed && (e = hipEventRecord(c->ev[0], s)) != hipSuccess) return e;
-    ScanArgs sa = scan_args(ix, dq, c->d_scores, hist1);
+    ScanArgs sa = scan_args(ix, dq, c->d_scores.get(), hist1);
     sa.query_host = c->h_q_kq ? c->h_q_kq + static_cast<size_t>(qi) * ix->q_pitch : nullptr;
     const bool q8 = scan_over_q8(ix);
     const bool img = !q8 && scan_over_image(ix, c);
     if (q8)
-        e = launch_q8_scan(ix->d_q8, ix->d_q8_scale, n, ix->dim, dq, c->d_scores, hist1, ix->n_cu, s);
+        e = launch_q8_scan(ix->d_q8.get(), ix->d_q8_scale.get(), n, ix->dim, dq, c->d_scores.get(), hist1, ix->n_cu, s);
     else if (img)
-        e = launch_scan_image(ix->d_image, n, ix->dim, dq, c->d_scores, hist1, ix->n_cu, s);
+        e = launch_scan_image(ix->d_image.get(), n, ix->dim, dq, c->d_scores.get(), hist1, ix->n_cu, s);
     else
         e = launch_scan(sa, s);
     if (e != hipSuccess) return e;
@@ -1880,9 +1804,9 @@ hipError_t enqueue_query_rest(rlr_index *ix, Ctx *c, uint32_t qi, const SearchPl
     hipStream_t s = c->stream;
     hipError_t e;
     const uint32_t n = static_cast<uint32_t>(ix->n_rows);
-    uint32_t *hist1 = c->d_hist, *hist2 = c->d_hist + kHistBins;
-    SelectState *st = c->d_state + qi;
-    const float *dq = c->d_query + static_cast<size_t>(qi) * ix->q_pitch;
+    uint32_t *hist1 = c->d_hist.get(), *hist2 = c->d_hist.get() + kHistBins;
+    SelectState *st = c->d_state.get() + qi;
+    const float *dq = c->d_query.get() + static_cast<size_t>(qi) * ix->q_pitch;
     // (master_scan: the scores in front of this tail came from the master rows whatever copies the index keeps -- the masked scan)
     const bool q8 = !master_scan && scan_over_q8(ix);
     const bool img = !master_scan && !q8 && scan_over_image(ix, c);
@@ -1896,19 +1820,19 @@ hipError_t enqueue_query_rest(rlr_index *ix, Ctx *c, uint32_t qi, const SearchPl
     if (fused && p.cap <= kLdsSortCap && tail_fits(ix->pitch16, ix->dim, ix->dtype)) {
         // two launches (tail.hip): bin search + collect + re-score (or the digit-2 histogram of a crowded bin), then sort + emit
         TailArgs ta;
-        ta.scores = c->d_scores;
+        ta.scores = c->d_scores.get();
         ta.n = n;
-        ta.hist = c->d_hist;
+        ta.hist = c->d_hist.get();
         ta.st = st;
         ta.k = p.k;
         ta.cap = p.cap;
         ta.two_eps = band;
-        ta.rows = ix->d_rows;
+        ta.rows = ix->d_rows.get();
         ta.pitch16 = ix->pitch16;
         ta.dim = ix->dim;
         ta.dtype = ix->dtype;
         ta.query = dq;
-        ta.packed = c->d_packed;
+        ta.packed = c->d_packed.get();
         ta.out = emit ? d_out_q : nullptr;
         ta.meta = d_meta_q;
         ta.unordered = p.unordered;
@@ -1923,22 +1847,22 @@ hipError_t enqueue_query_rest(rlr_index *ix, Ctx *c, uint32_t qi, const SearchPl
         if (timed && (e = hipEventRecord(c->ev[3], s)) != hipSuccess) return e;
         return hipSuccess;
     }
-    if ((e = launch_hist2_find1(c->d_scores, n, hist1, hist2, st, p.k, p.cap, ix->n_cu, s)) != hipSuccess) return e;
-    if ((e = launch_collect_find2(c->d_scores, n, hist2, st, band, c->d_cand, ix->n_cu, s)) != hipSuccess)
+    if ((e = launch_hist2_find1(c->d_scores.get(), n, hist1, hist2, st, p.k, p.cap, ix->n_cu, s)) != hipSuccess) return e;
+    if ((e = launch_collect_find2(c->d_scores.get(), n, hist2, st, band, c->d_cand.get(), ix->n_cu, s)) != hipSuccess)
         return e;
     if (timed && (e = hipEventRecord(c->ev[2], s)) != hipSuccess) return e;
     const uint32_t n_max = std::min<uint32_t>(p.cap, kLdsSortCap);
-    if (!launch_rescore_staged(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, dq, c->d_cand, st, c->d_packed, n_max,
-                               c->d_hist, s, &e)) {
+    if (!launch_rescore_staged(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, dq, c->d_cand.get(), st, c->d_packed.get(), n_max,
+                               c->d_hist.get(), s, &e)) {
         // rows too large for the staged layout: one lane per candidate, then clear the histograms
-        if ((e = launch_rescore(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, dq, c->d_cand, st, c->d_packed, n_max, s)) !=
+        if ((e = launch_rescore(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, dq, c->d_cand.get(), st, c->d_packed.get(), n_max, s)) !=
             hipSuccess)
             return e;
-        e = hipMemsetAsync(c->d_hist, 0, 2 * kHistBins * sizeof(uint32_t), s);
+        e = hipMemsetAsync(c->d_hist.get(), 0, 2 * kHistBins * sizeof(uint32_t), s);
     }
     if (e != hipSuccess) return e;
     if (emit) { // (a caller that orders the re-scored candidates itself -- pool_prepare_kernel<true> -- skips this launch)
-        hipLaunchKernelGGL(rlr::sort_emit_kernel, dim3(1), dim3(1024), 0, s, c->d_packed, st, d_out_q, p.k, d_meta_q, p.unordered);
+        hipLaunchKernelGGL(rlr::sort_emit_kernel, dim3(1), dim3(1024), 0, s, c->d_packed.get(), st, d_out_q, p.k, d_meta_q, p.unordered);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (timed && (e = hipEventRecord(c->ev[3], s)) != hipSuccess) return e;
@@ -1963,20 +1887,11 @@ int32_t big_query(rlr_index *ix, Ctx *c, uint32_t qi, const SearchPlan &p, uint3
     const uint32_t cap = next_pow2(std::max<uint32_t>(n_cand, p.k));
     SearchPlan big = p;
     big.cap = cap;
-    if (c->cand_cap < cap) {
-        if (c->d_cand) (void)hipFree(c->d_cand);
-        if (c->d_packed) (void)hipFree(c->d_packed);
-        c->d_cand = nullptr;
-        c->d_packed = nullptr;
-        c->cand_cap = 0;
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_cand), static_cast<size_t>(cap) * sizeof(uint32_t)));
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_packed), static_cast<size_t>(cap) * sizeof(uint64_t)));
-        c->cand_cap = cap;
-    }
-    SelectState *st = c->d_state + qi;
-    const float *dq = c->d_query + static_cast<size_t>(qi) * ix->q_pitch;
+    RLR_TRY(reserve_cand(c, cap));
+    SelectState *st = c->d_state.get() + qi;
+    const float *dq = c->d_query.get() + static_cast<size_t>(qi) * ix->q_pitch;
     if (rescan)
-        RLR_HIP(launch_scan(scan_args(ix, dq, c->d_scores, nullptr), s));
+        RLR_HIP(launch_scan(scan_args(ix, dq, c->d_scores.get(), nullptr), s));
     // key_lo is still valid in the state; reset the counter and the capacity
     SelectState h;
     RLR_HIP(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, s));
@@ -1984,22 +1899,22 @@ int32_t big_query(rlr_index *ix, Ctx *c, uint32_t qi, const SearchPlan &p, uint3
     h.n_cand = 0;
     h.cap = cap;
     RLR_HIP(hipMemcpyAsync(st, &h, sizeof(h), hipMemcpyHostToDevice, s));
-    RLR_HIP(launch_collect(c->d_scores, n, st, c->d_cand, ix->n_cu, s));
+    RLR_HIP(launch_collect(c->d_scores.get(), n, st, c->d_cand.get(), ix->n_cu, s));
     hipError_t e = hipSuccess;
     const bool second_level = p.k <= kLdsSortCap;
     // (the staged kernel writes the n_cand keys only; the global sort below needs the zero padding up to `cap` that the
     // one-lane kernel writes)
-    const bool staged = second_level && launch_rescore_staged(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, dq, c->d_cand, st,
-                                                              c->d_packed, cap, nullptr, s, &e);
+    const bool staged = second_level && launch_rescore_staged(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, dq, c->d_cand.get(), st,
+                                                              c->d_packed.get(), cap, nullptr, s, &e);
     RLR_HIP(e);
     if (!staged) // rows too large for the staged layout, or k beyond the one-workgroup finish
-        RLR_HIP(launch_rescore(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, dq, c->d_cand, st, c->d_packed, cap, s));
+        RLR_HIP(launch_rescore(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, dq, c->d_cand.get(), st, c->d_packed.get(), cap, s));
     if (second_level) {
         // second level: the exact keys are selected and sorted by one workgroup
-        hipLaunchKernelGGL(rlr::topk_global_kernel, dim3(1), dim3(1024), 0, s, c->d_packed, st, cap, d_out_q, p.k);
+        hipLaunchKernelGGL(rlr::topk_global_kernel, dim3(1), dim3(1024), 0, s, c->d_packed.get(), st, cap, d_out_q, p.k);
     } else {
-        RLR_HIP(launch_sort_desc(c->d_packed, cap, s));
-        hipLaunchKernelGGL(rlr::emit_kernel, dim3((p.k + 255) / 256), dim3(256), 0, s, c->d_packed, n_cand, d_out_q, p.k);
+        RLR_HIP(launch_sort_desc(c->d_packed.get(), cap, s));
+        hipLaunchKernelGGL(rlr::emit_kernel, dim3((p.k + 255) / 256), dim3(256), 0, s, c->d_packed.get(), n_cand, d_out_q, p.k);
     }
     RLR_HIP(hipGetLastError());
     RLR_HIP(hipStreamSynchronize(s));
@@ -2025,7 +1940,7 @@ bool batch_eligible(const rlr_index *ix, uint32_t nq, uint32_t k, bool f16_ok = 
     if (nq < 2 || ix->dim % 128 != 0 || ix->n_rows < 4096 || k * 8 > batch_finish_capacity())
         return false;
     // operands beyond binary16 range: only the f32 shared scan may nominate
-    if (!f16_ok && !(batch_multi_shape(ix, nq, coalesced) && !(ix->image_enabled && ix->d_image)))
+    if (!f16_ok && !(batch_multi_shape(ix, nq, coalesced) && !(ix->image_enabled && ix->d_image.get())))
         return false;
     if (ix->batch_min > 0)
         return nq >= ix->batch_min;
@@ -2037,7 +1952,7 @@ bool batch_eligible(const rlr_index *ix, uint32_t nq, uint32_t k, bool f16_ok = 
     // the single-query scan streams the 8-bit copy / the binary16 image when those are switched on
     const double scan_bytes = static_cast<double>(ix->n_rows) * ix->dim * static_cast<double>(scan_bytes_per_element(ix, nullptr));
     const double t_single = 60e-6 + scan_bytes / 6.2e12;
-    const bool image = ix->image_enabled && ix->d_image;
+    const bool image = ix->image_enabled && ix->d_image.get();
     // (over the image, batches of <= 128 queries take the resident-query kernel: ~5 TB/s of binary16)
     const double pass = image ? static_cast<double>(ix->n_rows) * ix->dim * 2.0 / (nq <= 128 ? 5.0e12 : 3.0e12)
                               : row_bytes / 3.7e12;
@@ -2054,36 +1969,20 @@ bool batch_eligible(const rlr_index *ix, uint32_t nq, uint32_t k, bool f16_ok = 
 int32_t batch_arm(Ctx *c, uint32_t nq, uint32_t fin_cap, uint64_t s_stride, uint32_t rank, uint64_t n)
 {
     hipStream_t s = c->stream;
-    if (c->bq_cap < nq) {
-        (void)hipFree(c->d_tau);
-        (void)hipFree(c->d_bstate);
-        (void)hipFree(c->d_bhist);
-        (void)hipFree(c->d_bstatus);
-        if (c->h_batch) (void)hipHostFree(c->h_batch);
-        c->h_batch = nullptr;
-        c->d_tau = nullptr;
-        c->d_bstate = nullptr;
-        c->d_bhist = nullptr;
-        c->d_bstatus = nullptr;
-        c->bq_cap = 0;
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_tau), static_cast<size_t>(nq) * sizeof(float)));
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_bstate), static_cast<size_t>(nq) * sizeof(SelectState)));
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_bhist), static_cast<size_t>(nq) * 2 * kHistBins * sizeof(uint32_t)));
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_bstatus), static_cast<size_t>(nq) * sizeof(uint32_t)));
-        RLR_HIP(hipHostMalloc(&c->h_batch, static_cast<size_t>(nq) * (sizeof(SelectState) + sizeof(uint32_t)), hipHostMallocDefault));
-        c->bq_cap = nq;
-    }
-    RLR_TRY(grow(&c->d_bcand, &c->bcand_cap, static_cast<uint64_t>(nq) * fin_cap));
-    RLR_TRY(grow(&c->d_sample, &c->sample_cap, static_cast<uint64_t>(nq) * s_stride));
-    SelectState *h_st = static_cast<SelectState *>(c->h_batch);
+    // (the status words of h_batch start behind d_bstate.capacity() states: all five or none)
+    RLR_HIP(reserve_group(Want{c->d_tau, nq}, Want{c->d_bstate, nq}, Want{c->d_bhist, static_cast<size_t>(nq) * 2 * kHistBins},
+                          Want{c->d_bstatus, nq}, Want{c->h_batch, static_cast<size_t>(nq) * (sizeof(SelectState) + sizeof(uint32_t))}));
+    RLR_HIP(c->d_bcand.reserve(static_cast<uint64_t>(nq) * fin_cap));
+    RLR_HIP(c->d_sample.reserve(static_cast<uint64_t>(nq) * s_stride));
+    SelectState *h_st = static_cast<SelectState *>(c->h_batch.get());
     for (uint32_t i = 0; i < nq; ++i) {
         std::memset(&h_st[i], 0, sizeof(SelectState));
         h_st[i].k = static_cast<uint32_t>(std::min<uint64_t>(rank, n));
         h_st[i].cap = fin_cap;
     }
-    RLR_HIP(hipMemcpyAsync(c->d_bstate, h_st, nq * sizeof(SelectState), hipMemcpyHostToDevice, s));
-    RLR_HIP(hipMemsetAsync(c->d_bhist, 0, static_cast<size_t>(nq) * 2 * kHistBins * sizeof(uint32_t), s));
-    RLR_HIP(hipMemsetAsync(c->d_bstatus, 0xFF, static_cast<size_t>(nq) * sizeof(uint32_t), s));
+    RLR_HIP(hipMemcpyAsync(c->d_bstate.get(), h_st, nq * sizeof(SelectState), hipMemcpyHostToDevice, s));
+    RLR_HIP(hipMemsetAsync(c->d_bhist.get(), 0, static_cast<size_t>(nq) * 2 * kHistBins * sizeof(uint32_t), s));
+    RLR_HIP(hipMemsetAsync(c->d_bstatus.get(), 0xFF, static_cast<size_t>(nq) * sizeof(uint32_t), s));
     return RLR_OK;
 }
 
@@ -2095,16 +1994,16 @@ int32_t batch_finish(rlr_index *ix, Ctx *c, const float *dq, uint32_t nq, uint32
                      std::vector<uint32_t> &h_status, uint64_t *h_res_out, std::vector<uint32_t> *n_cand_out = nullptr)
 {
     hipStream_t s = c->stream;
-    uint32_t *h_stat = reinterpret_cast<uint32_t *>(static_cast<SelectState *>(c->h_batch) + c->bq_cap);
-    RLR_HIP(launch_batch_finish(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, dq, ix->q_pitch, nq, c->d_bcand, batch_finish_capacity(),
-                                c->d_bstate, k, two_eps, d_out, c->d_bstatus, s));
+    uint32_t *h_stat = reinterpret_cast<uint32_t *>(static_cast<SelectState *>(c->h_batch.get()) + c->d_bstate.capacity());
+    RLR_HIP(launch_batch_finish(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, dq, ix->q_pitch, nq, c->d_bcand.get(), batch_finish_capacity(),
+                                c->d_bstate.get(), k, two_eps, d_out, c->d_bstatus.get(), s));
     if (ix->profiling) RLR_HIP(hipEventRecord(c->ev[3], s));
-    RLR_HIP(hipMemcpyAsync(h_stat, c->d_bstatus, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    RLR_HIP(hipMemcpyAsync(h_stat, c->d_bstatus.get(), nq * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     if (h_res_out) // the batch's results ride on the same synchronisation (queries handed back are fetched again by the caller)
         RLR_HIP(hipMemcpyAsync(h_res_out, d_out, static_cast<size_t>(nq) * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    SelectState *h_st = static_cast<SelectState *>(c->h_batch);
+    SelectState *h_st = static_cast<SelectState *>(c->h_batch.get());
     if (n_cand_out)
-        RLR_HIP(hipMemcpyAsync(h_st, c->d_bstate, nq * sizeof(SelectState), hipMemcpyDeviceToHost, s));
+        RLR_HIP(hipMemcpyAsync(h_st, c->d_bstate.get(), nq * sizeof(SelectState), hipMemcpyDeviceToHost, s));
     RLR_HIP(hipStreamSynchronize(s));
     h_status.assign(h_stat, h_stat + nq);
     if (n_cand_out) {
@@ -2127,7 +2026,7 @@ int32_t run_batched(rlr_index *ix, Ctx *c, uint32_t q0, uint32_t nq, const Searc
     const uint32_t n_qblocks = (nq + 255) / 256;
     // 2..8 queries over f32 rows: one VALU pass over the rows for all of them (scan_multi_kernel) instead of the
     // matrix-core pipeline -- about the cost of a single scan, scores in wavefront order (the tight f32 band)
-    const bool use_multi = batch_multi_shape(ix, nq, coalesced) && !(ix->image_enabled && ix->d_image);
+    const bool use_multi = batch_multi_shape(ix, nq, coalesced) && !(ix->image_enabled && ix->d_image.get());
     const float eps_nom = use_multi ? 0.5f * p.two_eps : nomination_eps(ix->dim, ix->dtype, p.scale, p.norm_sum);
     const float two_eps = 2.0f * eps_nom;
     // Sample rows [0, S): the floor for the rest of the corpus is the sample's rank-th score, and S is large enough that
@@ -2159,25 +2058,18 @@ int32_t run_batched(rlr_index *ix, Ctx *c, uint32_t q0, uint32_t nq, const Searc
 
     // workspace
     const uint64_t qfrag_bytes = static_cast<uint64_t>(n_qblocks) * 256 * ix->dim * 2;
-    if (c->qfrag_cap < qfrag_bytes) {
-        if (c->d_qfrag) (void)hipFree(c->d_qfrag);
-        c->d_qfrag = nullptr;
-        c->qfrag_cap = 0;
-        RLR_HIP(rlr::dev_malloc(&c->d_qfrag, qfrag_bytes));
-        c->qfrag_cap = qfrag_bytes;
-    }
-    if (!c->d_gsync)
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_gsync), 256 * sizeof(uint32_t)));
+    RLR_HIP(c->d_qfrag.reserve(qfrag_bytes));
+    RLR_HIP(c->d_gsync.reserve(256));
     RLR_TRY(batch_arm(c, nq, fin_cap, s_stride, rank, S));
 
-    const float *dq = c->d_query + static_cast<size_t>(q0) * ix->q_pitch;
+    const float *dq = c->d_query.get() + static_cast<size_t>(q0) * ix->q_pitch;
     const bool timed = ix->profiling;
     if (timed) RLR_HIP(hipEventRecord(c->bev[0], s));
-    const bool use_image = ix->image_enabled && ix->d_image && gemm_image_usable(ix->dim);
-    const void *image = use_image ? ix->d_image : nullptr;
+    const bool use_image = ix->image_enabled && ix->d_image.get() && gemm_image_usable(ix->dim);
+    const void *image = use_image ? ix->d_image.get() : nullptr;
     // the image stores k in natural order (like binary16 rows); only the direct f32-row loads permute it
     if (use_multi) {
-        const ScanArgs sa = scan_args(ix, dq, c->d_sample, nullptr);
+        const ScanArgs sa = scan_args(ix, dq, c->d_sample.get(), nullptr);
         hipError_t e = hipSuccess;
         // (binary16 rows: the same band -- the widening is exact and the products and sums are f32 as in the single-query scan)
         if (!(ix->dtype == RLR_F16 ? launch_scan_multi_f16(sa, ix->q_pitch, nq, s_stride, s, &e)
@@ -2185,21 +2077,21 @@ int32_t run_batched(rlr_index *ix, Ctx *c, uint32_t q0, uint32_t nq, const Searc
             return fail(RLR_E_INTERNAL, "multi-query scan refused a shape its gate accepted");
         RLR_HIP(e);
     } else {
-        RLR_HIP(launch_prep_queries(dq, nq, ix->q_pitch, ix->dim, use_image ? static_cast<int>(RLR_F16) : ix->dtype, c->d_qfrag, s));
+        RLR_HIP(launch_prep_queries(dq, nq, ix->q_pitch, ix->dim, use_image ? static_cast<int>(RLR_F16) : ix->dtype, c->d_qfrag.get(), s));
         // 1. nominated scores of the sample rows, materialised
-        RLR_HIP(launch_gemm_nominate(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, 0, static_cast<uint32_t>(S), c->d_qfrag, nq,
-                                     nullptr, nullptr, 0, nullptr, c->d_sample, s_stride, image, s));
+        RLR_HIP(launch_gemm_nominate(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, 0, static_cast<uint32_t>(S), c->d_qfrag.get(), nq,
+                                     nullptr, nullptr, 0, nullptr, c->d_sample.get(), s_stride, image, s));
     }
     if (timed) RLR_HIP(hipEventRecord(c->bev[1], s));
     // 2. per-query k-th score of the sample -> threshold; the sample's own candidates
-    RLR_HIP(launch_batch_select(c->d_sample, static_cast<uint32_t>(S), s_stride, nq, c->d_bhist, c->d_bstate, two_eps,
-                                c->d_tau, c->d_bcand, fin_cap, ix->n_cu, s));
+    RLR_HIP(launch_batch_select(c->d_sample.get(), static_cast<uint32_t>(S), s_stride, nq, c->d_bhist.get(), c->d_bstate.get(), two_eps,
+                                c->d_tau.get(), c->d_bcand.get(), fin_cap, ix->n_cu, s));
     if (timed) RLR_HIP(hipEventRecord(c->bev[2], s));
     const uint32_t rest_begin = static_cast<uint32_t>(S);
     // 3. the rest of the corpus, filtered in the GEMM epilogue
     if (timed) RLR_HIP(hipEventRecord(c->bev[4], s));
-    RLR_HIP(launch_gemm_nominate(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, rest_begin, n, c->d_qfrag, nq,
-                                 c->d_tau, c->d_bcand, fin_cap, c->d_bstate, nullptr, 0, image, s, c->d_gsync));
+    RLR_HIP(launch_gemm_nominate(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, rest_begin, n, c->d_qfrag.get(), nq,
+                                 c->d_tau.get(), c->d_bcand.get(), fin_cap, c->d_bstate.get(), nullptr, 0, image, s, c->d_gsync.get()));
     if (timed) RLR_HIP(hipEventRecord(c->bev[3], s));
     // 4. per-query finish: band, reference-order re-score, order, emit
     RLR_TRY(batch_finish(ix, c, dq, nq, p.k, two_eps, d_out, h_status, h_res_out));
@@ -2256,15 +2148,15 @@ int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uin
         return RLR_OK;
     RLR_TRY(ctx_prepare(ix, c, nq, p));
     const size_t n_res = static_cast<size_t>(nq) * p.k;
-    uint64_t *d_out = d_out_user ? d_out_user : c->d_out;
-    uint64_t *d_meta = c->d_out + n_res; // per-query candidate counts, right behind the context's results
+    uint64_t *d_out = d_out_user ? d_out_user : c->d_out.get();
+    uint64_t *d_meta = c->d_out.get() + n_res; // per-query candidate counts, right behind the context's results
 
     // stage queries (zero padded to the row pitch)
     const size_t q_bytes = static_cast<size_t>(nq) * ix->q_pitch * sizeof(float);
     const size_t res_bytes = (n_res + nq) * sizeof(uint64_t);
     RLR_TRY(pin_reserve(c, q_bytes + res_bytes));
-    float *h_q = static_cast<float *>(c->h_pin);
-    uint64_t *h_res = reinterpret_cast<uint64_t *>(static_cast<char *>(c->h_pin) + q_bytes);
+    float *h_q = static_cast<float *>(c->h_pin.get());
+    uint64_t *h_res = reinterpret_cast<uint64_t *>(static_cast<char *>(c->h_pin.get()) + q_bytes);
     uint64_t *h_meta = h_res + n_res;
     stage_queries(ix, c, queries, nq, h_q);
     hipStream_t s = c->stream;
@@ -2282,7 +2174,7 @@ int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uin
     uint64_t n_cand_total = 0, n_retry = 0;
     auto fetch_results = [&](size_t first, size_t count) -> int32_t { // packed results -> pinned host
         if (!d_out_user && count)
-            RLR_HIP(hipMemcpyAsync(h_res + first, c->d_out + first, count * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+            RLR_HIP(hipMemcpyAsync(h_res + first, c->d_out.get() + first, count * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         return RLR_OK;
     };
 
@@ -2365,20 +2257,11 @@ int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uin
     return note_search(ix, c, nq, n_cand_total, n_retry, timed, /*mmr_chain=*/false, nq > 1 ? &per_query_ms : nullptr);
 }
 
-// c->d_list / c->d_vals for n rows (at least 1024)
+// c->d_list / c->d_vals for n rows (a power of two, at least 1024)
 int32_t reserve_list(Ctx *c, uint32_t n)
 {
-    if (c->list_cap >= n && c->d_list)
-        return RLR_OK;
-    if (c->d_list) (void)hipFree(c->d_list);
-    if (c->d_vals) (void)hipFree(c->d_vals);
-    c->d_list = nullptr;
-    c->d_vals = nullptr;
-    c->list_cap = 0;
     const uint32_t cap = std::max<uint32_t>(next_pow2(n), 1024);
-    RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_list), static_cast<size_t>(cap) * sizeof(uint32_t)));
-    RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_vals), static_cast<size_t>(cap) * sizeof(float)));
-    c->list_cap = cap;
+    RLR_HIP(reserve_group(Want{c->d_list, cap}, Want{c->d_vals, cap}));
     return RLR_OK;
 }
 
@@ -2388,14 +2271,14 @@ int32_t upload_list(rlr_index *ix, Ctx *c, const uint64_t *rows, uint32_t n, uin
         bound = ix->n_rows;
     RLR_TRY(reserve_list(c, n));
     RLR_TRY(pin_reserve(c, static_cast<size_t>(n) * 8 + 64));
-    uint32_t *h = static_cast<uint32_t *>(c->h_pin);
+    uint32_t *h = static_cast<uint32_t *>(c->h_pin.get());
     for (uint32_t i = 0; i < n; ++i) {
         if (rows[i] >= bound)
             return fail(RLR_E_RANGE, "row %llu out of range (%llu rows)", static_cast<unsigned long long>(rows[i]),
                         static_cast<unsigned long long>(bound));
         h[i] = static_cast<uint32_t>(rows[i]);
     }
-    RLR_HIP(hipMemcpyAsync(c->d_list, h, static_cast<size_t>(n) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    RLR_HIP(hipMemcpyAsync(c->d_list.get(), h, static_cast<size_t>(n) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     return RLR_OK;
 }
 
@@ -2453,21 +2336,6 @@ int32_t check_filter(const rlr_index *ix, const rlr_filter *f)
     return RLR_OK;
 }
 
-int32_t reserve_cand(Ctx *c, uint32_t cap)
-{
-    if (c->cand_cap >= cap)
-        return RLR_OK;
-    if (c->d_cand) (void)hipFree(c->d_cand);
-    if (c->d_packed) (void)hipFree(c->d_packed);
-    c->d_cand = nullptr;
-    c->d_packed = nullptr;
-    c->cand_cap = 0;
-    RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_cand), static_cast<size_t>(cap) * sizeof(uint32_t)));
-    RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_packed), static_cast<size_t>(cap) * sizeof(uint64_t)));
-    c->cand_cap = cap;
-    return RLR_OK;
-}
-
 // The list path, and the exact fall-back of the masked scan: every allowed row scored in reference order (no nomination,
 // no band), the keys sorted -- or, for k <= 4096, the k best selected and sorted by one workgroup.  The query is in
 // c->d_query; p.k <= n_allowed.  The k packed results end up in h_res.
@@ -2476,11 +2344,11 @@ int32_t filtered_exact_enqueue(rlr_index *ix, Ctx *c, const rlr_filter *f, const
 {
     hipStream_t s = c->stream;
     const uint32_t n = static_cast<uint32_t>(f->n_allowed);
-    SelectState *st = c->d_state + qi;
-    RLR_HIP(launch_score_rows(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_query + static_cast<size_t>(qi) * ix->q_pitch,
-                              f->d_list, n, d_vals, s));
+    SelectState *st = c->d_state.get() + qi;
+    RLR_HIP(launch_score_rows(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, c->d_query.get() + static_cast<size_t>(qi) * ix->q_pitch,
+                              f->d_list.get(), n, d_vals, s));
     hipLaunchKernelGGL(rlr::pack_list_kernel, dim3(std::min<uint32_t>((cap + 255) / 256, 1024)), dim3(256), 0, s, d_vals,
-                       f->d_list, n, d_packed, cap, st);
+                       f->d_list.get(), n, d_packed, cap, st);
     RLR_HIP(hipGetLastError());
     if (p.k <= kLdsSortCap) {
         hipLaunchKernelGGL(rlr::topk_global_kernel, dim3(1), dim3(1024), 0, s, d_packed, st, cap, d_out, p.k);
@@ -2499,8 +2367,8 @@ int32_t filtered_exact(rlr_index *ix, Ctx *c, const rlr_filter *f, const SearchP
     const uint32_t cap = next_pow2(std::max<uint32_t>(n, p.k));
     RLR_TRY(reserve_list(c, n));
     RLR_TRY(reserve_cand(c, cap));
-    RLR_TRY(filtered_exact_enqueue(ix, c, f, p, 0, c->d_vals, c->d_packed, cap, c->d_out));
-    RLR_HIP(hipMemcpyAsync(h_res, c->d_out, static_cast<size_t>(p.k) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    RLR_TRY(filtered_exact_enqueue(ix, c, f, p, 0, c->d_vals.get(), c->d_packed.get(), cap, c->d_out.get()));
+    RLR_HIP(hipMemcpyAsync(h_res, c->d_out.get(), static_cast<size_t>(p.k) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     RLR_HIP(hipStreamSynchronize(s));
     return RLR_OK;
 }
@@ -2521,8 +2389,8 @@ int32_t filtered_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *
     RLR_TRY(ctx_prepare(ix, c, 1, p));
     const size_t q_bytes = static_cast<size_t>(ix->q_pitch) * sizeof(float);
     RLR_TRY(pin_reserve(c, q_bytes + (static_cast<size_t>(p.k) + 1) * sizeof(uint64_t)));
-    float *h_q = static_cast<float *>(c->h_pin);
-    uint64_t *h_res = reinterpret_cast<uint64_t *>(static_cast<char *>(c->h_pin) + q_bytes);
+    float *h_q = static_cast<float *>(c->h_pin.get());
+    uint64_t *h_res = reinterpret_cast<uint64_t *>(static_cast<char *>(c->h_pin.get()) + q_bytes);
     uint64_t *h_meta = h_res + p.k;
     stage_queries(ix, c, query, 1, h_q);
     hipStream_t s = c->stream;
@@ -2535,12 +2403,13 @@ int32_t filtered_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *
     } else {
         arm_meta(h_meta, 1);
         if (c->h_assert) {
-            hipLaunchKernelGGL(rlr::hist_assert_zero_kernel, dim3(4), dim3(256), 0, s, c->d_hist, 2u * kHistBins, c->h_assert);
+            hipLaunchKernelGGL(rlr::hist_assert_zero_kernel, dim3(4), dim3(256), 0, s, c->d_hist.get(), 2u * kHistBins,
+                           static_cast<uint32_t *>(c->h_assert.get()));
             RLR_HIP(hipGetLastError());
         }
         if (timed)
             RLR_HIP(hipEventRecord(c->ev[0], s));
-        RLR_HIP(launch_scan_masked(scan_args(ix, c->d_query, c->d_scores, c->d_hist), f->d_mask, f->n_allowed, s));
+        RLR_HIP(launch_scan_masked(scan_args(ix, c->d_query.get(), c->d_scores.get(), c->d_hist.get()), f->d_mask.get(), f->n_allowed, s));
         if (timed)
             RLR_HIP(hipEventRecord(c->ev[1], s));
         RLR_HIP(enqueue_query_rest(ix, c, 0, p, h_res, h_meta, timed, true, nullptr, nullptr, /*master_scan=*/true));
@@ -2614,8 +2483,8 @@ int32_t filtered_batch(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *
     const size_t q_bytes = static_cast<size_t>(m) * ix->q_pitch * sizeof(float);
     const size_t n_res = static_cast<size_t>(m) * p.k;
     RLR_TRY(pin_reserve(c, q_bytes + n_res * sizeof(uint64_t)));
-    float *h_q = static_cast<float *>(c->h_pin);
-    uint64_t *h_res = reinterpret_cast<uint64_t *>(static_cast<char *>(c->h_pin) + q_bytes);
+    float *h_q = static_cast<float *>(c->h_pin.get());
+    uint64_t *h_res = reinterpret_cast<uint64_t *>(static_cast<char *>(c->h_pin.get()) + q_bytes);
     stage_queries(ix, c, queries, m, h_q);
     hipStream_t s = c->stream;
     c->h_q_kq = nullptr;
@@ -2627,15 +2496,15 @@ int32_t filtered_batch(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *
     const bool timed = ix->profiling;
     if (timed) RLR_HIP(hipEventRecord(c->bev[0], s));
     hipError_t e = hipSuccess;
-    if (!launch_scan_masked_multi(scan_args(ix, c->d_query, c->d_sample, nullptr), f->d_mask, f->n_allowed, ix->q_pitch, m,
+    if (!launch_scan_masked_multi(scan_args(ix, c->d_query.get(), c->d_sample.get(), nullptr), f->d_mask.get(), f->n_allowed, ix->q_pitch, m,
                                   s_stride, s, &e))
         return fail(RLR_E_INTERNAL, "masked multi-query scan refused a shape its gate accepted");
     RLR_HIP(e);
     if (timed) RLR_HIP(hipEventRecord(c->bev[1], s));
-    RLR_HIP(launch_batch_select(c->d_sample, static_cast<uint32_t>(n), s_stride, m, c->d_bhist, c->d_bstate, two_eps, c->d_tau,
-                                c->d_bcand, batch_finish_capacity(), ix->n_cu, s));
+    RLR_HIP(launch_batch_select(c->d_sample.get(), static_cast<uint32_t>(n), s_stride, m, c->d_bhist.get(), c->d_bstate.get(), two_eps, c->d_tau.get(),
+                                c->d_bcand.get(), batch_finish_capacity(), ix->n_cu, s));
     std::vector<uint32_t> status, n_cand;
-    RLR_TRY(batch_finish(ix, c, c->d_query, m, p.k, two_eps, c->d_out, status, h_res, &n_cand));
+    RLR_TRY(batch_finish(ix, c, c->d_query.get(), m, p.k, two_eps, c->d_out.get(), status, h_res, &n_cand));
     c->hist_dirty = false;
     std::vector<uint32_t> redo;
     uint64_t n_cand_total = 0; // of the queries served here, as filtered_query reports its own
@@ -2683,8 +2552,8 @@ int32_t filtered_list_batch(rlr_index *ix, Ctx *c, const rlr_filter *f, const fl
     const size_t q_bytes = static_cast<size_t>(m) * ix->q_pitch * sizeof(float);
     const size_t n_res = static_cast<size_t>(m) * p.k;
     RLR_TRY(pin_reserve(c, q_bytes + n_res * sizeof(uint64_t)));
-    float *h_q = static_cast<float *>(c->h_pin);
-    uint64_t *h_res = reinterpret_cast<uint64_t *>(static_cast<char *>(c->h_pin) + q_bytes);
+    float *h_q = static_cast<float *>(c->h_pin.get());
+    uint64_t *h_res = reinterpret_cast<uint64_t *>(static_cast<char *>(c->h_pin.get()) + q_bytes);
     stage_queries(ix, c, queries, m, h_q);
     hipStream_t s = c->stream;
     c->h_q_kq = nullptr;
@@ -2693,9 +2562,9 @@ int32_t filtered_list_batch(rlr_index *ix, Ctx *c, const rlr_filter *f, const fl
     RLR_TRY(reserve_list(c, m * cap));
     RLR_TRY(reserve_cand(c, next_pow2(m * cap)));
     for (uint32_t q = 0; q < m; ++q)
-        RLR_TRY(filtered_exact_enqueue(ix, c, f, p, q, c->d_vals + static_cast<size_t>(q) * cap, c->d_packed + static_cast<size_t>(q) * cap,
-                                       cap, c->d_out + static_cast<size_t>(q) * p.k));
-    RLR_HIP(hipMemcpyAsync(h_res, c->d_out, n_res * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        RLR_TRY(filtered_exact_enqueue(ix, c, f, p, q, c->d_vals.get() + static_cast<size_t>(q) * cap, c->d_packed.get() + static_cast<size_t>(q) * cap,
+                                       cap, c->d_out.get() + static_cast<size_t>(q) * p.k));
+    RLR_HIP(hipMemcpyAsync(h_res, c->d_out.get(), n_res * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     RLR_HIP(hipStreamSynchronize(s));
     c->hist_dirty = false;
     for (uint32_t q = 0; q < m; ++q) {
@@ -2723,23 +2592,18 @@ int32_t filter_finish(rlr_index *ix, std::vector<uint64_t> &&mask, rlr_filter **
     CtxLease lease(ix);
     RLR_TRY(ctx_acquire(ix, &lease.c));
     hipStream_t s = lease.c->stream;
-    const size_t mask_bytes = std::max<size_t>(f->h_mask.size(), 1) * sizeof(uint64_t);
-    const size_t list_bytes = std::max<size_t>(list.size(), 1) * sizeof(uint32_t);
-    hipError_t e = rlr::dev_malloc(reinterpret_cast<void **>(&f->d_mask), mask_bytes);
+    hipError_t e = f->d_mask.reserve(std::max<size_t>(f->h_mask.size(), 1));
     if (e == hipSuccess)
-        e = rlr::dev_malloc(reinterpret_cast<void **>(&f->d_list), list_bytes);
+        e = f->d_list.reserve(std::max<size_t>(list.size(), 1));
     // uploaded on a stream and waited for: the searches that read them run on other, non-blocking streams
     if (e == hipSuccess && !f->h_mask.empty())
-        e = hipMemcpyAsync(f->d_mask, f->h_mask.data(), f->h_mask.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s);
+        e = hipMemcpyAsync(f->d_mask.get(), f->h_mask.data(), f->h_mask.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s);
     if (e == hipSuccess && !list.empty())
-        e = hipMemcpyAsync(f->d_list, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+        e = hipMemcpyAsync(f->d_list.get(), list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s);
     if (e == hipSuccess)
         e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-        if (f->d_mask) (void)hipFree(f->d_mask);
-        if (f->d_list) (void)hipFree(f->d_list);
+    if (e != hipSuccess)
         return fail(e == hipErrorOutOfMemory ? RLR_E_OOM : RLR_E_HIP, "filter upload failed: %s", hipGetErrorString(e));
-    }
     *out = f.release();
     return RLR_OK;
 }
@@ -3016,14 +2880,7 @@ int32_t rlr_index_destroy(rlr_index *ix)
     (void)hipDeviceSynchronize();
     for (Ctx *c : ix->free_ctx)
         ctx_free(c);
-    if (ix->d_rows) (void)hipFree(ix->d_rows);
-    ix->d_rows = nullptr;
-    if (ix->d_q8) (void)hipFree(ix->d_q8);
-    if (ix->d_q8_scale) (void)hipFree(ix->d_q8_scale);
-    if (ix->d_q8_stats) (void)hipFree(ix->d_q8_stats);
-    if (ix->d_image)
-        (void)hipFree(ix->d_image);
-    delete ix;
+    delete ix; // (the rows and the nomination copies free themselves)
     return RLR_OK;
 }
 
@@ -3105,31 +2962,29 @@ int32_t rlr_index_delete_rows(rlr_index *ix, const uint64_t *rows, uint64_t n)
     // stable in-place compaction through a bounce buffer: destination rows
     // [first_dead + i0, first_dead + i1) only overwrite rows below every source still to move.
     const uint64_t chunk = std::max<uint64_t>(1, (256ull << 20) / row_bytes(ix));
-    void *d_bounce = nullptr;
-    uint32_t *d_keep = nullptr;
+    DevBuf<uint8_t> bounce;
+    DevBuf<uint32_t> keep_dev;
     const uint64_t cr = std::min<uint64_t>(chunk, std::max<size_t>(keep.size(), 1));
-    RLR_HIP(rlr::dev_malloc(&d_bounce, cr * row_bytes(ix)));
-    hipError_t e = rlr::dev_malloc(reinterpret_cast<void **>(&d_keep), cr * sizeof(uint32_t));
-    if (e != hipSuccess) {
-        (void)hipFree(d_bounce);
+    RLR_HIP(bounce.reserve(cr * row_bytes(ix)));
+    hipError_t e = keep_dev.reserve(cr);
+    if (e != hipSuccess)
         return fail(RLR_E_OOM, "compaction buffer allocation failed");
-    }
+    void *const d_bounce = bounce.get();
+    uint32_t *const d_keep = keep_dev.get();
     int32_t st = RLR_OK;
     for (uint64_t i0 = 0; i0 < keep.size() && st == RLR_OK; i0 += cr) {
         const uint64_t m = std::min<uint64_t>(cr, keep.size() - i0);
         e = hipMemcpy(d_keep, keep.data() + i0, m * sizeof(uint32_t), hipMemcpyHostToDevice);
         if (e == hipSuccess)
-            e = launch_compact_rows(ix->d_rows, d_bounce, ix->pitch16, d_keep, static_cast<uint32_t>(m), nullptr);
+            e = launch_compact_rows(ix->d_rows.get(), d_bounce, ix->pitch16, d_keep, static_cast<uint32_t>(m), nullptr);
         if (e == hipSuccess)
-            e = hipMemcpyAsync(static_cast<char *>(ix->d_rows) + (first_dead + i0) * row_bytes(ix), d_bounce,
+            e = hipMemcpyAsync(static_cast<char *>(ix->d_rows.get()) + (first_dead + i0) * row_bytes(ix), d_bounce,
                                m * row_bytes(ix), hipMemcpyDeviceToDevice, nullptr);
         if (e == hipSuccess)
             e = hipStreamSynchronize(nullptr);
         if (e != hipSuccess)
             st = fail(RLR_E_HIP, "row compaction failed: %s", hipGetErrorString(e));
     }
-    (void)hipFree(d_bounce);
-    (void)hipFree(d_keep);
     if (st == RLR_OK) {
         ix->n_rows = first_dead + keep.size();
         st = sync_image(ix, first_dead);
@@ -3144,19 +2999,13 @@ int32_t rlr_index_enable_batch_image(rlr_index *ix, int32_t enable)
     const bool want_image = (enable & 3) != 0, want_q8 = (enable & 4) != 0;
     if (!want_q8 && ix->q8_enabled) {
         ix->q8_enabled = false;
-        if (ix->d_q8) (void)hipFree(ix->d_q8);
-        if (ix->d_q8_scale) (void)hipFree(ix->d_q8_scale);
-        ix->d_q8 = nullptr;
-        ix->d_q8_scale = nullptr;
-        ix->q8_cap_rows = 0;
+        ix->d_q8.reset();
+        ix->d_q8_scale.reset();
     }
     if (!want_image) {
         ix->image_enabled = false;
         ix->image_scan = false;
-        if (ix->d_image)
-            (void)hipFree(ix->d_image);
-        ix->d_image = nullptr;
-        ix->image_cap = 0;
+        ix->d_image.reset();
     }
     if (want_q8 && !ix->q8_enabled) {
         if (ix->dim % 16 != 0 || ix->dim > 2048)
@@ -3168,7 +3017,7 @@ int32_t rlr_index_enable_batch_image(rlr_index *ix, int32_t enable)
         if (ix->dim % 64 != 0)
             return fail(RLR_E_INVALID, "the nomination image needs dim %% 64 == 0 (dim = %u)", ix->dim);
         ix->image_scan = (enable & 2) != 0;
-        if (!(ix->image_enabled && ix->d_image)) {
+        if (!(ix->image_enabled && ix->d_image.get())) {
             ix->image_enabled = true;
             const bool q8 = ix->q8_enabled;
             ix->q8_enabled = false; // the 8-bit copy is current: rebuild the image only
@@ -3188,8 +3037,9 @@ int32_t rlr_index_fill_synthetic(rlr_index *ix, uint64_t n_rows, uint64_t row0, 
     ix->n_rows = 0;
     RLR_TRY(ensure_rows(ix, n_rows));
     const uint64_t chunk = 1ull << 20;
-    float *d_norm = nullptr;
-    RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&d_norm), std::min(chunk, std::max<uint64_t>(n_rows, 1)) * sizeof(float)));
+    DevBuf<float> norm;
+    RLR_HIP(norm.reserve(std::min(chunk, std::max<uint64_t>(n_rows, 1))));
+    float *const d_norm = norm.get();
     int32_t st = RLR_OK;
     // bit 30: the last n_rows / 100 rows repeat the first n_rows / 100 (exact duplicates)
     const uint64_t n_dup = (n_clusters & 0x40000000u) ? n_rows / 100 : 0;
@@ -3200,7 +3050,7 @@ int32_t rlr_index_fill_synthetic(rlr_index *ix, uint64_t n_rows, uint64_t row0, 
         if (r0 < seam)
             m = std::min(m, seam - r0); // (a launch never straddles the seam)
         const uint64_t src = r0 < seam ? row0 + r0 : row0 + (r0 - seam);
-        hipError_t e = launch_synth(static_cast<char *>(ix->d_rows) + r0 * row_bytes(ix), ix->pitch16, ix->dim, ix->dtype,
+        hipError_t e = launch_synth(static_cast<char *>(ix->d_rows.get()) + r0 * row_bytes(ix), ix->pitch16, ix->dim, ix->dtype,
                                     src, static_cast<uint32_t>(m), seed, n_clusters, d_norm, nullptr);
         if (e == hipSuccess)
             e = hipStreamSynchronize(nullptr);
@@ -3208,7 +3058,6 @@ int32_t rlr_index_fill_synthetic(rlr_index *ix, uint64_t n_rows, uint64_t row0, 
             st = fail(RLR_E_HIP, "synthetic fill failed: %s", hipGetErrorString(e));
         r0 += m;
     }
-    (void)hipFree(d_norm);
     if (st == RLR_OK) {
         ix->n_rows = n_rows;
         st = sync_image(ix, 0);
@@ -3279,8 +3128,6 @@ int32_t rlr_filter_destroy(rlr_filter *f)
         return RLR_OK;
     if (f->ix)
         (void)hipSetDevice(f->ix->device);
-    if (f->d_mask) (void)hipFree(f->d_mask);
-    if (f->d_list) (void)hipFree(f->d_list);
     delete f;
     return RLR_OK;
 }
@@ -3410,8 +3257,8 @@ int32_t rlr_search_topk_device_begin(rlr_index *ix, const float *queries, uint32
     count_f16_fallbacks(ix, p, n_queries, false);
     const size_t q_bytes = static_cast<size_t>(n_queries) * ix->q_pitch * sizeof(float);
     RLR_TRY(pin_reserve(c, q_bytes + (static_cast<size_t>(n_queries) * k + n_queries) * sizeof(uint64_t)));
-    float *h_q = static_cast<float *>(c->h_pin);
-    uint64_t *h_meta = reinterpret_cast<uint64_t *>(static_cast<char *>(c->h_pin) + q_bytes) + static_cast<size_t>(n_queries) * k;
+    float *h_q = static_cast<float *>(c->h_pin.get());
+    uint64_t *h_meta = reinterpret_cast<uint64_t *>(static_cast<char *>(c->h_pin.get()) + q_bytes) + static_cast<size_t>(n_queries) * k;
     stage_queries(ix, c, queries, n_queries, h_q);
     // The pipelines go on the CALLER's stream: whatever it queues next (all-gather, merge) is ordered behind
     // them by the stream itself.  (A cross-stream event wait was measured first: +20 us per step.)  The
@@ -3489,19 +3336,14 @@ int32_t rlr_merge_topk(int32_t device_id, const void *d_gathered, uint32_t world
             return fail(RLR_E_INVALID, "shard base %llu is not below 2^32 - 1", static_cast<unsigned long long>(bases[r]));
     RLR_HIP(hipSetDevice(device_id));
     // results are written straight into pinned, device-mapped host memory: no D2H copy
-    thread_local void *h_buf = nullptr;
-    thread_local size_t h_cap = 0;
+    // Freed when the calling thread exits (it used to be leaked).  Intended: a thread's destructors run at its own exit,
+    // the main thread's at the start of exit(), both before the HIP runtime's statics go; a thread still alive when the
+    // process exits never runs them at all.
+    thread_local PinBuf h_pin;
     const size_t nk = static_cast<size_t>(n_queries) * k;
     const size_t need = nk * (sizeof(uint64_t) + sizeof(float)) + n_queries * (sizeof(uint32_t) + sizeof(uint64_t)) + 64;
-    if (h_cap < need) {
-        if (h_buf)
-            (void)hipHostFree(h_buf);
-        h_buf = nullptr;
-        h_cap = 0;
-        RLR_HIP(hipHostMalloc(&h_buf, std::max<size_t>(need, 1 << 16), hipHostMallocDefault));
-        h_cap = std::max<size_t>(need, 1 << 16);
-    }
-    uint64_t *h_rows = static_cast<uint64_t *>(h_buf);
+    RLR_HIP(h_pin.reserve(std::max<size_t>(need, 1 << 16)));
+    uint64_t *h_rows = static_cast<uint64_t *>(h_pin.get());
     uint64_t *h_flag = h_rows + nk;
     float *h_cos = reinterpret_cast<float *>(h_flag + n_queries);
     uint32_t *h_n = reinterpret_cast<uint32_t *>(h_cos + nk);
@@ -3570,16 +3412,11 @@ int32_t rlr_score_rows(rlr_index *ix, const float *query, const uint64_t *rows, 
     RLR_TRY(ctx_acquire(ix, &lease.c));
     Ctx *c = lease.c;
     RLR_TRY(upload_list(ix, c, rows, n));
-    if (c->q_cap < 1) {
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_query), static_cast<size_t>(ix->q_pitch) * sizeof(float)));
-        RLR_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&c->d_state), sizeof(SelectState)));
-        RLR_HIP(hipMemsetAsync(c->d_state, 0, sizeof(SelectState), c->stream)); // (the fused tail's counters, as in ctx_prepare)
-        c->q_cap = 1;
-    }
-    RLR_HIP(hipMemcpyAsync(c->d_query, query, ix->dim * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    RLR_HIP(launch_score_rows(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_query, c->d_list, n, c->d_vals,
+    RLR_TRY(reserve_queries(ix, c, 1));
+    RLR_HIP(hipMemcpyAsync(c->d_query.get(), query, ix->dim * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    RLR_HIP(launch_score_rows(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, c->d_query.get(), c->d_list.get(), n, c->d_vals.get(),
                               c->stream));
-    RLR_HIP(hipMemcpyAsync(cos_out, c->d_vals, static_cast<size_t>(n) * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    RLR_HIP(hipMemcpyAsync(cos_out, c->d_vals.get(), static_cast<size_t>(n) * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     RLR_HIP(hipStreamSynchronize(c->stream));
     return RLR_OK;
 }
@@ -3596,9 +3433,9 @@ int32_t rlr_fetch_rows(rlr_index *ix, const uint64_t *rows, uint32_t n, float *o
     RLR_TRY(ctx_acquire(ix, &lease.c));
     Ctx *c = lease.c;
     RLR_TRY(upload_list(ix, c, rows, n));
-    RLR_TRY(grow(&c->d_pool, &c->pool_cap, static_cast<uint64_t>(n) * ix->dim));
-    RLR_HIP(launch_gather_f32(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_list, n, c->d_pool, c->stream));
-    RLR_HIP(hipMemcpyAsync(out, c->d_pool, static_cast<size_t>(n) * ix->dim * sizeof(float), hipMemcpyDeviceToHost,
+    RLR_HIP(c->d_pool.reserve(static_cast<uint64_t>(n) * ix->dim));
+    RLR_HIP(launch_gather_f32(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, c->d_list.get(), n, c->d_pool.get(), c->stream));
+    RLR_HIP(hipMemcpyAsync(out, c->d_pool.get(), static_cast<size_t>(n) * ix->dim * sizeof(float), hipMemcpyDeviceToHost,
                            c->stream));
     RLR_HIP(hipStreamSynchronize(c->stream));
     return RLR_OK;
@@ -3626,16 +3463,16 @@ static int32_t mmr_single_impl(rlr_index *ix, const uint64_t *pool_rows, const f
     hipStream_t s = c->stream;
     RLR_TRY(upload_list(ix, c, pool_rows, P, d_matrix ? n_matrix : ~0ull));
     const uint64_t head = static_cast<uint64_t>(P) * ix->dim;
-    RLR_TRY(grow(&c->d_pool, &c->pool_cap, MmrWs(nullptr, 1, P, head).d.floats()));
-    const MmrWs ws(c->d_pool, 1, P, head);
+    RLR_HIP(c->d_pool.reserve(MmrWs(nullptr, 1, P, head).d.floats()));
+    const MmrWs ws(c->d_pool.get(), 1, P, head);
     const bool timed = ix->profiling;
     RLR_HIP(hipMemcpyAsync(ws.scores, pool_scores, static_cast<size_t>(P) * sizeof(float), hipMemcpyHostToDevice, s));
     if (timed) RLR_HIP(hipEventRecord(c->ev[0], s));
-    RLR_HIP(launch_gram_rows(d_matrix ? d_matrix : ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_list, P, ws.gram, 1, s));
+    RLR_HIP(launch_gram_rows(d_matrix ? d_matrix : ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, c->d_list.get(), P, ws.gram, 1, s));
     RLR_HIP(launch_mmr_greedy(ws.gram, ws.scores, P, k, lambda, ws.res.order, ws.res.mmr, ws.res.n, nullptr, 1, s));
     if (timed) RLR_HIP(hipEventRecord(c->ev[1], s));
     RLR_TRY(pin_reserve(c, (MmrResults::words(1, P) + 3) * 4));
-    Carver pin(c->h_pin); // (upload_list's copy out of it is ahead on the stream)
+    Carver pin(c->h_pin.get()); // (upload_list's copy out of it is ahead on the stream)
     const MmrResults h(pin, 1, P);
     RLR_HIP(hipMemcpyAsync(h.order, ws.res.order, MmrResults::words(1, P) * 4, hipMemcpyDeviceToHost, s));
     RLR_HIP(hipStreamSynchronize(s));
@@ -3692,31 +3529,31 @@ int32_t rlr_search_diverse(rlr_index *ix, const float *query, uint32_t pool, uin
     const uint32_t P = need;
     const uint32_t k_cap = rlr::result_k_cap(k, P, true);
     const DiverseWs sizes(nullptr, nullptr, ix, P, k_cap);
-    RLR_TRY(grow(&c->d_pool, &c->pool_cap, sizes.d.floats()));
+    RLR_HIP(c->d_pool.reserve(sizes.d.floats()));
     RLR_TRY(reserve_list(c, P));
     RLR_TRY(pin_reserve(c, sizes.h.bytes));
-    const DiverseWs ws(c->d_pool, c->h_pin, ix, P, k_cap);
+    const DiverseWs ws(c->d_pool.get(), c->h_pin.get(), ix, P, k_cap);
     uint32_t *h_out = ws.h_out;
     h_out[block_done(k_cap)] = kBlockPending; // (the greedy kernel's last store replaces it: what the wait below polls)
     stage_queries(ix, c, query, 1, ws.h_q);
     const bool timed = ix->profiling;
     RLR_HIP(stage_queries_for_scans(ix, c, ws.h_q, static_cast<size_t>(ix->q_pitch) * sizeof(float), s));
-    uint64_t *d_meta = c->d_out + fetch;
+    uint64_t *d_meta = c->d_out.get() + fetch;
     const bool from_candidates = fetch <= 512; // (the band of a larger fetch rarely fits 1024)
-    const PoolArgs pa{fetch, need, n, w_embedding, w_lexical, c->d_list, ws.comb, ws.cos, ws.info};
+    const PoolArgs pa{fetch, need, n, w_embedding, w_lexical, c->d_list.get(), ws.comb, ws.cos, ws.info};
     bool pool_done = false; // (the fused tail's finish builds the pool itself: one launch and ~13 us of config 2's chain less)
-    RLR_HIP(enqueue_query(ix, c, 0, p, c->d_out, d_meta, timed, /*emit=*/!from_candidates, from_candidates ? &pa : nullptr,
+    RLR_HIP(enqueue_query(ix, c, 0, p, c->d_out.get(), d_meta, timed, /*emit=*/!from_candidates, from_candidates ? &pa : nullptr,
                           &pool_done));
     if (timed) RLR_HIP(hipEventRecord(c->bev[0], s));
     if (!pool_done) {
         if (from_candidates)
-            hipLaunchKernelGGL(rlr::pool_prepare_kernel<true>, dim3(1), dim3(1024), 0, s, c->d_packed, c->d_state, pa);
+            hipLaunchKernelGGL(rlr::pool_prepare_kernel<true>, dim3(1), dim3(1024), 0, s, c->d_packed.get(), c->d_state.get(), pa);
         else
-            hipLaunchKernelGGL(rlr::pool_prepare_kernel<false>, dim3(1), dim3(1024), 0, s, c->d_out, c->d_state, pa);
+            hipLaunchKernelGGL(rlr::pool_prepare_kernel<false>, dim3(1), dim3(1024), 0, s, c->d_out.get(), c->d_state.get(), pa);
         RLR_HIP(hipGetLastError());
     }
-    RLR_HIP(launch_gram_rows(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_list, P, ws.gram, 1, s));
-    const rlr::MmrEmit emit = mmr_emit(c->d_list, ws.comb, ws.cos, nullptr, ws.info, k_cap, h_out);
+    RLR_HIP(launch_gram_rows(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, c->d_list.get(), P, ws.gram, 1, s));
+    const rlr::MmrEmit emit = mmr_emit(c->d_list.get(), ws.comb, ws.cos, nullptr, ws.info, k_cap, h_out);
     RLR_HIP(launch_mmr_greedy(ws.gram, ws.comb, P, k, lambda, ws.order, ws.mmr, ws.nsel, ws.info, 1, s, &emit));
     if (timed) RLR_HIP(hipEventRecord(c->bev[1], s));
     if (timed)
@@ -3755,7 +3592,7 @@ struct HybridTicket {
     int32_t diversify;
     bool timed;
     // begin hands the lexical side of it to the BM25 kernels (LexSink), finish blends from the same object.  It points into
-    // c->d_pool and c->h_pin: the ticket holds the context's lease, and nothing may grow() / pin_reserve() on this context
+    // c->d_pool and c->h_pin: the ticket holds the context's lease, and nothing may reserve() / pin_reserve() on this context
     // between begin and finish.
     HybridWs ws;
     explicit HybridTicket(rlr_index *i) : ix(i), lease(i) {}
@@ -3799,10 +3636,10 @@ static int32_t hybrid_begin_impl(rlr_index *ix, const float *query, uint32_t nee
     const uint32_t P = need;
     const uint32_t k_cap = result_k_cap(k, P, diversify != 0);
     const HybridWs sizes(nullptr, nullptr, ix->q_pitch, P, n_lex_bound, k_cap);
-    RLR_TRY(grow(&c->d_pool, &c->pool_cap, sizes.d.floats()));
+    RLR_HIP(c->d_pool.reserve(sizes.d.floats()));
     RLR_TRY(reserve_list(c, P));
     RLR_TRY(pin_reserve(c, sizes.h.bytes));
-    t->ws = HybridWs(c->d_pool, c->h_pin, ix->q_pitch, P, n_lex_bound, k_cap);
+    t->ws = HybridWs(c->d_pool.get(), c->h_pin.get(), ix->q_pitch, P, n_lex_bound, k_cap);
     const HybridWs &ws = t->ws;
     t->n = n;
     t->need = need;
@@ -3817,7 +3654,7 @@ static int32_t hybrid_begin_impl(rlr_index *ix, const float *query, uint32_t nee
     stage_queries(ix, c, query, 1, ws.h_q);
     StreamDrain drain{s};
     RLR_HIP(stage_queries_for_scans(ix, c, ws.h_q, static_cast<size_t>(ix->q_pitch) * sizeof(float), s));
-    uint64_t *d_meta = c->d_out + fetch;
+    uint64_t *d_meta = c->d_out.get() + fetch;
     // the scan first; then whatever the caller runs beside it (the BM25 chain on its own stream: about as long as scan +
     // select + re-score + sort, so it must not wait for the host to have launched those -- it used to start 39 us behind the
     // scan and was the critical path by as much); then the four launches that wait for the scan anyway
@@ -3831,7 +3668,7 @@ static int32_t hybrid_begin_impl(rlr_index *ix, const float *query, uint32_t nee
         sink.n_index_rows = n;
         RLR_TRY(behind_scan(behind_scan_arg, &sink));
     }
-    RLR_HIP(enqueue_query_rest(ix, c, 0, p, c->d_out, d_meta, t->timed));
+    RLR_HIP(enqueue_query_rest(ix, c, 0, p, c->d_out.get(), d_meta, t->timed));
     if (t->timed) RLR_HIP(hipEventRecord(c->bev[0], s));
     drain.armed = false;
     *out = t.release();
@@ -3876,16 +3713,16 @@ static int32_t hybrid_finish_impl(HybridTicket *ticket, const HybridLexSrc &src,
             std::memcpy(HybridWs::h_lscore(h_lex, n_lex), src.h_scores, static_cast<size_t>(n_lex) * sizeof(float));
         RLR_HIP(hipMemcpyAsync(ws.hdr, h_lex, HybridWs::lex_copy_bytes(n_lex), hipMemcpyHostToDevice, s));
     }
-    RLR_HIP(launch_score_rows(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_query, ws.lrow, n_lex, ws.lcos, s,
+    RLR_HIP(launch_score_rows(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, c->d_query.get(), ws.lrow, n_lex, ws.lcos, s,
                               src.dev ? &ws.hdr->n_lex : nullptr, n));
     const bool pool_emits = !t->diversify; // (without diversification the blend kernel emits by itself)
-    hipLaunchKernelGGL(hybrid_pool_kernel, dim3(1), dim3(1024), 0, s, c->d_out, t->fetch, t->need, n, t->w_e, t->w_l, ws.lrow,
-                       d_lscore, ws.lcos, ws.hdr, ws.cand, c->d_list, ws.comb, ws.cos, ws.lexv, ws.info, k_cap,
+    hipLaunchKernelGGL(hybrid_pool_kernel, dim3(1), dim3(1024), 0, s, c->d_out.get(), t->fetch, t->need, n, t->w_e, t->w_l, ws.lrow,
+                       d_lscore, ws.lcos, ws.hdr, ws.cand, c->d_list.get(), ws.comb, ws.cos, ws.lexv, ws.info, k_cap,
                        pool_emits ? h_out : static_cast<uint32_t *>(nullptr));
     RLR_HIP(hipGetLastError());
     if (t->diversify) {
-        RLR_HIP(launch_gram_rows(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_list, P, ws.gram, 1, s));
-        const MmrEmit emit = mmr_emit(c->d_list, ws.comb, ws.cos, ws.lexv, ws.info, k_cap, h_out);
+        RLR_HIP(launch_gram_rows(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, c->d_list.get(), P, ws.gram, 1, s));
+        const MmrEmit emit = mmr_emit(c->d_list.get(), ws.comb, ws.cos, ws.lexv, ws.info, k_cap, h_out);
         RLR_HIP(launch_mmr_greedy(ws.gram, ws.comb, P, t->k, t->lambda, ws.order, ws.mmr, ws.nsel, ws.info, 1, s, &emit));
     }
     if (t->timed) RLR_HIP(hipEventRecord(c->bev[1], s));
@@ -3967,8 +3804,8 @@ int32_t search_hybrid_batch(rlr_index *ix, const float *queries, uint32_t nq, ui
     const uint32_t P = need, B = n_lex_bound;
     const uint32_t k_cap = result_k_cap(k, P, diversify != 0);
     const uint64_t Q = nq;
-    RLR_TRY(grow(&c->d_pool, &c->pool_cap, HybridBatchWs(nullptr, ix, Q, fetch, P, B, diversify != 0).d.floats()));
-    const HybridBatchWs ws(c->d_pool, ix, Q, fetch, P, B, diversify != 0);
+    RLR_HIP(c->d_pool.reserve(HybridBatchWs(nullptr, ix, Q, fetch, P, B, diversify != 0).d.floats()));
+    const HybridBatchWs ws(c->d_pool.get(), ix, Q, fetch, P, B, diversify != 0);
     // whatever goes wrong from here on: the BM25 chain (another stream, writing into this workspace) and this stream must
     // be drained before the context goes back
     StreamDrain drain{s};
@@ -3994,7 +3831,7 @@ int32_t search_hybrid_batch(rlr_index *ix, const float *queries, uint32_t nq, ui
     // copy is the one place every path leaves them; Q x fetch x 8 bytes each way)
     std::vector<uint64_t> fetched(h, h + Q * fetch); // (the pinned buffer is re-laid out below)
     RLR_TRY(pin_reserve(c, HybridBatchPin(nullptr, ix, Q, fetch, P).h.bytes));
-    const HybridBatchPin pin(c->h_pin, ix, Q, fetch, P);
+    const HybridBatchPin pin(c->h_pin.get(), ix, Q, fetch, P);
     const size_t b_packed = Q * fetch * sizeof(uint64_t), b_q = Q * ix->q_pitch * sizeof(float);
     std::memcpy(pin.packed, fetched.data(), b_packed);
     pad_queries(ix, queries, nq, pin.q);
@@ -4002,7 +3839,7 @@ int32_t search_hybrid_batch(rlr_index *ix, const float *queries, uint32_t nq, ui
     RLR_HIP(hipMemcpyAsync(ws.q, pin.q, b_q, hipMemcpyHostToDevice, s));
     // 3. join the BM25 chain; exact cosines of the lexical rows, blend, order, cut -- one workgroup per query
     RLR_HIP(hipStreamWaitEvent(s, static_cast<hipEvent_t>(ready), 0));
-    RLR_HIP(launch_score_rows_batch(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, ws.q, ix->q_pitch, nq, ws.lrow, B, ws.lcos,
+    RLR_HIP(launch_score_rows_batch(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, ws.q, ix->q_pitch, nq, ws.lrow, B, ws.lcos,
                                     reinterpret_cast<const uint32_t *>(ws.hdr), 2, n, s));
     const HybridBatchRes &d = ws.res, &r = pin.res;
     hipLaunchKernelGGL(hybrid_pool_batch_kernel, dim3(nq), dim3(1024), 0, s, ws.packed, fetch, P, n, w_embedding, w_lexical, B,
@@ -4010,7 +3847,7 @@ int32_t search_hybrid_batch(rlr_index *ix, const float *queries, uint32_t nq, ui
     RLR_HIP(hipGetLastError());
     // 4. MMR over every pool at once
     if (diversify) {
-        RLR_HIP(launch_gram_rows(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, d.list, P, ws.gram, nq, s));
+        RLR_HIP(launch_gram_rows(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, d.list, P, ws.gram, nq, s));
         RLR_HIP(launch_mmr_greedy(ws.gram, d.comb, P, k, lambda, d.order, d.mmr, d.nsel, d.sizes, nq, s));
     }
     RLR_HIP(hipMemcpyAsync(r.list, d.list, HybridBatchRes::words(Q, P) * 4, hipMemcpyDeviceToHost, s));
@@ -4120,9 +3957,9 @@ static int32_t mmr_batch_impl(rlr_index *ix, const uint64_t *pool_rows, const fl
             }
             RLR_TRY(upload_list(ix, c, src_rows, n_list, d_matrix ? n_matrix : ~0ull));
         }
-        RLR_TRY(grow(&c->d_pool, &c->pool_cap, MmrWs(nullptr, m, P).d.floats()));
-        const MmrWs ws(c->d_pool, m, P);
-        const MmrStaging h(c->h_pin, m, P);
+        RLR_HIP(c->d_pool.reserve(MmrWs(nullptr, m, P).d.floats()));
+        const MmrWs ws(c->d_pool.get(), m, P);
+        const MmrStaging h(c->h_pin.get(), m, P);
         std::memcpy(h.scores, pool_scores + static_cast<size_t>(q0) * P, static_cast<size_t>(n_list) * sizeof(float));
         std::memcpy(h.sizes, pool_sizes + q0, m * sizeof(uint32_t));
         RLR_HIP(hipMemcpyAsync(ws.scores, h.scores, static_cast<size_t>(n_list) * sizeof(float), hipMemcpyHostToDevice, s));
@@ -4130,7 +3967,7 @@ static int32_t mmr_batch_impl(rlr_index *ix, const uint64_t *pool_rows, const fl
         const bool timed = ix->profiling;
         if (timed) RLR_HIP(hipEventRecord(c->ev[0], s));
         if (pool_rows) // the Gram kernel reads the index rows through the list: no gathered copy
-            RLR_HIP(launch_gram_rows(d_matrix ? d_matrix : ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_list, P, ws.gram, m, s));
+            RLR_HIP(launch_gram_rows(d_matrix ? d_matrix : ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, c->d_list.get(), P, ws.gram, m, s));
         else
             RLR_HIP(launch_gram(d_values + static_cast<size_t>(q0) * P * ix->dim, P, ix->dim, ws.gram, m, s));
         RLR_HIP(launch_mmr_greedy(ws.gram, ws.scores, P, k, lambda, ws.res.order, ws.res.mmr, ws.res.n, ws.sizes, m, s));
@@ -4203,7 +4040,7 @@ int32_t rlr_gather_rows_device(rlr_index *ix, const uint64_t *rows, uint32_t n, 
     RLR_TRY(ctx_acquire(ix, &lease.c));
     Ctx *c = lease.c;
     RLR_TRY(upload_list(ix, c, rows, n));
-    RLR_HIP(launch_compact_rows(ix->d_rows, d_out, ix->pitch16, c->d_list, n, c->stream));
+    RLR_HIP(launch_compact_rows(ix->d_rows.get(), d_out, ix->pitch16, c->d_list.get(), n, c->stream));
     RLR_HIP(hipStreamSynchronize(c->stream));
     return RLR_OK;
 }
@@ -4220,7 +4057,7 @@ int32_t rlr_fetch_rows_device(rlr_index *ix, const uint64_t *rows, uint32_t n, v
     RLR_TRY(ctx_acquire(ix, &lease.c));
     Ctx *c = lease.c;
     RLR_TRY(upload_list(ix, c, rows, n));
-    RLR_HIP(launch_gather_f32(ix->d_rows, ix->pitch16, ix->dim, ix->dtype, c->d_list, n, static_cast<float *>(d_out), c->stream));
+    RLR_HIP(launch_gather_f32(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, c->d_list.get(), n, static_cast<float *>(d_out), c->stream));
     RLR_HIP(hipStreamSynchronize(c->stream));
     return RLR_OK;
 }
@@ -4242,7 +4079,7 @@ int32_t rlr_index_probe_bandwidth(rlr_index *ix, int32_t mode, uint32_t reps, do
     RLR_TRY(ctx_acquire(ix, &lease.c));
     Ctx *c = lease.c;
     hipStream_t s = c->stream;
-    void *scratch = nullptr;
+    DevBuf<uint8_t> scratch_buf;
     int32_t st = RLR_OK;
     double best_ms = 0.0;
     size_t moved = 0;
@@ -4261,15 +4098,17 @@ int32_t rlr_index_probe_bandwidth(rlr_index *ix, int32_t mode, uint32_t reps, do
         return RLR_OK;
     };
     if (mode == 0) {
-        RLR_HIP(rlr::dev_malloc(&scratch, static_cast<size_t>(ix->n_cu) * 8 * 256 * sizeof(float)));
+        RLR_HIP(scratch_buf.reserve(static_cast<size_t>(ix->n_cu) * 8 * 256 * sizeof(float)));
+        void *const scratch = scratch_buf.get();
         moved = bytes / 1024 * 1024;
         for (int shape = 0; shape < 3 && st == RLR_OK; ++shape)
-            st = timed([&] { return launch_probe_read(ix->d_rows, bytes, static_cast<float *>(scratch), ix->n_cu, shape, s); });
+            st = timed([&] { return launch_probe_read(ix->d_rows.get(), bytes, static_cast<float *>(scratch), ix->n_cu, shape, s); });
     } else if (mode >= 2) {
         // diagnostic: the scan kernel itself over the rows with a zero query, scores into a scratch array, without (2) or
         // with (3) the digit-1 histogram it accumulates in LDS and flushes with global atomics
         const size_t sc_bytes = (static_cast<size_t>(ix->n_rows) + 2 * kHistBins + ix->q_pitch) * sizeof(float);
-        RLR_HIP(rlr::dev_malloc(&scratch, sc_bytes));
+        RLR_HIP(scratch_buf.reserve(sc_bytes));
+        void *const scratch = scratch_buf.get();
         RLR_HIP(hipMemsetAsync(scratch, 0, sc_bytes, s));
         float *sc = static_cast<float *>(scratch);
         const ScanArgs sa = scan_args(ix, sc + ix->n_rows + 2 * kHistBins, sc,
@@ -4278,14 +4117,13 @@ int32_t rlr_index_probe_bandwidth(rlr_index *ix, int32_t mode, uint32_t reps, do
         st = timed([&] { return launch_scan(sa, s); });
     } else {
         const size_t half = std::min<size_t>(bytes / 2, 4ull << 30) & ~static_cast<size_t>(255);
-        hipError_t e = rlr::dev_malloc(&scratch, half);
-        if (e != hipSuccess)
+        if (scratch_buf.reserve(half) != hipSuccess)
             return fail(RLR_E_OOM, "scratch allocation of %zu bytes for the copy probe failed", half);
+        void *const scratch = scratch_buf.get();
         moved = 2 * half;
-        st = timed([&] { return hipMemcpyAsync(scratch, ix->d_rows, half, hipMemcpyDeviceToDevice, s); });
+        st = timed([&] { return hipMemcpyAsync(scratch, ix->d_rows.get(), half, hipMemcpyDeviceToDevice, s); });
     }
     (void)hipStreamSynchronize(s);
-    (void)hipFree(scratch);
     if (st != RLR_OK)
         return st;
     *gbps_out = static_cast<double>(moved) / (best_ms * 1e-3) / 1e9;
@@ -4349,7 +4187,7 @@ int32_t filter_view(const rlr_filter *f, FilterView *out)
         return fail(RLR_E_INVALID, "null filter handle");
     RLR_TRY(check_filter(f->ix, f));
     out->h_mask = f->h_mask.data();
-    out->d_mask = f->d_mask;
+    out->d_mask = f->d_mask.get();
     out->index_rows = f->index_rows;
     out->n_allowed = f->n_allowed;
     out->device = f->ix->device;

@@ -25,6 +25,7 @@
 // sum(df) postings x 8 B.
 #include "../../include/rlr_lexical.h"
 #include "common.h"
+#include "device_buffer.h"
 #include "kernels.h"
 #include "lds_select.h"
 #include "lexical_internal.h"
@@ -959,22 +960,18 @@ __global__ __launch_bounds__(256) void lex_batch_collect_kernel(const BatchQuery
     lex_collect_body(keys + bq[blockIdx.y].key_off, ctl, limit, sel + static_cast<uint64_t>(blockIdx.y) * limit, limit);
 }
 
+// room for `need` elements, 1024 at the least; zero: a new buffer is cleared
 template <typename T>
-int32_t dev_grow(T **p, uint64_t *cap, uint64_t need, bool zero = false)
+int32_t dev_grow(DevBuf<T> &b, uint64_t need, bool zero = false)
 {
-    if (*cap >= need && *p)
+    if (b && b.capacity() >= need)
         return RLR_OK;
-    if (*p)
-        (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
     const uint64_t n = std::max<uint64_t>(need, 1024);
-    LEX_HIP(rlr::dev_malloc(reinterpret_cast<void **>(p), n * sizeof(T)));
+    LEX_HIP(b.reserve(n));
     if (zero) { // null stream, then wait: the scoring stream is non-blocking and not ordered against it
-        LEX_HIP(hipMemset(*p, 0, n * sizeof(T)));
+        LEX_HIP(hipMemset(b.get(), 0, n * sizeof(T)));
         LEX_HIP(hipStreamSynchronize(nullptr));
     }
-    *cap = n;
     return RLR_OK;
 }
 
@@ -1000,23 +997,18 @@ void split_tokens(const char *s, size_t len, std::vector<std::string> *out)
 struct LexWorkspace {
     hipStream_t stream = nullptr;
     hipEvent_t ready = nullptr; // recorded behind a call's last kernel (consumers on other streams wait on it)
-    float *d_scores = nullptr; // one f32 per row, all zero between calls
-    uint64_t scores_cap = 0;
-    uint32_t *d_touched = nullptr;
-    uint64_t touched_cap = 0;
-    uint64_t *d_keys = nullptr;
-    uint64_t keys_cap = 0;
-    uint64_t *d_sel = nullptr;
-    LexControl *d_ctl = nullptr; // TWO control blocks: a call works in d_ctl[ctl_cur] and its clean-up launch (behind `ready`, off
+    DevBuf<float> d_scores; // one f32 per row, all zero between calls
+    DevBuf<uint32_t> d_touched;
+    DevBuf<uint64_t> d_keys, d_sel;
+    DevBuf<LexControl> d_ctl;    // TWO control blocks: a call works in d_ctl[ctl_cur] and its clean-up launch (behind `ready`, off
                                  // the critical path) zeroes the other one for the next call -- it was a launch in front of every call
     uint32_t ctl_cur = 0;
-    uint64_t *d_out = nullptr; // kMaxLimit keys + count
-    uint64_t *h_out = nullptr; // pinned mirror
+    DevBuf<uint64_t> d_out;    // kMaxLimit keys + count
+    PinBuf h_out;              // pinned mirror
     bool dirty = false;        // a call failed after enqueuing work: accumulators / control may be non-zero
     // batched calls (lexical_batch_enqueue): term table, keys of every query, per-query control blocks and results
-    uint64_t *d_btab = nullptr, *d_bkeys = nullptr, *d_bsel = nullptr;
-    uint64_t btab_cap = 0, bkeys_cap = 0, bsel_cap = 0, bctl_cap = 0;
-    LexControl *d_bctl = nullptr;
+    DevBuf<uint64_t> d_btab, d_bkeys, d_bsel;
+    DevBuf<LexControl> d_bctl;
 };
 
 constexpr int kMaxWorkspaces = 8; // callers beyond this wait for a free one
@@ -1046,11 +1038,9 @@ struct rlr_lexical {
     std::vector<uint32_t> main_df; // documents per term inside MAIN (terms born later: beyond its end, 0)
     // ---- device CSR
     std::vector<uint64_t> term_off, dterm_off; // MAIN / DELTA offsets by term
-    uint32_t *d_post_row = nullptr, *d_post_tf = nullptr, *d_doc_len = nullptr;
-    uint32_t *d_dpost_row = nullptr, *d_dpost_tf = nullptr;
-    uint64_t post_cap = 0, post_tf_cap = 0, doc_cap = 0, dpost_cap = 0, dpost_tf_cap = 0;
-    uint32_t *d_remap = nullptr, *d_blocks = nullptr; // row removal on the device: old row -> new row, block counts
-    uint64_t remap_cap = 0, blocks_cap = 0;
+    DevBuf<uint32_t> d_post_row, d_post_tf, d_doc_len;
+    DevBuf<uint32_t> d_dpost_row, d_dpost_tf;
+    DevBuf<uint32_t> d_remap, d_blocks; // row removal on the device: old row -> new row, block counts
     uint64_t n_device_removals = 0;
     // ---- per-call workspaces
     std::mutex ws_mu;
@@ -1094,13 +1084,7 @@ void workspace_destroy(LexWorkspace *ws)
     }
     if (ws->ready)
         (void)hipEventDestroy(ws->ready);
-    void *dev[] = {ws->d_scores, ws->d_touched, ws->d_keys, ws->d_sel, ws->d_ctl, ws->d_out, ws->d_btab, ws->d_bkeys, ws->d_bsel, ws->d_bctl};
-    for (void *p : dev)
-        if (p)
-            (void)hipFree(p);
-    if (ws->h_out)
-        (void)hipHostFree(ws->h_out);
-    delete ws;
+    delete ws; // (the buffers free themselves)
 }
 
 int32_t workspace_create(LexWorkspace **out)
@@ -1112,15 +1096,15 @@ int32_t workspace_create(LexWorkspace **out)
     if (e == hipSuccess)
         e = hipEventCreateWithFlags(&ws->ready, hipEventDisableTiming);
     if (e == hipSuccess)
-        e = rlr::dev_malloc(reinterpret_cast<void **>(&ws->d_ctl), 2 * sizeof(LexControl));
+        e = ws->d_ctl.reserve(2);
     if (e == hipSuccess)
-        e = hipMemsetAsync(ws->d_ctl, 0, 2 * sizeof(LexControl), ws->stream); // ordered before every call on this stream
+        e = hipMemsetAsync(ws->d_ctl.get(), 0, 2 * sizeof(LexControl), ws->stream); // ordered before every call on this stream
     if (e == hipSuccess)
-        e = rlr::dev_malloc(reinterpret_cast<void **>(&ws->d_sel), kMaxLimit * sizeof(uint64_t));
+        e = ws->d_sel.reserve(kMaxLimit);
     if (e == hipSuccess)
-        e = rlr::dev_malloc(reinterpret_cast<void **>(&ws->d_out), (kMaxLimit + 1) * sizeof(uint64_t));
+        e = ws->d_out.reserve(kMaxLimit + 1);
     if (e == hipSuccess)
-        e = hipHostMalloc(reinterpret_cast<void **>(&ws->h_out), (kMaxLimit + 1) * sizeof(uint64_t), hipHostMallocDefault);
+        e = ws->h_out.reserve((kMaxLimit + 1) * sizeof(uint64_t));
     if (e != hipSuccess) {
         workspace_destroy(ws);
         return set_error(e == hipErrorOutOfMemory ? RLR_E_OOM : RLR_E_HIP, "lexical workspace setup failed: %s",
@@ -1171,15 +1155,15 @@ int32_t commit_full(rlr_lexical *lx)
             rows[at] = static_cast<uint32_t>(r);
             tfs[at] = tc.second;
         }
-    LEX_TRY(dev_grow(&lx->d_post_row, &lx->post_cap, total));
-    LEX_TRY(dev_grow(&lx->d_post_tf, &lx->post_tf_cap, total));
-    LEX_TRY(dev_grow(&lx->d_doc_len, &lx->doc_cap, n_rows + n_rows / 4)); // headroom: appends upload only their part
+    LEX_TRY(dev_grow(lx->d_post_row, total));
+    LEX_TRY(dev_grow(lx->d_post_tf, total));
+    LEX_TRY(dev_grow(lx->d_doc_len, n_rows + n_rows / 4)); // headroom: appends upload only their part
     if (total) {
-        LEX_HIP(hipMemcpy(lx->d_post_row, rows.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice));
-        LEX_HIP(hipMemcpy(lx->d_post_tf, tfs.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice));
+        LEX_HIP(hipMemcpy(lx->d_post_row.get(), rows.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice));
+        LEX_HIP(hipMemcpy(lx->d_post_tf.get(), tfs.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     if (n_rows)
-        LEX_HIP(hipMemcpy(lx->d_doc_len, lx->doc_len.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice));
+        LEX_HIP(hipMemcpy(lx->d_doc_len.get(), lx->doc_len.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice));
     lx->main_rows = n_rows;
     lx->main_postings = total;
     lx->main_df = lx->df;
@@ -1209,17 +1193,17 @@ int32_t commit_delta(rlr_lexical *lx)
             rows[at] = static_cast<uint32_t>(r);
             tfs[at] = tc.second;
         }
-    LEX_TRY(dev_grow(&lx->d_dpost_row, &lx->dpost_cap, total + total / 2));
-    LEX_TRY(dev_grow(&lx->d_dpost_tf, &lx->dpost_tf_cap, total + total / 2));
+    LEX_TRY(dev_grow(lx->d_dpost_row, total + total / 2));
+    LEX_TRY(dev_grow(lx->d_dpost_tf, total + total / 2));
     if (total) {
-        LEX_HIP(hipMemcpy(lx->d_dpost_row, rows.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice));
-        LEX_HIP(hipMemcpy(lx->d_dpost_tf, tfs.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice));
+        LEX_HIP(hipMemcpy(lx->d_dpost_row.get(), rows.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice));
+        LEX_HIP(hipMemcpy(lx->d_dpost_tf.get(), tfs.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
-    if (n_rows > lx->doc_cap || !lx->d_doc_len) { // outgrew the headroom: new buffer, every length again
-        LEX_TRY(dev_grow(&lx->d_doc_len, &lx->doc_cap, n_rows + n_rows / 4));
-        LEX_HIP(hipMemcpy(lx->d_doc_len, lx->doc_len.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (n_rows > lx->d_doc_len.capacity() || !lx->d_doc_len) { // outgrew the headroom: new buffer, every length again
+        LEX_TRY(dev_grow(lx->d_doc_len, n_rows + n_rows / 4));
+        LEX_HIP(hipMemcpy(lx->d_doc_len.get(), lx->doc_len.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice));
     } else if (n_rows > lx->main_rows) {
-        LEX_HIP(hipMemcpy(lx->d_doc_len + lx->main_rows, lx->doc_len.data() + lx->main_rows,
+        LEX_HIP(hipMemcpy(lx->d_doc_len.get() + lx->main_rows, lx->doc_len.data() + lx->main_rows,
                           (n_rows - lx->main_rows) * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     lx->delta_postings = total;
@@ -1241,38 +1225,29 @@ int32_t commit(rlr_lexical *lx)
 
 // Bring both posting segments, the per-term offsets and the document lengths in line with a removal the host state has
 // already absorbed.  remap: old row -> new row (kDeadRow: removed).  Caller holds the index exclusively.
-int32_t compact_segment(rlr_lexical *lx, uint32_t **rows, uint32_t **tfs, uint64_t *cap_rows, uint64_t *cap_tfs, uint64_t total,
-                        uint64_t new_total)
+int32_t compact_segment(rlr_lexical *lx, DevBuf<uint32_t> &rows, DevBuf<uint32_t> &tfs, uint64_t total, uint64_t new_total)
 {
     if (total == 0)
         return RLR_OK;
     const uint32_t nb = static_cast<uint32_t>((total + kCsrBlock - 1) / kCsrBlock);
-    LEX_TRY(dev_grow(&lx->d_blocks, &lx->blocks_cap, nb));
-    uint32_t *out_rows = nullptr, *out_tfs = nullptr;
+    LEX_TRY(dev_grow(lx->d_blocks, nb));
+    DevBuf<uint32_t> out_rows, out_tfs;
     const uint64_t cap = std::max<uint64_t>(new_total + new_total / 8, 1024);
-    LEX_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&out_rows), cap * sizeof(uint32_t)));
-    hipError_t e = rlr::dev_malloc(reinterpret_cast<void **>(&out_tfs), cap * sizeof(uint32_t));
-    if (e != hipSuccess) {
-        (void)hipFree(out_rows);
+    LEX_HIP(out_rows.reserve(cap));
+    hipError_t e = out_tfs.reserve(cap);
+    if (e != hipSuccess)
         return set_error(RLR_E_OOM, "lexical compaction: %s", hipGetErrorString(e));
-    }
-    hipLaunchKernelGGL(csr_count_kernel, dim3(nb), dim3(256), 0, nullptr, *rows, total, lx->d_remap, lx->d_blocks);
-    hipLaunchKernelGGL(csr_scan_kernel, dim3(1), dim3(1024), 0, nullptr, lx->d_blocks, nb);
-    hipLaunchKernelGGL(csr_scatter_kernel, dim3(nb), dim3(256), 0, nullptr, *rows, *tfs, total, lx->d_remap, lx->d_blocks, out_rows,
-                       out_tfs);
+    hipLaunchKernelGGL(csr_count_kernel, dim3(nb), dim3(256), 0, nullptr, rows.get(), total, lx->d_remap.get(), lx->d_blocks.get());
+    hipLaunchKernelGGL(csr_scan_kernel, dim3(1), dim3(1024), 0, nullptr, lx->d_blocks.get(), nb);
+    hipLaunchKernelGGL(csr_scatter_kernel, dim3(nb), dim3(256), 0, nullptr, rows.get(), tfs.get(), total, lx->d_remap.get(),
+                       lx->d_blocks.get(), out_rows.get(), out_tfs.get());
     e = hipGetLastError();
     if (e == hipSuccess)
         e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        (void)hipFree(out_rows);
-        (void)hipFree(out_tfs);
+    if (e != hipSuccess)
         return set_error(RLR_E_HIP, "lexical compaction failed: %s", hipGetErrorString(e));
-    }
-    (void)hipFree(*rows);
-    (void)hipFree(*tfs);
-    *rows = out_rows;
-    *tfs = out_tfs;
-    *cap_rows = *cap_tfs = cap;
+    rows = std::move(out_rows); // (frees the old segment)
+    tfs = std::move(out_tfs);
     return RLR_OK;
 }
 
@@ -1280,12 +1255,11 @@ int32_t remove_on_device(rlr_lexical *lx, const std::vector<uint32_t> &remap, ui
                          uint64_t dead_delta_postings)
 {
     LEX_HIP(hipSetDevice(lx->device));
-    LEX_TRY(dev_grow(&lx->d_remap, &lx->remap_cap, remap.size()));
-    LEX_HIP(hipMemcpy(lx->d_remap, remap.data(), remap.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    LEX_TRY(dev_grow(lx->d_remap, remap.size()));
+    LEX_HIP(hipMemcpy(lx->d_remap.get(), remap.data(), remap.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     const uint64_t new_main = lx->main_postings - dead_main_postings, new_delta = lx->delta_postings - dead_delta_postings;
-    LEX_TRY(compact_segment(lx, &lx->d_post_row, &lx->d_post_tf, &lx->post_cap, &lx->post_tf_cap, lx->main_postings, new_main));
-    LEX_TRY(compact_segment(lx, &lx->d_dpost_row, &lx->d_dpost_tf, &lx->dpost_cap, &lx->dpost_tf_cap, lx->delta_postings,
-                            new_delta));
+    LEX_TRY(compact_segment(lx, lx->d_post_row, lx->d_post_tf, lx->main_postings, new_main));
+    LEX_TRY(compact_segment(lx, lx->d_dpost_row, lx->d_dpost_tf, lx->delta_postings, new_delta));
     // per-term offsets from the counts the host keeps (the compaction preserved the order inside every posting list)
     const size_t n_terms = lx->df.size();
     lx->main_df.resize(n_terms, 0);
@@ -1303,10 +1277,10 @@ int32_t remove_on_device(rlr_lexical *lx, const std::vector<uint32_t> &remap, ui
     lx->main_postings = new_main;
     lx->delta_postings = new_delta;
     const uint64_t n_rows = lx->doc_terms.size();
-    if (n_rows > lx->doc_cap || !lx->d_doc_len)
-        LEX_TRY(dev_grow(&lx->d_doc_len, &lx->doc_cap, n_rows + n_rows / 4));
+    if (n_rows > lx->d_doc_len.capacity() || !lx->d_doc_len)
+        LEX_TRY(dev_grow(lx->d_doc_len, n_rows + n_rows / 4));
     if (n_rows)
-        LEX_HIP(hipMemcpy(lx->d_doc_len, lx->doc_len.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice));
+        LEX_HIP(hipMemcpy(lx->d_doc_len.get(), lx->doc_len.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice));
     lx->n_device_removals++;
     return RLR_OK;
 }
@@ -1364,11 +1338,7 @@ void rlr_lexical_destroy(rlr_lexical *lx)
     (void)hipSetDevice(lx->device);
     for (LexWorkspace *ws : lx->ws_free) // every call has returned (the caller's contract), so all of them are here
         workspace_destroy(ws);
-    void *dev[] = {lx->d_post_row, lx->d_post_tf, lx->d_doc_len, lx->d_dpost_row, lx->d_dpost_tf, lx->d_remap, lx->d_blocks};
-    for (void *p : dev)
-        if (p)
-            (void)hipFree(p);
-    delete lx;
+    delete lx; // (the posting segments free themselves)
 }
 
 int32_t rlr_lexical_add_chunk(rlr_lexical *lx, uint64_t row, const char *tokens, size_t len)
@@ -1734,19 +1704,19 @@ static int32_t lexical_enqueue_masked(rlr_lexical *lx, const char *query_tokens,
     LEX_TRY(workspace_acquire(lx, &ws));
     out->ws = ws;
     const uint64_t n_rows = lx->doc_terms.size();
-    if (ws->scores_cap < n_rows || !ws->d_scores) { // the index grew since this workspace last ran
+    if (ws->d_scores.capacity() < n_rows || !ws->d_scores) { // the index grew since this workspace last ran
         LEX_HIP(hipStreamSynchronize(ws->stream));
-        LEX_TRY(dev_grow(&ws->d_scores, &ws->scores_cap, n_rows + n_rows / 4, /*zero=*/true));
+        LEX_TRY(dev_grow(ws->d_scores, n_rows + n_rows / 4, /*zero=*/true));
         ws->dirty = false;
-        LEX_HIP(hipMemsetAsync(ws->d_ctl, 0, 2 * sizeof(LexControl), ws->stream));
+        LEX_HIP(hipMemsetAsync(ws->d_ctl.get(), 0, 2 * sizeof(LexControl), ws->stream));
     }
     if (ws->dirty) { // restore the all-zero invariant a failed call may have broken
         LEX_HIP(hipStreamSynchronize(ws->stream));
-        LEX_HIP(hipMemsetAsync(ws->d_scores, 0, ws->scores_cap * sizeof(float), ws->stream));
-        LEX_HIP(hipMemsetAsync(ws->d_ctl, 0, 2 * sizeof(LexControl), ws->stream));
+        LEX_HIP(hipMemsetAsync(ws->d_scores.get(), 0, ws->d_scores.capacity() * sizeof(float), ws->stream));
+        LEX_HIP(hipMemsetAsync(ws->d_ctl.get(), 0, 2 * sizeof(LexControl), ws->stream));
         ws->dirty = false;
     }
-    LEX_TRY(dev_grow(&ws->d_touched, &ws->touched_cap, upper));
+    LEX_TRY(dev_grow(ws->d_touched, upper));
 
     const float n_docs = static_cast<float>(lx->total_docs);
     const float avg = static_cast<float>(lx->total_length) / n_docs; // :2184-2188
@@ -1756,8 +1726,8 @@ static int32_t lexical_enqueue_masked(rlr_lexical *lx, const char *query_tokens,
     // memsets above) saw to that -- and readable for a consumer on another stream until the workspace is handed back: the
     // next call works in the other block and zeroes this one only behind its own `ready`.
     static_assert(sizeof(LexControl) % 4 == 0, "cleared as 32-bit words");
-    LexControl *ctl = ws->d_ctl + ws->ctl_cur;
-    LexControl *ctl_next = ws->d_ctl + (ws->ctl_cur ^ 1u);
+    LexControl *ctl = ws->d_ctl.get() + ws->ctl_cur;
+    LexControl *ctl_next = ws->d_ctl.get() + (ws->ctl_cur ^ 1u);
     ws->ctl_cur ^= 1u;
     const uint32_t max_blocks = static_cast<uint32_t>(lx->n_cu) * 8;
     // workgroups of the row-partitioned kernel: one per CU while each still owns a few hundred rows
@@ -1771,8 +1741,8 @@ static int32_t lexical_enqueue_masked(rlr_lexical *lx, const char *query_tokens,
     const bool terms_lds = !lx->terms_global && (n_rows + lds_wgs - 1) / lds_wgs + 1 <= kLdsRows;
     auto flush_terms = [&]() {
 #define RLR_LEX_TERMS_ARGS                                                                                                   \
-    tb, lx->d_post_row, lx->d_post_tf, lx->d_dpost_row, lx->d_dpost_tf, lx->d_doc_len, static_cast<uint32_t>(n_rows), avg,      \
-        ws->d_scores, ws->d_touched, ctl, d_mask, mask_rows
+    tb, lx->d_post_row.get(), lx->d_post_tf.get(), lx->d_dpost_row.get(), lx->d_dpost_tf.get(), lx->d_doc_len.get(), static_cast<uint32_t>(n_rows), avg,      \
+        ws->d_scores.get(), ws->d_touched.get(), ctl, d_mask, mask_rows
         if (tb.n_terms && terms_lds && d_mask)
             hipLaunchKernelGGL(bm25_terms_lds_kernel<true>, dim3(lds_wgs), dim3(256), 0, s, RLR_LEX_TERMS_ARGS);
         else if (tb.n_terms && terms_lds)
@@ -1802,13 +1772,13 @@ static int32_t lexical_enqueue_masked(rlr_lexical *lx, const char *query_tokens,
     }
     flush_terms();
     LEX_HIP(hipGetLastError());
-    uint32_t *d_out_n = reinterpret_cast<uint32_t *>(ws->d_out + kMaxLimit);
+    uint32_t *d_out_n = reinterpret_cast<uint32_t *>(ws->d_out.get() + kMaxLimit);
     const uint32_t blocks_u = std::min<uint32_t>(static_cast<uint32_t>((upper + 255) / 256), max_blocks);
-    const uint64_t *d_result = ws->d_out;
+    const uint64_t *d_result = ws->d_out.get();
     const uint32_t *d_result_n = d_out_n;
     if (upper <= kMaxLimit) {
-        hipLaunchKernelGGL(lex_sort_kernel<true>, dim3(1), dim3(1024), 0, s, ws->d_scores, ws->d_touched, nullptr, ctl,
-                           lim, ws->d_out, d_out_n);
+        hipLaunchKernelGGL(lex_sort_kernel<true>, dim3(1), dim3(1024), 0, s, ws->d_scores.get(), ws->d_touched.get(), nullptr, ctl,
+                           lim, ws->d_out.get(), d_out_n);
     } else if (!exact_passes && lim <= kFastLimitMax && sampled_candidates(lim, upper, kSampleMax) <= 6000.0) {
         // (beyond ~3 M touched documents even the 8192-entry sample is too coarse for the 8192-entry candidate list)
         // 4096 sample keys while that keeps the list short: half the gathers and LDS work of the sample launch for ~15 % more
@@ -1822,27 +1792,27 @@ static int32_t lexical_enqueue_masked(rlr_lexical *lx, const char *query_tokens,
         while (row_bits < 32 && (n_rows - 1) >> row_bits)
             ++row_bits;
         static const uint32_t r_forced = getenv("RLR_LEX_SAMPLE_RANK") ? static_cast<uint32_t>(atoi(getenv("RLR_LEX_SAMPLE_RANK"))) : 0u;
-        hipLaunchKernelGGL(lex_sample_kernel, dim3(1), dim3(1024), 0, s, ws->d_scores, ws->d_touched, ctl, lim, r_forced, row_bits,
+        hipLaunchKernelGGL(lex_sample_kernel, dim3(1), dim3(1024), 0, s, ws->d_scores.get(), ws->d_touched.get(), ctl, lim, r_forced, row_bits,
                            sample_log2);
-        hipLaunchKernelGGL(lex_filter_kernel, dim3(blocks_u), dim3(256), 0, s, ws->d_scores, ws->d_touched, ctl, ws->d_sel);
+        hipLaunchKernelGGL(lex_filter_kernel, dim3(blocks_u), dim3(256), 0, s, ws->d_scores.get(), ws->d_touched.get(), ctl, ws->d_sel.get());
         if (need_sorted)
-            hipLaunchKernelGGL(lex_final_kernel<true>, dim3(1), dim3(1024), 0, s, ws->d_sel, ctl, lim, ws->d_out, d_out_n, row_bits);
+            hipLaunchKernelGGL(lex_final_kernel<true>, dim3(1), dim3(1024), 0, s, ws->d_sel.get(), ctl, lim, ws->d_out.get(), d_out_n, row_bits);
         else
-            hipLaunchKernelGGL(lex_final_kernel<false>, dim3(1), dim3(1024), 0, s, ws->d_sel, ctl, lim, ws->d_out, d_out_n, row_bits);
+            hipLaunchKernelGGL(lex_final_kernel<false>, dim3(1), dim3(1024), 0, s, ws->d_sel.get(), ctl, lim, ws->d_out.get(), d_out_n, row_bits);
         out->may_retry = true;
     } else {
-        LEX_TRY(dev_grow(&ws->d_keys, &ws->keys_cap, upper));
-        hipLaunchKernelGGL(lex_select_pass_kernel<true>, dim3(blocks_u), dim3(256), 0, s, ws->d_keys, ctl, lim, 0,
-                           ws->d_scores, ws->d_touched);
+        LEX_TRY(dev_grow(ws->d_keys, upper));
+        hipLaunchKernelGGL(lex_select_pass_kernel<true>, dim3(blocks_u), dim3(256), 0, s, ws->d_keys.get(), ctl, lim, 0,
+                           ws->d_scores.get(), ws->d_touched.get());
         for (int p = 1; p < kPasses; ++p)
-            hipLaunchKernelGGL(lex_select_pass_kernel<false>, dim3(blocks_u), dim3(256), 0, s, ws->d_keys, ctl, lim, p,
+            hipLaunchKernelGGL(lex_select_pass_kernel<false>, dim3(blocks_u), dim3(256), 0, s, ws->d_keys.get(), ctl, lim, p,
                                nullptr, nullptr);
-        hipLaunchKernelGGL(lex_collect_kernel, dim3(blocks_u), dim3(256), 0, s, ws->d_keys, ctl, lim, ws->d_sel);
+        hipLaunchKernelGGL(lex_collect_kernel, dim3(blocks_u), dim3(256), 0, s, ws->d_keys.get(), ctl, lim, ws->d_sel.get());
         if (need_sorted) {
-            hipLaunchKernelGGL(lex_sort_kernel<false>, dim3(1), dim3(1024), 0, s, nullptr, nullptr, ws->d_sel, ctl, lim,
-                               ws->d_out, d_out_n);
+            hipLaunchKernelGGL(lex_sort_kernel<false>, dim3(1), dim3(1024), 0, s, nullptr, nullptr, ws->d_sel.get(), ctl, lim,
+                               ws->d_out.get(), d_out_n);
         } else { // the consumer (the hybrid blend) wants the set, not its order: one LDS sort less on the critical path
-            d_result = ws->d_sel;
+            d_result = ws->d_sel.get();
             d_result_n = &ctl->n_sel;
         }
     }
@@ -1852,7 +1822,7 @@ static int32_t lexical_enqueue_masked(rlr_lexical *lx, const char *query_tokens,
     }
     LEX_HIP(hipGetLastError());
     LEX_HIP(hipEventRecord(ws->ready, s)); // the result list is complete here; the clean-up below runs behind it
-    hipLaunchKernelGGL(lex_clear_kernel, dim3(blocks_u), dim3(256), 0, s, ws->d_scores, ws->d_touched, ctl,
+    hipLaunchKernelGGL(lex_clear_kernel, dim3(blocks_u), dim3(256), 0, s, ws->d_scores.get(), ws->d_touched.get(), ctl,
                        reinterpret_cast<uint32_t *>(ctl_next), static_cast<uint32_t>(sizeof(LexControl) / 4));
     LEX_HIP(hipGetLastError());
     out->stream = s;
@@ -1871,11 +1841,12 @@ int32_t lexical_fetch(LexPending *p, uint64_t *rows_out, float *scores_out, uint
         return RLR_OK;
     LexWorkspace *ws = static_cast<LexWorkspace *>(p->ws);
     hipStream_t s = ws->stream;
+    uint64_t *h_out = static_cast<uint64_t *>(ws->h_out.get());
     // one copy: the count sits right behind the keys; only `limit` keys can be valid
-    LEX_HIP(hipMemcpyAsync(ws->h_out + kMaxLimit, ws->d_out + kMaxLimit, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    LEX_HIP(hipMemcpyAsync(ws->h_out, ws->d_out, static_cast<size_t>(p->limit) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    LEX_HIP(hipMemcpyAsync(h_out + kMaxLimit, ws->d_out.get() + kMaxLimit, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    LEX_HIP(hipMemcpyAsync(h_out, ws->d_out.get(), static_cast<size_t>(p->limit) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     LEX_HIP(hipStreamSynchronize(s));
-    const uint32_t n_dev = *reinterpret_cast<const uint32_t *>(ws->h_out + kMaxLimit);
+    const uint32_t n_dev = *reinterpret_cast<const uint32_t *>(h_out + kMaxLimit);
     if (n_dev == kLexRetry) { // the sampled selection gave up: the caller repeats the query on the exact path
         *n_out = kLexRetry;
         return RLR_OK;
@@ -1884,7 +1855,7 @@ int32_t lexical_fetch(LexPending *p, uint64_t *rows_out, float *scores_out, uint
     for (uint32_t i = 0; i < n; ++i) {
         float sc;
         uint32_t row;
-        unpack_result(ws->h_out[i], &sc, &row);
+        unpack_result(h_out[i], &sc, &row);
         rows_out[i] = row;
         scores_out[i] = sc;
     }
@@ -2019,31 +1990,31 @@ int32_t lexical_batch_enqueue(rlr_lexical *lx, uint32_t nq, const char *tokens, 
     LexWorkspace *ws = nullptr;
     LEX_TRY(workspace_acquire(lx, &ws));
     out->ws = ws;
-    LEX_TRY(dev_grow(&ws->d_btab, &ws->btab_cap, out->table.size()));
-    LEX_TRY(dev_grow(&ws->d_bkeys, &ws->bkeys_cap, std::max<uint64_t>(total_keys, 1)));
-    LEX_TRY(dev_grow(&ws->d_bsel, &ws->bsel_cap, static_cast<uint64_t>(nq) * limit));
-    LEX_TRY(dev_grow(&ws->d_bctl, &ws->bctl_cap, nq));
+    LEX_TRY(dev_grow(ws->d_btab, out->table.size()));
+    LEX_TRY(dev_grow(ws->d_bkeys, std::max<uint64_t>(total_keys, 1)));
+    LEX_TRY(dev_grow(ws->d_bsel, static_cast<uint64_t>(nq) * limit));
+    LEX_TRY(dev_grow(ws->d_bctl, nq));
     hipStream_t s = ws->stream;
-    const BatchQuery *d_q = reinterpret_cast<const BatchQuery *>(ws->d_btab);
-    const BatchTerm *d_t = reinterpret_cast<const BatchTerm *>(reinterpret_cast<const char *>(ws->d_btab) + q_bytes);
-    LEX_HIP(hipMemsetAsync(ws->d_bctl, 0, static_cast<size_t>(nq) * sizeof(LexControl), s));
-    LEX_HIP(hipMemcpyAsync(ws->d_btab, out->table.data(), tab_bytes, hipMemcpyHostToDevice, s));
+    const BatchQuery *d_q = reinterpret_cast<const BatchQuery *>(ws->d_btab.get());
+    const BatchTerm *d_t = reinterpret_cast<const BatchTerm *>(reinterpret_cast<const char *>(ws->d_btab.get()) + q_bytes);
+    LEX_HIP(hipMemsetAsync(ws->d_bctl.get(), 0, static_cast<size_t>(nq) * sizeof(LexControl), s));
+    LEX_HIP(hipMemcpyAsync(ws->d_btab.get(), out->table.data(), tab_bytes, hipMemcpyHostToDevice, s));
     if (!ts.empty() && n_rows > 0) {
         const uint32_t slices = static_cast<uint32_t>((n_rows + kLdsRows - 1) / kLdsRows);
-        hipLaunchKernelGGL(bm25_batch_kernel, dim3(slices, nq), dim3(256), 0, s, d_q, d_t, lx->d_post_row, lx->d_post_tf,
-                           lx->d_dpost_row, lx->d_dpost_tf, lx->d_doc_len, static_cast<uint32_t>(n_rows), avg, ws->d_bkeys,
-                           ws->d_bctl);
+        hipLaunchKernelGGL(bm25_batch_kernel, dim3(slices, nq), dim3(256), 0, s, d_q, d_t, lx->d_post_row.get(), lx->d_post_tf.get(),
+                           lx->d_dpost_row.get(), lx->d_dpost_tf.get(), lx->d_doc_len.get(), static_cast<uint32_t>(n_rows), avg, ws->d_bkeys.get(),
+                           ws->d_bctl.get());
     }
-    hipLaunchKernelGGL(lex_batch_sort_kernel, dim3(nq), dim3(1024), 0, s, d_q, ws->d_bkeys, ws->d_bctl, limit, ws->d_bsel);
+    hipLaunchKernelGGL(lex_batch_sort_kernel, dim3(nq), dim3(1024), 0, s, d_q, ws->d_bkeys.get(), ws->d_bctl.get(), limit, ws->d_bsel.get());
     if (max_keys > kMaxLimit) { // some query may have more keys than the LDS sort holds: the radix passes take those
         const uint32_t blocks_u = std::min<uint32_t>(static_cast<uint32_t>((max_keys + 255) / 256), static_cast<uint32_t>(lx->n_cu) * 8);
         for (int p = 0; p < kPasses; ++p)
-            hipLaunchKernelGGL(lex_batch_pass_kernel, dim3(blocks_u, nq), dim3(256), 0, s, d_q, ws->d_bkeys, ws->d_bctl, limit, p);
-        hipLaunchKernelGGL(lex_batch_collect_kernel, dim3(blocks_u, nq), dim3(256), 0, s, d_q, ws->d_bkeys, ws->d_bctl, limit,
-                           ws->d_bsel);
+            hipLaunchKernelGGL(lex_batch_pass_kernel, dim3(blocks_u, nq), dim3(256), 0, s, d_q, ws->d_bkeys.get(), ws->d_bctl.get(), limit, p);
+        hipLaunchKernelGGL(lex_batch_collect_kernel, dim3(blocks_u, nq), dim3(256), 0, s, d_q, ws->d_bkeys.get(), ws->d_bctl.get(), limit,
+                           ws->d_bsel.get());
     }
     static_assert(sizeof(LexControl) % 4 == 0 && offsetof(LexControl, n_sel) % 4 == 0, "count words");
-    launch_lex_unpack_batch(ws->d_bsel, limit, &ws->d_bctl[0].n_sel, static_cast<uint32_t>(sizeof(LexControl) / 4), nq, limit,
+    launch_lex_unpack_batch(ws->d_bsel.get(), limit, &ws->d_bctl.get()[0].n_sel, static_cast<uint32_t>(sizeof(LexControl) / 4), nq, limit,
                             sink, s);
     LEX_HIP(hipGetLastError());
     LEX_HIP(hipEventRecord(ws->ready, s));
@@ -2084,18 +2055,6 @@ struct LexBatchHeader { // index.hip's HybridLexHeader, as lex_unpack_batch_kern
 };
 static_assert(sizeof(LexBatchHeader) == 8, "two 32-bit words per query");
 
-struct SinkBuffers { // the device side of one call's LexBatchSink
-    uint32_t *rows = nullptr;
-    float *scores = nullptr;
-    LexBatchHeader *headers = nullptr;
-    ~SinkBuffers()
-    {
-        void *dev[] = {rows, scores, headers};
-        for (void *p : dev)
-            if (p)
-                (void)hipFree(p);
-    }
-};
 } // namespace
 
 extern "C" int32_t rlr_lexical_score_batch(rlr_lexical *lx, uint32_t nq, const char *tokens, const uint64_t *offsets,
@@ -2121,14 +2080,16 @@ extern "C" int32_t rlr_lexical_score_batch(rlr_lexical *lx, uint32_t nq, const c
     // sub-batches of the engine's size (one grid row of bm25_batch_kernel per query)
     constexpr uint32_t kSub = 256;
     const uint32_t sub = std::min(nq, kSub);
-    SinkBuffers buf;
-    LEX_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&buf.rows), static_cast<size_t>(sub) * limit * sizeof(uint32_t)));
-    LEX_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&buf.scores), static_cast<size_t>(sub) * limit * sizeof(float)));
-    LEX_HIP(rlr::dev_malloc(reinterpret_cast<void **>(&buf.headers), sub * sizeof(LexBatchHeader)));
+    DevBuf<uint32_t> d_rows; // the device side of this call's LexBatchSink
+    DevBuf<float> d_scores;
+    DevBuf<LexBatchHeader> d_headers;
+    LEX_HIP(d_rows.reserve(static_cast<size_t>(sub) * limit));
+    LEX_HIP(d_scores.reserve(static_cast<size_t>(sub) * limit));
+    LEX_HIP(d_headers.reserve(sub));
     rlr::LexBatchSink sink;
-    sink.d_rows = buf.rows;
-    sink.d_scores = buf.scores;
-    sink.d_headers = buf.headers;
+    sink.d_rows = d_rows.get();
+    sink.d_scores = d_scores.get();
+    sink.d_headers = d_headers.get();
     sink.bound = limit;
     sink.n_index_rows = 0xFFFFFFFFu; // no embedding index: no pair is marked
     std::vector<uint32_t> h_rows(static_cast<size_t>(sub) * limit);
@@ -2144,9 +2105,9 @@ extern "C" int32_t rlr_lexical_score_batch(rlr_lexical *lx, uint32_t nq, const c
         if (st == RLR_OK && hipEventSynchronize(static_cast<hipEvent_t>(lp.ready)) != hipSuccess)
             st = set_error(RLR_E_HIP, "lexical batch did not complete");
         if (st == RLR_OK &&
-            (hipMemcpy(h_hdr.data(), buf.headers, m * sizeof(LexBatchHeader), hipMemcpyDeviceToHost) != hipSuccess ||
-             hipMemcpy(h_rows.data(), buf.rows, static_cast<size_t>(m) * limit * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess ||
-             hipMemcpy(h_scores.data(), buf.scores, static_cast<size_t>(m) * limit * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess))
+            (hipMemcpy(h_hdr.data(), d_headers.get(), m * sizeof(LexBatchHeader), hipMemcpyDeviceToHost) != hipSuccess ||
+             hipMemcpy(h_rows.data(), d_rows.get(), static_cast<size_t>(m) * limit * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess ||
+             hipMemcpy(h_scores.data(), d_scores.get(), static_cast<size_t>(m) * limit * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess))
             st = set_error(RLR_E_HIP, "lexical batch: copy to the host failed");
         rlr::lexical_batch_finish(&lp, st == RLR_OK);
         if (st != RLR_OK)

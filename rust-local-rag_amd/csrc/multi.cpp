@@ -17,6 +17,7 @@
 #include "../../include/rlr_gpu.h"
 #include "../../include/rlr_engine.h"
 #include "../../include/rlr_lexical.h"
+#include "device_buffer.h"
 #include "engine_host.h"
 
 #include <hip/hip_runtime_api.h>
@@ -39,7 +40,6 @@
 
 namespace rlr {
 int32_t set_error(int32_t code, const char *fmt, ...); // index.hip: the calling thread's rlr_last_error() text
-hipError_t dev_malloc(void **p, size_t bytes);         // index.hip: every device allocation (RLR_POISON_ALLOC covers it)
 }
 
 namespace {
@@ -165,15 +165,14 @@ struct rlr_multi {
 
 struct ExWs {
     std::vector<hipStream_t> stream;
-    std::vector<void *> d_local, d_gath;
+    std::vector<rlr::DevBuf<uint64_t>> d_local, d_gath; // per shard, on its device
     size_t cap = 0; // entries (u64) d_local holds per shard
 };
 
 constexpr int kMaxExWs = 4;
 
 struct XferWs {
-    std::vector<void *> d_stage, d_recv; // per shard, on its device
-    std::vector<size_t> stage_cap, recv_cap;
+    std::vector<rlr::DevBuf<char>> d_stage, d_recv; // per shard, on its device
     std::vector<hipStream_t> stream;
 };
 
@@ -247,8 +246,8 @@ void exws_destroy(rlr_multi *m, ExWs *w)
             (void)hipStreamSynchronize(w->stream[g]);
             (void)hipStreamDestroy(w->stream[g]);
         }
-        if (w->d_local[g]) (void)hipFree(w->d_local[g]);
-        if (w->d_gath[g]) (void)hipFree(w->d_gath[g]);
+        w->d_local[g].reset();
+        w->d_gath[g].reset();
     }
     delete w;
 }
@@ -300,8 +299,8 @@ int32_t exws_acquire(rlr_multi *m, ExWs **out)
     hipError_t e = w ? hipSuccess : hipErrorOutOfMemory;
     if (w) {
         w->stream.assign(G, nullptr);
-        w->d_local.assign(G, nullptr);
-        w->d_gath.assign(G, nullptr);
+        w->d_local.resize(G);
+        w->d_gath.resize(G);
         for (size_t g = 0; g < G && e == hipSuccess; ++g) {
             e = hipSetDevice(m->device[g]);
             if (e == hipSuccess)
@@ -366,15 +365,12 @@ int32_t search_rccl(rlr_multi *m, const float *queries, uint32_t nq, uint32_t k,
     ExWs *w = lease.w;
     const size_t per = static_cast<size_t>(nq) * k;
     if (w->cap < per) {
+        // (w->cap is the authority: after a regrow that failed half way some shards keep larger blocks than it says)
         w->cap = 0; // nothing usable until every buffer of the new size exists
         for (size_t g = 0; g < G; ++g) {
             RLR_X_HIP(hipSetDevice(m->device[g]));
             RLR_X_HIP(hipStreamSynchronize(w->stream[g])); // (an earlier call's collective may still read the old buffers)
-            if (w->d_local[g]) (void)hipFree(w->d_local[g]);
-            if (w->d_gath[g]) (void)hipFree(w->d_gath[g]);
-            w->d_local[g] = w->d_gath[g] = nullptr;
-            RLR_X_HIP(rlr::dev_malloc(&w->d_local[g], per * sizeof(uint64_t)));
-            RLR_X_HIP(rlr::dev_malloc(&w->d_gath[g], G * per * sizeof(uint64_t)));
+            RLR_X_HIP(rlr::reserve_group(rlr::Want{w->d_local[g], per}, rlr::Want{w->d_gath[g], G * per}));
         }
         w->cap = per;
     }
@@ -394,7 +390,7 @@ int32_t search_rccl(rlr_multi *m, const float *queries, uint32_t nq, uint32_t k,
         return std::make_pair(est, over);
     };
     int32_t st = for_each_shard(m, [&](uint32_t g) {
-        return rlr_search_topk_device_begin(m->shard[g], queries, nq, k, guard_eps, w->d_local[g], w->stream[g], &ticket[g]);
+        return rlr_search_topk_device_begin(m->shard[g], queries, nq, k, guard_eps, w->d_local[g].get(), w->stream[g], &ticket[g]);
     });
     if (st != RLR_OK) {
         (void)end_all();
@@ -405,7 +401,7 @@ int32_t search_rccl(rlr_multi *m, const float *queries, uint32_t nq, uint32_t k,
         std::lock_guard<std::mutex> xl(m->xmu);
         ncclResult_t r = rccl().GroupStart();
         for (size_t g = 0; g < G && r == ncclSuccess; ++g)
-            r = rccl().AllGather(w->d_local[g], w->d_gath[g], per, ncclUint64, m->comm[g], w->stream[g]);
+            r = rccl().AllGather(w->d_local[g].get(), w->d_gath[g].get(), per, ncclUint64, m->comm[g], w->stream[g]);
         const ncclResult_t r2 = rccl().GroupEnd();
         if (r == ncclSuccess)
             r = r2;
@@ -415,7 +411,7 @@ int32_t search_rccl(rlr_multi *m, const float *queries, uint32_t nq, uint32_t k,
         }
     }
     // merge on the first device (a single process needs the answer once); queued behind its all-gather
-    st = rlr_merge_topk(m->device[0], w->d_gath[0], static_cast<uint32_t>(G), nq, k, m->base.data(), rows_out, cos_out,
+    st = rlr_merge_topk(m->device[0], w->d_gath[0].get(), static_cast<uint32_t>(G), nq, k, m->base.data(), rows_out, cos_out,
                         n_out, w->stream[0]);
     const auto ended = end_all();
     if (st != RLR_OK)
@@ -440,8 +436,8 @@ void xfer_destroy(rlr_multi *m, XferWs *w)
             (void)hipStreamSynchronize(w->stream[g]);
             (void)hipStreamDestroy(w->stream[g]);
         }
-        if (w->d_stage[g]) (void)hipFree(w->d_stage[g]);
-        if (w->d_recv[g]) (void)hipFree(w->d_recv[g]);
+        w->d_stage[g].reset();
+        w->d_recv[g].reset();
     }
     delete w;
 }
@@ -464,10 +460,8 @@ int32_t xfer_acquire(rlr_multi *m, XferWs **out)
     lk.unlock();
     const size_t G = m->shard.size();
     XferWs *w = new XferWs();
-    w->d_stage.assign(G, nullptr);
-    w->d_recv.assign(G, nullptr);
-    w->stage_cap.assign(G, 0);
-    w->recv_cap.assign(G, 0);
+    w->d_stage.resize(G);
+    w->d_recv.resize(G);
     w->stream.assign(G, nullptr);
     for (size_t g = 0; g < G; ++g) {
         hipError_t e = hipSetDevice(m->device[g]);
@@ -506,18 +500,13 @@ struct XferLease {
     }
 };
 
-int32_t dev_reserve(int32_t device, void **p, size_t *cap, size_t bytes)
+// room for `bytes` on `device`: a quarter of headroom, 1 MiB at the least
+int32_t dev_reserve(int32_t device, rlr::DevBuf<char> &b, size_t bytes)
 {
-    if (*cap >= bytes && *p)
+    if (b && b.capacity() >= bytes)
         return RLR_OK;
     RLR_X_HIP(hipSetDevice(device));
-    if (*p)
-        (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const size_t want = std::max<size_t>(bytes + bytes / 4, 1 << 20);
-    RLR_X_HIP(rlr::dev_malloc(p, want));
-    *cap = want;
+    RLR_X_HIP(b.reserve(std::max<size_t>(bytes + bytes / 4, 1 << 20)));
     return RLR_OK;
 }
 
@@ -601,9 +590,9 @@ int32_t multi_mmr(rlr_multi *m, const uint64_t *pool_rows, const float *pool_sco
     XferWs *w = lease.w;
     uint64_t moved = 0;
     for (size_t g = 0; g < G; ++g) { // buffers first: a copy must never target memory that is still being (re)allocated
-        if ((st = dev_reserve(m->device[g], &w->d_stage[g], &w->stage_cap[g], send_off[g][G] * rb)) != RLR_OK)
+        if ((st = dev_reserve(m->device[g], w->d_stage[g], send_off[g][G] * rb)) != RLR_OK)
             return st;
-        if ((st = dev_reserve(m->device[g], &w->d_recv[g], &w->recv_cap[g], recv_off[g][G] * rb)) != RLR_OK)
+        if ((st = dev_reserve(m->device[g], w->d_recv[g], recv_off[g][G] * rb)) != RLR_OK)
             return st;
         moved += send_off[g][G] * rb;
     }
@@ -613,7 +602,7 @@ int32_t multi_mmr(rlr_multi *m, const uint64_t *pool_rows, const float *pool_sco
         if (n_g == 0)
             return RLR_OK;
         const int32_t rc = [&]() -> int32_t {
-            int32_t s1 = rlr_gather_rows_device(m->shard[g], send_rows[g].data(), static_cast<uint32_t>(n_g), w->d_stage[g]);
+            int32_t s1 = rlr_gather_rows_device(m->shard[g], send_rows[g].data(), static_cast<uint32_t>(n_g), w->d_stage[g].get());
             if (s1 != RLR_OK)
                 return s1;
             RLR_X_HIP(hipSetDevice(m->device[g]));
@@ -621,8 +610,8 @@ int32_t multi_mmr(rlr_multi *m, const uint64_t *pool_rows, const float *pool_sco
                 const size_t cnt = send_count[g][o];
                 if (cnt == 0)
                     continue;
-                char *dst = static_cast<char *>(w->d_recv[o]) + recv_off[o][g] * rb;
-                const char *src = static_cast<const char *>(w->d_stage[g]) + send_off[g][o] * rb;
+                char *dst = w->d_recv[o].get() + recv_off[o][g] * rb;
+                const char *src = w->d_stage[g].get() + send_off[g][o] * rb;
                 if (m->device[o] == m->device[g]) {
                     RLR_X_HIP(hipMemcpyAsync(dst, src, cnt * rb, hipMemcpyDeviceToDevice, w->stream[g]));
                 } else if (hipMemcpyPeerAsync(dst, m->device[o], src, m->device[g], cnt * rb, w->stream[g]) != hipSuccess) {
@@ -666,7 +655,7 @@ int32_t multi_mmr(rlr_multi *m, const uint64_t *pool_rows, const float *pool_sco
         nsel[o].assign(nqo, 0);
         if (recv_off[o][G] == 0)
             return RLR_OK; // (only empty pools)
-        return rlr_mmr_select_staged(m->shard[o], w->d_recv[o], recv_off[o][G], slots[o].data(), scores[o].data(), sizes[o].data(),
+        return rlr_mmr_select_staged(m->shard[o], w->d_recv[o].get(), recv_off[o][G], slots[o].data(), scores[o].data(), sizes[o].data(),
                                      nqo, P, k, lambda, ord[o].data(), mmrv[o].data(), nsel[o].data());
     });
     if (st != RLR_OK)

@@ -34,6 +34,24 @@ def test_host_logic_under_asan_and_ubsan(tmp_path):
 
 HIPCC = "/opt/rocm/bin/hipcc"
 CLANGXX = "/opt/rocm/lib/llvm/bin/clang++"
+HIP_INCLUDE = "/opt/rocm/include"
+
+
+@pytest.mark.skipif(shutil.which("g++") is None or not os.path.exists(os.path.join(HIP_INCLUDE, "hip", "hip_runtime_api.h")),
+                    reason="needs g++ and the HIP runtime's API header")
+def test_buffer_owners_under_asan_and_ubsan(tmp_path):
+    """csrc/device_buffer.h (DevBuf, PinBuf, reserve_group) over counting stand-ins for the allocator
+    (tests/sanitize/devbuf_san.cpp): reserve growing / equal / smaller, a failed regrow leaving the buffer empty, moves,
+    reset, an allocation failing at every position of a group leaving the whole group empty, nothing live at exit."""
+    exe = str(tmp_path / "devbuf_san")
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1"]
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", *san, "-D__HIP_PLATFORM_AMD__", "-isystem", HIP_INCLUDE,
+                    os.path.join(ROOT, "tests", "sanitize", "devbuf_san.cpp"), "-o", exe], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    env.pop("LD_PRELOAD", None)
+    out = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-6000:]
+    assert "devbuf_san ok" in out.stdout
 
 
 @pytest.mark.skipif(not (os.path.exists(HIPCC) and os.path.exists(CLANGXX)), reason="needs hipcc + clang++")

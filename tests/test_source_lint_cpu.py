@@ -1,5 +1,7 @@
-"""Source-level guards for two classes of defect the GPU fuzzers have found or would not find reliably:
+"""Source-level guards for three classes of defect the GPU fuzzers have found or would not find reliably:
 * device memory the library allocates must come from rlr::dev_malloc, so that RLR_POISON_ALLOC=1 covers every buffer;
+* device and pinned memory is owned by a DevBuf / PinBuf (csrc/device_buffer.h), so that no early return can leak it and
+  no destructor's list can fall behind the members;
 * a null-stream fill / device-to-device copy of device memory may return before it has run and is NOT ordered
   against the non-blocking streams searches run on (the histogram defect of round 1), so each one must be followed
   by an explicit wait before the function goes on, or be issued Async on the consumer's own stream.
@@ -10,7 +12,8 @@ import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SOURCES = sorted(glob.glob(os.path.join(ROOT, "rust-local-rag_amd", "csrc", "*.hip")) +
-                 glob.glob(os.path.join(ROOT, "rust-local-rag_amd", "csrc", "*.cpp")))
+                 glob.glob(os.path.join(ROOT, "rust-local-rag_amd", "csrc", "*.cpp")) +
+                 glob.glob(os.path.join(ROOT, "rust-local-rag_amd", "csrc", "*.h")))
 
 
 def _lines(path):
@@ -28,6 +31,43 @@ def test_every_device_allocation_goes_through_dev_malloc():
                 bare.append((os.path.basename(path), i))
     # the one call inside rlr::dev_malloc itself
     assert len(bare) == 1 and bare[0][0] == "index.hip", bare
+
+
+# (file, enclosing function) -> why that function frees or pins memory by hand.  An entry must not be a function that
+# itself allocates what it frees (a scoped temporary is a local DevBuf / PinBuf).  Empty: every buffer has an owner.
+HAND_MANAGED = {}
+
+
+def _enclosing_function(lines, i):
+    """Name of the function whose body holds line i: the nearest line above that starts in column 0 and opens a
+    parameter list (csrc/ puts every function's name there and its opening brace on the next line).  A heuristic: a
+    macro or a file-scope initialiser above the hit would be taken for the function.  That cannot pass a hit while
+    HAND_MANAGED is empty (any name fails); check the first entry that is ever added against the source by hand."""
+    for j in range(i, -1, -1):
+        m = re.match(r"[A-Za-z_].*?([A-Za-z_][A-Za-z0-9_]*)\(", lines[j])
+        if m and not lines[j].startswith(("namespace", "extern", "struct", "class", "template", "constexpr", "static_assert")):
+            return m.group(1)
+    return ""
+
+
+def test_device_and_pinned_memory_is_freed_only_by_its_owner_types():
+    found, used = [], set()
+    for path in SOURCES:
+        name = os.path.basename(path)
+        if name == "device_buffer.h":
+            continue
+        lines = _lines(path)
+        for i, line in enumerate(lines):
+            if re.search(r"(?<![A-Za-z_])(hipFree|hipHostFree|hipHostMalloc)\(", line.split("//")[0]):
+                key = (name, _enclosing_function(lines, i))
+                used.add(key)
+                if key not in HAND_MANAGED:
+                    found.append((name, i + 1, key[1]))
+    assert not found, found
+    assert used == set(HAND_MANAGED), f"stale allow-list entries: {sorted(set(HAND_MANAGED) - used)}"
+    with open(os.path.join(ROOT, "rust-local-rag_amd", "csrc", "device_buffer.h")) as f:
+        owner = f.read()
+    assert "hipFree(" in owner and "hipHostFree(" in owner and "hipHostMalloc(" in owner
 
 
 def test_null_stream_fills_and_device_copies_are_followed_by_a_wait():
