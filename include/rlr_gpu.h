@@ -248,7 +248,8 @@ int32_t rlr_index_row_bytes(const rlr_index *idx, uint32_t *bytes_out);
 /* rlr_mmr_select_batch for pools whose rows sit in a STAGED matrix in device memory instead of the index: d_staged =
  * n_staged raw rows in idx's dtype and row pitch (what rlr_gather_rows_device writes; e.g. the receive buffer of the
  * winner-row exchange), pool_slots[q * P + j] = the staged row that is candidate j of pool q.  `idx` supplies device,
- * dim, dtype and workspace; its own rows are not read.  n_queries == 1 takes pools up to 4096 candidates. */
+ * dim, dtype and workspace; its own rows are not read.  Only the first dim elements of a staged row are read, never its
+ * padding.  n_queries == 1 takes P and pool_sizes[0] up to 4096 (one pool does not use the stride P). */
 int32_t rlr_mmr_select_staged(rlr_index *idx, const void *d_staged, uint64_t n_staged, const uint64_t *pool_slots,
                               const float *pool_scores, const uint32_t *pool_sizes, uint32_t n_queries, uint32_t P,
                               uint32_t k, float lambda, uint32_t *order_out, float *mmr_out, uint32_t *n_out);

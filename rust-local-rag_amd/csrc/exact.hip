@@ -1140,8 +1140,8 @@ typedef float v32f __attribute__((ext_vector_type(32)));
 // UPR = 16-byte units per row and chunk: the K chunk is 8 UPR binary16 elements (UPR = 4: 7.7 KB of LDS per wave, five waves per SIMD
 // fit; UPR = 8 would be 13.8 KB, 2.75 per SIMD).
 __global__ __launch_bounds__(64) void gram_mfma_f32_kernel(const unsigned char *__restrict__ rows, uint32_t pitch_bytes,
-                                                           const uint32_t *__restrict__ list, uint32_t P, uint32_t n_pools,
-                                                           uint32_t jobs_per_pool, float *__restrict__ gram)
+                                                           uint32_t dim, const uint32_t *__restrict__ list, uint32_t P,
+                                                           uint32_t n_pools, uint32_t jobs_per_pool, float *__restrict__ gram)
 {
     constexpr int UPR = 4;
     constexpr int kGmPitch = UPR * 16 + 16; // bytes per staged row: 16-byte reads of consecutive rows land in different slots
@@ -1172,12 +1172,22 @@ __global__ __launch_bounds__(64) void gram_mfma_f32_kernel(const unsigned char *
     const uint32_t seg = lane % UPR;
     const uint32_t row_units = pitch_bytes / 16; // a row's last chunk may be short: units beyond the pitch read as zero
     const uint32_t n_chunks = (row_units + UPR - 1) / UPR;
+    // the elements behind dim in a row's last unit (dim % 8 != 0) are padding: zero in the index, anything in a caller's staged
+    // matrix, so they are masked to +0.0 instead of multiplied
+    const uint32_t tail_unit = dim / 8, tail_keep = dim % 8;
+    const auto half_mask = [&](uint32_t j) { return tail_keep >= 2 * j + 2 ? 0xFFFFFFFFu : tail_keep == 2 * j + 1 ? 0xFFFFu : 0u; };
+    const uint4 tail_mask = make_uint4(half_mask(0), half_mask(1), half_mask(2), half_mask(3));
     uint4 pre[kPer];
     auto fetch = [&](uint32_t c) {
         const bool in = c * UPR + seg < row_units;
 #pragma unroll
         for (int i = 0; i < kPer; ++i)
             pre[i] = in ? *reinterpret_cast<const uint4 *>(src[i] + static_cast<size_t>(c) * (UPR * 16)) : make_uint4(0u, 0u, 0u, 0u);
+        if (tail_keep && c * UPR + seg == tail_unit) {
+#pragma unroll
+            for (int i = 0; i < kPer; ++i)
+                pre[i] = make_uint4(pre[i].x & tail_mask.x, pre[i].y & tail_mask.y, pre[i].z & tail_mask.z, pre[i].w & tail_mask.w);
+        }
     };
     v32f acc;
 #pragma unroll
@@ -1271,7 +1281,7 @@ hipError_t launch_gram_rows(const void *rows, uint32_t pitch16, uint32_t dim, in
                 jobs_per_pool += nb - 2 * pr;
             const uint32_t pools8 = (n_queries + 7) / 8 * 8;
             hipLaunchKernelGGL(gram_mfma_f32_kernel, dim3(pools8 * jobs_per_pool), dim3(64), 0, s, static_cast<const unsigned char *>(rows),
-                               pitch16 * 16u, list, P, n_queries, jobs_per_pool, gram);
+                               pitch16 * 16u, dim, list, P, n_queries, jobs_per_pool, gram);
             return hipGetLastError();
         }
         return launch_gram_src<2>(nullptr, P, dim, gram, n_queries, rows, pitch16, list, s);

@@ -4012,9 +4012,14 @@ int32_t rlr_mmr_select_staged(rlr_index *ix, const void *d_staged, uint64_t n_st
 {
     if (n_queries && (!d_staged || !pool_slots || n_staged == 0))
         return fail(RLR_E_INVALID, "null argument");
-    if (n_queries == 1 && pool_sizes && pool_sizes[0] > 1024) // one large pool: the single-pool kernels (up to 4096)
+    // one large pool: the single-pool kernels (up to 4096).  P is only the stride, which one pool does not use, so a
+    // small pool in a wide slot list goes the same way
+    if (n_queries == 1 && pool_sizes && (pool_sizes[0] > 1024 || P > 1024)) {
+        if (pool_sizes[0] > P)
+            return fail(RLR_E_INVALID, "pool_sizes[0] = %u exceeds P = %u", pool_sizes[0], P);
         return mmr_single_impl(ix, pool_slots, pool_scores, pool_sizes[0], k, lambda, order_out, mmr_out, n_out, d_staged,
                                n_staged);
+    }
     return mmr_batch_impl(ix, pool_slots, nullptr, pool_scores, pool_sizes, n_queries, P, k, lambda, order_out, mmr_out, n_out,
                           d_staged, n_staged);
 }

@@ -262,6 +262,33 @@ class GpuIndex:
         if rows.size:
             N.check(self._L.rlr_fetch_rows_device(self._h, _up(rows), rows.size, C.c_void_p(d_out_ptr)))
 
+    def row_bytes(self) -> int:
+        """bytes of one stored row: dim elements of the index' dtype, padded to 16 bytes (rlr_index_row_bytes)"""
+        b = C.c_uint32()
+        N.check(self._L.rlr_index_row_bytes(self._h, C.byref(b)))
+        return int(b.value)
+
+    def gather_rows_device(self, rows, d_out_ptr: int) -> None:
+        """rows of this index as stored (row_bytes() bytes each, dense) into device memory at `d_out_ptr`"""
+        rows = _u64(rows).ravel()
+        if rows.size:
+            N.check(self._L.rlr_gather_rows_device(self._h, _up(rows), rows.size, C.c_void_p(d_out_ptr)))
+
+    def mmr_select_staged(self, d_staged_ptr: int, n_staged: int, pool_slots, pool_scores, pool_sizes, k: int, lam: float):
+        """mmr_select_batch for pools whose rows sit in a staged matrix in device memory: `n_staged` raw rows of this index'
+        dtype at row_bytes() pitch (what gather_rows_device writes); pool_slots [Q, P] index that matrix"""
+        pool_slots = _u64(pool_slots)
+        pool_scores = _f32(pool_scores)
+        nq, P = pool_slots.shape
+        sizes = np.ascontiguousarray(pool_sizes, dtype=np.uint32)
+        order = np.zeros((nq, max(P, 1)), dtype=np.uint32)
+        mmr = np.zeros((nq, max(P, 1)), dtype=np.float32)
+        n = np.zeros(max(nq, 1), dtype=np.uint32)
+        N.check(self._L.rlr_mmr_select_staged(self._h, C.c_void_p(d_staged_ptr), n_staged, _up(pool_slots), _fp(pool_scores),
+                                              sizes.ctypes.data_as(N.u32p), nq, P, k, lam, order.ctypes.data_as(N.u32p),
+                                              _fp(mmr), n.ctypes.data_as(N.u32p)))
+        return order, mmr, n[:nq]
+
     def mmr_select_values(self, d_values_ptr: int, pool_scores, pool_sizes, k: int, lam: float):
         """mmr_select_batch for pools whose row values are in device memory: [Q, P, dim] f32 at `d_values_ptr`"""
         pool_scores = _f32(pool_scores)
