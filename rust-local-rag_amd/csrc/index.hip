@@ -38,19 +38,10 @@ namespace {
 
 thread_local char g_err[512] = "";
 
-int32_t fail(int32_t code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 } // namespace
 
 namespace rlr {
-// the same thread-local message for the other translation units of the library (lexical.hip)
+// the thread-local message behind rlr_last_error(), for this file and the other translation units of the library
 int32_t set_error(int32_t code, const char *fmt, ...)
 {
     va_list ap;
@@ -63,12 +54,12 @@ int32_t set_error(int32_t code, const char *fmt, ...)
 
 namespace {
 
-#define RLR_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(e_ == hipErrorOutOfMemory ? RLR_E_OOM : RLR_E_HIP, "%s failed: %s (%s:%d)", \
-                        #call, hipGetErrorString(e_), __FILE__, __LINE__);                         \
+#define RLR_HIP(call)                                                                                    \
+    do {                                                                                                 \
+        hipError_t e_ = (call);                                                                          \
+        if (e_ != hipSuccess)                                                                            \
+            return set_error(e_ == hipErrorOutOfMemory ? RLR_E_OOM : RLR_E_HIP, "%s failed: %s (%s:%d)", \
+                             #call, hipGetErrorString(e_), __FILE__, __LINE__);                          \
     } while (0)
 
 #define RLR_TRY(call)                                                                              \
@@ -356,7 +347,7 @@ int32_t ctx_acquire(rlr_index *ix, Ctx **out)
     Ctx *c = new (std::nothrow) Ctx();
     if (!c) {
         give_up(nullptr);
-        return fail(RLR_E_OOM, "host allocation failed");
+        return set_error(RLR_E_OOM, "host allocation failed");
     }
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     for (int i = 0; i < 4 && e == hipSuccess; ++i)
@@ -380,7 +371,7 @@ int32_t ctx_acquire(rlr_index *ix, Ctx **out)
         e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         give_up(c);
-        return fail(RLR_E_HIP, "context setup failed: %s", hipGetErrorString(e));
+        return set_error(RLR_E_HIP, "context setup failed: %s", hipGetErrorString(e));
     }
     *out = c;
     return RLR_OK;
@@ -409,7 +400,7 @@ struct CtxLease {
 int32_t check_handle(const rlr_index *ix)
 {
     if (!ix)
-        return fail(RLR_E_INVALID, "null index handle");
+        return set_error(RLR_E_INVALID, "null index handle");
     return RLR_OK;
 }
 
@@ -418,7 +409,7 @@ int32_t ensure_rows(rlr_index *ix, uint64_t want_rows)
     if (want_rows <= ix->cap_rows)
         return RLR_OK;
     if (want_rows > 0xFFFFFFF0ull)
-        return fail(RLR_E_INVALID, "an index shard holds at most 2^32-16 rows");
+        return set_error(RLR_E_INVALID, "an index shard holds at most 2^32-16 rows");
     uint64_t cap = std::max<uint64_t>(want_rows, ix->cap_rows + ix->cap_rows / 2);
     cap = std::max<uint64_t>(cap, 1024);
     DevBuf<char> n;
@@ -428,14 +419,14 @@ int32_t ensure_rows(rlr_index *ix, uint64_t want_rows)
         e = n.reserve(cap * row_bytes(ix));
     }
     if (e != hipSuccess)
-        return fail(RLR_E_OOM, "allocation of %llu rows x %zu B failed: %s",
-                    static_cast<unsigned long long>(cap), row_bytes(ix), hipGetErrorString(e));
+        return set_error(RLR_E_OOM, "allocation of %llu rows x %zu B failed: %s",
+                         static_cast<unsigned long long>(cap), row_bytes(ix), hipGetErrorString(e));
     if (ix->d_rows.get() && ix->n_rows) {
         hipError_t ce = hipMemcpy(n.get(), ix->d_rows.get(), ix->n_rows * row_bytes(ix), hipMemcpyDeviceToDevice);
         if (ce == hipSuccess)
             ce = hipStreamSynchronize(nullptr); // a device-to-device copy may return before it has run
         if (ce != hipSuccess)
-            return fail(RLR_E_HIP, "moving the rows into the larger allocation failed: %s", hipGetErrorString(ce));
+            return set_error(RLR_E_HIP, "moving the rows into the larger allocation failed: %s", hipGetErrorString(ce));
     }
     ix->d_rows = std::move(n); // (frees the old rows)
     ix->cap_rows = cap;
@@ -510,7 +501,7 @@ int32_t ingest(rlr_index *ix, const float *rows, uint64_t n, uint64_t first, int
     RLR_HIP(stage.reserve(cr * ix->dim));
     hipError_t e = norm.reserve(cr);
     if (e != hipSuccess)
-        return fail(RLR_E_OOM, "staging allocation failed");
+        return set_error(RLR_E_OOM, "staging allocation failed");
     float *const d_stage = stage.get(), *const d_norm = norm.get();
     int32_t st = RLR_OK;
     std::vector<float> h_norm;
@@ -536,7 +527,7 @@ int32_t ingest(rlr_index *ix, const float *rows, uint64_t n, uint64_t first, int
             }
         }
         if (e != hipSuccess)
-            st = fail(RLR_E_HIP, "row ingest failed: %s", hipGetErrorString(e));
+            st = set_error(RLR_E_HIP, "row ingest failed: %s", hipGetErrorString(e));
     }
     return st;
 }
@@ -622,10 +613,10 @@ int32_t wait_polling(Complete &&complete, hipStream_t s, WaitEma *c, uint32_t ke
                 }
                 if (ok)
                     break;
-                return fail(RLR_E_INTERNAL, "the stream drained but a completion word was never written");
+                return set_error(RLR_E_INTERNAL, "the stream drained but a completion word was never written");
             }
             if (e != hipErrorNotReady)
-                return fail(RLR_E_HIP, "stream failed while a search was in flight: %s", hipGetErrorString(e));
+                return set_error(RLR_E_HIP, "stream failed while a search was in flight: %s", hipGetErrorString(e));
         }
         if (polls > 8192 && (polls & 0xFF) == 0)
             std::this_thread::yield(); // a long wait: more waiters than cores must not starve the threads that feed the GPU
@@ -728,18 +719,6 @@ __global__ __launch_bounds__(256) void stage_query_kernel(const float4 *__restri
 } // namespace rlr
 
 namespace {
-
-// Will this index's single-query scans take their query in the kernel arguments?  (Then nothing is uploaded in front of
-// them: workgroup 0 of the scan leaves the query in the context's device buffer for the kernels behind it.)
-bool scans_take_host_query(const rlr_index *ix, const Ctx *c, const float *h_q);
-
-// The queries of a call whose pipelines start with enqueue_query_scan: by the scans themselves where they can, else uploaded.
-hipError_t upload_queries(Ctx *c, const float *h_q, size_t q_bytes, hipStream_t s);
-hipError_t stage_queries_for_scans(const rlr_index *ix, Ctx *c, const float *h_q, size_t q_bytes, hipStream_t s)
-{
-    c->h_q_kq = scans_take_host_query(ix, c, h_q) ? h_q : nullptr;
-    return c->h_q_kq ? hipSuccess : upload_queries(c, h_q, q_bytes, s);
-}
 
 hipError_t upload_queries(Ctx *c, const float *h_q, size_t q_bytes, hipStream_t s)
 {
@@ -1434,6 +1413,8 @@ ScanArgs scan_args(const rlr_index *ix, const float *query, float *scores, uint3
     return sa;
 }
 
+// Will this index's single-query scans take their query in the kernel arguments?  (Then nothing is uploaded in front of
+// them: workgroup 0 of the scan leaves the query in the context's device buffer for the kernels behind it.)
 bool scans_take_host_query(const rlr_index *ix, const Ctx *c, const float *h_q)
 {
     if (scan_over_q8(ix) || scan_over_image(ix, c) || ix->n_rows == 0)
@@ -1441,6 +1422,13 @@ bool scans_take_host_query(const rlr_index *ix, const Ctx *c, const float *h_q)
     ScanArgs sa = scan_args(ix, nullptr, nullptr, nullptr);
     sa.query_host = h_q;
     return launch_scan_takes_host_query(sa);
+}
+
+// The queries of a call whose pipelines start with enqueue_query_scan: by the scans themselves where they can, else uploaded.
+hipError_t stage_queries_for_scans(const rlr_index *ix, Ctx *c, const float *h_q, size_t q_bytes, hipStream_t s)
+{
+    c->h_q_kq = scans_take_host_query(ix, c, h_q) ? h_q : nullptr;
+    return c->h_q_kq ? hipSuccess : upload_queries(c, h_q, q_bytes, s);
 }
 
 // band for 8-bit-nominated scores of a query of norm q_norm (Cauchy-Schwarz on the stored row error norms)
@@ -1478,7 +1466,7 @@ int32_t check_hist_assert(Ctx *c)
     if (h && *h) {
         const uint32_t n = *h;
         *h = 0;
-        return fail(RLR_E_INTERNAL, "zero-histogram invariant violated: %u non-zero bins in front of a scan", n);
+        return set_error(RLR_E_INTERNAL, "zero-histogram invariant violated: %u non-zero bins in front of a scan", n);
     }
     return RLR_OK;
 }
@@ -1515,6 +1503,29 @@ void stage_queries(const rlr_index *ix, Ctx *c, const float *queries, uint32_t n
     pad_queries(ix, queries, nq, h_q);
     stage_query_norms(ix, c, queries, nq);
     c->hist_dirty = true;
+}
+
+// The pinned memory of a call (c->h_pin): nq staged queries, res_words result words behind them.
+struct Staged {
+    float *h_q;
+    uint64_t *h_res;
+};
+
+// Reserve and carve that memory, stage the queries (stage_queries) and send them on their way -- for_scans: left to the
+// scans where they can take them (stage_queries_for_scans), else uploaded, with c->h_q_kq null.
+int32_t stage_call(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, size_t res_words, bool for_scans, Staged *out)
+{
+    const size_t q_bytes = static_cast<size_t>(nq) * ix->q_pitch * sizeof(float);
+    RLR_TRY(pin_reserve(c, q_bytes + res_words * sizeof(uint64_t)));
+    out->h_q = static_cast<float *>(c->h_pin.get());
+    out->h_res = reinterpret_cast<uint64_t *>(static_cast<char *>(c->h_pin.get()) + q_bytes);
+    stage_queries(ix, c, queries, nq, out->h_q);
+    c->h_q_kq = nullptr;
+    if (for_scans)
+        RLR_HIP(stage_queries_for_scans(ix, c, out->h_q, q_bytes, c->stream));
+    else
+        RLR_HIP(upload_queries(c, out->h_q, q_bytes, c->stream));
+    return RLR_OK;
 }
 
 // the completion words a polling wait watches (sort_emit.h): pre-set before the first enqueue, replaced by each
@@ -1764,7 +1775,8 @@ rlr::MmrEmit mmr_emit(const uint32_t *list, const float *comb, const float *cosv
 // The context's histograms are zero on entry: cleared at creation and by every pipeline (tail stage 2 / the re-score kernel).
 // (in two halves, so that a caller with work for ANOTHER stream -- the BM25 kernels of a text search -- can launch it right
 // behind the scan instead of behind every launch of the pipeline: enqueue_query_scan, then enqueue_query_rest)
-hipError_t enqueue_query_scan(rlr_index *ix, Ctx *c, uint32_t qi, bool timed)
+// f != nullptr: a document-scoped search -- the masked scan over the master rows, whatever copies the index keeps.
+hipError_t enqueue_query_scan(rlr_index *ix, Ctx *c, uint32_t qi, bool timed, const rlr_filter *f = nullptr)
 {
     hipStream_t s = c->stream;
     hipError_t e;
@@ -1780,9 +1792,11 @@ hipError_t enqueue_query_scan(rlr_index *ix, Ctx *c, uint32_t qi, bool timed)
     if (timed && (e = hipEventRecord(c->ev[0], s)) != hipSuccess) return e;
     ScanArgs sa = scan_args(ix, dq, c->d_scores.get(), hist1);
     sa.query_host = c->h_q_kq ? c->h_q_kq + static_cast<size_t>(qi) * ix->q_pitch : nullptr;
-    const bool q8 = scan_over_q8(ix);
-    const bool img = !q8 && scan_over_image(ix, c);
-    if (q8)
+    const bool q8 = !f && scan_over_q8(ix);
+    const bool img = !f && !q8 && scan_over_image(ix, c);
+    if (f)
+        e = launch_scan_masked(sa, f->d_mask.get(), f->n_allowed, s);
+    else if (q8)
         e = launch_q8_scan(ix->d_q8.get(), ix->d_q8_scale.get(), n, ix->dim, dq, c->d_scores.get(), hist1, ix->n_cu, s);
     else if (img)
         e = launch_scan_image(ix->d_image.get(), n, ix->dim, dq, c->d_scores.get(), hist1, ix->n_cu, s);
@@ -1876,6 +1890,22 @@ hipError_t enqueue_query(rlr_index *ix, Ctx *c, uint32_t qi, const SearchPlan &p
     return e != hipSuccess ? e : enqueue_query_rest(ix, c, qi, p, d_out_q, d_meta_q, timed, emit, pool, pool_done);
 }
 
+// The ending of the exact paths (big_query, the filtered list path): the k best of the exactly scored keys in d_packed
+// (cap slots, zero padded) into d_out.
+hipError_t enqueue_order_emit(uint64_t *d_packed, const SelectState *st, uint32_t cap, uint32_t n_valid, uint64_t *d_out,
+                              uint32_t k, hipStream_t s)
+{
+    if (k <= kLdsSortCap) {
+        // second level: the exact keys (st->n_cand of them) are selected and sorted by one workgroup
+        hipLaunchKernelGGL(rlr::topk_global_kernel, dim3(1), dim3(1024), 0, s, d_packed, st, cap, d_out, k);
+    } else {
+        const hipError_t e = launch_sort_desc(d_packed, cap, s);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(rlr::emit_kernel, dim3((k + 255) / 256), dim3(256), 0, s, d_packed, n_valid, d_out, k);
+    }
+    return hipGetLastError();
+}
+
 // Large-candidate path for one query whose band overflowed the LDS sort (massive ties /
 // duplicated chunks, or k > kLdsSortCap).  Re-uses the scores still resident from the scan
 // only when the query was the last one scanned; otherwise re-scans.
@@ -1909,14 +1939,7 @@ int32_t big_query(rlr_index *ix, Ctx *c, uint32_t qi, const SearchPlan &p, uint3
     RLR_HIP(e);
     if (!staged) // rows too large for the staged layout, or k beyond the one-workgroup finish
         RLR_HIP(launch_rescore(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, dq, c->d_cand.get(), st, c->d_packed.get(), cap, s));
-    if (second_level) {
-        // second level: the exact keys are selected and sorted by one workgroup
-        hipLaunchKernelGGL(rlr::topk_global_kernel, dim3(1), dim3(1024), 0, s, c->d_packed.get(), st, cap, d_out_q, p.k);
-    } else {
-        RLR_HIP(launch_sort_desc(c->d_packed.get(), cap, s));
-        hipLaunchKernelGGL(rlr::emit_kernel, dim3((p.k + 255) / 256), dim3(256), 0, s, c->d_packed.get(), n_cand, d_out_q, p.k);
-    }
-    RLR_HIP(hipGetLastError());
+    RLR_HIP(enqueue_order_emit(c->d_packed.get(), st, cap, n_cand, d_out_q, p.k, s));
     RLR_HIP(hipStreamSynchronize(s));
     return RLR_OK;
 }
@@ -2074,7 +2097,7 @@ int32_t run_batched(rlr_index *ix, Ctx *c, uint32_t q0, uint32_t nq, const Searc
         // (binary16 rows: the same band -- the widening is exact and the products and sums are f32 as in the single-query scan)
         if (!(ix->dtype == RLR_F16 ? launch_scan_multi_f16(sa, ix->q_pitch, nq, s_stride, s, &e)
                                    : launch_scan_multi(sa, ix->q_pitch, nq, s_stride, s, &e)))
-            return fail(RLR_E_INTERNAL, "multi-query scan refused a shape its gate accepted");
+            return set_error(RLR_E_INTERNAL, "multi-query scan refused a shape its gate accepted");
         RLR_HIP(e);
     } else {
         RLR_HIP(launch_prep_queries(dq, nq, ix->q_pitch, ix->dim, use_image ? static_cast<int>(RLR_F16) : ix->dtype, c->d_qfrag.get(), s));
@@ -2151,23 +2174,14 @@ int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uin
     uint64_t *d_out = d_out_user ? d_out_user : c->d_out.get();
     uint64_t *d_meta = c->d_out.get() + n_res; // per-query candidate counts, right behind the context's results
 
-    // stage queries (zero padded to the row pitch)
-    const size_t q_bytes = static_cast<size_t>(nq) * ix->q_pitch * sizeof(float);
-    const size_t res_bytes = (n_res + nq) * sizeof(uint64_t);
-    RLR_TRY(pin_reserve(c, q_bytes + res_bytes));
-    float *h_q = static_cast<float *>(c->h_pin.get());
-    uint64_t *h_res = reinterpret_cast<uint64_t *>(static_cast<char *>(c->h_pin.get()) + q_bytes);
-    uint64_t *h_meta = h_res + n_res;
-    stage_queries(ix, c, queries, nq, h_q);
-    hipStream_t s = c->stream;
+    // stage queries (zero padded to the row pitch); the matrix-core pipeline reads them from device memory
     const bool batched = batch_eligible(ix, nq, p.k, p.f16_ok, coalesced);
+    Staged pin;
+    RLR_TRY(stage_call(ix, c, queries, nq, n_res + nq, /*for_scans=*/!batched, &pin));
+    uint64_t *h_res = pin.h_res, *h_meta = h_res + n_res;
+    hipStream_t s = c->stream;
     if (!batched)
         count_f16_fallbacks(ix, p, nq, batch_eligible(ix, nq, p.k));
-    c->h_q_kq = nullptr;
-    if (batched) // (the matrix-core pipeline reads the queries from device memory)
-        RLR_HIP(upload_queries(c, h_q, q_bytes, s));
-    else
-        RLR_HIP(stage_queries_for_scans(ix, c, h_q, q_bytes, s));
 
     const bool timed = ix->profiling;
     StageMs per_query_ms; // (profiling several queries: summed query by query)
@@ -2274,8 +2288,8 @@ int32_t upload_list(rlr_index *ix, Ctx *c, const uint64_t *rows, uint32_t n, uin
     uint32_t *h = static_cast<uint32_t *>(c->h_pin.get());
     for (uint32_t i = 0; i < n; ++i) {
         if (rows[i] >= bound)
-            return fail(RLR_E_RANGE, "row %llu out of range (%llu rows)", static_cast<unsigned long long>(rows[i]),
-                        static_cast<unsigned long long>(bound));
+            return set_error(RLR_E_RANGE, "row %llu out of range (%llu rows)", static_cast<unsigned long long>(rows[i]),
+                             static_cast<unsigned long long>(bound));
         h[i] = static_cast<uint32_t>(rows[i]);
     }
     RLR_HIP(hipMemcpyAsync(c->d_list.get(), h, static_cast<size_t>(n) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
@@ -2308,7 +2322,7 @@ int32_t search_topk_host(rlr_index *ix, const float *queries, uint32_t n_queries
     const uint64_t *h = nullptr;
     RLR_TRY(run_search(ix, c, queries, n_queries, k, guard_eps, nullptr, &p, &h));
     if (!h)
-        return fail(RLR_E_INTERNAL, "search produced no result buffer");
+        return set_error(RLR_E_INTERNAL, "search produced no result buffer");
     for (uint32_t q = 0; q < n_queries; ++q) {
         n_out[q] = p.k;
         unpack_results(h + static_cast<size_t>(q) * p.k, p.k, rows_out + static_cast<size_t>(q) * k, cos_out + static_cast<size_t>(q) * k);
@@ -2328,11 +2342,11 @@ constexpr uint64_t kFilterListBatchQueries = 256;    // ... and queries enqueued
 int32_t check_filter(const rlr_index *ix, const rlr_filter *f)
 {
     if (!f)
-        return fail(RLR_E_INVALID, "null filter handle");
+        return set_error(RLR_E_INVALID, "null filter handle");
     if (f->ix != ix)
-        return fail(RLR_E_INVALID, "the filter was made for another index");
+        return set_error(RLR_E_INVALID, "the filter was made for another index");
     if (f->mutations != ix->mutations.load(std::memory_order_acquire))
-        return fail(RLR_E_INVALID, "stale filter: the index was mutated after the filter was made (rows may have been renumbered)");
+        return set_error(RLR_E_INVALID, "stale filter: the index was mutated after the filter was made (rows may have been renumbered)");
     return RLR_OK;
 }
 
@@ -2350,13 +2364,7 @@ int32_t filtered_exact_enqueue(rlr_index *ix, Ctx *c, const rlr_filter *f, const
     hipLaunchKernelGGL(rlr::pack_list_kernel, dim3(std::min<uint32_t>((cap + 255) / 256, 1024)), dim3(256), 0, s, d_vals,
                        f->d_list.get(), n, d_packed, cap, st);
     RLR_HIP(hipGetLastError());
-    if (p.k <= kLdsSortCap) {
-        hipLaunchKernelGGL(rlr::topk_global_kernel, dim3(1), dim3(1024), 0, s, d_packed, st, cap, d_out, p.k);
-    } else {
-        RLR_HIP(launch_sort_desc(d_packed, cap, s));
-        hipLaunchKernelGGL(rlr::emit_kernel, dim3((p.k + 255) / 256), dim3(256), 0, s, d_packed, n, d_out, p.k);
-    }
-    RLR_HIP(hipGetLastError());
+    RLR_HIP(enqueue_order_emit(d_packed, st, cap, n, d_out, p.k, s));
     return RLR_OK;
 }
 
@@ -2387,31 +2395,17 @@ int32_t filtered_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *
     // k is clamped to the allowed rows BEFORE the plan: the histogram of a masked scan counts n_allowed scores
     const SearchPlan p = make_plan(ix, query, 1, static_cast<uint32_t>(std::min<uint64_t>(k, f->n_allowed)), guard_eps);
     RLR_TRY(ctx_prepare(ix, c, 1, p));
-    const size_t q_bytes = static_cast<size_t>(ix->q_pitch) * sizeof(float);
-    RLR_TRY(pin_reserve(c, q_bytes + (static_cast<size_t>(p.k) + 1) * sizeof(uint64_t)));
-    float *h_q = static_cast<float *>(c->h_pin.get());
-    uint64_t *h_res = reinterpret_cast<uint64_t *>(static_cast<char *>(c->h_pin.get()) + q_bytes);
-    uint64_t *h_meta = h_res + p.k;
-    stage_queries(ix, c, query, 1, h_q);
+    Staged pin;
+    RLR_TRY(stage_call(ix, c, query, 1, static_cast<size_t>(p.k) + 1, /*for_scans=*/false, &pin));
+    uint64_t *h_res = pin.h_res, *h_meta = h_res + p.k;
     hipStream_t s = c->stream;
-    c->h_q_kq = nullptr;
-    RLR_HIP(upload_queries(c, h_q, q_bytes, s));
     const bool timed = ix->profiling;
     uint64_t n_cand = 0, n_retry = 0;
     if (f->path == 0) {
         RLR_TRY(filtered_exact(ix, c, f, p, h_res));
     } else {
         arm_meta(h_meta, 1);
-        if (c->h_assert) {
-            hipLaunchKernelGGL(rlr::hist_assert_zero_kernel, dim3(4), dim3(256), 0, s, c->d_hist.get(), 2u * kHistBins,
-                           static_cast<uint32_t *>(c->h_assert.get()));
-            RLR_HIP(hipGetLastError());
-        }
-        if (timed)
-            RLR_HIP(hipEventRecord(c->ev[0], s));
-        RLR_HIP(launch_scan_masked(scan_args(ix, c->d_query.get(), c->d_scores.get(), c->d_hist.get()), f->d_mask.get(), f->n_allowed, s));
-        if (timed)
-            RLR_HIP(hipEventRecord(c->ev[1], s));
+        RLR_HIP(enqueue_query_scan(ix, c, 0, timed, f));
         RLR_HIP(enqueue_query_rest(ix, c, 0, p, h_res, h_meta, timed, true, nullptr, nullptr, /*master_scan=*/true));
         if (timed)
             RLR_HIP(hipStreamSynchronize(s));
@@ -2480,15 +2474,11 @@ int32_t filtered_batch(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *
 {
     const SearchPlan p = make_plan(ix, queries, m, static_cast<uint32_t>(std::min<uint64_t>(k, f->n_allowed)), guard_eps);
     RLR_TRY(ctx_prepare(ix, c, m, p));
-    const size_t q_bytes = static_cast<size_t>(m) * ix->q_pitch * sizeof(float);
     const size_t n_res = static_cast<size_t>(m) * p.k;
-    RLR_TRY(pin_reserve(c, q_bytes + n_res * sizeof(uint64_t)));
-    float *h_q = static_cast<float *>(c->h_pin.get());
-    uint64_t *h_res = reinterpret_cast<uint64_t *>(static_cast<char *>(c->h_pin.get()) + q_bytes);
-    stage_queries(ix, c, queries, m, h_q);
+    Staged pin;
+    RLR_TRY(stage_call(ix, c, queries, m, n_res, /*for_scans=*/false, &pin));
+    uint64_t *h_res = pin.h_res;
     hipStream_t s = c->stream;
-    c->h_q_kq = nullptr;
-    RLR_HIP(upload_queries(c, h_q, q_bytes, s));
     const uint64_t n = ix->n_rows;
     const uint64_t s_stride = (n + 3) / 4 * 4;
     const float two_eps = p.two_eps; // the summation-order band: 2 x (0.5 x two_eps), as run_batched's shared scan
@@ -2498,7 +2488,7 @@ int32_t filtered_batch(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *
     hipError_t e = hipSuccess;
     if (!launch_scan_masked_multi(scan_args(ix, c->d_query.get(), c->d_sample.get(), nullptr), f->d_mask.get(), f->n_allowed, ix->q_pitch, m,
                                   s_stride, s, &e))
-        return fail(RLR_E_INTERNAL, "masked multi-query scan refused a shape its gate accepted");
+        return set_error(RLR_E_INTERNAL, "masked multi-query scan refused a shape its gate accepted");
     RLR_HIP(e);
     if (timed) RLR_HIP(hipEventRecord(c->bev[1], s));
     RLR_HIP(launch_batch_select(c->d_sample.get(), static_cast<uint32_t>(n), s_stride, m, c->d_bhist.get(), c->d_bstate.get(), two_eps, c->d_tau.get(),
@@ -2549,15 +2539,11 @@ int32_t filtered_list_batch(rlr_index *ix, Ctx *c, const rlr_filter *f, const fl
 {
     const SearchPlan p = make_plan(ix, queries, m, static_cast<uint32_t>(std::min<uint64_t>(k, f->n_allowed)), guard_eps);
     RLR_TRY(ctx_prepare(ix, c, m, p));
-    const size_t q_bytes = static_cast<size_t>(m) * ix->q_pitch * sizeof(float);
     const size_t n_res = static_cast<size_t>(m) * p.k;
-    RLR_TRY(pin_reserve(c, q_bytes + n_res * sizeof(uint64_t)));
-    float *h_q = static_cast<float *>(c->h_pin.get());
-    uint64_t *h_res = reinterpret_cast<uint64_t *>(static_cast<char *>(c->h_pin.get()) + q_bytes);
-    stage_queries(ix, c, queries, m, h_q);
+    Staged pin;
+    RLR_TRY(stage_call(ix, c, queries, m, n_res, /*for_scans=*/false, &pin));
+    uint64_t *h_res = pin.h_res;
     hipStream_t s = c->stream;
-    c->h_q_kq = nullptr;
-    RLR_HIP(upload_queries(c, h_q, q_bytes, s));
     const uint32_t cap = next_pow2(std::max<uint32_t>(static_cast<uint32_t>(f->n_allowed), p.k));
     RLR_TRY(reserve_list(c, m * cap));
     RLR_TRY(reserve_cand(c, next_pow2(m * cap)));
@@ -2578,7 +2564,7 @@ int32_t filter_finish(rlr_index *ix, std::vector<uint64_t> &&mask, rlr_filter **
 {
     std::unique_ptr<rlr_filter> f(new (std::nothrow) rlr_filter());
     if (!f)
-        return fail(RLR_E_OOM, "host allocation failed");
+        return set_error(RLR_E_OOM, "host allocation failed");
     f->ix = ix;
     f->index_rows = ix->n_rows;
     f->mutations = ix->mutations.load(std::memory_order_acquire);
@@ -2603,7 +2589,7 @@ int32_t filter_finish(rlr_index *ix, std::vector<uint64_t> &&mask, rlr_filter **
     if (e == hipSuccess)
         e = hipStreamSynchronize(s);
     if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? RLR_E_OOM : RLR_E_HIP, "filter upload failed: %s", hipGetErrorString(e));
+        return set_error(e == hipErrorOutOfMemory ? RLR_E_OOM : RLR_E_HIP, "filter upload failed: %s", hipGetErrorString(e));
     *out = f.release();
     return RLR_OK;
 }
@@ -2611,10 +2597,10 @@ int32_t filter_finish(rlr_index *ix, std::vector<uint64_t> &&mask, rlr_filter **
 int32_t filter_create_check(rlr_index *ix, rlr_filter **out)
 {
     if (!out)
-        return fail(RLR_E_INVALID, "out is null");
+        return set_error(RLR_E_INVALID, "out is null");
     *out = nullptr;
     if (rlr_device_count() <= 0)
-        return fail(RLR_E_NO_DEVICE, "no HIP device is visible (this library has no CPU path)");
+        return set_error(RLR_E_NO_DEVICE, "no HIP device is visible (this library has no CPU path)");
     RLR_TRY(check_handle(ix));
     return use_device(ix);
 }
@@ -2664,7 +2650,7 @@ void coalesce_run(rlr_index *ix, CoalesceGroup *g, float guard_eps)
         try {
             qs.resize(static_cast<size_t>(nq) * ix->dim);
         } catch (const std::bad_alloc &) {
-            st = fail(RLR_E_OOM, "host allocation failed");
+            st = set_error(RLR_E_OOM, "host allocation failed");
         }
         for (uint32_t i = 0; st == RLR_OK && i < nq; ++i)
             std::memcpy(qs.data() + static_cast<size_t>(i) * ix->dim, g->members[i]->query, ix->dim * sizeof(float));
@@ -2676,7 +2662,7 @@ void coalesce_run(rlr_index *ix, CoalesceGroup *g, float guard_eps)
         if (st == RLR_OK)
             st = run_search(ix, lease.c, qs.data(), nq, kmax, guard_eps, nullptr, &p, &h, /*coalesced=*/true, &handed);
         if (st == RLR_OK && !h)
-            st = fail(RLR_E_INTERNAL, "search produced no result buffer");
+            st = set_error(RLR_E_INTERNAL, "search produced no result buffer");
         if (st == RLR_OK) {
             ran = true;
             for (uint32_t i = 0; i < nq; ++i) {
@@ -2721,7 +2707,7 @@ int32_t coalesced_search(rlr_index *ix, const float *query, uint32_t k, float gu
         }
         ix->co_cv.wait(lk, [&] { return g->done; });
         if (g->status != RLR_OK)
-            return fail(g->status, "%s", g->msg);
+            return set_error(g->status, "%s", g->msg);
         return RLR_OK;
     }
     const bool idle = ix->co_running < kCoalesceInflight && ix->co_pending.empty();
@@ -2830,20 +2816,20 @@ float rlr_default_guard_eps(uint32_t dim)
 int32_t rlr_index_create(uint32_t dim, int32_t dtype, int32_t device_id, rlr_index **out)
 {
     if (!out)
-        return fail(RLR_E_INVALID, "out is null");
+        return set_error(RLR_E_INVALID, "out is null");
     *out = nullptr;
     if (dim == 0 || dim > kMaxDim)
-        return fail(RLR_E_INVALID, "dim must be in [1, %u]", kMaxDim);
+        return set_error(RLR_E_INVALID, "dim must be in [1, %u]", kMaxDim);
     if (dtype != RLR_F32 && dtype != RLR_F16)
-        return fail(RLR_E_INVALID, "unknown dtype %d", dtype);
+        return set_error(RLR_E_INVALID, "unknown dtype %d", dtype);
     int n_dev = rlr_device_count();
     if (n_dev <= 0)
-        return fail(RLR_E_NO_DEVICE, "no HIP device is visible (this library has no CPU path)");
+        return set_error(RLR_E_NO_DEVICE, "no HIP device is visible (this library has no CPU path)");
     if (device_id < 0 || device_id >= n_dev)
-        return fail(RLR_E_NO_DEVICE, "device %d out of range (%d visible)", device_id, n_dev);
+        return set_error(RLR_E_NO_DEVICE, "device %d out of range (%d visible)", device_id, n_dev);
     rlr_index *ix = new (std::nothrow) rlr_index();
     if (!ix)
-        return fail(RLR_E_OOM, "host allocation failed");
+        return set_error(RLR_E_OOM, "host allocation failed");
     ix->dim = dim;
     ix->dtype = dtype;
     ix->device = device_id;
@@ -2853,7 +2839,7 @@ int32_t rlr_index_create(uint32_t dim, int32_t dtype, int32_t device_id, rlr_ind
     hipDeviceProp_t prop;
     if (hipSetDevice(device_id) != hipSuccess || hipGetDeviceProperties(&prop, device_id) != hipSuccess) {
         delete ix;
-        return fail(RLR_E_HIP, "cannot query device %d", device_id);
+        return set_error(RLR_E_HIP, "cannot query device %d", device_id);
     }
     ix->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (const char *v = getenv("RLR_SCAN_VARIANT"))
@@ -2906,7 +2892,7 @@ int32_t rlr_index_upload(rlr_index *ix, const float *rows, uint64_t n_rows, int3
     RLR_TRY(check_handle(ix));
     ix->mutations.fetch_add(1, std::memory_order_acq_rel); // (row filters made before this call are stale from here on)
     if (n_rows && !rows)
-        return fail(RLR_E_INVALID, "rows is null");
+        return set_error(RLR_E_INVALID, "rows is null");
     RLR_TRY(use_device(ix));
     ix->n_rows = 0;
     ix->max_row_sumsq = 1.0f;
@@ -2923,7 +2909,7 @@ int32_t rlr_index_append(rlr_index *ix, const float *rows, uint64_t n_rows, int3
     RLR_TRY(check_handle(ix));
     ix->mutations.fetch_add(1, std::memory_order_acq_rel); // (row filters made before this call are stale from here on)
     if (n_rows && !rows)
-        return fail(RLR_E_INVALID, "rows is null");
+        return set_error(RLR_E_INVALID, "rows is null");
     RLR_TRY(use_device(ix));
     const uint64_t first = ix->n_rows;
     RLR_TRY(ensure_rows(ix, first + n_rows));
@@ -2940,15 +2926,15 @@ int32_t rlr_index_delete_rows(rlr_index *ix, const uint64_t *rows, uint64_t n)
     if (n == 0)
         return RLR_OK;
     if (!rows)
-        return fail(RLR_E_INVALID, "rows is null");
+        return set_error(RLR_E_INVALID, "rows is null");
     ix->mutations.fetch_add(1, std::memory_order_acq_rel); // (deletion renumbers rows: a filter made before it names other rows now)
     RLR_TRY(use_device(ix));
     const uint64_t N = ix->n_rows;
     std::vector<uint8_t> dead(N, 0);
     for (uint64_t i = 0; i < n; ++i) {
         if (rows[i] >= N)
-            return fail(RLR_E_RANGE, "row %llu out of range (index holds %llu rows)",
-                        static_cast<unsigned long long>(rows[i]), static_cast<unsigned long long>(N));
+            return set_error(RLR_E_RANGE, "row %llu out of range (index holds %llu rows)",
+                             static_cast<unsigned long long>(rows[i]), static_cast<unsigned long long>(N));
         dead[rows[i]] = 1;
     }
     uint64_t first_dead = 0;
@@ -2968,7 +2954,7 @@ int32_t rlr_index_delete_rows(rlr_index *ix, const uint64_t *rows, uint64_t n)
     RLR_HIP(bounce.reserve(cr * row_bytes(ix)));
     hipError_t e = keep_dev.reserve(cr);
     if (e != hipSuccess)
-        return fail(RLR_E_OOM, "compaction buffer allocation failed");
+        return set_error(RLR_E_OOM, "compaction buffer allocation failed");
     void *const d_bounce = bounce.get();
     uint32_t *const d_keep = keep_dev.get();
     int32_t st = RLR_OK;
@@ -2983,7 +2969,7 @@ int32_t rlr_index_delete_rows(rlr_index *ix, const uint64_t *rows, uint64_t n)
         if (e == hipSuccess)
             e = hipStreamSynchronize(nullptr);
         if (e != hipSuccess)
-            st = fail(RLR_E_HIP, "row compaction failed: %s", hipGetErrorString(e));
+            st = set_error(RLR_E_HIP, "row compaction failed: %s", hipGetErrorString(e));
     }
     if (st == RLR_OK) {
         ix->n_rows = first_dead + keep.size();
@@ -3009,13 +2995,13 @@ int32_t rlr_index_enable_batch_image(rlr_index *ix, int32_t enable)
     }
     if (want_q8 && !ix->q8_enabled) {
         if (ix->dim % 16 != 0 || ix->dim > 2048)
-            return fail(RLR_E_INVALID, "the 8-bit nomination copy needs dim %% 16 == 0, dim <= 2048 (dim = %u)", ix->dim);
+            return set_error(RLR_E_INVALID, "the 8-bit nomination copy needs dim %% 16 == 0, dim <= 2048 (dim = %u)", ix->dim);
         ix->q8_enabled = true;
         RLR_TRY(sync_q8(ix, 0));
     }
     if (want_image) {
         if (ix->dim % 64 != 0)
-            return fail(RLR_E_INVALID, "the nomination image needs dim %% 64 == 0 (dim = %u)", ix->dim);
+            return set_error(RLR_E_INVALID, "the nomination image needs dim %% 64 == 0 (dim = %u)", ix->dim);
         ix->image_scan = (enable & 2) != 0;
         if (!(ix->image_enabled && ix->d_image.get())) {
             ix->image_enabled = true;
@@ -3055,7 +3041,7 @@ int32_t rlr_index_fill_synthetic(rlr_index *ix, uint64_t n_rows, uint64_t row0, 
         if (e == hipSuccess)
             e = hipStreamSynchronize(nullptr);
         if (e != hipSuccess)
-            st = fail(RLR_E_HIP, "synthetic fill failed: %s", hipGetErrorString(e));
+            st = set_error(RLR_E_HIP, "synthetic fill failed: %s", hipGetErrorString(e));
         r0 += m;
     }
     if (st == RLR_OK) {
@@ -3070,9 +3056,9 @@ int32_t rlr_search_topk(rlr_index *ix, const float *queries, uint32_t n_queries,
 {
     RLR_TRY(check_handle(ix));
     if (n_queries && (!queries || !n_out))
-        return fail(RLR_E_INVALID, "queries / n_out is null");
+        return set_error(RLR_E_INVALID, "queries / n_out is null");
     if (n_queries && k && (!rows_out || !cos_out))
-        return fail(RLR_E_INVALID, "output buffers are null");
+        return set_error(RLR_E_INVALID, "output buffers are null");
     RLR_TRY(use_device(ix));
     if (ix->n_rows == 0 || k == 0) {
         for (uint32_t q = 0; q < n_queries; ++q)
@@ -3088,12 +3074,12 @@ int32_t rlr_filter_create_rows(rlr_index *ix, const uint64_t *rows, uint64_t n, 
 {
     RLR_TRY(filter_create_check(ix, out));
     if (n && !rows)
-        return fail(RLR_E_INVALID, "rows is null");
+        return set_error(RLR_E_INVALID, "rows is null");
     std::vector<uint64_t> mask((ix->n_rows + 63) / 64, 0);
     for (uint64_t i = 0; i < n; ++i) {
         if (rows[i] >= ix->n_rows)
-            return fail(RLR_E_RANGE, "row %llu out of range (index holds %llu rows)", static_cast<unsigned long long>(rows[i]),
-                        static_cast<unsigned long long>(ix->n_rows));
+            return set_error(RLR_E_RANGE, "row %llu out of range (index holds %llu rows)", static_cast<unsigned long long>(rows[i]),
+                             static_cast<unsigned long long>(ix->n_rows));
         mask[rows[i] >> 6] |= 1ull << (rows[i] & 63);
     }
     return filter_finish(ix, std::move(mask), out);
@@ -3103,15 +3089,15 @@ int32_t rlr_filter_create_ranges(rlr_index *ix, const uint64_t *first, const uin
 {
     RLR_TRY(filter_create_check(ix, out));
     if (n_ranges && (!first || !count))
-        return fail(RLR_E_INVALID, "first / count is null");
+        return set_error(RLR_E_INVALID, "first / count is null");
     std::vector<uint64_t> mask((ix->n_rows + 63) / 64, 0);
     for (uint32_t i = 0; i < n_ranges; ++i) {
         if (count[i] == 0)
             continue;
         if (first[i] >= ix->n_rows || count[i] > ix->n_rows - first[i])
-            return fail(RLR_E_RANGE, "range [%llu, +%llu) out of range (index holds %llu rows)",
-                        static_cast<unsigned long long>(first[i]), static_cast<unsigned long long>(count[i]),
-                        static_cast<unsigned long long>(ix->n_rows));
+            return set_error(RLR_E_RANGE, "range [%llu, +%llu) out of range (index holds %llu rows)",
+                             static_cast<unsigned long long>(first[i]), static_cast<unsigned long long>(count[i]),
+                             static_cast<unsigned long long>(ix->n_rows));
         const uint64_t lo = first[i], hi = first[i] + count[i]; // [lo, hi)
         for (uint64_t w = lo >> 6; w <= (hi - 1) >> 6; ++w) {
             const uint64_t b0 = std::max<uint64_t>(lo, w * 64) - w * 64, b1 = std::min<uint64_t>(hi, w * 64 + 64) - w * 64; // bits [b0, b1)
@@ -3135,7 +3121,7 @@ int32_t rlr_filter_destroy(rlr_filter *f)
 int32_t rlr_filter_info(const rlr_filter *f, uint64_t *index_rows, uint64_t *n_allowed, int32_t *path, int32_t *stale)
 {
     if (!f)
-        return fail(RLR_E_INVALID, "null filter handle");
+        return set_error(RLR_E_INVALID, "null filter handle");
     if (index_rows) *index_rows = f->index_rows;
     if (n_allowed) *n_allowed = f->n_allowed;
     if (path) *path = f->path;
@@ -3146,7 +3132,7 @@ int32_t rlr_filter_info(const rlr_filter *f, uint64_t *index_rows, uint64_t *n_a
 int32_t rlr_filter_set_path(rlr_filter *f, int32_t path)
 {
     if (!f || (path != 0 && path != 1))
-        return fail(RLR_E_INVALID, "null filter handle, or a path other than 0 / 1");
+        return set_error(RLR_E_INVALID, "null filter handle, or a path other than 0 / 1");
     f->path = path;
     return RLR_OK;
 }
@@ -3157,9 +3143,9 @@ int32_t rlr_search_topk_filtered(rlr_index *ix, const rlr_filter *f, const float
     RLR_TRY(check_handle(ix));
     RLR_TRY(check_filter(ix, f)); // (a stale filter is refused before any GPU work)
     if (n_queries && (!queries || !n_out))
-        return fail(RLR_E_INVALID, "queries / n_out is null");
+        return set_error(RLR_E_INVALID, "queries / n_out is null");
     if (n_queries && k && (!rows_out || !cos_out))
-        return fail(RLR_E_INVALID, "output buffers are null");
+        return set_error(RLR_E_INVALID, "output buffers are null");
     RLR_TRY(use_device(ix));
     for (uint32_t q = 0; q < n_queries; ++q)
         n_out[q] = 0;
@@ -3199,7 +3185,7 @@ int32_t rlr_search_topk_device(rlr_index *ix, const float *queries, uint32_t n_q
 {
     RLR_TRY(check_handle(ix));
     if (n_queries && k && (!queries || !d_packed_out))
-        return fail(RLR_E_INVALID, "queries / d_packed_out is null");
+        return set_error(RLR_E_INVALID, "queries / d_packed_out is null");
     RLR_TRY(use_device(ix));
     if (n_queries == 0 || k == 0)
         return RLR_OK;
@@ -3238,10 +3224,10 @@ int32_t rlr_search_topk_device_begin(rlr_index *ix, const float *queries, uint32
 {
     RLR_TRY(check_handle(ix));
     if (!ticket_out)
-        return fail(RLR_E_INVALID, "ticket_out is null");
+        return set_error(RLR_E_INVALID, "ticket_out is null");
     *ticket_out = nullptr;
     if (n_queries && k && (!queries || !d_packed_out))
-        return fail(RLR_E_INVALID, "queries / d_packed_out is null");
+        return set_error(RLR_E_INVALID, "queries / d_packed_out is null");
     RLR_TRY(use_device(ix));
     // anything but the plain single-query pipelines runs synchronously (ticket stays null)
     const bool timed = ix->profiling; // one query: its four events are read in end()
@@ -3276,7 +3262,7 @@ int32_t rlr_search_topk_device_begin(rlr_index *ix, const float *queries, uint32
         // pipelines already enqueued on the caller's stream still use this context's buffers: wait for them before
         // the lease hands the context back to the pool (ctx_acquire's recovery only knows the context's own stream)
         (void)hipStreamSynchronize(s);
-        return fail(RLR_E_HIP, "enqueue on the caller's stream failed: %s", hipGetErrorString(e));
+        return set_error(RLR_E_HIP, "enqueue on the caller's stream failed: %s", hipGetErrorString(e));
     }
     c->pending_stream = s;
     c->pending_timed = timed;
@@ -3326,14 +3312,14 @@ int32_t rlr_merge_topk(int32_t device_id, const void *d_gathered, uint32_t world
     if (n_queries == 0 || k == 0)
         return RLR_OK;
     if (!d_gathered || !bases || !rows_out || !cos_out || !n_out)
-        return fail(RLR_E_INVALID, "null argument");
+        return set_error(RLR_E_INVALID, "null argument");
     if (world == 0 || world > 16)
-        return fail(RLR_E_INVALID, "world size %u not in [1, 16]", world);
+        return set_error(RLR_E_INVALID, "world size %u not in [1, 16]", world);
     if (static_cast<uint64_t>(world) * k > 8192)
-        return fail(RLR_E_INVALID, "world * k = %llu exceeds the 8192-entry merge", static_cast<unsigned long long>(world) * k);
+        return set_error(RLR_E_INVALID, "world * k = %llu exceeds the 8192-entry merge", static_cast<unsigned long long>(world) * k);
     for (uint32_t r = 0; r < world; ++r) // (the merge key holds the global row in 32 bits: corpora of < 2^32 rows)
         if (bases[r] >= 0xFFFFFFFFull)
-            return fail(RLR_E_INVALID, "shard base %llu is not below 2^32 - 1", static_cast<unsigned long long>(bases[r]));
+            return set_error(RLR_E_INVALID, "shard base %llu is not below 2^32 - 1", static_cast<unsigned long long>(bases[r]));
     RLR_HIP(hipSetDevice(device_id));
     // results are written straight into pinned, device-mapped host memory: no D2H copy
     // Freed when the calling thread exits (it used to be leaked).  Intended: a thread's destructors run at its own exit,
@@ -3406,7 +3392,7 @@ int32_t rlr_score_rows(rlr_index *ix, const float *query, const uint64_t *rows, 
     if (n == 0)
         return RLR_OK;
     if (!query || !rows || !cos_out)
-        return fail(RLR_E_INVALID, "null argument");
+        return set_error(RLR_E_INVALID, "null argument");
     RLR_TRY(use_device(ix));
     CtxLease lease(ix);
     RLR_TRY(ctx_acquire(ix, &lease.c));
@@ -3427,7 +3413,7 @@ int32_t rlr_fetch_rows(rlr_index *ix, const uint64_t *rows, uint32_t n, float *o
     if (n == 0)
         return RLR_OK;
     if (!rows || !out)
-        return fail(RLR_E_INVALID, "null argument");
+        return set_error(RLR_E_INVALID, "null argument");
     RLR_TRY(use_device(ix));
     CtxLease lease(ix);
     RLR_TRY(ctx_acquire(ix, &lease.c));
@@ -3448,14 +3434,14 @@ static int32_t mmr_single_impl(rlr_index *ix, const uint64_t *pool_rows, const f
 {
     RLR_TRY(check_handle(ix));
     if (!n_out)
-        return fail(RLR_E_INVALID, "n_out is null");
+        return set_error(RLR_E_INVALID, "n_out is null");
     *n_out = 0;
     if (P == 0)
         return RLR_OK; // `if candidates.is_empty() { return vec![] }`
     if (!pool_rows || !pool_scores || !order_out)
-        return fail(RLR_E_INVALID, "null argument");
+        return set_error(RLR_E_INVALID, "null argument");
     if (P > 4096)
-        return fail(RLR_E_INVALID, "pool of %u exceeds the supported 4096 candidates", P);
+        return set_error(RLR_E_INVALID, "pool of %u exceeds the supported 4096 candidates", P);
     RLR_TRY(use_device(ix));
     CtxLease lease(ix);
     RLR_TRY(ctx_acquire(ix, &lease.c));
@@ -3500,13 +3486,13 @@ int32_t rlr_search_diverse(rlr_index *ix, const float *query, uint32_t pool, uin
 {
     RLR_TRY(check_handle(ix));
     if (!n_out || !fallback)
-        return fail(RLR_E_INVALID, "n_out / fallback is null");
+        return set_error(RLR_E_INVALID, "n_out / fallback is null");
     *n_out = 0;
     *fallback = 0;
     if (ix->n_rows == 0 || pool == 0)
         return RLR_OK;
     if (!query || !rows_out || !cos_out || !score_out)
-        return fail(RLR_E_INVALID, "null argument");
+        return set_error(RLR_E_INVALID, "null argument");
     const uint32_t n = static_cast<uint32_t>(ix->n_rows);
     const uint32_t need = std::min<uint32_t>(n, pool);
     const uint32_t fetch = static_cast<uint32_t>(std::min<uint64_t>(n, static_cast<uint64_t>(need) + 8));
@@ -3607,7 +3593,7 @@ static int32_t hybrid_begin_impl(rlr_index *ix, const float *query, uint32_t nee
     *fallback = 0;
     RLR_TRY(check_handle(ix));
     if (!query)
-        return fail(RLR_E_INVALID, "null argument");
+        return set_error(RLR_E_INVALID, "null argument");
     const uint32_t n = static_cast<uint32_t>(ix->n_rows);
     const uint32_t need = std::min<uint32_t>(n, need_in);
     const uint64_t fetch_full = std::min<uint64_t>(n, static_cast<uint64_t>(need) + n_lex_bound + 8);
@@ -3625,7 +3611,7 @@ static int32_t hybrid_begin_impl(rlr_index *ix, const float *query, uint32_t nee
     RLR_TRY(use_device(ix));
     std::unique_ptr<HybridTicket> t(new (std::nothrow) HybridTicket(ix));
     if (!t)
-        return fail(RLR_E_OOM, "host allocation failed");
+        return set_error(RLR_E_OOM, "host allocation failed");
     RLR_TRY(ctx_acquire(ix, &t->lease.c));
     Ctx *c = t->lease.c;
     hipStream_t s = c->stream;
@@ -3689,7 +3675,7 @@ static int32_t hybrid_finish_impl(HybridTicket *ticket, const HybridLexSrc &src,
     const HybridWs &ws = t->ws;
     const uint32_t n_lex = src.dev ? static_cast<uint32_t>(ws.n_lex_bound) : src.n_host;
     if (n_lex > ws.n_lex_bound || !rows_out || !cos_out || !score_out || !lex_out)
-        return fail(RLR_E_INVALID, "hybrid search: bad arguments");
+        return set_error(RLR_E_INVALID, "hybrid search: bad arguments");
     const uint32_t P = t->need, k_cap = t->k_cap, n = t->n;
     float *d_lscore = ws.lscore(n_lex);
     uint32_t *h_lex = ws.h_lex, *h_out = ws.h_out;
@@ -3704,7 +3690,7 @@ static int32_t hybrid_finish_impl(HybridTicket *ticket, const HybridLexSrc &src,
     } else {
         for (uint32_t i = 0; i < n_lex; ++i)
             if (src.h_rows[i] >= n || (i && src.h_rows[i] <= src.h_rows[i - 1]))
-                return fail(RLR_E_INVALID, "lex_rows must be ascending, unique and inside the index");
+                return set_error(RLR_E_INVALID, "lex_rows must be ascending, unique and inside the index");
         h_lex[0] = n_lex;
         h_lex[1] = __builtin_bit_cast(uint32_t, src.max_lex);
         for (uint32_t i = 0; i < n_lex; ++i)
@@ -3792,10 +3778,10 @@ int32_t search_hybrid_batch(rlr_index *ix, const float *queries, uint32_t nq, ui
     if (nq == 0 || n == 0 || need == 0 || need > kPoolMax || n_lex_bound == 0 || n_lex_bound > kHybridLexMax || !lex_launch ||
         !queries || !rows_out || !cos_out || !score_out || !lex_out || !n_out || !status || !(w_embedding > 0.0f) ||
         !std::isfinite(w_embedding) || !std::isfinite(w_lexical))
-        return fail(RLR_E_INVALID, "batched hybrid search: arguments outside the fused kernels");
+        return set_error(RLR_E_INVALID, "batched hybrid search: arguments outside the fused kernels");
     const uint32_t fetch = static_cast<uint32_t>(std::min<uint64_t>(n, static_cast<uint64_t>(need) + kHybridFetchMargin));
     if (fetch + n_lex_bound > kHybridSlots)
-        return fail(RLR_E_INVALID, "batched hybrid search: %u fetched + %u lexical rows exceed the blend's slots", fetch, n_lex_bound);
+        return set_error(RLR_E_INVALID, "batched hybrid search: %u fetched + %u lexical rows exceed the blend's slots", fetch, n_lex_bound);
     RLR_TRY(use_device(ix));
     CtxLease lease(ix);
     RLR_TRY(ctx_acquire(ix, &lease.c));
@@ -3825,7 +3811,7 @@ int32_t search_hybrid_batch(rlr_index *ix, const float *queries, uint32_t nq, ui
     const uint64_t *h = nullptr;
     RLR_TRY(run_search(ix, c, queries, nq, fetch, -1.0f, nullptr, &p, &h));
     if (!h || p.k != fetch)
-        return fail(RLR_E_INTERNAL, "batched hybrid search: the cosine batch produced no result");
+        return set_error(RLR_E_INTERNAL, "batched hybrid search: the cosine batch produced no result");
     // (the fetch goes through the host on purpose: run_search's single-query pipelines -- the planner's choice for batches
     // too small for a shared pass -- write their results straight into pinned host memory, not into c->d_out, so the host
     // copy is the one place every path leaves them; Q x fetch x 8 bytes each way)
@@ -3883,13 +3869,13 @@ int32_t rlr_search_hybrid(rlr_index *ix, const float *query, uint32_t need, uint
 {
     RLR_TRY(check_handle(ix));
     if (!n_out || !fallback)
-        return fail(RLR_E_INVALID, "n_out / fallback is null");
+        return set_error(RLR_E_INVALID, "n_out / fallback is null");
     *n_out = 0;
     *fallback = 0;
     if (ix->n_rows == 0 || need == 0)
         return RLR_OK;
     if (!query || !rows_out || !cos_out || !score_out || !lex_out || (n_lex && (!lex_rows || !lex_scores)))
-        return fail(RLR_E_INVALID, "null argument");
+        return set_error(RLR_E_INVALID, "null argument");
     rlr::HybridTicket *t = nullptr;
     RLR_TRY(rlr::hybrid_begin_impl(ix, query, need, k, lambda, diversify, w_embedding, w_lexical, n_lex, guard_eps, &t, fallback));
     if (*fallback)
@@ -3916,14 +3902,14 @@ static int32_t mmr_batch_impl(rlr_index *ix, const uint64_t *pool_rows, const fl
     if (n_queries == 0)
         return RLR_OK;
     if ((!pool_rows && !d_values) || !pool_scores || !pool_sizes || !order_out || !n_out)
-        return fail(RLR_E_INVALID, "null argument");
+        return set_error(RLR_E_INVALID, "null argument");
     if (P == 0) {
         for (uint32_t q = 0; q < n_queries; ++q)
             n_out[q] = 0;
         return RLR_OK;
     }
     if (P > 1024)
-        return fail(RLR_E_INVALID, "batched MMR supports pools of at most 1024 candidates (got %u)", P);
+        return set_error(RLR_E_INVALID, "batched MMR supports pools of at most 1024 candidates (got %u)", P);
     RLR_TRY(use_device(ix));
     CtxLease lease(ix);
     RLR_TRY(ctx_acquire(ix, &lease.c));
@@ -3940,7 +3926,7 @@ static int32_t mmr_batch_impl(rlr_index *ix, const uint64_t *pool_rows, const fl
         const uint32_t n_list = m * P;
         for (uint32_t q = 0; q < m; ++q)
             if (pool_sizes[q0 + q] > P)
-                return fail(RLR_E_INVALID, "pool_sizes[%u] = %u exceeds P = %u", q0 + q, pool_sizes[q0 + q], P);
+                return set_error(RLR_E_INVALID, "pool_sizes[%u] = %u exceeds P = %u", q0 + q, pool_sizes[q0 + q], P);
         RLR_TRY(pin_reserve(c, MmrStaging(nullptr, m, P).h.bytes));
         if (pool_rows) {
             // unused slots (j >= pool_sizes[q]) gather row 0: never read by the greedy kernel
@@ -3992,7 +3978,7 @@ int32_t rlr_mmr_select_batch(rlr_index *ix, const uint64_t *pool_rows, const flo
                              uint32_t *order_out, float *mmr_out, uint32_t *n_out)
 {
     if (n_queries && !pool_rows)
-        return fail(RLR_E_INVALID, "null argument");
+        return set_error(RLR_E_INVALID, "null argument");
     return mmr_batch_impl(ix, pool_rows, nullptr, pool_scores, pool_sizes, n_queries, P, k, lambda, order_out, mmr_out, n_out);
 }
 
@@ -4001,7 +3987,7 @@ int32_t rlr_mmr_select_values(rlr_index *ix, const void *d_values, const float *
                               float *mmr_out, uint32_t *n_out)
 {
     if (n_queries && !d_values)
-        return fail(RLR_E_INVALID, "null argument");
+        return set_error(RLR_E_INVALID, "null argument");
     return mmr_batch_impl(ix, nullptr, static_cast<const float *>(d_values), pool_scores, pool_sizes, n_queries, P, k, lambda,
                           order_out, mmr_out, n_out);
 }
@@ -4011,12 +3997,12 @@ int32_t rlr_mmr_select_staged(rlr_index *ix, const void *d_staged, uint64_t n_st
                               float lambda, uint32_t *order_out, float *mmr_out, uint32_t *n_out)
 {
     if (n_queries && (!d_staged || !pool_slots || n_staged == 0))
-        return fail(RLR_E_INVALID, "null argument");
+        return set_error(RLR_E_INVALID, "null argument");
     // one large pool: the single-pool kernels (up to 4096).  P is only the stride, which one pool does not use, so a
     // small pool in a wide slot list goes the same way
     if (n_queries == 1 && pool_sizes && (pool_sizes[0] > 1024 || P > 1024)) {
         if (pool_sizes[0] > P)
-            return fail(RLR_E_INVALID, "pool_sizes[0] = %u exceeds P = %u", pool_sizes[0], P);
+            return set_error(RLR_E_INVALID, "pool_sizes[0] = %u exceeds P = %u", pool_sizes[0], P);
         return mmr_single_impl(ix, pool_slots, pool_scores, pool_sizes[0], k, lambda, order_out, mmr_out, n_out, d_staged,
                                n_staged);
     }
@@ -4028,7 +4014,7 @@ int32_t rlr_index_row_bytes(const rlr_index *ix, uint32_t *bytes_out)
 {
     RLR_TRY(check_handle(ix));
     if (!bytes_out)
-        return fail(RLR_E_INVALID, "bytes_out is null");
+        return set_error(RLR_E_INVALID, "bytes_out is null");
     *bytes_out = static_cast<uint32_t>(row_bytes(ix));
     return RLR_OK;
 }
@@ -4039,7 +4025,7 @@ int32_t rlr_gather_rows_device(rlr_index *ix, const uint64_t *rows, uint32_t n, 
     if (n == 0)
         return RLR_OK;
     if (!rows || !d_out)
-        return fail(RLR_E_INVALID, "null argument");
+        return set_error(RLR_E_INVALID, "null argument");
     RLR_TRY(use_device(ix));
     CtxLease lease(ix);
     RLR_TRY(ctx_acquire(ix, &lease.c));
@@ -4056,7 +4042,7 @@ int32_t rlr_fetch_rows_device(rlr_index *ix, const uint64_t *rows, uint32_t n, v
     if (n == 0)
         return RLR_OK;
     if (!rows || !d_out)
-        return fail(RLR_E_INVALID, "null argument");
+        return set_error(RLR_E_INVALID, "null argument");
     RLR_TRY(use_device(ix));
     CtxLease lease(ix);
     RLR_TRY(ctx_acquire(ix, &lease.c));
@@ -4071,14 +4057,14 @@ int32_t rlr_index_probe_bandwidth(rlr_index *ix, int32_t mode, uint32_t reps, do
 {
     RLR_TRY(check_handle(ix));
     if (!gbps_out || mode < 0 || mode > 3)
-        return fail(RLR_E_INVALID, "mode must be 0 (read), 1 (copy), 2 / 3 (the scan kernel without / with its histogram), gbps_out non-null");
+        return set_error(RLR_E_INVALID, "mode must be 0 (read), 1 (copy), 2 / 3 (the scan kernel without / with its histogram), gbps_out non-null");
     *gbps_out = 0.0;
     if (ms_out)
         *ms_out = 0.0;
     RLR_TRY(use_device(ix));
     const size_t bytes = static_cast<size_t>(ix->n_rows) * row_bytes(ix);
     if (bytes < (1u << 20))
-        return fail(RLR_E_INVALID, "the probe needs at least 1 MiB of rows");
+        return set_error(RLR_E_INVALID, "the probe needs at least 1 MiB of rows");
     reps = std::max(reps, 1u);
     CtxLease lease(ix);
     RLR_TRY(ctx_acquire(ix, &lease.c));
@@ -4123,7 +4109,7 @@ int32_t rlr_index_probe_bandwidth(rlr_index *ix, int32_t mode, uint32_t reps, do
     } else {
         const size_t half = std::min<size_t>(bytes / 2, 4ull << 30) & ~static_cast<size_t>(255);
         if (scratch_buf.reserve(half) != hipSuccess)
-            return fail(RLR_E_OOM, "scratch allocation of %zu bytes for the copy probe failed", half);
+            return set_error(RLR_E_OOM, "scratch allocation of %zu bytes for the copy probe failed", half);
         void *const scratch = scratch_buf.get();
         moved = 2 * half;
         st = timed([&] { return hipMemcpyAsync(scratch, ix->d_rows.get(), half, hipMemcpyDeviceToDevice, s); });
@@ -4141,9 +4127,9 @@ int32_t rlr_index_set_coalescing(rlr_index *ix, uint32_t max_group, uint32_t lin
 {
     RLR_TRY(check_handle(ix));
     if (max_group > 8)
-        return fail(RLR_E_INVALID, "max_group %u: at most 8 queries share one pass", max_group);
+        return set_error(RLR_E_INVALID, "max_group %u: at most 8 queries share one pass", max_group);
     if (linger_us > 1000000)
-        return fail(RLR_E_INVALID, "linger_us %u: at most 1 s", linger_us);
+        return set_error(RLR_E_INVALID, "linger_us %u: at most 1 s", linger_us);
     {
         std::lock_guard<std::mutex> lk(ix->co_mu);
         ix->co_linger_us = linger_us;
@@ -4156,7 +4142,7 @@ int32_t rlr_index_coalesce_stats(rlr_index *ix, rlr_coalesce_stats *out, int32_t
 {
     RLR_TRY(check_handle(ix));
     if (!out)
-        return fail(RLR_E_INVALID, "out is null");
+        return set_error(RLR_E_INVALID, "out is null");
     std::lock_guard<std::mutex> lk(ix->co_mu);
     *out = ix->co_stats;
     if (reset)
@@ -4175,7 +4161,7 @@ int32_t rlr_profile_read(rlr_index *ix, rlr_profile *out, int32_t reset)
 {
     RLR_TRY(check_handle(ix));
     if (!out)
-        return fail(RLR_E_INVALID, "out is null");
+        return set_error(RLR_E_INVALID, "out is null");
     std::lock_guard<std::mutex> lk(ix->mu);
     *out = ix->prof;
     if (reset)
@@ -4189,7 +4175,7 @@ namespace rlr {
 int32_t filter_view(const rlr_filter *f, FilterView *out)
 {
     if (!f)
-        return fail(RLR_E_INVALID, "null filter handle");
+        return set_error(RLR_E_INVALID, "null filter handle");
     RLR_TRY(check_filter(f->ix, f));
     out->h_mask = f->h_mask.data();
     out->d_mask = f->d_mask.get();

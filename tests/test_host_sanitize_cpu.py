@@ -62,8 +62,9 @@ def test_pools_locks_and_leases_under_thread_sanitizer(tmp_path):
     with a simulated device latency so that callers really queue on the condition variables, and a mutation between
     rounds.  Pass = no ThreadSanitizer report, no deadlock (timeout), every call returned RLR_OK."""
     csrc = os.path.join(ROOT, "rust-local-rag_amd", "csrc")
-    units = ["scan.hip", "select.hip", "tail.hip", "exact.hip", "gemm.hip", "index.hip", "engine.cpp", "multi.cpp", "lexical.hip",
-             "q8.hip", "jsonio.cpp"]
+    import __graft_entry__  # (the repository root is on sys.path: tests/conftest.py)
+
+    units = __graft_entry__._load_build_module().SOURCES  # the library's one list of translation units
     san = ["-fsanitize=thread", "-g", "-O1"]
     procs, objs = [], []
     for u in units:
