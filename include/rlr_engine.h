@@ -157,12 +157,27 @@ int32_t rlr_engine_search_text_filtered(rlr_index *idx, rlr_lexical *lex, const 
  * rlr_search_topk_filtered call -- chunks of up to 8 queries share one masked pass over f32 rows of 256 / 512 / 768 /
  * 1024 elements; binary16 rows, other widths and other pitches run query by query -- and the MMR from
  * rlr_mmr_select_batch.  Argument checks and error codes of rlr_engine_search_with_diversity_batch; a stale filter, or
- * one of another index: RLR_E_INVALID before any GPU work.  Batched TEXT search inside a filter (a masked batched
- * BM25) does not exist: callers with query text loop rlr_engine_search_text_filtered. */
+ * one of another index: RLR_E_INVALID before any GPU work.  Queries WITH text inside a filter:
+ * rlr_engine_search_text_batch_filtered below. */
 int32_t rlr_engine_search_with_diversity_batch_filtered(rlr_index *idx, const rlr_filter *f, const float *queries_raw,
                                                         uint32_t dq, uint32_t n_queries, uint32_t top_k,
                                                         float diversity_factor, const rlr_query_weights *weights,
                                                         rlr_search_hit *out, uint32_t cap, uint32_t *n_out);
+/* rlr_engine_search_text_batch inside a filter: query q equals rlr_engine_search_text_filtered(query q, tokens q), bit
+ * for bit, N = |F| everywhere (|F| = 0: no hits, RLR_OK).  Per sub-batch of up to 256 queries: one masked batched BM25
+ * (rlr_lexical_score_batch_filtered, limit = 5 * k_seen as the single call computes it), one rlr_search_topk_filtered
+ * call for all queries with fetch = min(|F|, need + the longest lexical list + 8), one batched scoring of every query's
+ * lexical rows, the single call's blend arithmetic per query on the host, one rlr_mmr_select_batch -- one host
+ * synchronisation per stage.  A query whose rounding-tie chain reaches the last fetched row is re-run alone through
+ * rlr_engine_search_text_filtered (info->n_single_blend); the whole call loops that entry point (n_single_shape) when
+ * w_embedding == 0, a weight is not finite, more than 1024 candidates are kept, or the batch has one query.  A query with more than 128 unique
+ * known terms has its BM25 scored alone inside the lexical call and stays in the batch.  Argument checks of
+ * rlr_engine_search_text_batch; a null, stale or foreign filter: RLR_E_INVALID before any GPU work. */
+int32_t rlr_engine_search_text_batch_filtered(rlr_index *idx, rlr_lexical *lex, const rlr_filter *f, const float *queries_raw,
+                                              uint32_t dq, uint32_t n_queries, const char *tokens,
+                                              const uint64_t *token_offsets, uint32_t top_k, float diversity_factor,
+                                              int32_t stage, const rlr_query_weights *weights, rlr_search_hit *out,
+                                              uint32_t cap, uint32_t *n_out, rlr_text_batch_info *info);
 
 /* Additive batched entry point (the reference has no batched API; its oracle is "loop
  * search_with_diversity over the batch"): n_queries raw query embeddings,

@@ -117,6 +117,19 @@ int32_t rlr_lexical_score_batch(rlr_lexical *lex, uint32_t n_queries, const char
                                 float *scores_out, uint32_t *n_out, float *max_lexical_out,
                                 uint32_t *n_single);
 
+/* rlr_lexical_score_batch restricted to the rows of a filter: the same arguments and result layout with the filter
+ * behind `lex`, and query q's result exactly what rlr_lexical_score_filtered(lex, f, tokens_q, len_q, limit, ...)
+ * returns -- the same rows, order and score bits (corpus statistics of the whole index, masked rows never accumulated).
+ * One chain of the batched kernels per sub-batch of 256 queries: a workgroup of the accumulate kernel owns 2048 rows,
+ * reads its 32 words of the mask first and leaves at once when none has a bit set, so a narrow filter pays for its own
+ * rows only.  `limit` 1 .. RLR_LEXICAL_MAX_LIMIT; queries with more than 128 unique known terms go through
+ * rlr_lexical_score_filtered and count in *n_single.  A stale filter, or one on another device: RLR_E_INVALID before any
+ * GPU work; an empty filter: zero pairs per query, RLR_OK. */
+int32_t rlr_lexical_score_batch_filtered(rlr_lexical *lex, const rlr_filter *f, uint32_t n_queries, const char *tokens,
+                                         const uint64_t *token_offsets, uint32_t limit, uint64_t *rows_out,
+                                         float *scores_out, uint32_t *n_out, float *max_lexical_out,
+                                         uint32_t *n_single);
+
 /* Convenience tokenizer for hosts without Unicode tables: exact for ASCII text; every
  * non-ASCII code point is treated as alphanumeric and left unchanged (the reference would
  * split at non-ASCII punctuation and lower-case non-ASCII letters).  Writes the space-joined

@@ -1,5 +1,5 @@
 // engine_filtered.cpp -- rlr_engine_search_filtered / _search_with_diversity_filtered / _search_text_filtered /
-// _search_with_diversity_batch_filtered
+// _search_with_diversity_batch_filtered / _search_text_batch_filtered
 // (include/rlr_engine.h): RagEngine::search / search_with_diversity inside a row filter.  The corpus the reference's
 // code sees is the filter's rows in ascending order: the host half is engine_host.h over a backend whose candidate
 // universe is the filter -- its size where the reference uses the corpus size, its bit where a lexical pair is checked
@@ -11,6 +11,7 @@
 #include "../../include/rlr_lexical.h"
 #include "engine_host.h"
 #include "filter_internal.h"
+#include "lexical_internal.h"
 
 #include <algorithm>
 #include <cmath>
@@ -176,6 +177,159 @@ int32_t rlr_engine_search_with_diversity_batch_filtered(rlr_index *idx, const rl
         return st;
     for (uint32_t q = 0; q < n_queries; ++q)
         emit(results[q], out + static_cast<size_t>(q) * cap, cap, &n_out[q]);
+    return RLR_OK;
+}
+
+// rlr_engine_search_text_filtered for many queries: per sub-batch ONE masked batched BM25, ONE rlr_search_topk_filtered call,
+// ONE scoring of every query's lexical rows, the arithmetic of blend_search's w_embedding != 0 branch per query
+// (blend_fetched: the same union, combine, order and boundary rule) and ONE batched MMR.  A wider fetch than the single
+// call's changes nothing: where the boundary rule holds, the first `need` candidates are the first `need` of the whole
+// universe, whichever fetch showed it.
+int32_t rlr_engine_search_text_batch_filtered(rlr_index *idx, rlr_lexical *lex, const rlr_filter *f, const float *queries_raw,
+                                              uint32_t dq, uint32_t n_queries, const char *tokens, const uint64_t *token_offsets,
+                                              uint32_t top_k, float diversity_factor, int32_t stage,
+                                              const rlr_query_weights *weights, rlr_search_hit *out, uint32_t cap, uint32_t *n_out,
+                                              rlr_text_batch_info *info)
+{
+    if (info)
+        *info = rlr_text_batch_info{};
+    if (!idx || !lex || !f || (n_queries && (!n_out || !token_offsets || (dq && !queries_raw))))
+        return RLR_E_INVALID;
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        if (token_offsets[q + 1] < token_offsets[q])
+            return RLR_E_INVALID;
+    }
+    if (n_queries && token_offsets[n_queries] > token_offsets[0] && !tokens)
+        return RLR_E_INVALID;
+    for (uint32_t q = 0; q < n_queries; ++q)
+        n_out[q] = 0;
+    int32_t st = rlr::filter_check(idx, f); // a stale filter, or one of another index: before any GPU work
+    if (st != RLR_OK)
+        return st;
+    FilteredBackend be;
+    st = filtered_backend(idx, f, &be);
+    if (st != RLR_OK)
+        return st;
+    const uint64_t N = be.n_rows;
+    if (n_queries == 0 || N == 0) // :476-478
+        return RLR_OK;
+    // the sizes rlr_engine_search_text_filtered works with
+    float lambda = diversity_factor;
+    if (lambda < 0.0f) lambda = 0.0f;
+    if (lambda > 1.0f) lambda = 1.0f;
+    const bool diversify = !(lambda == 0.0f);
+    rlr_resolved_weights w;
+    rlr_resolve_weights(weights, &w);
+    const uint32_t k_seen = std::max<uint32_t>(diversify ? pool_size_of(top_k) : top_k, 1u);
+    const uint32_t limit = static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(k_seen) * 5, 0xFFFFFFFFull));
+    const uint32_t lcap = std::min<uint32_t>(limit, RLR_LEXICAL_MAX_LIMIT);
+    const uint64_t need = need_of(N, diversify ? pool_size_of(top_k) : top_k, diversify ? 0 : stage);
+    const uint64_t n_res = rlr::result_k_cap(top_k, static_cast<uint32_t>(std::min<uint64_t>(need, 0xFFFFFFFFull)), diversify);
+    if (!out || cap < n_res)
+        return RLR_E_INVALID; // (cap below the result count of a query)
+    auto single = [&](uint32_t q) {
+        return rlr_engine_search_text_filtered(idx, lex, f, queries_raw ? queries_raw + static_cast<size_t>(q) * dq : nullptr, dq,
+                                               tokens ? tokens + token_offsets[q] : nullptr,
+                                               static_cast<size_t>(token_offsets[q + 1] - token_offsets[q]), top_k, diversity_factor,
+                                               stage, weights, out + static_cast<size_t>(q) * cap, cap, &n_out[q]);
+    };
+    // the shapes the unscoped batch hands to the single entry point as well
+    if (w.embedding == 0.0f || !std::isfinite(w.embedding) || !std::isfinite(w.lexical) || need > 1024 || n_queries == 1) {
+        for (uint32_t q = 0; q < n_queries; ++q)
+            if ((st = single(q)) != RLR_OK)
+                return st;
+        if (info) {
+            info->n_single = n_queries;
+            info->n_single_shape = n_queries;
+        }
+        return RLR_OK;
+    }
+    const uint32_t nd = static_cast<uint32_t>(need);
+    const uint32_t sub = std::min(text_sub_batch(nd, diversify), n_queries);
+    std::vector<uint64_t> lrows(static_cast<size_t>(sub) * lcap), rows, lists, prow;
+    std::vector<float> lscores(lrows.size()), qn(static_cast<size_t>(sub) * be.dim), cosv, lcos, psc;
+    std::vector<uint32_t> n_lex(sub), got(sub), counts(sub), psz(sub), order, nsel(sub), redo;
+    std::vector<LexPrep> lexp(sub);
+    std::vector<std::vector<Cand>> pools(sub);
+    std::vector<char> seen, undecided(sub);
+    for (uint32_t q0 = 0; q0 < n_queries; q0 += sub) {
+        const uint32_t m = std::min(sub, n_queries - q0);
+        // 1. BM25 of every query inside the filter
+        st = rlr_lexical_score_batch_filtered(lex, f, m, tokens, token_offsets + q0, lcap, lrows.data(), lscores.data(), n_lex.data(),
+                                              nullptr, nullptr);
+        if (st != RLR_OK)
+            return st;
+        // 2. the queries and the lexical maps, as generic_search prepares them
+        if (dq)
+            prepare_queries(queries_raw + static_cast<size_t>(q0) * dq, dq, m, be.dim, qn.data());
+        else
+            std::fill(qn.begin(), qn.end(), 0.0f);
+        uint32_t max_lex = 0;
+        for (uint32_t q = 0; q < m; ++q) {
+            lexp[q] = prepare_lexical_in([&be](uint64_t row) { return be.holds(row); }, lrows.data() + static_cast<size_t>(q) * lcap,
+                                         lscores.data() + static_cast<size_t>(q) * lcap, n_lex[q]);
+            counts[q] = static_cast<uint32_t>(lexp[q].rows.size());
+            max_lex = std::max(max_lex, counts[q]);
+        }
+        // 3. one top-k call: every query fetches what the query with the longest lexical list needs
+        const uint32_t fetch = static_cast<uint32_t>(std::min<uint64_t>(N, need + max_lex + 8));
+        rows.assign(static_cast<size_t>(m) * fetch, 0);
+        cosv.assign(rows.size(), 0.0f);
+        st = be.topk(qn.data(), m, fetch, rows.data(), cosv.data(), got.data());
+        if (st != RLR_OK)
+            return st;
+        // 4. exact cosines of every query's lexical rows
+        lists.assign(static_cast<size_t>(m) * max_lex, 0);
+        lcos.assign(lists.size(), 0.0f);
+        for (uint32_t q = 0; q < m; ++q)
+            std::copy(lexp[q].rows.begin(), lexp[q].rows.end(), lists.begin() + static_cast<size_t>(q) * max_lex);
+        st = rlr::score_rows_batch(idx, qn.data(), m, lists.data(), counts.data(), max_lex, lcos.data());
+        if (st != RLR_OK)
+            return st;
+        // 5. blend per query
+        for (uint32_t q = 0; q < m; ++q) {
+            undecided[q] = !blend_fetched(w, lexp[q], lcos.data() + static_cast<size_t>(q) * max_lex, rows.data() + static_cast<size_t>(q) * fetch,
+                                          cosv.data() + static_cast<size_t>(q) * fetch, got[q], N, need, seen, pools[q]);
+            if (undecided[q])
+                redo.push_back(q0 + q); // the single call widens its fetch
+            if (pools[q].size() > need)
+                pools[q].resize(need);
+        }
+        // 6. one MMR over the pools (generic_search_with_diversity per query)
+        if (diversify) {
+            prow.assign(static_cast<size_t>(m) * nd, 0);
+            psc.assign(prow.size(), 0.0f);
+            order.assign(prow.size(), 0);
+            for (uint32_t q = 0; q < m; ++q) {
+                psz[q] = static_cast<uint32_t>(pools[q].size()); // (an undecided query's as well: overwritten below)
+                for (uint32_t i = 0; i < psz[q]; ++i) {
+                    prow[static_cast<size_t>(q) * nd + i] = pools[q][i].row;
+                    psc[static_cast<size_t>(q) * nd + i] = pools[q][i].c;
+                }
+            }
+            st = be.mmr(prow.data(), psc.data(), psz.data(), m, nd, top_k, lambda, order.data(), nsel.data());
+            if (st != RLR_OK)
+                return st;
+            std::vector<Cand> picked;
+            for (uint32_t q = 0; q < m; ++q) {
+                picked.clear();
+                for (uint32_t i = 0; i < nsel[q]; ++i)
+                    picked.push_back(pools[q][order[static_cast<size_t>(q) * nd + i]]);
+                pools[q].swap(picked);
+            }
+        }
+        for (uint32_t q = 0; q < m; ++q)
+            if (!undecided[q])
+                emit(pools[q], out + static_cast<size_t>(q0 + q) * cap, cap, &n_out[q0 + q]);
+    }
+    for (uint32_t q : redo)
+        if ((st = single(q)) != RLR_OK)
+            return st;
+    if (info) {
+        info->n_single_blend = static_cast<uint32_t>(redo.size());
+        info->n_single = info->n_single_blend;
+        info->n_batched = n_queries - info->n_single;
+    }
     return RLR_OK;
 }
 

@@ -172,6 +172,40 @@ inline uint32_t pool_size_of(uint32_t top_k) // max(3k, k + 10) (:734)
     return static_cast<uint32_t>(std::min<uint64_t>(std::max(p3, p10), 0xFFFFFFFFull));
 }
 
+// One round of blend_search's w_embedding != 0 branch, from a fetch that is already on the host: the `got` best rows of the
+// universe by cosine (rows / cosv) united with the lexical rows (their exact cosines in lcos), combined and ordered into
+// `cands`.  true: the fetch decides the first `need` candidates -- it holds the whole universe (got >= N) or nothing, or
+// the need-th combined score lies strictly above the bound on every unfetched row; false: a rounding-tie chain reaches the
+// last fetched row (or fewer than `need` candidates came together) and the fetch has to be widened.  `seen`: scratch.
+inline bool blend_fetched(const rlr_resolved_weights &w, const LexPrep &lex, const float *lcos, const uint64_t *rows,
+                          const float *cosv, uint32_t got, uint64_t N, uint64_t need, std::vector<char> &seen,
+                          std::vector<Cand> &cands)
+{
+    const std::vector<uint64_t> &lrows = lex.rows;
+    cands.clear();
+    seen.assign(lrows.size(), 0);
+    for (uint32_t i = 0; i < got; ++i) {
+        float l = 0.0f;
+        const auto it = std::lower_bound(lrows.begin(), lrows.end(), rows[i]);
+        if (it != lrows.end() && *it == rows[i]) {
+            const size_t j = static_cast<size_t>(it - lrows.begin());
+            l = lex.scores[j] / lex.max_lex;
+            seen[j] = 1;
+        }
+        cands.push_back({rows[i], combine(w, cosv[i], l), cosv[i], l});
+    }
+    for (size_t i = 0; i < lrows.size(); ++i)
+        if (!seen[i]) {
+            const float l = lex.scores[i] / lex.max_lex;
+            cands.push_back({lrows[i], combine(w, lcos[i], l), lcos[i], l});
+        }
+    std::sort(cands.begin(), cands.end(), cand_before);
+    if (got >= N || got == 0)
+        return true;
+    const float c_tail = combine(w, cosv[got - 1], 0.0f); // bound on every unfetched row
+    return cands.size() >= need && (std::isnan(c_tail) || cands[need - 1].c > c_tail);
+}
+
 // search() from the prepared query on (:496-565, :667-698), exact-scan branch, reranker absent: `need` candidates by
 // (combined desc, row asc).  The part of search_impl that needs nothing but topk / score_rows.
 template <typename B>
@@ -218,7 +252,7 @@ int32_t blend_search(const B &be, const std::vector<float> &q, uint64_t need, co
         uint64_t fetch = std::min<uint64_t>(N, need + lrows.size() + 8);
         std::vector<uint64_t> rows;
         std::vector<float> cosv;
-        std::vector<char> seen(lrows.size());
+        std::vector<char> seen;
         for (;;) {
             rows.assign(fetch, 0);
             cosv.assign(fetch, 0.0f);
@@ -226,28 +260,7 @@ int32_t blend_search(const B &be, const std::vector<float> &q, uint64_t need, co
             st = be.topk(q.data(), 1, static_cast<uint32_t>(fetch), rows.data(), cosv.data(), &got);
             if (st != RLR_OK)
                 return st;
-            cands.clear();
-            std::fill(seen.begin(), seen.end(), 0);
-            for (uint32_t i = 0; i < got; ++i) {
-                float l = 0.0f;
-                const auto it = std::lower_bound(lrows.begin(), lrows.end(), rows[i]);
-                if (it != lrows.end() && *it == rows[i]) {
-                    const size_t j = static_cast<size_t>(it - lrows.begin());
-                    l = lex.scores[j] / lex.max_lex;
-                    seen[j] = 1;
-                }
-                cands.push_back({rows[i], combine(w, cosv[i], l), cosv[i], l});
-            }
-            for (size_t i = 0; i < lrows.size(); ++i)
-                if (!seen[i]) {
-                    const float l = lex.scores[i] / lex.max_lex;
-                    cands.push_back({lrows[i], combine(w, lcos[i], l), lcos[i], l});
-                }
-            std::sort(cands.begin(), cands.end(), cand_before);
-            if (got >= N || got == 0)
-                break;
-            const float c_tail = combine(w, cosv[got - 1], 0.0f); // bound on every unfetched row
-            if (cands.size() >= need && (std::isnan(c_tail) || cands[need - 1].c > c_tail))
+            if (blend_fetched(w, lex, lcos.data(), rows.data(), cosv.data(), got, N, need, seen, cands))
                 break;
             fetch = std::min<uint64_t>(N, fetch * 2);
         }
@@ -256,6 +269,16 @@ int32_t blend_search(const B &be, const std::vector<float> &q, uint64_t need, co
         cands.resize(need);
     result.swap(cands);
     return RLR_OK;
+}
+
+// Queries per sub-batch of a batched text search that keeps `need` candidates per query: one GEMM query block of 256, fewer
+// when the sub-batch's Gram matrices (diversify: need x need floats per query) would exceed 256 MB; two at the least.
+inline uint32_t text_sub_batch(uint32_t need, bool diversify)
+{
+    constexpr uint32_t kSubBatch = 256;
+    const uint64_t nd = std::max<uint64_t>(need, 1);
+    const uint64_t gram_q = diversify ? std::max<uint64_t>(1, (64ull << 20) / (nd * nd)) : kSubBatch;
+    return static_cast<uint32_t>(std::max<uint64_t>(2, std::min<uint64_t>(kSubBatch, gram_q)));
 }
 
 // how many candidates search(top_k) keeps: the initial_k a reranker would get (stage 1, :544) or the final cut (:667-698)

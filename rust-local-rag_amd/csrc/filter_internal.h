@@ -19,4 +19,10 @@ int32_t filter_view(const rlr_filter *f, FilterView *out);
 // the same, and RLR_E_INVALID for a filter that was made for another index than `ix`; no GPU work
 int32_t filter_check(const rlr_index *ix, const rlr_filter *f);
 
+// rlr_score_rows for nq prepared (dim-long) queries with a row list each, for the batched text search inside a filter:
+// query q against rows[q * stride .. q * stride + counts[q]) -> cos_out at the same places, bit for bit what
+// rlr_score_rows returns per pair.  One upload, one launch, one copy back, one synchronisation.
+int32_t score_rows_batch(rlr_index *ix, const float *queries, uint32_t nq, const uint64_t *rows, const uint32_t *counts,
+                         uint32_t stride, float *cos_out);
+
 } // namespace rlr

@@ -4189,4 +4189,52 @@ int32_t filter_check(const rlr_index *ix, const rlr_filter *f)
 {
     return check_filter(ix, f);
 }
+
+// rlr_score_rows for nq queries with a list each: queries, lists and counts go up in one copy, launch_score_rows_batch
+// scores every list (the reference-order dot product of rlr_score_rows per pair), one copy back, one synchronisation.
+int32_t score_rows_batch(rlr_index *ix, const float *queries, uint32_t nq, const uint64_t *rows, const uint32_t *counts,
+                         uint32_t stride, float *cos_out)
+{
+    RLR_TRY(check_handle(ix));
+    if (nq == 0 || stride == 0)
+        return RLR_OK;
+    if (!queries || !rows || !counts || !cos_out)
+        return set_error(RLR_E_INVALID, "null argument");
+    RLR_TRY(use_device(ix));
+    CtxLease lease(ix);
+    RLR_TRY(ctx_acquire(ix, &lease.c));
+    Ctx *c = lease.c;
+    // [queries nq x q_pitch | lists nq x stride | counts nq | cosines nq x stride], 32-bit words, on both sides
+    const size_t w_q = static_cast<size_t>(nq) * ix->q_pitch, w_list = static_cast<size_t>(nq) * stride;
+    const size_t w_in = w_q + w_list + nq, w_all = w_in + w_list;
+    RLR_TRY(pin_reserve(c, w_all * 4));
+    RLR_HIP(c->d_pool.reserve(w_all));
+    float *h_q = static_cast<float *>(c->h_pin.get());
+    uint32_t *h_list = reinterpret_cast<uint32_t *>(h_q + w_q), *h_cnt = h_list + w_list;
+    pad_queries(ix, queries, nq, h_q);
+    for (uint32_t q = 0; q < nq; ++q) {
+        if (counts[q] > stride)
+            return set_error(RLR_E_INVALID, "list %u holds %u rows, the stride is %u", q, counts[q], stride);
+        h_cnt[q] = counts[q];
+        for (uint32_t i = 0; i < stride; ++i) {
+            const uint64_t r = i < counts[q] ? rows[static_cast<size_t>(q) * stride + i] : 0;
+            if (r >= ix->n_rows)
+                return set_error(RLR_E_RANGE, "row %llu out of range (%llu rows)", static_cast<unsigned long long>(r),
+                                 static_cast<unsigned long long>(ix->n_rows));
+            h_list[static_cast<size_t>(q) * stride + i] = static_cast<uint32_t>(r);
+        }
+    }
+    float *d_q = c->d_pool.get();
+    const uint32_t *d_list = reinterpret_cast<const uint32_t *>(d_q + w_q), *d_cnt = d_list + w_list;
+    float *d_cos = d_q + w_in;
+    RLR_HIP(hipMemcpyAsync(d_q, h_q, w_in * 4, hipMemcpyHostToDevice, c->stream));
+    RLR_HIP(launch_score_rows_batch(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, d_q, ix->q_pitch, nq, d_list, stride, d_cos, d_cnt, 1,
+                                    static_cast<uint32_t>(ix->n_rows), c->stream));
+    float *h_cos = reinterpret_cast<float *>(h_cnt + nq);
+    RLR_HIP(hipMemcpyAsync(h_cos, d_cos, w_list * 4, hipMemcpyDeviceToHost, c->stream));
+    RLR_HIP(hipStreamSynchronize(c->stream));
+    for (uint32_t q = 0; q < nq; ++q)
+        std::memcpy(cos_out + static_cast<size_t>(q) * stride, h_cos + static_cast<size_t>(q) * stride, counts[q] * sizeof(float));
+    return RLR_OK;
+}
 } // namespace rlr

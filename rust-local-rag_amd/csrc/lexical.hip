@@ -810,22 +810,45 @@ struct BatchQuery {
     uint64_t key_off; // its region of the key buffer
 };
 
+// MASKED (rlr_lexical_score_batch_filtered): the semantics of lex_row_allowed per query -- a row the filter does not allow,
+// rows at or beyond `mask_rows` included, is never added to, gets no flag and emits no key, and an allowed row's sum is the
+// unfiltered one term by term.  A slice is kLdsRows / 64 = 32 words of the mask and starts on a word boundary: the
+// workgroup reads its words FIRST (one lane each; words at or beyond ceil(mask_rows / 64) do not exist and read as zero,
+// the last existing word has zero tail bits already) and leaves before the posting searches when no bit is set -- the
+// uniform exit a narrow scope saves its time with.  A posting's bit is tested in those LDS words, never by a global load.
+constexpr uint32_t kSliceWords = kLdsRows / 64;
+static_assert(kLdsRows % 64 == 0, "a slice starts on a mask word");
+
+template <bool MASKED>
 __global__ __launch_bounds__(256) void bm25_batch_kernel(const BatchQuery *__restrict__ bq, const BatchTerm *__restrict__ bt,
                                                          const uint32_t *__restrict__ post_row, const uint32_t *__restrict__ post_tf,
                                                          const uint32_t *__restrict__ dpost_row, const uint32_t *__restrict__ dpost_tf,
                                                          const uint32_t *__restrict__ doc_len, uint32_t n_rows, float avg,
-                                                         uint64_t *__restrict__ keys, LexControl *__restrict__ ctls)
+                                                         uint64_t *__restrict__ keys, LexControl *__restrict__ ctls,
+                                                         const uint64_t *__restrict__ mask, uint32_t mask_rows)
 {
     __shared__ uint32_t s_range[kBatchTermsMax][4]; // [term][main lo, main hi, appended lo, appended hi]
     __shared__ float s_sc[kLdsRows], s_dl[kLdsRows], s_nk[kLdsRows];
     __shared__ uint8_t s_fl[kLdsRows];
     __shared__ uint32_t s_cnt, s_base;
+    __shared__ uint64_t s_mask[MASKED ? kSliceWords : 1];
     const uint32_t tid = threadIdx.x;
     const BatchQuery Q = bq[blockIdx.y];
     const uint32_t r0 = blockIdx.x * kLdsRows;
     if (Q.nt == 0 || r0 >= n_rows)
         return;
     const uint32_t r1 = min(r0 + kLdsRows, n_rows), nr = r1 - r0;
+    if constexpr (MASKED) {
+        int allowed = 0;
+        if (tid < kSliceWords) {
+            const uint32_t w = (r0 >> 6) + tid, n_words = (mask_rows >> 6) + ((mask_rows & 63u) != 0u); // (no overflow)
+            const uint64_t m = w < n_words ? mask[w] : 0ull;
+            s_mask[tid] = m;
+            allowed = m != 0ull;
+        }
+        if (!__syncthreads_or(allowed))
+            return; // (uniform) the filter allows no row of this slice
+    }
     const BatchTerm *terms = bt + Q.t0;
     // the slice's share of every posting list, one search per wave at a time (uniform per wave): the estimated-window search
     // of bm25_terms_lds_kernel -- one coalesced window of kSearchWin entries around cnt * key / n_rows decides it as a rule,
@@ -884,6 +907,10 @@ __global__ __launch_bounds__(256) void bm25_batch_kernel(const BatchQuery *__res
             const uint32_t *tfs = seg ? dpost_tf + terms[t].off_d : post_tf + terms[t].off_m;
             for (uint32_t i = lo + tid; i < hi; i += 256) {
                 const uint32_t r = rows[i] - r0;
+                if constexpr (MASKED) {
+                    if (!((s_mask[r >> 6] >> (r & 63u)) & 1ull))
+                        continue; // (no barrier inside the loop)
+                }
                 const float dl = s_dl[r];
                 const float tf = static_cast<float>(tfs[i]);
                 const float denom = tf + s_nk[r];
@@ -1537,6 +1564,15 @@ int32_t lexical_score_exact(rlr_lexical *lx, const char *query_tokens, size_t le
 } // namespace rlr
 } // extern "C++"
 
+// the filter a scoring call may use: current, and on the device of the lexical index (no GPU work)
+static int32_t lex_filter_view(const rlr_lexical *lx, const rlr_filter *f, rlr::FilterView *v)
+{
+    LEX_TRY(rlr::filter_view(f, v)); // (null or stale)
+    if (v->device != lx->device)
+        return set_error(RLR_E_INVALID, "the filter lives on device %d, the lexical index on device %d", v->device, lx->device);
+    return RLR_OK;
+}
+
 int32_t rlr_lexical_score_filtered(rlr_lexical *lx, const rlr_filter *f, const char *query_tokens, size_t len, uint32_t limit,
                                    uint64_t *rows_out, float *scores_out, uint32_t *n_out)
 {
@@ -1546,9 +1582,7 @@ int32_t rlr_lexical_score_filtered(rlr_lexical *lx, const rlr_filter *f, const c
         return set_error(RLR_E_INVALID, "n_out is null");
     *n_out = 0;
     rlr::FilterView v;
-    LEX_TRY(rlr::filter_view(f, &v)); // (null or stale: refused before any GPU work)
-    if (v.device != lx->device)
-        return set_error(RLR_E_INVALID, "the filter lives on device %d, the lexical index on device %d", v.device, lx->device);
+    LEX_TRY(lex_filter_view(lx, f, &v));
     if (v.n_allowed == 0)
         return RLR_OK;
     return lexical_score_from(lx, query_tokens, len, limit, rows_out, scores_out, n_out, 0, v.d_mask,
@@ -1908,7 +1942,7 @@ struct BatchGuard { // releases whatever lexical_batch_enqueue had taken when it
 } // namespace
 
 int32_t lexical_batch_enqueue(rlr_lexical *lx, uint32_t nq, const char *tokens, const uint64_t *offsets, uint32_t limit,
-                              const LexBatchSink &sink, uint8_t *too_many_terms, LexBatchPending *out)
+                              const LexBatchSink &sink, uint8_t *too_many_terms, LexBatchPending *out, const FilterView *filter)
 {
     out->lx = lx;
     out->ws = nullptr;
@@ -1999,11 +2033,20 @@ int32_t lexical_batch_enqueue(rlr_lexical *lx, uint32_t nq, const char *tokens, 
     const BatchTerm *d_t = reinterpret_cast<const BatchTerm *>(reinterpret_cast<const char *>(ws->d_btab.get()) + q_bytes);
     LEX_HIP(hipMemsetAsync(ws->d_bctl.get(), 0, static_cast<size_t>(nq) * sizeof(LexControl), s));
     LEX_HIP(hipMemcpyAsync(ws->d_btab.get(), out->table.data(), tab_bytes, hipMemcpyHostToDevice, s));
-    if (!ts.empty() && n_rows > 0) {
+    if (!ts.empty() && n_rows > 0 && !filter) {
         const uint32_t slices = static_cast<uint32_t>((n_rows + kLdsRows - 1) / kLdsRows);
-        hipLaunchKernelGGL(bm25_batch_kernel, dim3(slices, nq), dim3(256), 0, s, d_q, d_t, lx->d_post_row.get(), lx->d_post_tf.get(),
+        hipLaunchKernelGGL(bm25_batch_kernel<false>, dim3(slices, nq), dim3(256), 0, s, d_q, d_t, lx->d_post_row.get(), lx->d_post_tf.get(),
                            lx->d_dpost_row.get(), lx->d_dpost_tf.get(), lx->d_doc_len.get(), static_cast<uint32_t>(n_rows), avg, ws->d_bkeys.get(),
-                           ws->d_bctl.get());
+                           ws->d_bctl.get(), nullptr, 0u);
+    } else if (!ts.empty() && n_rows > 0 && filter->index_rows > 0) {
+        // (no slice at or beyond the filter's index size: every row there is masked.  The key regions stay sized from df,
+        // an upper bound on the allowed rows with a posting.)
+        const uint32_t mask_rows = static_cast<uint32_t>(std::min<uint64_t>(filter->index_rows, 0xFFFFFFFFull));
+        const uint64_t covered = std::min<uint64_t>(n_rows, mask_rows);
+        const uint32_t slices = static_cast<uint32_t>((covered + kLdsRows - 1) / kLdsRows);
+        hipLaunchKernelGGL(bm25_batch_kernel<true>, dim3(slices, nq), dim3(256), 0, s, d_q, d_t, lx->d_post_row.get(), lx->d_post_tf.get(),
+                           lx->d_dpost_row.get(), lx->d_dpost_tf.get(), lx->d_doc_len.get(), static_cast<uint32_t>(n_rows), avg, ws->d_bkeys.get(),
+                           ws->d_bctl.get(), filter->d_mask, mask_rows);
     }
     hipLaunchKernelGGL(lex_batch_sort_kernel, dim3(nq), dim3(1024), 0, s, d_q, ws->d_bkeys.get(), ws->d_bctl.get(), limit, ws->d_bsel.get());
     if (max_keys > kMaxLimit) { // some query may have more keys than the LDS sort holds: the radix passes take those
@@ -2057,12 +2100,10 @@ static_assert(sizeof(LexBatchHeader) == 8, "two 32-bit words per query");
 
 } // namespace
 
-extern "C" int32_t rlr_lexical_score_batch(rlr_lexical *lx, uint32_t nq, const char *tokens, const uint64_t *offsets,
-                                           uint32_t limit, uint64_t *rows_out, float *scores_out, uint32_t *n_out,
-                                           float *max_lexical_out, uint32_t *n_single)
+// the argument checks of both batched entry points (no GPU work, no handle is read)
+static int32_t lex_batch_check_args(const rlr_lexical *lx, uint32_t nq, const char *tokens, const uint64_t *offsets, uint32_t limit,
+                                    const uint64_t *rows_out, const float *scores_out, const uint32_t *n_out)
 {
-    if (n_single)
-        *n_single = 0;
     if (!lx)
         return set_error(RLR_E_INVALID, "lexical handle is null");
     if (limit == 0 || limit > kMaxLimit)
@@ -2076,6 +2117,53 @@ extern "C" int32_t rlr_lexical_score_batch(rlr_lexical *lx, uint32_t nq, const c
             return set_error(RLR_E_INVALID, "token_offsets decrease at query %u", q);
     if (offsets[nq] > offsets[0] && !tokens)
         return set_error(RLR_E_INVALID, "tokens is null");
+    return RLR_OK;
+}
+
+// f / v: null (every row), or a filter and its checked view
+static int32_t lexical_score_batch_impl(rlr_lexical *lx, const rlr_filter *f, const rlr::FilterView *v, uint32_t nq, const char *tokens,
+                                        const uint64_t *offsets, uint32_t limit, uint64_t *rows_out, float *scores_out,
+                                        uint32_t *n_out, float *max_lexical_out, uint32_t *n_single);
+
+extern "C" int32_t rlr_lexical_score_batch(rlr_lexical *lx, uint32_t nq, const char *tokens, const uint64_t *offsets,
+                                           uint32_t limit, uint64_t *rows_out, float *scores_out, uint32_t *n_out,
+                                           float *max_lexical_out, uint32_t *n_single)
+{
+    if (n_single)
+        *n_single = 0;
+    LEX_TRY(lex_batch_check_args(lx, nq, tokens, offsets, limit, rows_out, scores_out, n_out));
+    if (nq == 0)
+        return RLR_OK;
+    return lexical_score_batch_impl(lx, nullptr, nullptr, nq, tokens, offsets, limit, rows_out, scores_out, n_out, max_lexical_out,
+                                    n_single);
+}
+
+extern "C" int32_t rlr_lexical_score_batch_filtered(rlr_lexical *lx, const rlr_filter *f, uint32_t nq, const char *tokens,
+                                                    const uint64_t *offsets, uint32_t limit, uint64_t *rows_out, float *scores_out,
+                                                    uint32_t *n_out, float *max_lexical_out, uint32_t *n_single)
+{
+    if (n_single)
+        *n_single = 0;
+    LEX_TRY(lex_batch_check_args(lx, nq, tokens, offsets, limit, rows_out, scores_out, n_out));
+    rlr::FilterView v;
+    LEX_TRY(lex_filter_view(lx, f, &v)); // (null, stale, another device: before any GPU work)
+    if (nq == 0)
+        return RLR_OK;
+    if (v.n_allowed == 0) { // no row is a candidate
+        for (uint32_t q = 0; q < nq; ++q) {
+            n_out[q] = 0;
+            if (max_lexical_out)
+                max_lexical_out[q] = 1.1920929e-07f;
+        }
+        return RLR_OK;
+    }
+    return lexical_score_batch_impl(lx, f, &v, nq, tokens, offsets, limit, rows_out, scores_out, n_out, max_lexical_out, n_single);
+}
+
+static int32_t lexical_score_batch_impl(rlr_lexical *lx, const rlr_filter *f, const rlr::FilterView *v, uint32_t nq, const char *tokens,
+                                        const uint64_t *offsets, uint32_t limit, uint64_t *rows_out, float *scores_out,
+                                        uint32_t *n_out, float *max_lexical_out, uint32_t *n_single)
+{
     LEX_HIP(hipSetDevice(lx->device));
     // sub-batches of the engine's size (one grid row of bm25_batch_kernel per query)
     constexpr uint32_t kSub = 256;
@@ -2101,7 +2189,7 @@ extern "C" int32_t rlr_lexical_score_batch(rlr_lexical *lx, uint32_t nq, const c
     for (uint32_t q0 = 0; q0 < nq; q0 += sub) {
         const uint32_t m = std::min(sub, nq - q0);
         rlr::LexBatchPending lp;
-        int32_t st = rlr::lexical_batch_enqueue(lx, m, tokens, offsets + q0, limit, sink, many.data(), &lp);
+        int32_t st = rlr::lexical_batch_enqueue(lx, m, tokens, offsets + q0, limit, sink, many.data(), &lp, v);
         if (st == RLR_OK && hipEventSynchronize(static_cast<hipEvent_t>(lp.ready)) != hipSuccess)
             st = set_error(RLR_E_HIP, "lexical batch did not complete");
         if (st == RLR_OK &&
@@ -2139,8 +2227,12 @@ extern "C" int32_t rlr_lexical_score_batch(rlr_lexical *lx, uint32_t nq, const c
     // the queries the batched kernel does not take: alone (after the batch dropped the readers' lock)
     for (uint32_t g : redo) {
         const size_t o = static_cast<size_t>(g) * limit;
-        LEX_TRY(rlr_lexical_score(lx, tokens ? tokens + offsets[g] : nullptr, static_cast<size_t>(offsets[g + 1] - offsets[g]), limit,
-                                  rows_out + o, scores_out + o, &n_out[g]));
+        const char *tk = tokens ? tokens + offsets[g] : nullptr;
+        const size_t len = static_cast<size_t>(offsets[g + 1] - offsets[g]);
+        if (f)
+            LEX_TRY(rlr_lexical_score_filtered(lx, f, tk, len, limit, rows_out + o, scores_out + o, &n_out[g]));
+        else
+            LEX_TRY(rlr_lexical_score(lx, tk, len, limit, rows_out + o, scores_out + o, &n_out[g]));
         if (max_lexical_out) {
             float mx = 0.0f; // fold(0.0, f32::max), floored at f32::EPSILON (rag_engine.rs:515-519)
             for (uint32_t i = 0; i < n_out[g]; ++i)

@@ -95,8 +95,13 @@ struct LexBatchPending {
 // BM25 of nq queries (tokens[offsets[q] .. offsets[q + 1]) each) -> the best `limit` (<= sink.bound, <= RLR_LEXICAL_MAX_LIMIT)
 // pairs of every query unpacked into `sink`, on the workspace's stream.  No synchronisation.  too_many_terms[q] = 1: the
 // query has more unique known terms than the batched kernel takes; it was left without pairs (score it alone).
+// filter (may be null: every row): the view of a current row filter on the device of `lx` (filter_internal.h; the caller
+// checked both) -- only its rows are candidates, with the semantics of rlr_lexical_score_filtered per query; the caller
+// keeps the filter alive until lexical_batch_finish.
+struct FilterView;
 int32_t lexical_batch_enqueue(rlr_lexical *lx, uint32_t nq, const char *tokens, const uint64_t *offsets, uint32_t limit,
-                              const LexBatchSink &sink, uint8_t *too_many_terms, LexBatchPending *out);
+                              const LexBatchSink &sink, uint8_t *too_many_terms, LexBatchPending *out,
+                              const FilterView *filter = nullptr);
 // drains the workspace's stream, hands it back and drops the readers' lock (also after a failed enqueue)
 void lexical_batch_finish(LexBatchPending *p, bool ok);
 // (index.hip) query q's keys at d_sel[q * sel_stride], count at d_count[q * count_stride]; no error check inside

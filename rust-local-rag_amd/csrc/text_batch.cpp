@@ -82,12 +82,9 @@ int32_t rlr_engine_search_text_batch(rlr_index *idx, rlr_lexical *lex, const flo
         }
         return RLR_OK;
     }
-    constexpr uint32_t kSubBatch = 256; // one GEMM query block
     const uint32_t nd = static_cast<uint32_t>(need);
     const uint32_t k_cap = static_cast<uint32_t>(n_res);
-    // (the Gram matrices of a sub-batch stay below 256 MB)
-    const uint64_t gram_q = diversify ? std::max<uint64_t>(1, (64ull << 20) / (static_cast<uint64_t>(nd) * nd)) : kSubBatch;
-    const uint32_t sub = static_cast<uint32_t>(std::max<uint64_t>(2, std::min<uint64_t>(kSubBatch, gram_q)));
+    const uint32_t sub = text_sub_batch(nd, diversify); // (one GEMM query block; the Gram matrices stay below 256 MB)
     std::vector<float> qs;
     std::vector<uint64_t> rows;
     std::vector<float> cosv, sc, lx;

@@ -386,10 +386,15 @@ class RagEngine:
 
     # -- many query texts at once (oracle: search / search_with_diversity with query_text, per query) -------------
     def search_text_batch(self, query_embeddings, query_texts: Sequence[str], top_k: int, diversity_factor: float = 0.0,
-                          weights: Optional[QueryWeights] = None, stage: int = 0, return_info: bool = False):
+                          weights: Optional[QueryWeights] = None, stage: int = 0, return_info: bool = False,
+                          documents: Optional[Sequence[str]] = None):
         """`search_with_diversity(q, top_k, diversity_factor, weights, query_text=t)` (diversity 0: `search(q, top_k,
         weights, stage=stage, query_text=t)`) for every (q, t) pair, bit for bit, through the batched kernels.  Returns
-        one result list per query, and with return_info also a dict of how the queries were served."""
+        one result list per query, and with return_info also a dict of how the queries were served.
+        `documents`: every query searches only inside these documents, as with `documents=` on the single calls (None:
+        the whole corpus; an empty list or unknown names: no rows, an empty list per query) -- one masked batched BM25,
+        one filtered top-k call, one scoring of the lexical rows and one MMR per sub-batch
+        (rlr_engine_search_text_batch_filtered)."""
         q = _f32(query_embeddings)
         if q.ndim == 1:
             q = q.reshape(1, -1)
@@ -405,10 +410,13 @@ class RagEngine:
         n_out = np.zeros(max(nq, 1), dtype=np.uint32)
         info = N.TextBatchInfoC()
         wc = weights.to_c() if weights is not None else None
-        N.check(N.lib().rlr_engine_search_text_batch(
-            self.index.handle, self.lexical._h, q.ctypes.data_as(N.f32p), dq, nq, blob, offsets.ctypes.data_as(N.u64p),
-            top_k, float(diversity_factor), stage, C.byref(wc) if wc is not None else None, hits, cap,
-            n_out.ctypes.data_as(N.u32p), C.byref(info)))
+        tail = (q.ctypes.data_as(N.f32p), dq, nq, blob, offsets.ctypes.data_as(N.u64p), top_k, float(diversity_factor), stage,
+                C.byref(wc) if wc is not None else None, hits, cap, n_out.ctypes.data_as(N.u32p), C.byref(info))
+        if documents is None:
+            N.check(N.lib().rlr_engine_search_text_batch(self.index.handle, self.lexical._h, *tail))
+        elif document_ranges(self._chunks, documents):
+            f = self._filter_for(documents)
+            N.check(N.lib().rlr_engine_search_text_batch_filtered(self.index.handle, self.lexical._h, f.handle, *tail))
         out = []
         for i in range(nq):
             view = (N.SearchHitC * cap).from_buffer(hits, i * cap * C.sizeof(N.SearchHitC))
@@ -420,8 +428,9 @@ class RagEngine:
     def search_documents_batch(self, requests: Sequence[SearchRequest]) -> List[List[SearchResult]]:
         """search_documents for every request, grouped by (top_k, diversity, weights, documents) after its caps and
         clamps.  Unscoped groups run through search_text_batch (a request without text is scored with no query terms);
-        scoped groups without query text through search_with_diversity_batch(documents=...); scoped requests WITH query
-        text one by one through search_documents (there is no batched BM25 inside a filter)."""
+        scoped groups without query text through search_with_diversity_batch(documents=...); the scoped requests of a
+        group WITH query text through one search_text_batch(documents=...) when there are two or more of them, a lone
+        one through search_documents."""
         groups: Dict[tuple, List[int]] = {}
         for i, r in enumerate(requests):
             if r.lexical:
@@ -448,9 +457,14 @@ class RagEngine:
                 emb = np.stack([_f32(requests[i].query_embedding).ravel() for i in plain])
                 for i, res in zip(plain, self.search_with_diversity_batch(emb, top_k, div, w, documents=sorted(scope))):
                     out[i] = res
-            for i in members:
-                if requests[i].query:
-                    out[i] = self.search_documents(requests[i])
+            text = [i for i in members if requests[i].query]
+            if len(text) >= 2:
+                emb = np.stack([_f32(requests[i].query_embedding).ravel() for i in text])
+                texts = [requests[i].query for i in text]
+                for i, res in zip(text, self.search_text_batch(emb, texts, top_k, div, w, documents=sorted(scope))):
+                    out[i] = res
+            elif text:  # (a batch of one is outside the fused path)
+                out[text[0]] = self.search_documents(requests[text[0]])
         return out
 
     # -- RagEngine::get_embedding_candidates (rag_engine.rs:415-461) -----------------------

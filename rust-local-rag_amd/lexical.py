@@ -110,10 +110,11 @@ class LexicalIndex:
                                               sc.ctypes.data_as(N.f32p), C.byref(n)))
         return rows[: n.value], sc[: n.value]
 
-    def score_batch(self, queries: Sequence[str], limit: int, return_info: bool = False):
+    def score_batch(self, queries: Sequence[str], limit: int, return_info: bool = False, filter=None):
         """`score(q, limit)` for every query text, through the batched BM25 kernels (rlr_lexical_score_batch) -> one
         (rows u64, scores f32) pair per query; with return_info also a dict: n_single (queries scored alone) and
-        max_lexical (f32 per query, the blend's normalisation input)"""
+        max_lexical (f32 per query, the blend's normalisation input).  filter (a RowFilter, as for score): every query
+        is `score(q, limit, filter)`, through the masked batched kernels (rlr_lexical_score_batch_filtered)"""
         toks = [self._joined(tokenize(q)) for q in queries]
         nq = len(toks)
         offsets = np.zeros(nq + 1, dtype=np.uint64)
@@ -126,9 +127,12 @@ class LexicalIndex:
         n = np.zeros(max(nq, 1), dtype=np.uint32)
         mx = np.zeros(max(nq, 1), dtype=np.float32)
         n_single = C.c_uint32()
-        N.check(self._L.rlr_lexical_score_batch(self._h, nq, blob, offsets.ctypes.data_as(N.u64p), limit,
-                                                rows.ctypes.data_as(N.u64p), sc.ctypes.data_as(N.f32p),
-                                                n.ctypes.data_as(N.u32p), mx.ctypes.data_as(N.f32p), C.byref(n_single)))
+        tail = (nq, blob, offsets.ctypes.data_as(N.u64p), limit, rows.ctypes.data_as(N.u64p), sc.ctypes.data_as(N.f32p),
+                n.ctypes.data_as(N.u32p), mx.ctypes.data_as(N.f32p), C.byref(n_single))
+        if filter is not None:
+            N.check(self._L.rlr_lexical_score_batch_filtered(self._h, filter.handle, *tail))
+        else:
+            N.check(self._L.rlr_lexical_score_batch(self._h, *tail))
         out = [(rows[q * limit: q * limit + n[q]], sc[q * limit: q * limit + n[q]]) for q in range(nq)]
         if return_info:
             return out, dict(n_single=n_single.value, max_lexical=mx[:nq])
