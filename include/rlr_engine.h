@@ -163,6 +163,19 @@ int32_t rlr_engine_search_with_diversity_batch_filtered(rlr_index *idx, const rl
                                                         uint32_t dq, uint32_t n_queries, uint32_t top_k,
                                                         float diversity_factor, const rlr_query_weights *weights,
                                                         rlr_search_hit *out, uint32_t cap, uint32_t *n_out);
+/* The same with a filter PER QUERY (requests scoped to different documents): query q equals
+ * rlr_engine_search_with_diversity_filtered(idx, filters[q], query q, n_lex = 0), and N is |F_q| per query -- need_q =
+ * min(|F_q|, k_eff) with k_eff = top_k (diversity 0) or max(3 * top_k, top_k + 10), fetch_q = min(|F_q|, need_q + 8).
+ * ONE rlr_search_topk_scoped call with the largest fetch (chunks of up to 8 queries share one masked pass over the
+ * union of their scopes), ONE rlr_mmr_select_batch with pool_sizes[q] = need_q.  An empty filter gives n_out[q] = 0.
+ * The fall-backs of the other batched calls: w_embedding == 0 or a pool above 1024 loops the single call; a query whose
+ * rounding-tie chain reaches its last fetched row is re-run alone.  A null array, a null, stale or foreign entry:
+ * RLR_E_INVALID before any GPU work.  Queries WITH text take one filter per call (..._text_batch_filtered). */
+int32_t rlr_engine_search_with_diversity_batch_scoped(rlr_index *idx, const rlr_filter *const *filters,
+                                                      const float *queries_raw, uint32_t dq, uint32_t n_queries,
+                                                      uint32_t top_k, float diversity_factor,
+                                                      const rlr_query_weights *weights, rlr_search_hit *out, uint32_t cap,
+                                                      uint32_t *n_out);
 /* rlr_engine_search_text_batch inside a filter: query q equals rlr_engine_search_text_filtered(query q, tokens q), bit
  * for bit, N = |F| everywhere (|F| = 0: no hits, RLR_OK).  Per sub-batch of up to 256 queries: one masked batched BM25
  * (rlr_lexical_score_batch_filtered, limit = 5 * k_seen as the single call computes it), one rlr_search_topk_filtered

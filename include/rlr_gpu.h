@@ -381,6 +381,19 @@ int32_t rlr_filter_set_path(rlr_filter *f, int32_t path);
  * pass: n_batches, n_batch_queries, n_batch_fallbacks (queries re-run by the single-query filtered path). */
 int32_t rlr_search_topk_filtered(rlr_index *idx, const rlr_filter *f, const float *queries, uint32_t n_queries,
                                  uint32_t k, float guard_eps, uint64_t *rows_out, float *cos_out, uint32_t *n_out);
+/* A filter PER QUERY (a request queue in which every user is scoped to their own documents): filters[q] is query q's
+ * filter, and query q's result is rlr_search_topk_filtered(idx, filters[q], query q, 1, k, ...), bit for bit.  Results of
+ * query q start at rows_out[q * k] / cos_out[q * k] (the stride is k whatever the counts); n_out[q] = min(k, |F_q|), 0 with
+ * RLR_OK for an empty filter.  Entries may repeat.  A null array, a null entry, a stale entry or an entry made for
+ * another index: RLR_E_INVALID before any GPU work.
+ * The queries whose filter is on the masked-scan path with |F_q| >= k, over f32 rows of 256 / 512 / 768 / 1024 elements,
+ * are taken in call order in chunks of up to 8; a chunk shares ONE masked pass that reads the UNION of its scopes once
+ * (a row in several scopes is fetched once, a row in none is never requested) when a cost model over the union's bytes
+ * (or RLR_BATCH_MIN) says so.  Every other query -- list-path filter, |F_q| < k, binary16 rows, other widths and
+ * pitches, a chunk the model declines -- runs alone inside its own filter.  Profile counters as for
+ * rlr_search_topk_filtered; under profiling scan_bytes grows by the rows of the union. */
+int32_t rlr_search_topk_scoped(rlr_index *idx, const rlr_filter *const *filters, const float *queries, uint32_t n_queries,
+                               uint32_t k, float guard_eps, uint64_t *rows_out, float *cos_out, uint32_t *n_out);
 
 /* ---- coalescing of concurrent single-query searches ----------------------- */
 /* Serve concurrent single-query rlr_search_topk calls on this index from shared passes over the rows.

@@ -148,6 +148,7 @@ PROTOTYPES = [
     ("rlr_filter_info", C.c_int32, [_H, u64p, u64p, i32p, i32p]),
     ("rlr_filter_set_path", C.c_int32, [_H, C.c_int32]),
     ("rlr_search_topk_filtered", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, C.c_float, u64p, f32p, u32p]),
+    ("rlr_search_topk_scoped", C.c_int32, [_H, C.POINTER(_H), f32p, C.c_uint32, C.c_uint32, C.c_float, u64p, f32p, u32p]),
     ("rlr_index_set_coalescing", C.c_int32, [_H, C.c_uint32, C.c_uint32]),
     ("rlr_index_coalesce_stats", C.c_int32, [_H, C.POINTER(CoalesceStatsC), C.c_int32]),
     ("rlr_profile_enable", C.c_int32, [_H, C.c_int32]),
@@ -178,6 +179,9 @@ PROTOTYPES = [
     ("rlr_engine_search_with_diversity_batch_filtered", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, C.c_uint32,
                                                                     C.c_float, C.POINTER(QueryWeightsC),
                                                                     C.POINTER(SearchHitC), C.c_uint32, u32p]),
+    ("rlr_engine_search_with_diversity_batch_scoped", C.c_int32, [_H, C.POINTER(_H), f32p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                                  C.c_float, C.POINTER(QueryWeightsC),
+                                                                  C.POINTER(SearchHitC), C.c_uint32, u32p]),
     ("rlr_engine_search_text_batch_filtered", C.c_int32, [_H, _H, _H, f32p, C.c_uint32, C.c_uint32, C.c_char_p, u64p,
                                                           C.c_uint32, C.c_float, C.c_int32, C.POINTER(QueryWeightsC),
                                                           C.POINTER(SearchHitC), C.c_uint32, u32p,

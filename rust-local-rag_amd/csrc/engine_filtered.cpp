@@ -180,6 +180,65 @@ int32_t rlr_engine_search_with_diversity_batch_filtered(rlr_index *idx, const rl
     return RLR_OK;
 }
 
+int32_t rlr_engine_search_with_diversity_batch_scoped(rlr_index *idx, const rlr_filter *const *filters, const float *queries_raw,
+                                                      uint32_t dq, uint32_t n_queries, uint32_t top_k, float diversity_factor,
+                                                      const rlr_query_weights *weights, rlr_search_hit *out, uint32_t cap,
+                                                      uint32_t *n_out)
+{
+    if (!idx || !filters || !n_out || (n_queries && !queries_raw && dq) || (n_queries && cap && !out))
+        return RLR_E_INVALID;
+    for (uint32_t q = 0; q < n_queries; ++q)
+        n_out[q] = 0;
+    int32_t st = RLR_OK;
+    for (uint32_t q = 0; q < n_queries; ++q) // a null or stale entry, or one of another index: before any GPU work
+        if ((st = rlr::filter_check(idx, filters[q])) != RLR_OK)
+            return st;
+    if (n_queries == 0)
+        return RLR_OK;
+    if (diversity_factor < 0.0f) diversity_factor = 0.0f;
+    if (diversity_factor > 1.0f) diversity_factor = 1.0f;
+    rlr_resolved_weights w;
+    rlr_resolve_weights(weights, &w);
+    // the candidate universe of query q is filters[q]: its size where the one-filter batch has |F|, one
+    // rlr_search_topk_scoped call for every query's top-k, the single filtered call where a query runs alone
+    struct ScopedBackend {
+        rlr_index *idx;
+        const rlr_filter *const *filters;
+        std::vector<FilteredBackend> one;
+        const float *queries_raw;
+        uint32_t dq, top_k, dim = 0;
+        float lambda;
+        const rlr_resolved_weights *w;
+        uint64_t universe(uint32_t q) const { return one[q].n_rows; }
+        int32_t topk(const float *queries, uint32_t nq, uint32_t k, uint64_t *rows, float *cos, uint32_t *n) const
+        {
+            return rlr_search_topk_scoped(idx, filters, queries, nq, k, -1.0f, rows, cos, n);
+        }
+        int32_t mmr(const uint64_t *pool_rows, const float *pool_scores, const uint32_t *pool_sizes, uint32_t nq, uint32_t P,
+                    uint32_t k, float lam, uint32_t *order, uint32_t *n_sel) const
+        {
+            return one[0].mmr(pool_rows, pool_scores, pool_sizes, nq, P, k, lam, order, n_sel);
+        }
+        int32_t single(uint32_t q, std::vector<Cand> &res) const
+        {
+            return generic_search_with_diversity(one[q], queries_raw + static_cast<size_t>(q) * dq, dq, top_k, lambda, *w, nullptr,
+                                                 nullptr, 0, res);
+        }
+    } be{idx, filters, {}, queries_raw, dq, top_k, 0, diversity_factor, &w};
+    be.one.resize(n_queries);
+    for (uint32_t q = 0; q < n_queries; ++q)
+        if ((st = filtered_backend(idx, filters[q], &be.one[q])) != RLR_OK)
+            return st;
+    be.dim = be.one[0].dim;
+    std::vector<std::vector<Cand>> results;
+    st = generic_search_with_diversity_batch_scoped(be, queries_raw, dq, n_queries, top_k, diversity_factor, w, results);
+    if (st != RLR_OK)
+        return st;
+    for (uint32_t q = 0; q < n_queries; ++q)
+        emit(results[q], out + static_cast<size_t>(q) * cap, cap, &n_out[q]);
+    return RLR_OK;
+}
+
 // rlr_engine_search_text_filtered for many queries: per sub-batch ONE masked batched BM25, ONE rlr_search_topk_filtered call,
 // ONE scoring of every query's lexical rows, the arithmetic of blend_search's w_embedding != 0 branch per query
 // (blend_fetched: the same union, combine, order and boundary rule) and ONE batched MMR.  A wider fetch than the single

@@ -420,4 +420,102 @@ int32_t generic_search_with_diversity_batch(const B &be, const float *queries_ra
     return RLR_OK;
 }
 
+// generic_search_with_diversity_batch with a candidate universe PER QUERY (queries scoped to different documents): N is
+// be.universe(q) wherever that function has be.n_rows, so need_q = min(N_q, k_eff) and fetch_q = min(N_q, need_q + 8)
+// differ from query to query.  be.topk is ONE call with the largest fetch (query q gets min(fetch, N_q) rows back, of
+// which the first fetch_q are looked at: the pool and the boundary rule see what the one-universe function shows them);
+// the MMR is ONE batched call over the non-empty pools with pool_sizes[q] = need_q.  be.single(q, out) is the reference
+// path for query q inside its own universe.  The same fall-backs: w_embedding == 0 or a pool above 1024 loops
+// be.single; a rounding-tie chain that reaches the last looked-at row re-runs that query alone.
+template <typename B>
+int32_t generic_search_with_diversity_batch_scoped(const B &be, const float *queries_raw, uint32_t dq, uint32_t n_queries,
+                                                   uint32_t top_k, float lambda, const rlr_resolved_weights &w,
+                                                   std::vector<std::vector<Cand>> &results)
+{
+    results.assign(n_queries, {});
+    if (n_queries == 0)
+        return RLR_OK;
+    const bool plain = lambda == 0.0f;
+    const uint32_t k_eff = std::max<uint32_t>(plain ? top_k : pool_size_of(top_k), 1u); // search() treats 0 as 1 (:490)
+    std::vector<uint64_t> need(n_queries);
+    uint64_t max_need = 0, max_fetch = 0;
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        const uint64_t N = be.universe(q);
+        need[q] = std::min<uint64_t>(N, k_eff);
+        max_need = std::max(max_need, need[q]);
+        max_fetch = std::max(max_fetch, std::min<uint64_t>(N, need[q] + 8));
+    }
+    if (max_need == 0) // every universe is empty (:476-478)
+        return RLR_OK;
+    int32_t st = RLR_OK;
+    if (w.embedding == 0.0f || max_need > 1024) { // degenerate weight / pool beyond the batched MMR: loop
+        for (uint32_t q = 0; q < n_queries; ++q)
+            if (need[q] && (st = be.single(q, results[q])) != RLR_OK)
+                return st;
+        return RLR_OK;
+    }
+    std::vector<float> qn(static_cast<size_t>(n_queries) * be.dim);
+    prepare_queries(queries_raw, dq, n_queries, be.dim, qn.data());
+    const uint32_t fetch = static_cast<uint32_t>(max_fetch);
+    std::vector<uint64_t> rows(static_cast<size_t>(n_queries) * fetch);
+    std::vector<float> cosv(static_cast<size_t>(n_queries) * fetch);
+    std::vector<uint32_t> got(n_queries);
+    st = be.topk(qn.data(), n_queries, fetch, rows.data(), cosv.data(), got.data());
+    if (st != RLR_OK)
+        return st;
+    std::vector<std::vector<Cand>> pools(n_queries);
+    std::vector<uint32_t> redo, live;
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        if (need[q] == 0)
+            continue;
+        const uint64_t N = be.universe(q);
+        const uint32_t seen = static_cast<uint32_t>(std::min<uint64_t>(got[q], std::min<uint64_t>(N, need[q] + 8)));
+        std::vector<Cand> &c = pools[q];
+        c.reserve(seen);
+        for (uint32_t i = 0; i < seen; ++i) {
+            const float e = cosv[static_cast<size_t>(q) * fetch + i];
+            c.push_back({rows[static_cast<size_t>(q) * fetch + i], combine(w, e, 0.0f), e, 0.0f});
+        }
+        std::sort(c.begin(), c.end(), cand_before);
+        if (seen < N && seen > 0) { // (the boundary rule of generic_search_with_diversity_batch)
+            const float c_tail = combine(w, cosv[static_cast<size_t>(q) * fetch + seen - 1], 0.0f);
+            if (!(c.size() >= need[q] && (std::isnan(c_tail) || c[need[q] - 1].c > c_tail)))
+                redo.push_back(q);
+        }
+        if (c.size() > need[q])
+            c.resize(need[q]);
+        if (!c.empty())
+            live.push_back(q);
+    }
+    if (plain) {
+        for (uint32_t q = 0; q < n_queries; ++q)
+            results[q] = pools[q];
+    } else if (!live.empty()) {
+        const uint32_t P = static_cast<uint32_t>(max_need), nl = static_cast<uint32_t>(live.size());
+        std::vector<uint64_t> prow(static_cast<size_t>(nl) * P, 0);
+        std::vector<float> psc(static_cast<size_t>(nl) * P, 0.0f);
+        std::vector<uint32_t> psz(nl), order(static_cast<size_t>(nl) * P), nsel(nl);
+        for (uint32_t j = 0; j < nl; ++j) {
+            const std::vector<Cand> &c = pools[live[j]];
+            psz[j] = static_cast<uint32_t>(c.size());
+            for (uint32_t i = 0; i < psz[j]; ++i) {
+                prow[static_cast<size_t>(j) * P + i] = c[i].row;
+                psc[static_cast<size_t>(j) * P + i] = c[i].c;
+            }
+        }
+        st = be.mmr(prow.data(), psc.data(), psz.data(), nl, P, top_k, lambda, order.data(), nsel.data());
+        if (st != RLR_OK)
+            return st;
+        for (uint32_t j = 0; j < nl; ++j) {
+            const uint32_t q = live[j];
+            for (uint32_t i = 0; i < nsel[j]; ++i)
+                results[q].push_back(pools[q][order[static_cast<size_t>(j) * P + i]]);
+        }
+    }
+    for (uint32_t q : redo)
+        if ((st = be.single(q, results[q])) != RLR_OK)
+            return st;
+    return RLR_OK;
+}
+
 } // namespace rlr_host

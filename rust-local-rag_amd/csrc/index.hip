@@ -2532,6 +2532,130 @@ int32_t filtered_batch(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *
     return RLR_OK;
 }
 
+// ---- several queries, a filter each (rlr_search_topk_scoped) --------------------------------------------------------
+// Can query q of a scoped call join a shared pass at all?  Its filter is on the masked-scan path and holds at least k
+// rows (one plan, one rank k for the whole chunk), the rows are a shape the kernel serves and k leaves the finish its band.
+bool scoped_query_joins(const rlr_index *ix, const rlr_filter *f, uint32_t k)
+{
+    return f->path == 1 && k <= f->n_allowed && batch_multi_shape(ix, 2) && k * 8 <= batch_finish_capacity();
+}
+
+// Does a chunk of nq (2..8) such queries take ONE pass over the union of their scopes (scan_masked_scopes_kernel)?
+// RLR_BATCH_MIN decides when set.  Else the model of filtered_batch_eligible with a filter per query: one by one every
+// query pays its launches, its synchronisation and its OWN allowed bytes; shared, the pass reads the union once.  The
+// union is estimated as min(n_rows, sum of |F_q|) -- exact for disjoint scopes, an upper bound otherwise (identical
+// scopes are overestimated nq-fold, which only makes the gate decline earlier) -- so that no call popcounts ORed masks.
+// The one-by-one side and the fixed costs are filtered_batch_eligible's.  The pass rates are refitted to the forced
+// leg of tools/bench_scoped.py (MI355X, 1 M x 768 f32, k = 100; DESIGN.md "Queries with different scopes in one pass" has
+// the table and what was NOT measured), (whole call - fixed costs) per byte of the union, the slower of the disjoint and
+// the overlapping scope sets: 5.5 / 4.8 / 3.8 TB/s for the Q = 2 / 4 / 8 instance where the one-filter pass has
+// 6.5 / 6.0 / 4.1 -- a unit reads Q mask words and branches per query and row.  With these no measured configuration is
+// slower than one by one, and the gate declines three that the forced pass won: two random halves (20 %: the estimate,
+// every row, exceeds the union, three quarters) and 4 / 8 disjoint eighths (9 / 15 %: the one-by-one side, 104 us per
+// query, is below the 118 us measured through the Python layer).  The 10 % margin is kept; the model errs to the parent's path.
+bool scoped_batch_eligible(const rlr_index *ix, const rlr_filter *const *fs, uint32_t nq, uint32_t k)
+{
+    if (nq < 2 || nq > 8)
+        return false;
+    for (uint32_t q = 0; q < nq; ++q)
+        if (!scoped_query_joins(ix, fs[q], k))
+            return false;
+    if (ix->batch_min > 0)
+        return nq >= ix->batch_min;
+    double t_single = 0.0, sum_rows = 0.0;
+    for (uint32_t q = 0; q < nq; ++q) {
+        t_single += 45e-6 + static_cast<double>(fs[q]->n_allowed) * ix->dim * 4.0 / 6.5e12;
+        sum_rows += static_cast<double>(fs[q]->n_allowed);
+    }
+    const double union_bytes = std::min(static_cast<double>(ix->n_rows), sum_rows) * ix->dim * 4.0;
+    const double pass_rate = nq <= 2 ? 5.5e12 : nq <= 4 ? 4.8e12 : 3.8e12;
+    const double t_shared = 100e-6 + nq * (static_cast<double>(ix->n_rows) * 6e-12) + union_bytes / pass_rate;
+    return t_single > 1.1 * t_shared;
+}
+
+// filtered_batch with a filter per query: a chunk of m (2..8) queries, query q inside fs[q], through ONE pass over the
+// union of the scopes.  k <= every |F_q| (scoped_batch_eligible), so one plan serves the chunk.  Query q's score array is
+// what the one-filter pass writes with fs[q], so the select and the finish are filtered_batch's; the leak test runs
+// against the query's OWN host mask and a query handed back is re-run by filtered_query inside its OWN filter.
+int32_t scoped_batch(rlr_index *ix, Ctx *c, const rlr_filter *const *fs, const float *queries, uint32_t m, uint32_t k,
+                     float guard_eps, uint64_t *rows_out, float *cos_out, uint32_t *n_out)
+{
+    const SearchPlan p = make_plan(ix, queries, m, k, guard_eps);
+    RLR_TRY(ctx_prepare(ix, c, m, p));
+    const size_t n_res = static_cast<size_t>(m) * p.k;
+    Staged pin;
+    RLR_TRY(stage_call(ix, c, queries, m, n_res, /*for_scans=*/false, &pin));
+    uint64_t *h_res = pin.h_res;
+    hipStream_t s = c->stream;
+    const uint64_t n = ix->n_rows;
+    const uint64_t s_stride = (n + 3) / 4 * 4;
+    const float two_eps = p.two_eps;
+    RLR_TRY(batch_arm(c, m, batch_finish_capacity(), s_stride, p.k, n));
+    const bool timed = ix->profiling;
+    const uint64_t *masks[8] = {};
+    uint64_t sum_rows = 0;
+    for (uint32_t q = 0; q < m; ++q) {
+        masks[q] = fs[q]->d_mask.get();
+        sum_rows += fs[q]->n_allowed;
+    }
+    if (timed) RLR_HIP(hipEventRecord(c->bev[0], s));
+    hipError_t e = hipSuccess;
+    if (!launch_scan_masked_scopes(scan_args(ix, c->d_query.get(), c->d_sample.get(), nullptr), masks, std::min<uint64_t>(n, sum_rows),
+                                   ix->q_pitch, m, s_stride, s, &e))
+        return set_error(RLR_E_INTERNAL, "masked multi-scope scan refused a shape its gate accepted");
+    RLR_HIP(e);
+    if (timed) RLR_HIP(hipEventRecord(c->bev[1], s));
+    RLR_HIP(launch_batch_select(c->d_sample.get(), static_cast<uint32_t>(n), s_stride, m, c->d_bhist.get(), c->d_bstate.get(), two_eps, c->d_tau.get(),
+                                c->d_bcand.get(), batch_finish_capacity(), ix->n_cu, s));
+    std::vector<uint32_t> status, n_cand;
+    RLR_TRY(batch_finish(ix, c, c->d_query.get(), m, p.k, two_eps, c->d_out.get(), status, h_res, &n_cand));
+    c->hist_dirty = false;
+    std::vector<uint32_t> redo;
+    uint64_t n_cand_total = 0;
+    for (uint32_t q = 0; q < m; ++q) {
+        bool back = status[q] != 0;
+        for (uint32_t i = 0; i < p.k && !back; ++i)
+            back = !filter_holds(fs[q], 0xFFFFFFFFu - static_cast<uint32_t>(h_res[static_cast<size_t>(q) * p.k + i]));
+        if (back) {
+            redo.push_back(q);
+            continue;
+        }
+        n_out[q] = p.k;
+        n_cand_total += n_cand[q];
+        unpack_results(h_res + static_cast<size_t>(q) * p.k, p.k, rows_out + static_cast<size_t>(q) * k, cos_out + static_cast<size_t>(q) * k);
+    }
+    {
+        float scan_ms = 0;
+        uint64_t union_rows = 0;
+        if (timed) {
+            (void)hipEventElapsedTime(&scan_ms, c->bev[0], c->bev[1]);
+            // the rows the pass read: the exact union (profiling is off by default; no call pays this otherwise)
+            const size_t n_words = fs[0]->h_mask.size();
+            for (size_t w = 0; w < n_words; ++w) {
+                uint64_t any = 0;
+                for (uint32_t q = 0; q < m; ++q)
+                    any |= fs[q]->h_mask[w];
+                union_rows += static_cast<uint64_t>(__builtin_popcountll(any));
+            }
+        }
+        std::lock_guard<std::mutex> lk(ix->mu);
+        ix->prof.n_batches += 1;
+        ix->prof.n_batch_queries += m;
+        ix->prof.n_batch_fallbacks += redo.size();
+        ix->prof.n_searches += m - redo.size(); // (a query handed back is counted by filtered_query)
+        ix->prof.n_candidates += n_cand_total;
+        if (timed) {
+            ix->prof.scan_ms += scan_ms;
+            ix->prof.scan_bytes += union_rows * ix->dim * 4;
+        }
+    }
+    // (from here on the pinned buffer and the context are filtered_query's)
+    for (uint32_t q : redo)
+        RLR_TRY(filtered_query(ix, c, fs[q], queries + static_cast<size_t>(q) * ix->dim, k, guard_eps, rows_out + static_cast<size_t>(q) * k,
+                               cos_out + static_cast<size_t>(q) * k, &n_out[q]));
+    return RLR_OK;
+}
+
 // The list path for a run of m >= 2 queries: score -> pack -> select of every query enqueued back to back on per-query
 // slices of the workspace, then one result copy and one synchronisation.  Same kernels, same results as filtered_exact.
 int32_t filtered_list_batch(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *queries, uint32_t m, uint32_t k,
@@ -3175,6 +3299,78 @@ int32_t rlr_search_topk_filtered(rlr_index *ix, const rlr_filter *f, const float
             RLR_TRY(filtered_query(ix, lease.c, f, qs, k, guard_eps, ro, co, &n_out[q0]));
         }
         q0 += m;
+    }
+    drain.armed = false;
+    return RLR_OK;
+}
+
+int32_t rlr_search_topk_scoped(rlr_index *ix, const rlr_filter *const *filters, const float *queries, uint32_t n_queries,
+                               uint32_t k, float guard_eps, uint64_t *rows_out, float *cos_out, uint32_t *n_out)
+{
+    if (!filters)
+        return set_error(RLR_E_INVALID, "null filter array");
+    RLR_TRY(check_handle(ix));
+    for (uint32_t q = 0; q < n_queries; ++q)
+        RLR_TRY(check_filter(ix, filters[q])); // (null, foreign, stale: every entry, before any GPU work)
+    if (n_queries && (!queries || !n_out))
+        return set_error(RLR_E_INVALID, "queries / n_out is null");
+    if (n_queries && k && (!rows_out || !cos_out))
+        return set_error(RLR_E_INVALID, "output buffers are null");
+    RLR_TRY(use_device(ix));
+    for (uint32_t q = 0; q < n_queries; ++q)
+        n_out[q] = 0;
+    if (k == 0 || n_queries == 0)
+        return RLR_OK;
+    CtxLease lease(ix);
+    RLR_TRY(ctx_acquire(ix, &lease.c));
+    StreamDrain drain{lease.c->stream};
+    // The queries that can join a shared pass (scoped_query_joins), in call order, in chunks of up to 8: a chunk the gate
+    // accepts is one pass over the union of its scopes (or, all filters being one object, the one-filter pass); every
+    // other query -- a list-path filter, fewer allowed rows than k, binary16 rows, other widths, a chunk the gate
+    // declines, a last chunk of one -- runs alone through filtered_query inside its own filter.
+    std::vector<uint32_t> joins;
+    for (uint32_t q = 0; q < n_queries; ++q)
+        if (scoped_query_joins(ix, filters[q], k))
+            joins.push_back(q);
+    std::vector<char> served(n_queries, 0);
+    std::vector<float> qs;
+    std::vector<uint64_t> ro;
+    std::vector<float> co;
+    for (size_t j0 = 0; j0 < joins.size(); j0 += 8) {
+        const uint32_t m = static_cast<uint32_t>(std::min<size_t>(8, joins.size() - j0));
+        const rlr_filter *fs[8] = {};
+        bool same = true;
+        for (uint32_t i = 0; i < m; ++i) {
+            fs[i] = filters[joins[j0 + i]];
+            same = same && fs[i] == fs[0];
+        }
+        const bool one_filter = same && filtered_batch_eligible(ix, fs[0], m, k);
+        if (!one_filter && !scoped_batch_eligible(ix, fs, m, k))
+            continue;
+        qs.resize(static_cast<size_t>(m) * ix->dim);
+        ro.resize(static_cast<size_t>(m) * k);
+        co.resize(static_cast<size_t>(m) * k);
+        uint32_t got[8] = {};
+        for (uint32_t i = 0; i < m; ++i)
+            std::memcpy(qs.data() + static_cast<size_t>(i) * ix->dim, queries + static_cast<size_t>(joins[j0 + i]) * ix->dim,
+                        static_cast<size_t>(ix->dim) * sizeof(float));
+        if (one_filter)
+            RLR_TRY(filtered_batch(ix, lease.c, fs[0], qs.data(), m, k, guard_eps, ro.data(), co.data(), got));
+        else
+            RLR_TRY(scoped_batch(ix, lease.c, fs, qs.data(), m, k, guard_eps, ro.data(), co.data(), got));
+        for (uint32_t i = 0; i < m; ++i) {
+            const uint32_t q = joins[j0 + i];
+            n_out[q] = got[i];
+            std::memcpy(rows_out + static_cast<size_t>(q) * k, ro.data() + static_cast<size_t>(i) * k, static_cast<size_t>(got[i]) * sizeof(uint64_t));
+            std::memcpy(cos_out + static_cast<size_t>(q) * k, co.data() + static_cast<size_t>(i) * k, static_cast<size_t>(got[i]) * sizeof(float));
+            served[q] = 1;
+        }
+    }
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        if (served[q] || filters[q]->n_allowed == 0)
+            continue;
+        RLR_TRY(filtered_query(ix, lease.c, filters[q], queries + static_cast<size_t>(q) * ix->dim, k, guard_eps,
+                               rows_out + static_cast<size_t>(q) * k, cos_out + static_cast<size_t>(q) * k, &n_out[q]));
     }
     drain.armed = false;
     return RLR_OK;

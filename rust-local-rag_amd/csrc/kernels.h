@@ -50,6 +50,16 @@ bool launch_scan_multi(const ScanArgs &a, uint32_t q_pitch, uint32_t n_queries, 
 // only -- binary16 rows, other widths and other pitches return false and keep the one-by-one masked scans.
 bool launch_scan_masked_multi(const ScanArgs &a, const uint64_t *mask, uint64_t n_allowed, uint32_t q_pitch, uint32_t n_queries,
                               size_t score_stride, hipStream_t s, hipError_t *err);
+// one masked pass for 2..8 queries with a mask EACH (queries scoped to different documents): masks[q] is query q's mask as
+// launch_scan_masked takes it (slots at or beyond n_queries are ignored; two slots may hold the same pointer), the pass
+// reads every row of the UNION of the masks once and query q's score array is the one launch_scan_masked_multi writes
+// with masks[q].  union_estimate (an upper bound of the rows in the union is enough) only picks the launch shape, the
+// way n_allowed does there.  Same shapes, same return value.
+struct ScopeMasks {
+    const uint64_t *m[8];
+};
+bool launch_scan_masked_scopes(const ScanArgs &a, const uint64_t *const masks[8], uint64_t union_estimate, uint32_t q_pitch,
+                               uint32_t n_queries, size_t score_stride, hipStream_t s, hipError_t *err);
 // launch_scan_multi over binary16 rows of C x 512 B (C = 1..4), f32 arithmetic on the exactly widened elements (coalesced
 // single-query calls only; see run_batched)
 bool launch_scan_multi_f16(const ScanArgs &a, uint32_t q_pitch, uint32_t n_queries, size_t score_stride, hipStream_t s,

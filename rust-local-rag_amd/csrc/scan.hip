@@ -794,6 +794,110 @@ __global__ __launch_bounds__(256) void scan_masked_multi_kernel(const float4 *__
     }
 }
 
+// ---------------------------------------------------------------------------
+// Masked multi-query kernel with ONE MASK PER QUERY SLOT (queries of a batch scoped to different documents):
+// scan_masked_multi_kernel whose unit reads the Q mask words of its rows (each through a wave-uniform address; a null
+// slot counts as an all-zero word; two slots may hold the same pointer), ORs them into `any` and walks `any` exactly as
+// that kernel walks its one word -- ctz / clear-lowest, R = 4 rows in flight, every branch on `any` wave-uniform, a row
+// outside the UNION never requested from HBM.  A loaded row feeds the dot4 chain and the DPP wave sum of every query
+// whose OWN word has bit[rr] set -- the chain of scan_masked_multi_kernel, so query q's score array is bit for bit the
+// one that kernel writes with q's mask (NaN sentinel everywhere else) and the band, the batched select and the finish
+// behind it are unchanged.  Whether a load is issued depends on `any` alone: membership is tested after the load group,
+// on scalars, and only decides whether a chain runs.  The chains of non-members are skipped under that wave-uniform
+// branch because it measured faster than computing and dropping them (MI355X, 1 M x 768 f32, k = 100, the pass forced,
+// whole call against the same requests one by one; DESIGN.md "Queries with different scopes in one pass"): 8 disjoint
+// scopes of 1/8 of the rows 1.17 -> 0.86 of one by one, 4 such scopes 1.02 -> 0.93, 8 random halves 0.51 -> 0.43,
+// 8 disjoint scopes of 1/80 level (0.42 / 0.43) -- Q = 8 is VALU-bound and disjoint scopes drop 7/8 of its chains.
+// The mask pointers arrive by value in the kernel arguments and, like the words read through them, live in SGPRs.
+// Registers (the compiler's resource report for gfx950, __launch_bounds__(256); VGPRs -> waves per SIMD, SGPRs):
+//            Q = 2           Q = 4           Q = 8
+//   CH = 1   35 -> 8, 46     47 -> 8, 64     65 -> 7, 104
+//   CH = 2   60 -> 8, 46     77 -> 6, 64    112 -> 4, 104
+//   CH = 3   84 -> 5, 44    110 -> 4, 64    161 -> 3, 104
+//   CH = 4  108 -> 4, 46    141 -> 3, 64    208 -> 2, 104
+// (no AGPRs, no scratch, no spill.  The VGPRs and the waves per SIMD are scan_masked_multi_kernel's, but for CH = 1, Q = 2
+// and CH = 2, Q = 8, which are one and two under; the SGPRs grow from 34-62 there by the Q pointers and the Q words.)
+// ---------------------------------------------------------------------------
+template <int CH, int Q>
+__global__ __launch_bounds__(256) void scan_masked_scopes_kernel(const float4 *__restrict__ rows, const float *__restrict__ queries,
+                                                                 uint32_t q_pitch, uint32_t n_queries, ScopeMasks masks,
+                                                                 float *__restrict__ scores, size_t score_stride, uint32_t n_rows,
+                                                                 uint32_t unit)
+{
+    constexpr int P16 = CH * 64;
+    constexpr int R = 4;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    float4 qv[Q][CH];
+#pragma unroll
+    for (int q = 0; q < Q; ++q)
+#pragma unroll
+        for (int c = 0; c < CH; ++c)
+            qv[q][c] = static_cast<uint32_t>(q) < n_queries
+                           ? reinterpret_cast<const float4 *>(queries + static_cast<size_t>(q) * q_pitch)[c * 64 + lane]
+                           : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+
+    const float masked = __builtin_bit_cast(float, 0x7FC00000u);
+    const uint32_t n_groups = (n_rows + unit - 1) / unit;
+    const uint32_t n_waves = gridDim.x * 4;
+    for (uint32_t g = blockIdx.x * 4 + wave; g < n_groups; g += n_waves) {
+        const uint32_t row0 = g * unit;
+        const uint32_t nr = min(unit, n_rows - row0);
+        uint64_t word[Q];
+        uint64_t any = 0;
+        float mine[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            word[q] = masks.m[q] ? mask_bits(masks.m[q], row0, unit, nr) : 0ull; // (uniform)
+            any |= word[q];
+            mine[q] = masked;
+        }
+        uint64_t rem = any;
+        while (rem) { // (uniform)
+            uint32_t bit[R];
+            float4 x[R][CH];
+            int m = 0;
+#pragma unroll
+            for (int rr = 0; rr < R; ++rr) {
+                bit[rr] = 0;
+                if (rem) { // (uniform)
+                    bit[rr] = static_cast<uint32_t>(__builtin_ctzll(rem));
+                    rem &= rem - 1;
+                    m = rr + 1;
+                    const float4 *p = rows + static_cast<size_t>(row0 + bit[rr]) * P16 + lane;
+#pragma unroll
+                    for (int c = 0; c < CH; ++c)
+                        x[rr][c] = ld16<true>(p + c * 64);
+                }
+            }
+#pragma unroll
+            for (int rr = 0; rr < R; ++rr) {
+                if (rr < m) { // (uniform)
+#pragma unroll
+                    for (int q = 0; q < Q; ++q) {
+                        const bool member = (word[q] >> bit[rr]) & 1ull; // is the row in query q's own scope?  (uniform)
+                        if (member) {                                     // (uniform)
+                            float acc = 0.0f;
+#pragma unroll
+                            for (int c = 0; c < CH; ++c)
+                                acc = dot4(x[rr][c], qv[q][c], acc);
+                            const float tot = wave_sum(acc);
+                            mine[q] = static_cast<uint32_t>(lane) == bit[rr] ? tot : mine[q];
+                        }
+                    }
+                }
+            }
+        }
+        if (static_cast<uint32_t>(lane) < nr) {
+#pragma unroll
+            for (int q = 0; q < Q; ++q)
+                if (static_cast<uint32_t>(q) < n_queries)
+                    scores[static_cast<size_t>(q) * score_stride + row0 + lane] = mine[q];
+        }
+    }
+}
+
 struct ScanPlan {
     uint32_t group_rows;
     uint32_t blocks;
@@ -1230,6 +1334,55 @@ bool launch_scan_masked_multi(const ScanArgs &a, const uint64_t *mask, uint64_t 
     }
 #undef RLR_MASKED_MULTI_Q
 #undef RLR_MASKED_MULTI
+    *err = hipGetLastError();
+    return true;
+}
+
+// launch_scan_masked_multi with a mask per query (kernels.h): the same shapes and the same launch policy, with the rows
+// of the union -- union_estimate, an upper bound is enough -- where that launcher has the allowed rows: a pass reads the
+// union, so the union decides between the dense and the sparse shape.  The scopes kernel's registers are those of
+// scan_masked_multi_kernel (its table), so the resident workgroups are the same.
+bool launch_scan_masked_scopes(const ScanArgs &a, const uint64_t *const masks[8], uint64_t union_estimate, uint32_t q_pitch,
+                               uint32_t n_queries, size_t score_stride, hipStream_t s, hipError_t *err)
+{
+    int ch = 0;
+    if (a.dtype != RLR_F32 || n_queries < 2 || n_queries > 8 || !fixed_shape(a, &ch) || ch > 4 || q_pitch < a.dim ||
+        score_stride < a.n_rows)
+        return false;
+    ScopeMasks sm;
+    for (uint32_t q = 0; q < 8; ++q) {
+        sm.m[q] = q < n_queries ? masks[q] : nullptr;
+        if (q < n_queries && !masks[q])
+            return false;
+    }
+    *err = hipSuccess;
+    if (a.n_rows == 0)
+        return true;
+    const bool dense = union_estimate * 4 >= a.n_rows;
+    const uint32_t unit = dense ? 8u : 16u;
+    const uint32_t q_inst = n_queries <= 2 ? 2u : n_queries <= 4 ? 4u : 8u;
+    const uint32_t resident = ch == 4 && q_inst == 8 ? 2u : (ch == 4 && q_inst == 4) || (ch == 3 && q_inst == 8) ? 3u : 4u;
+    const uint32_t wgs = dense ? 1u : resident;
+    const uint32_t n_groups = (a.n_rows + unit - 1) / unit;
+    const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((n_groups + 3) / 4, static_cast<uint32_t>(a.n_cu) * wgs));
+    const float4 *rows = static_cast<const float4 *>(a.rows);
+#define RLR_MASKED_SCOPES(CHV, QV)                                                                                       \
+    hipLaunchKernelGGL((scan_masked_scopes_kernel<CHV, QV>), dim3(blocks), dim3(256), 0, s, rows, a.query,  \
+                       q_pitch, n_queries, sm, a.scores, score_stride, a.n_rows, unit)
+#define RLR_MASKED_SCOPES_Q(CHV)                                  \
+    do {                                                          \
+        if (n_queries <= 2) RLR_MASKED_SCOPES(CHV, 2);            \
+        else if (n_queries <= 4) RLR_MASKED_SCOPES(CHV, 4);       \
+        else RLR_MASKED_SCOPES(CHV, 8);                           \
+    } while (0)
+    switch (ch) {
+    case 1: RLR_MASKED_SCOPES_Q(1); break;
+    case 2: RLR_MASKED_SCOPES_Q(2); break;
+    case 3: RLR_MASKED_SCOPES_Q(3); break;
+    default: RLR_MASKED_SCOPES_Q(4); break;
+    }
+#undef RLR_MASKED_SCOPES_Q
+#undef RLR_MASKED_SCOPES
     *err = hipGetLastError();
     return true;
 }

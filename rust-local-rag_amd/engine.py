@@ -355,10 +355,14 @@ class RagEngine:
     # -- additive batched entry point (oracle: loop search_with_diversity over the batch) -------
     def search_with_diversity_batch(self, query_embeddings, top_k: int, diversity_factor: float,
                                     weights: Optional[QueryWeights] = None,
-                                    documents: Optional[Sequence[str]] = None) -> List[List[SearchResult]]:
+                                    documents: Optional[Sequence[str]] = None,
+                                    scopes: Optional[Sequence[Sequence[str]]] = None) -> List[List[SearchResult]]:
         """`documents`: as for search_with_diversity -- every query searches only inside these documents (None: the
         whole corpus; an empty list or unknown names: no rows, an empty list per query); chunks of up to 8 queries
-        share one masked pass over the documents' rows."""
+        share one masked pass over the documents' rows.
+        `scopes`: one document list PER QUERY instead (not together with `documents`): query i is
+        search_with_diversity(q_i, ..., documents=scopes[i]); chunks of up to 8 queries share one masked pass over the
+        union of their scopes (rlr_engine_search_with_diversity_batch_scoped)."""
         q = _f32(query_embeddings)
         if q.ndim == 1:
             q = q.reshape(1, -1)
@@ -367,7 +371,20 @@ class RagEngine:
         hits = (N.SearchHitC * (cap * max(nq, 1)))()
         n_out = np.zeros(max(nq, 1), dtype=np.uint32)
         wc = weights.to_c() if weights is not None else None
-        if documents is not None:
+        if scopes is not None:
+            if documents is not None:
+                raise ValueError("search_with_diversity_batch: give `documents` or `scopes`, not both")
+            scopes = list(scopes)
+            if len(scopes) != nq:
+                raise ValueError(f"{nq} query embeddings but {len(scopes)} scopes")
+            for s in scopes:  # (a look-up that finds the index replaced drops every cached filter, those made just before too)
+                self._filter_for(s)
+            filters = [self._filter_for(s) for s in scopes]
+            handles = (C.c_void_p * max(nq, 1))(*[f.handle for f in filters])
+            N.check(N.lib().rlr_engine_search_with_diversity_batch_scoped(
+                self.index.handle, handles, q.ctypes.data_as(N.f32p), dq, nq, top_k, float(diversity_factor),
+                C.byref(wc) if wc is not None else None, hits, cap, n_out.ctypes.data_as(N.u32p)))
+        elif documents is not None:
             if not document_ranges(self._chunks, documents):
                 return [[] for _ in range(nq)]
             f = self._filter_for(documents)
@@ -425,13 +442,16 @@ class RagEngine:
             return out, {name: int(getattr(info, name)) for name, _ in N.TextBatchInfoC._fields_}
         return out
 
-    def search_documents_batch(self, requests: Sequence[SearchRequest]) -> List[List[SearchResult]]:
+    def search_documents_batch(self, requests: Sequence[SearchRequest], share_scopes: bool = False) -> List[List[SearchResult]]:
         """search_documents for every request, grouped by (top_k, diversity, weights, documents) after its caps and
         clamps.  Unscoped groups run through search_text_batch (a request without text is scored with no query terms);
         scoped groups without query text through search_with_diversity_batch(documents=...); the scoped requests of a
         group WITH query text through one search_text_batch(documents=...) when there are two or more of them, a lone
-        one through search_documents."""
+        one through search_documents.
+        share_scopes: the scoped requests WITHOUT query text of one (top_k, diversity, weights) key go through one
+        search_with_diversity_batch(scopes=...) call, whatever their scopes; everything else routes as above."""
         groups: Dict[tuple, List[int]] = {}
+        shared: Dict[tuple, List[int]] = {}
         for i, r in enumerate(requests):
             if r.lexical:
                 raise ValueError("search_documents_batch: requests carry caller-computed lexical pairs; "
@@ -442,8 +462,17 @@ class RagEngine:
             w = r.weights
             wkey = None if w is None else (w.embedding, w.lexical, w.reranker, w.initial)
             scope = None if r.documents is None else frozenset(r.documents)  # ([] is a scope: no rows)
+            if share_scopes and scope is not None and not r.query:
+                shared.setdefault((top_k, div, wkey), []).append(i)
+                continue
             groups.setdefault((top_k, div, wkey, scope), []).append(i)
         out: List[List[SearchResult]] = [[] for _ in requests]
+        for (top_k, div, _), members in shared.items():
+            emb = np.stack([_f32(requests[i].query_embedding).ravel() for i in members])
+            scopes = [sorted(set(requests[i].documents)) for i in members]
+            for i, res in zip(members, self.search_with_diversity_batch(emb, top_k, div, requests[members[0]].weights,
+                                                                        scopes=scopes)):
+                out[i] = res
         for (top_k, div, _, scope), members in groups.items():
             w = requests[members[0]].weights
             if scope is None:

@@ -198,6 +198,24 @@ class GpuIndex:
         kk = int(n_out[0]) if nq else 0
         return rows[:, :kk], cos[:, :kk]
 
+    def search_topk_scoped(self, queries, k: int, filters, guard_eps: float = -1.0):
+        """queries: [Q, dim] already normalised, filters: one RowFilter per query (entries may repeat) -> a list of
+        (rows u64 [k_q], cos f32 [k_q]) per query with k_q = min(k, rows of that query's filter): query q is
+        search_topk(queries[q], k, filter=filters[q]).  Chunks of up to 8 queries share one masked pass over the union of
+        their filters (rlr_search_topk_scoped)."""
+        q = _f32(queries).reshape(-1, self.dim)
+        nq = q.shape[0]
+        filters = list(filters)
+        if len(filters) != nq:
+            raise ValueError(f"{nq} queries but {len(filters)} filters")
+        handles = (C.c_void_p * max(nq, 1))(*[None if f is None else f.handle for f in filters])
+        rows = np.zeros((nq, max(k, 1)), dtype=np.uint64)
+        cos = np.zeros((nq, max(k, 1)), dtype=np.float32)
+        n_out = np.zeros(max(nq, 1), dtype=np.uint32)
+        N.check(self._L.rlr_search_topk_scoped(self._h, handles, _fp(q), nq, k, guard_eps, _up(rows), _fp(cos),
+                                               n_out.ctypes.data_as(N.u32p)))
+        return [(rows[i, :int(n_out[i])], cos[i, :int(n_out[i])]) for i in range(nq)]
+
     def search_topk_device(self, queries, k: int, d_out_ptr: int, stream: int = 0, guard_eps: float = -1.0) -> None:
         q = _f32(queries).reshape(-1, self.dim)
         N.check(self._L.rlr_search_topk_device(self._h, _fp(q), q.shape[0], k, guard_eps,
