@@ -158,7 +158,7 @@ int32_t rlr_engine_search_text_filtered(rlr_index *idx, rlr_lexical *lex, const 
  * 1024 elements; binary16 rows, other widths and other pitches run query by query -- and the MMR from
  * rlr_mmr_select_batch.  Argument checks and error codes of rlr_engine_search_with_diversity_batch; a stale filter, or
  * one of another index: RLR_E_INVALID before any GPU work.  Queries WITH text inside a filter:
- * rlr_engine_search_text_batch_filtered below. */
+ * rlr_engine_search_text_batch_filtered (one filter) and rlr_engine_search_text_batch_scoped (a filter per query) below. */
 int32_t rlr_engine_search_with_diversity_batch_filtered(rlr_index *idx, const rlr_filter *f, const float *queries_raw,
                                                         uint32_t dq, uint32_t n_queries, uint32_t top_k,
                                                         float diversity_factor, const rlr_query_weights *weights,
@@ -170,7 +170,7 @@ int32_t rlr_engine_search_with_diversity_batch_filtered(rlr_index *idx, const rl
  * union of their scopes), ONE rlr_mmr_select_batch with pool_sizes[q] = need_q.  An empty filter gives n_out[q] = 0.
  * The fall-backs of the other batched calls: w_embedding == 0 or a pool above 1024 loops the single call; a query whose
  * rounding-tie chain reaches its last fetched row is re-run alone.  A null array, a null, stale or foreign entry:
- * RLR_E_INVALID before any GPU work.  Queries WITH text take one filter per call (..._text_batch_filtered). */
+ * RLR_E_INVALID before any GPU work.  Queries WITH text and a filter each: rlr_engine_search_text_batch_scoped. */
 int32_t rlr_engine_search_with_diversity_batch_scoped(rlr_index *idx, const rlr_filter *const *filters,
                                                       const float *queries_raw, uint32_t dq, uint32_t n_queries,
                                                       uint32_t top_k, float diversity_factor,
@@ -191,6 +191,26 @@ int32_t rlr_engine_search_text_batch_filtered(rlr_index *idx, rlr_lexical *lex, 
                                               const uint64_t *token_offsets, uint32_t top_k, float diversity_factor,
                                               int32_t stage, const rlr_query_weights *weights, rlr_search_hit *out,
                                               uint32_t cap, uint32_t *n_out, rlr_text_batch_info *info);
+/* The same with a filter PER QUERY -- the request mcp_server.rs:89-93 serves carries a query text and a document list of
+ * its own, so a request queue holds text queries scoped to different documents.  Query q equals
+ * rlr_engine_search_text_filtered(idx, lex, filters[q], query q, tokens q, ...), bit for bit; N is |F_q| per query where
+ * the reference uses the corpus size (:476-478, :490, :544, :734), so need_q, the pool size and the result count differ
+ * inside one batch, while the BM25 limit = 5 * k_seen (:505) depends on top_k alone.  Per sub-batch of
+ * text_sub_batch(largest need) queries: ONE rlr_lexical_score_batch_scoped (a grid row per query with its own mask), ONE
+ * rlr_search_topk_scoped with k = the largest min(|F_q|, need_q + lexical count of q + 8) -- query q looks at its own
+ * first min(|F_q|, need_q + its lexical count + 8) rows, the fetch of the single call's first round -- one batched scoring
+ * of the lexical rows, the single call's blend per query (:515-532) with that query's N and need, and ONE
+ * rlr_mmr_select_batch with P = the largest need and pool_sizes[q] = need_q.  A query with an empty filter gets
+ * n_out[q] = 0 and counts neither in n_batched nor in n_single.  A query whose rounding-tie chain reaches its last
+ * looked-at row is re-run alone (n_single_blend); the whole call loops the single entry point (n_single_shape counts every
+ * query) when w_embedding == 0, a weight is not finite, the largest need is above 1024, or the batch has one query.
+ * Entries of `filters` may repeat.  A null array, a null, stale or foreign entry, or a cap below the result count of some
+ * query: RLR_E_INVALID before any GPU work; the other argument checks of rlr_engine_search_text_batch_filtered. */
+int32_t rlr_engine_search_text_batch_scoped(rlr_index *idx, rlr_lexical *lex, const rlr_filter *const *filters,
+                                            const float *queries_raw, uint32_t dq, uint32_t n_queries, const char *tokens,
+                                            const uint64_t *token_offsets, uint32_t top_k, float diversity_factor,
+                                            int32_t stage, const rlr_query_weights *weights, rlr_search_hit *out,
+                                            uint32_t cap, uint32_t *n_out, rlr_text_batch_info *info);
 
 /* Additive batched entry point (the reference has no batched API; its oracle is "loop
  * search_with_diversity over the batch"): n_queries raw query embeddings,

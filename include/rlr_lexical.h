@@ -130,6 +130,20 @@ int32_t rlr_lexical_score_batch_filtered(rlr_lexical *lex, const rlr_filter *f, 
                                          float *scores_out, uint32_t *n_out, float *max_lexical_out,
                                          uint32_t *n_single);
 
+/* The same with a filter PER QUERY (requests scoped to different documents; LexicalIndex::score :2169-2225 over the rows
+ * of filters[q] for query q): query q's result is exactly what rlr_lexical_score_filtered(lex, filters[q], tokens_q,
+ * len_q, limit, ...) returns -- the same rows, order and score bits, with the statistics of the whole index.  Result
+ * layout and max_lexical_out as above.  One chain of the batched kernels per sub-batch of 256 queries: workgroup (slice,
+ * query) of the accumulate kernel takes its mask and the index size that mask was made for from a record per query, so
+ * filters made for indexes of different sizes may stand in one call, reads its 32 mask words first and leaves when none
+ * has a bit set.  Entries may repeat.  An empty filter gives that query zero pairs and max_lexical = f32::EPSILON at no
+ * cost.  A query with more than 128 unique known terms goes through rlr_lexical_score_filtered with ITS filter and
+ * counts in *n_single.  A null array, a null or stale entry, or an entry on another device: RLR_E_INVALID before any GPU
+ * work; the other argument checks are those of rlr_lexical_score_batch. */
+int32_t rlr_lexical_score_batch_scoped(rlr_lexical *lex, const rlr_filter *const *filters, uint32_t n_queries, const char *tokens,
+                                       const uint64_t *token_offsets, uint32_t limit, uint64_t *rows_out, float *scores_out,
+                                       uint32_t *n_out, float *max_lexical_out, uint32_t *n_single);
+
 /* Convenience tokenizer for hosts without Unicode tables: exact for ASCII text; every
  * non-ASCII code point is treated as alphanumeric and left unchanged (the reference would
  * split at non-ASCII punctuation and lower-case non-ASCII letters).  Writes the space-joined

@@ -186,6 +186,10 @@ PROTOTYPES = [
                                                           C.c_uint32, C.c_float, C.c_int32, C.POINTER(QueryWeightsC),
                                                           C.POINTER(SearchHitC), C.c_uint32, u32p,
                                                           C.POINTER(TextBatchInfoC)]),
+    ("rlr_engine_search_text_batch_scoped", C.c_int32, [_H, _H, C.POINTER(_H), f32p, C.c_uint32, C.c_uint32, C.c_char_p, u64p,
+                                                        C.c_uint32, C.c_float, C.c_int32, C.POINTER(QueryWeightsC),
+                                                        C.POINTER(SearchHitC), C.c_uint32, u32p,
+                                                        C.POINTER(TextBatchInfoC)]),
     ("rlr_engine_search_with_diversity_batch", C.c_int32, [_H, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
                                                            C.POINTER(QueryWeightsC), C.POINTER(SearchHitC), C.c_uint32,
                                                            u32p]),
@@ -219,6 +223,8 @@ PROTOTYPES = [
     ("rlr_lexical_score_batch", C.c_int32, [_H, C.c_uint32, C.c_char_p, u64p, C.c_uint32, u64p, f32p, u32p, f32p, u32p]),
     ("rlr_lexical_score_batch_filtered", C.c_int32, [_H, _H, C.c_uint32, C.c_char_p, u64p, C.c_uint32, u64p, f32p, u32p, f32p,
                                                      u32p]),
+    ("rlr_lexical_score_batch_scoped", C.c_int32, [_H, C.POINTER(_H), C.c_uint32, C.c_char_p, u64p, C.c_uint32, u64p, f32p, u32p,
+                                                   f32p, u32p]),
     ("rlr_tokenize_ascii", C.c_int32, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
 ]
 

@@ -1,6 +1,6 @@
 // engine_filtered.cpp -- rlr_engine_search_filtered / _search_with_diversity_filtered / _search_text_filtered /
-// _search_with_diversity_batch_filtered / _search_text_batch_filtered
-// (include/rlr_engine.h): RagEngine::search / search_with_diversity inside a row filter.  The corpus the reference's
+// _search_with_diversity_batch_filtered / _search_with_diversity_batch_scoped / _search_text_batch_filtered /
+// _search_text_batch_scoped (include/rlr_engine.h): RagEngine::search / search_with_diversity inside a row filter.  The corpus the reference's
 // code sees is the filter's rows in ascending order: the host half is engine_host.h over a backend whose candidate
 // universe is the filter -- its size where the reference uses the corpus size, its bit where a lexical pair is checked
 // against the corpus, its first rows where w_embedding == 0 enumerates rows -- and whose top-k is
@@ -388,6 +388,195 @@ int32_t rlr_engine_search_text_batch_filtered(rlr_index *idx, rlr_lexical *lex, 
         info->n_single_blend = static_cast<uint32_t>(redo.size());
         info->n_single = info->n_single_blend;
         info->n_batched = n_queries - info->n_single;
+    }
+    return RLR_OK;
+}
+
+// rlr_engine_search_text_filtered for many queries with a filter EACH: the chain of rlr_engine_search_text_batch_filtered
+// with the candidate universe of query q = filters[q].  N, need, the pool size and the result count are per query; the
+// BM25 limit depends on top_k alone.  ONE rlr_search_topk_scoped call fetches the largest min(|F_q|, need_q + lexical
+// count + 8) of the sub-batch and query q looks at its own first rows only -- the fetch of the single call's first
+// round, so its boundary rule decides the same way.  The MMR runs over the non-empty pools with P = the largest need.
+int32_t rlr_engine_search_text_batch_scoped(rlr_index *idx, rlr_lexical *lex, const rlr_filter *const *filters,
+                                            const float *queries_raw, uint32_t dq, uint32_t n_queries, const char *tokens,
+                                            const uint64_t *token_offsets, uint32_t top_k, float diversity_factor, int32_t stage,
+                                            const rlr_query_weights *weights, rlr_search_hit *out, uint32_t cap, uint32_t *n_out,
+                                            rlr_text_batch_info *info)
+{
+    if (info)
+        *info = rlr_text_batch_info{};
+    if (!idx || !lex || !filters || (n_queries && (!n_out || !token_offsets || (dq && !queries_raw))))
+        return RLR_E_INVALID;
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        if (token_offsets[q + 1] < token_offsets[q])
+            return RLR_E_INVALID;
+    }
+    if (n_queries && token_offsets[n_queries] > token_offsets[0] && !tokens)
+        return RLR_E_INVALID;
+    for (uint32_t q = 0; q < n_queries; ++q)
+        n_out[q] = 0;
+    int32_t st = RLR_OK;
+    for (uint32_t q = 0; q < n_queries; ++q) // a null or stale entry, or one of another index: before any GPU work
+        if ((st = rlr::filter_check(idx, filters[q])) != RLR_OK)
+            return st;
+    if (n_queries == 0)
+        return RLR_OK;
+    std::vector<FilteredBackend> one(n_queries);
+    for (uint32_t q = 0; q < n_queries; ++q)
+        if ((st = filtered_backend(idx, filters[q], &one[q])) != RLR_OK)
+            return st;
+    const uint32_t dim = one[0].dim;
+    // the sizes rlr_engine_search_text_filtered works with, per query where they depend on |F_q|
+    float lambda = diversity_factor;
+    if (lambda < 0.0f) lambda = 0.0f;
+    if (lambda > 1.0f) lambda = 1.0f;
+    const bool diversify = !(lambda == 0.0f);
+    rlr_resolved_weights w;
+    rlr_resolve_weights(weights, &w);
+    const uint32_t k_seen = std::max<uint32_t>(diversify ? pool_size_of(top_k) : top_k, 1u);
+    const uint32_t limit = static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(k_seen) * 5, 0xFFFFFFFFull));
+    const uint32_t lcap = std::min<uint32_t>(limit, RLR_LEXICAL_MAX_LIMIT);
+    std::vector<uint64_t> need(n_queries);
+    uint64_t max_need = 0, n_res_max = 0;
+    uint32_t n_live = 0;
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        const uint64_t N = one[q].n_rows;
+        need[q] = N ? need_of(N, diversify ? pool_size_of(top_k) : top_k, diversify ? 0 : stage) : 0;
+        if (N == 0) // :476-478
+            continue;
+        ++n_live;
+        max_need = std::max(max_need, need[q]);
+        n_res_max = std::max<uint64_t>(
+            n_res_max, rlr::result_k_cap(top_k, static_cast<uint32_t>(std::min<uint64_t>(need[q], 0xFFFFFFFFull)), diversify));
+    }
+    if (n_live == 0)
+        return RLR_OK;
+    if (!out || cap < n_res_max)
+        return RLR_E_INVALID; // (cap below the result count of a query)
+    auto single = [&](uint32_t q) {
+        return rlr_engine_search_text_filtered(idx, lex, filters[q], queries_raw ? queries_raw + static_cast<size_t>(q) * dq : nullptr,
+                                               dq, tokens ? tokens + token_offsets[q] : nullptr,
+                                               static_cast<size_t>(token_offsets[q + 1] - token_offsets[q]), top_k, diversity_factor,
+                                               stage, weights, out + static_cast<size_t>(q) * cap, cap, &n_out[q]);
+    };
+    // the shapes the one-filter batch hands to the single entry point as well
+    if (w.embedding == 0.0f || !std::isfinite(w.embedding) || !std::isfinite(w.lexical) || max_need > 1024 || n_queries == 1) {
+        for (uint32_t q = 0; q < n_queries; ++q)
+            if ((st = single(q)) != RLR_OK)
+                return st;
+        if (info) {
+            info->n_single = n_queries;
+            info->n_single_shape = n_queries;
+        }
+        return RLR_OK;
+    }
+    const uint32_t P = static_cast<uint32_t>(max_need);
+    const uint32_t sub = std::min(text_sub_batch(P, diversify), n_queries);
+    std::vector<uint64_t> lrows(static_cast<size_t>(sub) * lcap), rows, lists, prow;
+    std::vector<float> lscores(lrows.size()), qn(static_cast<size_t>(sub) * dim), cosv, lcos, psc;
+    std::vector<uint32_t> n_lex(sub), got(sub), counts(sub), psz, order, nsel, redo, live;
+    std::vector<LexPrep> lexp(sub);
+    std::vector<std::vector<Cand>> pools(sub);
+    std::vector<char> seen, undecided(sub);
+    for (uint32_t q0 = 0; q0 < n_queries; q0 += sub) {
+        const uint32_t m = std::min(sub, n_queries - q0);
+        bool any_row = false;
+        for (uint32_t q = 0; q < m; ++q)
+            any_row = any_row || one[q0 + q].n_rows != 0;
+        if (!any_row)
+            continue; // (every scope of this sub-batch is empty)
+        // 1. BM25 of every query inside its own filter
+        st = rlr_lexical_score_batch_scoped(lex, filters + q0, m, tokens, token_offsets + q0, lcap, lrows.data(), lscores.data(),
+                                            n_lex.data(), nullptr, nullptr);
+        if (st != RLR_OK)
+            return st;
+        // 2. the queries and the lexical maps, as generic_search prepares them
+        if (dq)
+            prepare_queries(queries_raw + static_cast<size_t>(q0) * dq, dq, m, dim, qn.data());
+        else
+            std::fill(qn.begin(), qn.end(), 0.0f);
+        uint32_t max_lex = 0;
+        uint64_t max_fetch = 0;
+        for (uint32_t q = 0; q < m; ++q) {
+            const FilteredBackend &be = one[q0 + q];
+            lexp[q] = prepare_lexical_in([&be](uint64_t row) { return be.holds(row); }, lrows.data() + static_cast<size_t>(q) * lcap,
+                                         lscores.data() + static_cast<size_t>(q) * lcap, n_lex[q]);
+            counts[q] = static_cast<uint32_t>(lexp[q].rows.size());
+            max_lex = std::max(max_lex, counts[q]);
+            max_fetch = std::max(max_fetch, std::min<uint64_t>(be.n_rows, need[q0 + q] + counts[q] + 8));
+        }
+        // 3. one top-k call with the largest fetch: query q gets min(fetch, |F_q|) rows back and looks at its own first ones
+        const uint32_t fetch = static_cast<uint32_t>(max_fetch);
+        rows.assign(static_cast<size_t>(m) * fetch, 0);
+        cosv.assign(rows.size(), 0.0f);
+        st = rlr_search_topk_scoped(idx, filters + q0, qn.data(), m, fetch, -1.0f, rows.data(), cosv.data(), got.data());
+        if (st != RLR_OK)
+            return st;
+        // 4. exact cosines of every query's lexical rows
+        lists.assign(static_cast<size_t>(m) * max_lex, 0);
+        lcos.assign(lists.size(), 0.0f);
+        for (uint32_t q = 0; q < m; ++q)
+            std::copy(lexp[q].rows.begin(), lexp[q].rows.end(), lists.begin() + static_cast<size_t>(q) * max_lex);
+        st = rlr::score_rows_batch(idx, qn.data(), m, lists.data(), counts.data(), max_lex, lcos.data());
+        if (st != RLR_OK)
+            return st;
+        // 5. blend per query, with its own N and need
+        live.clear();
+        for (uint32_t q = 0; q < m; ++q) {
+            const uint64_t N = one[q0 + q].n_rows, nd = need[q0 + q];
+            pools[q].clear();
+            undecided[q] = 0;
+            if (N == 0)
+                continue; // (an empty scope: no result, neither batched nor single)
+            const uint32_t look = static_cast<uint32_t>(std::min<uint64_t>(got[q], std::min<uint64_t>(N, nd + counts[q] + 8)));
+            undecided[q] = !blend_fetched(w, lexp[q], lcos.data() + static_cast<size_t>(q) * max_lex, rows.data() + static_cast<size_t>(q) * fetch,
+                                          cosv.data() + static_cast<size_t>(q) * fetch, look, N, nd, seen, pools[q]);
+            if (undecided[q])
+                redo.push_back(q0 + q); // the single call widens its fetch
+            if (pools[q].size() > nd)
+                pools[q].resize(nd);
+            if (!undecided[q] && !pools[q].empty())
+                live.push_back(q);
+        }
+        // 6. one MMR over the decided, non-empty pools (generic_search_with_diversity per query)
+        if (diversify && !live.empty()) {
+            const uint32_t nl = static_cast<uint32_t>(live.size());
+            prow.assign(static_cast<size_t>(nl) * P, 0);
+            psc.assign(prow.size(), 0.0f);
+            order.assign(prow.size(), 0);
+            psz.assign(nl, 0);
+            nsel.assign(nl, 0);
+            for (uint32_t j = 0; j < nl; ++j) {
+                const std::vector<Cand> &c = pools[live[j]];
+                psz[j] = static_cast<uint32_t>(c.size());
+                for (uint32_t i = 0; i < psz[j]; ++i) {
+                    prow[static_cast<size_t>(j) * P + i] = c[i].row;
+                    psc[static_cast<size_t>(j) * P + i] = c[i].c;
+                }
+            }
+            st = one[0].mmr(prow.data(), psc.data(), psz.data(), nl, P, top_k, lambda, order.data(), nsel.data());
+            if (st != RLR_OK)
+                return st;
+            std::vector<Cand> picked;
+            for (uint32_t j = 0; j < nl; ++j) {
+                const uint32_t q = live[j];
+                picked.clear();
+                for (uint32_t i = 0; i < nsel[j]; ++i)
+                    picked.push_back(pools[q][order[static_cast<size_t>(j) * P + i]]);
+                pools[q].swap(picked);
+            }
+        }
+        for (uint32_t q = 0; q < m; ++q)
+            if (!undecided[q])
+                emit(pools[q], out + static_cast<size_t>(q0 + q) * cap, cap, &n_out[q0 + q]);
+    }
+    for (uint32_t q : redo)
+        if ((st = single(q)) != RLR_OK)
+            return st;
+    if (info) {
+        info->n_single_blend = static_cast<uint32_t>(redo.size());
+        info->n_single = info->n_single_blend;
+        info->n_batched = n_live - info->n_single;
     }
     return RLR_OK;
 }

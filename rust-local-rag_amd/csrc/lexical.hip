@@ -42,6 +42,7 @@
 #include <shared_mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -819,14 +820,29 @@ struct BatchQuery {
 constexpr uint32_t kSliceWords = kLdsRows / 64;
 static_assert(kLdsRows % 64 == 0, "a slice starts on a mask word");
 
-template <bool MASKED>
+// SCOPED (rlr_lexical_score_batch_scoped; implies MASKED): a mask PER QUERY.  Grid row q takes its mask and the index size
+// that mask was made for from scope record q, uploaded behind the term table; `mask_arg` carries the records and
+// `mask_rows_arg` is unused.  mask_rows is per query because filters made for indexes of different sizes are legal
+// in one call: the grid is sized by the largest min(n_rows, mask_rows_q), and a workgroup whose slice starts at or beyond
+// its own query's mask_rows leaves at once.  Everything else is the masked form: the 32 words first, the uniform exit, the
+// bit test in LDS.
+struct BatchScope {
+    const uint64_t *mask;
+    uint32_t mask_rows;
+    uint32_t pad;
+};
+static_assert(sizeof(BatchScope) == 16, "two 64-bit words of the term table per query");
+
+template <bool MASKED, bool SCOPED = false>
 __global__ __launch_bounds__(256) void bm25_batch_kernel(const BatchQuery *__restrict__ bq, const BatchTerm *__restrict__ bt,
                                                          const uint32_t *__restrict__ post_row, const uint32_t *__restrict__ post_tf,
                                                          const uint32_t *__restrict__ dpost_row, const uint32_t *__restrict__ dpost_tf,
                                                          const uint32_t *__restrict__ doc_len, uint32_t n_rows, float avg,
                                                          uint64_t *__restrict__ keys, LexControl *__restrict__ ctls,
-                                                         const uint64_t *__restrict__ mask, uint32_t mask_rows)
+                                                         std::conditional_t<SCOPED, const BatchScope *, const uint64_t *> __restrict__ mask_arg,
+                                                         uint32_t mask_rows_arg)
 {
+    static_assert(MASKED || !SCOPED, "a scope is a mask");
     __shared__ uint32_t s_range[kBatchTermsMax][4]; // [term][main lo, main hi, appended lo, appended hi]
     __shared__ float s_sc[kLdsRows], s_dl[kLdsRows], s_nk[kLdsRows];
     __shared__ uint8_t s_fl[kLdsRows];
@@ -839,6 +855,18 @@ __global__ __launch_bounds__(256) void bm25_batch_kernel(const BatchQuery *__res
         return;
     const uint32_t r1 = min(r0 + kLdsRows, n_rows), nr = r1 - r0;
     if constexpr (MASKED) {
+        const uint64_t *__restrict__ mask;
+        uint32_t mask_rows;
+        if constexpr (SCOPED) {
+            const BatchScope S = mask_arg[blockIdx.y]; // (uniform)
+            mask = S.mask;
+            mask_rows = S.mask_rows;
+            if (r0 >= mask_rows)
+                return; // (uniform) the slice lies beyond the index this query's filter was made for
+        } else {
+            mask = mask_arg;
+            mask_rows = mask_rows_arg;
+        }
         int allowed = 0;
         if (tid < kSliceWords) {
             const uint32_t w = (r0 >> 6) + tid, n_words = (mask_rows >> 6) + ((mask_rows & 63u) != 0u); // (no overflow)
@@ -1942,13 +1970,14 @@ struct BatchGuard { // releases whatever lexical_batch_enqueue had taken when it
 } // namespace
 
 int32_t lexical_batch_enqueue(rlr_lexical *lx, uint32_t nq, const char *tokens, const uint64_t *offsets, uint32_t limit,
-                              const LexBatchSink &sink, uint8_t *too_many_terms, LexBatchPending *out, const FilterView *filter)
+                              const LexBatchSink &sink, uint8_t *too_many_terms, LexBatchPending *out, const FilterView *filter,
+                              const FilterView *scopes)
 {
     out->lx = lx;
     out->ws = nullptr;
     out->ready = nullptr;
     out->locked = false;
-    if (nq == 0 || limit == 0 || limit > kMaxLimit || limit > sink.bound)
+    if (nq == 0 || limit == 0 || limit > kMaxLimit || limit > sink.bound || (filter && scopes))
         return set_error(RLR_E_INVALID, "lexical batch: bad arguments");
     lx->mu.lock_shared(); // held until lexical_batch_finish: mutators wait, scoring calls do not
     out->locked = true;
@@ -1965,8 +1994,8 @@ int32_t lexical_batch_enqueue(rlr_lexical *lx, uint32_t nq, const char *tokens, 
         lx->mu.lock_shared();
         out->locked = true;
     }
-    // the term table: [BatchQuery x nq][BatchTerm ...], each query's unique known terms in order of first occurrence (the
-    // order lexical_enqueue adds them in)
+    // the term table: [BatchQuery x nq][BatchTerm ...][BatchScope x nq, scoped calls only], each query's unique known terms in
+    // order of first occurrence (the order lexical_enqueue adds them in)
     const uint64_t n_rows = lx->doc_terms.size();
     const bool any_docs = lx->total_docs > 0;
     const float n_docs = static_cast<float>(lx->total_docs);
@@ -1975,12 +2004,13 @@ int32_t lexical_batch_enqueue(rlr_lexical *lx, uint32_t nq, const char *tokens, 
     std::vector<BatchTerm> ts;
     std::vector<std::string> toks;
     std::vector<uint32_t> terms;
-    uint64_t total_keys = 0, max_keys = 0;
+    uint64_t total_keys = 0, max_keys = 0, covered_scopes = 0;
     for (uint32_t q = 0; q < nq; ++q) {
         too_many_terms[q] = 0;
         toks.clear();
         terms.clear();
-        if (any_docs)
+        const bool no_row = scopes && (scopes[q].n_allowed == 0 || scopes[q].index_rows == 0); // an empty scope: nt = 0, no work
+        if (any_docs && !no_row)
             split_tokens(tokens + offsets[q], static_cast<size_t>(offsets[q + 1] - offsets[q]), &toks);
         for (const auto &t : toks) {
             auto it = lx->term_id.find(t);
@@ -2011,15 +2041,27 @@ int32_t lexical_batch_enqueue(rlr_lexical *lx, uint32_t nq, const char *tokens, 
             upper += std::max<uint64_t>(lx->df[t], static_cast<uint64_t>(bt.cnt_m) + bt.cnt_d);
         }
         upper = std::min<uint64_t>(upper, n_rows); // at most one key per row
+        if (scopes) {
+            upper = std::min<uint64_t>(upper, scopes[q].n_allowed); // ... and per allowed row
+            if (!terms.empty()) // (a query without terms has no workgroup that goes on: it does not size the grid)
+                covered_scopes = std::max(covered_scopes, std::min<uint64_t>(n_rows, scopes[q].index_rows));
+        }
         total_keys += upper;
         max_keys = std::max(max_keys, upper);
     }
     const size_t q_bytes = static_cast<size_t>(nq) * sizeof(BatchQuery);
-    const size_t tab_bytes = q_bytes + ts.size() * sizeof(BatchTerm);
+    const size_t s_off = q_bytes + ts.size() * sizeof(BatchTerm); // (a multiple of 8: the records are 16 and 32 bytes)
+    const size_t tab_bytes = s_off + (scopes ? static_cast<size_t>(nq) * sizeof(BatchScope) : 0);
     out->table.resize((tab_bytes + 7) / 8);
     std::memcpy(out->table.data(), qs.data(), q_bytes);
     if (!ts.empty())
         std::memcpy(reinterpret_cast<char *>(out->table.data()) + q_bytes, ts.data(), ts.size() * sizeof(BatchTerm));
+    if (scopes) {
+        std::vector<BatchScope> sc(nq);
+        for (uint32_t q = 0; q < nq; ++q)
+            sc[q] = BatchScope{scopes[q].d_mask, static_cast<uint32_t>(std::min<uint64_t>(scopes[q].index_rows, 0xFFFFFFFFull)), 0u};
+        std::memcpy(reinterpret_cast<char *>(out->table.data()) + s_off, sc.data(), sc.size() * sizeof(BatchScope));
+    }
 
     LexWorkspace *ws = nullptr;
     LEX_TRY(workspace_acquire(lx, &ws));
@@ -2033,7 +2075,17 @@ int32_t lexical_batch_enqueue(rlr_lexical *lx, uint32_t nq, const char *tokens, 
     const BatchTerm *d_t = reinterpret_cast<const BatchTerm *>(reinterpret_cast<const char *>(ws->d_btab.get()) + q_bytes);
     LEX_HIP(hipMemsetAsync(ws->d_bctl.get(), 0, static_cast<size_t>(nq) * sizeof(LexControl), s));
     LEX_HIP(hipMemcpyAsync(ws->d_btab.get(), out->table.data(), tab_bytes, hipMemcpyHostToDevice, s));
-    if (!ts.empty() && n_rows > 0 && !filter) {
+    if (!ts.empty() && n_rows > 0 && scopes) {
+        // (one grid for every scope: as many slices as the widest min(n_rows, mask_rows_q) has; grid row q leaves by itself
+        // at or beyond its own mask_rows)
+        if (covered_scopes > 0) {
+            const BatchScope *d_s = reinterpret_cast<const BatchScope *>(reinterpret_cast<const char *>(ws->d_btab.get()) + s_off);
+            const uint32_t slices = static_cast<uint32_t>((covered_scopes + kLdsRows - 1) / kLdsRows);
+            hipLaunchKernelGGL((bm25_batch_kernel<true, true>), dim3(slices, nq), dim3(256), 0, s, d_q, d_t, lx->d_post_row.get(),
+                               lx->d_post_tf.get(), lx->d_dpost_row.get(), lx->d_dpost_tf.get(), lx->d_doc_len.get(),
+                               static_cast<uint32_t>(n_rows), avg, ws->d_bkeys.get(), ws->d_bctl.get(), d_s, 0u);
+        }
+    } else if (!ts.empty() && n_rows > 0 && !filter) {
         const uint32_t slices = static_cast<uint32_t>((n_rows + kLdsRows - 1) / kLdsRows);
         hipLaunchKernelGGL(bm25_batch_kernel<false>, dim3(slices, nq), dim3(256), 0, s, d_q, d_t, lx->d_post_row.get(), lx->d_post_tf.get(),
                            lx->d_dpost_row.get(), lx->d_dpost_tf.get(), lx->d_doc_len.get(), static_cast<uint32_t>(n_rows), avg, ws->d_bkeys.get(),
@@ -2120,10 +2172,11 @@ static int32_t lex_batch_check_args(const rlr_lexical *lx, uint32_t nq, const ch
     return RLR_OK;
 }
 
-// f / v: null (every row), or a filter and its checked view
+// f / v: null (every row), or a filter and its checked view; fs / vs: null, or a filter and its checked view per query
 static int32_t lexical_score_batch_impl(rlr_lexical *lx, const rlr_filter *f, const rlr::FilterView *v, uint32_t nq, const char *tokens,
                                         const uint64_t *offsets, uint32_t limit, uint64_t *rows_out, float *scores_out,
-                                        uint32_t *n_out, float *max_lexical_out, uint32_t *n_single);
+                                        uint32_t *n_out, float *max_lexical_out, uint32_t *n_single,
+                                        const rlr_filter *const *fs = nullptr, const rlr::FilterView *vs = nullptr);
 
 extern "C" int32_t rlr_lexical_score_batch(rlr_lexical *lx, uint32_t nq, const char *tokens, const uint64_t *offsets,
                                            uint32_t limit, uint64_t *rows_out, float *scores_out, uint32_t *n_out,
@@ -2160,9 +2213,29 @@ extern "C" int32_t rlr_lexical_score_batch_filtered(rlr_lexical *lx, const rlr_f
     return lexical_score_batch_impl(lx, f, &v, nq, tokens, offsets, limit, rows_out, scores_out, n_out, max_lexical_out, n_single);
 }
 
+extern "C" int32_t rlr_lexical_score_batch_scoped(rlr_lexical *lx, const rlr_filter *const *filters, uint32_t nq, const char *tokens,
+                                                  const uint64_t *offsets, uint32_t limit, uint64_t *rows_out, float *scores_out,
+                                                  uint32_t *n_out, float *max_lexical_out, uint32_t *n_single)
+{
+    if (n_single)
+        *n_single = 0;
+    LEX_TRY(lex_batch_check_args(lx, nq, tokens, offsets, limit, rows_out, scores_out, n_out));
+    if (!filters)
+        return set_error(RLR_E_INVALID, "the filter array is null");
+    std::vector<rlr::FilterView> vs(nq);
+    for (uint32_t q = 0; q < nq; ++q) // (null, stale, another device: before any GPU work)
+        LEX_TRY(lex_filter_view(lx, filters[q], &vs[q]));
+    if (nq == 0)
+        return RLR_OK;
+    // (a query with an empty filter runs through the chain with no terms: zero pairs, max_lexical = f32::EPSILON)
+    return lexical_score_batch_impl(lx, nullptr, nullptr, nq, tokens, offsets, limit, rows_out, scores_out, n_out, max_lexical_out,
+                                    n_single, filters, vs.data());
+}
+
 static int32_t lexical_score_batch_impl(rlr_lexical *lx, const rlr_filter *f, const rlr::FilterView *v, uint32_t nq, const char *tokens,
                                         const uint64_t *offsets, uint32_t limit, uint64_t *rows_out, float *scores_out,
-                                        uint32_t *n_out, float *max_lexical_out, uint32_t *n_single)
+                                        uint32_t *n_out, float *max_lexical_out, uint32_t *n_single, const rlr_filter *const *fs,
+                                        const rlr::FilterView *vs)
 {
     LEX_HIP(hipSetDevice(lx->device));
     // sub-batches of the engine's size (one grid row of bm25_batch_kernel per query)
@@ -2189,7 +2262,7 @@ static int32_t lexical_score_batch_impl(rlr_lexical *lx, const rlr_filter *f, co
     for (uint32_t q0 = 0; q0 < nq; q0 += sub) {
         const uint32_t m = std::min(sub, nq - q0);
         rlr::LexBatchPending lp;
-        int32_t st = rlr::lexical_batch_enqueue(lx, m, tokens, offsets + q0, limit, sink, many.data(), &lp, v);
+        int32_t st = rlr::lexical_batch_enqueue(lx, m, tokens, offsets + q0, limit, sink, many.data(), &lp, v, vs ? vs + q0 : nullptr);
         if (st == RLR_OK && hipEventSynchronize(static_cast<hipEvent_t>(lp.ready)) != hipSuccess)
             st = set_error(RLR_E_HIP, "lexical batch did not complete");
         if (st == RLR_OK &&
@@ -2229,7 +2302,9 @@ static int32_t lexical_score_batch_impl(rlr_lexical *lx, const rlr_filter *f, co
         const size_t o = static_cast<size_t>(g) * limit;
         const char *tk = tokens ? tokens + offsets[g] : nullptr;
         const size_t len = static_cast<size_t>(offsets[g + 1] - offsets[g]);
-        if (f)
+        if (fs) // (its own filter)
+            LEX_TRY(rlr_lexical_score_filtered(lx, fs[g], tk, len, limit, rows_out + o, scores_out + o, &n_out[g]));
+        else if (f)
             LEX_TRY(rlr_lexical_score_filtered(lx, f, tk, len, limit, rows_out + o, scores_out + o, &n_out[g]));
         else
             LEX_TRY(rlr_lexical_score(lx, tk, len, limit, rows_out + o, scores_out + o, &n_out[g]));

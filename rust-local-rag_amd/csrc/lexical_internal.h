@@ -98,10 +98,13 @@ struct LexBatchPending {
 // filter (may be null: every row): the view of a current row filter on the device of `lx` (filter_internal.h; the caller
 // checked both) -- only its rows are candidates, with the semantics of rlr_lexical_score_filtered per query; the caller
 // keeps the filter alive until lexical_batch_finish.
+// scopes (may be null; exclusive with filter): nq such views, one per query (entries may repeat) -- query q's candidates are
+// the rows of scopes[q], with the semantics of rlr_lexical_score_filtered(scopes[q]) per query; a query with an empty scope
+// gets no terms and costs nothing.  The views may belong to indexes of different sizes.
 struct FilterView;
 int32_t lexical_batch_enqueue(rlr_lexical *lx, uint32_t nq, const char *tokens, const uint64_t *offsets, uint32_t limit,
                               const LexBatchSink &sink, uint8_t *too_many_terms, LexBatchPending *out,
-                              const FilterView *filter = nullptr);
+                              const FilterView *filter = nullptr, const FilterView *scopes = nullptr);
 // drains the workspace's stream, hands it back and drops the readers' lock (also after a failed enqueue)
 void lexical_batch_finish(LexBatchPending *p, bool ok);
 // (index.hip) query q's keys at d_sel[q * sel_stride], count at d_count[q * count_stride]; no error check inside

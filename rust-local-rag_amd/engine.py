@@ -404,20 +404,31 @@ class RagEngine:
     # -- many query texts at once (oracle: search / search_with_diversity with query_text, per query) -------------
     def search_text_batch(self, query_embeddings, query_texts: Sequence[str], top_k: int, diversity_factor: float = 0.0,
                           weights: Optional[QueryWeights] = None, stage: int = 0, return_info: bool = False,
-                          documents: Optional[Sequence[str]] = None):
+                          documents: Optional[Sequence[str]] = None,
+                          scopes: Optional[Sequence[Sequence[str]]] = None):
         """`search_with_diversity(q, top_k, diversity_factor, weights, query_text=t)` (diversity 0: `search(q, top_k,
         weights, stage=stage, query_text=t)`) for every (q, t) pair, bit for bit, through the batched kernels.  Returns
         one result list per query, and with return_info also a dict of how the queries were served.
         `documents`: every query searches only inside these documents, as with `documents=` on the single calls (None:
         the whole corpus; an empty list or unknown names: no rows, an empty list per query) -- one masked batched BM25,
         one filtered top-k call, one scoring of the lexical rows and one MMR per sub-batch
-        (rlr_engine_search_text_batch_filtered)."""
+        (rlr_engine_search_text_batch_filtered).
+        `scopes`: one document list PER QUERY instead (not together with `documents`): query i is the single call with
+        query_text=t_i and documents=scopes[i] ([] or unknown names: an empty scope, no results for that query) -- one
+        batched BM25 with a mask per query, one scoped top-k call over the union of the scopes, one scoring of the lexical
+        rows and one MMR per sub-batch (rlr_engine_search_text_batch_scoped)."""
+        if scopes is not None and documents is not None:
+            raise ValueError("search_text_batch: give `documents` or `scopes`, not both")
         q = _f32(query_embeddings)
         if q.ndim == 1:
             q = q.reshape(1, -1)
         nq, dq = q.shape
         if len(query_texts) != nq:
             raise ValueError(f"{nq} query embeddings but {len(query_texts)} query texts")
+        if scopes is not None:
+            scopes = list(scopes)
+            if len(scopes) != nq:
+                raise ValueError(f"{nq} query embeddings but {len(scopes)} scopes")
         toks = [" ".join(tokenize(t)).encode("utf-8") for t in query_texts]
         offsets = np.zeros(nq + 1, dtype=np.uint64)
         offsets[1:] = np.cumsum([len(t) for t in toks], dtype=np.uint64) if nq else []
@@ -429,7 +440,13 @@ class RagEngine:
         wc = weights.to_c() if weights is not None else None
         tail = (q.ctypes.data_as(N.f32p), dq, nq, blob, offsets.ctypes.data_as(N.u64p), top_k, float(diversity_factor), stage,
                 C.byref(wc) if wc is not None else None, hits, cap, n_out.ctypes.data_as(N.u32p), C.byref(info))
-        if documents is None:
+        if scopes is not None:
+            for s in scopes:  # (a look-up that finds the index replaced drops every cached filter, those made just before too)
+                self._filter_for(s)
+            filters = [self._filter_for(s) for s in scopes]
+            handles = (C.c_void_p * max(nq, 1))(*[f.handle for f in filters])
+            N.check(N.lib().rlr_engine_search_text_batch_scoped(self.index.handle, self.lexical._h, handles, *tail))
+        elif documents is None:
             N.check(N.lib().rlr_engine_search_text_batch(self.index.handle, self.lexical._h, *tail))
         elif document_ranges(self._chunks, documents):
             f = self._filter_for(documents)
@@ -442,16 +459,21 @@ class RagEngine:
             return out, {name: int(getattr(info, name)) for name, _ in N.TextBatchInfoC._fields_}
         return out
 
-    def search_documents_batch(self, requests: Sequence[SearchRequest], share_scopes: bool = False) -> List[List[SearchResult]]:
+    def search_documents_batch(self, requests: Sequence[SearchRequest], share_scopes: bool = False,
+                               share_text_scopes: bool = False) -> List[List[SearchResult]]:
         """search_documents for every request, grouped by (top_k, diversity, weights, documents) after its caps and
         clamps.  Unscoped groups run through search_text_batch (a request without text is scored with no query terms);
         scoped groups without query text through search_with_diversity_batch(documents=...); the scoped requests of a
         group WITH query text through one search_text_batch(documents=...) when there are two or more of them, a lone
         one through search_documents.
         share_scopes: the scoped requests WITHOUT query text of one (top_k, diversity, weights) key go through one
-        search_with_diversity_batch(scopes=...) call, whatever their scopes; everything else routes as above."""
+        search_with_diversity_batch(scopes=...) call, whatever their scopes; everything else routes as above.
+        share_text_scopes (independent of share_scopes): the scoped requests WITH query text of one (top_k, diversity,
+        weights) key go through one search_text_batch(scopes=...) call, whatever their scopes, when there are two or
+        more of them; a lone one through search_documents."""
         groups: Dict[tuple, List[int]] = {}
         shared: Dict[tuple, List[int]] = {}
+        shared_text: Dict[tuple, List[int]] = {}
         for i, r in enumerate(requests):
             if r.lexical:
                 raise ValueError("search_documents_batch: requests carry caller-computed lexical pairs; "
@@ -465,6 +487,9 @@ class RagEngine:
             if share_scopes and scope is not None and not r.query:
                 shared.setdefault((top_k, div, wkey), []).append(i)
                 continue
+            if share_text_scopes and scope is not None and r.query:
+                shared_text.setdefault((top_k, div, wkey), []).append(i)
+                continue
             groups.setdefault((top_k, div, wkey, scope), []).append(i)
         out: List[List[SearchResult]] = [[] for _ in requests]
         for (top_k, div, _), members in shared.items():
@@ -472,6 +497,16 @@ class RagEngine:
             scopes = [sorted(set(requests[i].documents)) for i in members]
             for i, res in zip(members, self.search_with_diversity_batch(emb, top_k, div, requests[members[0]].weights,
                                                                         scopes=scopes)):
+                out[i] = res
+        for (top_k, div, _), members in shared_text.items():
+            if len(members) < 2:  # (a batch of one is outside the fused path)
+                out[members[0]] = self.search_documents(requests[members[0]])
+                continue
+            emb = np.stack([_f32(requests[i].query_embedding).ravel() for i in members])
+            texts = [requests[i].query for i in members]
+            scopes = [sorted(set(requests[i].documents)) for i in members]
+            for i, res in zip(members, self.search_text_batch(emb, texts, top_k, div, requests[members[0]].weights,
+                                                              scopes=scopes)):
                 out[i] = res
         for (top_k, div, _, scope), members in groups.items():
             w = requests[members[0]].weights

@@ -110,11 +110,15 @@ class LexicalIndex:
                                               sc.ctypes.data_as(N.f32p), C.byref(n)))
         return rows[: n.value], sc[: n.value]
 
-    def score_batch(self, queries: Sequence[str], limit: int, return_info: bool = False, filter=None):
+    def score_batch(self, queries: Sequence[str], limit: int, return_info: bool = False, filter=None, filters=None):
         """`score(q, limit)` for every query text, through the batched BM25 kernels (rlr_lexical_score_batch) -> one
         (rows u64, scores f32) pair per query; with return_info also a dict: n_single (queries scored alone) and
         max_lexical (f32 per query, the blend's normalisation input).  filter (a RowFilter, as for score): every query
-        is `score(q, limit, filter)`, through the masked batched kernels (rlr_lexical_score_batch_filtered)"""
+        is `score(q, limit, filter)`, through the masked batched kernels (rlr_lexical_score_batch_filtered).
+        filters (one RowFilter PER QUERY, not together with filter; entries may repeat): query i is
+        `score(q_i, limit, filters[i])`, one grid row per query with its own mask (rlr_lexical_score_batch_scoped)"""
+        if filter is not None and filters is not None:
+            raise ValueError("score_batch: give `filter` or `filters`, not both")
         toks = [self._joined(tokenize(q)) for q in queries]
         nq = len(toks)
         offsets = np.zeros(nq + 1, dtype=np.uint64)
@@ -129,7 +133,13 @@ class LexicalIndex:
         n_single = C.c_uint32()
         tail = (nq, blob, offsets.ctypes.data_as(N.u64p), limit, rows.ctypes.data_as(N.u64p), sc.ctypes.data_as(N.f32p),
                 n.ctypes.data_as(N.u32p), mx.ctypes.data_as(N.f32p), C.byref(n_single))
-        if filter is not None:
+        if filters is not None:
+            filters = list(filters)
+            if len(filters) != nq:
+                raise ValueError(f"{nq} queries but {len(filters)} filters")
+            handles = (C.c_void_p * max(nq, 1))(*[f.handle for f in filters])
+            N.check(self._L.rlr_lexical_score_batch_scoped(self._h, handles, *tail))
+        elif filter is not None:
             N.check(self._L.rlr_lexical_score_batch_filtered(self._h, filter.handle, *tail))
         else:
             N.check(self._L.rlr_lexical_score_batch(self._h, *tail))
