@@ -83,6 +83,14 @@ int32_t rlr_lexical_info(rlr_lexical *lex, uint64_t *total_docs, uint64_t *total
 int32_t rlr_lexical_segments(rlr_lexical *lex, uint64_t *main_postings, uint64_t *appended_postings,
                              uint64_t *full_rebuilds, uint64_t *append_rebuilds, uint64_t *select_retries);
 
+/* Which form of the top-`limit` selection the single-query scoring calls took so far (no reference counterpart), one
+ * count per launched chain: `sorted` (at most RLR_LEXICAL_MAX_LIMIT postings behind the query: one sort), `sampled_4096` /
+ * `sampled_8192` (a threshold from a sample of that many keys, one filter pass, an exact finish), `exact` (the eight radix
+ * passes).  A query the sampled selection hands back counts twice: its sampled attempt, then its exact one.  The batched
+ * calls count only the queries they score alone.  Any output pointer may be null. */
+int32_t rlr_lexical_select_forms(rlr_lexical *lex, uint64_t *sorted, uint64_t *sampled_4096, uint64_t *sampled_8192,
+                                 uint64_t *exact);
+
 /* LexicalIndex::score (:2169-2225).  `query_tokens` like `tokens` above.  Writes at most
  * min(limit, RLR_LEXICAL_MAX_LIMIT) pairs, ordered (score desc, row asc); limit == 0 means
  * "no truncation" in the reference (:2220) and is served up to RLR_LEXICAL_MAX_LIMIT pairs.

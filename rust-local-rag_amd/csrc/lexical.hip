@@ -1090,6 +1090,8 @@ struct rlr_lexical {
     bool delta_dirty = false; // only rows >= main_rows changed since the last commit
     uint64_t main_rows = 0, main_postings = 0, delta_postings = 0, n_full_commits = 0, n_delta_commits = 0;
     std::atomic<uint64_t> n_select_retries{0}; // queries the sampled selection handed back to the exact path
+    // selection chains launched, by form (rlr_lexical_select_forms): sort, sampled with 4096 / 8192 keys, exact
+    std::atomic<uint64_t> n_form_sort{0}, n_form_sampled_4096{0}, n_form_sampled_8192{0}, n_form_exact{0};
     std::vector<uint32_t> main_df; // documents per term inside MAIN (terms born later: beyond its end, 0)
     // ---- device CSR
     std::vector<uint64_t> term_off, dterm_off; // MAIN / DELTA offsets by term
@@ -1560,6 +1562,17 @@ int32_t rlr_lexical_segments(rlr_lexical *lx, uint64_t *main_postings, uint64_t 
     return RLR_OK;
 }
 
+int32_t rlr_lexical_select_forms(rlr_lexical *lx, uint64_t *sorted, uint64_t *sampled_4096, uint64_t *sampled_8192, uint64_t *exact)
+{
+    if (!lx)
+        return set_error(RLR_E_INVALID, "lexical handle is null");
+    if (sorted) *sorted = lx->n_form_sort.load();
+    if (sampled_4096) *sampled_4096 = lx->n_form_sampled_4096.load();
+    if (sampled_8192) *sampled_8192 = lx->n_form_sampled_8192.load();
+    if (exact) *exact = lx->n_form_exact.load();
+    return RLR_OK;
+}
+
 // first_attempt = 1: skip the sampled selection (a fused search already saw it hand this query back)
 static int32_t lexical_score_from(rlr_lexical *lx, const char *query_tokens, size_t len, uint32_t limit, uint64_t *rows_out,
                                   float *scores_out, uint32_t *n_out, int first_attempt, const uint64_t *d_mask = nullptr,
@@ -1839,6 +1852,7 @@ static int32_t lexical_enqueue_masked(rlr_lexical *lx, const char *query_tokens,
     const uint64_t *d_result = ws->d_out.get();
     const uint32_t *d_result_n = d_out_n;
     if (upper <= kMaxLimit) {
+        lx->n_form_sort++;
         hipLaunchKernelGGL(lex_sort_kernel<true>, dim3(1), dim3(1024), 0, s, ws->d_scores.get(), ws->d_touched.get(), nullptr, ctl,
                            lim, ws->d_out.get(), d_out_n);
     } else if (!exact_passes && lim <= kFastLimitMax && sampled_candidates(lim, upper, kSampleMax) <= 6000.0) {
@@ -1846,6 +1860,7 @@ static int32_t lexical_enqueue_masked(rlr_lexical *lx, const char *query_tokens,
         // 4096 sample keys while that keeps the list short: half the gathers and LDS work of the sample launch for ~15 % more
         // candidates at 100 k touched documents
         const uint32_t sample_log2 = sampled_candidates(lim, upper, 4096) <= 4000.0 ? 12u : 13u;
+        (sample_log2 == 12u ? lx->n_form_sampled_4096 : lx->n_form_sampled_8192)++;
         // sampled threshold -> one filter pass -> exact finish among the ~1.5 lim candidates (3 launches); the count word
         // says kLexRetry when that list overflowed or came out short
         // RLR_LEX_SAMPLE_RANK (a test switch): the sample rank to use instead of mu + 4.5 sqrt(mu) + 8 -- 1 makes the
@@ -1863,6 +1878,7 @@ static int32_t lexical_enqueue_masked(rlr_lexical *lx, const char *query_tokens,
             hipLaunchKernelGGL(lex_final_kernel<false>, dim3(1), dim3(1024), 0, s, ws->d_sel.get(), ctl, lim, ws->d_out.get(), d_out_n, row_bits);
         out->may_retry = true;
     } else {
+        lx->n_form_exact++;
         LEX_TRY(dev_grow(ws->d_keys, upper));
         hipLaunchKernelGGL(lex_select_pass_kernel<true>, dim3(blocks_u), dim3(256), 0, s, ws->d_keys.get(), ctl, lim, 0,
                            ws->d_scores.get(), ws->d_touched.get());

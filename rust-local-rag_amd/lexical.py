@@ -91,6 +91,12 @@ class LexicalIndex:
         return dict(zip(("main_postings", "appended_postings", "full_rebuilds", "append_rebuilds", "select_retries"),
                         (x.value for x in v)))
 
+    def select_forms(self) -> dict:
+        """selection chains launched so far, by form (one per single-query scoring call; a retry adds one `exact`)"""
+        v = [C.c_uint64() for _ in range(4)]
+        N.check(self._L.rlr_lexical_select_forms(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("sort", "sampled_4096", "sampled_8192", "exact"), (x.value for x in v)))
+
     def score(self, query: str, limit: int, filter=None) -> Tuple[np.ndarray, np.ndarray]:
         """LexicalIndex::score :2169-2225 -> (rows u64, scores f32), (score desc, row asc).  filter (a RowFilter of the
         index whose rows these are): only its rows are candidates; the BM25 statistics stay those of the whole index"""

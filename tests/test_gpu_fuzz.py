@@ -428,7 +428,8 @@ def test_lexical_sampled_selection_retry_path():
     """RLR_LEX_SAMPLE_RANK=1 in a child process: the sampled BM25 selection takes the largest sample key as threshold, its
     candidate list comes out short, and every large query goes through the retry -- host API (rlr_lexical_score repeats
     the query on the exact radix path) and fused hybrid search (the blend hands the query back, status 3) alike.  Same
-    differential tests, same answers."""
+    differential tests, same answers -- and the designed postings of test_gpu_lexsel.py, whose form accounting holds every
+    sampled case that must come out short to one sampled and one exact launch."""
     import os
     import subprocess
 
@@ -438,6 +439,7 @@ def test_lexical_sampled_selection_retry_path():
             "print('lexical fuzz ok: %d' % F.fuzz_lexical(12, 77)); print('engine fuzz ok: %d' % F.fuzz_engine(6, 78)); "
             "import test_gpu_lexical as L, importlib, conftest; rlr = conftest.load_pkg(); from oracle import oracle as O; O.lib(); "
             "L.test_bm25_select_path_many_postings_and_ties(rlr); L.test_engine_search_text_fused_and_fallback_paths(rlr, O); L.test_engine_search_text_with_more_candidates_than_one_workgroup_sorts(rlr, O); "
+            "import test_gpu_lexsel as S; S.test_single_path_every_case(rlr); "
             "print('retry path ok')")
     out = subprocess.run([sys.executable, "-u", "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
