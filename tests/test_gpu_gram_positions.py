@@ -11,7 +11,9 @@ pool count its instance is chosen by.
 
 A side effect: a and b are winners, so in the plans that read every ordered pair (33, 37, 70, 100 and 130 slots) every
 candidate position (lane, register slot j) of mmr_greedy_lazy_kernel<1>, <2> and <5> wins somewhere; <5> and <8> also run at
-180 and 325 slots on the sampled blocks, mmr_greedy_kernel at 1030.  No shape here reaches <16> (pools above 512)."""
+180 and 325 slots on the sampled blocks, mmr_greedy_kernel at 1030.  No shape here reaches <16> (pools above 512), and the
+winners here are always alone at the maximum: every (lane, j) of every J, <16> included, as a lone winner and as the winner
+of a tie, and the chain's other branches, are test_gpu_greedy.py's (on the pools of tests/greedy_vectors.py)."""
 import numpy as np
 import pytest
 
