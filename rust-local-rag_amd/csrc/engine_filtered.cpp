@@ -66,6 +66,174 @@ int32_t filtered_backend(rlr_index *idx, const rlr_filter *f, FilteredBackend *b
     return st;
 }
 
+// The scopes of a batched text search: ONE filter for every query (f) or a filter per query (filters, f == nullptr).
+// The one-filter form is the per-query form with filters[q] == f; what differs is named here and at `look` below.
+struct TextScopes {
+    rlr_index *idx;
+    rlr_lexical *lex;
+    const rlr_filter *f;
+    const rlr_filter *const *filters;
+    std::vector<FilteredBackend> one; // the backend of f, or of every filters[q]
+    const rlr_filter *filter(uint32_t q) const { return f ? f : filters[q]; }
+    const FilteredBackend &be(uint32_t q) const { return one[f ? 0 : q]; }
+    // BM25 of queries q0 .. q0 + m - 1 inside their scopes: the MASKED or the SCOPED batched kernel
+    int32_t bm25(uint32_t q0, uint32_t m, const char *tokens, const uint64_t *offsets, uint32_t lcap, uint64_t *rows, float *scores,
+                 uint32_t *n) const
+    {
+        return f ? rlr_lexical_score_batch_filtered(lex, f, m, tokens, offsets + q0, lcap, rows, scores, n, nullptr, nullptr)
+                 : rlr_lexical_score_batch_scoped(lex, filters + q0, m, tokens, offsets + q0, lcap, rows, scores, n, nullptr, nullptr);
+    }
+    // their top-k in ONE call: query q gets min(k, |F_q|) rows back
+    int32_t topk(uint32_t q0, const float *queries, uint32_t m, uint32_t k, uint64_t *rows, float *cos, uint32_t *n) const
+    {
+        return f ? one[0].topk(queries, m, k, rows, cos, n)
+                 : rlr_search_topk_scoped(idx, filters + q0, queries, m, k, -1.0f, rows, cos, n);
+    }
+};
+
+// rlr_engine_search_text_filtered for many queries, query q inside sc.filter(q): per sub-batch ONE batched BM25, ONE top-k
+// call, ONE scoring of every query's lexical rows, the arithmetic of blend_search's w_embedding != 0 branch per query
+// (blend_fetched: the same union, combine, order and boundary rule) and ONE batched MMR over the decided, non-empty
+// pools with P = the largest need.  N, need, the pool size and the result count are per query; the BM25 limit depends
+// on top_k alone.  A query with an empty scope has no result, neither batched nor single (:476-478).
+int32_t text_batch_chain(const TextScopes &sc, const float *queries_raw, uint32_t dq, uint32_t n_queries, const char *tokens,
+                         const uint64_t *token_offsets, uint32_t top_k, float diversity_factor, int32_t stage,
+                         const rlr_query_weights *weights, rlr_search_hit *out, uint32_t cap, uint32_t *n_out,
+                         rlr_text_batch_info *info)
+{
+    if (n_queries == 0)
+        return RLR_OK;
+    // the sizes rlr_engine_search_text_filtered works with, per query where they depend on |F_q|
+    const TextSizes ts = text_sizes(top_k, diversity_factor);
+    const bool diversify = ts.diversify;
+    const uint32_t lcap = ts.lcap, dim = sc.be(0).dim;
+    rlr_resolved_weights w;
+    rlr_resolve_weights(weights, &w);
+    std::vector<uint64_t> need(n_queries, 0);
+    uint64_t max_need = 0, n_res_max = 0;
+    uint32_t n_live = 0; // queries with a non-empty scope (one filter: all or none)
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        const uint64_t N = sc.be(q).n_rows;
+        if (N == 0)
+            continue;
+        ++n_live;
+        need[q] = need_of(N, ts.k_seen, diversify ? 0 : stage);
+        max_need = std::max(max_need, need[q]);
+        n_res_max = std::max<uint64_t>(
+            n_res_max, rlr::result_k_cap(top_k, static_cast<uint32_t>(std::min<uint64_t>(need[q], 0xFFFFFFFFull)), diversify));
+    }
+    if (n_live == 0)
+        return RLR_OK;
+    if (!out || cap < n_res_max)
+        return RLR_E_INVALID; // (cap below the result count of a query)
+    int32_t st = RLR_OK;
+    auto single = [&](uint32_t q) {
+        return rlr_engine_search_text_filtered(sc.idx, sc.lex, sc.filter(q), queries_raw ? queries_raw + static_cast<size_t>(q) * dq : nullptr,
+                                               dq, tokens ? tokens + token_offsets[q] : nullptr,
+                                               static_cast<size_t>(token_offsets[q + 1] - token_offsets[q]), top_k, diversity_factor,
+                                               stage, weights, out + static_cast<size_t>(q) * cap, cap, &n_out[q]);
+    };
+    // the shapes the unscoped batch hands to the single entry point as well
+    if (w.embedding == 0.0f || !std::isfinite(w.embedding) || !std::isfinite(w.lexical) || max_need > 1024 || n_queries == 1) {
+        for (uint32_t q = 0; q < n_queries; ++q)
+            if ((st = single(q)) != RLR_OK)
+                return st;
+        if (info) {
+            info->n_single = n_queries;
+            info->n_single_shape = n_queries;
+        }
+        return RLR_OK;
+    }
+    const uint32_t P = static_cast<uint32_t>(max_need);
+    const uint32_t sub = std::min(text_sub_batch(P, diversify), n_queries);
+    std::vector<uint64_t> lrows(static_cast<size_t>(sub) * lcap), rows, lists, round1(sub);
+    std::vector<float> lscores(lrows.size()), qn(static_cast<size_t>(sub) * dim), cosv, lcos;
+    std::vector<uint32_t> n_lex(sub), got(sub), counts(sub), redo, live;
+    std::vector<LexPrep> lexp(sub);
+    std::vector<std::vector<Cand>> pools(sub);
+    std::vector<char> seen, undecided(sub);
+    for (uint32_t q0 = 0; q0 < n_queries; q0 += sub) {
+        const uint32_t m = std::min(sub, n_queries - q0);
+        bool any_row = false;
+        for (uint32_t q = 0; q < m; ++q)
+            any_row = any_row || need[q0 + q] != 0;
+        if (!any_row)
+            continue; // (every scope of this sub-batch is empty)
+        // 1. BM25 of every query inside its own filter
+        st = sc.bm25(q0, m, tokens, token_offsets, lcap, lrows.data(), lscores.data(), n_lex.data());
+        if (st != RLR_OK)
+            return st;
+        // 2. the queries and the lexical maps, as generic_search prepares them
+        if (dq)
+            prepare_queries(queries_raw + static_cast<size_t>(q0) * dq, dq, m, dim, qn.data());
+        else
+            std::fill(qn.begin(), qn.end(), 0.0f);
+        uint32_t max_lex = 0;
+        uint64_t max_fetch = 0;
+        for (uint32_t q = 0; q < m; ++q) {
+            const FilteredBackend &be = sc.be(q0 + q);
+            lexp[q] = prepare_lexical_in([&be](uint64_t row) { return be.holds(row); }, lrows.data() + static_cast<size_t>(q) * lcap,
+                                         lscores.data() + static_cast<size_t>(q) * lcap, n_lex[q]);
+            counts[q] = static_cast<uint32_t>(lexp[q].rows.size());
+            max_lex = std::max(max_lex, counts[q]);
+            round1[q] = std::min<uint64_t>(be.n_rows, need[q0 + q] + counts[q] + 8); // the single call's first fetch
+            max_fetch = std::max(max_fetch, round1[q]);
+        }
+        // 3. one top-k call with the largest fetch (one filter: min(N, need + the longest lexical list + 8))
+        const uint32_t fetch = static_cast<uint32_t>(max_fetch);
+        rows.assign(static_cast<size_t>(m) * fetch, 0);
+        cosv.assign(rows.size(), 0.0f);
+        st = sc.topk(q0, qn.data(), m, fetch, rows.data(), cosv.data(), got.data());
+        if (st != RLR_OK)
+            return st;
+        // 4. exact cosines of every query's lexical rows
+        lists.assign(static_cast<size_t>(m) * max_lex, 0);
+        lcos.assign(lists.size(), 0.0f);
+        for (uint32_t q = 0; q < m; ++q)
+            std::copy(lexp[q].rows.begin(), lexp[q].rows.end(), lists.begin() + static_cast<size_t>(q) * max_lex);
+        st = rlr::score_rows_batch(sc.idx, qn.data(), m, lists.data(), counts.data(), max_lex, lcos.data());
+        if (st != RLR_OK)
+            return st;
+        // 5. blend per query, with its own N and need.  One filter: a query looks at everything it got -- a wider fetch
+        // than the single call's changes nothing: where the boundary rule holds, the first `need` candidates are the
+        // first `need` of the whole universe, whichever fetch showed it.  A filter per query: at its own first-round
+        // fetch only, so its boundary rule decides as the single call's first round does.  (Which queries are handed
+        // back -- info->n_single_blend -- depends on this width; the results do not.)
+        live.clear();
+        for (uint32_t q = 0; q < m; ++q) {
+            const uint64_t N = sc.be(q0 + q).n_rows, nd = need[q0 + q];
+            pools[q].clear();
+            undecided[q] = 0;
+            if (N == 0)
+                continue;
+            const uint32_t look = sc.f ? got[q] : static_cast<uint32_t>(std::min<uint64_t>(got[q], round1[q]));
+            undecided[q] = !blend_fetched(w, lexp[q], lcos.data() + static_cast<size_t>(q) * max_lex, rows.data() + static_cast<size_t>(q) * fetch,
+                                          cosv.data() + static_cast<size_t>(q) * fetch, look, N, nd, seen, pools[q]);
+            if (undecided[q])
+                redo.push_back(q0 + q); // the single call widens its fetch
+            if (pools[q].size() > nd)
+                pools[q].resize(nd);
+            if (!undecided[q] && !pools[q].empty())
+                live.push_back(q);
+        }
+        // 6. one MMR over the decided, non-empty pools (generic_search_with_diversity per query)
+        if (diversify && (st = mmr_pools(sc.be(0), pools, live, P, top_k, ts.lambda)) != RLR_OK)
+            return st;
+        for (uint32_t q = 0; q < m; ++q)
+            if (!undecided[q])
+                emit(pools[q], out + static_cast<size_t>(q0 + q) * cap, cap, &n_out[q0 + q]);
+    }
+    for (uint32_t q : redo)
+        if ((st = single(q)) != RLR_OK)
+            return st;
+    if (info) {
+        info->n_single_blend = static_cast<uint32_t>(redo.size());
+        info->n_single = info->n_single_blend;
+        info->n_batched = n_live - info->n_single; // (one filter: n_live == n_queries)
+    }
+    return RLR_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -127,21 +295,14 @@ int32_t rlr_engine_search_text_filtered(rlr_index *idx, rlr_lexical *lex, const 
     if (!idx || !lex || !f || !n_out || (!query_raw && dq) || (tokens_len && !query_tokens))
         return RLR_E_INVALID;
     *n_out = 0;
-    float lambda = diversity_factor;
-    if (lambda < 0.0f) lambda = 0.0f;
-    if (lambda > 1.0f) lambda = 1.0f;
-    const bool diversify = !(lambda == 0.0f);
-    // the sizes rlr_engine_search_text works with: `search` sees top_k (or the pool) and asks BM25 for five times that (:505)
-    const uint32_t k_seen = std::max<uint32_t>(diversify ? pool_size_of(top_k) : top_k, 1u);
-    const uint32_t limit = static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(k_seen) * 5, 0xFFFFFFFFull));
-    const uint32_t lcap = std::min<uint32_t>(limit, RLR_LEXICAL_MAX_LIMIT);
-    std::vector<uint64_t> lrows(lcap);
-    std::vector<float> lscores(lcap);
+    const TextSizes ts = text_sizes(top_k, diversity_factor); // the sizes rlr_engine_search_text works with
+    std::vector<uint64_t> lrows(ts.lcap);
+    std::vector<float> lscores(ts.lcap);
     uint32_t n_lex = 0;
-    const int32_t st = rlr_lexical_score_filtered(lex, f, query_tokens, tokens_len, limit, lrows.data(), lscores.data(), &n_lex);
+    const int32_t st = rlr_lexical_score_filtered(lex, f, query_tokens, tokens_len, ts.limit, lrows.data(), lscores.data(), &n_lex);
     if (st != RLR_OK)
         return st;
-    return diversify ? rlr_engine_search_with_diversity_filtered(idx, f, query_raw, dq, top_k, diversity_factor, weights,
+    return ts.diversify ? rlr_engine_search_with_diversity_filtered(idx, f, query_raw, dq, top_k, diversity_factor, weights,
                                                                  lrows.data(), lscores.data(), n_lex, out, cap, n_out)
                      : rlr_engine_search_filtered(idx, f, query_raw, dq, top_k, weights, lrows.data(), lscores.data(), n_lex,
                                                   stage, out, cap, n_out);
@@ -205,11 +366,7 @@ int32_t rlr_engine_search_with_diversity_batch_scoped(rlr_index *idx, const rlr_
         rlr_index *idx;
         const rlr_filter *const *filters;
         std::vector<FilteredBackend> one;
-        const float *queries_raw;
-        uint32_t dq, top_k, dim = 0;
-        float lambda;
-        const rlr_resolved_weights *w;
-        uint64_t universe(uint32_t q) const { return one[q].n_rows; }
+        uint32_t dim = 0;
         int32_t topk(const float *queries, uint32_t nq, uint32_t k, uint64_t *rows, float *cos, uint32_t *n) const
         {
             return rlr_search_topk_scoped(idx, filters, queries, nq, k, -1.0f, rows, cos, n);
@@ -219,19 +376,19 @@ int32_t rlr_engine_search_with_diversity_batch_scoped(rlr_index *idx, const rlr_
         {
             return one[0].mmr(pool_rows, pool_scores, pool_sizes, nq, P, k, lam, order, n_sel);
         }
-        int32_t single(uint32_t q, std::vector<Cand> &res) const
-        {
-            return generic_search_with_diversity(one[q], queries_raw + static_cast<size_t>(q) * dq, dq, top_k, lambda, *w, nullptr,
-                                                 nullptr, 0, res);
-        }
-    } be{idx, filters, {}, queries_raw, dq, top_k, 0, diversity_factor, &w};
-    be.one.resize(n_queries);
+    } be{idx, filters, std::vector<FilteredBackend>(n_queries)};
     for (uint32_t q = 0; q < n_queries; ++q)
         if ((st = filtered_backend(idx, filters[q], &be.one[q])) != RLR_OK)
             return st;
     be.dim = be.one[0].dim;
     std::vector<std::vector<Cand>> results;
-    st = generic_search_with_diversity_batch_scoped(be, queries_raw, dq, n_queries, top_k, diversity_factor, w, results);
+    st = generic_search_with_diversity_universes(
+        be, [&](uint32_t q) { return be.one[q].n_rows; },
+        [&](uint32_t q, std::vector<Cand> &res) {
+            return generic_search_with_diversity(be.one[q], queries_raw + static_cast<size_t>(q) * dq, dq, top_k, diversity_factor, w,
+                                                 nullptr, nullptr, 0, res);
+        },
+        queries_raw, dq, n_queries, top_k, diversity_factor, w, results);
     if (st != RLR_OK)
         return st;
     for (uint32_t q = 0; q < n_queries; ++q)
@@ -239,11 +396,6 @@ int32_t rlr_engine_search_with_diversity_batch_scoped(rlr_index *idx, const rlr_
     return RLR_OK;
 }
 
-// rlr_engine_search_text_filtered for many queries: per sub-batch ONE masked batched BM25, ONE rlr_search_topk_filtered call,
-// ONE scoring of every query's lexical rows, the arithmetic of blend_search's w_embedding != 0 branch per query
-// (blend_fetched: the same union, combine, order and boundary rule) and ONE batched MMR.  A wider fetch than the single
-// call's changes nothing: where the boundary rule holds, the first `need` candidates are the first `need` of the whole
-// universe, whichever fetch showed it.
 int32_t rlr_engine_search_text_batch_filtered(rlr_index *idx, rlr_lexical *lex, const rlr_filter *f, const float *queries_raw,
                                               uint32_t dq, uint32_t n_queries, const char *tokens, const uint64_t *token_offsets,
                                               uint32_t top_k, float diversity_factor, int32_t stage,
@@ -252,151 +404,18 @@ int32_t rlr_engine_search_text_batch_filtered(rlr_index *idx, rlr_lexical *lex, 
 {
     if (info)
         *info = rlr_text_batch_info{};
-    if (!idx || !lex || !f || (n_queries && (!n_out || !token_offsets || (dq && !queries_raw))))
+    if (!idx || !lex || !f || !text_batch_args(queries_raw, dq, n_queries, tokens, token_offsets, n_out))
         return RLR_E_INVALID;
-    for (uint32_t q = 0; q < n_queries; ++q) {
-        if (token_offsets[q + 1] < token_offsets[q])
-            return RLR_E_INVALID;
-    }
-    if (n_queries && token_offsets[n_queries] > token_offsets[0] && !tokens)
-        return RLR_E_INVALID;
-    for (uint32_t q = 0; q < n_queries; ++q)
-        n_out[q] = 0;
     int32_t st = rlr::filter_check(idx, f); // a stale filter, or one of another index: before any GPU work
     if (st != RLR_OK)
         return st;
-    FilteredBackend be;
-    st = filtered_backend(idx, f, &be);
-    if (st != RLR_OK)
+    TextScopes sc{idx, lex, f, nullptr, std::vector<FilteredBackend>(1)};
+    if ((st = filtered_backend(idx, f, &sc.one[0])) != RLR_OK)
         return st;
-    const uint64_t N = be.n_rows;
-    if (n_queries == 0 || N == 0) // :476-478
-        return RLR_OK;
-    // the sizes rlr_engine_search_text_filtered works with
-    float lambda = diversity_factor;
-    if (lambda < 0.0f) lambda = 0.0f;
-    if (lambda > 1.0f) lambda = 1.0f;
-    const bool diversify = !(lambda == 0.0f);
-    rlr_resolved_weights w;
-    rlr_resolve_weights(weights, &w);
-    const uint32_t k_seen = std::max<uint32_t>(diversify ? pool_size_of(top_k) : top_k, 1u);
-    const uint32_t limit = static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(k_seen) * 5, 0xFFFFFFFFull));
-    const uint32_t lcap = std::min<uint32_t>(limit, RLR_LEXICAL_MAX_LIMIT);
-    const uint64_t need = need_of(N, diversify ? pool_size_of(top_k) : top_k, diversify ? 0 : stage);
-    const uint64_t n_res = rlr::result_k_cap(top_k, static_cast<uint32_t>(std::min<uint64_t>(need, 0xFFFFFFFFull)), diversify);
-    if (!out || cap < n_res)
-        return RLR_E_INVALID; // (cap below the result count of a query)
-    auto single = [&](uint32_t q) {
-        return rlr_engine_search_text_filtered(idx, lex, f, queries_raw ? queries_raw + static_cast<size_t>(q) * dq : nullptr, dq,
-                                               tokens ? tokens + token_offsets[q] : nullptr,
-                                               static_cast<size_t>(token_offsets[q + 1] - token_offsets[q]), top_k, diversity_factor,
-                                               stage, weights, out + static_cast<size_t>(q) * cap, cap, &n_out[q]);
-    };
-    // the shapes the unscoped batch hands to the single entry point as well
-    if (w.embedding == 0.0f || !std::isfinite(w.embedding) || !std::isfinite(w.lexical) || need > 1024 || n_queries == 1) {
-        for (uint32_t q = 0; q < n_queries; ++q)
-            if ((st = single(q)) != RLR_OK)
-                return st;
-        if (info) {
-            info->n_single = n_queries;
-            info->n_single_shape = n_queries;
-        }
-        return RLR_OK;
-    }
-    const uint32_t nd = static_cast<uint32_t>(need);
-    const uint32_t sub = std::min(text_sub_batch(nd, diversify), n_queries);
-    std::vector<uint64_t> lrows(static_cast<size_t>(sub) * lcap), rows, lists, prow;
-    std::vector<float> lscores(lrows.size()), qn(static_cast<size_t>(sub) * be.dim), cosv, lcos, psc;
-    std::vector<uint32_t> n_lex(sub), got(sub), counts(sub), psz(sub), order, nsel(sub), redo;
-    std::vector<LexPrep> lexp(sub);
-    std::vector<std::vector<Cand>> pools(sub);
-    std::vector<char> seen, undecided(sub);
-    for (uint32_t q0 = 0; q0 < n_queries; q0 += sub) {
-        const uint32_t m = std::min(sub, n_queries - q0);
-        // 1. BM25 of every query inside the filter
-        st = rlr_lexical_score_batch_filtered(lex, f, m, tokens, token_offsets + q0, lcap, lrows.data(), lscores.data(), n_lex.data(),
-                                              nullptr, nullptr);
-        if (st != RLR_OK)
-            return st;
-        // 2. the queries and the lexical maps, as generic_search prepares them
-        if (dq)
-            prepare_queries(queries_raw + static_cast<size_t>(q0) * dq, dq, m, be.dim, qn.data());
-        else
-            std::fill(qn.begin(), qn.end(), 0.0f);
-        uint32_t max_lex = 0;
-        for (uint32_t q = 0; q < m; ++q) {
-            lexp[q] = prepare_lexical_in([&be](uint64_t row) { return be.holds(row); }, lrows.data() + static_cast<size_t>(q) * lcap,
-                                         lscores.data() + static_cast<size_t>(q) * lcap, n_lex[q]);
-            counts[q] = static_cast<uint32_t>(lexp[q].rows.size());
-            max_lex = std::max(max_lex, counts[q]);
-        }
-        // 3. one top-k call: every query fetches what the query with the longest lexical list needs
-        const uint32_t fetch = static_cast<uint32_t>(std::min<uint64_t>(N, need + max_lex + 8));
-        rows.assign(static_cast<size_t>(m) * fetch, 0);
-        cosv.assign(rows.size(), 0.0f);
-        st = be.topk(qn.data(), m, fetch, rows.data(), cosv.data(), got.data());
-        if (st != RLR_OK)
-            return st;
-        // 4. exact cosines of every query's lexical rows
-        lists.assign(static_cast<size_t>(m) * max_lex, 0);
-        lcos.assign(lists.size(), 0.0f);
-        for (uint32_t q = 0; q < m; ++q)
-            std::copy(lexp[q].rows.begin(), lexp[q].rows.end(), lists.begin() + static_cast<size_t>(q) * max_lex);
-        st = rlr::score_rows_batch(idx, qn.data(), m, lists.data(), counts.data(), max_lex, lcos.data());
-        if (st != RLR_OK)
-            return st;
-        // 5. blend per query
-        for (uint32_t q = 0; q < m; ++q) {
-            undecided[q] = !blend_fetched(w, lexp[q], lcos.data() + static_cast<size_t>(q) * max_lex, rows.data() + static_cast<size_t>(q) * fetch,
-                                          cosv.data() + static_cast<size_t>(q) * fetch, got[q], N, need, seen, pools[q]);
-            if (undecided[q])
-                redo.push_back(q0 + q); // the single call widens its fetch
-            if (pools[q].size() > need)
-                pools[q].resize(need);
-        }
-        // 6. one MMR over the pools (generic_search_with_diversity per query)
-        if (diversify) {
-            prow.assign(static_cast<size_t>(m) * nd, 0);
-            psc.assign(prow.size(), 0.0f);
-            order.assign(prow.size(), 0);
-            for (uint32_t q = 0; q < m; ++q) {
-                psz[q] = static_cast<uint32_t>(pools[q].size()); // (an undecided query's as well: overwritten below)
-                for (uint32_t i = 0; i < psz[q]; ++i) {
-                    prow[static_cast<size_t>(q) * nd + i] = pools[q][i].row;
-                    psc[static_cast<size_t>(q) * nd + i] = pools[q][i].c;
-                }
-            }
-            st = be.mmr(prow.data(), psc.data(), psz.data(), m, nd, top_k, lambda, order.data(), nsel.data());
-            if (st != RLR_OK)
-                return st;
-            std::vector<Cand> picked;
-            for (uint32_t q = 0; q < m; ++q) {
-                picked.clear();
-                for (uint32_t i = 0; i < nsel[q]; ++i)
-                    picked.push_back(pools[q][order[static_cast<size_t>(q) * nd + i]]);
-                pools[q].swap(picked);
-            }
-        }
-        for (uint32_t q = 0; q < m; ++q)
-            if (!undecided[q])
-                emit(pools[q], out + static_cast<size_t>(q0 + q) * cap, cap, &n_out[q0 + q]);
-    }
-    for (uint32_t q : redo)
-        if ((st = single(q)) != RLR_OK)
-            return st;
-    if (info) {
-        info->n_single_blend = static_cast<uint32_t>(redo.size());
-        info->n_single = info->n_single_blend;
-        info->n_batched = n_queries - info->n_single;
-    }
-    return RLR_OK;
+    return text_batch_chain(sc, queries_raw, dq, n_queries, tokens, token_offsets, top_k, diversity_factor, stage, weights, out, cap,
+                            n_out, info);
 }
 
-// rlr_engine_search_text_filtered for many queries with a filter EACH: the chain of rlr_engine_search_text_batch_filtered
-// with the candidate universe of query q = filters[q].  N, need, the pool size and the result count are per query; the
-// BM25 limit depends on top_k alone.  ONE rlr_search_topk_scoped call fetches the largest min(|F_q|, need_q + lexical
-// count + 8) of the sub-batch and query q looks at its own first rows only -- the fetch of the single call's first
-// round, so its boundary rule decides the same way.  The MMR runs over the non-empty pools with P = the largest need.
 int32_t rlr_engine_search_text_batch_scoped(rlr_index *idx, rlr_lexical *lex, const rlr_filter *const *filters,
                                             const float *queries_raw, uint32_t dq, uint32_t n_queries, const char *tokens,
                                             const uint64_t *token_offsets, uint32_t top_k, float diversity_factor, int32_t stage,
@@ -405,180 +424,18 @@ int32_t rlr_engine_search_text_batch_scoped(rlr_index *idx, rlr_lexical *lex, co
 {
     if (info)
         *info = rlr_text_batch_info{};
-    if (!idx || !lex || !filters || (n_queries && (!n_out || !token_offsets || (dq && !queries_raw))))
+    if (!idx || !lex || !filters || !text_batch_args(queries_raw, dq, n_queries, tokens, token_offsets, n_out))
         return RLR_E_INVALID;
-    for (uint32_t q = 0; q < n_queries; ++q) {
-        if (token_offsets[q + 1] < token_offsets[q])
-            return RLR_E_INVALID;
-    }
-    if (n_queries && token_offsets[n_queries] > token_offsets[0] && !tokens)
-        return RLR_E_INVALID;
-    for (uint32_t q = 0; q < n_queries; ++q)
-        n_out[q] = 0;
     int32_t st = RLR_OK;
     for (uint32_t q = 0; q < n_queries; ++q) // a null or stale entry, or one of another index: before any GPU work
         if ((st = rlr::filter_check(idx, filters[q])) != RLR_OK)
             return st;
-    if (n_queries == 0)
-        return RLR_OK;
-    std::vector<FilteredBackend> one(n_queries);
+    TextScopes sc{idx, lex, nullptr, filters, std::vector<FilteredBackend>(n_queries)};
     for (uint32_t q = 0; q < n_queries; ++q)
-        if ((st = filtered_backend(idx, filters[q], &one[q])) != RLR_OK)
+        if ((st = filtered_backend(idx, filters[q], &sc.one[q])) != RLR_OK)
             return st;
-    const uint32_t dim = one[0].dim;
-    // the sizes rlr_engine_search_text_filtered works with, per query where they depend on |F_q|
-    float lambda = diversity_factor;
-    if (lambda < 0.0f) lambda = 0.0f;
-    if (lambda > 1.0f) lambda = 1.0f;
-    const bool diversify = !(lambda == 0.0f);
-    rlr_resolved_weights w;
-    rlr_resolve_weights(weights, &w);
-    const uint32_t k_seen = std::max<uint32_t>(diversify ? pool_size_of(top_k) : top_k, 1u);
-    const uint32_t limit = static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(k_seen) * 5, 0xFFFFFFFFull));
-    const uint32_t lcap = std::min<uint32_t>(limit, RLR_LEXICAL_MAX_LIMIT);
-    std::vector<uint64_t> need(n_queries);
-    uint64_t max_need = 0, n_res_max = 0;
-    uint32_t n_live = 0;
-    for (uint32_t q = 0; q < n_queries; ++q) {
-        const uint64_t N = one[q].n_rows;
-        need[q] = N ? need_of(N, diversify ? pool_size_of(top_k) : top_k, diversify ? 0 : stage) : 0;
-        if (N == 0) // :476-478
-            continue;
-        ++n_live;
-        max_need = std::max(max_need, need[q]);
-        n_res_max = std::max<uint64_t>(
-            n_res_max, rlr::result_k_cap(top_k, static_cast<uint32_t>(std::min<uint64_t>(need[q], 0xFFFFFFFFull)), diversify));
-    }
-    if (n_live == 0)
-        return RLR_OK;
-    if (!out || cap < n_res_max)
-        return RLR_E_INVALID; // (cap below the result count of a query)
-    auto single = [&](uint32_t q) {
-        return rlr_engine_search_text_filtered(idx, lex, filters[q], queries_raw ? queries_raw + static_cast<size_t>(q) * dq : nullptr,
-                                               dq, tokens ? tokens + token_offsets[q] : nullptr,
-                                               static_cast<size_t>(token_offsets[q + 1] - token_offsets[q]), top_k, diversity_factor,
-                                               stage, weights, out + static_cast<size_t>(q) * cap, cap, &n_out[q]);
-    };
-    // the shapes the one-filter batch hands to the single entry point as well
-    if (w.embedding == 0.0f || !std::isfinite(w.embedding) || !std::isfinite(w.lexical) || max_need > 1024 || n_queries == 1) {
-        for (uint32_t q = 0; q < n_queries; ++q)
-            if ((st = single(q)) != RLR_OK)
-                return st;
-        if (info) {
-            info->n_single = n_queries;
-            info->n_single_shape = n_queries;
-        }
-        return RLR_OK;
-    }
-    const uint32_t P = static_cast<uint32_t>(max_need);
-    const uint32_t sub = std::min(text_sub_batch(P, diversify), n_queries);
-    std::vector<uint64_t> lrows(static_cast<size_t>(sub) * lcap), rows, lists, prow;
-    std::vector<float> lscores(lrows.size()), qn(static_cast<size_t>(sub) * dim), cosv, lcos, psc;
-    std::vector<uint32_t> n_lex(sub), got(sub), counts(sub), psz, order, nsel, redo, live;
-    std::vector<LexPrep> lexp(sub);
-    std::vector<std::vector<Cand>> pools(sub);
-    std::vector<char> seen, undecided(sub);
-    for (uint32_t q0 = 0; q0 < n_queries; q0 += sub) {
-        const uint32_t m = std::min(sub, n_queries - q0);
-        bool any_row = false;
-        for (uint32_t q = 0; q < m; ++q)
-            any_row = any_row || one[q0 + q].n_rows != 0;
-        if (!any_row)
-            continue; // (every scope of this sub-batch is empty)
-        // 1. BM25 of every query inside its own filter
-        st = rlr_lexical_score_batch_scoped(lex, filters + q0, m, tokens, token_offsets + q0, lcap, lrows.data(), lscores.data(),
-                                            n_lex.data(), nullptr, nullptr);
-        if (st != RLR_OK)
-            return st;
-        // 2. the queries and the lexical maps, as generic_search prepares them
-        if (dq)
-            prepare_queries(queries_raw + static_cast<size_t>(q0) * dq, dq, m, dim, qn.data());
-        else
-            std::fill(qn.begin(), qn.end(), 0.0f);
-        uint32_t max_lex = 0;
-        uint64_t max_fetch = 0;
-        for (uint32_t q = 0; q < m; ++q) {
-            const FilteredBackend &be = one[q0 + q];
-            lexp[q] = prepare_lexical_in([&be](uint64_t row) { return be.holds(row); }, lrows.data() + static_cast<size_t>(q) * lcap,
-                                         lscores.data() + static_cast<size_t>(q) * lcap, n_lex[q]);
-            counts[q] = static_cast<uint32_t>(lexp[q].rows.size());
-            max_lex = std::max(max_lex, counts[q]);
-            max_fetch = std::max(max_fetch, std::min<uint64_t>(be.n_rows, need[q0 + q] + counts[q] + 8));
-        }
-        // 3. one top-k call with the largest fetch: query q gets min(fetch, |F_q|) rows back and looks at its own first ones
-        const uint32_t fetch = static_cast<uint32_t>(max_fetch);
-        rows.assign(static_cast<size_t>(m) * fetch, 0);
-        cosv.assign(rows.size(), 0.0f);
-        st = rlr_search_topk_scoped(idx, filters + q0, qn.data(), m, fetch, -1.0f, rows.data(), cosv.data(), got.data());
-        if (st != RLR_OK)
-            return st;
-        // 4. exact cosines of every query's lexical rows
-        lists.assign(static_cast<size_t>(m) * max_lex, 0);
-        lcos.assign(lists.size(), 0.0f);
-        for (uint32_t q = 0; q < m; ++q)
-            std::copy(lexp[q].rows.begin(), lexp[q].rows.end(), lists.begin() + static_cast<size_t>(q) * max_lex);
-        st = rlr::score_rows_batch(idx, qn.data(), m, lists.data(), counts.data(), max_lex, lcos.data());
-        if (st != RLR_OK)
-            return st;
-        // 5. blend per query, with its own N and need
-        live.clear();
-        for (uint32_t q = 0; q < m; ++q) {
-            const uint64_t N = one[q0 + q].n_rows, nd = need[q0 + q];
-            pools[q].clear();
-            undecided[q] = 0;
-            if (N == 0)
-                continue; // (an empty scope: no result, neither batched nor single)
-            const uint32_t look = static_cast<uint32_t>(std::min<uint64_t>(got[q], std::min<uint64_t>(N, nd + counts[q] + 8)));
-            undecided[q] = !blend_fetched(w, lexp[q], lcos.data() + static_cast<size_t>(q) * max_lex, rows.data() + static_cast<size_t>(q) * fetch,
-                                          cosv.data() + static_cast<size_t>(q) * fetch, look, N, nd, seen, pools[q]);
-            if (undecided[q])
-                redo.push_back(q0 + q); // the single call widens its fetch
-            if (pools[q].size() > nd)
-                pools[q].resize(nd);
-            if (!undecided[q] && !pools[q].empty())
-                live.push_back(q);
-        }
-        // 6. one MMR over the decided, non-empty pools (generic_search_with_diversity per query)
-        if (diversify && !live.empty()) {
-            const uint32_t nl = static_cast<uint32_t>(live.size());
-            prow.assign(static_cast<size_t>(nl) * P, 0);
-            psc.assign(prow.size(), 0.0f);
-            order.assign(prow.size(), 0);
-            psz.assign(nl, 0);
-            nsel.assign(nl, 0);
-            for (uint32_t j = 0; j < nl; ++j) {
-                const std::vector<Cand> &c = pools[live[j]];
-                psz[j] = static_cast<uint32_t>(c.size());
-                for (uint32_t i = 0; i < psz[j]; ++i) {
-                    prow[static_cast<size_t>(j) * P + i] = c[i].row;
-                    psc[static_cast<size_t>(j) * P + i] = c[i].c;
-                }
-            }
-            st = one[0].mmr(prow.data(), psc.data(), psz.data(), nl, P, top_k, lambda, order.data(), nsel.data());
-            if (st != RLR_OK)
-                return st;
-            std::vector<Cand> picked;
-            for (uint32_t j = 0; j < nl; ++j) {
-                const uint32_t q = live[j];
-                picked.clear();
-                for (uint32_t i = 0; i < nsel[j]; ++i)
-                    picked.push_back(pools[q][order[static_cast<size_t>(j) * P + i]]);
-                pools[q].swap(picked);
-            }
-        }
-        for (uint32_t q = 0; q < m; ++q)
-            if (!undecided[q])
-                emit(pools[q], out + static_cast<size_t>(q0 + q) * cap, cap, &n_out[q0 + q]);
-    }
-    for (uint32_t q : redo)
-        if ((st = single(q)) != RLR_OK)
-            return st;
-    if (info) {
-        info->n_single_blend = static_cast<uint32_t>(redo.size());
-        info->n_single = info->n_single_blend;
-        info->n_batched = n_live - info->n_single;
-    }
-    return RLR_OK;
+    return text_batch_chain(sc, queries_raw, dq, n_queries, tokens, token_offsets, top_k, diversity_factor, stage, weights, out, cap,
+                            n_out, info);
 }
 
 } // extern "C"

@@ -20,6 +20,7 @@
 #pragma once
 
 #include "../../include/rlr_engine.h"
+#include "../../include/rlr_lexical.h"
 
 #include <algorithm>
 #include <cmath>
@@ -291,6 +292,41 @@ inline uint64_t need_of(uint64_t N, uint32_t top_k, int32_t stage)
     return stage ? initial_k : std::min<uint64_t>(initial_k, top_k);
 }
 
+// The sizes a text search works with: the clamped diversity factor (f32::clamp(0.0, 1.0), :725; NaN takes the MMR
+// branch), what `search` sees as top_k -- top_k or the pool, 0 as 1 -- and the five times that it asks BM25 for (:505).
+struct TextSizes {
+    float lambda;
+    bool diversify;
+    uint32_t k_seen, limit, lcap; // lcap: the pairs a BM25 call returns at the most
+};
+inline TextSizes text_sizes(uint32_t top_k, float diversity_factor)
+{
+    TextSizes t;
+    t.lambda = diversity_factor < 0.0f ? 0.0f : diversity_factor > 1.0f ? 1.0f : diversity_factor;
+    t.diversify = !(t.lambda == 0.0f);
+    t.k_seen = std::max<uint32_t>(t.diversify ? pool_size_of(top_k) : top_k, 1u);
+    t.limit = static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(t.k_seen) * 5, 0xFFFFFFFFull));
+    t.lcap = std::min<uint32_t>(t.limit, RLR_LEXICAL_MAX_LIMIT);
+    return t;
+}
+
+// What every batched text entry point asks of its arguments -- n_out, the token offsets (ascending) and, where there is
+// anything to read, the queries and the tokens -- and n_out zeroed.  false: RLR_E_INVALID.
+inline bool text_batch_args(const float *queries_raw, uint32_t dq, uint32_t n_queries, const char *tokens,
+                            const uint64_t *token_offsets, uint32_t *n_out)
+{
+    if (n_queries && (!n_out || !token_offsets || (dq && !queries_raw)))
+        return false;
+    for (uint32_t q = 0; q < n_queries; ++q)
+        if (token_offsets[q + 1] < token_offsets[q])
+            return false;
+    if (n_queries && token_offsets[n_queries] > token_offsets[0] && !tokens)
+        return false;
+    for (uint32_t q = 0; q < n_queries; ++q)
+        n_out[q] = 0;
+    return true;
+}
+
 // RagEngine::search on a backend without fused kernels.
 template <typename B>
 int32_t generic_search(const B &be, const float *query_raw, uint32_t dq, uint32_t top_k, const rlr_resolved_weights &w,
@@ -335,102 +371,53 @@ int32_t generic_search_with_diversity(const B &be, const float *query_raw, uint3
     return RLR_OK;
 }
 
-// The additive batched entry point (loop of search_with_diversity over the batch, no lexical candidates): one batched
-// top-k, per-query pools on the host, one batched MMR; queries whose fetch cannot decide the pool order (rounding ties
-// at its boundary) take the single-query path.  results[q] = that query's hits.
+// mmr_diversify (:767-839) over the pools that `live` names, in ONE be.mmr call: the pools strided by P (at least the
+// longest pool), each replaced by its picks in pick order.  A pool that `live` does not name is left as it is.
 template <typename B>
-int32_t generic_search_with_diversity_batch(const B &be, const float *queries_raw, uint32_t dq, uint32_t n_queries,
-                                            uint32_t top_k, float lambda, const rlr_resolved_weights &w,
-                                            std::vector<std::vector<Cand>> &results)
+int32_t mmr_pools(const B &be, std::vector<std::vector<Cand>> &pools, const std::vector<uint32_t> &live, uint32_t P,
+                  uint32_t top_k, float lambda)
 {
-    results.assign(n_queries, {});
-    const uint64_t N = be.n_rows;
-    if (n_queries == 0 || N == 0)
+    const uint32_t nl = static_cast<uint32_t>(live.size());
+    if (nl == 0)
         return RLR_OK;
-    const bool plain = lambda == 0.0f;
-    const uint32_t k_eff = std::max<uint32_t>(plain ? top_k : pool_size_of(top_k), 1u); // search() treats 0 as 1 (:490)
-    const uint64_t need = std::min<uint64_t>(N, k_eff);
-    int32_t st = RLR_OK;
-    auto single = [&](uint32_t q) -> int32_t { // reference path for one query of the batch
-        return generic_search_with_diversity(be, queries_raw + static_cast<size_t>(q) * dq, dq, top_k, lambda, w, nullptr, nullptr,
-                                             0, results[q]);
-    };
-    if (w.embedding == 0.0f || need > 1024) { // degenerate weight / pool beyond the batched MMR: loop
-        for (uint32_t q = 0; q < n_queries; ++q)
-            if ((st = single(q)) != RLR_OK)
-                return st;
-        return RLR_OK;
+    std::vector<uint64_t> prow(static_cast<size_t>(nl) * P, 0);
+    std::vector<float> psc(prow.size(), 0.0f);
+    std::vector<uint32_t> psz(nl), order(prow.size()), nsel(nl);
+    for (uint32_t j = 0; j < nl; ++j) {
+        const std::vector<Cand> &c = pools[live[j]];
+        psz[j] = static_cast<uint32_t>(c.size());
+        for (uint32_t i = 0; i < psz[j]; ++i) {
+            prow[static_cast<size_t>(j) * P + i] = c[i].row;
+            psc[static_cast<size_t>(j) * P + i] = c[i].c;
+        }
     }
-    std::vector<float> qn(static_cast<size_t>(n_queries) * be.dim);
-    prepare_queries(queries_raw, dq, n_queries, be.dim, qn.data());
-    const uint32_t fetch = static_cast<uint32_t>(std::min<uint64_t>(N, need + 8));
-    std::vector<uint64_t> rows(static_cast<size_t>(n_queries) * fetch);
-    std::vector<float> cosv(static_cast<size_t>(n_queries) * fetch);
-    std::vector<uint32_t> got(n_queries);
-    st = be.topk(qn.data(), n_queries, fetch, rows.data(), cosv.data(), got.data());
+    const int32_t st = be.mmr(prow.data(), psc.data(), psz.data(), nl, P, top_k, lambda, order.data(), nsel.data());
     if (st != RLR_OK)
         return st;
-    const uint32_t P = static_cast<uint32_t>(need);
-    std::vector<std::vector<Cand>> pools(n_queries);
-    std::vector<uint32_t> redo;
-    for (uint32_t q = 0; q < n_queries; ++q) {
-        std::vector<Cand> &c = pools[q];
-        c.reserve(got[q]);
-        for (uint32_t i = 0; i < got[q]; ++i) {
-            const float e = cosv[static_cast<size_t>(q) * fetch + i];
-            c.push_back({rows[static_cast<size_t>(q) * fetch + i], combine(w, e, 0.0f), e, 0.0f});
-        }
-        std::sort(c.begin(), c.end(), cand_before);
-        // same boundary rule as blend_search: a rounding tie that reaches the last fetched row
-        // cannot be resolved from this fetch -> that query takes the single-query path
-        if (got[q] < N && got[q] > 0) {
-            const float c_tail = combine(w, cosv[static_cast<size_t>(q) * fetch + got[q] - 1], 0.0f);
-            if (!(c.size() >= need && (std::isnan(c_tail) || c[need - 1].c > c_tail)))
-                redo.push_back(q);
-        }
-        if (c.size() > need)
-            c.resize(need);
+    std::vector<Cand> picked;
+    for (uint32_t j = 0; j < nl; ++j) {
+        std::vector<Cand> &c = pools[live[j]];
+        picked.clear();
+        for (uint32_t i = 0; i < nsel[j]; ++i)
+            picked.push_back(c[order[static_cast<size_t>(j) * P + i]]);
+        c.swap(picked);
     }
-    if (plain) {
-        for (uint32_t q = 0; q < n_queries; ++q)
-            results[q] = pools[q];
-    } else {
-        std::vector<uint64_t> prow(static_cast<size_t>(n_queries) * P, 0);
-        std::vector<float> psc(static_cast<size_t>(n_queries) * P, 0.0f);
-        std::vector<uint32_t> psz(n_queries), order(static_cast<size_t>(n_queries) * P), nsel(n_queries);
-        for (uint32_t q = 0; q < n_queries; ++q) {
-            psz[q] = static_cast<uint32_t>(pools[q].size());
-            for (uint32_t i = 0; i < psz[q]; ++i) {
-                prow[static_cast<size_t>(q) * P + i] = pools[q][i].row;
-                psc[static_cast<size_t>(q) * P + i] = pools[q][i].c;
-            }
-        }
-        st = be.mmr(prow.data(), psc.data(), psz.data(), n_queries, P, top_k, lambda, order.data(), nsel.data());
-        if (st != RLR_OK)
-            return st;
-        for (uint32_t q = 0; q < n_queries; ++q) {
-            results[q].clear();
-            for (uint32_t i = 0; i < nsel[q]; ++i)
-                results[q].push_back(pools[q][order[static_cast<size_t>(q) * P + i]]);
-        }
-    }
-    for (uint32_t q : redo)
-        if ((st = single(q)) != RLR_OK)
-            return st;
     return RLR_OK;
 }
 
-// generic_search_with_diversity_batch with a candidate universe PER QUERY (queries scoped to different documents): N is
-// be.universe(q) wherever that function has be.n_rows, so need_q = min(N_q, k_eff) and fetch_q = min(N_q, need_q + 8)
-// differ from query to query.  be.topk is ONE call with the largest fetch (query q gets min(fetch, N_q) rows back, of
-// which the first fetch_q are looked at: the pool and the boundary rule see what the one-universe function shows them);
-// the MMR is ONE batched call over the non-empty pools with pool_sizes[q] = need_q.  be.single(q, out) is the reference
-// path for query q inside its own universe.  The same fall-backs: w_embedding == 0 or a pool above 1024 loops
-// be.single; a rounding-tie chain that reaches the last looked-at row re-runs that query alone.
-template <typename B>
-int32_t generic_search_with_diversity_batch_scoped(const B &be, const float *queries_raw, uint32_t dq, uint32_t n_queries,
-                                                   uint32_t top_k, float lambda, const rlr_resolved_weights &w,
-                                                   std::vector<std::vector<Cand>> &results)
+// The additive batched entry point (loop of search_with_diversity over the batch, no lexical candidates) with a candidate
+// universe PER QUERY: one batched top-k, per-query pools on the host, one batched MMR; results[q] = that query's hits.
+// universe(q) is N of query q (the reference's corpus size), single(q, out) the reference path for query q inside its
+// own universe; be provides dim, topk and mmr.  need_q = min(N_q, k_eff) and fetch_q = min(N_q, need_q + 8) differ from
+// query to query: be.topk is ONE call with the largest fetch (query q gets min(fetch, N_q) rows back, of which the first
+// fetch_q are looked at -- the pool and the boundary rule see what a call for that query alone shows them), the MMR ONE
+// call over the non-empty pools with P = the largest need.  w_embedding == 0 or a pool above 1024 loops `single`; a
+// query whose fetch cannot decide the pool order (rounding ties at its boundary) is re-run by `single`; a query with
+// an empty universe has no result (:476-478).
+template <typename B, typename Universe, typename Single>
+int32_t generic_search_with_diversity_universes(const B &be, Universe universe, Single single, const float *queries_raw,
+                                                uint32_t dq, uint32_t n_queries, uint32_t top_k, float lambda,
+                                                const rlr_resolved_weights &w, std::vector<std::vector<Cand>> &results)
 {
     results.assign(n_queries, {});
     if (n_queries == 0)
@@ -440,17 +427,17 @@ int32_t generic_search_with_diversity_batch_scoped(const B &be, const float *que
     std::vector<uint64_t> need(n_queries);
     uint64_t max_need = 0, max_fetch = 0;
     for (uint32_t q = 0; q < n_queries; ++q) {
-        const uint64_t N = be.universe(q);
+        const uint64_t N = universe(q);
         need[q] = std::min<uint64_t>(N, k_eff);
         max_need = std::max(max_need, need[q]);
         max_fetch = std::max(max_fetch, std::min<uint64_t>(N, need[q] + 8));
     }
-    if (max_need == 0) // every universe is empty (:476-478)
+    if (max_need == 0) // every universe is empty
         return RLR_OK;
     int32_t st = RLR_OK;
     if (w.embedding == 0.0f || max_need > 1024) { // degenerate weight / pool beyond the batched MMR: loop
         for (uint32_t q = 0; q < n_queries; ++q)
-            if (need[q] && (st = be.single(q, results[q])) != RLR_OK)
+            if (need[q] && (st = single(q, results[q])) != RLR_OK)
                 return st;
         return RLR_OK;
     }
@@ -463,12 +450,12 @@ int32_t generic_search_with_diversity_batch_scoped(const B &be, const float *que
     st = be.topk(qn.data(), n_queries, fetch, rows.data(), cosv.data(), got.data());
     if (st != RLR_OK)
         return st;
-    std::vector<std::vector<Cand>> pools(n_queries);
+    std::vector<std::vector<Cand>> &pools = results;
     std::vector<uint32_t> redo, live;
     for (uint32_t q = 0; q < n_queries; ++q) {
         if (need[q] == 0)
             continue;
-        const uint64_t N = be.universe(q);
+        const uint64_t N = universe(q);
         const uint32_t seen = static_cast<uint32_t>(std::min<uint64_t>(got[q], std::min<uint64_t>(N, need[q] + 8)));
         std::vector<Cand> &c = pools[q];
         c.reserve(seen);
@@ -477,7 +464,9 @@ int32_t generic_search_with_diversity_batch_scoped(const B &be, const float *que
             c.push_back({rows[static_cast<size_t>(q) * fetch + i], combine(w, e, 0.0f), e, 0.0f});
         }
         std::sort(c.begin(), c.end(), cand_before);
-        if (seen < N && seen > 0) { // (the boundary rule of generic_search_with_diversity_batch)
+        // same boundary rule as blend_search: a rounding tie that reaches the last looked-at row
+        // cannot be resolved from this fetch -> that query takes the single-query path
+        if (seen < N && seen > 0) {
             const float c_tail = combine(w, cosv[static_cast<size_t>(q) * fetch + seen - 1], 0.0f);
             if (!(c.size() >= need[q] && (std::isnan(c_tail) || c[need[q] - 1].c > c_tail)))
                 redo.push_back(q);
@@ -487,35 +476,27 @@ int32_t generic_search_with_diversity_batch_scoped(const B &be, const float *que
         if (!c.empty())
             live.push_back(q);
     }
-    if (plain) {
-        for (uint32_t q = 0; q < n_queries; ++q)
-            results[q] = pools[q];
-    } else if (!live.empty()) {
-        const uint32_t P = static_cast<uint32_t>(max_need), nl = static_cast<uint32_t>(live.size());
-        std::vector<uint64_t> prow(static_cast<size_t>(nl) * P, 0);
-        std::vector<float> psc(static_cast<size_t>(nl) * P, 0.0f);
-        std::vector<uint32_t> psz(nl), order(static_cast<size_t>(nl) * P), nsel(nl);
-        for (uint32_t j = 0; j < nl; ++j) {
-            const std::vector<Cand> &c = pools[live[j]];
-            psz[j] = static_cast<uint32_t>(c.size());
-            for (uint32_t i = 0; i < psz[j]; ++i) {
-                prow[static_cast<size_t>(j) * P + i] = c[i].row;
-                psc[static_cast<size_t>(j) * P + i] = c[i].c;
-            }
-        }
-        st = be.mmr(prow.data(), psc.data(), psz.data(), nl, P, top_k, lambda, order.data(), nsel.data());
-        if (st != RLR_OK)
-            return st;
-        for (uint32_t j = 0; j < nl; ++j) {
-            const uint32_t q = live[j];
-            for (uint32_t i = 0; i < nsel[j]; ++i)
-                results[q].push_back(pools[q][order[static_cast<size_t>(j) * P + i]]);
-        }
-    }
+    if (!plain && (st = mmr_pools(be, pools, live, static_cast<uint32_t>(max_need), top_k, lambda)) != RLR_OK)
+        return st;
     for (uint32_t q : redo)
-        if ((st = be.single(q, results[q])) != RLR_OK)
+        if ((st = single(q, results[q])) != RLR_OK)
             return st;
     return RLR_OK;
+}
+
+// The same for ONE universe, the backend's own: N_q = be.n_rows makes every fetch_q the fetch and every need_q the need.
+template <typename B>
+int32_t generic_search_with_diversity_batch(const B &be, const float *queries_raw, uint32_t dq, uint32_t n_queries,
+                                            uint32_t top_k, float lambda, const rlr_resolved_weights &w,
+                                            std::vector<std::vector<Cand>> &results)
+{
+    return generic_search_with_diversity_universes(
+        be, [&](uint32_t) { return be.n_rows; },
+        [&](uint32_t q, std::vector<Cand> &out) {
+            return generic_search_with_diversity(be, queries_raw + static_cast<size_t>(q) * dq, dq, top_k, lambda, w, nullptr,
+                                                 nullptr, 0, out);
+        },
+        queries_raw, dq, n_queries, top_k, lambda, w, results);
 }
 
 } // namespace rlr_host

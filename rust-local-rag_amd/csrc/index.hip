@@ -2436,43 +2436,82 @@ int32_t filtered_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *
     return note_search(ix, c, 1, n_cand, n_retry, timed && f->path != 0);
 }
 
-// ---- several queries inside one filter ------------------------------------------------------------------------------
-// Does a chunk of nq (2..8) queries over `f` take the shared masked pass (scan_masked_multi_kernel)?  The filter's path
-// must be the masked scan and the rows a shape the kernel serves; k (already clamped to the allowed rows) must leave the
-// finish its band.  RLR_BATCH_MIN decides when set.  Else a cost model over the ALLOWED bytes A, fitted to the calls
-// measured at 1 M x 768 f32, k = 100 (tools/bench_filtered.py --queries against the parent build, natural and with the
-// pass forced; DESIGN.md "Several queries inside one filter" has the table and what was NOT measured):
-//   one by one   per query 45 us of launches and its own synchronisation + A / 6.5 TB/s
+// ---- several queries, inside one filter or a filter each: one shared masked pass ------------------------------------
+// Can a query over `f` join a shared pass at all?  Its filter is on the masked-scan path and holds at least k rows (one
+// plan, one rank k for the whole chunk), the rows are a shape the kernel serves and k leaves the finish its band.
+bool masked_query_joins(const rlr_index *ix, const rlr_filter *f, uint32_t k)
+{
+    return f->path == 1 && k <= f->n_allowed && batch_multi_shape(ix, 2) && k * 8 <= batch_finish_capacity();
+}
+
+// Does a chunk of nq (2..8) queries, query q inside fs[q], take ONE shared masked pass -- with one_filter (every fs[q] the
+// same object; k already clamped to its allowed rows) scan_masked_multi_kernel over that filter, else
+// scan_masked_scopes_kernel over the union of the scopes?  Every query must be able to join.  RLR_BATCH_MIN decides when
+// set.  Else a cost model over the ALLOWED bytes A_q, fitted to the calls measured at 1 M x 768 f32, k = 100:
+//   one by one   per query 45 us of launches and its own synchronisation + its OWN A_q / 6.5 TB/s
 //                (measured 0.050 / 0.10 / 0.28 / 0.50 ms per query at 0.01 / 0.1 / 0.5 / 1.0 of the rows)
 //   shared       100 us for the batched select, the finish and the one synchronisation, 6 us per query and million rows
 //                (the select reads an n_rows-long score array per query, sentinels included, whatever the filter allows)
-//                and one pass at 6.5 / 6.0 / 4.1 TB/s for the Q = 2 / 4 / 8 instance (eight queries are VALU-bound)
-//                (measured 0.106 / 0.112 / 0.142 ms at 0.01, 0.55 / 0.62 / 0.88 with every row allowed)
-// and the shared pass must win by 10 %: two queries over a hundredth of the rows measured 3-5 % SLOWER shared and stay
-// one by one, as the model has it.
-bool filtered_batch_eligible(const rlr_index *ix, const rlr_filter *f, uint32_t nq, uint32_t k)
+//                and one pass over the bytes of the union at the rate of the Q = 2 / 4 / 8 instance
+// and the shared pass must win by 10 %.
+// One filter (tools/bench_filtered.py --queries against the parent build, natural and with the pass forced; DESIGN.md
+// "Several queries inside one filter" has the table and what was NOT measured): the union is the filter, the pass runs
+// at 6.5 / 6.0 / 4.1 TB/s (eight queries are VALU-bound; measured 0.106 / 0.112 / 0.142 ms at 0.01, 0.55 / 0.62 / 0.88
+// with every row allowed).  Two queries over a hundredth of the rows measured 3-5 % SLOWER shared and stay one by one,
+// as the model has it.
+// A filter per query: the union is estimated as min(n_rows, sum of |F_q|) -- exact for disjoint scopes, an upper bound
+// otherwise (identical scopes are overestimated nq-fold, which only makes the gate decline earlier) -- so that no call
+// popcounts ORed masks.  The pass rates are refitted to the forced leg of tools/bench_scoped.py (MI355X, 1 M x 768 f32,
+// k = 100; DESIGN.md "Queries with different scopes in one pass" has the table and what was NOT measured), (whole call -
+// fixed costs) per byte of the union, the slower of the disjoint and the overlapping scope sets: 5.5 / 4.8 / 3.8 TB/s --
+// a unit reads Q mask words and branches per query and row.  With these no measured configuration is slower than one by
+// one, and the gate declines three that the forced pass won: two random halves (20 %: the estimate, every row, exceeds
+// the union, three quarters) and 4 / 8 disjoint eighths (9 / 15 %: the one-by-one side, 104 us per query, is below the
+// 118 us measured through the Python layer).  The model errs to the parent's path.
+bool filtered_batch_eligible(const rlr_index *ix, const rlr_filter *const *fs, uint32_t nq, uint32_t k, bool one_filter)
 {
-    if (nq < 2 || f->path != 1 || !batch_multi_shape(ix, nq) || k * 8 > batch_finish_capacity())
+    if (nq < 2 || nq > 8)
         return false;
+    for (uint32_t q = 0; q < nq; ++q)
+        if (!masked_query_joins(ix, fs[q], k))
+            return false;
     if (ix->batch_min > 0)
         return nq >= ix->batch_min;
-    const double allowed_bytes = static_cast<double>(f->n_allowed) * ix->dim * 4.0;
-    const double t_single = 45e-6 + allowed_bytes / 6.5e12;
-    const double pass_rate = nq <= 2 ? 6.5e12 : nq <= 4 ? 6.0e12 : 4.1e12;
-    const double t_shared = 100e-6 + nq * (static_cast<double>(ix->n_rows) * 6e-12) + allowed_bytes / pass_rate;
-    return nq * t_single > 1.1 * t_shared;
+    double t_single = 0.0, union_rows = 0.0;
+    if (one_filter) {
+        union_rows = static_cast<double>(fs[0]->n_allowed);
+        t_single = nq * (45e-6 + union_rows * ix->dim * 4.0 / 6.5e12);
+    } else {
+        for (uint32_t q = 0; q < nq; ++q) {
+            t_single += 45e-6 + static_cast<double>(fs[q]->n_allowed) * ix->dim * 4.0 / 6.5e12;
+            union_rows += static_cast<double>(fs[q]->n_allowed);
+        }
+        union_rows = std::min(static_cast<double>(ix->n_rows), union_rows);
+    }
+    const double pass_rate = one_filter ? (nq <= 2 ? 6.5e12 : nq <= 4 ? 6.0e12 : 4.1e12) : (nq <= 2 ? 5.5e12 : nq <= 4 ? 4.8e12 : 3.8e12);
+    const double t_shared = 100e-6 + nq * (static_cast<double>(ix->n_rows) * 6e-12) + union_rows * ix->dim * 4.0 / pass_rate;
+    return t_single > 1.1 * t_shared;
 }
 
-// A chunk of m (2..8) queries over `f` through ONE masked pass: the queries staged and uploaded once, the pass into
-// c->d_sample (the "sample" is the whole score array: rank = k, as run_batched's use_multi branch), the batched select and
-// finish, one result copy and one synchronisation.  The hazards filtered_query closes are closed per query: a result
-// holding a masked row (k reached allowed rows whose nominated score is NaN: threshold key 0) and a query the finish
-// handed back (band overflow, mass ties) are re-run by filtered_query -- never by an unfiltered path.  c->d_hist is not
-// touched (the select's histograms are c->d_bhist, cleared in front of every use).
-int32_t filtered_batch(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *queries, uint32_t m, uint32_t k, float guard_eps,
-                       uint64_t *rows_out, float *cos_out, uint32_t *n_out)
+// A chunk of m (2..8) queries, query q inside fs[q], through ONE masked pass (the gate's one_filter says which): the
+// queries staged and uploaded once, the pass into c->d_sample (the "sample" is the whole score array: rank = k, as
+// run_batched's use_multi branch), the batched select and finish, one result copy and one synchronisation.  k is clamped
+// to the smallest scope, so one plan serves the chunk (a filter each: k <= every |F_q| already).  Query q's score array
+// is the same whichever pass wrote it.  The hazards filtered_query closes are closed per query: a result holding a row
+// its OWN filter masks (k reached allowed rows whose nominated score is NaN: threshold key 0) and a query the finish
+// handed back (band overflow, mass ties) are re-run by filtered_query inside that filter -- never by an unfiltered path.
+// c->d_hist is not touched (the select's histograms are c->d_bhist, cleared in front of every use).
+int32_t masked_batch(rlr_index *ix, Ctx *c, const rlr_filter *const *fs, bool one_filter, const float *queries, uint32_t m,
+                     uint32_t k, float guard_eps, uint64_t *rows_out, float *cos_out, uint32_t *n_out)
 {
-    const SearchPlan p = make_plan(ix, queries, m, static_cast<uint32_t>(std::min<uint64_t>(k, f->n_allowed)), guard_eps);
+    uint64_t k_plan = k, sum_rows = 0;
+    const uint64_t *masks[8] = {};
+    for (uint32_t q = 0; q < m; ++q) {
+        k_plan = std::min<uint64_t>(k_plan, fs[q]->n_allowed);
+        sum_rows += fs[q]->n_allowed;
+        masks[q] = fs[q]->d_mask.get();
+    }
+    const SearchPlan p = make_plan(ix, queries, m, static_cast<uint32_t>(k_plan), guard_eps);
     RLR_TRY(ctx_prepare(ix, c, m, p));
     const size_t n_res = static_cast<size_t>(m) * p.k;
     Staged pin;
@@ -2486,9 +2525,13 @@ int32_t filtered_batch(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *
     const bool timed = ix->profiling;
     if (timed) RLR_HIP(hipEventRecord(c->bev[0], s));
     hipError_t e = hipSuccess;
-    if (!launch_scan_masked_multi(scan_args(ix, c->d_query.get(), c->d_sample.get(), nullptr), f->d_mask.get(), f->n_allowed, ix->q_pitch, m,
-                                  s_stride, s, &e))
-        return set_error(RLR_E_INTERNAL, "masked multi-query scan refused a shape its gate accepted");
+    const ScanArgs sa = scan_args(ix, c->d_query.get(), c->d_sample.get(), nullptr);
+    if (one_filter) {
+        if (!launch_scan_masked_multi(sa, masks[0], fs[0]->n_allowed, ix->q_pitch, m, s_stride, s, &e))
+            return set_error(RLR_E_INTERNAL, "masked multi-query scan refused a shape its gate accepted");
+    } else if (!launch_scan_masked_scopes(sa, masks, std::min<uint64_t>(n, sum_rows), ix->q_pitch, m, s_stride, s, &e)) {
+        return set_error(RLR_E_INTERNAL, "masked multi-scope scan refused a shape its gate accepted");
+    }
     RLR_HIP(e);
     if (timed) RLR_HIP(hipEventRecord(c->bev[1], s));
     RLR_HIP(launch_batch_select(c->d_sample.get(), static_cast<uint32_t>(n), s_stride, m, c->d_bhist.get(), c->d_bstate.get(), two_eps, c->d_tau.get(),
@@ -2498,120 +2541,6 @@ int32_t filtered_batch(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *
     c->hist_dirty = false;
     std::vector<uint32_t> redo;
     uint64_t n_cand_total = 0; // of the queries served here, as filtered_query reports its own
-    for (uint32_t q = 0; q < m; ++q) {
-        bool back = status[q] != 0;
-        for (uint32_t i = 0; i < p.k && !back; ++i)
-            back = !filter_holds(f, 0xFFFFFFFFu - static_cast<uint32_t>(h_res[static_cast<size_t>(q) * p.k + i]));
-        if (back) {
-            redo.push_back(q);
-            continue;
-        }
-        n_out[q] = p.k;
-        n_cand_total += n_cand[q];
-        unpack_results(h_res + static_cast<size_t>(q) * p.k, p.k, rows_out + static_cast<size_t>(q) * k, cos_out + static_cast<size_t>(q) * k);
-    }
-    {
-        float scan_ms = 0;
-        if (timed)
-            (void)hipEventElapsedTime(&scan_ms, c->bev[0], c->bev[1]);
-        std::lock_guard<std::mutex> lk(ix->mu);
-        ix->prof.n_batches += 1;
-        ix->prof.n_batch_queries += m;
-        ix->prof.n_batch_fallbacks += redo.size();
-        ix->prof.n_searches += m - redo.size(); // (a query handed back is counted by filtered_query)
-        ix->prof.n_candidates += n_cand_total;
-        if (timed) {
-            ix->prof.scan_ms += scan_ms;
-            ix->prof.scan_bytes += f->n_allowed * ix->dim * 4;
-        }
-    }
-    // (from here on the pinned buffer and the context are filtered_query's)
-    for (uint32_t q : redo)
-        RLR_TRY(filtered_query(ix, c, f, queries + static_cast<size_t>(q) * ix->dim, k, guard_eps, rows_out + static_cast<size_t>(q) * k,
-                               cos_out + static_cast<size_t>(q) * k, &n_out[q]));
-    return RLR_OK;
-}
-
-// ---- several queries, a filter each (rlr_search_topk_scoped) --------------------------------------------------------
-// Can query q of a scoped call join a shared pass at all?  Its filter is on the masked-scan path and holds at least k
-// rows (one plan, one rank k for the whole chunk), the rows are a shape the kernel serves and k leaves the finish its band.
-bool scoped_query_joins(const rlr_index *ix, const rlr_filter *f, uint32_t k)
-{
-    return f->path == 1 && k <= f->n_allowed && batch_multi_shape(ix, 2) && k * 8 <= batch_finish_capacity();
-}
-
-// Does a chunk of nq (2..8) such queries take ONE pass over the union of their scopes (scan_masked_scopes_kernel)?
-// RLR_BATCH_MIN decides when set.  Else the model of filtered_batch_eligible with a filter per query: one by one every
-// query pays its launches, its synchronisation and its OWN allowed bytes; shared, the pass reads the union once.  The
-// union is estimated as min(n_rows, sum of |F_q|) -- exact for disjoint scopes, an upper bound otherwise (identical
-// scopes are overestimated nq-fold, which only makes the gate decline earlier) -- so that no call popcounts ORed masks.
-// The one-by-one side and the fixed costs are filtered_batch_eligible's.  The pass rates are refitted to the forced
-// leg of tools/bench_scoped.py (MI355X, 1 M x 768 f32, k = 100; DESIGN.md "Queries with different scopes in one pass" has
-// the table and what was NOT measured), (whole call - fixed costs) per byte of the union, the slower of the disjoint and
-// the overlapping scope sets: 5.5 / 4.8 / 3.8 TB/s for the Q = 2 / 4 / 8 instance where the one-filter pass has
-// 6.5 / 6.0 / 4.1 -- a unit reads Q mask words and branches per query and row.  With these no measured configuration is
-// slower than one by one, and the gate declines three that the forced pass won: two random halves (20 %: the estimate,
-// every row, exceeds the union, three quarters) and 4 / 8 disjoint eighths (9 / 15 %: the one-by-one side, 104 us per
-// query, is below the 118 us measured through the Python layer).  The 10 % margin is kept; the model errs to the parent's path.
-bool scoped_batch_eligible(const rlr_index *ix, const rlr_filter *const *fs, uint32_t nq, uint32_t k)
-{
-    if (nq < 2 || nq > 8)
-        return false;
-    for (uint32_t q = 0; q < nq; ++q)
-        if (!scoped_query_joins(ix, fs[q], k))
-            return false;
-    if (ix->batch_min > 0)
-        return nq >= ix->batch_min;
-    double t_single = 0.0, sum_rows = 0.0;
-    for (uint32_t q = 0; q < nq; ++q) {
-        t_single += 45e-6 + static_cast<double>(fs[q]->n_allowed) * ix->dim * 4.0 / 6.5e12;
-        sum_rows += static_cast<double>(fs[q]->n_allowed);
-    }
-    const double union_bytes = std::min(static_cast<double>(ix->n_rows), sum_rows) * ix->dim * 4.0;
-    const double pass_rate = nq <= 2 ? 5.5e12 : nq <= 4 ? 4.8e12 : 3.8e12;
-    const double t_shared = 100e-6 + nq * (static_cast<double>(ix->n_rows) * 6e-12) + union_bytes / pass_rate;
-    return t_single > 1.1 * t_shared;
-}
-
-// filtered_batch with a filter per query: a chunk of m (2..8) queries, query q inside fs[q], through ONE pass over the
-// union of the scopes.  k <= every |F_q| (scoped_batch_eligible), so one plan serves the chunk.  Query q's score array is
-// what the one-filter pass writes with fs[q], so the select and the finish are filtered_batch's; the leak test runs
-// against the query's OWN host mask and a query handed back is re-run by filtered_query inside its OWN filter.
-int32_t scoped_batch(rlr_index *ix, Ctx *c, const rlr_filter *const *fs, const float *queries, uint32_t m, uint32_t k,
-                     float guard_eps, uint64_t *rows_out, float *cos_out, uint32_t *n_out)
-{
-    const SearchPlan p = make_plan(ix, queries, m, k, guard_eps);
-    RLR_TRY(ctx_prepare(ix, c, m, p));
-    const size_t n_res = static_cast<size_t>(m) * p.k;
-    Staged pin;
-    RLR_TRY(stage_call(ix, c, queries, m, n_res, /*for_scans=*/false, &pin));
-    uint64_t *h_res = pin.h_res;
-    hipStream_t s = c->stream;
-    const uint64_t n = ix->n_rows;
-    const uint64_t s_stride = (n + 3) / 4 * 4;
-    const float two_eps = p.two_eps;
-    RLR_TRY(batch_arm(c, m, batch_finish_capacity(), s_stride, p.k, n));
-    const bool timed = ix->profiling;
-    const uint64_t *masks[8] = {};
-    uint64_t sum_rows = 0;
-    for (uint32_t q = 0; q < m; ++q) {
-        masks[q] = fs[q]->d_mask.get();
-        sum_rows += fs[q]->n_allowed;
-    }
-    if (timed) RLR_HIP(hipEventRecord(c->bev[0], s));
-    hipError_t e = hipSuccess;
-    if (!launch_scan_masked_scopes(scan_args(ix, c->d_query.get(), c->d_sample.get(), nullptr), masks, std::min<uint64_t>(n, sum_rows),
-                                   ix->q_pitch, m, s_stride, s, &e))
-        return set_error(RLR_E_INTERNAL, "masked multi-scope scan refused a shape its gate accepted");
-    RLR_HIP(e);
-    if (timed) RLR_HIP(hipEventRecord(c->bev[1], s));
-    RLR_HIP(launch_batch_select(c->d_sample.get(), static_cast<uint32_t>(n), s_stride, m, c->d_bhist.get(), c->d_bstate.get(), two_eps, c->d_tau.get(),
-                                c->d_bcand.get(), batch_finish_capacity(), ix->n_cu, s));
-    std::vector<uint32_t> status, n_cand;
-    RLR_TRY(batch_finish(ix, c, c->d_query.get(), m, p.k, two_eps, c->d_out.get(), status, h_res, &n_cand));
-    c->hist_dirty = false;
-    std::vector<uint32_t> redo;
-    uint64_t n_cand_total = 0;
     for (uint32_t q = 0; q < m; ++q) {
         bool back = status[q] != 0;
         for (uint32_t i = 0; i < p.k && !back; ++i)
@@ -2626,12 +2555,11 @@ int32_t scoped_batch(rlr_index *ix, Ctx *c, const rlr_filter *const *fs, const f
     }
     {
         float scan_ms = 0;
-        uint64_t union_rows = 0;
+        uint64_t union_rows = one_filter ? fs[0]->n_allowed : 0;
         if (timed) {
             (void)hipEventElapsedTime(&scan_ms, c->bev[0], c->bev[1]);
-            // the rows the pass read: the exact union (profiling is off by default; no call pays this otherwise)
-            const size_t n_words = fs[0]->h_mask.size();
-            for (size_t w = 0; w < n_words; ++w) {
+            // the rows the pass read: a filter each, the exact union (profiling is off by default; no call pays this otherwise)
+            for (size_t w = 0; !one_filter && w < fs[0]->h_mask.size(); ++w) {
                 uint64_t any = 0;
                 for (uint32_t q = 0; q < m; ++q)
                     any |= fs[q]->h_mask[w];
@@ -3285,13 +3213,14 @@ int32_t rlr_search_topk_filtered(rlr_index *ix, const rlr_filter *f, const float
     const uint32_t list_run = static_cast<uint32_t>(std::min<uint64_t>(
         kFilterListBatchQueries,
         std::max<uint64_t>(1, kFilterListBatchEntries / next_pow2(std::max<uint32_t>(static_cast<uint32_t>(f->n_allowed), k_eff)))));
+    const rlr_filter *const fs[8] = {f, f, f, f, f, f, f, f}; // (a chunk's filter per query)
     for (uint32_t q0 = 0; q0 < n_queries;) {
         const float *qs = queries + static_cast<size_t>(q0) * ix->dim;
         uint64_t *ro = rows_out + static_cast<size_t>(q0) * k;
         float *co = cos_out + static_cast<size_t>(q0) * k;
         uint32_t m = std::min<uint32_t>(8, n_queries - q0);
-        if (filtered_batch_eligible(ix, f, m, k_eff)) {
-            RLR_TRY(filtered_batch(ix, lease.c, f, qs, m, k, guard_eps, ro, co, n_out + q0));
+        if (filtered_batch_eligible(ix, fs, m, k_eff, /*one_filter=*/true)) {
+            RLR_TRY(masked_batch(ix, lease.c, fs, /*one_filter=*/true, qs, m, k, guard_eps, ro, co, n_out + q0));
         } else if (f->path == 0 && (m = std::min(list_run, n_queries - q0)) >= 2) {
             RLR_TRY(filtered_list_batch(ix, lease.c, f, qs, m, k, guard_eps, ro, co, n_out + q0));
         } else {
@@ -3324,13 +3253,13 @@ int32_t rlr_search_topk_scoped(rlr_index *ix, const rlr_filter *const *filters, 
     CtxLease lease(ix);
     RLR_TRY(ctx_acquire(ix, &lease.c));
     StreamDrain drain{lease.c->stream};
-    // The queries that can join a shared pass (scoped_query_joins), in call order, in chunks of up to 8: a chunk the gate
+    // The queries that can join a shared pass (masked_query_joins), in call order, in chunks of up to 8: a chunk the gate
     // accepts is one pass over the union of its scopes (or, all filters being one object, the one-filter pass); every
     // other query -- a list-path filter, fewer allowed rows than k, binary16 rows, other widths, a chunk the gate
     // declines, a last chunk of one -- runs alone through filtered_query inside its own filter.
     std::vector<uint32_t> joins;
     for (uint32_t q = 0; q < n_queries; ++q)
-        if (scoped_query_joins(ix, filters[q], k))
+        if (masked_query_joins(ix, filters[q], k))
             joins.push_back(q);
     std::vector<char> served(n_queries, 0);
     std::vector<float> qs;
@@ -3344,8 +3273,8 @@ int32_t rlr_search_topk_scoped(rlr_index *ix, const rlr_filter *const *filters, 
             fs[i] = filters[joins[j0 + i]];
             same = same && fs[i] == fs[0];
         }
-        const bool one_filter = same && filtered_batch_eligible(ix, fs[0], m, k);
-        if (!one_filter && !scoped_batch_eligible(ix, fs, m, k))
+        const bool one_filter = same && filtered_batch_eligible(ix, fs, m, k, /*one_filter=*/true);
+        if (!one_filter && !filtered_batch_eligible(ix, fs, m, k, /*one_filter=*/false))
             continue;
         qs.resize(static_cast<size_t>(m) * ix->dim);
         ro.resize(static_cast<size_t>(m) * k);
@@ -3354,10 +3283,7 @@ int32_t rlr_search_topk_scoped(rlr_index *ix, const rlr_filter *const *filters, 
         for (uint32_t i = 0; i < m; ++i)
             std::memcpy(qs.data() + static_cast<size_t>(i) * ix->dim, queries + static_cast<size_t>(joins[j0 + i]) * ix->dim,
                         static_cast<size_t>(ix->dim) * sizeof(float));
-        if (one_filter)
-            RLR_TRY(filtered_batch(ix, lease.c, fs[0], qs.data(), m, k, guard_eps, ro.data(), co.data(), got));
-        else
-            RLR_TRY(scoped_batch(ix, lease.c, fs, qs.data(), m, k, guard_eps, ro.data(), co.data(), got));
+        RLR_TRY(masked_batch(ix, lease.c, fs, one_filter, qs.data(), m, k, guard_eps, ro.data(), co.data(), got));
         for (uint32_t i = 0; i < m; ++i) {
             const uint32_t q = joins[j0 + i];
             n_out[q] = got[i];

@@ -24,29 +24,17 @@ int32_t rlr_engine_search_text_batch(rlr_index *idx, rlr_lexical *lex, const flo
 {
     if (info)
         *info = rlr_text_batch_info{};
-    if (!idx || !lex || (n_queries && (!n_out || !token_offsets || (dq && !queries_raw))))
+    if (!idx || !lex || !text_batch_args(queries_raw, dq, n_queries, tokens, token_offsets, n_out))
         return RLR_E_INVALID;
-    for (uint32_t q = 0; q < n_queries; ++q) {
-        if (token_offsets[q + 1] < token_offsets[q])
-            return RLR_E_INVALID;
-    }
-    if (n_queries && token_offsets[n_queries] > token_offsets[0] && !tokens)
-        return RLR_E_INVALID;
-    for (uint32_t q = 0; q < n_queries; ++q)
-        n_out[q] = 0;
     if (n_queries == 0)
         return RLR_OK;
     // the sizes rlr_engine_search_text works with
-    float lambda = diversity_factor;
-    if (lambda < 0.0f) lambda = 0.0f; // f32::clamp(0.0, 1.0) (:725); NaN takes the MMR branch
-    if (lambda > 1.0f) lambda = 1.0f;
-    const bool diversify = !(lambda == 0.0f);
+    const TextSizes ts = text_sizes(top_k, diversity_factor);
+    const float lambda = ts.lambda;
+    const bool diversify = ts.diversify;
+    const uint32_t k_seen = ts.k_seen, limit = ts.limit;
     rlr_resolved_weights w;
     rlr_resolve_weights(weights, &w);
-    const uint64_t p3 = static_cast<uint64_t>(top_k) * 3, p10 = static_cast<uint64_t>(top_k) + 10;
-    const uint32_t pool_size = static_cast<uint32_t>(std::min<uint64_t>(std::max(p3, p10), 0xFFFFFFFFull)); // :734
-    const uint32_t k_seen = std::max<uint32_t>(diversify ? pool_size : top_k, 1u);
-    const uint32_t limit = static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(k_seen) * 5, 0xFFFFFFFFull)); // :505
     uint64_t N = 0;
     uint32_t dim = 0;
     int32_t st = rlr_index_info(idx, &N, &dim, nullptr, nullptr);
@@ -66,7 +54,7 @@ int32_t rlr_engine_search_text_batch(rlr_index *idx, rlr_lexical *lex, const flo
                                       &n_out[q]);
     };
     // the shapes the fused kernels cover (the conditions of search_hybrid_begin for the same request)
-    const uint32_t n_lex_bound = std::min<uint32_t>(limit, RLR_LEXICAL_MAX_LIMIT);
+    const uint32_t n_lex_bound = ts.lcap;
     const uint64_t fetch_full = std::min<uint64_t>(N, need + n_lex_bound + 8);
     const bool fused = w.embedding > 0.0f && std::isfinite(w.embedding) && std::isfinite(w.lexical) && need <= 1024 &&
                        n_lex_bound <= 2048 && fetch_full + n_lex_bound <= 4096 && N <= 0xFFFFFFFFull;

@@ -3,7 +3,9 @@
 // search / search_with_diversity / blend on random corpora with lexical candidates, ties, NaN rows and weight overrides.
 // Exit code 0 = every comparison matched and no sanitizer report was raised (-fno-sanitize-recover aborts on the first).
 #include "../../include/rlr_engine.h"
+#include "../../rust-local-rag_amd/csrc/engine_host.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -41,6 +43,42 @@ static int g_fail = 0;
     } while (0)
 
 static bool same_bits(float a, float b) { return std::memcmp(&a, &b, 4) == 0; }
+
+// A toy backend of csrc/engine_host.h whose candidate universe is a row subset (ascending) of the stub's matrix: the
+// top-k is a brute-force ranking restricted to the subset, scoring and MMR go through the stub.
+struct SubsetBackend {
+    rlr_index *ix;
+    std::vector<uint64_t> sub;
+    uint64_t n_rows;
+    uint32_t dim;
+    bool holds(uint64_t row) const { return std::binary_search(sub.begin(), sub.end(), row); }
+    void first_rows(uint64_t take, uint64_t *rows) const { std::copy(sub.begin(), sub.begin() + take, rows); }
+    int32_t score_rows(const float *q, const uint64_t *rows, uint32_t n, float *cos) const { return rlr_score_rows(ix, q, rows, n, cos); }
+    int32_t topk(const float *queries, uint32_t nq, uint32_t k, uint64_t *rows, float *cos, uint32_t *n) const
+    {
+        std::vector<float> e(sub.size());
+        std::vector<uint32_t> order(sub.size());
+        for (uint32_t q = 0; q < nq; ++q) {
+            score_rows(queries + static_cast<size_t>(q) * dim, sub.data(), static_cast<uint32_t>(sub.size()), e.data());
+            for (uint32_t i = 0; i < order.size(); ++i) order[i] = i;
+            std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { // (cos desc, NaN last, row asc)
+                return std::isnan(e[a]) || std::isnan(e[b]) ? !std::isnan(e[a]) && std::isnan(e[b]) : e[a] > e[b];
+            });
+            n[q] = static_cast<uint32_t>(std::min<size_t>(k, sub.size()));
+            for (uint32_t i = 0; i < n[q]; ++i) {
+                rows[static_cast<size_t>(q) * k + i] = sub[order[i]];
+                cos[static_cast<size_t>(q) * k + i] = e[order[i]];
+            }
+        }
+        return RLR_OK;
+    }
+    int32_t mmr(const uint64_t *pr, const float *ps, const uint32_t *pz, uint32_t nq, uint32_t P, uint32_t k, float lam, uint32_t *order,
+                uint32_t *n_sel) const
+    {
+        return nq == 1 ? rlr_mmr_select(ix, pr, ps, pz[0], k, lam, order, nullptr, n_sel)
+                       : rlr_mmr_select_batch(ix, pr, ps, pz, nq, P, k, lam, order, nullptr, n_sel);
+    }
+};
 
 int main(int argc, char **argv)
 {
@@ -143,6 +181,86 @@ int main(int argc, char **argv)
             for (uint32_t i = 0; i < nf && i < nb; ++i)
                 CHECK(fin[i].row == crow[oidx[i]] && same_bits(fin[i].score, osc[i]) && fhas[i] == ohas[i], "blend rep %d q %d i %u", rep, qi, i);
         }
+        rlr_index_destroy(ix);
+    }
+    // ---- the batched diversity search: one universe through the engine's entry point, a universe per query on a toy backend
+    {
+        const uint32_t dim = 8, n = 60, nq = 5, top_k = 3;
+        std::vector<float> rows(n * dim), qs(nq * dim);
+        for (auto &v : rows) v = gauss(rng);
+        for (auto &v : qs) v = gauss(rng);
+        for (uint32_t r = 11; r < 40; ++r) // 30 equal rows, query 0 along them: an exact-tie chain past any fetch boundary
+            std::memcpy(rows.data() + r * dim, rows.data() + 10 * dim, dim * 4);
+        std::memcpy(qs.data(), rows.data() + 10 * dim, dim * 4);
+        rlr_index *ix = nullptr;
+        rlr_index_create(dim, RLR_F32, 0, &ix);
+        rlr_index_upload(ix, rows.data(), n, 1);
+        // universes: 0 the tie rows and more, 1 smaller than the pool (13), 2 empty, 3 (16 rows) below the pool's fetch (21), 4 above it
+        std::vector<SubsetBackend> one(nq, SubsetBackend{ix, {}, 0, dim});
+        for (uint64_t r = 0; r < n; ++r) {
+            if (r % 13 == 2) one[1].sub.push_back(r);
+            if (r >= 8 && r < 50) one[0].sub.push_back(r);
+            if (r % 2 == 0 && (r <= 10 || r >= 40)) one[3].sub.push_back(r);
+            if (r < 12 || r >= 40) one[4].sub.push_back(r); // (rows 10 and 11: a tie of two, which no boundary rule trips over)
+        }
+        for (auto &b : one) b.n_rows = b.sub.size();
+        struct { // (what the batch asks of its backend: dim, a top-k of query q inside universe q, the stub's MMR)
+            const std::vector<SubsetBackend> &one;
+            uint32_t dim;
+            int32_t topk(const float *queries, uint32_t m, uint32_t k, uint64_t *r, float *c, uint32_t *cnt) const
+            {
+                for (uint32_t q = 0; q < m; ++q)
+                    one[q].topk(queries + static_cast<size_t>(q) * dim, 1, k, r + static_cast<size_t>(q) * k, c + static_cast<size_t>(q) * k, cnt + q);
+                return RLR_OK;
+            }
+            int32_t mmr(const uint64_t *pr, const float *ps, const uint32_t *pz, uint32_t m, uint32_t P, uint32_t k, float lam,
+                        uint32_t *order, uint32_t *n_sel) const
+            {
+                return one[0].mmr(pr, ps, pz, m, P, k, lam, order, n_sel);
+            }
+        } toy{one, dim};
+        for (float lam : {0.0f, 0.7f})
+            for (float we : {0.7f, 0.0f}) {
+                rlr_query_weights wq{};
+                wq.has_embedding = 1; wq.embedding = we;
+                rlr_resolved_weights w;
+                rlr_resolve_weights(&wq, &w);
+                const uint32_t cap = 16;
+                std::vector<rlr_search_hit> hb(nq * cap), hs(cap);
+                std::vector<uint32_t> nb(nq);
+                int32_t st = rlr_engine_search_with_diversity_batch(ix, qs.data(), dim, nq, top_k, lam, &wq, hb.data(), cap, nb.data());
+                CHECK(st == RLR_OK, "diversity batch status %d", st);
+                for (uint32_t q = 0; q < nq; ++q) {
+                    uint32_t ns = 0;
+                    st = rlr_engine_search_with_diversity(ix, qs.data() + q * dim, dim, top_k, lam, &wq, nullptr, nullptr, 0, hs.data(), cap, &ns);
+                    CHECK(st == RLR_OK && ns == nb[q] && ns == top_k, "diversity batch count lam %g we %g q %u: %u vs %u", lam, we, q, nb[q], ns);
+                    for (uint32_t i = 0; i < ns && i < nb[q]; ++i)
+                        CHECK(hb[q * cap + i].row == hs[i].row && same_bits(hb[q * cap + i].score, hs[i].score) &&
+                                  same_bits(hb[q * cap + i].embedding_score, hs[i].embedding_score),
+                              "diversity batch lam %g we %g q %u i %u", lam, we, q, i);
+                }
+                uint32_t n_single = 0;
+                auto single = [&](uint32_t q, std::vector<rlr_host::Cand> &out) {
+                    ++n_single;
+                    return rlr_host::generic_search_with_diversity(one[q], qs.data() + q * dim, dim, top_k, lam, w, nullptr, nullptr, 0, out);
+                };
+                std::vector<std::vector<rlr_host::Cand>> res;
+                st = rlr_host::generic_search_with_diversity_universes(
+                    toy, [&](uint32_t q) { return one[q].n_rows; }, single, qs.data(), dim, nq, top_k, lam, w, res);
+                CHECK(st == RLR_OK && res.size() == nq, "universes status %d", st);
+                // w_e == 0 loops the non-empty universes; else exactly query 0's tie chain reaches its boundary
+                CHECK(n_single == (we == 0.0f ? nq - 1 : 1u), "universes lam %g we %g: %u single calls", lam, we, n_single);
+                for (uint32_t q = 0; q < nq && q < res.size(); ++q) {
+                    std::vector<rlr_host::Cand> want;
+                    st = rlr_host::generic_search_with_diversity(one[q], qs.data() + q * dim, dim, top_k, lam, w, nullptr, nullptr, 0, want);
+                    CHECK(st == RLR_OK && res[q].size() == want.size() && want.size() == std::min<size_t>(top_k, one[q].sub.size()),
+                          "universes count lam %g we %g q %u: %zu vs %zu", lam, we, q, res[q].size(), want.size());
+                    for (size_t i = 0; i < want.size() && i < res[q].size(); ++i)
+                        CHECK(res[q][i].row == want[i].row && same_bits(res[q][i].c, want[i].c) && same_bits(res[q][i].e, want[i].e) &&
+                                  one[q].holds(res[q][i].row),
+                              "universes lam %g we %g q %u i %zu", lam, we, q, i);
+                }
+            }
         rlr_index_destroy(ix);
     }
     // ---- corpus file reader / formatter

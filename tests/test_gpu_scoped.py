@@ -124,6 +124,34 @@ def test_identical_filter_objects(corpus):
             f.close()
 
 
+def test_one_filter_object_in_every_slot_is_the_one_filter_pass(rlr, oracle):
+    """eight queries over ONE filter object through rlr_search_topk_scoped and the same eight through
+    rlr_search_topk_filtered (4096 x 256 f32, k = 5, the pass forced): the two entries meet in the same shared pass --
+    equal rows, cosine bits and profile deltas (one pass of eight queries, nothing handed back, no single scan, the
+    filter's rows read once)"""
+    n, dim, k, m = 4096, 256, 5, 8
+    ix, stored, qs, e_all = make_corpus(rlr, oracle, n, dim, seed=4096, nq=m)
+    ix.profile_enable(True)
+    rows = np.arange(n)[::3]
+    f, = make_filters(ix, [rows])
+    try:
+        ix.profile_read(reset=True)
+        scoped = ix.search_topk_scoped(qs, k, [f] * m)
+        ps = ix.profile_read(reset=True)
+        one_r, one_c = ix.search_topk(qs, k, filter=f)
+        pf = ix.profile_read(reset=True)
+        for i, (r, c) in enumerate(scoped):
+            assert np.array_equal(r, one_r[i]) and np.array_equal(bits(c), bits(one_c[i])), i
+        counters = ("n_batches", "n_batch_queries", "n_batch_fallbacks", "n_searches", "n_scan_launches", "n_candidates",
+                    "n_retries", "scan_bytes")
+        assert [getattr(ps, c) for c in counters] == [getattr(pf, c) for c in counters], (ps, pf)
+        assert ps.n_batches == 1 and ps.n_batch_queries == m and ps.n_batch_fallbacks == 0 and ps.n_searches == m, ps
+        assert ps.n_scan_launches == 0 and ps.scan_bytes == len(rows) * dim * 4, ps
+    finally:
+        f.close()
+        ix.close()
+
+
 @pytest.fixture(scope="module")
 def corpus768(rlr, oracle):
     ix, stored, qs, e_all = make_corpus(rlr, oracle, 2397, 768)
