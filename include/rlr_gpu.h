@@ -355,7 +355,7 @@ int32_t rlr_multi_stats(rlr_multi *m, rlr_multi_stats_t *out, int32_t reset);
  * The filter keeps one bit per index row on the device (tail bits of the last word zero), the allowed rows as an
  * ascending list, and their count.  It is immutable and may be shared by any number of concurrent searches; destroying
  * one while a search uses it is the caller's error, as with index mutators.  Every call that changes which rows the
- * index holds (upload, append, delete_rows, fill_synthetic, load_json) makes the filters made before it STALE: every
+ * index holds (upload, append, delete_rows, delete_documents, fill_synthetic, load_json) makes the filters made before it STALE: every
  * filtered call with a stale filter returns RLR_E_INVALID before any GPU work (deletion renumbers rows; a silently
  * stale filter would return other documents).  Without a usable device: RLR_E_NO_DEVICE.
  * rlr_filter_info: any pointer may be null.  *path = how searches with this filter run: 0 = list path (few allowed rows:
@@ -394,6 +394,39 @@ int32_t rlr_search_topk_filtered(rlr_index *idx, const rlr_filter *f, const floa
  * rlr_search_topk_filtered; under profiling scan_bytes grows by the rows of the union. */
 int32_t rlr_search_topk_scoped(rlr_index *idx, const rlr_filter *const *filters, const float *queries, uint32_t n_queries,
                                uint32_t k, float guard_eps, uint64_t *rows_out, float *cos_out, uint32_t *n_out);
+
+/* ---- document column: which document a row belongs to, kept on the device --------------------- */
+/* An optional uint32 per row in HBM (absent, and free, until the first rlr_index_set_documents / rlr_index_tag_rows).
+ * The ids are the host's: the library only compares them.  RLR_DOC_NONE means "no document" and is never matched.
+ *   rlr_index_set_documents  the whole column at once; n must equal the row count (RLR_E_INVALID otherwise)
+ *   rlr_index_tag_rows       rows [first, first + count) := doc (RLR_DOC_NONE untags); a range that leaves the index:
+ *                            RLR_E_RANGE; count == 0 is a no-op
+ *   rlr_index_get_documents  read rows [first, first + count) back; an index without a column reports RLR_DOC_NONE
+ * set_documents and tag_rows are mutator-class (the same external exclusion as append), but they do NOT make filters
+ * stale: a filter is a set of ROWS fixed when it is made, and re-tagging changes no row.  The column follows the rows:
+ * rlr_index_append gives the new rows RLR_DOC_NONE, rlr_index_delete_rows / rlr_index_delete_documents compact it with
+ * the rows, a regrow carries it over; upload, fill_synthetic and load_json replace the rows and drop the column. */
+#define RLR_DOC_NONE 0xFFFFFFFFu
+int32_t rlr_index_set_documents(rlr_index *idx, const uint32_t *doc_of_row, uint64_t n);
+int32_t rlr_index_tag_rows(rlr_index *idx, uint64_t first, uint64_t count, uint32_t doc);
+int32_t rlr_index_get_documents(rlr_index *idx, uint64_t first, uint64_t count, uint32_t *out);
+/* The filter rlr_filter_create_rows makes from {r : doc[r] is one of docs}, built on the device from the column: the
+ * same mask words, the same ascending list, the same count and path.  docs may be unsorted and may repeat; an id that
+ * tags no row contributes nothing; RLR_DOC_NONE among them, or n_docs > 0 with docs null: RLR_E_INVALID.  n_docs == 0
+ * or an index without a column: the empty filter.  Threading and staleness as for the other two creators. */
+int32_t rlr_filter_create_documents(rlr_index *idx, const uint32_t *docs, uint32_t n_docs, rlr_filter **out);
+/* The filter's DEVICE copies of the mask (ceil(index_rows / 64) words) and of the row list (n_allowed entries), copied
+ * back; either pointer may be null.  Test / inspection support. */
+int32_t rlr_filter_read(const rlr_filter *f, uint64_t *mask_words_out, uint32_t *list_out);
+/* rlr_index_delete_rows over {r : doc[r] is one of docs} (the site `chunks.retain(|_, c| c.document_name != filename)`,
+ * rag_engine.rs:347-348), decided on the device: the same stable renumbering, the nomination copies re-synced, filters
+ * made before it stale.  rows_out (cap entries) receives the deleted OLD row numbers in ascending order, *n_deleted
+ * their count -- what the host passes to rlr_lexical_remove_rows and cuts from its own tables.  More than cap rows to
+ * delete: *n_deleted is set, RLR_E_RANGE is returned and NOTHING has changed (call again with room).  Nothing to delete
+ * (no column, n_docs == 0, ids that tag no row): RLR_OK with *n_deleted = 0, and no filter becomes stale.  Argument
+ * rules for docs as for rlr_filter_create_documents.  Mutator-class. */
+int32_t rlr_index_delete_documents(rlr_index *idx, const uint32_t *docs, uint32_t n_docs, uint64_t *rows_out, uint64_t cap,
+                                   uint64_t *n_deleted);
 
 /* ---- coalescing of concurrent single-query searches ----------------------- */
 /* Serve concurrent single-query rlr_search_topk calls on this index from shared passes over the rows.

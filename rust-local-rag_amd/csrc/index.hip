@@ -160,6 +160,10 @@ struct rlr_index {
     uint64_t n_rows = 0;
     uint64_t cap_rows = 0;
     DevBuf<char> d_rows;    // cap_rows x row_bytes
+    DevBuf<uint32_t> d_docs; // optional document column: one id per row (capacity >= cap_rows), RLR_DOC_NONE = no document;
+                             // absent until rlr_index_set_documents / rlr_index_tag_rows
+    uint64_t compact_chunk_rows = 0; // RLR_COMPACT_CHUNK_ROWS: rows per bounce-buffer step of rlr_index_delete_documents
+                                     // (0: as many as fit in 256 MiB); a test forces several steps on a small index with it
     int n_cu = 256;
     int scan_variant = 0;
     int fused_tail = -1;         // select -> re-score -> sort behind the scan in two launches (tail.hip): RLR_TAIL=1 always, 0 never
@@ -421,13 +425,23 @@ int32_t ensure_rows(rlr_index *ix, uint64_t want_rows)
     if (e != hipSuccess)
         return set_error(RLR_E_OOM, "allocation of %llu rows x %zu B failed: %s",
                          static_cast<unsigned long long>(cap), row_bytes(ix), hipGetErrorString(e));
+    DevBuf<uint32_t> nd; // the document column moves with the rows
+    if (ix->d_docs && nd.reserve(cap) != hipSuccess)
+        return set_error(RLR_E_OOM, "allocation of the document column for %llu rows failed", static_cast<unsigned long long>(cap));
     if (ix->d_rows.get() && ix->n_rows) {
         hipError_t ce = hipMemcpy(n.get(), ix->d_rows.get(), ix->n_rows * row_bytes(ix), hipMemcpyDeviceToDevice);
         if (ce == hipSuccess)
             ce = hipStreamSynchronize(nullptr); // a device-to-device copy may return before it has run
+        if (ce == hipSuccess && ix->d_docs) {
+            ce = hipMemcpyAsync(nd.get(), ix->d_docs.get(), ix->n_rows * sizeof(uint32_t), hipMemcpyDeviceToDevice, nullptr);
+            if (ce == hipSuccess)
+                ce = hipStreamSynchronize(nullptr);
+        }
         if (ce != hipSuccess)
             return set_error(RLR_E_HIP, "moving the rows into the larger allocation failed: %s", hipGetErrorString(ce));
     }
+    if (ix->d_docs)
+        ix->d_docs = std::move(nd);
     ix->d_rows = std::move(n); // (frees the old rows)
     ix->cap_rows = cap;
     return RLR_OK;
@@ -2657,6 +2671,83 @@ int32_t filter_create_check(rlr_index *ix, rlr_filter **out)
     return use_device(ix);
 }
 
+// ---- document column (rlr_index_set_documents ... rlr_index_delete_documents; kernels in docs.hip) ------------------
+int32_t docs_entry_check(const rlr_index *ix)
+{
+    if (rlr_device_count() <= 0)
+        return set_error(RLR_E_NO_DEVICE, "no HIP device is visible (this library has no CPU path)");
+    RLR_TRY(check_handle(ix));
+    return use_device(ix);
+}
+
+// the column, created on first use with every row in no document
+int32_t ensure_docs(rlr_index *ix)
+{
+    if (ix->d_docs)
+        return RLR_OK;
+    RLR_HIP(ix->d_docs.reserve(std::max<uint64_t>(std::max<uint64_t>(ix->cap_rows, ix->n_rows), 1)));
+    hipError_t e = launch_docs_fill(ix->d_docs.get(), ix->n_rows, RLR_DOC_NONE, nullptr);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess)
+        ix->d_docs.reset();
+    RLR_HIP(e);
+    return RLR_OK;
+}
+
+// the caller's ids sorted and distinct (what the membership search of docs.hip takes)
+int32_t docs_set(const uint32_t *docs, uint32_t n_docs, std::vector<uint32_t> *set)
+{
+    if (n_docs && !docs)
+        return set_error(RLR_E_INVALID, "docs is null");
+    set->assign(docs, docs + n_docs);
+    std::sort(set->begin(), set->end());
+    set->erase(std::unique(set->begin(), set->end()), set->end());
+    if (!set->empty() && set->back() == RLR_DOC_NONE)
+        return set_error(RLR_E_INVALID, "RLR_DOC_NONE is not a document");
+    return RLR_OK;
+}
+
+// The device side of one "rows of these documents" pass: the uploaded id set and the counts the scan works on,
+// laid out [one count per workgroup of the mask launch | one sum per scan tile | the total].
+struct DocsPass {
+    DevBuf<uint32_t> d_set, d_scan;
+    uint32_t groups = 0, tiles = 0;
+    uint32_t *counts() const { return d_scan.get(); }
+    uint32_t *tile_sums() const { return d_scan.get() + groups; }
+    uint32_t *total() const { return d_scan.get() + groups + tiles; }
+};
+
+// Mark the rows of `set` (non-empty; the index has a column and rows) in d_mask, scan the per-workgroup counts and
+// wait: *n_marked = rows marked; h_mask (nullable) receives the mask words.  The scanned counts stay in `pass` for the
+// scatter launches.
+int32_t docs_mark(rlr_index *ix, hipStream_t s, const std::vector<uint32_t> &set, uint64_t *d_mask, DocsPass *pass,
+                  uint64_t *h_mask, uint32_t *n_marked)
+{
+    const uint32_t N = static_cast<uint32_t>(ix->n_rows);
+    pass->groups = docs_groups(N);
+    pass->tiles = docs_tiles(pass->groups);
+    RLR_HIP(pass->d_set.reserve(set.size()));
+    RLR_HIP(pass->d_scan.reserve(static_cast<size_t>(pass->groups) + pass->tiles + 1));
+    RLR_HIP(hipMemcpyAsync(pass->d_set.get(), set.data(), set.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    RLR_HIP(launch_docs_mask(ix->d_docs.get(), N, pass->d_set.get(), static_cast<uint32_t>(set.size()), d_mask, pass->counts(), s));
+    if (h_mask)
+        RLR_HIP(hipMemcpyAsync(h_mask, d_mask, static_cast<size_t>((N + 63ull) / 64) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    RLR_HIP(launch_docs_scan(pass->counts(), pass->groups, pass->tile_sums(), pass->total(), s));
+    RLR_HIP(hipMemcpyAsync(n_marked, pass->total(), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    RLR_HIP(hipStreamSynchronize(s));
+    return RLR_OK;
+}
+
+// one bounce-buffer step of a deletion on the document column: rows keep[0 .. m) move to [dst_first, dst_first + m)
+hipError_t compact_docs_step(rlr_index *ix, const uint32_t *d_keep, uint64_t m, uint64_t dst_first, uint32_t *d_bounce, hipStream_t s)
+{
+    hipError_t e = launch_docs_gather(ix->d_docs.get(), d_keep, m, d_bounce, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(ix->d_docs.get() + dst_first, d_bounce, m * sizeof(uint32_t), hipMemcpyDeviceToDevice, s);
+    return e;
+}
+
 // ---- coalescer: concurrent single-query calls served from shared passes (rlr_index_set_coalescing) ----------------
 // A caller that finds no coalescer pipeline running and nothing pending runs today's single-query pipeline at once
 // (after linger_us, if set, as the leader of a group others may join meanwhile).  A caller that arrives while one runs
@@ -2904,6 +2995,8 @@ int32_t rlr_index_create(uint32_t dim, int32_t dtype, int32_t device_id, rlr_ind
         ix->hybrid_fetch_full = !strcmp(v, "full");
     if (const char *v = getenv("RLR_BATCH_MIN"))
         ix->batch_min = static_cast<uint32_t>(strtoul(v, nullptr, 0));
+    if (const char *v = getenv("RLR_COMPACT_CHUNK_ROWS"))
+        ix->compact_chunk_rows = strtoull(v, nullptr, 0);
     if (const char *v = getenv("RLR_MAX_CONTEXTS"))
         ix->ctx_cap = static_cast<int>(std::min<long>(std::max<long>(strtol(v, nullptr, 0), 1), 64));
     *out = ix;
@@ -2947,6 +3040,7 @@ int32_t rlr_index_upload(rlr_index *ix, const float *rows, uint64_t n_rows, int3
         return set_error(RLR_E_INVALID, "rows is null");
     RLR_TRY(use_device(ix));
     ix->n_rows = 0;
+    ix->d_docs.reset(); // (new rows: the document column goes with the old ones)
     ix->max_row_sumsq = 1.0f;
     ix->f16_overflow = false;
     RLR_TRY(ensure_rows(ix, n_rows));
@@ -2966,6 +3060,10 @@ int32_t rlr_index_append(rlr_index *ix, const float *rows, uint64_t n_rows, int3
     const uint64_t first = ix->n_rows;
     RLR_TRY(ensure_rows(ix, first + n_rows));
     RLR_TRY(ingest(ix, rows, n_rows, first, normalize_on_device));
+    if (ix->d_docs && n_rows) { // the new rows belong to no document until the host tags them
+        RLR_HIP(launch_docs_fill(ix->d_docs.get() + first, n_rows, RLR_DOC_NONE, nullptr));
+        RLR_HIP(hipStreamSynchronize(nullptr));
+    }
     ix->n_rows = first + n_rows;
     if (first_row_out)
         *first_row_out = first;
@@ -3001,10 +3099,12 @@ int32_t rlr_index_delete_rows(rlr_index *ix, const uint64_t *rows, uint64_t n)
     // [first_dead + i0, first_dead + i1) only overwrite rows below every source still to move.
     const uint64_t chunk = std::max<uint64_t>(1, (256ull << 20) / row_bytes(ix));
     DevBuf<uint8_t> bounce;
-    DevBuf<uint32_t> keep_dev;
+    DevBuf<uint32_t> keep_dev, docs_bounce;
     const uint64_t cr = std::min<uint64_t>(chunk, std::max<size_t>(keep.size(), 1));
     RLR_HIP(bounce.reserve(cr * row_bytes(ix)));
     hipError_t e = keep_dev.reserve(cr);
+    if (e == hipSuccess && ix->d_docs)
+        e = docs_bounce.reserve(cr);
     if (e != hipSuccess)
         return set_error(RLR_E_OOM, "compaction buffer allocation failed");
     void *const d_bounce = bounce.get();
@@ -3018,6 +3118,8 @@ int32_t rlr_index_delete_rows(rlr_index *ix, const uint64_t *rows, uint64_t n)
         if (e == hipSuccess)
             e = hipMemcpyAsync(static_cast<char *>(ix->d_rows.get()) + (first_dead + i0) * row_bytes(ix), d_bounce,
                                m * row_bytes(ix), hipMemcpyDeviceToDevice, nullptr);
+        if (e == hipSuccess && ix->d_docs) // the document column is compacted through the same keep list
+            e = compact_docs_step(ix, d_keep, m, first_dead + i0, docs_bounce.get(), nullptr);
         if (e == hipSuccess)
             e = hipStreamSynchronize(nullptr);
         if (e != hipSuccess)
@@ -3028,6 +3130,127 @@ int32_t rlr_index_delete_rows(rlr_index *ix, const uint64_t *rows, uint64_t n)
         st = sync_image(ix, first_dead);
     }
     return st;
+}
+
+int32_t rlr_index_set_documents(rlr_index *ix, const uint32_t *doc_of_row, uint64_t n)
+{
+    RLR_TRY(docs_entry_check(ix));
+    if (n != ix->n_rows)
+        return set_error(RLR_E_INVALID, "%llu document ids for an index of %llu rows", static_cast<unsigned long long>(n),
+                         static_cast<unsigned long long>(ix->n_rows));
+    if (n == 0)
+        return RLR_OK;
+    if (!doc_of_row)
+        return set_error(RLR_E_INVALID, "doc_of_row is null");
+    RLR_TRY(ensure_docs(ix));
+    RLR_HIP(hipMemcpy(ix->d_docs.get(), doc_of_row, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return RLR_OK;
+}
+
+int32_t rlr_index_tag_rows(rlr_index *ix, uint64_t first, uint64_t count, uint32_t doc)
+{
+    RLR_TRY(docs_entry_check(ix));
+    if (first > ix->n_rows || count > ix->n_rows - first)
+        return set_error(RLR_E_RANGE, "rows [%llu, +%llu) out of range (index holds %llu rows)", static_cast<unsigned long long>(first),
+                         static_cast<unsigned long long>(count), static_cast<unsigned long long>(ix->n_rows));
+    if (count == 0)
+        return RLR_OK;
+    RLR_TRY(ensure_docs(ix));
+    RLR_HIP(launch_docs_fill(ix->d_docs.get() + first, count, doc, nullptr));
+    RLR_HIP(hipStreamSynchronize(nullptr));
+    return RLR_OK;
+}
+
+int32_t rlr_index_get_documents(rlr_index *ix, uint64_t first, uint64_t count, uint32_t *out)
+{
+    RLR_TRY(docs_entry_check(ix));
+    if (first > ix->n_rows || count > ix->n_rows - first)
+        return set_error(RLR_E_RANGE, "rows [%llu, +%llu) out of range (index holds %llu rows)", static_cast<unsigned long long>(first),
+                         static_cast<unsigned long long>(count), static_cast<unsigned long long>(ix->n_rows));
+    if (count == 0)
+        return RLR_OK;
+    if (!out)
+        return set_error(RLR_E_INVALID, "out is null");
+    if (!ix->d_docs) {
+        std::fill(out, out + count, RLR_DOC_NONE);
+        return RLR_OK;
+    }
+    RLR_HIP(hipMemcpy(out, ix->d_docs.get() + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RLR_OK;
+}
+
+int32_t rlr_index_delete_documents(rlr_index *ix, const uint32_t *docs, uint32_t n_docs, uint64_t *rows_out, uint64_t cap,
+                                   uint64_t *n_deleted)
+{
+    if (n_deleted)
+        *n_deleted = 0;
+    RLR_TRY(docs_entry_check(ix));
+    if (!n_deleted)
+        return set_error(RLR_E_INVALID, "n_deleted is null");
+    std::vector<uint32_t> set;
+    RLR_TRY(docs_set(docs, n_docs, &set));
+    if (set.empty() || !ix->d_docs || ix->n_rows == 0)
+        return RLR_OK;
+    const uint64_t N = ix->n_rows;
+    CtxLease lease(ix);
+    RLR_TRY(ctx_acquire(ix, &lease.c));
+    hipStream_t s = lease.c->stream;
+    // phase 1: mark and count
+    DocsPass pass;
+    DevBuf<uint64_t> dead_mask;
+    RLR_HIP(dead_mask.reserve((N + 63) / 64));
+    uint32_t n_dead = 0;
+    RLR_TRY(docs_mark(ix, s, set, dead_mask.get(), &pass, nullptr, &n_dead));
+    *n_deleted = n_dead;
+    if (n_dead == 0)
+        return RLR_OK;
+    if (n_dead > cap)
+        return set_error(RLR_E_RANGE, "%u rows to delete but room for %llu row numbers (nothing was changed)", n_dead,
+                         static_cast<unsigned long long>(cap));
+    if (!rows_out)
+        return set_error(RLR_E_INVALID, "rows_out is null");
+    // phase 2: the dead list (the size of a document) comes back; the keep list stays on the device
+    DevBuf<uint32_t> dead_list;
+    RLR_HIP(dead_list.reserve(n_dead));
+    RLR_HIP(launch_docs_scatter(dead_mask.get(), static_cast<uint32_t>(N), pass.counts(), pass.tile_sums(), 0, 0, dead_list.get(), s));
+    std::vector<uint32_t> h_dead(n_dead);
+    RLR_HIP(hipMemcpyAsync(h_dead.data(), dead_list.get(), n_dead * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    RLR_HIP(hipStreamSynchronize(s));
+    const uint64_t first_dead = h_dead[0], n_keep = N - first_dead - n_dead;
+    const uint64_t chunk = ix->compact_chunk_rows ? ix->compact_chunk_rows : std::max<uint64_t>(1, (256ull << 20) / row_bytes(ix));
+    const uint64_t cr = std::min<uint64_t>(chunk, std::max<uint64_t>(n_keep, 1));
+    DevBuf<uint32_t> keep, docs_bounce;
+    DevBuf<uint8_t> bounce;
+    hipError_t e = keep.reserve(std::max<uint64_t>(n_keep, 1));
+    if (e == hipSuccess)
+        e = bounce.reserve(cr * row_bytes(ix));
+    if (e == hipSuccess)
+        e = docs_bounce.reserve(cr);
+    if (e != hipSuccess)
+        return set_error(RLR_E_OOM, "compaction buffer allocation failed");
+    for (uint32_t i = 0; i < n_dead; ++i)
+        rows_out[i] = h_dead[i];
+    ix->mutations.fetch_add(1, std::memory_order_acq_rel); // (deletion renumbers rows: a filter made before it names other rows now)
+    if (n_keep)
+        e = launch_docs_scatter(dead_mask.get(), static_cast<uint32_t>(N), pass.counts(), pass.tile_sums(), 1,
+                                static_cast<uint32_t>(first_dead), keep.get(), s);
+    // stable in-place compaction through a bounce buffer, as in rlr_index_delete_rows: destination rows
+    // [first_dead + i0, first_dead + i1) only overwrite rows below every source still to move.  One stream orders the steps.
+    for (uint64_t i0 = 0; i0 < n_keep && e == hipSuccess; i0 += cr) {
+        const uint64_t m = std::min<uint64_t>(cr, n_keep - i0);
+        e = launch_compact_rows(ix->d_rows.get(), bounce.get(), ix->pitch16, keep.get() + i0, static_cast<uint32_t>(m), s);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(static_cast<char *>(ix->d_rows.get()) + (first_dead + i0) * row_bytes(ix), bounce.get(),
+                               m * row_bytes(ix), hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess)
+            e = compact_docs_step(ix, keep.get() + i0, m, first_dead + i0, docs_bounce.get(), s);
+    }
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    if (e != hipSuccess)
+        return set_error(RLR_E_HIP, "row compaction failed: %s", hipGetErrorString(e));
+    ix->n_rows = first_dead + n_keep;
+    return sync_image(ix, first_dead);
 }
 
 int32_t rlr_index_enable_batch_image(rlr_index *ix, int32_t enable)
@@ -3073,6 +3296,7 @@ int32_t rlr_index_fill_synthetic(rlr_index *ix, uint64_t n_rows, uint64_t row0, 
     ix->mutations.fetch_add(1, std::memory_order_acq_rel); // (row filters made before this call are stale from here on)
     RLR_TRY(use_device(ix));
     ix->n_rows = 0;
+    ix->d_docs.reset(); // (new rows: the document column goes with the old ones)
     RLR_TRY(ensure_rows(ix, n_rows));
     const uint64_t chunk = 1ull << 20;
     DevBuf<float> norm;
@@ -3158,6 +3382,57 @@ int32_t rlr_filter_create_ranges(rlr_index *ix, const uint64_t *first, const uin
         }
     }
     return filter_finish(ix, std::move(mask), out);
+}
+
+int32_t rlr_filter_create_documents(rlr_index *ix, const uint32_t *docs, uint32_t n_docs, rlr_filter **out)
+{
+    RLR_TRY(filter_create_check(ix, out));
+    std::vector<uint32_t> set;
+    RLR_TRY(docs_set(docs, n_docs, &set));
+    const size_t words = (ix->n_rows + 63) / 64;
+    if (set.empty() || !ix->d_docs || ix->n_rows == 0) // no document names a row: the empty filter
+        return filter_finish(ix, std::vector<uint64_t>(words, 0), out);
+    std::unique_ptr<rlr_filter> f(new (std::nothrow) rlr_filter());
+    if (!f)
+        return set_error(RLR_E_OOM, "host allocation failed");
+    f->ix = ix;
+    f->index_rows = ix->n_rows;
+    f->mutations = ix->mutations.load(std::memory_order_acquire);
+    f->h_mask.resize(words);
+    RLR_HIP(f->d_mask.reserve(words));
+    CtxLease lease(ix);
+    RLR_TRY(ctx_acquire(ix, &lease.c));
+    hipStream_t s = lease.c->stream;
+    // mask words and their count on the device, the mask copied to h_mask as well (the host-side checks read it); the
+    // row list is scattered on the device and never built on the host
+    DocsPass pass;
+    uint32_t n_allowed = 0;
+    RLR_TRY(docs_mark(ix, s, set, f->d_mask.get(), &pass, f->h_mask.data(), &n_allowed));
+    f->n_allowed = n_allowed;
+    f->path = f->n_allowed < kFilterListMax ? 0 : 1;
+    RLR_HIP(f->d_list.reserve(std::max<size_t>(n_allowed, 1)));
+    if (n_allowed) {
+        RLR_HIP(launch_docs_scatter(f->d_mask.get(), static_cast<uint32_t>(ix->n_rows), pass.counts(), pass.tile_sums(), 0, 0,
+                                    f->d_list.get(), s));
+        RLR_HIP(hipStreamSynchronize(s)); // (the searches that read the list run on other, non-blocking streams)
+    }
+    *out = f.release();
+    return RLR_OK;
+}
+
+int32_t rlr_filter_read(const rlr_filter *f, uint64_t *mask_words_out, uint32_t *list_out)
+{
+    if (rlr_device_count() <= 0)
+        return set_error(RLR_E_NO_DEVICE, "no HIP device is visible (this library has no CPU path)");
+    if (!f)
+        return set_error(RLR_E_INVALID, "null filter handle");
+    RLR_TRY(use_device(f->ix));
+    const size_t words = (f->index_rows + 63) / 64;
+    if (mask_words_out && words)
+        RLR_HIP(hipMemcpy(mask_words_out, f->d_mask.get(), words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (list_out && f->n_allowed)
+        RLR_HIP(hipMemcpy(list_out, f->d_list.get(), f->n_allowed * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RLR_OK;
 }
 
 int32_t rlr_filter_destroy(rlr_filter *f)

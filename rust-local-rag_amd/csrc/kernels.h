@@ -233,4 +233,27 @@ hipError_t launch_q8_scan(const void *q8, const float *scale, uint32_t n_rows, u
                           float *scores, uint32_t *hist, int n_cu, hipStream_t s);
 float q8_arith_eps(uint32_t dim, float scale_max, float q_norm);
 
+// ---- docs.hip : the per-row document column -> filter mask / row list / keep list, on the device ----
+constexpr uint32_t kDocsRowsPerGroup = 4096; // rows (64 mask words) one workgroup of the mask / scatter launches covers
+constexpr uint32_t kDocsSumsPerGroup = 1024; // per-workgroup counts one workgroup of the scan launches covers
+// The membership switch: up to this many distinct document ids are staged in LDS (8 KiB: a workgroup's 4096 rows then
+// cost 12 LDS probes each and the set is read from global memory once per workgroup); a larger set is binary-searched
+// where it lies (global memory, L2-resident).
+constexpr uint32_t kDocsLdsMax = 2048;
+uint32_t docs_groups(uint32_t n_rows);  // workgroups (= counts) of the mask launch
+uint32_t docs_tiles(uint32_t n_groups); // workgroups (= tile sums) of the first scan launch
+// mask[w] bit b = (col[64 w + b] is one of the n_docs sorted, distinct ids at `docs`), tail bits zero; counts[g] = set
+// bits of workgroup g's words.  n_rows, n_docs >= 1; RLR_DOC_NONE is never a member.
+hipError_t launch_docs_mask(const uint32_t *col, uint32_t n_rows, const uint32_t *docs, uint32_t n_docs, uint64_t *mask,
+                            uint32_t *counts, hipStream_t s);
+// counts[0 .. n_groups) -> exclusive scan within tiles of kDocsSumsPerGroup, tile_sums[0 .. docs_tiles) -> exclusive
+// scan of the tiles' sums (untouched for one tile), *total = the sum of all counts
+hipError_t launch_docs_scan(uint32_t *counts, uint32_t n_groups, uint32_t *tile_sums, uint32_t *total, hipStream_t s);
+// the rows of the set bits in ascending order -> list; invert != 0: the rows >= first_row (= the first set bit's row)
+// with a CLEAR bit instead, i.e. the keep list of a deletion from its first dead row on
+hipError_t launch_docs_scatter(const uint64_t *mask, uint32_t n_rows, const uint32_t *offsets, const uint32_t *tile_offsets,
+                               int invert, uint32_t first_row, uint32_t *list, hipStream_t s);
+hipError_t launch_docs_fill(uint32_t *col, uint64_t n, uint32_t doc, hipStream_t s);                               // col[i] = doc
+hipError_t launch_docs_gather(const uint32_t *col, const uint32_t *keep, uint64_t n, uint32_t *out, hipStream_t s); // out[i] = col[keep[i]]
+
 } // namespace rlr

@@ -14,6 +14,7 @@ reference obtains it from Ollama, embeddings.rs:91-102), BM25 candidates
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 import uuid
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -158,6 +159,11 @@ class RagEngine:
         self._chunks: List[DocumentChunk] = []       # row -> chunk
         self._row_of: Dict[str, int] = {}            # chunk_id -> row
         self._filters: Dict[frozenset, RowFilter] = {}  # documents -> their rows as a filter; dropped by every mutation
+        self._doc_ids: Dict[str, int] = {}           # document name -> its id in the index's document column
+        self._tagged: Optional[list] = None          # the chunk table the column was last made to agree with ...
+        self._tagged_len = 0                         # ... and its length then (see _sync_documents)
+
+    _next_doc_id = itertools.count()                 # shared by every engine: an id is never reused within a process
 
     def close(self) -> None:
         self._drop_filters()
@@ -178,9 +184,25 @@ class RagEngine:
             self._drop_filters()
             f = None
         if f is None:
-            f = self.index.filter_ranges(document_ranges(self._chunks, key))
+            self._sync_documents()
+            f = self.index.filter_documents([self._doc_ids[d] for d in key if d in self._doc_ids])  # built on the device
             self._filters[key] = f
         return f
+
+    def _doc_id(self, document_name: str) -> int:
+        doc = self._doc_ids.get(document_name)
+        if doc is None:
+            doc = self._doc_ids[document_name] = next(RagEngine._next_doc_id)
+        return doc
+
+    def _sync_documents(self) -> None:
+        """The index's document column names the document of every row.  add_document / remove_document keep it so; a
+        chunk table that was replaced as a whole (load_from_disk, a synthetic corpus) is tagged here, in one call."""
+        if self._tagged is self._chunks and self._tagged_len == len(self._chunks):
+            return
+        ids = np.fromiter((self._doc_id(ch.document_name) for ch in self._chunks), dtype=np.uint32, count=len(self._chunks))
+        self.index.set_documents(ids)
+        self._tagged, self._tagged_len = self._chunks, len(self._chunks)
 
     # -- index mutation (sites rag_engine.rs:347-348, :358-384) --------------------------
     def add_document(self, document_name: str, texts: Sequence[str], embeddings, pages: Optional[Sequence[int]] = None,
@@ -197,19 +219,46 @@ class RagEngine:
             self._row_of[cid] = first + i
             self.lexical.add_chunk(first + i, text)   # lexical_index.add_chunk(&chunk.id, &chunk.text) :382
             ids.append(cid)
+        self.index.tag_rows(first, len(texts), self._doc_id(document_name))  # (append left them in no document)
+        self._tagged_len = len(self._chunks)
         self._drop_filters()
         return ids
 
     def remove_document(self, document_name: str) -> int:
-        dead = [r for r, ch in enumerate(self._chunks) if ch.document_name == document_name]
-        if dead:
+        self._sync_documents()
+        doc = self._doc_ids.get(document_name)
+        if doc is None:
+            return 0
+        # chunks.retain(|_, c| c.document_name != filename): which rows go is decided on the device from the column
+        dead = self.index.delete_documents([doc])
+        if dead.size:
             self._drop_filters()
-            self.index.delete_rows(dead)  # chunks.retain(|_, c| c.document_name != filename)
             self.lexical.remove_rows(dead)
-            dead_set = set(dead)
-            self._chunks = [ch for r, ch in enumerate(self._chunks) if r not in dead_set]
-            self._row_of = {ch.id: r for r, ch in enumerate(self._chunks)}
-        return len(dead)
+            self._cut_rows(dead.astype(np.int64))
+            self._tagged, self._tagged_len = self._chunks, len(self._chunks)
+        return int(dead.size)
+
+    def _cut_rows(self, dead: np.ndarray) -> None:
+        """Cut the (ascending) rows `dead` out of the row -> chunk table and renumber chunk_id -> row, as the index's
+        stable compaction renumbered the rows: whole runs of surviving chunks are copied as slices, and only the rows
+        from the first dead one on get a new number."""
+        old, first = self._chunks, int(dead[0])
+        complete = len(self._row_of) == len(old)        # (a planted table may come without its ids: rebuild them all)
+        edges = np.flatnonzero(np.diff(dead) != 1)
+        starts, ends = dead[np.r_[0, edges + 1]], dead[np.r_[edges, dead.size - 1]] + 1   # the dead runs [start, end)
+        if complete:
+            for a, b in zip(starts, ends):
+                for ch in old[a:b]:
+                    self._row_of.pop(ch.id, None)
+        new = old[:first]
+        for end, nxt in zip(ends, np.r_[starts[1:], len(old)]):
+            new += old[end:nxt]
+        self._chunks = new
+        if complete:
+            for r in range(first, len(new)):
+                self._row_of[new[r].id] = r
+        else:
+            self._row_of = {ch.id: r for r, ch in enumerate(new)}
 
     def __len__(self) -> int:
         return len(self._chunks)

@@ -17,6 +17,17 @@ def _u64(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.uint64)
 
 
+DOC_NONE = 0xFFFFFFFF  # RLR_DOC_NONE: a row that belongs to no document
+
+
+def _u32(a) -> np.ndarray:
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def _u32ptr(a: np.ndarray):
+    return a.ctypes.data_as(N.u32p)
+
+
 def _fp(a: np.ndarray):
     return a.ctypes.data_as(N.f32p)
 
@@ -72,6 +83,15 @@ class RowFilter:
         N.check(self._L.rlr_filter_info(self._h, C.byref(rows), C.byref(allowed), C.byref(path), C.byref(stale)))
         return {"index_rows": int(rows.value), "n_allowed": int(allowed.value), "path": ("list", "scan")[path.value],
                 "stale": bool(stale.value)}
+
+    def read(self):
+        """the filter's DEVICE copies, copied back: (mask u64 [ceil(index_rows / 64)], list u32 [n_allowed])"""
+        info = self.info()
+        mask = np.zeros((info["index_rows"] + 63) // 64, dtype=np.uint64)
+        rows = np.zeros(info["n_allowed"], dtype=np.uint32)
+        N.check(self._L.rlr_filter_read(self._h, _up(mask) if mask.size else None,
+                                        rows.ctypes.data_as(N.u32p) if rows.size else None))
+        return mask, rows
 
     def set_path(self, path: str) -> None:
         """measurement hook (tools/bench_filtered.py): "list" or "scan" from now on; results do not depend on it"""
@@ -180,6 +200,46 @@ class GpuIndex:
         N.check(self._L.rlr_filter_create_ranges(self._h, _up(first) if r.shape[0] else None,
                                                  _up(count) if r.shape[0] else None, r.shape[0], C.byref(h)))
         return RowFilter(self, h)
+
+    # -- document column ---------------------------------------------------------
+    def set_documents(self, doc_of_row) -> None:
+        """the whole column at once: one uint32 document id per row (DOC_NONE: no document)"""
+        d = _u32(doc_of_row).ravel()
+        N.check(self._L.rlr_index_set_documents(self._h, _u32ptr(d) if d.size else None, d.size))
+
+    def tag_rows(self, first: int, count: int, doc: int) -> None:
+        """rows [first, first + count) belong to document `doc` from now on"""
+        N.check(self._L.rlr_index_tag_rows(self._h, first, count, doc))
+
+    def get_documents(self, first: int = 0, count: "int | None" = None) -> np.ndarray:
+        """the document ids of rows [first, first + count) (to the end by default); DOC_NONE everywhere before any tag"""
+        if count is None:
+            count = len(self) - first
+        out = np.zeros(max(count, 0), dtype=np.uint32)
+        N.check(self._L.rlr_index_get_documents(self._h, first, count, _u32ptr(out) if out.size else None))
+        return out
+
+    def filter_documents(self, docs) -> RowFilter:
+        """every row tagged with one of these document ids as a RowFilter, built on the device from the column"""
+        d = _u32(docs).ravel()
+        h = C.c_void_p()
+        N.check(self._L.rlr_filter_create_documents(self._h, _u32ptr(d) if d.size else None, d.size, C.byref(h)))
+        return RowFilter(self, h)
+
+    def delete_documents(self, docs) -> np.ndarray:
+        """delete every row tagged with one of these document ids (stable compaction, as delete_rows) -> the deleted
+        OLD row numbers, ascending"""
+        d = _u32(docs).ravel()
+        dp = _u32ptr(d) if d.size else None
+        cap, n = 4096, C.c_uint64()
+        rows = np.zeros(cap, dtype=np.uint64)
+        st = self._L.rlr_index_delete_documents(self._h, dp, d.size, _up(rows), cap, C.byref(n))
+        if st == N.RLR_E_RANGE and n.value > cap:  # (nothing was changed: again with room for every row number)
+            cap = int(n.value)
+            rows = np.zeros(cap, dtype=np.uint64)
+            st = self._L.rlr_index_delete_documents(self._h, dp, d.size, _up(rows), cap, C.byref(n))
+        N.check(st)
+        return rows[:int(n.value)].copy()
 
     # -- hot path ------------------------------------------------------------
     def search_topk(self, queries, k: int, guard_eps: float = -1.0, filter: "RowFilter | None" = None):

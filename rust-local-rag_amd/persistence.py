@@ -188,6 +188,7 @@ def _apply_loaded_state(engine: RagEngine, state: dict, rows: np.ndarray, source
     engine.index.upload(rows, normalize=True)
     engine._chunks = metas
     engine._row_of = {ch.id: r for r, ch in enumerate(metas)}
+    engine._sync_documents()  # the whole document column in one call
     # validate_index_sync (:1378-1388): every chunk is (re-)added to the lexical index
     engine.lexical.clear()
     for r, ch in enumerate(metas):
@@ -267,6 +268,7 @@ def _load_sidecar(engine: RagEngine, data_dir: str, model_name: str) -> Optional
     engine.index.upload(rows.reshape(n, engine.dim), normalize=False)   # already the post-load rows
     engine._chunks = [DocumentChunk(*c) for c in header["chunks"]]
     engine._row_of = {ch.id: r for r, ch in enumerate(engine._chunks)}
+    engine._sync_documents()  # the whole document column in one call
     engine.lexical.clear()
     for r, ch in enumerate(engine._chunks):
         engine.lexical.add_chunk(r, ch.text)
