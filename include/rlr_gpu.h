@@ -203,19 +203,26 @@ int32_t rlr_search_diverse(rlr_index *idx, const float *query, uint32_t pool, ui
  * `lexical_index.score(query, top_k * 5)`, then combined = w_e*cos + w_l*(lex / max_lex) over every chunk, order
  * (combined desc, row asc), cut to `need`), optionally followed by mmr_diversify (:756) -- scan -> select -> re-score ->
  * cosines of the lexical rows -> blend + order + cut -> [Gram -> greedy] -> results in pinned memory, one
- * synchronisation.  Candidates are the need + n_lex + 8 best rows by cosine united with the lexical rows: a row
- * without a lexical score is ordered by its cosine alone, so nothing else can reach the first `need`.
+ * synchronisation.  Candidates are the `fetch` best rows by cosine united with the lexical rows, with
+ *   fetch = min(N, need + n_lex + 8, need + 32)   by default (kHybridFetchMargin = 32), and
+ *   fetch = min(N, need + n_lex + 8)              for an index created under RLR_HYBRID_FETCH=full.
+ * A row without a lexical score is ordered by its cosine alone, so with need + n_lex + 8 rows nothing else can reach the
+ * first `need`; the shorter default fetch can leave the order undecided where fetched lexical rows fall behind, and the
+ * boundary rule then reports it (*fallback = 2) instead of guessing.  -0 and +0 combined scores tie (the row decides), NaN
+ * orders last.
  *   need         candidates the search keeps: min(top_k, 3*top_k) for a plain search (:544, :667-698), the pool
  *                max(3*top_k, top_k+10) under diversification (:734); <= 1024
  *   diversify    0: return the first `need` candidates in order (search); != 0: MMR-select k of them with `lambda`
  *   lex_rows / lex_scores   the BM25 pairs as rows: ascending, unique, inside the index; n_lex <= 2048 and
- *                need + 2*n_lex + 8 <= 4096
+ *                need + 2*n_lex + 8 <= 4096 (whatever the fetch mode).  The second limit binds first: the largest n_lex
+ *                this entry admits is 2043 (need = 1), 1532 at need = 1024 -- n_lex = 2048 is not reachable here.
  *   max_lex      max(lexical scores, f32::EPSILON) as the reference computes it (:515-519)
  *   rows_out / cos_out / score_out / lex_out   `need` entries (diversify: min(max(k,1), need)): row, embedding_score,
  *                combined score, normalised lexical score (0 for rows without one)
  *   *fallback    != 0: nothing was written, take the host path (same conditions as rlr_search_diverse, or sizes
  *                outside the limits above).
- * Results are identical to the host path of csrc/engine.cpp (tests: test_engine_hybrid_*, fuzz_engine). */
+ * Results are identical to the host path of csrc/engine.cpp (tests: test_engine_hybrid_*, fuzz_engine; every branch of
+ * the blend on designed rows, with the status each case must report: tests/test_gpu_pool.py). */
 int32_t rlr_search_hybrid(rlr_index *idx, const float *query, uint32_t need, uint32_t k, float lambda, int32_t diversify,
                           float w_embedding, float w_lexical, const uint64_t *lex_rows, const float *lex_scores,
                           uint32_t n_lex, float max_lex, float guard_eps, uint64_t *rows_out, float *cos_out,

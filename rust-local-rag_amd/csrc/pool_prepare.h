@@ -4,10 +4,10 @@
 // The device twin of the host code between `search` and `mmr_diversify` (csrc/engine.cpp: search_impl's candidate
 // list + rlr_engine_search_with_diversity; /root/reference/src/rag_engine.rs:531-532, :544, :734): the `fetch` best rows
 // by cosine become candidates with combined = w_e * cos + w_l * 0 (two rounded products, one add), ordered (combined
-// desc, NaN last, row asc) -- distinct cosines can round to one combined score, so this is NOT always the cosine order
-// -- cut to the first `need`.  If such a rounding tie chain reaches the last fetched row while rows remain unfetched
-// the order cannot be decided from this fetch: info[1] = 2 and the host takes the widening two-call path, exactly as
-// search_impl does.
+// desc, NaN last, row asc; -0 ties with +0 as in the host's float comparison) -- distinct cosines can round to
+// one combined score, so this is NOT always the cosine order -- cut to the first `need`.  If such a rounding tie
+// chain reaches the last fetched row while rows remain unfetched the order cannot be decided from this fetch:
+// info[1] = 2 and the host takes the widening two-call path, exactly as search_impl does.
 //   info[0] = pool size, info[1] = status (0 ok, 1 guard-band overflow upstream, 2 boundary tie)
 // Shared by index.hip (the stand-alone launch behind sort_emit / the split pipeline) and tail.hip (the fused tail's
 // finish: the workgroup that holds all re-scored candidates builds the pool in the same launch).
@@ -63,7 +63,9 @@ __device__ inline void pool_prepare_body(const uint64_t *packed, uint32_t n_raw,
             const float t0 = pa.w_e * e;
             const float t1 = pa.w_l * 0.0f;
             c = t0 + t1;
-            mine = (static_cast<uint64_t>(score_key(c)) << 32) | (p & 0xFFFFFFFFull); // unique: the row is part of the key
+            // unique: the row is part of the key; -0 ties with +0 as in the host's float comparison (the stored
+            // score keeps its sign)
+            mine = (static_cast<uint64_t>(score_key(c == 0.0f ? 0.0f : c)) << 32) | (p & 0xFFFFFFFFull);
             s_key[t] = mine;
         }
         __syncthreads();
@@ -111,7 +113,8 @@ __device__ inline void pool_prepare_body(const uint64_t *packed, uint32_t n_raw,
             const float c = t0 + t1;
             s_c[i] = c;
             s_e[i] = e;
-            key = (static_cast<uint64_t>(score_key(c)) << 32) | (p & 0xFFFFFFFFull);
+            // -0 ties with +0
+            key = (static_cast<uint64_t>(score_key(c == 0.0f ? 0.0f : c)) << 32) | (p & 0xFFFFFFFFull);
             atomicAdd(&s_got, 1u);
         }
         s_key[i] = key;
