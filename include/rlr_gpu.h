@@ -435,6 +435,29 @@ int32_t rlr_filter_read(const rlr_filter *f, uint64_t *mask_words_out, uint32_t 
 int32_t rlr_index_delete_documents(rlr_index *idx, const uint32_t *docs, uint32_t n_docs, uint64_t *rows_out, uint64_t cap,
                                    uint64_t *n_deleted);
 
+/* ---- grouped top-k: at most per_doc results from any one document ----------- */
+/* For one query over the allowed rows (all rows, or the rows of f): take them in the library's result order (reference-
+ * order dot product descending, row ascending, NaN last), walk that order, accept a row unless per_doc rows of its group
+ * are already accepted, stop at k accepted rows.  The group of a row is its document id; a row tagged RLR_DOC_NONE --
+ * and every row of an index without a column -- is a group of its own and is never capped.  Equivalently: the top k of
+ * the union of every group's top per_doc rows.  per_doc = 1 ranks documents by their best chunk.  Scores are bit-identical
+ * to rlr_score_rows; n_out[q] may be smaller than k when the groups run out.
+ *   k == 0, per_doc outside 1..RLR_MAX_PER_DOCUMENT: RLR_E_INVALID.  f may be null; filter rules (stale filters, another
+ *   index' filter) as for rlr_search_topk_filtered; an empty filter: RLR_OK with n_out = 0.
+ *   Results of query q start at q * k in rows_out / cos_out / docs_out; docs_out (may be null) receives each result row's
+ *   document id.
+ * Queries run one by one over the master rows: no coalescer, no nomination copy, no shared pass.  The selection runs on
+ * the device behind the scan (DESIGN.md "Grouped top-k"); what it cannot decide it hands to an exact form (reference-order
+ * scores of every allowed row, the walk on the host), never silently: */
+#define RLR_MAX_PER_DOCUMENT 8
+int32_t rlr_search_topk_grouped(rlr_index *idx, const rlr_filter *f, const float *queries, uint32_t n_queries, uint32_t k,
+                                uint32_t per_doc, float guard_eps, uint64_t *rows_out, float *cos_out, uint32_t *docs_out,
+                                uint32_t *n_out);
+/* Queries served by each form since the last reset: [0] selected on the device; exact form taken [1] on candidate
+ * overflow, [2] because rows with NaN nominations were needed to fill k or a masked row came back, [3] by rule (a
+ * list-path filter, k beyond the device finish, rows too wide for the staged re-score).  counts may be null. */
+int32_t rlr_index_grouped_forms(rlr_index *idx, uint64_t counts[4], int32_t reset);
+
 /* ---- coalescing of concurrent single-query searches ----------------------- */
 /* Serve concurrent single-query rlr_search_topk calls on this index from shared passes over the rows.
  * max_group 0 or 1: off (the default).  2..8: at most this many queries share one pass.

@@ -155,6 +155,8 @@ PROTOTYPES = [
     ("rlr_filter_create_documents", C.c_int32, [_H, u32p, C.c_uint32, C.POINTER(_H)]),
     ("rlr_filter_read", C.c_int32, [_H, u64p, u32p]),
     ("rlr_index_delete_documents", C.c_int32, [_H, u32p, C.c_uint32, u64p, C.c_uint64, u64p]),
+    ("rlr_search_topk_grouped", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, u64p, f32p, u32p, u32p]),
+    ("rlr_index_grouped_forms", C.c_int32, [_H, u64p, C.c_int32]),
     ("rlr_index_set_coalescing", C.c_int32, [_H, C.c_uint32, C.c_uint32]),
     ("rlr_index_coalesce_stats", C.c_int32, [_H, C.POINTER(CoalesceStatsC), C.c_int32]),
     ("rlr_profile_enable", C.c_int32, [_H, C.c_int32]),

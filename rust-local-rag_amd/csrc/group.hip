@@ -1,0 +1,491 @@
+// group.hip -- the tail of a grouped search (include/rlr_gpu.h, "Grouped top-k"): the best k rows with at most per_doc
+// of any one document, selected on the device from the nominated scores the scan left and the document column.
+//
+// With a = nominated score, e = reference-order score, |a - e| <= eps (DESIGN.md "Grouped top-k" has the proof):
+//   rounds     j = 1..per_doc, one launch each: every document's j-th largest packed key (score key << 32 | ~row) by a
+//              64-bit atomicMax into an open-addressing table keyed by document id, over the keys strictly below its
+//              (j-1)-th.  Integer maxima: the table is the same whatever order the workgroups run in.  Runs of equal ids
+//              inside a wave are reduced first, so a document of consecutive rows costs one atomic per wave.
+//   heads      t_g (the per_doc-th value, 0 for a smaller group) per row, and the digit-1 histogram of the heads: the
+//              rows among their group's best per_doc by nomination (every untagged row is one).
+//   refine     digit 2 of the heads inside the bin of the k-th head.
+//   collect    rows with a >= max(t_g, U) - 2 eps, U = the floor of the k-th head's 22-bit bin; each workgroup re-scores
+//              what it found in reference order (staged_dot.h).
+//   finish     one workgroup: exact order, rank inside the group, accept below per_doc, emit the first k.
+// An order between workgroups comes from the order of launches on one stream, never from a flag (the rule of tail.hip);
+// inside a launch the table is only touched by atomics, between launches by plain loads.
+#include "../../include/rlr_gpu.h"
+#include "common.h"
+#include "kernels.h"
+#include "select_dev.h"
+#include "sort_emit.h"
+#include "staged_dot.h"
+
+#include <algorithm>
+
+namespace rlr {
+
+namespace {
+
+constexpr uint32_t kGroupBlock = 256;
+constexpr uint32_t kGroupLocalCap = 1024; // candidates one workgroup keeps for its own re-score
+constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
+static_assert(kGroupBlock == kSelThreads, "find_rank_bin is written for 256 threads");
+
+struct GroupDev {
+    const float *scores;
+    const uint32_t *docs;
+    uint32_t n, k, per_doc;
+    float two_eps;
+    uint32_t *tab_keys;
+    uint64_t *tab_vals;
+    uint32_t tab_bits;
+    uint64_t *tg;
+    uint32_t *hist;
+    GroupState *st;
+    const float4 *rows;
+    uint32_t pitch16, dim;
+    const float *query;
+    uint64_t *cand;
+    uint32_t *cand_doc;
+    uint64_t *out;
+    uint64_t *meta;
+    uint32_t *ctx_hist;
+    uint32_t cpb;
+};
+
+__device__ inline uint32_t group_hash(uint32_t id, uint32_t bits)
+{
+    return (id * 0x9E3779B1u) >> (32u - bits); // multiplicative: ids that differ in any bit spread over the table
+}
+
+// the slot of `id`, claimed if it has none yet (launches that insert touch the keys with atomics only)
+__device__ inline uint32_t group_insert(uint32_t *keys, uint32_t bits, uint32_t id)
+{
+    const uint32_t mask = (1u << bits) - 1u;
+    uint32_t h = group_hash(id, bits);
+    for (uint32_t probes = 0; probes <= mask; ++probes) {
+        // (an agent-scope load first: the rows of a large document find its slot without a read-modify-write on one address)
+        uint32_t old = __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (old == RLR_DOC_NONE)
+            old = atomicCAS(&keys[h], RLR_DOC_NONE, id);
+        if (old == RLR_DOC_NONE || old == id)
+            return h;
+        h = (h + 1u) & mask;
+    }
+    return kNoSlot;
+}
+
+// the slot of `id` in a table no launch is inserting into, kNoSlot if it has none
+__device__ inline uint32_t group_find(const uint32_t *keys, uint32_t bits, uint32_t id)
+{
+    const uint32_t mask = (1u << bits) - 1u;
+    uint32_t h = group_hash(id, bits);
+    for (uint32_t probes = 0; probes <= mask; ++probes) {
+        const uint32_t key = keys[h];
+        if (key == id)
+            return h;
+        if (key == RLR_DOC_NONE)
+            return kNoSlot;
+        h = (h + 1u) & mask;
+    }
+    return kNoSlot;
+}
+
+__device__ inline uint64_t shfl_up_u64(uint64_t v, uint32_t d)
+{
+    const uint32_t lo = __shfl_up(static_cast<uint32_t>(v), d, 64), hi = __shfl_up(static_cast<uint32_t>(v >> 32), d, 64);
+    return (static_cast<uint64_t>(hi) << 32) | lo;
+}
+
+__global__ __launch_bounds__(kGroupBlock) void group_clear_kernel(GroupDev a)
+{
+    const uint32_t stride = gridDim.x * kGroupBlock, t0 = blockIdx.x * kGroupBlock + threadIdx.x;
+    const uint32_t slots = a.docs ? 1u << a.tab_bits : 0u;
+    for (uint32_t i = t0; i < slots; i += stride)
+        a.tab_keys[i] = RLR_DOC_NONE;
+    const uint64_t n_vals = static_cast<uint64_t>(slots) * a.per_doc;
+    for (uint64_t i = t0; i < n_vals; i += stride)
+        a.tab_vals[i] = 0ull;
+    for (uint32_t i = t0; i < 2u * kHistBins; i += stride)
+        a.hist[i] = 0u;
+    if (t0 == 0) {
+        a.st->n_cand = 0;
+        a.st->n_valid = 0;
+        a.st->flags = 0;
+        a.st->pad = 0;
+    }
+}
+
+// Round j (0-based): tab_vals[slot][j] = the largest packed key of the slot's document below tab_vals[slot][j - 1].
+// A wave takes 64 consecutive rows at a time; lanes of one run of equal ids combine their keys by a segmented maximum
+// and the last lane of the run issues the one atomic.  (A lane that meets an equal id beyond its run's start only adds
+// keys of the same document: still that document's maximum.)
+template <bool FIRST>
+__global__ __launch_bounds__(kGroupBlock) void group_round_kernel(GroupDev a, uint32_t j)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t n_words = a.n / 64 + ((a.n & 63) != 0 ? 1u : 0u);
+    const uint32_t waves = gridDim.x * (kGroupBlock / 64);
+    for (uint64_t w = blockIdx.x * (kGroupBlock / 64) + (threadIdx.x >> 6); w < n_words; w += waves) { // (wave-uniform)
+        const uint64_t row = w * 64 + lane;
+        const bool in = row < a.n;
+        const uint32_t id = in ? a.docs[row] : RLR_DOC_NONE;
+        const uint32_t key = in ? score_key(a.scores[row]) : 0u;
+        const bool act = id != RLR_DOC_NONE && key != 0u;
+        uint64_t v = act ? (static_cast<uint64_t>(key) << 32) | (0xFFFFFFFFu - static_cast<uint32_t>(row)) : 0ull;
+        uint32_t slot = kNoSlot;
+        if (!FIRST && act) {
+            slot = group_find(a.tab_keys, a.tab_bits, id);
+            const uint64_t bound = slot != kNoSlot ? a.tab_vals[static_cast<uint64_t>(slot) * a.per_doc + j - 1] : 0ull;
+            if (!(v < bound))
+                v = 0ull; // taken by an earlier round (or the document has no slot: the table overflowed, flagged)
+        }
+#pragma unroll
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const uint64_t ov = shfl_up_u64(v, d);
+            const uint32_t oid = __shfl_up(id, d, 64);
+            if (lane >= d && oid == id && ov > v)
+                v = ov;
+        }
+        const uint32_t next_id = __shfl_down(id, 1, 64);
+        const bool tail = lane == 63 || next_id != id;
+        if (tail && id != RLR_DOC_NONE && v != 0ull) {
+            if (FIRST)
+                slot = group_insert(a.tab_keys, a.tab_bits, id);
+            else if (slot == kNoSlot)
+                slot = group_find(a.tab_keys, a.tab_bits, id);
+            if (slot != kNoSlot) {
+                // The value only grows during a launch, so whatever a load sees is a lower bound of the final maximum: a
+                // key at or below it cannot be that maximum and needs no atomic.  (200 000 scattered rows of ONE document
+                // were 200 000 read-modify-writes on one address, 2 ms a round, before this test.)
+                unsigned long long *p = reinterpret_cast<unsigned long long *>(&a.tab_vals[static_cast<uint64_t>(slot) * a.per_doc + j]);
+                if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < v)
+                    atomicMax(p, static_cast<unsigned long long>(v));
+            } else {
+                atomicOr(&a.st->flags, 2u);
+            }
+        }
+    }
+}
+
+// is the row a head -- among its group's best per_doc by nomination?  (tg = 0 for a smaller group and an untagged row)
+__device__ inline bool group_is_head(uint32_t key, uint32_t row, uint64_t tg)
+{
+    return key != 0u && ((static_cast<uint64_t>(key) << 32) | (0xFFFFFFFFu - row)) >= tg;
+}
+
+__global__ __launch_bounds__(kGroupBlock) void group_heads_kernel(GroupDev a)
+{
+    __shared__ uint32_t s_hist[kHistBins];
+    __shared__ uint32_t s_valid;
+    for (uint32_t i = threadIdx.x; i < kHistBins; i += kGroupBlock)
+        s_hist[i] = 0;
+    if (threadIdx.x == 0)
+        s_valid = 0;
+    __syncthreads();
+    const uint32_t stride = gridDim.x * kGroupBlock;
+    uint32_t valid = 0;
+    for (uint64_t r = blockIdx.x * kGroupBlock + threadIdx.x; r < a.n; r += stride) { // (64-bit: r + stride may pass 2^32)
+        const uint32_t row = static_cast<uint32_t>(r);
+        const uint32_t key = score_key(a.scores[row]);
+        uint64_t tg = 0ull;
+        if (key != 0u && a.docs) {
+            const uint32_t id = a.docs[row];
+            if (id != RLR_DOC_NONE) {
+                const uint32_t slot = group_find(a.tab_keys, a.tab_bits, id);
+                // (no slot: the table overflowed, the flag is set and the host discards this pass)
+                tg = slot != kNoSlot ? a.tab_vals[static_cast<uint64_t>(slot) * a.per_doc + a.per_doc - 1] : 0ull;
+            }
+        }
+        a.tg[row] = tg;
+        if (key != 0u) {
+            valid++;
+            if (group_is_head(key, row, tg))
+                atomicAdd(&s_hist[key >> 21], 1u);
+        }
+    }
+    if (valid)
+        atomicAdd(&s_valid, valid);
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < kHistBins; i += kGroupBlock) {
+        const uint32_t c = s_hist[i];
+        if (c)
+            atomicAdd(&a.hist[i], c);
+    }
+    if (threadIdx.x == 0 && s_valid)
+        atomicAdd(&a.st->n_valid, s_valid);
+}
+
+// digit 2 (key bits 20..10) of the heads whose digit 1 is the k-th head's
+__global__ __launch_bounds__(kGroupBlock) void group_refine_kernel(GroupDev a)
+{
+    __shared__ uint32_t s_hist[kHistBins];
+    uint32_t bin1, k2, in_bin;
+    find_rank_bin(a.hist, a.k, &bin1, &k2, &in_bin);
+    if (in_bin == 0)
+        return; // fewer than k heads: no threshold (uniform)
+    for (uint32_t i = threadIdx.x; i < kHistBins; i += kGroupBlock)
+        s_hist[i] = 0;
+    __syncthreads();
+    const uint32_t stride = gridDim.x * kGroupBlock;
+    for (uint64_t r = blockIdx.x * kGroupBlock + threadIdx.x; r < a.n; r += stride) {
+        const uint32_t row = static_cast<uint32_t>(r);
+        const uint32_t key = score_key(a.scores[row]);
+        if ((key >> 21) == bin1 && group_is_head(key, row, a.tg[row]))
+            atomicAdd(&s_hist[(key >> 10) & (kHistBins - 1)], 1u);
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < kHistBins; i += kGroupBlock) {
+        const uint32_t c = s_hist[i];
+        if (c)
+            atomicAdd(&a.hist[kHistBins + i], c);
+    }
+}
+
+template <bool F16>
+__global__ __launch_bounds__(kGroupBlock) void group_collect_kernel(GroupDev a)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_mem[];
+    __shared__ uint32_t s_row[kGroupLocalCap];
+    __shared__ uint32_t s_cnt, s_base;
+    const uint32_t tid = threadIdx.x;
+    // U: the floor of the 22-bit bin of the k-th head, -inf with fewer than k heads
+    uint32_t bin1, k2, in_bin, bin2 = 0, r2;
+    find_rank_bin(a.hist, a.k, &bin1, &k2, &in_bin);
+    __syncthreads(); // (find_rank_bin's LDS words are reused by the second search)
+    if (in_bin != 0)
+        find_rank_bin(a.hist + kHistBins, k2, &bin2, &r2);
+    const uint32_t floor_key = in_bin != 0 ? (bin1 << 21) | (bin2 << 10) : 0u;
+    float u = floor_key ? key_score(floor_key) : -__builtin_inff();
+    if (!(u == u))
+        u = -__builtin_inff(); // (the bin of -inf decodes to a NaN pattern)
+    if (tid == 0)
+        s_cnt = 0;
+    __syncthreads();
+    const uint64_t chunk = (static_cast<uint64_t>(a.n) + gridDim.x - 1) / gridDim.x;
+    const uint64_t lo = min(blockIdx.x * chunk, static_cast<uint64_t>(a.n)), hi = min(lo + chunk, static_cast<uint64_t>(a.n));
+    for (uint64_t r = lo + tid; r < hi; r += kGroupBlock) {
+        const uint32_t row = static_cast<uint32_t>(r);
+        const float s = a.scores[row];
+        if (score_key(s) == 0u)
+            continue;
+        const uint32_t tkey = static_cast<uint32_t>(a.tg[row] >> 32);
+        const float t = tkey ? key_score(tkey) : -__builtin_inff();
+        const float thr = fmaxf(t, u) - a.two_eps;
+        if (!(s < thr)) { // (a band so wide that the threshold is no number takes every row)
+            const uint32_t l = atomicAdd(&s_cnt, 1u);
+            if (l < kGroupLocalCap)
+                s_row[l] = row;
+        }
+    }
+    __syncthreads();
+    const uint32_t found = s_cnt;
+    if (found == 0)
+        return; // (uniform)
+    if (tid == 0) {
+        s_base = atomicAdd(&a.st->n_cand, found);
+        if (found > kGroupLocalCap)
+            atomicOr(&a.st->flags, 1u);
+    }
+    const uint32_t q_floats = (a.dim + 7) & ~7u;
+    float *s_q = s_mem;
+    float *s_p = s_mem + q_floats;
+    for (uint32_t i = tid; i < q_floats; i += kGroupBlock)
+        s_q[i] = i < a.dim ? a.query[i] : 0.0f;
+    __syncthreads();
+    const uint32_t base = s_base;
+    const uint32_t cnt = min(found, kGroupLocalCap);
+    for (uint32_t g0 = 0; g0 < cnt; g0 += a.cpb) {
+        const uint32_t c = min(a.cpb, cnt - g0);
+        if (g0)
+            __syncthreads(); // the chains of the previous group have left s_p
+        const float sc = staged_reference_dot<F16, kGroupBlock>(a.rows, a.pitch16, a.dim, s_q, s_p, s_row + g0, c, tid);
+        const uint32_t slot = base + g0 + tid;
+        if (tid < c && slot < kGroupCap) {
+            const uint32_t row = s_row[g0 + tid];
+            a.cand[slot] = pack_result(sc, row);
+            a.cand_doc[slot] = a.docs ? a.docs[row] : RLR_DOC_NONE;
+        }
+    }
+}
+
+// One workgroup: the candidates in exact order, each one's rank inside its group, the accepted ones compacted, the
+// first k and their document ids into `out`, then the completion word.
+__global__ __launch_bounds__(1024) void group_finish_kernel(GroupDev a)
+{
+    __shared__ uint64_t s_pk[kGroupCap];
+    __shared__ uint32_t s_doc[kGroupCap];
+    __shared__ uint32_t s_acc[kGroupCap];
+    __shared__ uint32_t s_outdoc[kGroupKMax + 1];
+    __shared__ uint32_t s_chk, s_nacc;
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < kHistBins; i += 1024)
+        a.ctx_hist[i] = 0; // the scan counted its scores into the context's digit-1 histogram; nothing here read it
+    const uint32_t n_raw = a.st->n_cand, flags = a.st->flags, n_valid = a.st->n_valid;
+    if (tid == 0) {
+        s_chk = 0;
+        s_nacc = 0;
+    }
+    if (flags != 0 || n_raw > kGroupCap) { // (uniform) the host takes the exact path
+        if (tid == 0)
+            *a.meta = 0xFFFFFFFFull;
+        return;
+    }
+    for (uint32_t i = tid; i < n_raw; i += 1024) {
+        s_pk[i] = a.cand[i];
+        s_doc[i] = a.cand_doc[i];
+    }
+    for (uint32_t i = tid; i <= kGroupKMax; i += 1024)
+        s_outdoc[i] = 0;
+    __syncthreads();
+    for (uint32_t i = tid; i < n_raw; i += 1024) {
+        const uint64_t mine = s_pk[i];
+        const uint32_t d = s_doc[i];
+        uint32_t ahead = 0;
+        if (d != RLR_DOC_NONE)
+            for (uint32_t j = 0; j < n_raw; ++j)
+                ahead += (s_pk[j] > mine && s_doc[j] == d) ? 1u : 0u;
+        s_acc[i] = ahead < a.per_doc ? 1u : 0u;
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < n_raw; i += 1024) {
+        if (!s_acc[i])
+            continue;
+        const uint64_t mine = s_pk[i];
+        uint32_t pos = 0;
+        for (uint32_t j = 0; j < n_raw; ++j)
+            pos += (s_acc[j] && s_pk[j] > mine) ? 1u : 0u;
+        atomicAdd(&s_nacc, 1u);
+        if (pos < a.k) {
+            a.out[pos] = mine;
+            s_outdoc[pos] = s_doc[i];
+            atomicAdd(&s_chk, result_chk_term(mine, pos));
+        }
+    }
+    __syncthreads();
+    const uint32_t n_out = min(s_nacc, a.k);
+    for (uint32_t i = n_out + tid; i < a.k; i += 1024)
+        a.out[i] = 0ull;
+    const uint32_t doc_words = (a.k + 1) / 2;
+    for (uint32_t w = tid; w < doc_words; w += 1024) {
+        const uint64_t word = static_cast<uint64_t>(s_outdoc[2 * w]) | (static_cast<uint64_t>(s_outdoc[2 * w + 1]) << 32);
+        a.out[a.k + w] = word;
+        if (word)
+            atomicAdd(&s_chk, result_chk_term(word, a.k + w));
+    }
+    if (tid == 0) {
+        const uint64_t info = static_cast<uint64_t>(n_valid) | (static_cast<uint64_t>(n_out) << 32);
+        a.out[a.k + doc_words] = info;
+        if (info)
+            atomicAdd(&s_chk, result_chk_term(info, a.k + doc_words));
+    }
+    __threadfence_system();
+    __syncthreads();
+    if (tid == 0)
+        *a.meta = (static_cast<uint64_t>(s_chk) << 32) | n_raw; // (n_raw <= kGroupCap: never the pending pattern)
+}
+
+__global__ __launch_bounds__(kGroupBlock) void group_iota_kernel(uint32_t *__restrict__ list, uint32_t n)
+{
+    for (uint32_t i = blockIdx.x * kGroupBlock + threadIdx.x; i < n; i += gridDim.x * kGroupBlock)
+        list[i] = i;
+}
+
+// the staging of collect's re-score: the query and cpb rows of products (tail.hip's layout, under what is left of the
+// 64 KB beside the local candidate list and the bin search's words)
+bool group_shape(uint32_t pitch16, uint32_t dim, int dtype, uint32_t *cpb_out, size_t *staging_out)
+{
+    const size_t q_bytes = static_cast<size_t>((dim + 7) & ~7u) * sizeof(float);
+    const size_t row_bytes = q_bytes + 16;
+    if (pitch16 * (dtype == RLR_F16 ? 8u : 4u) < ((dim + 7) & ~7u))
+        return false;
+    constexpr size_t budget = 56 * 1024;
+    uint32_t cpb = 8;
+    while (cpb > 1 && q_bytes + cpb * row_bytes > budget)
+        cpb >>= 1;
+    if (q_bytes + cpb * row_bytes > budget)
+        return false;
+    *cpb_out = cpb;
+    *staging_out = q_bytes + cpb * row_bytes;
+    return true;
+}
+
+} // namespace
+
+bool group_fits(uint32_t pitch16, uint32_t dim, int dtype)
+{
+    uint32_t cpb;
+    size_t staging;
+    return group_shape(pitch16, dim, dtype, &cpb, &staging);
+}
+
+hipError_t launch_group_tail(const GroupArgs &a, hipStream_t s, hipEvent_t after_rounds)
+{
+    uint32_t cpb;
+    size_t staging;
+    if (a.n == 0 || a.k == 0 || a.k > kGroupKMax || a.per_doc == 0 || a.per_doc > RLR_MAX_PER_DOCUMENT || a.tab_bits < 1 ||
+        a.tab_bits > 31 || !group_shape(a.pitch16, a.dim, a.dtype, &cpb, &staging))
+        return hipErrorInvalidValue;
+    GroupDev d;
+    d.scores = a.scores;
+    d.docs = a.docs;
+    d.n = a.n;
+    d.k = a.k;
+    d.per_doc = a.per_doc;
+    d.two_eps = a.two_eps;
+    d.tab_keys = a.tab_keys;
+    d.tab_vals = a.tab_vals;
+    d.tab_bits = a.tab_bits;
+    d.tg = a.tg;
+    d.hist = a.hist;
+    d.st = a.st;
+    d.rows = static_cast<const float4 *>(a.rows);
+    d.pitch16 = a.pitch16;
+    d.dim = a.dim;
+    d.query = a.query;
+    d.cand = a.cand;
+    d.cand_doc = a.cand_doc;
+    d.out = a.out;
+    d.meta = a.meta;
+    d.ctx_hist = a.ctx_hist;
+    d.cpb = cpb;
+    const uint32_t max_blocks = static_cast<uint32_t>(std::max(a.n_cu, 1)) * 8;
+    const uint32_t row_blocks = std::max<uint32_t>(1, std::min<uint32_t>((a.n + kGroupBlock - 1) / kGroupBlock, max_blocks));
+    const uint64_t slots = a.docs ? 1ull << a.tab_bits : 0ull;
+    const uint32_t clear_blocks = static_cast<uint32_t>(
+        std::max<uint64_t>(2u * kHistBins / kGroupBlock, std::min<uint64_t>((slots * a.per_doc + kGroupBlock - 1) / kGroupBlock, max_blocks)));
+    hipLaunchKernelGGL(group_clear_kernel, dim3(clear_blocks), dim3(kGroupBlock), 0, s, d);
+    if (a.docs) {
+        hipLaunchKernelGGL(group_round_kernel<true>, dim3(row_blocks), dim3(kGroupBlock), 0, s, d, 0u);
+        for (uint32_t j = 1; j < a.per_doc; ++j)
+            hipLaunchKernelGGL(group_round_kernel<false>, dim3(row_blocks), dim3(kGroupBlock), 0, s, d, j);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return e;
+    if (after_rounds && (e = hipEventRecord(after_rounds, s)) != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(group_heads_kernel, dim3(row_blocks), dim3(kGroupBlock), 0, s, d);
+    hipLaunchKernelGGL(group_refine_kernel, dim3(row_blocks), dim3(kGroupBlock), 0, s, d);
+    // the workgroups re-score what they find, cpb candidates at a time: a small corpus is spread over more (partly idle)
+    // workgroups than its scores need, as in tail.hip's stage 1
+    const uint32_t collect_blocks =
+        std::max<uint32_t>(1, std::min<uint32_t>(std::max<uint32_t>(row_blocks, (a.n + 31) / 32), max_blocks));
+    if (a.dtype == RLR_F16)
+        hipLaunchKernelGGL(group_collect_kernel<true>, dim3(collect_blocks), dim3(kGroupBlock), staging, s, d);
+    else
+        hipLaunchKernelGGL(group_collect_kernel<false>, dim3(collect_blocks), dim3(kGroupBlock), staging, s, d);
+    hipLaunchKernelGGL(group_finish_kernel, dim3(1), dim3(1024), 0, s, d);
+    return hipGetLastError();
+}
+
+hipError_t launch_group_iota(uint32_t *list, uint32_t n, hipStream_t s)
+{
+    if (n == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(group_iota_kernel, dim3(std::min<uint32_t>((n + kGroupBlock - 1) / kGroupBlock, 4096)), dim3(kGroupBlock), 0, s, list, n);
+    return hipGetLastError();
+}
+
+} // namespace rlr

@@ -23,11 +23,13 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <memory>
 #include <new>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include <time.h>
@@ -121,6 +123,14 @@ struct Ctx {
                                    // (ScanArgs::query_host): the staged queries in pinned host memory, q_pitch floats each
     bool hist_dirty = false; // a pipeline was enqueued and did not complete: d_hist may hold counts
     PinBuf h_assert;         // RLR_POISON_ALLOC=1 only: pinned word the zero-histogram assertion kernel counts into
+    // grouped search (group.hip), grown lazily: the document table, t_g per row, the heads' histograms, the candidates
+    DevBuf<uint32_t> d_gkeys;      // 1 << bits slots, with d_gvals
+    DevBuf<uint64_t> d_gvals;      // slots x per_doc
+    DevBuf<uint64_t> d_gtg;        // rows
+    DevBuf<uint32_t> d_ghist;      // 2 * kHistBins, with d_gstate, d_gcand and d_gcdoc
+    DevBuf<GroupState> d_gstate;
+    DevBuf<uint64_t> d_gcand;      // kGroupCap
+    DevBuf<uint32_t> d_gcdoc;      // kGroupCap
     // rlr_search_topk_device_begin / _end
     hipStream_t pending_stream = nullptr;
     uint32_t pending_q = 0, pending_k = 0;
@@ -215,6 +225,7 @@ struct rlr_index {
     // bumped by every call that changes which rows the index holds (upload, append, delete_rows, fill_synthetic; load_json
     // goes through upload): a row filter records it at creation and is refused as stale once it has moved on
     std::atomic<uint64_t> mutations{0};
+    uint64_t grouped_forms[4] = {0, 0, 0, 0}; // rlr_index_grouped_forms: queries served by each form (mu)
 };
 
 // A set of rows of one index, fixed at creation (rlr_filter_create_*): one bit per index row on the device (tail bits of
@@ -1790,7 +1801,8 @@ rlr::MmrEmit mmr_emit(const uint32_t *list, const float *comb, const float *cosv
 // (in two halves, so that a caller with work for ANOTHER stream -- the BM25 kernels of a text search -- can launch it right
 // behind the scan instead of behind every launch of the pipeline: enqueue_query_scan, then enqueue_query_rest)
 // f != nullptr: a document-scoped search -- the masked scan over the master rows, whatever copies the index keeps.
-hipError_t enqueue_query_scan(rlr_index *ix, Ctx *c, uint32_t qi, bool timed, const rlr_filter *f = nullptr)
+// master_rows: the scan reads the master rows even where the index keeps a nomination copy (a grouped search: its band is the plan's).
+hipError_t enqueue_query_scan(rlr_index *ix, Ctx *c, uint32_t qi, bool timed, const rlr_filter *f = nullptr, bool master_rows = false)
 {
     hipStream_t s = c->stream;
     hipError_t e;
@@ -1806,8 +1818,8 @@ hipError_t enqueue_query_scan(rlr_index *ix, Ctx *c, uint32_t qi, bool timed, co
     if (timed && (e = hipEventRecord(c->ev[0], s)) != hipSuccess) return e;
     ScanArgs sa = scan_args(ix, dq, c->d_scores.get(), hist1);
     sa.query_host = c->h_q_kq ? c->h_q_kq + static_cast<size_t>(qi) * ix->q_pitch : nullptr;
-    const bool q8 = !f && scan_over_q8(ix);
-    const bool img = !f && !q8 && scan_over_image(ix, c);
+    const bool q8 = !f && !master_rows && scan_over_q8(ix);
+    const bool img = !f && !master_rows && !q8 && scan_over_image(ix, c);
     if (f)
         e = launch_scan_masked(sa, f->d_mask.get(), f->n_allowed, s);
     else if (q8)
@@ -2448,6 +2460,163 @@ int32_t filtered_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *
     *n_out = p.k;
     unpack_results(h_res, p.k, rows_out, cos_out);
     return note_search(ix, c, 1, n_cand, n_retry, timed && f->path != 0);
+}
+
+// ---- grouped search (rlr_search_topk_grouped): at most per_doc results per document ---------------------------------
+// The walk of the contract on the host: `keys` = the exact packed keys of the allowed rows, docs = the whole column (empty:
+// no column).  Descending keys are the library's result order; a row is accepted unless per_doc rows of its document are.
+uint32_t grouped_walk(std::vector<uint64_t> &keys, const std::vector<uint32_t> &docs, uint32_t k, uint32_t per_doc, uint64_t *res,
+                      uint32_t *res_docs)
+{
+    std::sort(keys.begin(), keys.end(), std::greater<uint64_t>());
+    std::unordered_map<uint32_t, uint32_t> taken;
+    uint32_t n = 0;
+    for (size_t i = 0; i < keys.size() && n < k; ++i) {
+        const uint32_t row = 0xFFFFFFFFu - static_cast<uint32_t>(keys[i]);
+        const uint32_t d = docs.empty() ? RLR_DOC_NONE : docs[row];
+        if (d != RLR_DOC_NONE && taken[d]++ >= per_doc)
+            continue;
+        res[n] = keys[i];
+        res_docs[n] = d;
+        n++;
+    }
+    return n;
+}
+
+// The exact form: reference-order scores of every allowed row, copied back, and the walk on the host.  Slow and always
+// right.  The query is in c->d_query.
+int32_t grouped_exact(rlr_index *ix, Ctx *c, const rlr_filter *f, uint32_t k, uint32_t per_doc, uint64_t *res, uint32_t *res_docs,
+                      uint32_t *n_res)
+{
+    hipStream_t s = c->stream;
+    const uint32_t n = static_cast<uint32_t>(f ? f->n_allowed : ix->n_rows);
+    std::vector<uint32_t> list(n);
+    RLR_TRY(reserve_list(c, n));
+    if (f) {
+        uint32_t at = 0;
+        for (size_t w = 0; w < f->h_mask.size(); ++w)
+            for (uint64_t bits = f->h_mask[w]; bits; bits &= bits - 1)
+                if (at < n)
+                    list[at++] = static_cast<uint32_t>(w * 64 + static_cast<uint32_t>(__builtin_ctzll(bits)));
+    } else {
+        for (uint32_t i = 0; i < n; ++i)
+            list[i] = i;
+        RLR_HIP(launch_group_iota(c->d_list.get(), n, s));
+    }
+    RLR_HIP(launch_score_rows(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, c->d_query.get(), f ? f->d_list.get() : c->d_list.get(), n,
+                              c->d_vals.get(), s));
+    std::vector<float> vals(n);
+    std::vector<uint32_t> docs(ix->d_docs ? ix->n_rows : 0);
+    RLR_HIP(hipMemcpyAsync(vals.data(), c->d_vals.get(), static_cast<size_t>(n) * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (!docs.empty())
+        RLR_HIP(hipMemcpyAsync(docs.data(), ix->d_docs.get(), docs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    RLR_HIP(hipStreamSynchronize(s));
+    std::vector<uint64_t> keys(n);
+    for (uint32_t i = 0; i < n; ++i)
+        keys[i] = pack_result(vals[i], list[i]);
+    *n_res = grouped_walk(keys, docs, k, per_doc, res, res_docs);
+    return RLR_OK;
+}
+
+// One grouped query over all rows (f == nullptr) or the rows of `f` (n_allowed > 0); k > 0, per_doc in 1..8.  The scan,
+// then group.hip's tail in place of enqueue_query_rest; every hand-off to the exact form is counted (form 1..3).
+int32_t grouped_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *query, uint32_t k, uint32_t per_doc, float guard_eps,
+                      uint64_t *rows_out, float *cos_out, uint32_t *docs_out, uint32_t *n_out)
+{
+    const uint64_t n_allowed = f ? f->n_allowed : ix->n_rows;
+    const SearchPlan p = make_plan(ix, query, 1, static_cast<uint32_t>(std::min<uint64_t>(k, n_allowed)), guard_eps);
+    RLR_TRY(ctx_prepare(ix, c, 1, p));
+    const uint32_t words = group_out_words(p.k);
+    Staged pin;
+    RLR_TRY(stage_call(ix, c, query, 1, static_cast<size_t>(words) + 1, /*for_scans=*/false, &pin));
+    uint64_t *h_res = pin.h_res, *h_meta = h_res + words;
+    hipStream_t s = c->stream;
+    const bool timed = ix->profiling;
+    uint64_t n_cand = 0;
+    uint32_t n_res = 0, form = 0;
+    std::vector<uint64_t> ex_res;
+    std::vector<uint32_t> ex_docs;
+    const uint64_t *res = h_res;
+    const uint32_t *res_docs = reinterpret_cast<const uint32_t *>(h_res + p.k);
+    // the table holds twice the documents it can meet (one per allowed row at most)
+    uint32_t tab_bits = 10;
+    while (tab_bits < 32 && (1ull << tab_bits) < 2 * n_allowed)
+        tab_bits++;
+    if ((f && f->path == 0) || p.k > kGroupKMax || tab_bits > 31 || !group_fits(ix->pitch16, ix->dim, ix->dtype)) {
+        form = 3; // by rule: a list-path filter, k beyond the finish, rows beyond the staged re-score
+    } else {
+        const uint32_t n = static_cast<uint32_t>(ix->n_rows);
+        if (ix->d_docs)
+            RLR_HIP(reserve_group(Want{c->d_gkeys, static_cast<size_t>(1) << tab_bits},
+                                  Want{c->d_gvals, (static_cast<size_t>(1) << tab_bits) * per_doc}));
+        RLR_HIP(c->d_gtg.reserve(std::max<uint32_t>(n, 1024)));
+        RLR_HIP(reserve_group(Want{c->d_ghist, 2 * kHistBins}, Want{c->d_gstate, 1}, Want{c->d_gcand, kGroupCap}, Want{c->d_gcdoc, kGroupCap}));
+        GroupArgs ga;
+        ga.scores = c->d_scores.get();
+        ga.docs = ix->d_docs.get();
+        ga.n = n;
+        ga.k = p.k;
+        ga.per_doc = per_doc;
+        ga.two_eps = p.two_eps;
+        ga.tab_keys = c->d_gkeys.get();
+        ga.tab_vals = c->d_gvals.get();
+        ga.tab_bits = tab_bits;
+        ga.tg = c->d_gtg.get();
+        ga.hist = c->d_ghist.get();
+        ga.st = c->d_gstate.get();
+        ga.rows = ix->d_rows.get();
+        ga.pitch16 = ix->pitch16;
+        ga.dim = ix->dim;
+        ga.dtype = ix->dtype;
+        ga.query = c->d_query.get();
+        ga.cand = c->d_gcand.get();
+        ga.cand_doc = c->d_gcdoc.get();
+        ga.out = h_res;
+        ga.meta = h_meta;
+        ga.ctx_hist = c->d_hist.get();
+        ga.n_cu = ix->n_cu;
+        arm_meta(h_meta, 1);
+        // (the masked scan for a filter; without one the scan over the master rows too: no nomination copy, as filtered calls)
+        RLR_HIP(enqueue_query_scan(ix, c, 0, timed, f, /*master_rows=*/true));
+        RLR_HIP(launch_group_tail(ga, s, timed ? c->ev[2] : nullptr));
+        if (timed) {
+            RLR_HIP(hipEventRecord(c->ev[3], s));
+            RLR_HIP(hipStreamSynchronize(s));
+        } else {
+            RLR_TRY(wait_results(h_meta, h_res, 1, words, kGroupCap, s, &c->wait_ema));
+        }
+        RLR_TRY(check_hist_assert(c));
+        n_cand = static_cast<uint32_t>(h_meta[0]);
+        if (n_cand > kGroupCap) {
+            form = 1; // more candidates than the finish holds (or a local list / the table overflowed)
+        } else {
+            const uint64_t info = h_res[words - 1];
+            n_res = static_cast<uint32_t>(info >> 32);
+            const uint32_t n_valid = static_cast<uint32_t>(info);
+            if (n_res < p.k && n_valid < n_allowed)
+                form = 2; // allowed rows with NaN nominations were left out and the answer is short
+            for (uint32_t i = 0; f && i < n_res && form == 0; ++i)
+                if (!filter_holds(f, 0xFFFFFFFFu - static_cast<uint32_t>(h_res[i])))
+                    form = 2; // a masked row came back (the hazard filtered_query documents)
+        }
+    }
+    if (form != 0) {
+        ex_res.resize(p.k);
+        ex_docs.resize(p.k);
+        RLR_TRY(grouped_exact(ix, c, f, p.k, per_doc, ex_res.data(), ex_docs.data(), &n_res));
+        res = ex_res.data();
+        res_docs = ex_docs.data();
+    }
+    c->hist_dirty = false;
+    *n_out = n_res;
+    unpack_results(res, n_res, rows_out, cos_out);
+    if (docs_out)
+        std::memcpy(docs_out, res_docs, static_cast<size_t>(n_res) * sizeof(uint32_t));
+    {
+        std::lock_guard<std::mutex> lk(ix->mu);
+        ix->grouped_forms[form]++;
+    }
+    return note_search(ix, c, 1, n_cand, form != 0 ? 1 : 0, timed && form != 3);
 }
 
 // ---- several queries, inside one filter or a filter each: one shared masked pass ------------------------------------
@@ -3505,6 +3674,45 @@ int32_t rlr_search_topk_filtered(rlr_index *ix, const rlr_filter *f, const float
         q0 += m;
     }
     drain.armed = false;
+    return RLR_OK;
+}
+
+int32_t rlr_search_topk_grouped(rlr_index *ix, const rlr_filter *f, const float *queries, uint32_t n_queries, uint32_t k,
+                                uint32_t per_doc, float guard_eps, uint64_t *rows_out, float *cos_out, uint32_t *docs_out, uint32_t *n_out)
+{
+    RLR_TRY(check_handle(ix));
+    if (f)
+        RLR_TRY(check_filter(ix, f)); // (a stale filter is refused before any GPU work)
+    if (k == 0 || per_doc < 1 || per_doc > RLR_MAX_PER_DOCUMENT)
+        return set_error(RLR_E_INVALID, "k must be positive and per_doc in 1..%d (k = %u, per_doc = %u)", RLR_MAX_PER_DOCUMENT, k, per_doc);
+    if (n_queries && (!queries || !n_out || !rows_out || !cos_out))
+        return set_error(RLR_E_INVALID, "queries / n_out / output buffers are null");
+    RLR_TRY(use_device(ix));
+    for (uint32_t q = 0; q < n_queries; ++q)
+        n_out[q] = 0;
+    if ((f ? f->n_allowed : ix->n_rows) == 0 || n_queries == 0)
+        return RLR_OK;
+    CtxLease lease(ix);
+    RLR_TRY(ctx_acquire(ix, &lease.c));
+    StreamDrain drain{lease.c->stream};
+    for (uint32_t q = 0; q < n_queries; ++q) // one by one: no coalescer, no nomination copy, no shared pass
+        RLR_TRY(grouped_query(ix, lease.c, f, queries + static_cast<size_t>(q) * ix->dim, k, per_doc, guard_eps,
+                              rows_out + static_cast<size_t>(q) * k, cos_out + static_cast<size_t>(q) * k,
+                              docs_out ? docs_out + static_cast<size_t>(q) * k : nullptr, &n_out[q]));
+    drain.armed = false;
+    return RLR_OK;
+}
+
+int32_t rlr_index_grouped_forms(rlr_index *ix, uint64_t counts[4], int32_t reset)
+{
+    RLR_TRY(check_handle(ix));
+    std::lock_guard<std::mutex> lk(ix->mu);
+    for (int i = 0; i < 4; ++i) {
+        if (counts)
+            counts[i] = ix->grouped_forms[i];
+        if (reset)
+            ix->grouped_forms[i] = 0;
+    }
     return RLR_OK;
 }
 

@@ -256,4 +256,40 @@ hipError_t launch_docs_scatter(const uint64_t *mask, uint32_t n_rows, const uint
 hipError_t launch_docs_fill(uint32_t *col, uint64_t n, uint32_t doc, hipStream_t s);                               // col[i] = doc
 hipError_t launch_docs_gather(const uint32_t *col, const uint32_t *keep, uint64_t n, uint32_t *out, hipStream_t s); // out[i] = col[keep[i]]
 
+// ---- group.hip : the tail of a grouped search (at most per_doc results per document), behind the scan ----
+constexpr uint32_t kGroupCap = 2048;  // candidates the one-workgroup finish holds
+constexpr uint32_t kGroupKMax = 1024; // largest k the finish emits
+struct GroupState {
+    uint32_t n_cand;  // candidate slots handed out (may exceed kGroupCap)
+    uint32_t n_valid; // rows whose nominated score is a number (masked rows and NaN nominations are not)
+    uint32_t flags;   // bit 0: a workgroup's local candidate list overflowed, bit 1: the document table ran out of slots
+    uint32_t pad;
+};
+struct GroupArgs {
+    const float *scores;  // n nominated scores (NaN: masked, or a NaN nomination)
+    const uint32_t *docs; // n document ids, or null: no column (every row a group of its own)
+    uint32_t n, k, per_doc;
+    float two_eps;        // 2 x the plan's half band
+    uint32_t *tab_keys;   // 1 << tab_bits document ids (open addressing)
+    uint64_t *tab_vals;   // per_doc packed keys per slot: the group's largest, second largest, ... nominated key
+    uint32_t tab_bits;
+    uint64_t *tg;         // n: the per_doc-th largest nominated key of the row's group (0: the group is smaller)
+    uint32_t *hist;       // 2 * kHistBins: digit 1 and digit 2 of the heads
+    GroupState *st;
+    const void *rows;
+    uint32_t pitch16, dim;
+    int dtype;
+    const float *query;
+    uint64_t *cand;       // kGroupCap exact packed keys
+    uint32_t *cand_doc;   // ... and their document ids
+    uint64_t *out;        // group_out_words(k) words: k results | ceil(k / 2) words of document ids | n_valid + (n_out << 32)
+    uint64_t *meta;       // candidate count | checksum of `out` << 32, written last
+    uint32_t *ctx_hist;   // the context's digit-1 histogram (the scan counted into it): cleared for the next query
+    int n_cu;
+};
+inline uint32_t group_out_words(uint32_t k) { return k + (k + 1) / 2 + 1; }
+bool group_fits(uint32_t pitch16, uint32_t dim, int dtype);
+hipError_t launch_group_tail(const GroupArgs &a, hipStream_t s, hipEvent_t after_rounds = nullptr);
+hipError_t launch_group_iota(uint32_t *list, uint32_t n, hipStream_t s); // list[i] = i
+
 } // namespace rlr

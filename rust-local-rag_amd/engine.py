@@ -591,6 +591,31 @@ class RagEngine:
                                                         C.byref(n)))
         return [(self._chunks[int(rows[i])].id, float(sc[i])) for i in range(n.value)]
 
+    # -- at most `per_document` chunks from any one document (rlr_search_topk_grouped; no reference site) ----
+    def search_per_document(self, query_embedding, top_k: int, per_document: int = 1,
+                            documents: Optional[Sequence[str]] = None) -> List[SearchResult]:
+        """The best `top_k` chunks by cosine with at most `per_document` (1..8) from any one document, selected on the
+        device.  Embedding-only: score = embedding_score = initial_score = the cosine, the lexical score is 0; the query
+        is normalised as `search` normalises it.  `documents`: only inside these (as `search`)."""
+        if top_k <= 0 or len(self._chunks) == 0:
+            return []
+        self._sync_documents()
+        f = self._filter_for(documents) if documents is not None else None
+        q = normalize(_f32(query_embedding).ravel())
+        rows, cos, _ = self.index.search_topk_grouped(q, top_k, per_document, filter=f)[0]
+        out = []
+        for row, c in zip(rows.tolist(), cos.tolist()):
+            ch = self._chunks[row]
+            out.append(SearchResult(ch.text, c, ch.document_name, ch.id, ch.chunk_index, ch.page_number, ch.section,
+                                    c, 0.0, c, None, None, None, row))
+        return out
+
+    def rank_documents(self, query_embedding, top_k: int,
+                       documents: Optional[Sequence[str]] = None) -> List[Tuple[str, SearchResult]]:
+        """The `top_k` documents closest to the query, each with its best chunk: search_per_document with one chunk
+        per document, keyed by document name."""
+        return [(r.document, r) for r in self.search_per_document(query_embedding, top_k, 1, documents)]
+
     # -- API layer: search_documents / http_search (mcp_server.rs:81-110, :371-389) --------
     def search_documents(self, request: SearchRequest) -> List[SearchResult]:
         top_k = min(request.top_k if request.top_k is not None else N.DEFAULT_TOP_K, N.MAX_TOP_K)

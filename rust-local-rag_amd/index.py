@@ -276,6 +276,28 @@ class GpuIndex:
                                                n_out.ctypes.data_as(N.u32p)))
         return [(rows[i, :int(n_out[i])], cos[i, :int(n_out[i])]) for i in range(nq)]
 
+    def search_topk_grouped(self, queries, k: int, per_document: int = 1, filter: "RowFilter | None" = None,
+                            guard_eps: float = -1.0):
+        """the best k rows per query with at most `per_document` (1..8) from any one document (rlr_search_topk_grouped);
+        untagged rows are never capped.  queries: [Q, dim] (or [dim]) already normalised -> a list of
+        (rows u64 [k_q], cos f32 [k_q], docs u32 [k_q]) per query; k_q < k when the documents run out"""
+        q = _f32(queries).reshape(-1, self.dim)
+        nq = q.shape[0]
+        rows = np.zeros((nq, max(k, 1)), dtype=np.uint64)
+        cos = np.zeros((nq, max(k, 1)), dtype=np.float32)
+        docs = np.zeros((nq, max(k, 1)), dtype=np.uint32)
+        n_out = np.zeros(max(nq, 1), dtype=np.uint32)
+        N.check(self._L.rlr_search_topk_grouped(self._h, None if filter is None else filter.handle, _fp(q), nq, k, per_document,
+                                                guard_eps, _up(rows), _fp(cos), _u32ptr(docs), _u32ptr(n_out)))
+        return [(rows[i, :int(n_out[i])], cos[i, :int(n_out[i])], docs[i, :int(n_out[i])]) for i in range(nq)]
+
+    def grouped_forms(self, reset: bool = False) -> list:
+        """queries search_topk_grouped served by each form: [device-selected, exact on candidate overflow, exact because
+        NaN nominations were needed or a masked row came back, exact by rule] (rlr_index_grouped_forms)"""
+        counts = np.zeros(4, dtype=np.uint64)
+        N.check(self._L.rlr_index_grouped_forms(self._h, _up(counts), int(reset)))
+        return [int(c) for c in counts]
+
     def search_topk_device(self, queries, k: int, d_out_ptr: int, stream: int = 0, guard_eps: float = -1.0) -> None:
         q = _f32(queries).reshape(-1, self.dim)
         N.check(self._L.rlr_search_topk_device(self._h, _fp(q), q.shape[0], k, guard_eps,
