@@ -151,6 +151,25 @@ int32_t rlr_engine_search_text_filtered(rlr_index *idx, rlr_lexical *lex, const 
                                         uint32_t dq, const char *query_tokens, size_t tokens_len, uint32_t top_k,
                                         float diversity_factor, int32_t stage, const rlr_query_weights *weights,
                                         rlr_search_hit *out, uint32_t cap, uint32_t *n_out);
+/* RagEngine::search / search_with_diversity with at most per_doc results from any one document (the document column of
+ * include/rlr_gpu.h; rows tagged RLR_DOC_NONE and an index without a column are never capped), over the whole index
+ * (f null) or inside a filter.  The query is normalised and the weights are resolved as the other entries do; `need` is
+ * what the uncapped entry computes over the allowed rows: min(top_k, N) at stage 0, initial_k at stage 1,
+ * min(N, max(3*top_k, top_k + 10)) under diversification (diversity_factor clamped to 0..1, != 0).  The candidates are
+ * walked in combined order and a row is accepted unless per_doc rows of its document are (rlr_search_capped); under
+ * diversification the accepted list is the pool of mmr_diversify, so the cap holds for the picks.  Fewer than `need`
+ * accepted rows is no error.  per_doc outside 1..RLR_MAX_PER_DOCUMENT: RLR_E_INVALID; a stale filter: RLR_E_INVALID; an
+ * empty filter or index: RLR_OK with *n_out = 0.  One host synchronisation. */
+int32_t rlr_engine_search_capped(rlr_index *idx, const rlr_filter *f, const float *query_raw, uint32_t dq, uint32_t top_k,
+                                 float diversity_factor, int32_t stage, const rlr_query_weights *weights,
+                                 const uint64_t *lex_rows, const float *lex_scores, uint32_t n_lex, uint32_t per_doc,
+                                 rlr_search_hit *out, uint32_t cap, uint32_t *n_out);
+/* The same from query text: rlr_lexical_score (rlr_lexical_score_filtered with a filter) with the limit
+ * rlr_engine_search_text uses, then the capped chain.  Two host synchronisations (the BM25 call, the search). */
+int32_t rlr_engine_search_text_capped(rlr_index *idx, rlr_lexical *lex, const rlr_filter *f, const float *query_raw,
+                                      uint32_t dq, const char *query_tokens, size_t tokens_len, uint32_t top_k,
+                                      float diversity_factor, int32_t stage, const rlr_query_weights *weights,
+                                      uint32_t per_doc, rlr_search_hit *out, uint32_t cap, uint32_t *n_out);
 /* rlr_engine_search_with_diversity_batch inside a filter: n_queries raw query embeddings, no lexical pairs; query q
  * equals rlr_engine_search_with_diversity_filtered(query q, n_lex = 0), N = |F| everywhere.  Hits of query q start at
  * out[q * cap]; n_out[q] = their count (every one 0 when |F| = 0).  The candidates come from ONE

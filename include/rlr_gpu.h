@@ -458,6 +458,33 @@ int32_t rlr_search_topk_grouped(rlr_index *idx, const rlr_filter *f, const float
  * list-path filter, k beyond the device finish, rows too wide for the staged re-score).  counts may be null. */
 int32_t rlr_index_grouped_forms(rlr_index *idx, uint64_t counts[4], int32_t reset);
 
+/* ---- capped hybrid search: the per-document cap inside the blend and MMR ---- */
+/* rlr_search_hybrid with at most per_doc candidates from any one document, over all rows (f null) or the rows of f.
+ * Every allowed row has cos = the reference-order dot product, lexn = lex / max_lex (0 without a lexical pair; pairs
+ * outside f are no candidates) and combined = w_e*cos + w_l*lexn in the blend's f32 arithmetic.  The allowed rows are
+ * walked in the engine's candidate order (combined desc, NaN last, row asc, -0 and +0 tying); a row is accepted unless
+ * per_doc rows of its document are, until `need` rows are accepted (need is clamped to the allowed rows; fewer accepted
+ * rows is no error).  Documents as for rlr_search_topk_grouped: RLR_DOC_NONE and an index without a column are never
+ * capped.  diversify == 0: the accepted list is the answer; else it is the pool of mmr_diversify (k, lambda as
+ * rlr_mmr_select), so the cap holds for the picks.  Without a column the call equals rlr_search_hybrid bit for bit.
+ *   per_doc outside 1..RLR_MAX_PER_DOCUMENT: RLR_E_INVALID; filter rules as for rlr_search_topk_filtered; an empty
+ *   filter: RLR_OK with *n_out = 0.  lex_rows ascending, unique, inside the index.
+ *   rows_out / cos_out / score_out / lex_out / docs_out (may be null): `need` entries (diversify: min(max(k,1), need)).
+ * The selection runs on the device behind one scan (DESIGN.md "Capped hybrid search").  There is no *fallback: what the
+ * device cannot decide is answered by an exact form (reference-order scores of every allowed row, blend and walk on the
+ * host, rlr_mmr_select over the pool), and every such hand-off is counted. */
+int32_t rlr_search_capped(rlr_index *idx, const rlr_filter *f, const float *query, uint32_t need, uint32_t k, float lambda,
+                          int32_t diversify, float w_embedding, float w_lexical, const uint64_t *lex_rows,
+                          const float *lex_scores, uint32_t n_lex, float max_lex, uint32_t per_doc, float guard_eps,
+                          uint64_t *rows_out, float *cos_out, float *score_out, float *lex_out, uint32_t *docs_out,
+                          uint32_t *n_out);
+/* Queries served by each form since the last reset: [0] decided on the device; exact form taken [1] on capacity (more
+ * candidates or lexical rows than the finish holds, the document table full), [2] because it was undecidable there (rows
+ * that order last were needed, a masked row came back, a rounding tie at the boundary), [3] by rule (a list-path filter,
+ * need > 1024, more than 2048 lexical rows, w_embedding <= 0, w_lexical < 0 or a non-finite weight, a negative lexical
+ * score, rows too wide for the staged re-score).  counts may be null. */
+int32_t rlr_index_capped_forms(rlr_index *idx, uint64_t counts[4], int32_t reset);
+
 /* ---- coalescing of concurrent single-query searches ----------------------- */
 /* Serve concurrent single-query rlr_search_topk calls on this index from shared passes over the rows.
  * max_group 0 or 1: off (the default).  2..8: at most this many queries share one pass.

@@ -18,6 +18,7 @@ RLR_F32, RLR_F16 = 0, 1
 MAX_TOP_K = 100          # mcp_server.rs:364
 DEFAULT_TOP_K = 5        # mcp_server.rs:85, :356-358
 DEFAULT_DIVERSITY = 0.3  # mcp_server.rs:86, :359-361
+MAX_PER_DOCUMENT = 8     # RLR_MAX_PER_DOCUMENT (include/rlr_gpu.h)
 
 f32p = C.POINTER(C.c_float)
 u64p = C.POINTER(C.c_uint64)
@@ -157,6 +158,9 @@ PROTOTYPES = [
     ("rlr_index_delete_documents", C.c_int32, [_H, u32p, C.c_uint32, u64p, C.c_uint64, u64p]),
     ("rlr_search_topk_grouped", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, u64p, f32p, u32p, u32p]),
     ("rlr_index_grouped_forms", C.c_int32, [_H, u64p, C.c_int32]),
+    ("rlr_search_capped", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, C.c_float, C.c_int32, C.c_float, C.c_float, u64p, f32p,
+                                      C.c_uint32, C.c_float, C.c_uint32, C.c_float, u64p, f32p, f32p, f32p, u32p, u32p]),
+    ("rlr_index_capped_forms", C.c_int32, [_H, u64p, C.c_int32]),
     ("rlr_index_set_coalescing", C.c_int32, [_H, C.c_uint32, C.c_uint32]),
     ("rlr_index_coalesce_stats", C.c_int32, [_H, C.POINTER(CoalesceStatsC), C.c_int32]),
     ("rlr_profile_enable", C.c_int32, [_H, C.c_int32]),
@@ -184,6 +188,11 @@ PROTOTYPES = [
     ("rlr_engine_search_text_filtered", C.c_int32, [_H, _H, _H, f32p, C.c_uint32, C.c_char_p, C.c_size_t, C.c_uint32,
                                                     C.c_float, C.c_int32, C.POINTER(QueryWeightsC), C.POINTER(SearchHitC),
                                                     C.c_uint32, u32p]),
+    ("rlr_engine_search_capped", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, C.c_float, C.c_int32, C.POINTER(QueryWeightsC),
+                                             u64p, f32p, C.c_uint32, C.c_uint32, C.POINTER(SearchHitC), C.c_uint32, u32p]),
+    ("rlr_engine_search_text_capped", C.c_int32, [_H, _H, _H, f32p, C.c_uint32, C.c_char_p, C.c_size_t, C.c_uint32, C.c_float,
+                                                  C.c_int32, C.POINTER(QueryWeightsC), C.c_uint32, C.POINTER(SearchHitC),
+                                                  C.c_uint32, u32p]),
     ("rlr_engine_search_with_diversity_batch_filtered", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, C.c_uint32,
                                                                     C.c_float, C.POINTER(QueryWeightsC),
                                                                     C.POINTER(SearchHitC), C.c_uint32, u32p]),

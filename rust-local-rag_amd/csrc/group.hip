@@ -12,6 +12,8 @@
 //   collect    rows with a >= max(t_g, U) - 2 eps, U = the floor of the k-th head's 22-bit bin; each workgroup re-scores
 //              what it found in reference order (staged_dot.h).
 //   finish     one workgroup: exact order, rank inside the group, accept below per_doc, emit the first k.
+// A capped hybrid search (rlr_search_capped) runs the same launches with k = the pool size and capped_finish_kernel as its
+// finish: the candidates united with the lexical rows, blended, ranked inside the group in COMBINED order (below).
 // An order between workgroups comes from the order of launches on one stream, never from a flag (the rule of tail.hip);
 // inside a launch the table is only touched by atomics, between launches by plain loads.
 #include "../../include/rlr_gpu.h"
@@ -113,7 +115,7 @@ __global__ __launch_bounds__(kGroupBlock) void group_clear_kernel(GroupDev a)
         a.st->n_cand = 0;
         a.st->n_valid = 0;
         a.st->flags = 0;
-        a.st->pad = 0;
+        a.st->u_bits = 0;
     }
 }
 
@@ -260,8 +262,11 @@ __global__ __launch_bounds__(kGroupBlock) void group_collect_kernel(GroupDev a)
     float u = floor_key ? key_score(floor_key) : -__builtin_inff();
     if (!(u == u))
         u = -__builtin_inff(); // (the bin of -inf decodes to a NaN pattern)
-    if (tid == 0)
+    if (tid == 0) {
         s_cnt = 0;
+        if (blockIdx.x == 0)
+            a.st->u_bits = __builtin_bit_cast(uint32_t, u); // (the capped finish bounds the rows left behind with it)
+    }
     __syncthreads();
     const uint64_t chunk = (static_cast<uint64_t>(a.n) + gridDim.x - 1) / gridDim.x;
     const uint64_t lo = min(blockIdx.x * chunk, static_cast<uint64_t>(a.n)), hi = min(lo + chunk, static_cast<uint64_t>(a.n));
@@ -386,6 +391,218 @@ __global__ __launch_bounds__(1024) void group_finish_kernel(GroupDev a)
         *a.meta = (static_cast<uint64_t>(s_chk) << 32) | n_raw; // (n_raw <= kGroupCap: never the pending pattern)
 }
 
+// ---- the finish of a capped hybrid search (rlr_search_capped; DESIGN.md "Capped hybrid search") ----------------------
+// -0 and +0 combined scores tie: the row decides
+__device__ inline uint32_t capped_comb_key(float c)
+{
+    return score_key(c == 0.0f ? 0.0f : c);
+}
+
+// The key of a combined score that no row the collect left behind can exceed, for a group whose per_doc-th nominated value
+// is t (-inf: a smaller group, an untagged row).  Such a row has a < fmaxf(t, u) - 2 eps in the collect's own arithmetic and
+// |a - e| <= eps, so e < (that threshold) + eps; the sum below is rounded to nearest and then stepped up once, so it is no
+// smaller than the real sum, and rounding is monotone: combined(e) <= combined(bound).  0: the threshold is -inf, the
+// collect left no row of this group behind.  ~0: the bound is no number -- nothing can be decided against it.
+__device__ inline uint32_t capped_bound_key(float t, float u, float two_eps, float eps, float w_e, float w_l)
+{
+    const float thr = fmaxf(t, u) - two_eps;
+    if (thr == -__builtin_inff())
+        return 0u;
+    float eb = thr + eps;
+    if (!(eb == eb))
+        return 0xFFFFFFFFu;
+    if (eb == 0.0f)
+        eb = 0.0f; // (-0 steps up from +0)
+    if (eb != __builtin_inff()) {
+        const uint32_t b = __builtin_bit_cast(uint32_t, eb);
+        eb = __builtin_bit_cast(float, (b & 0x80000000u) ? b - 1u : b + 1u);
+    }
+    const float t0 = w_e * eb;
+    const float t1 = w_l * 0.0f;
+    const float cb = t0 + t1;
+    return cb == cb ? capped_comb_key(cb) : 0xFFFFFFFFu;
+}
+
+// One workgroup in place of group_finish_kernel.  Entries [0, n_raw) are the re-scored grouped candidates, entries
+// [n_raw, n_raw + n_lex) the lexical rows no candidate is (a lexical row that is a candidate is blended where it sits:
+// once).  combined = w_e * cos + w_l * lexn in the arithmetic of pool_prepare.h; every entry is ranked inside its document
+// by (combined, row), entries ranked below per_doc are accepted, the accepted ones are ordered and the first `need` become
+// the pool.  LDS: kCappedSlots (= kGroupCap + kCappedLexMax = 4096) entries x 16 B + kCappedLexMax flags = 72 KB.
+// status 1: more candidates or lexical rows than that (or the collect / the table overflowed); status 2: the boundary rule
+// below cannot decide, or rows that order last (NaN) would be needed to fill the pool.
+//
+// The boundary rule.  Every row outside the union is non-lexical and bounded by capped_bound_key of its group.  A group is
+// closed when per_doc of its entries lie STRICTLY above its bound: whatever it left behind is capped out.  The bound of
+// every other group with rows left behind (untagged rows and groups without an entry have t <= u: the bound of u covers
+// them) must lie strictly below the need-th accepted entry: the walk ends before it reaches such a row.  If the collect
+// left no row behind (n_raw == n_valid) there is nothing to bound.
+__global__ __launch_bounds__(1024) void capped_finish_kernel(GroupDev a, CappedArgs c)
+{
+    __shared__ uint64_t s_key[kCappedSlots];
+    __shared__ uint32_t s_doc[kCappedSlots];
+    __shared__ uint32_t s_acc[kCappedSlots];
+    __shared__ uint32_t s_flag[kCappedLexMax]; // lexical pair j is one of the candidates
+    __shared__ uint32_t s_nacc, s_nan, s_req, s_tkey, s_status, s_side;
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < kHistBins; i += 1024)
+        a.ctx_hist[i] = 0; // the scan counted its scores into the context's digit-1 histogram; nothing here read it
+    const uint32_t n_raw = a.st->n_cand, flags = a.st->flags, n_valid = a.st->n_valid;
+    const float u = __builtin_bit_cast(float, a.st->u_bits);
+    const uint32_t need = a.k, m = a.per_doc, n_lex = min(c.n_lex, kCappedLexMax);
+    float *cc = c.scratch, *ce = c.scratch + kCappedSlots, *cl = c.scratch + 2 * kCappedSlots;
+    if (tid == 0) {
+        s_nacc = 0;
+        s_nan = 0;
+        s_req = 0;
+        s_tkey = 0;
+        s_side = 0;
+    }
+    const bool capacity = flags != 0 || n_raw > kGroupCap || c.n_lex > kCappedLexMax; // (uniform)
+    const bool all_collected = n_raw == n_valid;
+    if (!capacity) {
+        const uint32_t total = n_raw + n_lex;
+        for (uint32_t j = tid; j < n_lex; j += 1024)
+            s_flag[j] = 0;
+        __syncthreads();
+        for (uint32_t i = tid; i < n_raw; i += 1024) {
+            const uint64_t p = a.cand[i];
+            const uint32_t row = 0xFFFFFFFFu - static_cast<uint32_t>(p);
+            const float e = key_score(static_cast<uint32_t>(p >> 32));
+            float l = 0.0f;
+            uint32_t lo = 0, hi = n_lex;
+            while (lo < hi) { // the lexical rows ascend
+                const uint32_t mid = (lo + hi) >> 1;
+                if (c.lrow[mid] < row)
+                    lo = mid + 1;
+                else
+                    hi = mid;
+            }
+            if (lo < n_lex && c.lrow[lo] == row) {
+                l = c.lscore[lo] / c.max_lex;
+                s_flag[lo] = 1;
+            }
+            const float t0 = c.w_e * e;
+            const float t1 = c.w_l * l;
+            const float cmb = t0 + t1;
+            cc[i] = cmb;
+            ce[i] = e;
+            cl[i] = l;
+            if (cmb == cmb) {
+                s_key[i] = (static_cast<uint64_t>(capped_comb_key(cmb)) << 32) | (p & 0xFFFFFFFFull);
+            } else { // orders last: only wanted when the numbers run out, and then the exact form answers
+                s_key[i] = 0ull;
+                s_nan = 1;
+            }
+            s_doc[i] = a.cand_doc[i];
+        }
+        __syncthreads();
+        for (uint32_t j = tid; j < n_lex; j += 1024) {
+            const uint32_t slot = n_raw + j;
+            uint64_t key = 0ull;
+            uint32_t d = RLR_DOC_NONE;
+            if (!s_flag[j]) {
+                const uint32_t row = c.lrow[j];
+                const float e = c.lcos[j];
+                const float l = c.lscore[j] / c.max_lex;
+                const float t0 = c.w_e * e;
+                const float t1 = c.w_l * l;
+                const float cmb = t0 + t1;
+                cc[slot] = cmb;
+                ce[slot] = e;
+                cl[slot] = l;
+                if (cmb == cmb) {
+                    key = (static_cast<uint64_t>(capped_comb_key(cmb)) << 32) | (0xFFFFFFFFu - row);
+                    d = a.docs ? a.docs[row] : RLR_DOC_NONE;
+                } else {
+                    s_nan = 1;
+                }
+            }
+            s_key[slot] = key;
+            s_doc[slot] = d;
+        }
+        __syncthreads();
+        if (tid == 0 && !all_collected) {
+            const uint32_t kb = capped_bound_key(-__builtin_inff(), u, a.two_eps, c.eps, c.w_e, c.w_l);
+            if (kb != 0u)
+                atomicMax(&s_req, kb);
+        }
+        for (uint32_t i = tid; i < total; i += 1024) {
+            const uint64_t mine = s_key[i];
+            const uint32_t d = s_doc[i];
+            uint32_t ahead = 0;
+            if (mine != 0ull && d != RLR_DOC_NONE) {
+                uint32_t kb = 0u;
+                if (!all_collected) {
+                    const uint32_t slot = group_find(a.tab_keys, a.tab_bits, d);
+                    const uint32_t tkey =
+                        slot != kNoSlot ? static_cast<uint32_t>(a.tab_vals[static_cast<uint64_t>(slot) * m + m - 1] >> 32) : 0u;
+                    kb = capped_bound_key(tkey ? key_score(tkey) : -__builtin_inff(), u, a.two_eps, c.eps, c.w_e, c.w_l);
+                }
+                uint32_t above = 0;
+                for (uint32_t j = 0; j < total; ++j) {
+                    const uint64_t kj = s_key[j];
+                    const bool same = s_doc[j] == d && kj != 0ull;
+                    ahead += (same && kj > mine) ? 1u : 0u;
+                    above += (same && static_cast<uint32_t>(kj >> 32) > kb) ? 1u : 0u;
+                }
+                if (kb != 0u && above < m)
+                    atomicMax(&s_req, kb); // an open group with rows left behind
+            }
+            s_acc[i] = (mine != 0ull && ahead < m) ? 1u : 0u;
+        }
+        __syncthreads();
+        for (uint32_t i = tid; i < total; i += 1024) {
+            if (!s_acc[i])
+                continue;
+            const uint64_t mine = s_key[i];
+            uint32_t pos = 0;
+            for (uint32_t j = 0; j < total; ++j)
+                pos += (s_acc[j] && s_key[j] > mine) ? 1u : 0u;
+            atomicAdd(&s_nacc, 1u);
+            if (pos < need) {
+                const uint32_t row = 0xFFFFFFFFu - static_cast<uint32_t>(mine), d = s_doc[i];
+                c.list[pos] = row;
+                c.comb[pos] = cc[i];
+                c.cosv[pos] = ce[i];
+                c.lexv[pos] = cl[i];
+                c.h_side[2 + pos] = row;
+                c.h_side[2 + need + pos] = d;
+                atomicAdd(&s_side, result_chk_term(row, 2 + pos) + result_chk_term(d, 2 + need + pos));
+                if (pos == need - 1)
+                    s_tkey = static_cast<uint32_t>(mine >> 32);
+            }
+        }
+    }
+    __syncthreads();
+    const uint32_t n_acc = s_nacc, n_pool = min(n_acc, need);
+    if (tid == 0) {
+        uint32_t status = capacity ? 1u : 0u;
+        if (!status && s_req != 0u && !(n_acc >= need && s_tkey > s_req))
+            status = 2u; // a row left behind may tie with, or precede, the last entry that counts
+        if (!status && n_acc < need && (n_valid < c.n_allowed || s_nan != 0u))
+            status = 2u; // the numbers ran out: the rows that order last are wanted
+        c.info[0] = status ? 0u : n_pool;
+        c.info[1] = status;
+        s_status = status;
+    }
+    for (uint32_t r = n_pool + tid; r < need; r += 1024) { // unused slots: a valid row, never read by the greedy kernel
+        c.list[r] = 0;
+        c.comb[r] = 0.0f;
+        c.cosv[r] = 0.0f;
+        c.lexv[r] = 0.0f;
+    }
+    __threadfence_system();
+    __syncthreads();
+    const uint32_t status = s_status;
+    if (tid == 0) {
+        c.h_side[1] = status ? 0u : s_side;
+        __threadfence_system();
+        c.h_side[0] = status ? 0u : n_pool;
+    }
+    if (c.h_out)
+        hybrid_emit_body(c.list, c.comb, c.cosv, c.lexv, status ? 0u : min(n_pool, c.k_cap), status, c.k_cap, c.h_out);
+}
+
 __global__ __launch_bounds__(kGroupBlock) void group_iota_kernel(uint32_t *__restrict__ list, uint32_t n)
 {
     for (uint32_t i = blockIdx.x * kGroupBlock + threadIdx.x; i < n; i += gridDim.x * kGroupBlock)
@@ -425,7 +642,7 @@ hipError_t launch_group_tail(const GroupArgs &a, hipStream_t s, hipEvent_t after
     uint32_t cpb;
     size_t staging;
     if (a.n == 0 || a.k == 0 || a.k > kGroupKMax || a.per_doc == 0 || a.per_doc > RLR_MAX_PER_DOCUMENT || a.tab_bits < 1 ||
-        a.tab_bits > 31 || !group_shape(a.pitch16, a.dim, a.dtype, &cpb, &staging))
+        a.tab_bits > 31 || !group_shape(a.pitch16, a.dim, a.dtype, &cpb, &staging) || (a.capped && a.capped->n_lex > kCappedLexMax))
         return hipErrorInvalidValue;
     GroupDev d;
     d.scores = a.scores;
@@ -476,7 +693,10 @@ hipError_t launch_group_tail(const GroupArgs &a, hipStream_t s, hipEvent_t after
         hipLaunchKernelGGL(group_collect_kernel<true>, dim3(collect_blocks), dim3(kGroupBlock), staging, s, d);
     else
         hipLaunchKernelGGL(group_collect_kernel<false>, dim3(collect_blocks), dim3(kGroupBlock), staging, s, d);
-    hipLaunchKernelGGL(group_finish_kernel, dim3(1), dim3(1024), 0, s, d);
+    if (a.capped)
+        hipLaunchKernelGGL(capped_finish_kernel, dim3(1), dim3(1024), 0, s, d, *a.capped);
+    else
+        hipLaunchKernelGGL(group_finish_kernel, dim3(1), dim3(1024), 0, s, d);
     return hipGetLastError();
 }
 

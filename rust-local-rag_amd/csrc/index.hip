@@ -226,6 +226,7 @@ struct rlr_index {
     // goes through upload): a row filter records it at creation and is refused as stale once it has moved on
     std::atomic<uint64_t> mutations{0};
     uint64_t grouped_forms[4] = {0, 0, 0, 0}; // rlr_index_grouped_forms: queries served by each form (mu)
+    uint64_t capped_forms[4] = {0, 0, 0, 0};  // rlr_index_capped_forms: the same for rlr_search_capped (mu)
 };
 
 // A set of rows of one index, fixed at creation (rlr_filter_create_*): one bit per index row on the device (tail bits of
@@ -1141,39 +1142,6 @@ __global__ __launch_bounds__(1024) void lex_unpack_batch_kernel(const uint64_t *
     const uint32_t q = blockIdx.x;
     lex_unpack_body(packed + static_cast<size_t>(q) * sel_stride, count + static_cast<size_t>(q) * count_stride, limit, n_rows,
                     lrow + static_cast<size_t>(q) * bound, lscore + static_cast<size_t>(q) * bound, hdr + q);
-}
-
-// [row u32 | cos f32 | combined f32 | lexical f32] x k_cap, then n, status, checksum, done (the layout the greedy kernel's
-// emit tail writes) into pinned host memory, by all threads of one workgroup
-__device__ inline void hybrid_emit_body(const uint32_t *list, const float *comb, const float *cosv, const float *lexv, uint32_t n,
-                                        uint32_t status, uint32_t k_cap, uint32_t *__restrict__ h_out)
-{
-    __shared__ uint32_t s_chk;
-    if (threadIdx.x == 0)
-        s_chk = 0;
-    __syncthreads();
-    uint32_t chk = 0;
-    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-        const uint32_t w0 = list[i], w1 = __builtin_bit_cast(uint32_t, cosv[i]), w2 = __builtin_bit_cast(uint32_t, comb[i]);
-        const uint32_t w3 = __builtin_bit_cast(uint32_t, lexv[i]);
-        h_out[block_value(k_cap, kBlockRow, i)] = w0;
-        h_out[block_value(k_cap, kBlockCos, i)] = w1;
-        h_out[block_value(k_cap, kBlockComb, i)] = w2;
-        h_out[block_value(k_cap, kBlockLex, i)] = w3;
-        chk += result_chk_term(w0, block_value(k_cap, kBlockRow, i)) + result_chk_term(w1, block_value(k_cap, kBlockCos, i)) +
-               result_chk_term(w2, block_value(k_cap, kBlockComb, i)) + result_chk_term(w3, block_value(k_cap, kBlockLex, i));
-    }
-    if (chk)
-        atomicAdd(&s_chk, chk);
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) { // (the greedy kernel's emit tail writes the same four words)
-        h_out[block_n(k_cap)] = n;
-        h_out[block_status(k_cap)] = status;
-        h_out[block_chk(k_cap)] = block_chk_tail(s_chk, n, status, k_cap);
-        __threadfence_system();
-        h_out[block_done(k_cap)] = kBlockDone;
-    }
 }
 
 __device__ inline void hybrid_pool_body(const uint64_t *__restrict__ packed, uint32_t fetch, uint32_t need, uint32_t n_rows,
@@ -2483,14 +2451,15 @@ uint32_t grouped_walk(std::vector<uint64_t> &keys, const std::vector<uint32_t> &
     return n;
 }
 
-// The exact form: reference-order scores of every allowed row, copied back, and the walk on the host.  Slow and always
-// right.  The query is in c->d_query.
-int32_t grouped_exact(rlr_index *ix, Ctx *c, const rlr_filter *f, uint32_t k, uint32_t per_doc, uint64_t *res, uint32_t *res_docs,
-                      uint32_t *n_res)
+// Reference-order scores of every allowed row (all rows, or the rows of `f`), copied back with the document column: what
+// the exact forms of the grouped and the capped search walk over.  The query is in c->d_query.  list[i] = the i-th allowed
+// row, vals[i] = its score, docs = the whole column (empty: no column).
+int32_t exact_scores(rlr_index *ix, Ctx *c, const rlr_filter *f, std::vector<uint32_t> &list, std::vector<float> &vals,
+                     std::vector<uint32_t> &docs)
 {
     hipStream_t s = c->stream;
     const uint32_t n = static_cast<uint32_t>(f ? f->n_allowed : ix->n_rows);
-    std::vector<uint32_t> list(n);
+    list.assign(n, 0);
     RLR_TRY(reserve_list(c, n));
     if (f) {
         uint32_t at = 0;
@@ -2505,16 +2474,73 @@ int32_t grouped_exact(rlr_index *ix, Ctx *c, const rlr_filter *f, uint32_t k, ui
     }
     RLR_HIP(launch_score_rows(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, c->d_query.get(), f ? f->d_list.get() : c->d_list.get(), n,
                               c->d_vals.get(), s));
-    std::vector<float> vals(n);
-    std::vector<uint32_t> docs(ix->d_docs ? ix->n_rows : 0);
+    vals.assign(n, 0.0f);
+    docs.assign(ix->d_docs ? ix->n_rows : 0, 0);
     RLR_HIP(hipMemcpyAsync(vals.data(), c->d_vals.get(), static_cast<size_t>(n) * sizeof(float), hipMemcpyDeviceToHost, s));
     if (!docs.empty())
         RLR_HIP(hipMemcpyAsync(docs.data(), ix->d_docs.get(), docs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     RLR_HIP(hipStreamSynchronize(s));
-    std::vector<uint64_t> keys(n);
-    for (uint32_t i = 0; i < n; ++i)
+    return RLR_OK;
+}
+
+// The exact form: reference-order scores of every allowed row, copied back, and the walk on the host.  Slow and always
+// right.  The query is in c->d_query.
+int32_t grouped_exact(rlr_index *ix, Ctx *c, const rlr_filter *f, uint32_t k, uint32_t per_doc, uint64_t *res, uint32_t *res_docs,
+                      uint32_t *n_res)
+{
+    std::vector<uint32_t> list, docs;
+    std::vector<float> vals;
+    RLR_TRY(exact_scores(ix, c, f, list, vals, docs));
+    std::vector<uint64_t> keys(list.size());
+    for (size_t i = 0; i < list.size(); ++i)
         keys[i] = pack_result(vals[i], list[i]);
     *n_res = grouped_walk(keys, docs, k, per_doc, res, res_docs);
+    return RLR_OK;
+}
+
+// The table of a grouped tail holds twice the documents it can meet (one per allowed row at most); > 31: by rule, no table.
+uint32_t group_table_bits(uint64_t n_allowed)
+{
+    uint32_t tab_bits = 10;
+    while (tab_bits < 32 && (1ull << tab_bits) < 2 * n_allowed)
+        tab_bits++;
+    return tab_bits;
+}
+
+// Reserve the context's grouped-search state and describe one grouped tail over the scores the scan leaves in c->d_scores
+// (the query in c->d_query); out / meta / capped are the caller's.
+int32_t make_group_args(rlr_index *ix, Ctx *c, uint32_t k, uint32_t per_doc, float two_eps, uint32_t tab_bits, GroupArgs *out)
+{
+    const uint32_t n = static_cast<uint32_t>(ix->n_rows);
+    if (ix->d_docs)
+        RLR_HIP(reserve_group(Want{c->d_gkeys, static_cast<size_t>(1) << tab_bits},
+                              Want{c->d_gvals, (static_cast<size_t>(1) << tab_bits) * per_doc}));
+    RLR_HIP(c->d_gtg.reserve(std::max<uint32_t>(n, 1024)));
+    RLR_HIP(reserve_group(Want{c->d_ghist, 2 * kHistBins}, Want{c->d_gstate, 1}, Want{c->d_gcand, kGroupCap}, Want{c->d_gcdoc, kGroupCap}));
+    GroupArgs &ga = *out;
+    ga.scores = c->d_scores.get();
+    ga.docs = ix->d_docs.get();
+    ga.n = n;
+    ga.k = k;
+    ga.per_doc = per_doc;
+    ga.two_eps = two_eps;
+    ga.tab_keys = c->d_gkeys.get();
+    ga.tab_vals = c->d_gvals.get();
+    ga.tab_bits = tab_bits;
+    ga.tg = c->d_gtg.get();
+    ga.hist = c->d_ghist.get();
+    ga.st = c->d_gstate.get();
+    ga.rows = ix->d_rows.get();
+    ga.pitch16 = ix->pitch16;
+    ga.dim = ix->dim;
+    ga.dtype = ix->dtype;
+    ga.query = c->d_query.get();
+    ga.cand = c->d_gcand.get();
+    ga.cand_doc = c->d_gcdoc.get();
+    ga.out = nullptr;
+    ga.meta = nullptr;
+    ga.ctx_hist = c->d_hist.get();
+    ga.n_cu = ix->n_cu;
     return RLR_OK;
 }
 
@@ -2538,43 +2564,14 @@ int32_t grouped_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *q
     std::vector<uint32_t> ex_docs;
     const uint64_t *res = h_res;
     const uint32_t *res_docs = reinterpret_cast<const uint32_t *>(h_res + p.k);
-    // the table holds twice the documents it can meet (one per allowed row at most)
-    uint32_t tab_bits = 10;
-    while (tab_bits < 32 && (1ull << tab_bits) < 2 * n_allowed)
-        tab_bits++;
+    const uint32_t tab_bits = group_table_bits(n_allowed);
     if ((f && f->path == 0) || p.k > kGroupKMax || tab_bits > 31 || !group_fits(ix->pitch16, ix->dim, ix->dtype)) {
         form = 3; // by rule: a list-path filter, k beyond the finish, rows beyond the staged re-score
     } else {
-        const uint32_t n = static_cast<uint32_t>(ix->n_rows);
-        if (ix->d_docs)
-            RLR_HIP(reserve_group(Want{c->d_gkeys, static_cast<size_t>(1) << tab_bits},
-                                  Want{c->d_gvals, (static_cast<size_t>(1) << tab_bits) * per_doc}));
-        RLR_HIP(c->d_gtg.reserve(std::max<uint32_t>(n, 1024)));
-        RLR_HIP(reserve_group(Want{c->d_ghist, 2 * kHistBins}, Want{c->d_gstate, 1}, Want{c->d_gcand, kGroupCap}, Want{c->d_gcdoc, kGroupCap}));
         GroupArgs ga;
-        ga.scores = c->d_scores.get();
-        ga.docs = ix->d_docs.get();
-        ga.n = n;
-        ga.k = p.k;
-        ga.per_doc = per_doc;
-        ga.two_eps = p.two_eps;
-        ga.tab_keys = c->d_gkeys.get();
-        ga.tab_vals = c->d_gvals.get();
-        ga.tab_bits = tab_bits;
-        ga.tg = c->d_gtg.get();
-        ga.hist = c->d_ghist.get();
-        ga.st = c->d_gstate.get();
-        ga.rows = ix->d_rows.get();
-        ga.pitch16 = ix->pitch16;
-        ga.dim = ix->dim;
-        ga.dtype = ix->dtype;
-        ga.query = c->d_query.get();
-        ga.cand = c->d_gcand.get();
-        ga.cand_doc = c->d_gcdoc.get();
+        RLR_TRY(make_group_args(ix, c, p.k, per_doc, p.two_eps, tab_bits, &ga));
         ga.out = h_res;
         ga.meta = h_meta;
-        ga.ctx_hist = c->d_hist.get();
-        ga.n_cu = ix->n_cu;
         arm_meta(h_meta, 1);
         // (the masked scan for a filter; without one the scan over the master rows too: no nomination copy, as filtered calls)
         RLR_HIP(enqueue_query_scan(ix, c, 0, timed, f, /*master_rows=*/true));
@@ -4491,6 +4488,312 @@ int32_t rlr_search_hybrid(rlr_index *ix, const float *query, uint32_t need, uint
     src.n_host = n_lex;
     src.max_lex = max_lex;
     return rlr::hybrid_finish_impl(t, src, rows_out, cos_out, score_out, lex_out, n_out, fallback);
+}
+
+// ---- capped hybrid search (rlr_search_capped): at most per_doc results per document, in combined order ---------------
+// One pool entry on the host: what the exact form builds and every form hands back.
+struct CappedHit {
+    uint32_t row, doc;
+    float c, e, l;
+};
+
+// (combined desc, NaN last, row asc), -0 and +0 tying: the engine's candidate order
+static bool capped_before(const CappedHit &a, const CappedHit &b)
+{
+    const bool an = std::isnan(a.c), bn = std::isnan(b.c);
+    if (an || bn)
+        return an != bn ? bn : a.row < b.row;
+    if (a.c != b.c)
+        return a.c > b.c;
+    return a.row < b.row;
+}
+
+// A capped call's workspace: device (c->d_pool) and pinned (c->h_pin: the staged query | the lexical pairs, rows then
+// scores as on the device -- one copy | the pool's rows and document ids | the result block).
+struct CappedWs {
+    uint64_t P, n_lex, q_pitch, k_cap, gram_floats;
+    Carver d, h;
+    float *gram = d.take<float>(gram_floats), *comb = d.take<float>(P), *cos = d.take<float>(P), *lexv = d.take<float>(P);
+    uint32_t *order = d.take<uint32_t>(P);
+    float *mmr = d.take<float>(P);
+    uint32_t *nsel = d.take<uint32_t>(1), *info = d.take<uint32_t>(7);
+    uint32_t *lrow = d.take<uint32_t>(n_lex);
+    float *lscore = d.take<float>(n_lex), *lcos = d.take<float>(n_lex);
+    float *scratch = d.take<float>(3ull * rlr::kCappedSlots);
+    float *h_q = h.take<float>(q_pitch);
+    uint32_t *h_lrow = h.take<uint32_t>(n_lex);
+    float *h_lscore = h.take<float>(n_lex);
+    uint32_t *h_side = h.take<uint32_t>(rlr::capped_side_words(static_cast<uint32_t>(P)));
+    uint32_t *h_out = h.take<uint32_t>(block_words(static_cast<uint32_t>(k_cap)));
+    char *h_pad = h.take<char>(64);
+    CappedWs(float *d_base, void *h_base, uint32_t q_pitch_, uint32_t P_, uint32_t n_lex_, uint32_t k_cap_, bool diversify)
+        : P(P_), n_lex(n_lex_), q_pitch(q_pitch_), k_cap(k_cap_), gram_floats(diversify ? static_cast<uint64_t>(P_) * P_ : 0),
+          d(d_base), h(h_base) {}
+};
+
+struct CappedCall {
+    const float *query;
+    uint32_t need, k; // need: already min(., |A|)
+    float lambda;
+    bool diversify;
+    float w_e, w_l;
+    std::vector<uint32_t> lrow; // the lexical rows inside A, ascending and unique
+    std::vector<float> lscore;
+    float max_lex;
+    uint32_t per_doc;
+    float guard_eps;
+};
+
+// The exact form: reference-order scores of every allowed row, the blend and the walk on the host.  Slow and always
+// right.  The query is in c->d_query.  pool: the first `need` accepted rows in order.
+static int32_t capped_exact(rlr_index *ix, Ctx *c, const rlr_filter *f, const CappedCall &call, std::vector<CappedHit> &pool)
+{
+    std::vector<uint32_t> list, docs;
+    std::vector<float> vals;
+    RLR_TRY(exact_scores(ix, c, f, list, vals, docs));
+    const uint32_t n = static_cast<uint32_t>(list.size());
+    std::vector<CappedHit> all(n);
+    size_t lj = 0; // (the allowed rows and the lexical rows both ascend)
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t row = list[i];
+        while (lj < call.lrow.size() && call.lrow[lj] < row)
+            ++lj;
+        const float l = lj < call.lrow.size() && call.lrow[lj] == row ? call.lscore[lj] / call.max_lex : 0.0f;
+        const float t0 = call.w_e * vals[i]; // two rounded products, one add (engine_host.h: combine)
+        const float t1 = call.w_l * l;
+        all[i] = CappedHit{row, docs.empty() ? RLR_DOC_NONE : docs[row], t0 + t1, vals[i], l};
+    }
+    std::sort(all.begin(), all.end(), capped_before);
+    std::unordered_map<uint32_t, uint32_t> taken;
+    pool.clear();
+    for (size_t i = 0; i < all.size() && pool.size() < call.need; ++i) {
+        if (all[i].doc != RLR_DOC_NONE && taken[all[i].doc]++ >= call.per_doc)
+            continue;
+        pool.push_back(all[i]);
+    }
+    return RLR_OK;
+}
+
+// One capped query over all rows (f == nullptr) or the rows of `f` (n_allowed > 0); call.need > 0.  The scan, group.hip's
+// tail with the capped finish, then -- diversified -- the Gram and greedy launches in the same enqueue.  Every hand-off to
+// the exact form is counted (form 1..3).  *picked: the results are in `hits` (form 0, or no diversification); else `hits` is
+// the pool of the exact form and the caller runs the MMR selection over it once the context is back.
+static int32_t capped_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const CappedCall &call, std::vector<CappedHit> &hits,
+                            bool *picked)
+{
+    const uint64_t n_allowed = f ? f->n_allowed : ix->n_rows;
+    const uint32_t need = call.need, n_lex = static_cast<uint32_t>(call.lrow.size());
+    const SearchPlan p = make_plan(ix, call.query, 1, need, call.guard_eps);
+    RLR_TRY(ctx_prepare(ix, c, 1, p));
+    // by rule first: what the exact form answers needs the staged query alone -- no pool, no Gram matrix of need x need
+    const uint32_t tab_bits = group_table_bits(n_allowed);
+    bool lex_ok = std::isfinite(call.max_lex) && call.max_lex > 0.0f;
+    for (uint32_t i = 0; i < n_lex && lex_ok; ++i)
+        lex_ok = call.lscore[i] >= 0.0f; // (the proof needs w_l * lexn >= 0; NaN compares false)
+    const bool by_rule = (f && f->path == 0) || need > kGroupKMax || n_lex > rlr::kCappedLexMax || tab_bits > 31 ||
+                         !(call.w_e > 0.0f) || !std::isfinite(call.w_e) || !(call.w_l >= 0.0f) || !std::isfinite(call.w_l) || !lex_ok ||
+                         !group_fits(ix->pitch16, ix->dim, ix->dtype);
+    const uint32_t P = by_rule ? 0 : need;
+    const uint32_t k_cap = by_rule ? 0 : rlr::result_k_cap(call.k, P, call.diversify);
+    const uint32_t n_lex_ws = by_rule ? 0 : n_lex;
+    const CappedWs sizes(nullptr, nullptr, ix->q_pitch, P, n_lex_ws, k_cap, call.diversify);
+    RLR_HIP(c->d_pool.reserve(sizes.d.floats()));
+    RLR_TRY(reserve_list(c, std::max<uint32_t>(std::max<uint32_t>(P, n_lex_ws), 1)));
+    RLR_TRY(pin_reserve(c, sizes.h.bytes));
+    const CappedWs ws(c->d_pool.get(), c->h_pin.get(), ix->q_pitch, P, n_lex_ws, k_cap, call.diversify);
+    hipStream_t s = c->stream;
+    const bool timed = ix->profiling;
+    stage_queries(ix, c, call.query, 1, ws.h_q);
+    c->h_q_kq = nullptr;
+    RLR_HIP(upload_queries(c, ws.h_q, static_cast<size_t>(ix->q_pitch) * sizeof(float), s));
+    uint64_t n_cand = 0;
+    uint32_t form = 0;
+    if (by_rule) {
+        form = 3;
+    } else {
+        rlr::CappedArgs ca;
+        ca.w_e = call.w_e;
+        ca.w_l = call.w_l;
+        ca.eps = p.two_eps * 0.5f;
+        ca.n_allowed = static_cast<uint32_t>(n_allowed);
+        ca.lrow = ws.lrow;
+        ca.lscore = ws.lscore;
+        ca.lcos = ws.lcos;
+        ca.n_lex = n_lex;
+        ca.max_lex = call.max_lex;
+        ca.scratch = ws.scratch;
+        ca.list = c->d_list.get();
+        ca.comb = ws.comb;
+        ca.cosv = ws.cos;
+        ca.lexv = ws.lexv;
+        ca.info = ws.info;
+        ca.h_side = ws.h_side;
+        ca.k_cap = k_cap;
+        ca.h_out = call.diversify ? nullptr : ws.h_out;
+        GroupArgs ga;
+        RLR_TRY(make_group_args(ix, c, need, call.per_doc, p.two_eps, tab_bits, &ga));
+        ga.capped = &ca;
+        uint32_t *h_out = ws.h_out;
+        h_out[block_done(k_cap)] = kBlockPending; // (the last kernel's last store replaces it: what the wait below polls)
+        ws.h_side[0] = 0xFFFFFFFFu;
+        if (n_lex) { // the pairs and, behind the scan, their exact cosines
+            std::memcpy(ws.h_lrow, call.lrow.data(), static_cast<size_t>(n_lex) * sizeof(uint32_t));
+            std::memcpy(ws.h_lscore, call.lscore.data(), static_cast<size_t>(n_lex) * sizeof(float));
+            RLR_HIP(hipMemcpyAsync(ws.lrow, ws.h_lrow, static_cast<size_t>(n_lex) * 8, hipMemcpyHostToDevice, s));
+        }
+        // (the masked scan for a filter; without one the scan over the master rows too: no nomination copy, as grouped calls)
+        RLR_HIP(enqueue_query_scan(ix, c, 0, timed, f, /*master_rows=*/true));
+        RLR_HIP(launch_score_rows(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, c->d_query.get(), ws.lrow, n_lex, ws.lcos, s));
+        RLR_HIP(launch_group_tail(ga, s, timed ? c->ev[2] : nullptr));
+        if (call.diversify) {
+            RLR_HIP(launch_gram_rows(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, c->d_list.get(), P, ws.gram, 1, s));
+            const rlr::MmrEmit emit = mmr_emit(c->d_list.get(), ws.comb, ws.cos, ws.lexv, ws.info, k_cap, h_out);
+            RLR_HIP(launch_mmr_greedy(ws.gram, ws.comb, P, call.k, call.lambda, ws.order, ws.mmr, ws.nsel, ws.info, 1, s, &emit));
+        }
+        if (timed) {
+            RLR_HIP(hipEventRecord(c->ev[3], s));
+            RLR_HIP(hipStreamSynchronize(s));
+        } else {
+            RLR_TRY(wait_block(h_out, k_cap, s, &c->wait_ema));
+        }
+        RLR_TRY(check_hist_assert(c));
+        std::vector<uint64_t> r_rows(k_cap);
+        std::vector<float> r_cos(k_cap), r_comb(k_cap), r_lex(k_cap);
+        uint32_t n_res = 0;
+        const uint32_t status = read_block(h_out, k_cap, r_rows.data(), r_cos.data(), r_comb.data(), r_lex.data(), &n_res);
+        if (status != 0) {
+            form = status == 1 ? 1 : 2; // capacity | undecidable here (a boundary tie, rows that order last are wanted)
+        } else {
+            // the pool's rows and document ids: written by the finish, ahead of the block's last store on the stream
+            const volatile uint32_t *side = ws.h_side;
+            auto side_ok = [&]() {
+                const uint32_t ns = side[0];
+                if (ns > P)
+                    return false;
+                uint32_t chk = 0;
+                for (uint32_t i = 0; i < ns; ++i)
+                    chk += result_chk_term(side[2 + i], 2 + i) + result_chk_term(side[2 + P + i], 2 + P + i);
+                return chk == side[1];
+            };
+            if (!side_ok()) {
+                RLR_HIP(hipStreamSynchronize(s));
+                if (!side_ok())
+                    return set_error(RLR_E_INTERNAL, "capped search: the pool's document ids never arrived");
+            }
+            const uint32_t ns = side[0];
+            n_cand = ns;
+            hits.resize(n_res);
+            for (uint32_t i = 0; i < n_res && form == 0; ++i) {
+                const uint32_t row = static_cast<uint32_t>(r_rows[i]);
+                uint32_t at = call.diversify ? 0 : i; // (no diversification: result i is pool slot i)
+                while (at < ns && side[2 + at] != row)
+                    ++at;
+                if (at >= ns || (f && !filter_holds(f, row)))
+                    form = 2; // a masked row came back (the hazard filtered_query documents)
+                else
+                    hits[i] = CappedHit{row, side[2 + P + at], r_comb[i], r_cos[i], r_lex[i]};
+            }
+        }
+    }
+    *picked = true;
+    if (form != 0) {
+        RLR_TRY(capped_exact(ix, c, f, call, hits));
+        *picked = !call.diversify;
+    }
+    c->hist_dirty = false;
+    {
+        std::lock_guard<std::mutex> lk(ix->mu);
+        ix->capped_forms[form]++;
+    }
+    return note_search(ix, c, 1, n_cand, form != 0 ? 1 : 0, timed && form != 3);
+}
+
+int32_t rlr_search_capped(rlr_index *ix, const rlr_filter *f, const float *query, uint32_t need_in, uint32_t k, float lambda,
+                          int32_t diversify, float w_embedding, float w_lexical, const uint64_t *lex_rows, const float *lex_scores,
+                          uint32_t n_lex, float max_lex, uint32_t per_doc, float guard_eps, uint64_t *rows_out, float *cos_out,
+                          float *score_out, float *lex_out, uint32_t *docs_out, uint32_t *n_out)
+{
+    RLR_TRY(check_handle(ix));
+    if (f)
+        RLR_TRY(check_filter(ix, f)); // (a stale filter is refused before any GPU work)
+    if (per_doc < 1 || per_doc > RLR_MAX_PER_DOCUMENT)
+        return set_error(RLR_E_INVALID, "per_doc must be in 1..%d (per_doc = %u)", RLR_MAX_PER_DOCUMENT, per_doc);
+    if (!n_out)
+        return set_error(RLR_E_INVALID, "n_out is null");
+    *n_out = 0;
+    const uint64_t n_allowed = f ? f->n_allowed : ix->n_rows;
+    if (n_allowed == 0 || need_in == 0)
+        return RLR_OK;
+    if (!query || !rows_out || !cos_out || !score_out || !lex_out || (n_lex && (!lex_rows || !lex_scores)))
+        return set_error(RLR_E_INVALID, "null argument");
+    CappedCall call;
+    call.query = query;
+    call.need = static_cast<uint32_t>(std::min<uint64_t>(need_in, n_allowed));
+    call.k = k;
+    call.lambda = lambda;
+    call.diversify = diversify != 0;
+    call.w_e = w_embedding;
+    call.w_l = w_lexical;
+    call.max_lex = max_lex;
+    call.per_doc = per_doc;
+    call.guard_eps = guard_eps;
+    for (uint32_t i = 0; i < n_lex; ++i) {
+        if (lex_rows[i] >= ix->n_rows || (i && lex_rows[i] <= lex_rows[i - 1]))
+            return set_error(RLR_E_INVALID, "lex_rows must be ascending, unique and inside the index");
+        if (f && !filter_holds(f, static_cast<uint32_t>(lex_rows[i])))
+            continue; // a lexical row outside the filter is no candidate
+        call.lrow.push_back(static_cast<uint32_t>(lex_rows[i]));
+        call.lscore.push_back(lex_scores[i]);
+    }
+    RLR_TRY(use_device(ix));
+    std::vector<CappedHit> hits;
+    bool picked = true;
+    {
+        CtxLease lease(ix);
+        RLR_TRY(ctx_acquire(ix, &lease.c));
+        StreamDrain drain{lease.c->stream};
+        RLR_TRY(capped_query(ix, lease.c, f, call, hits, &picked));
+        drain.armed = false;
+    }
+    if (!picked && !hits.empty()) { // the exact form's pool: mmr_diversify over it, unchanged
+        const uint32_t P = static_cast<uint32_t>(hits.size());
+        std::vector<uint64_t> rows(P);
+        std::vector<float> scores(P);
+        for (uint32_t i = 0; i < P; ++i) {
+            rows[i] = hits[i].row;
+            scores[i] = hits[i].c;
+        }
+        std::vector<uint32_t> order(P);
+        uint32_t n_sel = 0;
+        RLR_TRY(mmr_single_impl(ix, rows.data(), scores.data(), P, k, lambda, order.data(), nullptr, &n_sel, nullptr, 0));
+        std::vector<CappedHit> sel(n_sel);
+        for (uint32_t i = 0; i < n_sel; ++i)
+            sel[i] = hits[order[i]];
+        hits.swap(sel);
+    }
+    for (size_t i = 0; i < hits.size(); ++i) {
+        rows_out[i] = hits[i].row;
+        cos_out[i] = hits[i].e;
+        score_out[i] = hits[i].c;
+        lex_out[i] = hits[i].l;
+        if (docs_out)
+            docs_out[i] = hits[i].doc;
+    }
+    *n_out = static_cast<uint32_t>(hits.size());
+    return RLR_OK;
+}
+
+int32_t rlr_index_capped_forms(rlr_index *ix, uint64_t counts[4], int32_t reset)
+{
+    RLR_TRY(check_handle(ix));
+    std::lock_guard<std::mutex> lk(ix->mu);
+    for (int i = 0; i < 4; ++i) {
+        if (counts)
+            counts[i] = ix->capped_forms[i];
+        if (reset)
+            ix->capped_forms[i] = 0;
+    }
+    return RLR_OK;
 }
 
 // Batched MMR over P-strided pools.  The pool rows either live in the index (pool_rows != null:

@@ -263,7 +263,30 @@ struct GroupState {
     uint32_t n_cand;  // candidate slots handed out (may exceed kGroupCap)
     uint32_t n_valid; // rows whose nominated score is a number (masked rows and NaN nominations are not)
     uint32_t flags;   // bit 0: a workgroup's local candidate list overflowed, bit 1: the document table ran out of slots
-    uint32_t pad;
+    uint32_t u_bits;  // collect: the bits of U, the floor of the k-th head's bin (-inf with fewer than k heads)
+};
+// A capped hybrid search (rlr_search_capped): capped_finish_kernel in place of group_finish_kernel.  The finish unites the
+// re-scored grouped candidates with the lexical rows, blends, caps per document in combined order and leaves the first
+// `k` (= need) accepted entries as the pool a PoolArgs consumer expects.
+constexpr uint32_t kCappedLexMax = 2048;                        // lexical rows the finish holds
+constexpr uint32_t kCappedSlots = kGroupCap + kCappedLexMax;    // entries of the union: its LDS is sized from this
+// pinned side block of a capped call: [n | checksum | rows x need | document ids x need]
+inline uint32_t capped_side_words(uint32_t need) { return 2 + 2 * need; }
+struct CappedArgs {
+    float w_e, w_l, eps;      // the resolved weights (w_e > 0, w_l >= 0) and the plan's half band
+    uint32_t n_allowed;       // |A|
+    const uint32_t *lrow;     // n_lex lexical rows: ascending, unique, inside A
+    const float *lscore;      // their BM25 scores (>= 0)
+    const float *lcos;        // their reference-order cosines
+    uint32_t n_lex;           // <= kCappedLexMax
+    float max_lex;
+    float *scratch;           // 3 x kCappedSlots floats: combined | cos | lexn per entry
+    uint32_t *list;           // the pool: slot -> row ...
+    float *comb, *cosv, *lexv; // ... combined, cosine, normalised lexical score
+    uint32_t *info;           // [0] pool size, [1] status (0 decided, 1 capacity, 2 undecidable here)
+    uint32_t *h_side;         // capped_side_words(need) pinned words: the pool's rows and document ids
+    uint32_t k_cap;
+    uint32_t *h_out;          // non-null: no diversification -- the pool is the result, emitted as a result block (sort_emit.h)
 };
 struct GroupArgs {
     const float *scores;  // n nominated scores (NaN: masked, or a NaN nomination)
@@ -286,6 +309,7 @@ struct GroupArgs {
     uint64_t *meta;       // candidate count | checksum of `out` << 32, written last
     uint32_t *ctx_hist;   // the context's digit-1 histogram (the scan counted into it): cleared for the next query
     int n_cu;
+    const CappedArgs *capped = nullptr; // non-null: out / meta unused, the capped finish runs
 };
 inline uint32_t group_out_words(uint32_t k) { return k + (k + 1) / 2 + 1; }
 bool group_fits(uint32_t pitch16, uint32_t dim, int dtype);

@@ -196,4 +196,38 @@ __host__ __device__ inline uint32_t block_chk_tail(uint32_t chk_values, uint32_t
     return chk_values + result_chk_term(n, block_n(k_cap)) + result_chk_term(status, block_status(k_cap));
 }
 
+
+// [row u32 | cos f32 | combined f32 | lexical f32] x k_cap, then n, status, checksum, done (the layout the greedy kernel's
+// emit tail writes) into pinned host memory, by all threads of one workgroup
+__device__ inline void hybrid_emit_body(const uint32_t *list, const float *comb, const float *cosv, const float *lexv, uint32_t n,
+                                        uint32_t status, uint32_t k_cap, uint32_t *__restrict__ h_out)
+{
+    __shared__ uint32_t s_chk;
+    if (threadIdx.x == 0)
+        s_chk = 0;
+    __syncthreads();
+    uint32_t chk = 0;
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+        const uint32_t w0 = list[i], w1 = __builtin_bit_cast(uint32_t, cosv[i]), w2 = __builtin_bit_cast(uint32_t, comb[i]);
+        const uint32_t w3 = __builtin_bit_cast(uint32_t, lexv[i]);
+        h_out[block_value(k_cap, kBlockRow, i)] = w0;
+        h_out[block_value(k_cap, kBlockCos, i)] = w1;
+        h_out[block_value(k_cap, kBlockComb, i)] = w2;
+        h_out[block_value(k_cap, kBlockLex, i)] = w3;
+        chk += result_chk_term(w0, block_value(k_cap, kBlockRow, i)) + result_chk_term(w1, block_value(k_cap, kBlockCos, i)) +
+               result_chk_term(w2, block_value(k_cap, kBlockComb, i)) + result_chk_term(w3, block_value(k_cap, kBlockLex, i));
+    }
+    if (chk)
+        atomicAdd(&s_chk, chk);
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) { // (the greedy kernel's emit tail writes the same four words)
+        h_out[block_n(k_cap)] = n;
+        h_out[block_status(k_cap)] = status;
+        h_out[block_chk(k_cap)] = block_chk_tail(s_chk, n, status, k_cap);
+        __threadfence_system();
+        h_out[block_done(k_cap)] = kBlockDone;
+    }
+}
+
 } // namespace rlr

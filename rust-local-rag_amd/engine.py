@@ -121,6 +121,7 @@ class SearchRequest:  # mcp_server.rs:17-31
     lexical: Sequence[Tuple[str, float]] = field(default_factory=list)
     query: Optional[str] = None   # the query text (mcp_server.rs:19); scored by the GPU LexicalIndex when given
     documents: Optional[Sequence[str]] = None  # search only inside these documents (None: the whole corpus; []: nothing)
+    per_document: Optional[int] = None  # at most this many (1..8) results from any one document (None: no cap)
 
 
 def document_ranges(chunks: Sequence[DocumentChunk], documents) -> List[Tuple[int, int]]:
@@ -296,15 +297,21 @@ class RagEngine:
     # -- RagEngine::search (rag_engine.rs:470-701) -----------------------------------------
     def search(self, query_embedding, top_k: int, weights: Optional[QueryWeights] = None,
                lexical: Sequence[Tuple[str, float]] = (), stage: int = 0,
-               query_text: Optional[str] = None, documents: Optional[Sequence[str]] = None) -> List[SearchResult]:
+               query_text: Optional[str] = None, documents: Optional[Sequence[str]] = None,
+               per_document: Optional[int] = None) -> List[SearchResult]:
         """`lexical`: BM25 pairs computed by the caller, or `query_text`: scored by the GPU LexicalIndex.
         `documents`: search only inside these documents -- the reference's search over the corpus that holds only their
-        chunks (None: the whole corpus; an empty list or unknown names: no rows, no results)."""
+        chunks (None: the whole corpus; an empty list or unknown names: no rows, no results).
+        `per_document`: at most this many (1..8) results from any one document, capped in combined-score order on the
+        device (rlr_engine_search_capped); None: no cap, the paths below untouched."""
         q = _f32(query_embedding).ravel()
         cap = max(3 * max(top_k, 1), 1)
         hits = (N.SearchHitC * cap)()
         n = C.c_uint32()
         wc = weights.to_c() if weights is not None else None
+        if per_document is not None:
+            return self._search_capped(q, top_k, 0.0, stage, wc, lexical, query_text, documents, per_document, hits, cap,
+                                       5 * max(top_k, 1))
         if documents is not None:
             f = self._filter_for(documents)
             if query_text is not None:
@@ -337,8 +344,10 @@ class RagEngine:
                               weights: Optional[QueryWeights] = None,
                               lexical: Sequence[Tuple[str, float]] = (),
                               query_text: Optional[str] = None,
-                              documents: Optional[Sequence[str]] = None) -> List[SearchResult]:
-        """`documents`: as for search -- the MMR pool is then min(rows of the documents, max(3 top_k, top_k + 10))"""
+                              documents: Optional[Sequence[str]] = None,
+                              per_document: Optional[int] = None) -> List[SearchResult]:
+        """`documents`: as for search -- the MMR pool is then min(rows of the documents, max(3 top_k, top_k + 10)).
+        `per_document`: as for search -- the cap is applied to the MMR pool, so it holds for the picks."""
         q = _f32(query_embedding).ravel()
         cap = max(3 * max(top_k, 1), top_k + 10)
         hits = (N.SearchHitC * cap)()
@@ -346,6 +355,9 @@ class RagEngine:
         lam = min(max(float(diversity_factor), 0.0), 1.0)
         k_eff = top_k if lam == 0.0 else max(3 * top_k, top_k + 10)  # the top_k `search` sees (:728-735)
         wc = weights.to_c() if weights is not None else None
+        if per_document is not None:
+            return self._search_capped(q, top_k, float(diversity_factor), 0, wc, lexical, query_text, documents, per_document,
+                                       hits, cap, 5 * max(k_eff, 1))
         if documents is not None:
             f = self._filter_for(documents)
             if query_text is not None:
@@ -371,6 +383,31 @@ class RagEngine:
             self.index.handle, q.ctypes.data_as(N.f32p), q.size, top_k, float(diversity_factor),
             C.byref(wc) if wc is not None else None, lr.ctypes.data_as(N.u64p), ls.ctypes.data_as(N.f32p), nl,
             hits, cap, C.byref(n)))
+        return self._results(hits, n.value)
+
+    def _search_capped(self, q, top_k: int, diversity_factor: float, stage: int, wc, lexical, query_text, documents,
+                       per_document: int, hits, cap: int, lex_limit: int) -> List[SearchResult]:
+        """search / search_with_diversity with `per_document` set: rlr_engine_search_text_capped with a query text,
+        rlr_engine_search_capped with the caller's BM25 pairs"""
+        if not isinstance(per_document, int) or isinstance(per_document, bool) or not 1 <= per_document <= N.MAX_PER_DOCUMENT:
+            raise ValueError(f"per_document must be an integer in 1..{N.MAX_PER_DOCUMENT}")
+        if len(self._chunks) == 0:
+            return []
+        self._sync_documents()
+        f = self._filter_for(documents) if documents is not None else None
+        fh = f.handle if f is not None else None
+        n = C.c_uint32()
+        if query_text is not None:
+            tok = " ".join(tokenize(query_text)).encode("utf-8")
+            N.check(N.lib().rlr_engine_search_text_capped(
+                self.index.handle, self.lexical._h, fh, q.ctypes.data_as(N.f32p), q.size, tok, len(tok), top_k,
+                diversity_factor, stage, C.byref(wc) if wc is not None else None, per_document, hits, cap, C.byref(n)))
+        else:
+            lr, ls, nl = self._lex(lexical, None, lex_limit)
+            N.check(N.lib().rlr_engine_search_capped(
+                self.index.handle, fh, q.ctypes.data_as(N.f32p), q.size, top_k, diversity_factor, stage,
+                C.byref(wc) if wc is not None else None, lr.ctypes.data_as(N.u64p), ls.ctypes.data_as(N.f32p), nl, per_document,
+                hits, cap, C.byref(n)))
         return self._results(hits, n.value)
 
     # -- tail of RagEngine::search when a reranker answered (rag_engine.rs:599-700) --------------
@@ -523,10 +560,14 @@ class RagEngine:
         groups: Dict[tuple, List[int]] = {}
         shared: Dict[tuple, List[int]] = {}
         shared_text: Dict[tuple, List[int]] = {}
+        capped: List[int] = []
         for i, r in enumerate(requests):
             if r.lexical:
                 raise ValueError("search_documents_batch: requests carry caller-computed lexical pairs; "
                                  "use search_documents")
+            if r.per_document is not None:
+                capped.append(i)
+                continue
             top_k = min(r.top_k if r.top_k is not None else N.DEFAULT_TOP_K, N.MAX_TOP_K)
             div = r.diversity_factor if r.diversity_factor is not None else N.DEFAULT_DIVERSITY
             div = min(max(div, 0.0), 1.0)
@@ -541,6 +582,8 @@ class RagEngine:
                 continue
             groups.setdefault((top_k, div, wkey, scope), []).append(i)
         out: List[List[SearchResult]] = [[] for _ in requests]
+        for i in capped:  # (the cap has no batched form: one capped call each)
+            out[i] = self.search_documents(requests[i])
         for (top_k, div, _), members in shared.items():
             emb = np.stack([_f32(requests[i].query_embedding).ravel() for i in members])
             scopes = [sorted(set(requests[i].documents)) for i in members]
@@ -622,7 +665,7 @@ class RagEngine:
         div = request.diversity_factor if request.diversity_factor is not None else N.DEFAULT_DIVERSITY
         div = min(max(div, 0.0), 1.0)
         return self.search_with_diversity(request.query_embedding, top_k, div, request.weights, request.lexical,
-                                          request.query, request.documents)
+                                          request.query, request.documents, request.per_document)
 
 
 def format_search_results(results: Sequence[SearchResult]) -> str:

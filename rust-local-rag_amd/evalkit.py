@@ -3,7 +3,9 @@ GPU path, and the retrieval metrics the reference's harness computes from it.
 
 What is mirrored (behaviour, not code):
   wire contract   POST /search  {"query": str, "top_k"?: int = 5, "diversity_factor"?: float = 0.3,
-                                 "documents"?: [str]  -- this build's addition: search only inside these documents}
+                                 "documents"?: [str]  -- this build's addition: search only inside these documents,
+                                 "per_document"?: int 1..8  -- this build's addition: at most so many results from any one
+                                                               document (422 on another type or value)}
                   -> 200 {"results": [SearchResult]}        src/mcp_server.rs:345-389
                   top_k capped at MAX_TOP_K = 100 (:364, :375), diversity clamped to [0, 1] (:376),
                   default weights (:378), engine error -> 500 (:384-387); a body without "query" is
@@ -32,6 +34,7 @@ from typing import Callable, Dict, Iterable, List, Optional, Sequence, Set, Tupl
 DEFAULT_TOP_K = 5          # mcp_server.rs:356-358
 DEFAULT_DIVERSITY = 0.3    # mcp_server.rs:359-361
 MAX_TOP_K = 100            # mcp_server.rs:364
+MAX_PER_DOCUMENT = 8       # RLR_MAX_PER_DOCUMENT (include/rlr_gpu.h)
 
 
 # ---------------------------------------------------------------------------------- metrics
@@ -136,6 +139,11 @@ class SearchService:
             if not isinstance(docs, list) or not all(isinstance(d, str) for d in docs):
                 return 422, {"error": "invalid type for `documents`: expected a sequence of strings"}
             scope["documents"] = docs
+        if "per_document" in body:  # optional: at most so many results from any one document; absent: no cap
+            per = body["per_document"]
+            if isinstance(per, bool) or not isinstance(per, int) or not 1 <= per <= MAX_PER_DOCUMENT:
+                return 422, {"error": f"invalid value for `per_document`: expected an integer in 1..{MAX_PER_DOCUMENT}"}
+            scope["per_document"] = per
         top_k = min(top_k, MAX_TOP_K)
         div = min(max(float(div), 0.0), 1.0)
         try:

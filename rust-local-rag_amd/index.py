@@ -298,6 +298,38 @@ class GpuIndex:
         N.check(self._L.rlr_index_grouped_forms(self._h, _up(counts), int(reset)))
         return [int(c) for c in counts]
 
+    def search_capped(self, query, need: int, per_document: int, k: int = 0, lam: float = 0.0, diversify: bool = False,
+                      w_embedding: float = 1.0, w_lexical: float = 0.0, lex_rows=None, lex_scores=None, max_lex: float = 1.0,
+                      filter: "RowFilter | None" = None, guard_eps: float = -1.0):
+        """rlr_search_hybrid with at most `per_document` (1..8) candidates from any one document (rlr_search_capped): the
+        allowed rows in combined order (w_embedding * cos + w_lexical * lex / max_lex), a row accepted unless
+        per_document rows of its document are, `need` accepted rows -- the answer, or with `diversify` the MMR pool k
+        rows are picked from with `lam`.  query: [dim], already normalised; lex_rows ascending and unique.
+        -> (rows u64, cos f32, combined f32, lexn f32, docs u32), as many as came together"""
+        q = _f32(query).reshape(self.dim)
+        lr = _u64(lex_rows if lex_rows is not None else [])
+        ls = _f32(lex_scores if lex_scores is not None else [])
+        if lr.size != ls.size:
+            raise ValueError("lex_rows and lex_scores differ in length")
+        cap = max(int(need), 1)
+        rows = np.zeros(cap, dtype=np.uint64)
+        cos, comb, lexn = (np.zeros(cap, dtype=np.float32) for _ in range(3))
+        docs = np.zeros(cap, dtype=np.uint32)
+        n_out = np.zeros(1, dtype=np.uint32)
+        N.check(self._L.rlr_search_capped(self._h, None if filter is None else filter.handle, _fp(q), need, k, lam, int(diversify),
+                                          w_embedding, w_lexical, _up(lr) if lr.size else None, _fp(ls) if ls.size else None,
+                                          lr.size, max_lex, per_document, guard_eps, _up(rows), _fp(cos), _fp(comb), _fp(lexn),
+                                          _u32ptr(docs), _u32ptr(n_out)))
+        n = int(n_out[0])
+        return rows[:n], cos[:n], comb[:n], lexn[:n], docs[:n]
+
+    def capped_forms(self, reset: bool = False) -> list:
+        """queries search_capped served by each form: [decided on the device, exact on capacity, exact because it was
+        undecidable there (NaN rows needed, a masked row came back, a boundary tie), exact by rule] (rlr_index_capped_forms)"""
+        counts = np.zeros(4, dtype=np.uint64)
+        N.check(self._L.rlr_index_capped_forms(self._h, _up(counts), int(reset)))
+        return [int(c) for c in counts]
+
     def search_topk_device(self, queries, k: int, d_out_ptr: int, stream: int = 0, guard_eps: float = -1.0) -> None:
         q = _f32(queries).reshape(-1, self.dim)
         N.check(self._L.rlr_search_topk_device(self._h, _fp(q), q.shape[0], k, guard_eps,
