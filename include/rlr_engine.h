@@ -170,6 +170,16 @@ int32_t rlr_engine_search_text_capped(rlr_index *idx, rlr_lexical *lex, const rl
                                       uint32_t dq, const char *query_tokens, size_t tokens_len, uint32_t top_k,
                                       float diversity_factor, int32_t stage, const rlr_query_weights *weights,
                                       uint32_t per_doc, rlr_search_hit *out, uint32_t cap, uint32_t *n_out);
+/* Every chunk whose cosine with the query is at least min_cosine, and how many there are (rlr_search_range,
+ * include/rlr_gpu.h), over the whole index (f null) or inside a filter.  No reference site: the reference only colours
+ * results by fixed score thresholds.  The query is normalised as rlr_engine_search does (rlr_normalize, zip-truncated
+ * or zero-extended to the index dim); hits are filled as get_embedding_candidates defines them (w_e = 1, no lexical
+ * term): score = embedding_score = initial_score = the cosine, lexical_score = 0.  *n_total_out is the exact number of
+ * hits whatever cap is; the first min(n_total, cap) in (cosine desc, row asc) order go to out, *n_out is their count.
+ * cap == 0 only counts (out and n_out may be null).  A NaN min_cosine, a stale filter: RLR_E_INVALID; an empty filter
+ * or index: RLR_OK with both counts 0. */
+int32_t rlr_engine_search_range(rlr_index *idx, const rlr_filter *f, const float *query_raw, uint32_t dq, float min_cosine,
+                                uint32_t cap, rlr_search_hit *out, uint32_t *n_out, uint64_t *n_total_out);
 /* rlr_engine_search_with_diversity_batch inside a filter: n_queries raw query embeddings, no lexical pairs; query q
  * equals rlr_engine_search_with_diversity_filtered(query q, n_lex = 0), N = |F| everywhere.  Hits of query q start at
  * out[q * cap]; n_out[q] = their count (every one 0 when |F| = 0).  The candidates come from ONE

@@ -458,6 +458,32 @@ int32_t rlr_search_topk_grouped(rlr_index *idx, const rlr_filter *f, const float
  * list-path filter, k beyond the device finish, rows too wide for the staged re-score).  counts may be null. */
 int32_t rlr_index_grouped_forms(rlr_index *idx, uint64_t counts[4], int32_t reset);
 
+/* ---- range search: every row scoring at or above a threshold, and how many -- */
+/* For one query over the allowed rows (all rows, or the rows of f) and a threshold tau: row r is a HIT iff e(r) >= tau in
+ * IEEE f32 comparison, e(r) the reference-order dot product, bit-identical to rlr_score_rows.  A NaN score is never a hit,
+ * +Inf is one, -0 >= +0 holds; tau = -inf makes every allowed row with a number for a score a hit.  Membership is decided
+ * on the exact score, never on a nominated one.
+ *   n_total_out[q]: the exact number of hits, whatever cap is.
+ *   The hits in the library's result order (score descending, row ascending): the first min(n_total, cap) are written
+ *   from q * cap on in rows_out / cos_out, n_out[q] is that count.  n_total > cap is no error: RLR_OK, the caller reads
+ *   n_total and decides.
+ *   cap == 0 is COUNT-ONLY: nothing is written; rows_out, cos_out and n_out may be null.
+ *   A NaN in tau: RLR_E_INVALID.  f may be null; filter rules (stale filters, another index' filter) as for
+ *   rlr_search_topk_filtered; an empty filter or an empty index: RLR_OK with both counts 0.
+ * Queries run one by one over the master rows, each with its own tau[q]: no coalescer, no nomination copy, no shared
+ * pass.  The threshold collect runs on the device behind the scan (DESIGN.md "Range search"); it holds up to
+ * RLR_RANGE_DEVICE_MAX hits per query.  What it cannot decide it hands on, never silently: */
+#define RLR_RANGE_DEVICE_MAX 65536
+int32_t rlr_search_range(rlr_index *idx, const rlr_filter *f, const float *queries, uint32_t n_queries, const float *tau,
+                         uint32_t cap, float guard_eps, uint64_t *rows_out, float *cos_out, uint32_t *n_out,
+                         uint64_t *n_total_out);
+/* Queries served by each form since the last reset: [0] decided on the device; [1] capacity -- rows were wanted and
+ * n_total > min(cap, RLR_RANGE_DEVICE_MAX): n_total is the device's count, the rows come from the existing top-k path at
+ * k = cap (cap <= 4096) or from the exact form (reference-order scores of every allowed row, threshold and order on the
+ * host); exact form taken [2] because allowed rows with NaN nominations exist or a masked row came back, [3] by rule (a
+ * list-path filter, rows too wide for the staged re-score).  counts may be null. */
+int32_t rlr_index_range_forms(rlr_index *idx, uint64_t counts[4], int32_t reset);
+
 /* ---- capped hybrid search: the per-document cap inside the blend and MMR ---- */
 /* rlr_search_hybrid with at most per_doc candidates from any one document, over all rows (f null) or the rows of f.
  * Every allowed row has cos = the reference-order dot product, lexn = lex / max_lex (0 without a lexical pair; pairs

@@ -438,4 +438,37 @@ int32_t rlr_engine_search_text_batch_scoped(rlr_index *idx, rlr_lexical *lex, co
                             n_out, info);
 }
 
+// Every chunk at or above a cosine (rlr_search_range), with the query normalised as rlr_engine_search does and the hits
+// filled as get_embedding_candidates defines them: w_e = 1, no lexical term.
+int32_t rlr_engine_search_range(rlr_index *idx, const rlr_filter *f, const float *query_raw, uint32_t dq, float min_cosine,
+                                uint32_t cap, rlr_search_hit *out, uint32_t *n_out, uint64_t *n_total_out)
+{
+    if (!idx || !n_total_out || (!query_raw && dq) || (cap && (!out || !n_out)))
+        return RLR_E_INVALID;
+    if (n_out)
+        *n_out = 0;
+    *n_total_out = 0;
+    uint32_t dim = 0;
+    int32_t st = rlr_index_info(idx, nullptr, &dim, nullptr, nullptr);
+    if (st != RLR_OK)
+        return st;
+    const std::vector<float> q = prepare_query(query_raw, dq, dim);
+    std::vector<uint64_t> rows(cap);
+    std::vector<float> cosv(cap);
+    uint32_t n = 0;
+    st = rlr_search_range(idx, f, q.data(), 1, &min_cosine, cap, -1.0f, rows.data(), cosv.data(), &n, n_total_out);
+    if (st != RLR_OK)
+        return st;
+    for (uint32_t i = 0; i < n; ++i) {
+        out[i].row = rows[i];
+        out[i].score = cosv[i];
+        out[i].embedding_score = cosv[i];
+        out[i].lexical_score = 0.0f;
+        out[i].initial_score = cosv[i];
+    }
+    if (n_out)
+        *n_out = n;
+    return RLR_OK;
+}
+
 } // extern "C"

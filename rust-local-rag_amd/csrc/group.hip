@@ -609,8 +609,10 @@ __global__ __launch_bounds__(kGroupBlock) void group_iota_kernel(uint32_t *__res
         list[i] = i;
 }
 
+} // namespace
+
 // the staging of collect's re-score: the query and cpb rows of products (tail.hip's layout, under what is left of the
-// 64 KB beside the local candidate list and the bin search's words)
+// 64 KB beside the local candidate list and the bin search's words); range.hip stages its re-score the same way
 bool group_shape(uint32_t pitch16, uint32_t dim, int dtype, uint32_t *cpb_out, size_t *staging_out)
 {
     const size_t q_bytes = static_cast<size_t>((dim + 7) & ~7u) * sizeof(float);
@@ -627,8 +629,6 @@ bool group_shape(uint32_t pitch16, uint32_t dim, int dtype, uint32_t *cpb_out, s
     *staging_out = q_bytes + cpb * row_bytes;
     return true;
 }
-
-} // namespace
 
 bool group_fits(uint32_t pitch16, uint32_t dim, int dtype)
 {

@@ -131,6 +131,9 @@ struct Ctx {
     DevBuf<GroupState> d_gstate;
     DevBuf<uint64_t> d_gcand;      // kGroupCap
     DevBuf<uint32_t> d_gcdoc;      // kGroupCap
+    // range search (range.hip), grown lazily: the two counters and the unordered exact keys of the hits
+    DevBuf<RangeState> d_rstate;   // with d_rhits
+    DevBuf<uint64_t> d_rhits;      // min(cap, RLR_RANGE_DEVICE_MAX) of the largest call so far
     // rlr_search_topk_device_begin / _end
     hipStream_t pending_stream = nullptr;
     uint32_t pending_q = 0, pending_k = 0;
@@ -227,6 +230,7 @@ struct rlr_index {
     std::atomic<uint64_t> mutations{0};
     uint64_t grouped_forms[4] = {0, 0, 0, 0}; // rlr_index_grouped_forms: queries served by each form (mu)
     uint64_t capped_forms[4] = {0, 0, 0, 0};  // rlr_index_capped_forms: the same for rlr_search_capped (mu)
+    uint64_t range_forms[4] = {0, 0, 0, 0};   // rlr_index_range_forms: the same for rlr_search_range (mu)
 };
 
 // A set of rows of one index, fixed at creation (rlr_filter_create_*): one bit per index row on the device (tail bits of
@@ -2616,6 +2620,150 @@ int32_t grouped_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *q
     return note_search(ix, c, 1, n_cand, form != 0 ? 1 : 0, timed && form != 3);
 }
 
+// ---- range search (rlr_search_range): every allowed row scoring at or above a threshold ---------------------------------
+// The exact form: reference-order scores of every allowed row, copied back; threshold, count and order on the host.  Slow
+// and always right.  The query is in c->d_query.  keys: the first min(n_total, cap) hits in result order.
+int32_t range_exact(rlr_index *ix, Ctx *c, const rlr_filter *f, float tau, uint32_t cap, std::vector<uint64_t> &keys, uint64_t *n_total)
+{
+    std::vector<uint32_t> list, docs;
+    std::vector<float> vals;
+    RLR_TRY(exact_scores(ix, c, f, list, vals, docs));
+    keys.clear();
+    uint64_t total = 0;
+    for (size_t i = 0; i < list.size(); ++i)
+        if (vals[i] >= tau) { // IEEE: a NaN is never a hit, -0 >= +0 holds
+            total++;
+            if (cap)
+                keys.push_back(pack_result(vals[i], list[i]));
+        }
+    *n_total = total;
+    if (keys.size() > cap) {
+        std::partial_sort(keys.begin(), keys.begin() + cap, keys.end(), std::greater<uint64_t>());
+        keys.resize(cap);
+    } else {
+        std::sort(keys.begin(), keys.end(), std::greater<uint64_t>());
+    }
+    return RLR_OK;
+}
+
+// One range query over all rows (f == nullptr) or the rows of `f` (n_allowed > 0); tau is a number.  The scan over the
+// master rows, then range.hip's tail in place of enqueue_query_rest.  Every query is counted in one form:
+//   [0] decided on the device: the finish's ordered keys, or (more than kRangeFinishMax hits, all within cap and the
+//       device capacity) one copy of the unordered exact keys and a sort of them here;
+//   [1] capacity, n_total > min(cap, RLR_RANGE_DEVICE_MAX) while rows are wanted: n_total is the device's exact count; the
+//       rows are the best `cap` of more than `cap` hits, i.e. the top-k answer at k = cap -- taken from the existing top-k
+//       path (rlr_search_topk / rlr_search_topk_filtered) while cap <= kLdsSortCap, from the exact form beyond;
+//   [2] allowed rows with NaN nominations exist (their exact score could be a number), or a returned row fails the
+//       filter's host mask: the exact form;
+//   [3] by rule, decided before any workspace is sized: a list-path filter, rows too wide for the staged re-score: the
+//       exact form (for a list-path filter that is launch_score_rows over its list).
+int32_t range_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *query, float tau, uint32_t cap, float guard_eps,
+                    uint64_t *rows_out, float *cos_out, uint32_t *n_out, uint64_t *n_total_out)
+{
+    const uint64_t n_allowed = f ? f->n_allowed : ix->n_rows;
+    const bool by_rule = (f && f->path == 0) || !group_fits(ix->pitch16, ix->dim, ix->dtype);
+    const SearchPlan p = make_plan(ix, query, 1, 1, guard_eps);
+    const uint32_t hit_cap = std::min<uint32_t>(cap, RLR_RANGE_DEVICE_MAX), out_keys = std::min<uint32_t>(cap, kRangeFinishMax);
+    const uint32_t words = range_out_words(out_keys);
+    if (by_rule)
+        RLR_TRY(reserve_queries(ix, c, 1));
+    else
+        RLR_TRY(ctx_prepare(ix, c, 1, p));
+    Staged pin;
+    RLR_TRY(stage_call(ix, c, query, 1, static_cast<size_t>(words) + 1, /*for_scans=*/false, &pin));
+    uint64_t *h_res = pin.h_res, *h_meta = h_res + words;
+    hipStream_t s = c->stream;
+    const bool timed = ix->profiling;
+    uint32_t form = by_rule ? 3 : 0, n_res = 0;
+    uint64_t n_total = 0;
+    std::vector<uint64_t> keys;
+    const uint64_t *res = h_res;
+    if (!by_rule) {
+        RLR_HIP(reserve_group(Want{c->d_rstate, 1}, Want{c->d_rhits, std::max<uint32_t>(hit_cap, 1)}));
+        RangeArgs ra;
+        ra.scores = c->d_scores.get();
+        ra.n = static_cast<uint32_t>(ix->n_rows);
+        ra.tau = tau;
+        ra.two_eps = p.two_eps;
+        ra.hit_cap = hit_cap;
+        ra.out_keys = out_keys;
+        ra.st = c->d_rstate.get();
+        ra.rows = ix->d_rows.get();
+        ra.pitch16 = ix->pitch16;
+        ra.dim = ix->dim;
+        ra.dtype = ix->dtype;
+        ra.query = c->d_query.get();
+        ra.hits = c->d_rhits.get();
+        ra.out = h_res;
+        ra.meta = h_meta;
+        ra.ctx_hist = c->d_hist.get();
+        ra.n_cu = ix->n_cu;
+        arm_meta(h_meta, 1);
+        // (the masked scan for a filter; without one the scan over the master rows too: no nomination copy, as filtered calls)
+        RLR_HIP(enqueue_query_scan(ix, c, 0, timed, f, /*master_rows=*/true));
+        RLR_HIP(launch_range_tail(ra, s));
+        if (timed) {
+            RLR_HIP(hipEventRecord(c->ev[2], s));
+            RLR_HIP(hipEventRecord(c->ev[3], s));
+            RLR_HIP(hipStreamSynchronize(s));
+        } else {
+            RLR_TRY(wait_results(h_meta, h_res, 1, words, 1, s, &c->wait_ema));
+        }
+        RLR_TRY(check_hist_assert(c));
+        const uint64_t info = h_res[out_keys];
+        const uint32_t n_hits = static_cast<uint32_t>(info), n_valid = static_cast<uint32_t>(info >> 32);
+        n_total = n_hits;
+        if (n_valid < n_allowed) {
+            form = 2; // allowed rows with NaN nominations: what they score exactly is not known here
+        } else if (cap && n_hits > hit_cap) {
+            form = 1;
+        } else if (cap && n_hits > out_keys) {
+            // beyond the finish, within the device capacity: the exact keys in no order -> one copy, ordered here
+            keys.resize(n_hits);
+            RLR_HIP(hipMemcpyAsync(keys.data(), c->d_rhits.get(), static_cast<size_t>(n_hits) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+            RLR_HIP(hipStreamSynchronize(s));
+            std::sort(keys.begin(), keys.end(), std::greater<uint64_t>());
+            res = keys.data();
+            n_res = n_hits;
+        } else {
+            n_res = cap ? n_hits : 0;
+        }
+        for (uint32_t i = 0; f && i < n_res && form == 0; ++i)
+            if (!filter_holds(f, 0xFFFFFFFFu - static_cast<uint32_t>(res[i])))
+                form = 2; // a masked row came back (the hazard filtered_query documents)
+    }
+    c->hist_dirty = false;
+    {
+        std::lock_guard<std::mutex> lk(ix->mu);
+        ix->range_forms[form]++;
+    }
+    *n_total_out = n_total;
+    if (form == 1 && cap <= kLdsSortCap) {
+        // more hits than cap: the first cap of them are the top-k answer at k = cap (all of them numbers at or above tau)
+        if (f)
+            return filtered_query(ix, c, f, query, cap, guard_eps, rows_out, cos_out, n_out);
+        SearchPlan tp;
+        const uint64_t *h = nullptr;
+        RLR_TRY(run_search(ix, c, query, 1, cap, guard_eps, nullptr, &tp, &h));
+        if (!h)
+            return set_error(RLR_E_INTERNAL, "search produced no result buffer");
+        *n_out = tp.k;
+        unpack_results(h, tp.k, rows_out, cos_out);
+        return RLR_OK;
+    }
+    if (form != 0) {
+        RLR_TRY(range_exact(ix, c, f, tau, cap, keys, &n_total));
+        *n_total_out = n_total;
+        res = keys.data();
+        n_res = static_cast<uint32_t>(keys.size());
+    }
+    if (n_out)
+        *n_out = n_res;
+    if (n_res)
+        unpack_results(res, n_res, rows_out, cos_out);
+    return note_search(ix, c, 1, n_total, form != 0 ? 1 : 0, timed && form != 3);
+}
+
 // ---- several queries, inside one filter or a filter each: one shared masked pass ------------------------------------
 // Can a query over `f` join a shared pass at all?  Its filter is on the masked-scan path and holds at least k rows (one
 // plan, one rank k for the whole chunk), the rows are a shape the kernel serves and k leaves the finish its band.
@@ -3709,6 +3857,51 @@ int32_t rlr_index_grouped_forms(rlr_index *ix, uint64_t counts[4], int32_t reset
             counts[i] = ix->grouped_forms[i];
         if (reset)
             ix->grouped_forms[i] = 0;
+    }
+    return RLR_OK;
+}
+
+int32_t rlr_search_range(rlr_index *ix, const rlr_filter *f, const float *queries, uint32_t n_queries, const float *tau, uint32_t cap,
+                         float guard_eps, uint64_t *rows_out, float *cos_out, uint32_t *n_out, uint64_t *n_total_out)
+{
+    RLR_TRY(check_handle(ix));
+    if (f)
+        RLR_TRY(check_filter(ix, f)); // (a stale filter is refused before any GPU work)
+    if (n_queries && (!queries || !tau || !n_total_out))
+        return set_error(RLR_E_INVALID, "queries / tau / n_total_out is null");
+    if (n_queries && cap && (!rows_out || !cos_out || !n_out))
+        return set_error(RLR_E_INVALID, "output buffers are null (only a count-only call, cap == 0, may leave them out)");
+    for (uint32_t q = 0; q < n_queries; ++q)
+        if (!(tau[q] == tau[q]))
+            return set_error(RLR_E_INVALID, "tau[%u] is NaN", q);
+    RLR_TRY(use_device(ix));
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        if (n_out)
+            n_out[q] = 0;
+        n_total_out[q] = 0;
+    }
+    if ((f ? f->n_allowed : ix->n_rows) == 0 || n_queries == 0)
+        return RLR_OK;
+    CtxLease lease(ix);
+    RLR_TRY(ctx_acquire(ix, &lease.c));
+    StreamDrain drain{lease.c->stream};
+    for (uint32_t q = 0; q < n_queries; ++q) // one by one: no coalescer, no nomination copy, no shared pass
+        RLR_TRY(range_query(ix, lease.c, f, queries + static_cast<size_t>(q) * ix->dim, tau[q], cap, guard_eps,
+                            cap ? rows_out + static_cast<size_t>(q) * cap : nullptr, cap ? cos_out + static_cast<size_t>(q) * cap : nullptr,
+                            n_out ? &n_out[q] : nullptr, &n_total_out[q]));
+    drain.armed = false;
+    return RLR_OK;
+}
+
+int32_t rlr_index_range_forms(rlr_index *ix, uint64_t counts[4], int32_t reset)
+{
+    RLR_TRY(check_handle(ix));
+    std::lock_guard<std::mutex> lk(ix->mu);
+    for (int i = 0; i < 4; ++i) {
+        if (counts)
+            counts[i] = ix->range_forms[i];
+        if (reset)
+            ix->range_forms[i] = 0;
     }
     return RLR_OK;
 }

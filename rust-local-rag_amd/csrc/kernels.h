@@ -315,5 +315,53 @@ inline uint32_t group_out_words(uint32_t k) { return k + (k + 1) / 2 + 1; }
 bool group_fits(uint32_t pitch16, uint32_t dim, int dtype);
 hipError_t launch_group_tail(const GroupArgs &a, hipStream_t s, hipEvent_t after_rounds = nullptr);
 hipError_t launch_group_iota(uint32_t *list, uint32_t n, hipStream_t s); // list[i] = i
+// the LDS staging of a workgroup's re-score (at most 56 KB): candidates per pass and the dynamic LDS bytes; false: too wide
+bool group_shape(uint32_t pitch16, uint32_t dim, int dtype, uint32_t *cpb_out, size_t *staging_out);
+
+// ---- range.hip : the tail of a range search (every row scoring at or above a threshold), behind the scan ----
+constexpr uint32_t kRangeFinishMax = 2048; // hits the one-workgroup finish orders and emits
+struct RangeState {
+    uint32_t n_hits;  // exact hits counted (may exceed the key capacity)
+    uint32_t n_valid; // rows whose nominated score is a number (masked rows and NaN nominations are not)
+};
+// One ulp outward; NaN and the infinity on that side stay.  (Host and device decide against the SAME two floats: the host
+// computes them once and the kernels only compare.)
+inline float range_step(float x, bool up)
+{
+    const float inf = __builtin_inff();
+    if (!(x == x) || x == (up ? inf : -inf))
+        return x;
+    if (x == 0.0f)
+        return __builtin_bit_cast(float, up ? 0x00000001u : 0x80000001u);
+    const uint32_t b = __builtin_bit_cast(uint32_t, x);
+    const bool neg = (b & 0x80000000u) != 0;
+    return __builtin_bit_cast(float, neg == up ? b - 1u : b + 1u);
+}
+// lo <= tau - 2 eps and hi >= tau + 2 eps in real arithmetic: the f32 difference / sum is rounded to nearest, so one step
+// outward covers the rounding.  A NaN bound (tau and the band both infinite) makes every row a candidate and none sure.
+inline void range_bounds(float tau, float two_eps, float *lo, float *hi)
+{
+    *lo = range_step(tau - two_eps, false);
+    *hi = range_step(tau + two_eps, true);
+}
+struct RangeArgs {
+    const float *scores; // n nominated scores (NaN: masked, or a NaN nomination)
+    uint32_t n;
+    float tau, two_eps;
+    uint32_t hit_cap;    // keys `hits` holds; 0: count only
+    uint32_t out_keys;   // keys the pinned block holds: min(hit_cap, kRangeFinishMax)
+    RangeState *st;
+    const void *rows;
+    uint32_t pitch16, dim;
+    int dtype;
+    const float *query;
+    uint64_t *hits;      // hit_cap exact packed keys, in no order
+    uint64_t *out;       // range_out_words(out_keys) pinned words: the keys in result order, zeros behind | n_hits + (n_valid << 32)
+    uint64_t *meta;      // keys emitted (0 / 1) | checksum of `out` << 32, written last
+    uint32_t *ctx_hist;  // the context's digit-1 histogram (the scan counted into it): cleared for the next query
+    int n_cu;
+};
+inline uint32_t range_out_words(uint32_t out_keys) { return out_keys + 1; }
+hipError_t launch_range_tail(const RangeArgs &a, hipStream_t s);
 
 } // namespace rlr

@@ -207,10 +207,14 @@ class RagEngine:
 
     # -- index mutation (sites rag_engine.rs:347-348, :358-384) --------------------------
     def add_document(self, document_name: str, texts: Sequence[str], embeddings, pages: Optional[Sequence[int]] = None,
-                     sections: Optional[Sequence[Optional[str]]] = None) -> List[str]:
-        """Replace `document_name`'s chunks: drop its old rows, normalise and append the new ones."""
+                     sections: Optional[Sequence[Optional[str]]] = None, report_duplicates_above: Optional[float] = None):
+        """Replace `document_name`'s chunks: drop its old rows, normalise and append the new ones -> the new chunk ids.
+        `report_duplicates_above`: a cosine; the call then returns (ids, duplicates) with, per new chunk, the ids of the
+        chunks ALREADY in the corpus (the document's own old chunks are gone by then) at or above it -- found before
+        the append, by search_range."""
         self.remove_document(document_name)
         emb = _f32(embeddings).reshape(len(texts), self.dim)
+        duplicates = None if report_duplicates_above is None else self._duplicates_of(emb, float(report_duplicates_above))
         first = self.index.append(emb, normalize=True)  # normalize(&mut embedding) :358-359, on the GPU
         ids = []
         for i, text in enumerate(texts):
@@ -223,7 +227,7 @@ class RagEngine:
         self.index.tag_rows(first, len(texts), self._doc_id(document_name))  # (append left them in no document)
         self._tagged_len = len(self._chunks)
         self._drop_filters()
-        return ids
+        return ids if duplicates is None else (ids, duplicates)
 
     def remove_document(self, document_name: str) -> int:
         self._sync_documents()
@@ -658,6 +662,65 @@ class RagEngine:
         """The `top_k` documents closest to the query, each with its best chunk: search_per_document with one chunk
         per document, keyed by document name."""
         return [(r.document, r) for r in self.search_per_document(query_embedding, top_k, 1, documents)]
+
+    # -- every chunk at or above a cosine, and how many (rlr_search_range; no reference site) ---------------
+    def _embedding_results(self, rows, cos) -> List[SearchResult]:
+        out = []
+        for row, c in zip(rows.tolist(), cos.tolist()):
+            ch = self._chunks[row]
+            out.append(SearchResult(ch.text, c, ch.document_name, ch.id, ch.chunk_index, ch.page_number, ch.section,
+                                    c, 0.0, c, None, None, None, row))
+        return out
+
+    def search_above(self, query_embedding, min_score: float, limit: int = 100,
+                     documents: Optional[Sequence[str]] = None) -> Tuple[List[SearchResult], int]:
+        """Every chunk whose cosine with the query is at least `min_score`: the best `limit` of them in (cosine desc, row
+        asc) order and the exact number of such chunks, whatever `limit` is.  Embedding-only (score = embedding_score =
+        initial_score = the cosine, lexical score 0); the query is normalised as `search` normalises it.  `documents`:
+        only inside these (as `search`)."""
+        if len(self._chunks) == 0:
+            return [], 0
+        f = self._filter_for(documents) if documents is not None else None
+        q = _f32(query_embedding).ravel()
+        cap = max(int(limit), 0)
+        hits = (N.SearchHitC * max(cap, 1))()
+        n, total = C.c_uint32(), C.c_uint64()
+        N.check(N.lib().rlr_engine_search_range(self.index.handle, f.handle if f is not None else None, q.ctypes.data_as(N.f32p),
+                                                q.size, float(min_score), cap, hits, C.byref(n), C.byref(total)))
+        return self._results(hits, n.value), int(total.value)
+
+    def count_above(self, query_embedding, min_score: float, documents: Optional[Sequence[str]] = None) -> int:
+        """how many chunks score at least `min_score` (nothing is fetched)"""
+        return self.search_above(query_embedding, min_score, 0, documents)[1]
+
+    def similar_chunks(self, chunk_id: str, min_score: float, limit: int = 100,
+                       documents: Optional[Sequence[str]] = None) -> Tuple[List[SearchResult], int]:
+        """The chunks at or above `min_score` against a STORED chunk (its row as the query, as stored: the rows are the
+        reference's normalised values), without the chunk itself; the total does not count it either."""
+        row = self._row_of[chunk_id]
+        f = self._filter_for(documents) if documents is not None else None
+        q = self.index.fetch_rows([row])[0]
+        rows, cos, total = self.index.search_range(q, min_score, max(int(limit), 0) + 1, filter=f)[0]
+        in_scope = documents is None or self._chunks[row].document_name in set(documents)
+        if in_scope and self.index.score_rows(q, [row])[0] >= np.float32(min_score):
+            total -= 1                                       # the chunk itself is one of the hits
+        keep = rows != np.uint64(row)
+        rows, cos = rows[keep][:max(int(limit), 0)], cos[keep][:max(int(limit), 0)]
+        return self._embedding_results(rows, cos), total
+
+    def _duplicates_of(self, emb: np.ndarray, min_score: float) -> List[List[str]]:
+        """per row of `emb` (raw embeddings, normalised here as the append normalises them): the ids of the chunks in
+        the index at or above `min_score`, best first"""
+        if len(self._chunks) == 0 or emb.shape[0] == 0:
+            return [[] for _ in range(emb.shape[0])]
+        q = np.stack([normalize(e) for e in emb])
+        res = self.index.search_range(q, min_score, 256)
+        out = []
+        for i, (rows, _, total) in enumerate(res):
+            if total > rows.size:                            # (a boilerplate chunk: fetch them all)
+                rows = self.index.search_range(q[i], min_score, total)[0][0]
+            out.append([self._chunks[int(r)].id for r in rows])
+        return out
 
     # -- API layer: search_documents / http_search (mcp_server.rs:81-110, :371-389) --------
     def search_documents(self, request: SearchRequest) -> List[SearchResult]:

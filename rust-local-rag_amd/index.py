@@ -298,6 +298,41 @@ class GpuIndex:
         N.check(self._L.rlr_index_grouped_forms(self._h, _up(counts), int(reset)))
         return [int(c) for c in counts]
 
+    def search_range(self, queries, tau, cap: int, filter: "RowFilter | None" = None, guard_eps: float = -1.0):
+        """every row whose reference-order score is at least tau (rlr_search_range).  queries: [Q, dim] (or [dim]) already
+        normalised, tau: one threshold or one per query -> a list of (rows u64, cos f32, n_total) per query: the first
+        min(n_total, cap) hits in (score desc, row asc) order and the exact number of hits, whatever cap is.  cap = 0
+        only counts."""
+        q = _f32(queries).reshape(-1, self.dim)
+        nq = q.shape[0]
+        t = _f32(tau).ravel()
+        if t.size == 1:
+            t = np.full(nq, t[0], dtype=np.float32)
+        if t.size != nq:
+            raise ValueError(f"{nq} queries but {t.size} thresholds")
+        cap = int(cap)
+        rows = np.zeros((nq, max(cap, 1)), dtype=np.uint64)
+        cos = np.zeros((nq, max(cap, 1)), dtype=np.float32)
+        n_out = np.zeros(max(nq, 1), dtype=np.uint32)
+        n_total = np.zeros(max(nq, 1), dtype=np.uint64)
+        N.check(self._L.rlr_search_range(self._h, None if filter is None else filter.handle, _fp(q), nq, _fp(t), cap, guard_eps,
+                                         _up(rows), _fp(cos), _u32ptr(n_out), _up(n_total)))
+        if cap == 0:
+            return [(rows[i, :0], cos[i, :0], int(n_total[i])) for i in range(nq)]
+        return [(rows[i, :int(n_out[i])], cos[i, :int(n_out[i])], int(n_total[i])) for i in range(nq)]
+
+    def count_range(self, queries, tau, filter: "RowFilter | None" = None) -> list:
+        """how many rows score at least tau, per query (rlr_search_range with cap = 0: nothing is fetched)"""
+        return [n for _, _, n in self.search_range(queries, tau, 0, filter=filter)]
+
+    def range_forms(self, reset: bool = False) -> list:
+        """queries search_range served by each form: [decided on the device, capacity (more hits than cap or than the
+        device holds: the count from the device, the rows from the top-k path or the exact form), exact because allowed
+        rows with NaN nominations exist or a masked row came back, exact by rule] (rlr_index_range_forms)"""
+        counts = np.zeros(4, dtype=np.uint64)
+        N.check(self._L.rlr_index_range_forms(self._h, _up(counts), int(reset)))
+        return [int(c) for c in counts]
+
     def search_capped(self, query, need: int, per_document: int, k: int = 0, lam: float = 0.0, diversify: bool = False,
                       w_embedding: float = 1.0, w_lexical: float = 0.0, lex_rows=None, lex_scores=None, max_lex: float = 1.0,
                       filter: "RowFilter | None" = None, guard_eps: float = -1.0):
