@@ -180,6 +180,13 @@ int32_t rlr_engine_search_text_capped(rlr_index *idx, rlr_lexical *lex, const rl
  * or index: RLR_OK with both counts 0. */
 int32_t rlr_engine_search_range(rlr_index *idx, const rlr_filter *f, const float *query_raw, uint32_t dq, float min_cosine,
                                 uint32_t cap, rlr_search_hit *out, uint32_t *n_out, uint64_t *n_total_out);
+/* rlr_engine_search_range for n_queries raw query embeddings (dq floats each) with a threshold each, through ONE
+ * rlr_search_range_batch call: the queries share passes over the rows (include/rlr_gpu.h).  Query q equals
+ * rlr_engine_search_range(query q, min_cosine[q]) bit for bit; its hits start at out[q * cap], n_out[q] is their count,
+ * n_total_out[q] the exact number of hits.  cap == 0 only counts (out and n_out may be null). */
+int32_t rlr_engine_search_range_batch(rlr_index *idx, const rlr_filter *f, const float *queries_raw, uint32_t n_queries,
+                                      uint32_t dq, const float *min_cosine, uint32_t cap, rlr_search_hit *out,
+                                      uint32_t *n_out, uint64_t *n_total_out);
 /* rlr_engine_search_with_diversity_batch inside a filter: n_queries raw query embeddings, no lexical pairs; query q
  * equals rlr_engine_search_with_diversity_filtered(query q, n_lex = 0), N = |F| everywhere.  Hits of query q start at
  * out[q * cap]; n_out[q] = their count (every one 0 when |F| = 0).  The candidates come from ONE

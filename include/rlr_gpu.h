@@ -471,7 +471,7 @@ int32_t rlr_index_grouped_forms(rlr_index *idx, uint64_t counts[4], int32_t rese
  *   A NaN in tau: RLR_E_INVALID.  f may be null; filter rules (stale filters, another index' filter) as for
  *   rlr_search_topk_filtered; an empty filter or an empty index: RLR_OK with both counts 0.
  * Queries run one by one over the master rows, each with its own tau[q]: no coalescer, no nomination copy, no shared
- * pass.  The threshold collect runs on the device behind the scan (DESIGN.md "Range search"); it holds up to
+ * pass (rlr_search_range_batch below shares passes among the queries of a call).  The threshold collect runs on the device behind the scan (DESIGN.md "Range search"); it holds up to
  * RLR_RANGE_DEVICE_MAX hits per query.  What it cannot decide it hands on, never silently: */
 #define RLR_RANGE_DEVICE_MAX 65536
 int32_t rlr_search_range(rlr_index *idx, const rlr_filter *f, const float *queries, uint32_t n_queries, const float *tau,
@@ -483,6 +483,29 @@ int32_t rlr_search_range(rlr_index *idx, const rlr_filter *f, const float *queri
  * host); exact form taken [2] because allowed rows with NaN nominations exist or a masked row came back, [3] by rule (a
  * list-path filter, rows too wide for the staged re-score).  counts may be null. */
 int32_t rlr_index_range_forms(rlr_index *idx, uint64_t counts[4], int32_t reset);
+/* rlr_search_range for a BATCH: the same arguments, outputs, error rules and result definition, query by query, and for
+ * every input the same bits in every output -- only the number of passes over the rows differs.  2..8 queries over f32
+ * rows of 256 / 512 / 768 / 1024 elements share ONE scan (inside a mask-path filter one masked scan) and keep the f32
+ * band; 9 or more queries (and 2..8 where no shared scan serves the shape) over rows of a multiple of 128 elements, at
+ * least 4096 of them, every operand inside binary16 range, share one pass of the nomination GEMM per 1024 queries (over
+ * the nomination image when that is enabled; with a mask-path filter the pass still reads every row and the filter acts
+ * behind it).  Membership is decided on the reference-order score behind either pass.  Per query the device holds 8192
+ * GEMM candidates and, when rows are wanted, 2048 hits; a query beyond either, or with NaN nominations among its allowed
+ * rows, is handed back to the single-query path of rlr_search_range, never dropped or answered approximately.  One host
+ * synchronisation per chunk plus those of the queries handed back. */
+int32_t rlr_search_range_batch(rlr_index *idx, const rlr_filter *f, const float *queries, uint32_t n_queries,
+                               const float *tau, uint32_t cap, float guard_eps, uint64_t *rows_out, float *cos_out,
+                               uint32_t *n_out, uint64_t *n_total_out);
+/* When rlr_search_range_batch shares a pass: 0 (the default) where a cost model over the measured rates expects the
+ * shared pass to win, 1 never (every query one by one), 2 wherever the shape allows.  Any other mode: RLR_E_INVALID.
+ * The answers do not depend on it. */
+int32_t rlr_index_set_range_sharing(rlr_index *idx, int32_t mode);
+/* Queries of rlr_search_range_batch by form since the last reset, each query in exactly one: decided on the device [0]
+ * behind a shared scan, [1] behind the GEMM; handed to the single-query path [2] because a per-query device capacity was
+ * exceeded (see above), [3] by rule (one query, mode 1, the cost model declined, a list-path filter, a row shape no
+ * shared launch serves, operands beyond binary16 range where only the GEMM could share).  A handed-over query is counted
+ * by rlr_index_range_forms as well.  counts may be null. */
+int32_t rlr_index_range_batch_forms(rlr_index *idx, uint64_t counts[4], int32_t reset);
 
 /* ---- capped hybrid search: the per-document cap inside the blend and MMR ---- */
 /* rlr_search_hybrid with at most per_doc candidates from any one document, over all rows (f null) or the rows of f.

@@ -160,6 +160,9 @@ PROTOTYPES = [
     ("rlr_index_grouped_forms", C.c_int32, [_H, u64p, C.c_int32]),
     ("rlr_search_range", C.c_int32, [_H, _H, f32p, C.c_uint32, f32p, C.c_uint32, C.c_float, u64p, f32p, u32p, u64p]),
     ("rlr_index_range_forms", C.c_int32, [_H, u64p, C.c_int32]),
+    ("rlr_search_range_batch", C.c_int32, [_H, _H, f32p, C.c_uint32, f32p, C.c_uint32, C.c_float, u64p, f32p, u32p, u64p]),
+    ("rlr_index_set_range_sharing", C.c_int32, [_H, C.c_int32]),
+    ("rlr_index_range_batch_forms", C.c_int32, [_H, u64p, C.c_int32]),
     ("rlr_search_capped", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, C.c_float, C.c_int32, C.c_float, C.c_float, u64p, f32p,
                                       C.c_uint32, C.c_float, C.c_uint32, C.c_float, u64p, f32p, f32p, f32p, u32p, u32p]),
     ("rlr_index_capped_forms", C.c_int32, [_H, u64p, C.c_int32]),
@@ -196,6 +199,8 @@ PROTOTYPES = [
                                                   C.c_int32, C.POINTER(QueryWeightsC), C.c_uint32, C.POINTER(SearchHitC),
                                                   C.c_uint32, u32p]),
     ("rlr_engine_search_range", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_float, C.c_uint32, C.POINTER(SearchHitC), u32p, u64p]),
+    ("rlr_engine_search_range_batch", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, f32p, C.c_uint32, C.POINTER(SearchHitC), u32p,
+                                                  u64p]),
     ("rlr_engine_search_with_diversity_batch_filtered", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, C.c_uint32,
                                                                     C.c_float, C.POINTER(QueryWeightsC),
                                                                     C.POINTER(SearchHitC), C.c_uint32, u32p]),

@@ -471,4 +471,47 @@ int32_t rlr_engine_search_range(rlr_index *idx, const rlr_filter *f, const float
     return RLR_OK;
 }
 
+// rlr_engine_search_range for n_queries queries through ONE rlr_search_range_batch call: every query normalised as there,
+// the hits of query q filled the same way from out[q * cap] on.
+int32_t rlr_engine_search_range_batch(rlr_index *idx, const rlr_filter *f, const float *queries_raw, uint32_t n_queries, uint32_t dq,
+                                      const float *min_cosine, uint32_t cap, rlr_search_hit *out, uint32_t *n_out,
+                                      uint64_t *n_total_out)
+{
+    if (!idx || (n_queries && (!n_total_out || !min_cosine || (!queries_raw && dq) || (cap && (!out || !n_out)))))
+        return RLR_E_INVALID;
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        if (n_out)
+            n_out[q] = 0;
+        n_total_out[q] = 0;
+    }
+    uint32_t dim = 0;
+    int32_t st = rlr_index_info(idx, nullptr, &dim, nullptr, nullptr);
+    if (st != RLR_OK)
+        return st;
+    std::vector<float> qs(static_cast<size_t>(n_queries) * dim);
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        const std::vector<float> one = prepare_query(queries_raw ? queries_raw + static_cast<size_t>(q) * dq : nullptr, dq, dim);
+        std::copy(one.begin(), one.end(), qs.begin() + static_cast<size_t>(q) * dim);
+    }
+    std::vector<uint64_t> rows(static_cast<size_t>(n_queries) * cap);
+    std::vector<float> cosv(static_cast<size_t>(n_queries) * cap);
+    std::vector<uint32_t> n(n_queries, 0);
+    st = rlr_search_range_batch(idx, f, qs.data(), n_queries, min_cosine, cap, -1.0f, rows.data(), cosv.data(), n.data(), n_total_out);
+    if (st != RLR_OK)
+        return st;
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        for (uint32_t i = 0; i < n[q]; ++i) {
+            const size_t at = static_cast<size_t>(q) * cap + i;
+            out[at].row = rows[at];
+            out[at].score = cosv[at];
+            out[at].embedding_score = cosv[at];
+            out[at].lexical_score = 0.0f;
+            out[at].initial_score = cosv[at];
+        }
+        if (n_out)
+            n_out[q] = n[q];
+    }
+    return RLR_OK;
+}
+
 } // extern "C"

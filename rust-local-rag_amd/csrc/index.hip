@@ -134,6 +134,9 @@ struct Ctx {
     // range search (range.hip), grown lazily: the two counters and the unordered exact keys of the hits
     DevBuf<RangeState> d_rstate;   // with d_rhits
     DevBuf<uint64_t> d_rhits;      // min(cap, RLR_RANGE_DEVICE_MAX) of the largest call so far
+    // batched range search (range_batch_chunk): tau | lo | hi per query, and the chunk's result words
+    DevBuf<float> d_rbounds;
+    DevBuf<uint64_t> d_rout;
     // rlr_search_topk_device_begin / _end
     hipStream_t pending_stream = nullptr;
     uint32_t pending_q = 0, pending_k = 0;
@@ -231,6 +234,8 @@ struct rlr_index {
     uint64_t grouped_forms[4] = {0, 0, 0, 0}; // rlr_index_grouped_forms: queries served by each form (mu)
     uint64_t capped_forms[4] = {0, 0, 0, 0};  // rlr_index_capped_forms: the same for rlr_search_capped (mu)
     uint64_t range_forms[4] = {0, 0, 0, 0};   // rlr_index_range_forms: the same for rlr_search_range (mu)
+    uint64_t range_batch_forms[4] = {0, 0, 0, 0}; // rlr_index_range_batch_forms: the same for rlr_search_range_batch (mu)
+    std::atomic<int32_t> range_sharing{0};    // rlr_index_set_range_sharing: 0 auto (the cost model), 1 never, 2 wherever the shape allows
 };
 
 // A set of rows of one index, fixed at creation (rlr_filter_create_*): one bit per index row on the device (tail bits of
@@ -2764,6 +2769,177 @@ int32_t range_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *que
     return note_search(ix, c, 1, n_total, form != 0 ? 1 : 0, timed && form != 3);
 }
 
+// ---- batched range search (rlr_search_range_batch): the queries of a call share passes over the rows ------------------
+// Which shared pass serves a chunk of nq queries of this call -- kRangeShareScan: one VALU scan for 2..8 queries
+// (scan_multi_kernel, with a mask-path filter scan_masked_multi_kernel), the f32 band; kRangeShareGemm: the nomination
+// GEMM in filter mode for 9 or more, and for 2..8 where no shared scan serves the shape, the binary16 band -- or none
+// (kRangeShareNone: one by one through range_query, by rule).  f16_ok: the plan's, over all queries of the call.
+enum RangeShare : int { kRangeShareNone = -1, kRangeShareScan = 0, kRangeShareGemm = 1 };
+RangeShare range_share_path(const rlr_index *ix, const rlr_filter *f, uint32_t nq, bool f16_ok)
+{
+    if (nq < 2 || (f && f->path == 0) || !group_fits(ix->pitch16, ix->dim, ix->dtype) || ix->n_rows > 0xFFFFFFFFull)
+        return kRangeShareNone;
+    if (nq <= 8 && batch_multi_shape(ix, nq))
+        return kRangeShareScan;
+    // (the rows run_batched requires; operands beyond binary16 range keep the f32 paths, as batch_eligible has it)
+    if (ix->dim % 128 == 0 && ix->n_rows >= 4096 && f16_ok)
+        return kRangeShareGemm;
+    return kRangeShareNone;
+}
+
+// The auto gate (rlr_index_set_range_sharing mode 0): does the shared path win?  A cost model in the style of
+// batch_eligible, from the rates DESIGN.md records (RLR_BATCH_MIN is not consulted):
+//   one by one   per query 50 us of launches and its own synchronisation + the ALLOWED bytes at 7.3 TB/s
+//   shared scan  40 us (one copy, one synchronisation) + 25 us per query (its collect and finish workgroups) + the allowed
+//                bytes at the rate of the Q = 2 / 4 / 8 instance (6.45 / 6.1 / 5.8 TB/s; the middle one interpolated) + 4
+//                bytes per row and query for the collect's read of the score arrays at 3 TB/s
+//   GEMM         150 us + 1 us per query (its finish workgroup) + per 256 queries one pass over ALL rows (the mask only
+//                acts in the finish) at 4.4 TB/s over the row-major rows, 5 TB/s (up to 128 queries) / 2.85 TB/s of
+//                binary16 over the image + the result words at 20 GB/s
+// and the shared path must win by 10 %.  Fitted to tools/bench_range_batch.py's cells with 0 hits at 100 k and 1 M rows of
+// 768 f32 elements (profiles/range_batch_bench.json; DESIGN.md "Batched range search" has the table, the fit and what was
+// NOT measured -- among it every shape at which this model declines: no measured cell lost with sharing forced).
+bool range_share_wins(const rlr_index *ix, const rlr_filter *f, uint32_t nq, uint32_t cap, RangeShare path)
+{
+    const double el = ix->dtype == RLR_F16 ? 2.0 : 4.0;
+    const double n = static_cast<double>(ix->n_rows), allowed = static_cast<double>(f ? f->n_allowed : ix->n_rows);
+    const double t_single = nq * (50e-6 + allowed * ix->dim * el / 7.3e12);
+    double t_shared;
+    if (path == kRangeShareScan) {
+        const double rate = nq <= 2 ? 6.45e12 : nq <= 4 ? 6.1e12 : 5.8e12;
+        t_shared = 40e-6 + nq * 25e-6 + allowed * ix->dim * el / rate + nq * n * 4.0 / 3.0e12;
+    } else {
+        const bool image = ix->image_enabled && ix->d_image.get() && gemm_image_usable(ix->dim);
+        const double pass = image ? n * ix->dim * 2.0 / (nq <= 128 ? 5.0e12 : 2.85e12) : n * ix->dim * el / 4.4e12;
+        const double words = static_cast<double>(nq) * range_batch_words(std::min<uint32_t>(cap, kRangeFinishMax)) * 8.0;
+        t_shared = 150e-6 + nq * 1e-6 + pass * ((nq + 255) / 256) + words / 20e9;
+    }
+    return t_single > 1.1 * t_shared;
+}
+
+// One chunk of m queries through ONE shared pass (path: range_share_path's answer for m) and range.hip's batched tail:
+// the queries staged and uploaded once, tau | lo | hi per query computed here once (range_bounds) and uploaded, the pass,
+// the tail, ONE copy of the chunk's result words (keys, counts, status) and one synchronisation.  The band: the plan's f32
+// band behind the shared scan, exactly as in range_query; behind the GEMM image_two_eps (nomination_eps for the plan's
+// norms, scaled by the caller's guard_eps -- the bound run_batched trusts), with d_tau[q] = lo[q].  The plan is the
+// chunk's (the largest query norm): a band that is wider than a query's own only adds candidates, membership is decided on
+// the reference-order score.  forms[q]: 0 / 1 decided on the device behind the scan / the GEMM, 2 handed back -- a device
+// capacity (the GEMM's candidate list, kRangeFinishMax hits while rows are wanted), allowed rows with NaN nominations
+// behind the scan, a masked row among the results -- and then answered by range_query on the same context, after every
+// decided query has been read out of the pinned block (range_query stages into it again).
+// c->d_hist is not touched: the shared scans run without a histogram.
+int32_t range_batch_chunk(rlr_index *ix, Ctx *c, const rlr_filter *f, RangeShare path, const float *queries, const float *tau,
+                          uint32_t m, uint32_t cap, float guard_eps, uint64_t *rows_out, float *cos_out, uint32_t *n_out,
+                          uint64_t *n_total_out, uint32_t *forms)
+{
+    const uint64_t n_allowed = f ? f->n_allowed : ix->n_rows;
+    const uint32_t n = static_cast<uint32_t>(ix->n_rows);
+    const SearchPlan p = make_plan(ix, queries, m, 1, guard_eps);
+    RLR_TRY(ctx_prepare(ix, c, m, p));
+    const uint32_t out_keys = std::min<uint32_t>(cap, kRangeFinishMax), words = range_batch_words(out_keys);
+    const size_t n_res = static_cast<size_t>(m) * words;
+    Staged pin;
+    RLR_TRY(stage_call(ix, c, queries, m, n_res + 2 * static_cast<size_t>(m), /*for_scans=*/false, &pin));
+    uint64_t *h_res = pin.h_res;
+    float *h_bounds = reinterpret_cast<float *>(h_res + n_res), *h_tau = h_bounds + 3 * static_cast<size_t>(m);
+    hipStream_t s = c->stream;
+    const float two_eps = path == kRangeShareScan ? p.two_eps : p.two_eps_img;
+    for (uint32_t q = 0; q < m; ++q) {
+        float *b = h_bounds + 3 * static_cast<size_t>(q);
+        b[0] = tau[q];
+        range_bounds(tau[q], two_eps, &b[1], &b[2]);
+        h_tau[q] = b[1] == b[1] ? b[1] : -__builtin_inff(); // (a bound that is no number takes every row)
+    }
+    RLR_HIP(reserve_group(Want{c->d_rstate, m}, Want{c->d_rhits, std::max<size_t>(cap ? static_cast<size_t>(m) * kRangeFinishMax : 1, 1)}));
+    RLR_HIP(c->d_rbounds.reserve(3 * static_cast<size_t>(m)));
+    RLR_HIP(c->d_rout.reserve(n_res));
+    RLR_HIP(hipMemcpyAsync(c->d_rbounds.get(), h_bounds, 3 * static_cast<size_t>(m) * sizeof(float), hipMemcpyHostToDevice, s));
+    RangeBatchArgs ra{};
+    ra.n_queries = m;
+    ra.n = n;
+    ra.bounds = c->d_rbounds.get();
+    ra.cap = cap;
+    ra.rows = ix->d_rows.get();
+    ra.pitch16 = ix->pitch16;
+    ra.dim = ix->dim;
+    ra.dtype = ix->dtype;
+    ra.queries = c->d_query.get();
+    ra.q_pitch = ix->q_pitch;
+    ra.hits = c->d_rhits.get();
+    ra.out = c->d_rout.get();
+    ra.n_cu = ix->n_cu;
+    if (path == kRangeShareScan) {
+        const uint64_t s_stride = (static_cast<uint64_t>(n) + 3) / 4 * 4;
+        RLR_HIP(c->d_sample.reserve(static_cast<uint64_t>(m) * s_stride));
+        RLR_HIP(hipMemsetAsync(c->d_rstate.get(), 0, m * sizeof(RangeState), s));
+        const ScanArgs sa = scan_args(ix, c->d_query.get(), c->d_sample.get(), nullptr);
+        hipError_t e = hipSuccess;
+        if (!(f ? launch_scan_masked_multi(sa, f->d_mask.get(), f->n_allowed, ix->q_pitch, m, s_stride, s, &e)
+                : launch_scan_multi(sa, ix->q_pitch, m, s_stride, s, &e)))
+            return set_error(RLR_E_INTERNAL, "multi-query scan refused a shape the range gate accepted");
+        RLR_HIP(e);
+        ra.scores = c->d_sample.get();
+        ra.score_stride = s_stride;
+        ra.st = c->d_rstate.get();
+    } else {
+        const uint32_t fin_cap = batch_finish_capacity();
+        const uint32_t n_qblocks = (m + 255) / 256;
+        RLR_HIP(c->d_qfrag.reserve(static_cast<uint64_t>(n_qblocks) * 256 * ix->dim * 2));
+        RLR_HIP(c->d_gsync.reserve(256));
+        RLR_TRY(batch_arm(c, m, fin_cap, 0, 1, n)); // the states: cap = fin_cap, n_cand = 0
+        RLR_HIP(hipMemcpyAsync(c->d_tau.get(), h_tau, m * sizeof(float), hipMemcpyHostToDevice, s));
+        const bool use_image = ix->image_enabled && ix->d_image.get() && gemm_image_usable(ix->dim);
+        RLR_HIP(launch_prep_queries(c->d_query.get(), m, ix->q_pitch, ix->dim, use_image ? static_cast<int>(RLR_F16) : ix->dtype,
+                                    c->d_qfrag.get(), s));
+        RLR_HIP(launch_gemm_nominate(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, 0, n, c->d_qfrag.get(), m, c->d_tau.get(),
+                                     c->d_bcand.get(), fin_cap, c->d_bstate.get(), nullptr, 0, use_image ? ix->d_image.get() : nullptr, s,
+                                     c->d_gsync.get()));
+        ra.cand = c->d_bcand.get();
+        ra.cand_stride = fin_cap;
+        ra.bst = c->d_bstate.get();
+        ra.mask = f ? f->d_mask.get() : nullptr;
+    }
+    RLR_HIP(launch_range_batch_tail(ra, s));
+    RLR_HIP(hipMemcpyAsync(h_res, c->d_rout.get(), n_res * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    RLR_HIP(hipStreamSynchronize(s));
+    c->hist_dirty = false;
+    std::vector<uint32_t> redo;
+    uint64_t hits_total = 0;
+    for (uint32_t q = 0; q < m; ++q) {
+        const uint64_t *r = h_res + static_cast<size_t>(q) * words;
+        const uint32_t n_hits = static_cast<uint32_t>(r[out_keys]), n_valid = static_cast<uint32_t>(r[out_keys] >> 32);
+        const uint32_t n_res_q = cap ? std::min(n_hits, out_keys) : 0;
+        bool back = r[out_keys + 1] != kRangeBatchDecided || (path == kRangeShareScan && n_valid < n_allowed);
+        for (uint32_t i = 0; f && i < n_res_q && !back; ++i)
+            back = !filter_holds(f, 0xFFFFFFFFu - static_cast<uint32_t>(r[i])); // (the hazard filtered_query documents)
+        if (back) {
+            forms[q] = 2;
+            redo.push_back(q);
+            continue;
+        }
+        forms[q] = path == kRangeShareScan ? 0 : 1;
+        n_total_out[q] = n_hits;
+        hits_total += n_hits;
+        if (n_out)
+            n_out[q] = n_res_q;
+        if (n_res_q)
+            unpack_results(r, n_res_q, rows_out + static_cast<size_t>(q) * cap, cos_out + static_cast<size_t>(q) * cap);
+    }
+    {
+        std::lock_guard<std::mutex> lk(ix->mu);
+        ix->prof.n_batches += 1;
+        ix->prof.n_batch_queries += m;
+        ix->prof.n_batch_fallbacks += redo.size();
+    }
+    RLR_TRY(note_search(ix, c, m - static_cast<uint32_t>(redo.size()), hits_total, 0, /*timed=*/false));
+    // (from here on the pinned block and the context are range_query's)
+    for (uint32_t q : redo)
+        RLR_TRY(range_query(ix, c, f, queries + static_cast<size_t>(q) * ix->dim, tau[q], cap, guard_eps,
+                            cap ? rows_out + static_cast<size_t>(q) * cap : nullptr, cap ? cos_out + static_cast<size_t>(q) * cap : nullptr,
+                            n_out ? &n_out[q] : nullptr, &n_total_out[q]));
+    return RLR_OK;
+}
+
 // ---- several queries, inside one filter or a filter each: one shared masked pass ------------------------------------
 // Can a query over `f` join a shared pass at all?  Its filter is on the masked-scan path and holds at least k rows (one
 // plan, one rank k for the whole chunk), the rows are a shape the kernel serves and k leaves the finish its band.
@@ -3902,6 +4078,93 @@ int32_t rlr_index_range_forms(rlr_index *ix, uint64_t counts[4], int32_t reset)
             counts[i] = ix->range_forms[i];
         if (reset)
             ix->range_forms[i] = 0;
+    }
+    return RLR_OK;
+}
+
+int32_t rlr_search_range_batch(rlr_index *ix, const rlr_filter *f, const float *queries, uint32_t n_queries, const float *tau,
+                               uint32_t cap, float guard_eps, uint64_t *rows_out, float *cos_out, uint32_t *n_out,
+                               uint64_t *n_total_out)
+{
+    RLR_TRY(check_handle(ix));
+    if (f)
+        RLR_TRY(check_filter(ix, f)); // (a stale filter is refused before any GPU work)
+    if (n_queries && (!queries || !tau || !n_total_out))
+        return set_error(RLR_E_INVALID, "queries / tau / n_total_out is null");
+    if (n_queries && cap && (!rows_out || !cos_out || !n_out))
+        return set_error(RLR_E_INVALID, "output buffers are null (only a count-only call, cap == 0, may leave them out)");
+    for (uint32_t q = 0; q < n_queries; ++q)
+        if (!(tau[q] == tau[q]))
+            return set_error(RLR_E_INVALID, "tau[%u] is NaN", q);
+    RLR_TRY(use_device(ix));
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        if (n_out)
+            n_out[q] = 0;
+        n_total_out[q] = 0;
+    }
+    if ((f ? f->n_allowed : ix->n_rows) == 0 || n_queries == 0)
+        return RLR_OK;
+    CtxLease lease(ix);
+    RLR_TRY(ctx_acquire(ix, &lease.c));
+    StreamDrain drain{lease.c->stream};
+    // the chunks: up to kBatchMaxQueries queries per GEMM pass, all of 2..8 in one shared scan; anything else one by one
+    const int32_t mode = ix->range_sharing.load();
+    RangeShare path = kRangeShareNone;
+    if (mode != 1 && n_queries >= 2) {
+        const bool f16_ok = make_plan(ix, queries, n_queries, 1, guard_eps).f16_ok;
+        path = range_share_path(ix, f, n_queries, f16_ok);
+        if (path != kRangeShareNone && mode == 0 && !range_share_wins(ix, f, std::min(n_queries, kBatchMaxQueries), cap, path))
+            path = kRangeShareNone;
+    }
+    uint64_t forms[4] = {0, 0, 0, 0};
+    std::vector<uint32_t> chunk_forms;
+    int32_t rc = RLR_OK;
+    for (uint32_t q0 = 0; q0 < n_queries && rc == RLR_OK;) {
+        const float *qs = queries + static_cast<size_t>(q0) * ix->dim;
+        uint64_t *ro = cap ? rows_out + static_cast<size_t>(q0) * cap : nullptr;
+        float *co = cap ? cos_out + static_cast<size_t>(q0) * cap : nullptr;
+        if (path == kRangeShareNone) {
+            rc = range_query(ix, lease.c, f, qs, tau[q0], cap, guard_eps, ro, co, n_out ? &n_out[q0] : nullptr, &n_total_out[q0]);
+            forms[3]++;
+            q0 += 1;
+            continue;
+        }
+        const uint32_t m = std::min(kBatchMaxQueries, n_queries - q0);
+        chunk_forms.assign(m, 0);
+        rc = range_batch_chunk(ix, lease.c, f, path, qs, tau + q0, m, cap, guard_eps, ro, co, n_out ? n_out + q0 : nullptr,
+                               n_total_out + q0, chunk_forms.data());
+        for (uint32_t i = 0; i < m && rc == RLR_OK; ++i)
+            forms[chunk_forms[i]]++;
+        q0 += m;
+    }
+    {
+        std::lock_guard<std::mutex> lk(ix->mu);
+        for (int i = 0; i < 4; ++i)
+            ix->range_batch_forms[i] += forms[i];
+    }
+    RLR_TRY(rc);
+    drain.armed = false;
+    return RLR_OK;
+}
+
+int32_t rlr_index_set_range_sharing(rlr_index *ix, int32_t mode)
+{
+    RLR_TRY(check_handle(ix));
+    if (mode < 0 || mode > 2)
+        return set_error(RLR_E_INVALID, "range sharing mode %d (0 auto, 1 never, 2 wherever the shape allows)", mode);
+    ix->range_sharing.store(mode);
+    return RLR_OK;
+}
+
+int32_t rlr_index_range_batch_forms(rlr_index *ix, uint64_t counts[4], int32_t reset)
+{
+    RLR_TRY(check_handle(ix));
+    std::lock_guard<std::mutex> lk(ix->mu);
+    for (int i = 0; i < 4; ++i) {
+        if (counts)
+            counts[i] = ix->range_batch_forms[i];
+        if (reset)
+            ix->range_batch_forms[i] = 0;
     }
     return RLR_OK;
 }

@@ -364,4 +364,41 @@ struct RangeArgs {
 inline uint32_t range_out_words(uint32_t out_keys) { return out_keys + 1; }
 hipError_t launch_range_tail(const RangeArgs &a, hipStream_t s);
 
+// The tail of a BATCHED range search (rlr_search_range_batch): n_queries queries whose nominated scores came from ONE
+// pass over the rows -- either `scores` (a shared VALU scan: one score array per query, score_stride apart; the multi-query
+// collect, then the finish orders and emits) or `cand` (the nomination GEMM in filter mode with d_tau[q] = lo[q]: query q's
+// (nominated key, row) words at cand + q * cand_stride, their count in bst[q].n_cand; the finish does the whole tail).
+// Every query keeps up to kRangeFinishMax exact keys when rows are wanted (cap != 0), whatever cap is -- lower than the
+// single path's min(cap, RLR_RANGE_DEVICE_MAX): a query with more hits is handed back and the single path owns that case.
+// Per query, range_batch_words(out_keys) words in `out` (device memory; one copy brings the whole chunk back):
+//   out_keys = min(cap, kRangeFinishMax) keys in result order, zeros behind | n_hits + (n_valid << 32) | status
+enum RangeBatchStatus : uint32_t {
+    kRangeBatchDecided = 0,
+    kRangeBatchCandidates = 1, // behind the GEMM: the candidate list overflowed (or the image kernel's bit 31 mark is set)
+    kRangeBatchHits = 2,       // rows wanted and more than kRangeFinishMax hits
+};
+struct RangeBatchArgs {
+    uint32_t n_queries;
+    uint32_t n;              // rows of the index
+    const float *scores;     // shared scan: n_queries x score_stride nominated scores (NaN: masked, or a NaN nomination); else null
+    size_t score_stride;
+    const uint64_t *cand;    // GEMM: n_queries x cand_stride nominated (key, row) words; else null
+    uint32_t cand_stride;    // = the capacity the lists were armed with
+    const SelectState *bst;  // GEMM: n_cand per query (bit 31: the image kernel's workgroup list overflowed)
+    const uint64_t *mask;    // GEMM with a mask-path filter: one bit per row, candidates with a clear bit are dropped; else null
+    const float *bounds;     // device, n_queries x 3: tau | lo | hi (range_bounds, computed once on the host)
+    uint32_t cap;            // the caller's cap; 0: count only
+    RangeState *st;          // shared scan: n_queries states
+    const void *rows;
+    uint32_t pitch16, dim;
+    int dtype;
+    const float *queries;    // device, q_pitch floats each
+    uint32_t q_pitch;
+    uint64_t *hits;          // n_queries x kRangeFinishMax exact packed keys, in no order (untouched when cap == 0)
+    uint64_t *out;           // n_queries x range_batch_words(min(cap, kRangeFinishMax)) words
+    int n_cu;
+};
+inline uint32_t range_batch_words(uint32_t out_keys) { return out_keys + 2; }
+hipError_t launch_range_batch_tail(const RangeBatchArgs &a, hipStream_t s);
+
 } // namespace rlr

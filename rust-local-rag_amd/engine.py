@@ -708,19 +708,48 @@ class RagEngine:
         rows, cos = rows[keep][:max(int(limit), 0)], cos[keep][:max(int(limit), 0)]
         return self._embedding_results(rows, cos), total
 
-    def _duplicates_of(self, emb: np.ndarray, min_score: float) -> List[List[str]]:
+    def _duplicates_of(self, emb: np.ndarray, min_score: float, f: Optional[RowFilter] = None) -> List[List[str]]:
         """per row of `emb` (raw embeddings, normalised here as the append normalises them): the ids of the chunks in
-        the index at or above `min_score`, best first"""
+        the index (inside `f`) at or above `min_score`, best first -- one search_range_batch call: the rows are read
+        once per shared pass, not once per embedding"""
         if len(self._chunks) == 0 or emb.shape[0] == 0:
             return [[] for _ in range(emb.shape[0])]
         q = np.stack([normalize(e) for e in emb])
-        res = self.index.search_range(q, min_score, 256)
+        res = self.index.search_range_batch(q, min_score, 256, filter=f)
         out = []
         for i, (rows, _, total) in enumerate(res):
             if total > rows.size:                            # (a boilerplate chunk: fetch them all)
-                rows = self.index.search_range(q[i], min_score, total)[0][0]
+                rows = self.index.search_range(q[i], min_score, total, filter=f)[0][0]
             out.append([self._chunks[int(r)].id for r in rows])
         return out
+
+    def duplicates_of(self, embeddings, min_score: float, documents: Optional[Sequence[str]] = None) -> List[List[str]]:
+        """Per embedding (raw; normalised as add_document normalises them): the ids of the stored chunks whose cosine
+        with it is at least `min_score`, best first -- what add_document(report_duplicates_above=) reports, without
+        adding anything.  `documents`: only inside these (as `search`).  The embeddings share passes over the rows."""
+        emb = _f32(embeddings).reshape(-1, self.dim)
+        if len(self._chunks) == 0:
+            return [[] for _ in range(emb.shape[0])]
+        f = self._filter_for(documents) if documents is not None else None
+        return self._duplicates_of(emb, float(min_score), f)
+
+    def duplicate_chunks(self, min_score: float, limit_per_chunk: int = 256) -> List[Tuple[str, str, float]]:
+        """The corpus against itself: every pair of stored chunks whose cosine is at least `min_score`, as (id_a, id_b,
+        cosine) with row_a < row_b, each pair once, a chunk never with itself; ordered by row_a, then best first.  Blocks
+        of up to 256 stored rows are fetched and used as the queries of one search_range_batch call each, so the whole
+        comparison costs ceil(N / 256) passes over the rows, not N.  `limit_per_chunk` bounds the hits looked at per
+        chunk (its best ones, the chunk itself among them): a chunk with more partners than that reports its best."""
+        n = len(self._chunks)
+        cap = max(int(limit_per_chunk), 1)
+        pairs: List[Tuple[str, str, float]] = []
+        for first in range(0, n, 256):
+            block = np.arange(first, min(first + 256, n))
+            q = self.index.fetch_rows(block)
+            for a, (rows, cos, _) in zip(block.tolist(), self.index.search_range_batch(q, min_score, cap)):
+                for b, c in zip(rows.tolist(), cos.tolist()):
+                    if b > a:
+                        pairs.append((self._chunks[a].id, self._chunks[b].id, c))
+        return pairs
 
     # -- API layer: search_documents / http_search (mcp_server.rs:81-110, :371-389) --------
     def search_documents(self, request: SearchRequest) -> List[SearchResult]:

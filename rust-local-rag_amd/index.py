@@ -333,6 +333,45 @@ class GpuIndex:
         N.check(self._L.rlr_index_range_forms(self._h, _up(counts), int(reset)))
         return [int(c) for c in counts]
 
+    def search_range_batch(self, queries, tau, cap: int, filter: "RowFilter | None" = None, guard_eps: float = -1.0):
+        """search_range with the queries of the call sharing passes over the rows (rlr_search_range_batch): the same
+        arguments, the same list of (rows u64, cos f32, n_total) per query, bit for bit -- 2..8 queries share one scan,
+        more share one matrix-core pass per 1024 where the rows allow it (set_range_sharing, range_batch_forms)"""
+        q = _f32(queries).reshape(-1, self.dim)
+        nq = q.shape[0]
+        t = _f32(tau).ravel()
+        if t.size == 1:
+            t = np.full(nq, t[0], dtype=np.float32)
+        if t.size != nq:
+            raise ValueError(f"{nq} queries but {t.size} thresholds")
+        cap = int(cap)
+        rows = np.zeros((nq, max(cap, 1)), dtype=np.uint64)
+        cos = np.zeros((nq, max(cap, 1)), dtype=np.float32)
+        n_out = np.zeros(max(nq, 1), dtype=np.uint32)
+        n_total = np.zeros(max(nq, 1), dtype=np.uint64)
+        N.check(self._L.rlr_search_range_batch(self._h, None if filter is None else filter.handle, _fp(q), nq, _fp(t), cap, guard_eps,
+                                               _up(rows), _fp(cos), _u32ptr(n_out), _up(n_total)))
+        if cap == 0:
+            return [(rows[i, :0], cos[i, :0], int(n_total[i])) for i in range(nq)]
+        return [(rows[i, :int(n_out[i])], cos[i, :int(n_out[i])], int(n_total[i])) for i in range(nq)]
+
+    def count_range_batch(self, queries, tau, filter: "RowFilter | None" = None) -> list:
+        """how many rows score at least tau, per query, over shared passes (rlr_search_range_batch with cap = 0)"""
+        return [n for _, _, n in self.search_range_batch(queries, tau, 0, filter=filter)]
+
+    def set_range_sharing(self, mode: int) -> None:
+        """when search_range_batch shares a pass: 0 where the cost model expects it to win (the default), 1 never, 2
+        wherever the shape allows (rlr_index_set_range_sharing); the answers do not depend on it"""
+        N.check(self._L.rlr_index_set_range_sharing(self._h, int(mode)))
+
+    def range_batch_forms(self, reset: bool = False) -> list:
+        """queries search_range_batch served by each form: [decided on the device behind a shared scan, behind the
+        matrix-core pass, handed to the single-query path because a device capacity was exceeded, handed to it by rule]
+        (rlr_index_range_batch_forms)"""
+        counts = np.zeros(4, dtype=np.uint64)
+        N.check(self._L.rlr_index_range_batch_forms(self._h, _up(counts), int(reset)))
+        return [int(c) for c in counts]
+
     def search_capped(self, query, need: int, per_document: int, k: int = 0, lam: float = 0.0, diversify: bool = False,
                       w_embedding: float = 1.0, w_lexical: float = 0.0, lex_rows=None, lex_scores=None, max_lex: float = 1.0,
                       filter: "RowFilter | None" = None, guard_eps: float = -1.0):
