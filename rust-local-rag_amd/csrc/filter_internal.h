@@ -1,5 +1,5 @@
 // filter_internal.h -- what the other translation units of the library see of a row filter (include/rlr_gpu.h,
-// rlr_filter_create_*; the object itself lives in index.hip).
+// rlr_filter_create_*; the object itself is declared in index_internal.h and made in index.hip).
 #pragma once
 
 #include "../../include/rlr_gpu.h"
@@ -19,7 +19,7 @@ int32_t filter_view(const rlr_filter *f, FilterView *out);
 // the same, and RLR_E_INVALID for a filter that was made for another index than `ix`; no GPU work
 int32_t filter_check(const rlr_index *ix, const rlr_filter *f);
 
-// rlr_score_rows for nq prepared (dim-long) queries with a row list each, for the batched text search inside a filter:
+// (index_fused.hip) rlr_score_rows for nq prepared (dim-long) queries with a row list each, for the batched text search inside a filter:
 // query q against rows[q * stride .. q * stride + counts[q]) -> cos_out at the same places, bit for bit what
 // rlr_score_rows returns per pair.  One upload, one launch, one copy back, one synchronisation.
 int32_t score_rows_batch(rlr_index *ix, const float *queries, uint32_t nq, const uint64_t *rows, const uint32_t *counts,

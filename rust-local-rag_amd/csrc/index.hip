@@ -3,15 +3,13 @@
 //   scan (+digit-1 histogram) -> tail stage 1 -> tail stage 2 (tail.hip: select, reference-order re-score, sort, results
 //   and a completion word straight into pinned host memory), or above 4 M rows the four specialised launches
 //   hist2_find1 -> collect_find2 -> rescore_staged -> sort_emit; batches of queries go through the matrix cores (gemm.hip).
+// This file defines the frame index_internal.h declares; the search chains that end in a blend or MMR on the device are
+// in index_fused.hip.
 // There is no CPU compute path in this file: without a HIP device every compute entry
 // point fails with RLR_E_NO_DEVICE.
-#include "../../include/rlr_gpu.h"
-#include "common.h"
-#include "device_buffer.h"
-#include "kernels.h"
+#include "index_internal.h"
 #include "lds_select.h"
 #include "sort_emit.h"
-#include "pool_prepare.h"
 #include "lexical_internal.h"
 #include "filter_internal.h"
 
@@ -27,7 +25,6 @@
 #include <mutex>
 #include <memory>
 #include <new>
-#include <string>
 #include <thread>
 #include <unordered_map>
 #include <vector>
@@ -54,211 +51,6 @@ int32_t set_error(int32_t code, const char *fmt, ...)
 }
 } // namespace rlr
 
-namespace {
-
-#define RLR_HIP(call)                                                                                    \
-    do {                                                                                                 \
-        hipError_t e_ = (call);                                                                          \
-        if (e_ != hipSuccess)                                                                            \
-            return set_error(e_ == hipErrorOutOfMemory ? RLR_E_OOM : RLR_E_HIP, "%s failed: %s (%s:%d)", \
-                             #call, hipGetErrorString(e_), __FILE__, __LINE__);                          \
-    } while (0)
-
-#define RLR_TRY(call)                                                                              \
-    do {                                                                                           \
-        int32_t s_ = (call);                                                                       \
-        if (s_ != RLR_OK)                                                                          \
-            return s_;                                                                             \
-    } while (0)
-
-constexpr uint32_t kLdsSortCap = 4096; // candidates the single-workgroup sort can take
-constexpr uint32_t kMaxDim = 8192;
-
-uint32_t next_pow2(uint32_t v)
-{
-    uint32_t p = 1;
-    while (p < v)
-        p <<= 1;
-    return p;
-}
-
-// how long the recent waits of one kind took (the hybrid wait sleeps through most of that before it polls)
-struct WaitEma {
-    double us = 0.0;
-    uint32_t key = 0; // what "one kind" means to the caller (number of queries, ...): a change resets the average
-};
-
-// -------- per-call context ---------------------------------------------------------
-struct Ctx {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    // device
-    // (buffers named together grow together: reserve_group, device_buffer.h)
-    DevBuf<float> d_query;         // q x q_pitch floats, with d_state
-    DevBuf<float> d_scores;
-    DevBuf<uint32_t> d_hist;       // 2 * kHistBins
-    DevBuf<SelectState> d_state;   // q states
-    DevBuf<uint32_t> d_cand;       // with d_packed
-    DevBuf<uint64_t> d_packed;     // (a power of two)
-    DevBuf<uint64_t> d_out;        // packed results
-    DevBuf<uint32_t> d_list;       // row lists (score_rows / fetch / mmr), with d_vals
-    DevBuf<float> d_vals;          // float outputs for lists / mmr
-    DevBuf<float> d_pool;          // mmr pool P x dim, then gram P x P
-    // batched (MFMA) path workspace
-    DevBuf<uint8_t> d_qfrag;        // binary16 fragment-major queries
-    DevBuf<float> d_tau;            // per-query nomination threshold; with d_bstate, d_bhist, d_bstatus and h_batch
-    DevBuf<SelectState> d_bstate;
-    DevBuf<uint32_t> d_bhist;       // q x 2 x kHistBins
-    DevBuf<uint32_t> d_bstatus;
-    DevBuf<uint32_t> d_gsync;      // 256 words: sibling-group arrival counters of the persistent batched GEMM (gemm.hip)
-    PinBuf h_batch;                // SelectState[q] | status[q] (pageable staging makes the async copies synchronous)
-    bool no_f16 = false;            // this call's queries or the rows leave binary16 range: no binary16 nomination
-    DevBuf<uint64_t> d_bcand;       // q x fin_cap packed candidates
-    DevBuf<float> d_sample;         // q x S nominated scores of the sample rows
-    hipEvent_t bev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    PinBuf h_pin;                   // staging of a call's queries and results
-    std::vector<float> q_norm; // ||q||_2 of the staged queries (band of the 8-bit nomination scan)
-    WaitEma wait_ema;          // how long the last waits for a call's completion words took (wait_flags)
-    const float *h_q_kq = nullptr; // set for the duration of a call whose scans take their query in the kernel arguments
-                                   // (ScanArgs::query_host): the staged queries in pinned host memory, q_pitch floats each
-    bool hist_dirty = false; // a pipeline was enqueued and did not complete: d_hist may hold counts
-    PinBuf h_assert;         // RLR_POISON_ALLOC=1 only: pinned word the zero-histogram assertion kernel counts into
-    // grouped search (group.hip), grown lazily: the document table, t_g per row, the heads' histograms, the candidates
-    DevBuf<uint32_t> d_gkeys;      // 1 << bits slots, with d_gvals
-    DevBuf<uint64_t> d_gvals;      // slots x per_doc
-    DevBuf<uint64_t> d_gtg;        // rows
-    DevBuf<uint32_t> d_ghist;      // 2 * kHistBins, with d_gstate, d_gcand and d_gcdoc
-    DevBuf<GroupState> d_gstate;
-    DevBuf<uint64_t> d_gcand;      // kGroupCap
-    DevBuf<uint32_t> d_gcdoc;      // kGroupCap
-    // range search (range.hip), grown lazily: the two counters and the unordered exact keys of the hits
-    DevBuf<RangeState> d_rstate;   // with d_rhits
-    DevBuf<uint64_t> d_rhits;      // min(cap, RLR_RANGE_DEVICE_MAX) of the largest call so far
-    // batched range search (range_batch_chunk): tau | lo | hi per query, and the chunk's result words
-    DevBuf<float> d_rbounds;
-    DevBuf<uint64_t> d_rout;
-    // rlr_search_topk_device_begin / _end
-    hipStream_t pending_stream = nullptr;
-    uint32_t pending_q = 0, pending_k = 0;
-    bool pending_timed = false;
-    const uint64_t *pending_meta = nullptr;
-};
-
-// One caller's part in a coalesced group: its query and where its results go (the caller's own buffers; the caller
-// blocks until the group is done, so they outlive the group's use of them).
-struct CoalesceMember {
-    const float *query;
-    uint32_t k;
-    uint64_t *rows_out;
-    float *cos_out;
-    uint32_t *n_out;
-};
-
-struct CoalesceGroup {
-    uint32_t key = 0;      // bits of the members' guard_eps
-    uint32_t cap = 0;      // members it takes
-    std::vector<CoalesceMember *> members; // [0] is the leader
-    bool sealed = false;   // takes no more members
-    bool go = false;       // holds a pipeline slot
-    bool done = false;     // results written (or status set)
-    int32_t status = 0;
-    char msg[512] = "";
-};
-
-} // namespace
-
-struct rlr_index {
-    uint32_t dim = 0;
-    int32_t dtype = RLR_F32;
-    int32_t device = 0;
-    uint32_t pitch16 = 0;   // row pitch in 16-byte units
-    uint32_t q_pitch = 0;   // floats per staged query (row pitch in elements)
-    uint64_t n_rows = 0;
-    uint64_t cap_rows = 0;
-    DevBuf<char> d_rows;    // cap_rows x row_bytes
-    DevBuf<uint32_t> d_docs; // optional document column: one id per row (capacity >= cap_rows), RLR_DOC_NONE = no document;
-                             // absent until rlr_index_set_documents / rlr_index_tag_rows
-    uint64_t compact_chunk_rows = 0; // RLR_COMPACT_CHUNK_ROWS: rows per bounce-buffer step of rlr_index_delete_documents
-                                     // (0: as many as fit in 256 MiB); a test forces several steps on a small index with it
-    int n_cu = 256;
-    int scan_variant = 0;
-    int fused_tail = -1;         // select -> re-score -> sort behind the scan in two launches (tail.hip): RLR_TAIL=1 always, 0 never
-                                 // (the five-launch form), unset: while the corpus is small enough for the one-pass mode to be the rule
-    uint32_t tail_direct_max = 3584; // RLR_TAIL_DIRECT_MAX: most scores in/above the k-th score's digit-1 bin for the one-pass mode (0: always
-                                     // refine).  Re-scoring a few thousand candidates costs less than the two extra passes of the refine
-                                     // mode (they spread over the workgroups that found them); 512 slots of the 4096 stay for the guard band.
-                                     // A call that builds an MMR pool from the candidates caps it at 1024 (what the pool kernel takes).
-    // Hybrid (text) searches: how many rows by cosine the blend asks the tail for beyond the `need` it keeps.  A lexical term
-    // only ever ADDS to a row's blended score (weights and BM25 scores are non-negative as a rule), so the need + 8 best
-    // cosines already hold every non-lexical row that can reach the pool, whatever the lexical rows among them do; the
-    // blend kernel checks that on what it got -- its need-th blended score must beat anything an unfetched row can reach,
-    // status 2 and the host's widening path else (a negative lexical weight, a tie across the boundary).  Rounds 2-3
-    // fetched need + n_lexical + 8 (every lexical row counted as if it displaced one): 1808 rows instead of 332 for a
-    // top-100 text search, a crowded digit-1 bin and ~25 us more tail.  RLR_HYBRID_FETCH=full at creation restores that.
-    bool hybrid_fetch_full = false;
-    uint32_t batch_min = 0;   // smallest batch that takes the matrix-core path; 0 = decide by the cost model,
-                              // RLR_BATCH_MIN=n forces a threshold (a huge n disables the path)
-    float max_row_sumsq = 1.0f; // largest sum of squares of a row stored with normalize_on_device = 0 (>= 1): the guard
-                                // bands are derived for unit-norm operands and scale with |row| * |query|
-    bool f16_overflow = false;  // an f32 row stored as given holds an element outside binary16 range (|x| > 65504):
-                                // binary16 nomination would see it as +-Inf (and Inf - Inf = NaN); such rows stay
-                                // on the f32 paths until the next upload
-    bool image_enabled = false; // keep a binary16 nomination image of the rows for the batched GEMM
-    bool image_scan = false;    // single queries nominate over the image too (half the bytes of f32 rows)
-    // optional 8-bit nomination copy for single queries (q8.hip): a quarter of the f32 bytes
-    bool q8_enabled = false;
-    DevBuf<uint8_t> d_q8;        // cap_rows x dim bytes, with d_q8_scale
-    DevBuf<float> d_q8_scale;    // cap_rows
-    DevBuf<uint32_t> d_q8_stats; // [0] max row error norm (float bits), [1] max scale (float bits), [2] an Inf row exists
-    float q8_delta = 0.0f, q8_scale_max = 0.0f;
-    bool q8_has_inf = false;
-    DevBuf<uint8_t> d_image;
-    std::mutex mu;
-    std::condition_variable ctx_cv; // callers beyond ctx_cap wait here for a context to come back
-    std::vector<Ctx *> free_ctx;
-    int ctx_made = 0;               // contexts alive (in free_ctx or leased)
-    int ctx_cap = 16;               // RLR_MAX_CONTEXTS (1..64)
-    bool profiling = false;
-    rlr_profile prof{};
-    // coalescing of concurrent single-query searches (rlr_index_set_coalescing; the coalescer section below)
-    std::atomic<uint32_t> co_max{0};  // 0: off -- the only thing a single-query call reads when it is
-    uint32_t co_linger_us = 0;        // (co_mu)
-    std::mutex co_mu;
-    std::condition_variable co_cv;    // leaders wait for a pipeline slot / their group to fill, members for their results
-    int co_running = 0;               // coalescer pipelines in flight (co_mu)
-    std::vector<std::shared_ptr<CoalesceGroup>> co_pending; // groups waiting for a slot, oldest first (co_mu)
-    rlr_coalesce_stats co_stats{};    // (co_mu)
-    // bumped by every call that changes which rows the index holds (upload, append, delete_rows, fill_synthetic; load_json
-    // goes through upload): a row filter records it at creation and is refused as stale once it has moved on
-    std::atomic<uint64_t> mutations{0};
-    uint64_t grouped_forms[4] = {0, 0, 0, 0}; // rlr_index_grouped_forms: queries served by each form (mu)
-    uint64_t capped_forms[4] = {0, 0, 0, 0};  // rlr_index_capped_forms: the same for rlr_search_capped (mu)
-    uint64_t range_forms[4] = {0, 0, 0, 0};   // rlr_index_range_forms: the same for rlr_search_range (mu)
-    uint64_t range_batch_forms[4] = {0, 0, 0, 0}; // rlr_index_range_batch_forms: the same for rlr_search_range_batch (mu)
-    std::atomic<int32_t> range_sharing{0};    // rlr_index_set_range_sharing: 0 auto (the cost model), 1 never, 2 wherever the shape allows
-};
-
-// A set of rows of one index, fixed at creation (rlr_filter_create_*): one bit per index row on the device (tail bits of
-// the last word zero) and on the host (the check that no returned row is masked, the engine's row enumeration), the
-// allowed rows as an ascending list on the device (the list path, and the exact fall-back of the masked scan), the count.
-struct rlr_filter {
-    rlr_index *ix = nullptr;
-    uint64_t index_rows = 0, n_allowed = 0, mutations = 0;
-    int32_t path = 0; // 0: list path, 1: masked scan
-    DevBuf<uint64_t> d_mask;
-    DevBuf<uint32_t> d_list;
-    std::vector<uint64_t> h_mask;
-};
-
-namespace {
-
-size_t row_bytes(const rlr_index *ix)
-{
-    return static_cast<size_t>(ix->pitch16) * 16;
-}
-
-} // namespace
-
 namespace rlr {
 bool poison_mode()
 {
@@ -282,9 +74,7 @@ hipError_t dev_malloc(void **p, size_t bytes)
     }
     return e;
 }
-} // namespace rlr
 
-namespace {
 int32_t use_device(const rlr_index *ix)
 {
     RLR_HIP(hipSetDevice(ix->device));
@@ -298,7 +88,7 @@ int32_t pin_reserve(Ctx *c, size_t bytes)
 }
 
 // c->d_query / c->d_state for nq queries
-int32_t reserve_queries(const rlr_index *ix, Ctx *c, uint32_t nq)
+static int32_t reserve_queries(const rlr_index *ix, Ctx *c, uint32_t nq)
 {
     if (c->d_state.capacity() >= nq)
         return RLR_OK;
@@ -312,13 +102,13 @@ int32_t reserve_queries(const rlr_index *ix, Ctx *c, uint32_t nq)
 }
 
 // c->d_cand / c->d_packed for cap candidates
-int32_t reserve_cand(Ctx *c, uint32_t cap)
+static int32_t reserve_cand(Ctx *c, uint32_t cap)
 {
     RLR_HIP(reserve_group(Want{c->d_cand, cap}, Want{c->d_packed, cap}));
     return RLR_OK;
 }
 
-void ctx_free(Ctx *c)
+static void ctx_free(Ctx *c)
 {
     if (!c)
         return;
@@ -330,10 +120,6 @@ void ctx_free(Ctx *c)
     delete c; // (the buffers free themselves)
 }
 
-// A free context, a new one while fewer than ctx_cap exist, else wait until a call hands one back.  The reference serves
-// searches from one tokio worker per core under a read lock (src/main.rs:140, src/mcp_server.rs:89, :377): callers may be
-// many, but every context costs a stream, pinned memory and n_rows x 4 B of scores, and more streams than hardware
-// queues buy no overlap -- so the pool is bounded like the lexical index' workspaces and the surplus callers queue.
 int32_t ctx_acquire(rlr_index *ix, Ctx **out)
 {
     {
@@ -411,17 +197,6 @@ void ctx_release(rlr_index *ix, Ctx *c)
     ix->ctx_cv.notify_one();
 }
 
-struct CtxLease {
-    rlr_index *ix;
-    Ctx *c = nullptr;
-    explicit CtxLease(rlr_index *i) : ix(i) {}
-    ~CtxLease()
-    {
-        if (c)
-            ctx_release(ix, c);
-    }
-};
-
 int32_t check_handle(const rlr_index *ix)
 {
     if (!ix)
@@ -429,7 +204,7 @@ int32_t check_handle(const rlr_index *ix)
     return RLR_OK;
 }
 
-int32_t ensure_rows(rlr_index *ix, uint64_t want_rows)
+static int32_t ensure_rows(rlr_index *ix, uint64_t want_rows)
 {
     if (want_rows <= ix->cap_rows)
         return RLR_OK;
@@ -470,7 +245,7 @@ int32_t ensure_rows(rlr_index *ix, uint64_t want_rows)
 
 // (Re)build the 8-bit nomination copy for rows >= first_row; the error / scale maxima only ever grow between
 // full rebuilds (a delete keeps the old maxima: conservative).
-int32_t sync_q8(rlr_index *ix, uint64_t first_row)
+static int32_t sync_q8(rlr_index *ix, uint64_t first_row)
 {
     if (!ix->q8_enabled)
         return RLR_OK;
@@ -493,7 +268,7 @@ int32_t sync_q8(rlr_index *ix, uint64_t first_row)
 }
 
 // (Re)build the nomination image for every tile that holds a row >= first_row.
-int32_t sync_image(rlr_index *ix, uint64_t first_row)
+static int32_t sync_image(rlr_index *ix, uint64_t first_row)
 {
     RLR_TRY(sync_q8(ix, first_row));
     if (!ix->image_enabled)
@@ -526,7 +301,7 @@ static bool beyond_f16(const float *v, uint32_t n)
 constexpr double kF16MaxSq = 65504.0 * 65504.0;
 
 // Copy host rows in, normalise (optionally) and store them at row `first`.
-int32_t ingest(rlr_index *ix, const float *rows, uint64_t n, uint64_t first, int normalize)
+static int32_t ingest(rlr_index *ix, const float *rows, uint64_t n, uint64_t first, int normalize)
 {
     if (n == 0)
         return RLR_OK;
@@ -575,6 +350,8 @@ int32_t ingest(rlr_index *ix, const float *rows, uint64_t n, uint64_t first, int
 // between two searches of a C loop); polling the word takes ~1 us.  RLR_WAIT: "hybrid" (default) polls, but sleeps
 // through the first two thirds of a wait that took more than 1.5 ms last time -- a 4.4 ms scan does not burn a core --,
 // "spin" always polls from the start, "block" is hipStreamSynchronize.
+namespace {
+
 enum WaitMode { kWaitHybrid = 0, kWaitSpin = 1, kWaitBlock = 2 };
 
 WaitMode wait_mode()
@@ -668,7 +445,8 @@ int32_t wait_polling(Complete &&complete, hipStream_t s, WaitEma *c, uint32_t ke
     return RLR_OK;
 }
 
-// The result block of a fused search -> MMR call (sort_emit.h).
+} // namespace
+
 int32_t wait_block(const volatile uint32_t *h_out, uint32_t k_cap, hipStream_t s, WaitEma *c)
 {
     return wait_polling(
@@ -687,7 +465,6 @@ int32_t wait_block(const volatile uint32_t *h_out, uint32_t k_cap, hipStream_t s
         s, c, 0x40000000u);
 }
 
-// The host reader of a complete block: its n picks into the caller's arrays (lex_out may be null), its status returned.
 uint32_t read_block(const uint32_t *h_out, uint32_t k_cap, uint64_t *rows_out, float *cos_out, float *score_out, float *lex_out,
                     uint32_t *n_out)
 {
@@ -708,8 +485,8 @@ uint32_t read_block(const uint32_t *h_out, uint32_t k_cap, uint64_t *rows_out, f
 // The completion words of nq single-query pipelines (sort_emit.h: count | checksum << 32, written last).  res != null:
 // the k result words of each query are in host memory too and must match the checksum -- the word alone can overtake
 // the results on their way through PCIe.
-int32_t wait_results(const volatile uint64_t *meta, const volatile uint64_t *res, uint32_t nq, uint32_t k, uint32_t limit,
-                     hipStream_t s, WaitEma *c)
+static int32_t wait_results(const volatile uint64_t *meta, const volatile uint64_t *res, uint32_t nq, uint32_t k, uint32_t limit,
+                            hipStream_t s, WaitEma *c)
 {
     uint32_t verified = nq; // queries [verified, nq) are complete (the last one finishes last)
     return wait_polling(
@@ -738,24 +515,18 @@ int32_t wait_results(const volatile uint64_t *meta, const volatile uint64_t *res
 }
 
 // ---- query upload -----------------------------------------------------------------------------------------------
-// The staged queries (pinned host memory, zero padded to the row pitch) -> the context's device buffer.  A few KB: one
-// small kernel on the search's own stream reads them over PCIe itself.  hipMemcpyAsync does the same with the runtime's
-// copy kernel, but the scan behind it then starts 4-5 us after that copy has finished (every other boundary of the
-// pipeline: < 1 us; scratch/step_timeline.py) -- a stream's copies and kernels are ordered through a signal, kernels
-// among themselves by the queue.
-} // namespace
-
-namespace rlr {
 __global__ __launch_bounds__(256) void stage_query_kernel(const float4 *__restrict__ src, float4 *__restrict__ dst, uint32_t n16)
 {
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n16; i += gridDim.x * 256)
         dst[i] = src[i];
 }
-} // namespace rlr
 
-namespace {
-
-hipError_t upload_queries(Ctx *c, const float *h_q, size_t q_bytes, hipStream_t s)
+// The staged queries (pinned host memory, zero padded to the row pitch) -> the context's device buffer.  A few KB: one
+// small kernel on the search's own stream reads them over PCIe itself.  hipMemcpyAsync does the same with the runtime's
+// copy kernel, but the scan behind it then starts 4-5 us after that copy has finished (every other boundary of the
+// pipeline: < 1 us; scratch/step_timeline.py) -- a stream's copies and kernels are ordered through a signal, kernels
+// among themselves by the queue.
+static hipError_t upload_queries(Ctx *c, const float *h_q, size_t q_bytes, hipStream_t s)
 {
     if (q_bytes > (64u << 10) || (q_bytes & 15) || (reinterpret_cast<uintptr_t>(h_q) & 15))
         return hipMemcpyAsync(c->d_query.get(), h_q, q_bytes, hipMemcpyHostToDevice, s);
@@ -766,17 +537,6 @@ hipError_t upload_queries(Ctx *c, const float *h_q, size_t q_bytes, hipStream_t 
 }
 
 // ---- the search pipeline ------------------------------------------------------------
-struct SearchPlan {
-    uint32_t k;        // per query, already clamped to n_rows
-    uint32_t cap;      // candidate capacity
-    float two_eps;
-    float two_eps_img; // band when the nomination scan ran over the binary16 image
-    float scale = 1.0f; // |row|_max * |query|_max when that exceeds 1 (the bands above already carry it)
-    float norm_sum = 2.0f; // |row|_max + |query|_max, rounded up: the binary16 subnormal term of nomination_eps
-    bool f16_ok = true;    // every operand fits binary16 (see plan_bands)
-    bool unordered = false; // the consumer wants the best k as a SET (the hybrid blend re-orders everything anyway)
-};
-
 // The guard bands are error bounds for unit-norm operands; every term of them is linear in |row| * |query|.
 // Rows stored with normalize_on_device = 0 and queries the caller did not normalise widen the band by that
 // product (norms rounded up); unit-norm data -- the reference's invariant, rag_engine.rs:359 / :494 -- gives 1.
@@ -796,7 +556,7 @@ static double sumsq_f64(const float *v, uint32_t n)
 }
 
 // The plan's band factors for this call's queries: p->scale (above), p->norm_sum (nomination_eps) and p->f16_ok.
-void plan_bands(const rlr_index *ix, const float *queries, uint32_t nq, SearchPlan *p)
+static void plan_bands(const rlr_index *ix, const float *queries, uint32_t nq, SearchPlan *p)
 {
     double qmax = 0.0;
     bool f16_ok = !(ix->dtype == RLR_F32 && ix->f16_overflow);
@@ -826,9 +586,6 @@ int32_t ctx_prepare(rlr_index *ix, Ctx *c, uint32_t nq, const SearchPlan &p)
     return RLR_OK;
 }
 
-} // namespace
-
-namespace rlr {
 // Debug assertion (RLR_POISON_ALLOC=1 runs only): every single-query pipeline relies on "the histograms are zero on
 // entry" -- established at context creation and re-established by the previous query's re-score kernel, which is only
 // stream-order-safe.  A second stream, a reordered launch or a skipped clear would break it silently (a wrong threshold,
@@ -1068,314 +825,14 @@ __global__ __launch_bounds__(256) void pack_list_kernel(const float *__restrict_
         st->n_cand = n;
 }
 
-// ---- search -> MMR without a host round trip (rlr_search_diverse): pool_prepare.h ---------------------------
-template <bool FROM_CANDIDATES>
-__global__ __launch_bounds__(1024) void pool_prepare_kernel(const uint64_t *__restrict__ packed, const SelectState *__restrict__ st,
-                                                            PoolArgs pa)
-{
-    __shared__ __attribute__((aligned(16))) char s_pool[kPoolLdsBytes];
-    pool_prepare_body<FROM_CANDIDATES, false>(packed, FROM_CANDIDATES ? st->n_cand : 0u, FROM_CANDIDATES ? st->cap : 0u, pa, s_pool);
-}
-
-
-// ---- hybrid search without host round trips (rlr_search_hybrid) -------------------------------------------
-// The device twin of search_impl's candidate list when lexical (BM25) candidates exist (csrc/engine.cpp;
-// rag_engine.rs:505-561): candidates = the `fetch` best rows by cosine UNITED with the lexical rows,
-// combined = w_e * cos + w_l * (lex / max_lex) (two rounded products, one add; IEEE division), ordered
-// (combined desc, NaN last, row asc), cut to `need`.  Slots [0, fetch) hold the fetched rows, [fetch, fetch + n_lex)
-// the lexical rows that were not fetched; one bitonic sort in LDS orders them.  The same boundary rule as the host:
-// every unfetched row is non-lexical and scores at most combine(cos of the last fetched row, 0); if the need-th
-// candidate does not beat that, info[1] = 2 and the host takes the widening path.
-constexpr uint32_t kHybridSlots = 4096, kHybridLexMax = 2048, kHybridSelMax = 2048, kHybridHash = 4096;
-constexpr uint32_t kHybridFetchMargin = 32; // rows by cosine fetched beyond `need` (rlr_index::hybrid_fetch_full): room for ties
-
-// What the blend needs to know about the lexical pairs, in device memory: written by the host copy (pairs handed in by
-// the caller) or by lex_unpack_kernel (pairs left on the device by a BM25 scoring call).
-struct HybridLexHeader {
-    uint32_t n_lex;
-    float max_lex; // max(lexical scores, f32::EPSILON) (rag_engine.rs:515-519)
-};
-
-// A scoring call's result (pack_result(score, row) keys, in any order) -> rows, scores, header.  Rows outside the index
-// (a lexical index that ran ahead of the embedding matrix) keep their place but are marked: they still count for
-// max_lexical, as in the reference, and never become candidates.  One workgroup (<= kHybridLexMax pairs).
-__device__ inline void lex_unpack_body(const uint64_t *__restrict__ packed, const uint32_t *__restrict__ count, uint32_t limit,
-                                       uint32_t n_rows, uint32_t *__restrict__ lrow, float *__restrict__ lscore,
-                                       HybridLexHeader *__restrict__ hdr)
-{
-    __shared__ uint32_t s_max;
-    if (threadIdx.x == 0)
-        s_max = 0;
-    __syncthreads();
-    if (*count == kLexicalRetry) { // the BM25 selection handed the query back: so does the blend (info[1] = 3)
-        if (threadIdx.x == 0) {
-            hdr->n_lex = kLexicalRetry;
-            hdr->max_lex = 1.0f;
-        }
-        return;
-    }
-    const uint32_t n = min(*count, limit);
-    uint32_t mx = 0; // largest ordered score key: fold(0.0, f32::max) over the scores (:515-519)
-    for (uint32_t i = threadIdx.x; i < n; i += 1024) {
-        float sc;
-        uint32_t row;
-        unpack_result(packed[i], &sc, &row);
-        lrow[i] = row < n_rows ? row : 0xFFFFFFFFu;
-        lscore[i] = sc;
-        mx = max(mx, static_cast<uint32_t>(packed[i] >> 32));
-    }
-    atomicMax(&s_max, mx);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        hdr->n_lex = n;
-        const float m = s_max ? fmaxf(0.0f, key_score(s_max)) : 0.0f; // NaN scores (key 0) are ignored like f32::max does
-        hdr->max_lex = m >= 1.1920929e-07f ? m : 1.1920929e-07f;
-    }
-}
-
-__global__ __launch_bounds__(1024) void lex_unpack_kernel(const uint64_t *__restrict__ packed, const uint32_t *__restrict__ count,
-                                                          uint32_t limit, uint32_t n_rows, uint32_t *__restrict__ lrow,
-                                                          float *__restrict__ lscore, HybridLexHeader *__restrict__ hdr)
-{
-    lex_unpack_body(packed, count, limit, n_rows, lrow, lscore, hdr);
-}
-
-// one query per workgroup (rlr_engine_search_text_batch): query q's keys at packed + q * sel_stride, its count at
-// count + q * count_stride, its pairs at lrow / lscore + q * bound
-__global__ __launch_bounds__(1024) void lex_unpack_batch_kernel(const uint64_t *__restrict__ packed, uint32_t sel_stride,
-                                                                const uint32_t *__restrict__ count, uint32_t count_stride,
-                                                                uint32_t limit, uint32_t n_rows, uint32_t bound,
-                                                                uint32_t *__restrict__ lrow, float *__restrict__ lscore,
-                                                                HybridLexHeader *__restrict__ hdr)
-{
-    const uint32_t q = blockIdx.x;
-    lex_unpack_body(packed + static_cast<size_t>(q) * sel_stride, count + static_cast<size_t>(q) * count_stride, limit, n_rows,
-                    lrow + static_cast<size_t>(q) * bound, lscore + static_cast<size_t>(q) * bound, hdr + q);
-}
-
-__device__ inline void hybrid_pool_body(const uint64_t *__restrict__ packed, uint32_t fetch, uint32_t need, uint32_t n_rows,
-                                        float w_e, float w_l, const uint32_t *__restrict__ lrow, const float *__restrict__ lscore,
-                                        const float *__restrict__ lcos, const HybridLexHeader *__restrict__ hdr,
-                                        float *__restrict__ cand, // 3 x kHybridSlots: combined | cos | lex
-                                        uint32_t *__restrict__ list, float *__restrict__ comb, float *__restrict__ cosv,
-                                        float *__restrict__ lexv, uint32_t *__restrict__ info, uint32_t k_cap,
-                                        uint32_t *__restrict__ h_out) // h_out != null: a search without diversification --
-                                                                      // the pool IS the result, emitted here
-{
-    __shared__ uint64_t s_key[kHybridSlots];   // slot -> (ordered combined score, ~row); 0 = empty
-    __shared__ uint64_t s_sel[kHybridSelMax];  // the keys that can be among the first `need`
-    __shared__ uint32_t s_slot[kHybridSelMax]; // ... and their slots
-    __shared__ uint32_t s_hrow[kHybridHash];   // open-addressing map lexical row + 1 -> its index in the pair list
-    __shared__ uint32_t s_hidx[kHybridHash];
-    __shared__ uint32_t s_flag[kHybridLexMax]; // lexical pair j was reached by the fetch
-    __shared__ uint32_t s_hist[2048];
-    __shared__ uint32_t s_pick[3];
-    __shared__ uint32_t s_got, s_cand, s_nsel, s_emin;
-    __shared__ float s_cneed;
-    const uint32_t t = threadIdx.x;
-    float *cc = cand, *ce = cand + kHybridSlots, *cl = cand + 2 * kHybridSlots;
-    if (hdr->n_lex == kLexicalRetry) { // (uniform) no usable lexical pairs: the host path repeats the BM25 query exactly
-        if (threadIdx.x == 0) {
-            info[0] = 0;
-            info[1] = 3;
-        }
-        if (h_out)
-            hybrid_emit_body(list, comb, cosv, lexv, 0u, 3u, k_cap, h_out);
-        return;
-    }
-    const uint32_t n_lex = min(hdr->n_lex, kHybridLexMax);
-    const float max_lex = hdr->max_lex;
-    if (t == 0) {
-        s_got = 0;
-        s_cand = 0;
-        s_nsel = 0;
-        s_cneed = 0.0f;
-        s_emin = 0xFFFFFFFFu;
-    }
-    for (uint32_t i = t; i < kHybridHash; i += 1024)
-        s_hrow[i] = 0;
-    for (uint32_t j = t; j < n_lex; j += 1024)
-        s_flag[j] = 0;
-    __syncthreads();
-    for (uint32_t j = t; j < n_lex; j += 1024) {
-        const uint32_t row = lrow[j];
-        if (row == 0xFFFFFFFFu)
-            continue;
-        uint32_t h = (row * 2654435761u) >> 20; // 12 bits
-        for (;;) {
-            const uint32_t old = atomicCAS(&s_hrow[h], 0u, row + 1);
-            if (old == 0u) {
-                s_hidx[h] = j;
-                break;
-            }
-            h = (h + 1) & (kHybridHash - 1); // rows are unique: never the same key twice
-        }
-    }
-    __syncthreads();
-    const bool overflow = packed[0] == ~0ull;
-    const uint32_t total = fetch + n_lex;
-    for (uint32_t i = t; i < fetch; i += 1024) {
-        const uint64_t p = overflow ? 0ull : packed[i];
-        uint64_t key = 0;
-        if (p != 0) { // valid entries are a prefix (in no particular order), padding zeros behind
-            const uint32_t row = 0xFFFFFFFFu - static_cast<uint32_t>(p & 0xFFFFFFFFull);
-            const float e = key_score(static_cast<uint32_t>(p >> 32));
-            atomicMin(&s_emin, static_cast<uint32_t>(p >> 32)); // the smallest fetched cosine (NaN orders lowest)
-            float l = 0.0f;
-            uint32_t h = (row * 2654435761u) >> 20;
-            for (;;) {
-                const uint32_t hr = s_hrow[h];
-                if (hr == 0u)
-                    break;
-                if (hr == row + 1) {
-                    const uint32_t j = s_hidx[h];
-                    l = lscore[j] / max_lex;
-                    s_flag[j] = 1;
-                    break;
-                }
-                h = (h + 1) & (kHybridHash - 1);
-            }
-            const float t0 = w_e * e;
-            const float t1 = w_l * l;
-            const float c = t0 + t1;
-            cc[i] = c;
-            ce[i] = e;
-            cl[i] = l;
-            key = (static_cast<uint64_t>(score_key(c == 0.0f ? 0.0f : c)) << 32) | (p & 0xFFFFFFFFull); // -0 ties with +0
-            atomicAdd(&s_got, 1u);
-        }
-        s_key[i] = key;
-    }
-    __syncthreads();
-    for (uint32_t j = t; j < n_lex; j += 1024) {
-        uint64_t key = 0;
-        const uint32_t slot = fetch + j;
-        const uint32_t row = lrow[j];
-        if (row != 0xFFFFFFFFu && !s_flag[j]) { // a lexical row the fetch did not reach
-            const float e = lcos[j];
-            const float l = lscore[j] / max_lex;
-            const float t0 = w_e * e;
-            const float t1 = w_l * l;
-            const float c = t0 + t1;
-            cc[slot] = c;
-            ce[slot] = e;
-            cl[slot] = l;
-            key = (static_cast<uint64_t>(score_key(c == 0.0f ? 0.0f : c)) << 32) | (0xFFFFFFFFu - row);
-            atomicAdd(&s_cand, 1u);
-        }
-        s_key[slot] = key;
-    }
-    __syncthreads();
-    const uint32_t got = s_got, n_cand = got + s_cand, n_pool = min(n_cand, need);
-    // a lower edge that between need and need + 32 of the full keys reach (the passes of the radix select stop as soon as a
-    // bin decides that much), then those are ranked.  [It was the need-th largest 32-bit SCORE in three fixed passes and
-    // everything at or above it: a score shared by thousands of candidates flooded the rank sort and sent the query to the
-    // host path -- the row half of the key splits such a class here.]
-    uint64_t key_lo = 0;
-    if (n_cand > need)
-        key_lo = lds_kth_key64(s_key, total, need, s_hist, s_pick, 1024, /*slack=*/32);
-    for (uint32_t i = t; i < total; i += 1024) {
-        const uint64_t v = s_key[i];
-        if (v != 0 && v >= key_lo) {
-            const uint32_t at = atomicAdd(&s_nsel, 1u);
-            if (at < kHybridSelMax) {
-                s_sel[at] = v;
-                s_slot[at] = i;
-            }
-        }
-    }
-    __syncthreads();
-    const uint32_t n_sel = s_nsel;
-    const bool flood = n_sel > kHybridSelMax; // (cannot happen with the select above; kept as the guard of s_sel's capacity)
-    if (!flood)
-        for (uint32_t i = t; i < n_sel; i += 1024) {
-            const uint64_t mine = s_sel[i];
-            const uint32_t rank = lds_rank_desc(s_sel, n_sel, mine); // keys are unique (the row is part of the key)
-            if (rank < n_pool) {
-                const uint32_t slot = s_slot[i];
-                list[rank] = 0xFFFFFFFFu - static_cast<uint32_t>(mine & 0xFFFFFFFFull);
-                comb[rank] = cc[slot];
-                cosv[rank] = ce[slot];
-                lexv[rank] = cl[slot];
-                if (rank == need - 1)
-                    s_cneed = cc[slot];
-            }
-        }
-    for (uint32_t r = n_pool + t; r < need; r += 1024) { // unused slots: a valid row, never read by the greedy kernel
-        list[r] = 0;
-        comb[r] = 0.0f;
-        cosv[r] = 0.0f;
-        lexv[r] = 0.0f;
-    }
-    __syncthreads();
-    if (t == 0) {
-        uint32_t status = overflow ? 1u : flood ? 2u : 0u;
-        if (!status && got < n_rows && got > 0) {
-            const float t0 = w_e * key_score(s_emin); // the smallest fetched cosine bounds every unfetched (non-lexical) row
-            const float t1 = w_l * 0.0f;
-            const float c_tail = t0 + t1;
-            const bool ok = n_cand >= need && (c_tail != c_tail || s_cneed > c_tail);
-            if (!ok)
-                status = 2u;
-        }
-        info[0] = status ? 0u : n_pool;
-        info[1] = status;
-        s_pick[0] = status;
-    }
-    if (h_out) { // (list .. lexv were stored by this workgroup's own threads in front of the barrier above)
-        __syncthreads();
-        const uint32_t status = s_pick[0];
-        hybrid_emit_body(list, comb, cosv, lexv, status ? 0u : min(n_pool, k_cap), status, k_cap, h_out);
-    }
-}
-
-__global__ __launch_bounds__(1024) void hybrid_pool_kernel(const uint64_t *__restrict__ packed, uint32_t fetch, uint32_t need,
-                                                           uint32_t n_rows, float w_e, float w_l,
-                                                           const uint32_t *__restrict__ lrow, const float *__restrict__ lscore,
-                                                           const float *__restrict__ lcos,
-                                                           const HybridLexHeader *__restrict__ hdr,
-                                                           float *__restrict__ cand, uint32_t *__restrict__ list,
-                                                           float *__restrict__ comb, float *__restrict__ cosv,
-                                                           float *__restrict__ lexv, uint32_t *__restrict__ info,
-                                                           uint32_t k_cap, uint32_t *__restrict__ h_out)
-{
-    hybrid_pool_body(packed, fetch, need, n_rows, w_e, w_l, lrow, lscore, lcos, hdr, cand, list, comb, cosv, lexv, info, k_cap,
-                     h_out);
-}
-
-// hybrid_pool_kernel for many queries (rlr_engine_search_text_batch), one workgroup each: query q's fetched keys at
-// packed + q * fetch, pairs at + q * bound, header q, pool at + q * need; info[2q .. 2q + 1] = (pool size, status), and
-// sizes[q] = the pool size again (the stride-1 array the batched greedy kernel reads)
-__global__ __launch_bounds__(1024) void hybrid_pool_batch_kernel(const uint64_t *__restrict__ packed, uint32_t fetch, uint32_t need,
-                                                                 uint32_t n_rows, float w_e, float w_l, uint32_t bound,
-                                                                 const uint32_t *__restrict__ lrow, const float *__restrict__ lscore,
-                                                                 const float *__restrict__ lcos,
-                                                                 const HybridLexHeader *__restrict__ hdr, float *__restrict__ cand,
-                                                                 uint32_t *__restrict__ list, float *__restrict__ comb,
-                                                                 float *__restrict__ cosv, float *__restrict__ lexv,
-                                                                 uint32_t *__restrict__ info, uint32_t *__restrict__ sizes)
-{
-    const uint32_t q = blockIdx.x;
-    const size_t lo = static_cast<size_t>(q) * bound, po = static_cast<size_t>(q) * need;
-    hybrid_pool_body(packed + static_cast<size_t>(q) * fetch, fetch, need, n_rows, w_e, w_l, lrow + lo, lscore + lo, lcos + lo,
-                     hdr + q, cand + static_cast<size_t>(q) * 3 * kHybridSlots, list + po, comb + po, cosv + po, lexv + po,
-                     info + 2 * q, 0u, nullptr);
-    if (threadIdx.x == 0) // (thread 0 wrote info itself)
-        sizes[q] = info[2 * q];
-}
-
-} // namespace rlr
-
-namespace {
-
 // f32 rows with an up-to-date image and the opt-in set: the nomination scan reads the binary16 image
-bool scan_over_image(const rlr_index *ix, const Ctx *c)
+static bool scan_over_image(const rlr_index *ix, const Ctx *c)
 {
     return ix->image_scan && ix->image_enabled && ix->d_image.get() && ix->dtype == RLR_F32 && !(c && c->no_f16);
 }
 
 // ||q||_2 per staged query, rounded up (only the 8-bit nomination band needs it)
-void stage_query_norms(const rlr_index *ix, Ctx *c, const float *queries, uint32_t nq)
+static void stage_query_norms(const rlr_index *ix, Ctx *c, const float *queries, uint32_t nq)
 {
     if (!ix->q8_enabled)
         return;
@@ -1387,19 +844,19 @@ void stage_query_norms(const rlr_index *ix, Ctx *c, const float *queries, uint32
 }
 
 // f32 rows with an up-to-date 8-bit copy: the nomination scan reads one byte per element
-bool scan_over_q8(const rlr_index *ix)
+static bool scan_over_q8(const rlr_index *ix)
 {
     return ix->q8_enabled && ix->d_q8.get() && !ix->q8_has_inf;
 }
 
 // bytes per element the single-query nomination scan streams (profile accounting)
-uint64_t scan_bytes_per_element(const rlr_index *ix, const Ctx *c)
+static uint64_t scan_bytes_per_element(const rlr_index *ix, const Ctx *c)
 {
     return scan_over_q8(ix) ? 1 : (ix->dtype == RLR_F16 || scan_over_image(ix, c)) ? 2 : 4;
 }
 
 // a scan over the index' rows (query_host stays null: the caller sets it where the query may travel in the arguments)
-ScanArgs scan_args(const rlr_index *ix, const float *query, float *scores, uint32_t *hist)
+static ScanArgs scan_args(const rlr_index *ix, const float *query, float *scores, uint32_t *hist)
 {
     ScanArgs sa;
     sa.rows = ix->d_rows.get();
@@ -1417,7 +874,7 @@ ScanArgs scan_args(const rlr_index *ix, const float *query, float *scores, uint3
 
 // Will this index's single-query scans take their query in the kernel arguments?  (Then nothing is uploaded in front of
 // them: workgroup 0 of the scan leaves the query in the context's device buffer for the kernels behind it.)
-bool scans_take_host_query(const rlr_index *ix, const Ctx *c, const float *h_q)
+static bool scans_take_host_query(const rlr_index *ix, const Ctx *c, const float *h_q)
 {
     if (scan_over_q8(ix) || scan_over_image(ix, c) || ix->n_rows == 0)
         return false;
@@ -1426,7 +883,6 @@ bool scans_take_host_query(const rlr_index *ix, const Ctx *c, const float *h_q)
     return launch_scan_takes_host_query(sa);
 }
 
-// The queries of a call whose pipelines start with enqueue_query_scan: by the scans themselves where they can, else uploaded.
 hipError_t stage_queries_for_scans(const rlr_index *ix, Ctx *c, const float *h_q, size_t q_bytes, hipStream_t s)
 {
     c->h_q_kq = scans_take_host_query(ix, c, h_q) ? h_q : nullptr;
@@ -1434,7 +890,7 @@ hipError_t stage_queries_for_scans(const rlr_index *ix, Ctx *c, const float *h_q
 }
 
 // band for 8-bit-nominated scores of a query of norm q_norm (Cauchy-Schwarz on the stored row error norms)
-float q8_two_eps(const rlr_index *ix, float q_norm, float guard_eps)
+static float q8_two_eps(const rlr_index *ix, float q_norm, float guard_eps)
 {
     const float dflt = rlr_default_guard_eps(ix->dim);
     const float scale = guard_eps > dflt ? guard_eps / dflt : 1.0f;
@@ -1444,15 +900,13 @@ float q8_two_eps(const rlr_index *ix, float q_norm, float guard_eps)
 
 // band for image-nominated scores: the nomination bound for the plan's norms, scaled like the caller scaled guard_eps
 // (eps = the caller's guard_eps, or the default, times p.scale)
-float image_two_eps(const rlr_index *ix, float eps, const SearchPlan &p)
+static float image_two_eps(const rlr_index *ix, float eps, const SearchPlan &p)
 {
     const float dflt = rlr_default_guard_eps(ix->dim) * p.scale;
     const float scale = eps > dflt ? eps / dflt : 1.0f;
     return 2.0f * nomination_eps(ix->dim, ix->dtype, p.scale, p.norm_sum) * scale;
 }
 
-// A call whose operands leave binary16 range (plan_bands) nominates over the f32 rows: count the queries a binary16
-// nomination would have served otherwise -- the batched GEMM (`batch_f16`) or the scan over the image.
 void count_f16_fallbacks(rlr_index *ix, const SearchPlan &p, uint32_t nq, bool batch_f16)
 {
     if (p.f16_ok || !(batch_f16 || scan_over_image(ix, nullptr)))
@@ -1461,7 +915,6 @@ void count_f16_fallbacks(rlr_index *ix, const SearchPlan &p, uint32_t nq, bool b
     ix->prof.n_f16_range_fallbacks += nq;
 }
 
-// after a synchronisation: did the zero-histogram assertion of a poisoned run fire?
 int32_t check_hist_assert(Ctx *c)
 {
     uint32_t *h = static_cast<uint32_t *>(c->h_assert.get());
@@ -1473,10 +926,8 @@ int32_t check_hist_assert(Ctx *c)
     return RLR_OK;
 }
 
-// ---- the frame every search entry point is built on ----------------------------------------------------------------
-// The plan of a call: k clamped to the rows, the band factors of its queries, the guard bands (the one place that knows
-// the rule: the caller's guard_eps, or the default for this dim, times the operands' scale) and the candidate capacity.
-SearchPlan make_plan(const rlr_index *ix, const float *queries, uint32_t nq, uint32_t k, float guard_eps, bool unordered = false)
+// ---- the frame every search entry point is built on (index_internal.h) ----------------------------------------------
+SearchPlan make_plan(const rlr_index *ix, const float *queries, uint32_t nq, uint32_t k, float guard_eps, bool unordered)
 {
     SearchPlan p;
     p.k = static_cast<uint32_t>(std::min<uint64_t>(k, ix->n_rows));
@@ -1489,7 +940,6 @@ SearchPlan make_plan(const rlr_index *ix, const float *queries, uint32_t nq, uin
     return p;
 }
 
-// nq dim-long queries -> h_q, q_pitch floats each, zero padded
 void pad_queries(const rlr_index *ix, const float *queries, uint32_t nq, float *h_q)
 {
     if (ix->q_pitch != ix->dim)
@@ -1498,8 +948,6 @@ void pad_queries(const rlr_index *ix, const float *queries, uint32_t nq, float *
         std::memcpy(h_q + static_cast<size_t>(q) * ix->q_pitch, queries + static_cast<size_t>(q) * ix->dim, ix->dim * sizeof(float));
 }
 
-// The queries of a call that enqueues single-query pipelines, staged in pinned memory (h_q), their norms for the 8-bit
-// band; from here on the context's histograms count as in use until the call has seen every pipeline finish.
 void stage_queries(const rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, float *h_q)
 {
     pad_queries(ix, queries, nq, h_q);
@@ -1515,7 +963,7 @@ struct Staged {
 
 // Reserve and carve that memory, stage the queries (stage_queries) and send them on their way -- for_scans: left to the
 // scans where they can take them (stage_queries_for_scans), else uploaded, with c->h_q_kq null.
-int32_t stage_call(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, size_t res_words, bool for_scans, Staged *out)
+static int32_t stage_call(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, size_t res_words, bool for_scans, Staged *out)
 {
     const size_t q_bytes = static_cast<size_t>(nq) * ix->q_pitch * sizeof(float);
     RLR_TRY(pin_reserve(c, q_bytes + res_words * sizeof(uint64_t)));
@@ -1532,19 +980,14 @@ int32_t stage_call(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, siz
 
 // the completion words a polling wait watches (sort_emit.h): pre-set before the first enqueue, replaced by each
 // pipeline's last store
-void arm_meta(uint64_t *h_meta, uint32_t nq)
+static void arm_meta(uint64_t *h_meta, uint32_t nq)
 {
     if (wait_mode() != kWaitBlock)
         for (uint32_t q = 0; q < nq; ++q)
             h_meta[q] = kMetaPending;
 }
 
-// c->ev[0] .. c->ev[3] of a timed single-query pipeline: scan | select | re-score + sort, added to *t
-struct StageMs {
-    double scan = 0, select = 0, rescore = 0, total = 0;
-};
-
-hipError_t add_stage_ms(Ctx *c, StageMs *t)
+static hipError_t add_stage_ms(Ctx *c, StageMs *t)
 {
     float a = 0, b = 0, d = 0;
     hipError_t e = hipEventElapsedTime(&a, c->ev[0], c->ev[1]);
@@ -1559,7 +1002,6 @@ hipError_t add_stage_ms(Ctx *c, StageMs *t)
     return e;
 }
 
-// profile bookkeeping of an MMR call: c->ev[0] .. c->ev[1] bracket gather + Gram + greedy on the context's stream
 void note_mmr(rlr_index *ix, Ctx *c, uint32_t n_queries)
 {
     float ms = 0;
@@ -1569,13 +1011,8 @@ void note_mmr(rlr_index *ix, Ctx *c, uint32_t n_queries)
     ix->prof.mmr_ms += ms;
 }
 
-// Profile bookkeeping of a search call that has synchronised: nq queries, their candidates and large-candidate retries.
-// timed: the pipelines recorded their events -- read here once, or already summed per query by the caller (*summed);
-// mmr_chain: c->bev[0] .. c->bev[1] bracket the blend / Gram / greedy chain of a fused search -> MMR call.
-// A failed event read leaves its times zero; the counters are kept either way and the failure is the return value (the
-// fused paths, whose results are complete by then, ignore it as they always have).
 int32_t note_search(rlr_index *ix, Ctx *c, uint32_t nq, uint64_t n_candidates, uint64_t n_retries, bool timed,
-                    bool mmr_chain = false, const StageMs *summed = nullptr)
+                    bool mmr_chain, const StageMs *summed)
 {
     StageMs t;
     float mmr_ms = 0;
@@ -1607,179 +1044,7 @@ int32_t note_search(rlr_index *ix, Ctx *c, uint32_t nq, uint64_t n_candidates, u
     return RLR_OK;
 }
 
-// From the first enqueue on, work may be running on `s` (and, for a batched text search, on the stream that records
-// `also`): an exit that has not seen it finish drains it before the lease hands the context back.
-struct StreamDrain {
-    hipStream_t s;
-    hipEvent_t also = nullptr;
-    bool armed = true;
-    ~StreamDrain()
-    {
-        if (also)
-            (void)hipEventSynchronize(also);
-        if (armed)
-            (void)hipStreamSynchronize(s);
-    }
-};
-
-// ---- workspace layouts ---------------------------------------------------------------------------------------------
-// A cursor over a base pointer that hands out regions in declaration order.  Each layout below is ONE list of regions, a
-// member per region initialised by its take(): built over null bases it only measures (what reserve() / pin_reserve() are
-// asked for), built again over the buffers it yields every pointer -- the size and the pointers cannot disagree.  Region
-// order and sizes are what the kernels and copies have always used; what a layout relies on is said next to it.
-struct Carver {
-    char *base;
-    size_t bytes = 0;
-    explicit Carver(void *b) : base(static_cast<char *>(b)) {}
-    template <typename T>
-    T *take(uint64_t count)
-    {
-        T *p = base ? reinterpret_cast<T *>(base + bytes) : nullptr;
-        bytes += static_cast<size_t>(count) * sizeof(T);
-        return p;
-    }
-    uint64_t floats() const { return bytes / sizeof(float); } // c->d_pool is grown in floats; every region is whole words
-};
-
-// The results of an MMR call over m pools of P: order | mmr | n, contiguous on the device and in pinned memory -- one
-// copy of words() words moves them.
-struct MmrResults {
-    uint32_t *order;
-    float *mmr;
-    uint32_t *n;
-    MmrResults(Carver &w, uint64_t m, uint64_t P)
-        : order(w.take<uint32_t>(m * P)), mmr(w.take<float>(m * P)), n(w.take<uint32_t>(m)) {}
-    static uint64_t words(uint64_t m, uint64_t P) { return 2 * m * P + m; }
-};
-
-// Device side (c->d_pool) of an MMR call over m pools of P.
-struct MmrWs {
-    uint64_t m, P, unused_head; // floats in front that no kernel reads (the single-pool call once gathered its pool there)
-    Carver d;
-    float *head = d.take<float>(unused_head), *gram = d.take<float>(m * P * P), *scores = d.take<float>(m * P);
-    MmrResults res{d, m, P};
-    uint32_t *sizes = d.take<uint32_t>(m), *pad = d.take<uint32_t>(8);
-    MmrWs(float *base, uint32_t m_, uint32_t P_, uint64_t head_ = 0) : m(m_), P(P_), unused_head(head_), d(base) {}
-};
-
-// Pinned side (c->h_pin) of a batched MMR call: the row list upload_list stages at the head of the buffer | scores |
-// sizes | the results.  Reserved as a whole BEFORE upload_list enqueues its copy, so that the buffer
-// is never reallocated under a transfer.
-struct MmrStaging {
-    uint64_t m, P;
-    Carver h;
-    char *list = h.take<char>(m * P * 8 + 64);
-    float *scores = h.take<float>(m * P);
-    uint32_t *sizes = h.take<uint32_t>(m + 4);
-    MmrResults res{h, m, P};
-    char *pad = h.take<char>(64);
-    MmrStaging(void *base, uint32_t m_, uint32_t P_) : m(m_), P(P_), h(base) {}
-};
-
-// rlr_search_diverse: device (c->d_pool) and pinned (c->h_pin: the staged query | the result block).
-struct DiverseWs {
-    uint64_t P, dim, q_pitch, k_cap;
-    Carver d, h;
-    float *unused = d.take<float>(P * dim); // (the Gram kernel reads the pool rows in place)
-    float *gram = d.take<float>(P * P), *comb = d.take<float>(P), *cos = d.take<float>(P);
-    uint32_t *order = d.take<uint32_t>(P);
-    float *mmr = d.take<float>(P);
-    uint32_t *nsel = d.take<uint32_t>(1), *info = d.take<uint32_t>(7);
-    float *h_q = h.take<float>(q_pitch);
-    uint32_t *h_out = h.take<uint32_t>(block_words(static_cast<uint32_t>(k_cap)));
-    char *h_pad = h.take<char>(64);
-    DiverseWs(float *d_base, void *h_base, const rlr_index *ix, uint32_t P_, uint32_t k_cap_)
-        : P(P_), dim(ix->dim), q_pitch(ix->q_pitch), k_cap(k_cap_), d(d_base), h(h_base) {}
-};
-
-// A hybrid search: hybrid_begin_impl lays it out, the ticket carries it to hybrid_finish_impl.  Header, lexical rows and
-// scores are adjacent on the device and in pinned memory (h_lex): host-supplied pairs travel in one copy.
-struct HybridWs {
-    uint64_t P, n_lex_bound, q_pitch, k_cap;
-    Carver d, h;
-    float *gram = d.take<float>(P * P), *comb = d.take<float>(P), *cos = d.take<float>(P), *lexv = d.take<float>(P);
-    uint32_t *order = d.take<uint32_t>(P);
-    float *mmr = d.take<float>(P);
-    uint32_t *nsel = d.take<uint32_t>(1), *info = d.take<uint32_t>(7);
-    HybridLexHeader *hdr = d.take<HybridLexHeader>(1);
-    uint32_t *lrow = d.take<uint32_t>(2 * n_lex_bound); // the rows, then their scores: lscore()
-    float *lcos = d.take<float>(n_lex_bound);
-    float *cand = d.take<float>(3ull * kHybridSlots);                                    // blend candidates: combined | cos | lex
-    float *h_q = h.take<float>(q_pitch);
-    uint32_t *h_lex = h.take<uint32_t>(2 + 2 * n_lex_bound), *h_out = h.take<uint32_t>(block_words(static_cast<uint32_t>(k_cap)));
-    char *h_pad = h.take<char>(64);
-    HybridWs(float *d_base, void *h_base, uint32_t q_pitch_, uint32_t P_, uint32_t bound, uint32_t k_cap_)
-        : P(P_), n_lex_bound(bound), q_pitch(q_pitch_), k_cap(k_cap_), d(d_base), h(h_base) {}
-    HybridWs() : HybridWs(nullptr, nullptr, 0, 0, 0, 0) {}
-    // The scores of n_lex pairs sit right behind their rows.  Pairs left on the device by the BM25 kernels use every slot
-    // (n_lex = n_lex_bound: the LexSink of begin and the blend of finish agree by construction); host-supplied pairs
-    // (n_lex <= n_lex_bound) are packed the same way in h_lex, so that header | rows | scores is one copy.
-    float *lscore(uint32_t n_lex) const { return reinterpret_cast<float *>(lrow + n_lex); }
-    static float *h_lscore(uint32_t *h_lex, uint32_t n_lex) { return reinterpret_cast<float *>(h_lex + 2 + n_lex); }
-    static size_t lex_copy_bytes(uint32_t n_lex) { return sizeof(HybridLexHeader) + static_cast<size_t>(n_lex) * 8; }
-};
-
-// The per-query results of search_hybrid_batch (Q x P each, then per-query words): the same list on the device and in
-// pinned memory, moved in one copy of words() words.
-struct HybridBatchRes {
-    uint32_t *list;
-    float *comb, *cos, *lexv;
-    uint32_t *order;
-    float *mmr;
-    uint32_t *nsel, *sizes, *info;
-    HybridBatchRes(Carver &w, uint64_t Q, uint64_t P)
-        : list(w.take<uint32_t>(Q * P)), comb(w.take<float>(Q * P)), cos(w.take<float>(Q * P)), lexv(w.take<float>(Q * P)),
-          order(w.take<uint32_t>(Q * P)), mmr(w.take<float>(Q * P)), nsel(w.take<uint32_t>(Q)), sizes(w.take<uint32_t>(Q)),
-          info(w.take<uint32_t>(2 * Q)) {}
-    static uint64_t words(uint64_t Q, uint64_t P) { return 6 * Q * P + 4 * Q; }
-};
-
-// search_hybrid_batch, device side (c->d_pool)
-struct HybridBatchWs {
-    uint64_t Q, fetch, P, bound, q_pitch, gram_floats;
-    Carver d;
-    uint64_t *packed = d.take<uint64_t>(Q * fetch); // the fetched keys of every query
-    float *q = d.take<float>(Q * q_pitch);
-    uint32_t *lrow = d.take<uint32_t>(Q * bound);
-    float *lscore = d.take<float>(Q * bound), *lcos = d.take<float>(Q * bound);
-    HybridLexHeader *hdr = d.take<HybridLexHeader>(Q);
-    float *cand = d.take<float>(Q * 3 * kHybridSlots);
-    HybridBatchRes res{d, Q, P};
-    float *gram = d.take<float>(gram_floats);
-    HybridBatchWs(float *base, const rlr_index *ix, uint64_t Q_, uint32_t fetch_, uint32_t P_, uint32_t bound_, bool diversify)
-        : Q(Q_), fetch(fetch_), P(P_), bound(bound_), q_pitch(ix->q_pitch), gram_floats(diversify ? Q_ * P_ * P_ : 0), d(base) {}
-};
-
-// search_hybrid_batch, pinned side (c->h_pin): fetched keys | queries | the results.  Laid out only once the cosine batch,
-// which stages through the same buffer, is back.
-struct HybridBatchPin {
-    uint64_t Q, fetch, P, q_pitch;
-    Carver h;
-    uint64_t *packed = h.take<uint64_t>(Q * fetch);
-    float *q = h.take<float>(Q * q_pitch);
-    HybridBatchRes res{h, Q, P};
-    char *pad = h.take<char>(64);
-    HybridBatchPin(void *base, const rlr_index *ix, uint64_t Q_, uint32_t fetch_, uint32_t P_)
-        : Q(Q_), fetch(fetch_), P(P_), q_pitch(ix->q_pitch), h(base) {}
-};
-
-// the greedy kernel writes the picks of a fused search into the pinned block itself
-rlr::MmrEmit mmr_emit(const uint32_t *list, const float *comb, const float *cosv, const float *lexv, const uint32_t *info,
-                      uint32_t k_cap, uint32_t *h_out)
-{
-    return rlr::MmrEmit{list, comb, cosv, lexv, info, k_cap, h_out};
-}
-
-// Enqueue the whole pipeline for query `qi` on the context's stream:
-//   scan (+digit-1 histogram) -> the tail in two launches (tail.hip), or in its split form: digit-2 histogram (bin search
-//   folded in) -> collect (bin search folded in) -> LDS-staged reference-order re-score -> sort + emit; either way the
-//   candidate count (| checksum) goes into *d_meta_q last.
-// The context's histograms are zero on entry: cleared at creation and by every pipeline (tail stage 2 / the re-score kernel).
-// (in two halves, so that a caller with work for ANOTHER stream -- the BM25 kernels of a text search -- can launch it right
-// behind the scan instead of behind every launch of the pipeline: enqueue_query_scan, then enqueue_query_rest)
-// f != nullptr: a document-scoped search -- the masked scan over the master rows, whatever copies the index keeps.
-// master_rows: the scan reads the master rows even where the index keeps a nomination copy (a grouped search: its band is the plan's).
-hipError_t enqueue_query_scan(rlr_index *ix, Ctx *c, uint32_t qi, bool timed, const rlr_filter *f = nullptr, bool master_rows = false)
+hipError_t enqueue_query_scan(rlr_index *ix, Ctx *c, uint32_t qi, bool timed, const rlr_filter *f, bool master_rows)
 {
     hipStream_t s = c->stream;
     hipError_t e;
@@ -1810,11 +1075,8 @@ hipError_t enqueue_query_scan(rlr_index *ix, Ctx *c, uint32_t qi, bool timed, co
     return hipSuccess;
 }
 
-// pool != nullptr (with emit == false): a diversified search -- when the fused tail runs, its finish builds the MMR pool in
-// the same launch and *pool_done = true; otherwise the caller launches pool_prepare_kernel itself.
 hipError_t enqueue_query_rest(rlr_index *ix, Ctx *c, uint32_t qi, const SearchPlan &p, uint64_t *d_out_q, uint64_t *d_meta_q,
-                              bool timed, bool emit = true, const PoolArgs *pool = nullptr, bool *pool_done = nullptr,
-                              bool master_scan = false)
+                              bool timed, bool emit, const PoolArgs *pool, bool *pool_done, bool master_scan)
 {
     if (pool_done)
         *pool_done = false;
@@ -1887,7 +1149,7 @@ hipError_t enqueue_query_rest(rlr_index *ix, Ctx *c, uint32_t qi, const SearchPl
 }
 
 hipError_t enqueue_query(rlr_index *ix, Ctx *c, uint32_t qi, const SearchPlan &p, uint64_t *d_out_q, uint64_t *d_meta_q,
-                         bool timed, bool emit = true, const PoolArgs *pool = nullptr, bool *pool_done = nullptr)
+                         bool timed, bool emit, const PoolArgs *pool, bool *pool_done)
 {
     const hipError_t e = enqueue_query_scan(ix, c, qi, timed);
     return e != hipSuccess ? e : enqueue_query_rest(ix, c, qi, p, d_out_q, d_meta_q, timed, emit, pool, pool_done);
@@ -1895,8 +1157,8 @@ hipError_t enqueue_query(rlr_index *ix, Ctx *c, uint32_t qi, const SearchPlan &p
 
 // The ending of the exact paths (big_query, the filtered list path): the k best of the exactly scored keys in d_packed
 // (cap slots, zero padded) into d_out.
-hipError_t enqueue_order_emit(uint64_t *d_packed, const SelectState *st, uint32_t cap, uint32_t n_valid, uint64_t *d_out,
-                              uint32_t k, hipStream_t s)
+static hipError_t enqueue_order_emit(uint64_t *d_packed, const SelectState *st, uint32_t cap, uint32_t n_valid, uint64_t *d_out,
+                                     uint32_t k, hipStream_t s)
 {
     if (k <= kLdsSortCap) {
         // second level: the exact keys (st->n_cand of them) are selected and sorted by one workgroup
@@ -1912,8 +1174,8 @@ hipError_t enqueue_order_emit(uint64_t *d_packed, const SelectState *st, uint32_
 // Large-candidate path for one query whose band overflowed the LDS sort (massive ties /
 // duplicated chunks, or k > kLdsSortCap).  Re-uses the scores still resident from the scan
 // only when the query was the last one scanned; otherwise re-scans.
-int32_t big_query(rlr_index *ix, Ctx *c, uint32_t qi, const SearchPlan &p, uint32_t n_cand, bool rescan,
-                  uint64_t *d_out_q)
+static int32_t big_query(rlr_index *ix, Ctx *c, uint32_t qi, const SearchPlan &p, uint32_t n_cand, bool rescan,
+                         uint64_t *d_out_q)
 {
     hipStream_t s = c->stream;
     const uint32_t n = static_cast<uint32_t>(ix->n_rows);
@@ -1954,14 +1216,14 @@ constexpr uint32_t kBatchMaxQueries = 1024; // queries per batched pipeline run 
 // queries are a group of concurrent single-query calls (rlr_index_set_coalescing) -- those also share one pass over
 // binary16 rows of 256 / 512 / 768 / 1024 elements (scan_multi_h_kernel); explicit multi-query calls over binary16
 // rows keep the matrix-core pipeline.
-bool batch_multi_shape(const rlr_index *ix, uint32_t nq, bool coalesced = false)
+static bool batch_multi_shape(const rlr_index *ix, uint32_t nq, bool coalesced = false)
 {
     if (coalesced && ix->dtype == RLR_F16)
         return nq <= 8 && ix->pitch16 % 32 == 0 && ix->pitch16 / 32 <= 4 && ix->pitch16 * 8 == ix->dim;
     return nq <= 8 && ix->dtype == RLR_F32 && ix->pitch16 % 64 == 0 && ix->pitch16 / 64 <= 4 && ix->pitch16 * 4 == ix->dim;
 }
 
-bool batch_eligible(const rlr_index *ix, uint32_t nq, uint32_t k, bool f16_ok = true, bool coalesced = false)
+static bool batch_eligible(const rlr_index *ix, uint32_t nq, uint32_t k, bool f16_ok = true, bool coalesced = false)
 {
     if (nq < 2 || ix->dim % 128 != 0 || ix->n_rows < 4096 || k * 8 > batch_finish_capacity())
         return false;
@@ -1992,7 +1254,7 @@ bool batch_eligible(const rlr_index *ix, uint32_t nq, uint32_t k, bool f16_ok = 
 // The per-query workspace of a batched run of nq queries (select states, histograms, status words, fin_cap candidates and
 // s_stride sample scores each), the states armed for rank `rank` of n scored rows, histograms and status words cleared on
 // the context's stream.  Shared by run_batched and the filtered shared pass.
-int32_t batch_arm(Ctx *c, uint32_t nq, uint32_t fin_cap, uint64_t s_stride, uint32_t rank, uint64_t n)
+static int32_t batch_arm(Ctx *c, uint32_t nq, uint32_t fin_cap, uint64_t s_stride, uint32_t rank, uint64_t n)
 {
     hipStream_t s = c->stream;
     // (the status words of h_batch start behind d_bstate.capacity() states: all five or none)
@@ -2016,8 +1278,8 @@ int32_t batch_arm(Ctx *c, uint32_t nq, uint32_t fin_cap, uint64_t s_stride, uint
 // select and the nomination left, then ONE copy of the status words (and of the results, when h_res_out is given) and one
 // synchronisation.  h_status[q] != 0: the finish handed query q back.  n_cand_out (optional): the candidates the select
 // collected per query (the rows at or above its floor), fetched with the same synchronisation.
-int32_t batch_finish(rlr_index *ix, Ctx *c, const float *dq, uint32_t nq, uint32_t k, float two_eps, uint64_t *d_out,
-                     std::vector<uint32_t> &h_status, uint64_t *h_res_out, std::vector<uint32_t> *n_cand_out = nullptr)
+static int32_t batch_finish(rlr_index *ix, Ctx *c, const float *dq, uint32_t nq, uint32_t k, float two_eps, uint64_t *d_out,
+                            std::vector<uint32_t> &h_status, uint64_t *h_res_out, std::vector<uint32_t> *n_cand_out = nullptr)
 {
     hipStream_t s = c->stream;
     uint32_t *h_stat = reinterpret_cast<uint32_t *>(static_cast<SelectState *>(c->h_batch.get()) + c->d_bstate.capacity());
@@ -2043,7 +1305,7 @@ int32_t batch_finish(rlr_index *ix, Ctx *c, const float *dq, uint32_t nq, uint32
 // Runs queries [q0, q0+nq) (already staged in c->d_query) through the GEMM nomination pipeline
 // and leaves k packed results per query in d_out; h_status[q] != 0 marks queries the caller must
 // re-run through the single-query pipeline.
-int32_t run_batched(rlr_index *ix, Ctx *c, uint32_t q0, uint32_t nq, const SearchPlan &p, uint64_t *d_out,
+static int32_t run_batched(rlr_index *ix, Ctx *c, uint32_t q0, uint32_t nq, const SearchPlan &p, uint64_t *d_out,
                     std::vector<uint32_t> &h_status, uint64_t *h_res_out, bool coalesced = false)
 {
     hipStream_t s = c->stream;
@@ -2154,15 +1416,9 @@ int32_t run_batched(rlr_index *ix, Ctx *c, uint32_t q0, uint32_t nq, const Searc
     return RLR_OK;
 }
 
-// Runs nq queries.  Packed results (k per query) end up in d_out_user when given (device-resident
-// variant), else in the context buffer AND in pinned host memory (*h_results, nq x k u64) -- one
-// H2D (queries), one D2H (results + per-query candidate counts) and one stream synchronisation
-// per call on the common path.
-// coalesced: the queries are a group of concurrent single-query calls (batch_multi_shape); *n_handed_back (optional):
-// how many of them the batched pipeline handed back to the single-query pipeline.
 int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uint32_t k_req, float guard_eps,
-                   uint64_t *d_out_user, SearchPlan *plan_out, const uint64_t **h_results, bool coalesced = false,
-                   uint32_t *n_handed_back = nullptr)
+                   uint64_t *d_out_user, SearchPlan *plan_out, const uint64_t **h_results, bool coalesced,
+                   uint32_t *n_handed_back)
 {
     if (n_handed_back)
         *n_handed_back = 0;
@@ -2274,7 +1530,6 @@ int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uin
     return note_search(ix, c, nq, n_cand_total, n_retry, timed, /*mmr_chain=*/false, nq > 1 ? &per_query_ms : nullptr);
 }
 
-// c->d_list / c->d_vals for n rows (a power of two, at least 1024)
 int32_t reserve_list(Ctx *c, uint32_t n)
 {
     const uint32_t cap = std::max<uint32_t>(next_pow2(n), 1024);
@@ -2282,7 +1537,7 @@ int32_t reserve_list(Ctx *c, uint32_t n)
     return RLR_OK;
 }
 
-int32_t upload_list(rlr_index *ix, Ctx *c, const uint64_t *rows, uint32_t n, uint64_t bound = ~0ull)
+int32_t upload_list(rlr_index *ix, Ctx *c, const uint64_t *rows, uint32_t n, uint64_t bound)
 {
     if (bound == ~0ull)
         bound = ix->n_rows;
@@ -2301,7 +1556,7 @@ int32_t upload_list(rlr_index *ix, Ctx *c, const uint64_t *rows, uint32_t n, uin
 
 // unpack_result of `take` packed results into a caller's rows / cosines, written without branches so that the loop
 // vectorises (a batch of 1024 x 308 results is 315 k of them)
-void unpack_results(const uint64_t *__restrict__ src, uint32_t take, uint64_t *__restrict__ ro, float *cos_out)
+static void unpack_results(const uint64_t *__restrict__ src, uint32_t take, uint64_t *__restrict__ ro, float *cos_out)
 {
     uint32_t *__restrict__ co = reinterpret_cast<uint32_t *>(cos_out);
     for (uint32_t i = 0; i < take; ++i) {
@@ -2315,7 +1570,7 @@ void unpack_results(const uint64_t *__restrict__ src, uint32_t take, uint64_t *_
 }
 
 // rlr_search_topk on a context of its own (n_rows > 0, k > 0)
-int32_t search_topk_host(rlr_index *ix, const float *queries, uint32_t n_queries, uint32_t k, float guard_eps, uint64_t *rows_out,
+static int32_t search_topk_host(rlr_index *ix, const float *queries, uint32_t n_queries, uint32_t k, float guard_eps, uint64_t *rows_out,
                          float *cos_out, uint32_t *n_out)
 {
     CtxLease lease(ix);
@@ -2332,6 +1587,8 @@ int32_t search_topk_host(rlr_index *ix, const float *queries, uint32_t n_queries
     }
     return RLR_OK;
 }
+
+namespace {
 
 // ---- filtered search (rlr_search_topk_filtered) ---------------------------------------------------------------------
 // Fewer allowed rows than this: the list path (reference-order scores of every allowed row, then a sort or a select).
@@ -2390,6 +1647,18 @@ bool filter_holds(const rlr_filter *f, uint32_t row)
     return row < f->index_rows && ((f->h_mask[row >> 6] >> (row & 63)) & 1ull);
 }
 
+// A masked row must never be returned.  Its sentinel keeps it out of every collect whose threshold key is above 0; a
+// threshold of 0 (k reaches allowed rows whose own nomination score is NaN) lets it in, and re-scored from its real values
+// it can rank anywhere.  So every returned row is tested against the host copy of the mask -- if none is masked the result
+// is the right one -- and a caller that finds one takes its exact path.  keys: n packed results; f == nullptr: no filter.
+bool masked_row_among(const rlr_filter *f, const uint64_t *keys, uint32_t n)
+{
+    for (uint32_t i = 0; f && i < n; ++i)
+        if (!filter_holds(f, 0xFFFFFFFFu - static_cast<uint32_t>(keys[i])))
+            return true;
+    return false;
+}
+
 // One query over the rows of `f` (n_allowed > 0, k > 0).  Filtered calls scan the master rows and never use the
 // nomination copies, the matrix-core batch or the coalescer.
 int32_t filtered_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *query, uint32_t k, float guard_eps,
@@ -2421,14 +1690,7 @@ int32_t filtered_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *
             n_retry++;
             RLR_TRY(big_query(ix, c, 0, p, static_cast<uint32_t>(n_cand), /*rescan=*/false, h_res));
         }
-        // A masked row must never be returned.  Its sentinel keeps it out of every collect whose threshold key is above
-        // 0; a threshold of 0 (k reaches allowed rows whose own nomination score is NaN) lets it in, and re-scored from
-        // its real values it can rank anywhere.  So every returned row is tested against the host copy of the mask --
-        // if none is masked the result is the right one -- and a failed test takes the exact path.
-        bool leaked = false;
-        for (uint32_t i = 0; i < p.k && !leaked; ++i)
-            leaked = !filter_holds(f, 0xFFFFFFFFu - static_cast<uint32_t>(h_res[i]));
-        if (leaked) {
+        if (masked_row_among(f, h_res, p.k)) { // a masked row came back: the exact path
             n_retry++;
             RLR_TRY(filtered_exact(ix, c, f, p, h_res));
         }
@@ -2601,9 +1863,8 @@ int32_t grouped_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *q
             const uint32_t n_valid = static_cast<uint32_t>(info);
             if (n_res < p.k && n_valid < n_allowed)
                 form = 2; // allowed rows with NaN nominations were left out and the answer is short
-            for (uint32_t i = 0; f && i < n_res && form == 0; ++i)
-                if (!filter_holds(f, 0xFFFFFFFFu - static_cast<uint32_t>(h_res[i])))
-                    form = 2; // a masked row came back (the hazard filtered_query documents)
+            if (form == 0 && masked_row_among(f, h_res, n_res))
+                form = 2; // a masked row came back
         }
     }
     if (form != 0) {
@@ -2733,9 +1994,8 @@ int32_t range_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *que
         } else {
             n_res = cap ? n_hits : 0;
         }
-        for (uint32_t i = 0; f && i < n_res && form == 0; ++i)
-            if (!filter_holds(f, 0xFFFFFFFFu - static_cast<uint32_t>(res[i])))
-                form = 2; // a masked row came back (the hazard filtered_query documents)
+        if (form == 0 && masked_row_among(f, res, n_res))
+            form = 2; // a masked row came back
     }
     c->hist_dirty = false;
     {
@@ -2909,9 +2169,8 @@ int32_t range_batch_chunk(rlr_index *ix, Ctx *c, const rlr_filter *f, RangeShare
         const uint64_t *r = h_res + static_cast<size_t>(q) * words;
         const uint32_t n_hits = static_cast<uint32_t>(r[out_keys]), n_valid = static_cast<uint32_t>(r[out_keys] >> 32);
         const uint32_t n_res_q = cap ? std::min(n_hits, out_keys) : 0;
-        bool back = r[out_keys + 1] != kRangeBatchDecided || (path == kRangeShareScan && n_valid < n_allowed);
-        for (uint32_t i = 0; f && i < n_res_q && !back; ++i)
-            back = !filter_holds(f, 0xFFFFFFFFu - static_cast<uint32_t>(r[i])); // (the hazard filtered_query documents)
+        const bool back = r[out_keys + 1] != kRangeBatchDecided || (path == kRangeShareScan && n_valid < n_allowed) ||
+                          masked_row_among(f, r, n_res_q);
         if (back) {
             forms[q] = 2;
             redo.push_back(q);
@@ -3046,10 +2305,7 @@ int32_t masked_batch(rlr_index *ix, Ctx *c, const rlr_filter *const *fs, bool on
     std::vector<uint32_t> redo;
     uint64_t n_cand_total = 0; // of the queries served here, as filtered_query reports its own
     for (uint32_t q = 0; q < m; ++q) {
-        bool back = status[q] != 0;
-        for (uint32_t i = 0; i < p.k && !back; ++i)
-            back = !filter_holds(fs[q], 0xFFFFFFFFu - static_cast<uint32_t>(h_res[static_cast<size_t>(q) * p.k + i]));
-        if (back) {
+        if (status[q] != 0 || masked_row_among(fs[q], h_res + static_cast<size_t>(q) * p.k, p.k)) {
             redo.push_back(q);
             continue;
         }
@@ -3229,6 +2485,20 @@ int32_t docs_mark(rlr_index *ix, hipStream_t s, const std::vector<uint32_t> &set
     return RLR_OK;
 }
 
+// One form read-out (rlr_index_*_forms): the queries each form served since the last reset.
+int32_t read_forms(rlr_index *ix, uint64_t (rlr_index::*forms)[4], uint64_t counts[4], int32_t reset)
+{
+    RLR_TRY(check_handle(ix));
+    std::lock_guard<std::mutex> lk(ix->mu);
+    for (int i = 0; i < 4; ++i) {
+        if (counts)
+            counts[i] = (ix->*forms)[i];
+        if (reset)
+            (ix->*forms)[i] = 0;
+    }
+    return RLR_OK;
+}
+
 // one bounce-buffer step of a deletion on the document column: rows keep[0 .. m) move to [dst_first, dst_first + m)
 hipError_t compact_docs_step(rlr_index *ix, const uint32_t *d_keep, uint64_t m, uint64_t dst_first, uint32_t *d_bounce, hipStream_t s)
 {
@@ -3401,9 +2671,8 @@ int32_t coalesced_search(rlr_index *ix, const float *query, uint32_t k, float gu
     return st;
 }
 
-// The fused one-enqueue calls (rlr_search_diverse / rlr_search_hybrid / search_hybrid_begin) cannot share their scan:
-// while coalescing is on and a group of two with this k would qualify, they hand the query back (*fallback = 1) so that
-// the caller's two-call path reaches the coalescer through rlr_search_topk.
+} // namespace
+
 bool coalesce_hands_back(rlr_index *ix, uint32_t k)
 {
     if (ix->co_max.load(std::memory_order_relaxed) < 2 || !coalesce_eligible(ix, k))
@@ -3413,7 +2682,7 @@ bool coalesce_hands_back(rlr_index *ix, uint32_t k)
     return true;
 }
 
-} // namespace
+} // namespace rlr
 
 // =====================================================================================
 // C ABI
@@ -4026,15 +3295,7 @@ int32_t rlr_search_topk_grouped(rlr_index *ix, const rlr_filter *f, const float 
 
 int32_t rlr_index_grouped_forms(rlr_index *ix, uint64_t counts[4], int32_t reset)
 {
-    RLR_TRY(check_handle(ix));
-    std::lock_guard<std::mutex> lk(ix->mu);
-    for (int i = 0; i < 4; ++i) {
-        if (counts)
-            counts[i] = ix->grouped_forms[i];
-        if (reset)
-            ix->grouped_forms[i] = 0;
-    }
-    return RLR_OK;
+    return read_forms(ix, &rlr_index::grouped_forms, counts, reset);
 }
 
 int32_t rlr_search_range(rlr_index *ix, const rlr_filter *f, const float *queries, uint32_t n_queries, const float *tau, uint32_t cap,
@@ -4071,15 +3332,7 @@ int32_t rlr_search_range(rlr_index *ix, const rlr_filter *f, const float *querie
 
 int32_t rlr_index_range_forms(rlr_index *ix, uint64_t counts[4], int32_t reset)
 {
-    RLR_TRY(check_handle(ix));
-    std::lock_guard<std::mutex> lk(ix->mu);
-    for (int i = 0; i < 4; ++i) {
-        if (counts)
-            counts[i] = ix->range_forms[i];
-        if (reset)
-            ix->range_forms[i] = 0;
-    }
-    return RLR_OK;
+    return read_forms(ix, &rlr_index::range_forms, counts, reset);
 }
 
 int32_t rlr_search_range_batch(rlr_index *ix, const rlr_filter *f, const float *queries, uint32_t n_queries, const float *tau,
@@ -4158,15 +3411,7 @@ int32_t rlr_index_set_range_sharing(rlr_index *ix, int32_t mode)
 
 int32_t rlr_index_range_batch_forms(rlr_index *ix, uint64_t counts[4], int32_t reset)
 {
-    RLR_TRY(check_handle(ix));
-    std::lock_guard<std::mutex> lk(ix->mu);
-    for (int i = 0; i < 4; ++i) {
-        if (counts)
-            counts[i] = ix->range_batch_forms[i];
-        if (reset)
-            ix->range_batch_forms[i] = 0;
-    }
-    return RLR_OK;
+    return read_forms(ix, &rlr_index::range_batch_forms, counts, reset);
 }
 
 int32_t rlr_search_topk_scoped(rlr_index *ix, const rlr_filter *const *filters, const float *queries, uint32_t n_queries,
@@ -4485,467 +3730,6 @@ int32_t rlr_fetch_rows(rlr_index *ix, const uint64_t *rows, uint32_t n, float *o
     return RLR_OK;
 }
 
-// one pool of up to 4096 candidates; d_matrix != null: pool_rows are slots of that staged matrix (see mmr_batch_impl)
-static int32_t mmr_single_impl(rlr_index *ix, const uint64_t *pool_rows, const float *pool_scores, uint32_t P, uint32_t k,
-                               float lambda, uint32_t *order_out, float *mmr_out, uint32_t *n_out, const void *d_matrix,
-                               uint64_t n_matrix)
-{
-    RLR_TRY(check_handle(ix));
-    if (!n_out)
-        return set_error(RLR_E_INVALID, "n_out is null");
-    *n_out = 0;
-    if (P == 0)
-        return RLR_OK; // `if candidates.is_empty() { return vec![] }`
-    if (!pool_rows || !pool_scores || !order_out)
-        return set_error(RLR_E_INVALID, "null argument");
-    if (P > 4096)
-        return set_error(RLR_E_INVALID, "pool of %u exceeds the supported 4096 candidates", P);
-    RLR_TRY(use_device(ix));
-    CtxLease lease(ix);
-    RLR_TRY(ctx_acquire(ix, &lease.c));
-    Ctx *c = lease.c;
-    hipStream_t s = c->stream;
-    RLR_TRY(upload_list(ix, c, pool_rows, P, d_matrix ? n_matrix : ~0ull));
-    const uint64_t head = static_cast<uint64_t>(P) * ix->dim;
-    RLR_HIP(c->d_pool.reserve(MmrWs(nullptr, 1, P, head).d.floats()));
-    const MmrWs ws(c->d_pool.get(), 1, P, head);
-    const bool timed = ix->profiling;
-    RLR_HIP(hipMemcpyAsync(ws.scores, pool_scores, static_cast<size_t>(P) * sizeof(float), hipMemcpyHostToDevice, s));
-    if (timed) RLR_HIP(hipEventRecord(c->ev[0], s));
-    RLR_HIP(launch_gram_rows(d_matrix ? d_matrix : ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, c->d_list.get(), P, ws.gram, 1, s));
-    RLR_HIP(launch_mmr_greedy(ws.gram, ws.scores, P, k, lambda, ws.res.order, ws.res.mmr, ws.res.n, nullptr, 1, s));
-    if (timed) RLR_HIP(hipEventRecord(c->ev[1], s));
-    RLR_TRY(pin_reserve(c, (MmrResults::words(1, P) + 3) * 4));
-    Carver pin(c->h_pin.get()); // (upload_list's copy out of it is ahead on the stream)
-    const MmrResults h(pin, 1, P);
-    RLR_HIP(hipMemcpyAsync(h.order, ws.res.order, MmrResults::words(1, P) * 4, hipMemcpyDeviceToHost, s));
-    RLR_HIP(hipStreamSynchronize(s));
-    if (timed)
-        note_mmr(ix, c, 1);
-    const uint32_t n_sel = h.n[0];
-    for (uint32_t i = 0; i < n_sel; ++i) {
-        order_out[i] = h.order[i];
-        if (mmr_out)
-            mmr_out[i] = h.mmr[i];
-    }
-    *n_out = n_sel;
-    return RLR_OK;
-}
-
-int32_t rlr_mmr_select(rlr_index *ix, const uint64_t *pool_rows, const float *pool_scores, uint32_t P, uint32_t k,
-                       float lambda, uint32_t *order_out, float *mmr_out, uint32_t *n_out)
-{
-    return mmr_single_impl(ix, pool_rows, pool_scores, P, k, lambda, order_out, mmr_out, n_out, nullptr, 0);
-}
-
-int32_t rlr_search_diverse(rlr_index *ix, const float *query, uint32_t pool, uint32_t k, float lambda, float w_embedding,
-                           float w_lexical, float guard_eps, uint64_t *rows_out, float *cos_out, float *score_out,
-                           uint32_t *n_out, int32_t *fallback)
-{
-    RLR_TRY(check_handle(ix));
-    if (!n_out || !fallback)
-        return set_error(RLR_E_INVALID, "n_out / fallback is null");
-    *n_out = 0;
-    *fallback = 0;
-    if (ix->n_rows == 0 || pool == 0)
-        return RLR_OK;
-    if (!query || !rows_out || !cos_out || !score_out)
-        return set_error(RLR_E_INVALID, "null argument");
-    const uint32_t n = static_cast<uint32_t>(ix->n_rows);
-    const uint32_t need = std::min<uint32_t>(n, pool);
-    const uint32_t fetch = static_cast<uint32_t>(std::min<uint64_t>(n, static_cast<uint64_t>(need) + 8));
-    if (need > rlr::kPoolMax || !(w_embedding > 0.0f) || !(w_lexical >= 0.0f) || !std::isfinite(w_lexical)) {
-        *fallback = 1; // outside what the fused kernels cover: the caller's two-call path handles it
-        return RLR_OK;
-    }
-    if (coalesce_hands_back(ix, need)) {
-        *fallback = 1; // the two-call path's rlr_search_topk shares a pass with concurrent callers
-        return RLR_OK;
-    }
-    RLR_TRY(use_device(ix));
-    CtxLease lease(ix);
-    RLR_TRY(ctx_acquire(ix, &lease.c));
-    Ctx *c = lease.c;
-    hipStream_t s = c->stream;
-    const SearchPlan p = make_plan(ix, query, 1, fetch, guard_eps);
-    RLR_TRY(ctx_prepare(ix, c, 1, p));
-    count_f16_fallbacks(ix, p, 1, false);
-    const uint32_t P = need;
-    const uint32_t k_cap = rlr::result_k_cap(k, P, true);
-    const DiverseWs sizes(nullptr, nullptr, ix, P, k_cap);
-    RLR_HIP(c->d_pool.reserve(sizes.d.floats()));
-    RLR_TRY(reserve_list(c, P));
-    RLR_TRY(pin_reserve(c, sizes.h.bytes));
-    const DiverseWs ws(c->d_pool.get(), c->h_pin.get(), ix, P, k_cap);
-    uint32_t *h_out = ws.h_out;
-    h_out[block_done(k_cap)] = kBlockPending; // (the greedy kernel's last store replaces it: what the wait below polls)
-    stage_queries(ix, c, query, 1, ws.h_q);
-    const bool timed = ix->profiling;
-    RLR_HIP(stage_queries_for_scans(ix, c, ws.h_q, static_cast<size_t>(ix->q_pitch) * sizeof(float), s));
-    uint64_t *d_meta = c->d_out.get() + fetch;
-    const bool from_candidates = fetch <= 512; // (the band of a larger fetch rarely fits 1024)
-    const PoolArgs pa{fetch, need, n, w_embedding, w_lexical, c->d_list.get(), ws.comb, ws.cos, ws.info};
-    bool pool_done = false; // (the fused tail's finish builds the pool itself: one launch and ~13 us of config 2's chain less)
-    RLR_HIP(enqueue_query(ix, c, 0, p, c->d_out.get(), d_meta, timed, /*emit=*/!from_candidates, from_candidates ? &pa : nullptr,
-                          &pool_done));
-    if (timed) RLR_HIP(hipEventRecord(c->bev[0], s));
-    if (!pool_done) {
-        if (from_candidates)
-            hipLaunchKernelGGL(rlr::pool_prepare_kernel<true>, dim3(1), dim3(1024), 0, s, c->d_packed.get(), c->d_state.get(), pa);
-        else
-            hipLaunchKernelGGL(rlr::pool_prepare_kernel<false>, dim3(1), dim3(1024), 0, s, c->d_out.get(), c->d_state.get(), pa);
-        RLR_HIP(hipGetLastError());
-    }
-    RLR_HIP(launch_gram_rows(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, c->d_list.get(), P, ws.gram, 1, s));
-    const rlr::MmrEmit emit = mmr_emit(c->d_list.get(), ws.comb, ws.cos, nullptr, ws.info, k_cap, h_out);
-    RLR_HIP(launch_mmr_greedy(ws.gram, ws.comb, P, k, lambda, ws.order, ws.mmr, ws.nsel, ws.info, 1, s, &emit));
-    if (timed) RLR_HIP(hipEventRecord(c->bev[1], s));
-    if (timed)
-        RLR_HIP(hipStreamSynchronize(s)); // (the events are read below)
-    else
-        RLR_TRY(wait_block(h_out, k_cap, s, &c->wait_ema));
-    RLR_TRY(check_hist_assert(c));
-    c->hist_dirty = false;
-    (void)note_search(ix, c, 1, 0, 0, timed, /*mmr_chain=*/true);
-    *fallback = static_cast<int32_t>(read_block(h_out, k_cap, rows_out, cos_out, score_out, nullptr, n_out));
-    return RLR_OK;
-}
-
-// where the lexical pairs of a hybrid search come from
-struct HybridLexSrc {
-    const uint64_t *h_rows = nullptr; // host pairs: ascending unique rows inside the index ...
-    const float *h_scores = nullptr;
-    uint32_t n_host = 0;
-    float max_lex = 1.1920929e-07f;
-    const rlr::LexPending *dev = nullptr; // ... or a BM25 call's result still on the device (null + n_host 0: no pairs)
-};
-
-} // extern "C"
-
-namespace rlr {
-
-// A hybrid search between its two enqueues: the scan / select / re-score / sort part is on the stream (it does not
-// depend on the lexical pairs, only on an upper bound of their number), the blend and everything behind it follows in
-// search_hybrid_finish.  In between the caller enqueues the BM25 kernels on their own stream: the device runs them
-// beside the scan, and the host's launch calls for both overlap the scan instead of preceding it.
-struct HybridTicket {
-    rlr_index *ix;
-    CtxLease lease;
-    uint32_t n, need, fetch, k, k_cap;
-    float lambda, w_e, w_l;
-    int32_t diversify;
-    bool timed;
-    // begin hands the lexical side of it to the BM25 kernels (LexSink), finish blends from the same object.  It points into
-    // c->d_pool and c->h_pin: the ticket holds the context's lease, and nothing may reserve() / pin_reserve() on this context
-    // between begin and finish.
-    HybridWs ws;
-    explicit HybridTicket(rlr_index *i) : ix(i), lease(i) {}
-};
-
-static int32_t hybrid_begin_impl(rlr_index *ix, const float *query, uint32_t need_in, uint32_t k, float lambda, int32_t diversify,
-                                 float w_embedding, float w_lexical, uint32_t n_lex_bound, float guard_eps, HybridTicket **out,
-                                 int32_t *fallback, int32_t (*behind_scan)(void *, const LexSink *) = nullptr,
-                                 void *behind_scan_arg = nullptr)
-{
-    *out = nullptr;
-    *fallback = 0;
-    RLR_TRY(check_handle(ix));
-    if (!query)
-        return set_error(RLR_E_INVALID, "null argument");
-    const uint32_t n = static_cast<uint32_t>(ix->n_rows);
-    const uint32_t need = std::min<uint32_t>(n, need_in);
-    const uint64_t fetch_full = std::min<uint64_t>(n, static_cast<uint64_t>(need) + n_lex_bound + 8);
-    const uint64_t fetch64 = ix->hybrid_fetch_full ? fetch_full : std::min<uint64_t>(fetch_full, static_cast<uint64_t>(need) + kHybridFetchMargin);
-    if (n == 0 || need == 0 || need > kPoolMax || n_lex_bound > kHybridLexMax || fetch_full + n_lex_bound > kHybridSlots ||
-        !(w_embedding > 0.0f) || !std::isfinite(w_embedding) || !std::isfinite(w_lexical)) {
-        *fallback = 1; // outside what the fused kernels cover: the caller's host path handles it
-        return RLR_OK;
-    }
-    if (coalesce_hands_back(ix, need)) {
-        *fallback = 1; // the host path's rlr_search_topk shares a pass with concurrent callers
-        return RLR_OK;
-    }
-    const uint32_t fetch = static_cast<uint32_t>(fetch64);
-    RLR_TRY(use_device(ix));
-    std::unique_ptr<HybridTicket> t(new (std::nothrow) HybridTicket(ix));
-    if (!t)
-        return set_error(RLR_E_OOM, "host allocation failed");
-    RLR_TRY(ctx_acquire(ix, &t->lease.c));
-    Ctx *c = t->lease.c;
-    hipStream_t s = c->stream;
-    // unordered: the blend orders fetched and lexical rows together -- it needs the fetched SET and its minimum
-    const SearchPlan p = make_plan(ix, query, 1, fetch, guard_eps, /*unordered=*/true);
-    RLR_TRY(ctx_prepare(ix, c, 1, p));
-    count_f16_fallbacks(ix, p, 1, false);
-    const uint32_t P = need;
-    const uint32_t k_cap = result_k_cap(k, P, diversify != 0);
-    const HybridWs sizes(nullptr, nullptr, ix->q_pitch, P, n_lex_bound, k_cap);
-    RLR_HIP(c->d_pool.reserve(sizes.d.floats()));
-    RLR_TRY(reserve_list(c, P));
-    RLR_TRY(pin_reserve(c, sizes.h.bytes));
-    t->ws = HybridWs(c->d_pool.get(), c->h_pin.get(), ix->q_pitch, P, n_lex_bound, k_cap);
-    const HybridWs &ws = t->ws;
-    t->n = n;
-    t->need = need;
-    t->fetch = fetch;
-    t->k = k;
-    t->k_cap = k_cap;
-    t->lambda = lambda;
-    t->w_e = w_embedding;
-    t->w_l = w_lexical;
-    t->diversify = diversify;
-    t->timed = ix->profiling;
-    stage_queries(ix, c, query, 1, ws.h_q);
-    StreamDrain drain{s};
-    RLR_HIP(stage_queries_for_scans(ix, c, ws.h_q, static_cast<size_t>(ix->q_pitch) * sizeof(float), s));
-    uint64_t *d_meta = c->d_out.get() + fetch;
-    // the scan first; then whatever the caller runs beside it (the BM25 chain on its own stream: about as long as scan +
-    // select + re-score + sort, so it must not wait for the host to have launched those -- it used to start 39 us behind the
-    // scan and was the critical path by as much); then the four launches that wait for the scan anyway
-    RLR_HIP(enqueue_query_scan(ix, c, 0, t->timed));
-    if (behind_scan) {
-        LexSink sink; // (pairs that stay on the device fill every slot)
-        sink.d_header = ws.hdr;
-        sink.d_rows = ws.lrow;
-        sink.d_scores = ws.lscore(n_lex_bound);
-        sink.n_bound = n_lex_bound;
-        sink.n_index_rows = n;
-        RLR_TRY(behind_scan(behind_scan_arg, &sink));
-    }
-    RLR_HIP(enqueue_query_rest(ix, c, 0, p, c->d_out.get(), d_meta, t->timed));
-    if (t->timed) RLR_HIP(hipEventRecord(c->bev[0], s));
-    drain.armed = false;
-    *out = t.release();
-    return RLR_OK;
-}
-
-// always consumes the ticket
-static int32_t hybrid_finish_impl(HybridTicket *ticket, const HybridLexSrc &src, uint64_t *rows_out, float *cos_out,
-                                  float *score_out, float *lex_out, uint32_t *n_out, int32_t *fallback)
-{
-    std::unique_ptr<HybridTicket> t(ticket);
-    rlr_index *ix = t->ix;
-    Ctx *c = t->lease.c;
-    hipStream_t s = c->stream;
-    *n_out = 0;
-    *fallback = 0;
-    StreamDrain drain{s};
-    const HybridWs &ws = t->ws;
-    const uint32_t n_lex = src.dev ? static_cast<uint32_t>(ws.n_lex_bound) : src.n_host;
-    if (n_lex > ws.n_lex_bound || !rows_out || !cos_out || !score_out || !lex_out)
-        return set_error(RLR_E_INVALID, "hybrid search: bad arguments");
-    const uint32_t P = t->need, k_cap = t->k_cap, n = t->n;
-    float *d_lscore = ws.lscore(n_lex);
-    uint32_t *h_lex = ws.h_lex, *h_out = ws.h_out;
-    h_out[block_done(k_cap)] = kBlockPending; // (the last kernel's last store replaces it: what the wait below polls)
-    if (src.dev) { // the BM25 kernels ran beside the scan on their own stream: join, then unpack their result
-        RLR_HIP(hipStreamWaitEvent(s, static_cast<hipEvent_t>(src.dev->ready), 0));
-        if (!src.dev->unpacked) { // (begin's LexSink: the scoring stream has done it in front of `ready`)
-            hipLaunchKernelGGL(lex_unpack_kernel, dim3(1), dim3(1024), 0, s, src.dev->d_packed, src.dev->d_count,
-                               std::min(n_lex, src.dev->limit), n, ws.lrow, d_lscore, ws.hdr);
-            RLR_HIP(hipGetLastError());
-        }
-    } else {
-        for (uint32_t i = 0; i < n_lex; ++i)
-            if (src.h_rows[i] >= n || (i && src.h_rows[i] <= src.h_rows[i - 1]))
-                return set_error(RLR_E_INVALID, "lex_rows must be ascending, unique and inside the index");
-        h_lex[0] = n_lex;
-        h_lex[1] = __builtin_bit_cast(uint32_t, src.max_lex);
-        for (uint32_t i = 0; i < n_lex; ++i)
-            h_lex[2 + i] = static_cast<uint32_t>(src.h_rows[i]);
-        if (n_lex)
-            std::memcpy(HybridWs::h_lscore(h_lex, n_lex), src.h_scores, static_cast<size_t>(n_lex) * sizeof(float));
-        RLR_HIP(hipMemcpyAsync(ws.hdr, h_lex, HybridWs::lex_copy_bytes(n_lex), hipMemcpyHostToDevice, s));
-    }
-    RLR_HIP(launch_score_rows(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, c->d_query.get(), ws.lrow, n_lex, ws.lcos, s,
-                              src.dev ? &ws.hdr->n_lex : nullptr, n));
-    const bool pool_emits = !t->diversify; // (without diversification the blend kernel emits by itself)
-    hipLaunchKernelGGL(hybrid_pool_kernel, dim3(1), dim3(1024), 0, s, c->d_out.get(), t->fetch, t->need, n, t->w_e, t->w_l, ws.lrow,
-                       d_lscore, ws.lcos, ws.hdr, ws.cand, c->d_list.get(), ws.comb, ws.cos, ws.lexv, ws.info, k_cap,
-                       pool_emits ? h_out : static_cast<uint32_t *>(nullptr));
-    RLR_HIP(hipGetLastError());
-    if (t->diversify) {
-        RLR_HIP(launch_gram_rows(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, c->d_list.get(), P, ws.gram, 1, s));
-        const MmrEmit emit = mmr_emit(c->d_list.get(), ws.comb, ws.cos, ws.lexv, ws.info, k_cap, h_out);
-        RLR_HIP(launch_mmr_greedy(ws.gram, ws.comb, P, t->k, t->lambda, ws.order, ws.mmr, ws.nsel, ws.info, 1, s, &emit));
-    }
-    if (t->timed) RLR_HIP(hipEventRecord(c->bev[1], s));
-    if (t->timed) {
-        drain.armed = false;
-        RLR_HIP(hipStreamSynchronize(s)); // (the events are read below)
-    } else {
-        RLR_TRY(wait_block(h_out, k_cap, s, &c->wait_ema)); // (a failure leaves the drain guard armed)
-        drain.armed = false;
-    }
-    RLR_TRY(check_hist_assert(c));
-    c->hist_dirty = false;
-    (void)note_search(ix, c, 1, 0, 0, t->timed, /*mmr_chain=*/true);
-    *fallback = static_cast<int32_t>(read_block(h_out, k_cap, rows_out, cos_out, score_out, lex_out, n_out));
-    return RLR_OK;
-}
-
-void launch_lex_unpack(const uint64_t *d_packed, const uint32_t *d_count, uint32_t limit, const LexSink &sink, void *stream)
-{
-    // (tried: the event recorded by this launch itself, hipExtLaunchKernelGGL's stop event, instead of a marker packet behind
-    // it -- the join on the search's stream resumed 3 us earlier under the profiler, nothing measurable without it)
-    hipLaunchKernelGGL(lex_unpack_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), d_packed, d_count, limit,
-                       sink.n_index_rows, sink.d_rows, sink.d_scores, static_cast<HybridLexHeader *>(sink.d_header));
-}
-
-int32_t search_hybrid_begin(rlr_index *ix, const float *query, uint32_t need, uint32_t k, float lambda, int32_t diversify,
-                            float w_embedding, float w_lexical, uint32_t n_lex_bound, float guard_eps, HybridTicket **ticket,
-                            int32_t *fallback, int32_t (*behind_scan)(void *, const LexSink *), void *behind_scan_arg)
-{
-    return hybrid_begin_impl(ix, query, need, k, lambda, diversify, w_embedding, w_lexical, n_lex_bound, guard_eps, ticket,
-                             fallback, behind_scan, behind_scan_arg);
-}
-
-int32_t search_hybrid_finish(HybridTicket *ticket, const LexPending *lex, uint64_t *rows_out, float *cos_out, float *score_out,
-                             float *lex_out, uint32_t *n_out, int32_t *fallback)
-{
-    HybridLexSrc src;
-    if (lex && lex->limit)
-        src.dev = lex; // else: no lexical pair at all -- the blend degenerates to w_e * cos + w_l * 0
-    return hybrid_finish_impl(ticket, src, rows_out, cos_out, score_out, lex_out, n_out, fallback);
-}
-
-void search_hybrid_abort(HybridTicket *ticket)
-{
-    if (!ticket)
-        return;
-    (void)hipStreamSynchronize(ticket->lease.c->stream);
-    delete ticket;
-}
-
-void launch_lex_unpack_batch(const uint64_t *d_sel, uint32_t sel_stride, const uint32_t *d_count, uint32_t count_stride,
-                             uint32_t nq, uint32_t limit, const LexBatchSink &sink, void *stream)
-{
-    hipLaunchKernelGGL(lex_unpack_batch_kernel, dim3(nq), dim3(1024), 0, static_cast<hipStream_t>(stream), d_sel, sel_stride,
-                       d_count, count_stride, limit, sink.n_index_rows, sink.bound, sink.d_rows, sink.d_scores,
-                       static_cast<HybridLexHeader *>(sink.d_headers));
-}
-
-int32_t search_hybrid_batch(rlr_index *ix, const float *queries, uint32_t nq, uint32_t need_in, uint32_t k, float lambda,
-                            int32_t diversify, float w_embedding, float w_lexical, uint32_t n_lex_bound,
-                            int32_t (*lex_launch)(void *, const LexBatchSink *, void **ready), void *lex_arg, uint64_t *rows_out,
-                            float *cos_out, float *score_out, float *lex_out, uint32_t *n_out, uint32_t *status)
-{
-    RLR_TRY(check_handle(ix));
-    const uint32_t n = static_cast<uint32_t>(ix->n_rows);
-    const uint32_t need = std::min<uint32_t>(n, need_in);
-    if (nq == 0 || n == 0 || need == 0 || need > kPoolMax || n_lex_bound == 0 || n_lex_bound > kHybridLexMax || !lex_launch ||
-        !queries || !rows_out || !cos_out || !score_out || !lex_out || !n_out || !status || !(w_embedding > 0.0f) ||
-        !std::isfinite(w_embedding) || !std::isfinite(w_lexical))
-        return set_error(RLR_E_INVALID, "batched hybrid search: arguments outside the fused kernels");
-    const uint32_t fetch = static_cast<uint32_t>(std::min<uint64_t>(n, static_cast<uint64_t>(need) + kHybridFetchMargin));
-    if (fetch + n_lex_bound > kHybridSlots)
-        return set_error(RLR_E_INVALID, "batched hybrid search: %u fetched + %u lexical rows exceed the blend's slots", fetch, n_lex_bound);
-    RLR_TRY(use_device(ix));
-    CtxLease lease(ix);
-    RLR_TRY(ctx_acquire(ix, &lease.c));
-    Ctx *c = lease.c;
-    hipStream_t s = c->stream;
-    const uint32_t P = need, B = n_lex_bound;
-    const uint32_t k_cap = result_k_cap(k, P, diversify != 0);
-    const uint64_t Q = nq;
-    RLR_HIP(c->d_pool.reserve(HybridBatchWs(nullptr, ix, Q, fetch, P, B, diversify != 0).d.floats()));
-    const HybridBatchWs ws(c->d_pool.get(), ix, Q, fetch, P, B, diversify != 0);
-    // whatever goes wrong from here on: the BM25 chain (another stream, writing into this workspace) and this stream must
-    // be drained before the context goes back
-    StreamDrain drain{s};
-    // 1. the BM25 chain on the lexical index' stream, into this workspace
-    LexBatchSink sink;
-    sink.d_rows = ws.lrow;
-    sink.d_scores = ws.lscore;
-    sink.d_headers = ws.hdr;
-    sink.bound = B;
-    sink.n_index_rows = n;
-    void *ready = nullptr;
-    RLR_TRY(lex_launch(lex_arg, &sink, &ready));
-    drain.also = static_cast<hipEvent_t>(ready);
-    // 2. beside it: the fetch of every query, the batched top-k (GEMM / shared scan / per-query pipeline as the planner picks);
-    //    its overflow handling needs the host, hence the first synchronisation
-    SearchPlan p;
-    const uint64_t *h = nullptr;
-    RLR_TRY(run_search(ix, c, queries, nq, fetch, -1.0f, nullptr, &p, &h));
-    if (!h || p.k != fetch)
-        return set_error(RLR_E_INTERNAL, "batched hybrid search: the cosine batch produced no result");
-    // (the fetch goes through the host on purpose: run_search's single-query pipelines -- the planner's choice for batches
-    // too small for a shared pass -- write their results straight into pinned host memory, not into c->d_out, so the host
-    // copy is the one place every path leaves them; Q x fetch x 8 bytes each way)
-    std::vector<uint64_t> fetched(h, h + Q * fetch); // (the pinned buffer is re-laid out below)
-    RLR_TRY(pin_reserve(c, HybridBatchPin(nullptr, ix, Q, fetch, P).h.bytes));
-    const HybridBatchPin pin(c->h_pin.get(), ix, Q, fetch, P);
-    const size_t b_packed = Q * fetch * sizeof(uint64_t), b_q = Q * ix->q_pitch * sizeof(float);
-    std::memcpy(pin.packed, fetched.data(), b_packed);
-    pad_queries(ix, queries, nq, pin.q);
-    RLR_HIP(hipMemcpyAsync(ws.packed, pin.packed, b_packed, hipMemcpyHostToDevice, s));
-    RLR_HIP(hipMemcpyAsync(ws.q, pin.q, b_q, hipMemcpyHostToDevice, s));
-    // 3. join the BM25 chain; exact cosines of the lexical rows, blend, order, cut -- one workgroup per query
-    RLR_HIP(hipStreamWaitEvent(s, static_cast<hipEvent_t>(ready), 0));
-    RLR_HIP(launch_score_rows_batch(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, ws.q, ix->q_pitch, nq, ws.lrow, B, ws.lcos,
-                                    reinterpret_cast<const uint32_t *>(ws.hdr), 2, n, s));
-    const HybridBatchRes &d = ws.res, &r = pin.res;
-    hipLaunchKernelGGL(hybrid_pool_batch_kernel, dim3(nq), dim3(1024), 0, s, ws.packed, fetch, P, n, w_embedding, w_lexical, B,
-                       ws.lrow, ws.lscore, ws.lcos, ws.hdr, ws.cand, d.list, d.comb, d.cos, d.lexv, d.info, d.sizes);
-    RLR_HIP(hipGetLastError());
-    // 4. MMR over every pool at once
-    if (diversify) {
-        RLR_HIP(launch_gram_rows(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, d.list, P, ws.gram, nq, s));
-        RLR_HIP(launch_mmr_greedy(ws.gram, d.comb, P, k, lambda, d.order, d.mmr, d.nsel, d.sizes, nq, s));
-    }
-    RLR_HIP(hipMemcpyAsync(r.list, d.list, HybridBatchRes::words(Q, P) * 4, hipMemcpyDeviceToHost, s));
-    RLR_HIP(hipStreamSynchronize(s));
-    drain.armed = false;
-    for (uint32_t q = 0; q < nq; ++q) {
-        status[q] = r.info[2 * q + 1];
-        n_out[q] = 0;
-        if (status[q])
-            continue;
-        const size_t base = static_cast<size_t>(q) * P, ob = static_cast<size_t>(q) * k_cap;
-        const uint32_t cnt = std::min<uint32_t>(diversify ? r.nsel[q] : r.info[2 * q], k_cap);
-        for (uint32_t i = 0; i < cnt; ++i) {
-            const size_t o = base + (diversify ? r.order[base + i] : i);
-            rows_out[ob + i] = r.list[o];
-            cos_out[ob + i] = r.cos[o];
-            score_out[ob + i] = r.comb[o];
-            lex_out[ob + i] = r.lexv[o];
-        }
-        n_out[q] = cnt;
-    }
-    return RLR_OK;
-}
-
-} // namespace rlr
-
-extern "C" {
-
-int32_t rlr_search_hybrid(rlr_index *ix, const float *query, uint32_t need, uint32_t k, float lambda, int32_t diversify,
-                          float w_embedding, float w_lexical, const uint64_t *lex_rows, const float *lex_scores, uint32_t n_lex,
-                          float max_lex, float guard_eps, uint64_t *rows_out, float *cos_out, float *score_out, float *lex_out,
-                          uint32_t *n_out, int32_t *fallback)
-{
-    RLR_TRY(check_handle(ix));
-    if (!n_out || !fallback)
-        return set_error(RLR_E_INVALID, "n_out / fallback is null");
-    *n_out = 0;
-    *fallback = 0;
-    if (ix->n_rows == 0 || need == 0)
-        return RLR_OK;
-    if (!query || !rows_out || !cos_out || !score_out || !lex_out || (n_lex && (!lex_rows || !lex_scores)))
-        return set_error(RLR_E_INVALID, "null argument");
-    rlr::HybridTicket *t = nullptr;
-    RLR_TRY(rlr::hybrid_begin_impl(ix, query, need, k, lambda, diversify, w_embedding, w_lexical, n_lex, guard_eps, &t, fallback));
-    if (*fallback)
-        return RLR_OK;
-    HybridLexSrc src;
-    src.h_rows = lex_rows;
-    src.h_scores = lex_scores;
-    src.n_host = n_lex;
-    src.max_lex = max_lex;
-    return rlr::hybrid_finish_impl(t, src, rows_out, cos_out, score_out, lex_out, n_out, fallback);
-}
-
 // ---- capped hybrid search (rlr_search_capped): at most per_doc results per document, in combined order ---------------
 // One pool entry on the host: what the exact form builds and every form hands back.
 struct CappedHit {
@@ -5145,7 +3929,7 @@ static int32_t capped_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const Ca
                 while (at < ns && side[2 + at] != row)
                     ++at;
                 if (at >= ns || (f && !filter_holds(f, row)))
-                    form = 2; // a masked row came back (the hazard filtered_query documents)
+                    form = 2; // a masked row came back (the hazard masked_row_among documents)
                 else
                     hits[i] = CappedHit{row, side[2 + P + at], r_comb[i], r_cos[i], r_lex[i]};
             }
@@ -5241,137 +4025,7 @@ int32_t rlr_search_capped(rlr_index *ix, const rlr_filter *f, const float *query
 
 int32_t rlr_index_capped_forms(rlr_index *ix, uint64_t counts[4], int32_t reset)
 {
-    RLR_TRY(check_handle(ix));
-    std::lock_guard<std::mutex> lk(ix->mu);
-    for (int i = 0; i < 4; ++i) {
-        if (counts)
-            counts[i] = ix->capped_forms[i];
-        if (reset)
-            ix->capped_forms[i] = 0;
-    }
-    return RLR_OK;
-}
-
-// Batched MMR over P-strided pools.  The pool rows either live in the index (pool_rows != null:
-// gathered to f32 here) or are already in device memory as n_queries x P x dim f32 values
-// (d_values != null: the sharded path, after the winner-row exchange).
-// d_matrix != null: pool_rows are slots of that matrix (n_matrix raw rows in the index' own dtype and pitch, e.g. the
-// receive buffer of the cross-shard winner-row exchange) instead of rows of the index.
-static int32_t mmr_batch_impl(rlr_index *ix, const uint64_t *pool_rows, const float *d_values, const float *pool_scores,
-                              const uint32_t *pool_sizes, uint32_t n_queries, uint32_t P, uint32_t k, float lambda,
-                              uint32_t *order_out, float *mmr_out, uint32_t *n_out, const void *d_matrix = nullptr,
-                              uint64_t n_matrix = 0)
-{
-    RLR_TRY(check_handle(ix));
-    if (n_queries == 0)
-        return RLR_OK;
-    if ((!pool_rows && !d_values) || !pool_scores || !pool_sizes || !order_out || !n_out)
-        return set_error(RLR_E_INVALID, "null argument");
-    if (P == 0) {
-        for (uint32_t q = 0; q < n_queries; ++q)
-            n_out[q] = 0;
-        return RLR_OK;
-    }
-    if (P > 1024)
-        return set_error(RLR_E_INVALID, "batched MMR supports pools of at most 1024 candidates (got %u)", P);
-    RLR_TRY(use_device(ix));
-    CtxLease lease(ix);
-    RLR_TRY(ctx_acquire(ix, &lease.c));
-    Ctx *c = lease.c;
-    hipStream_t s = c->stream;
-    // queries per pass: the workspace (gram m x P x P + scores / order / mmr) is capped at ~3 GB.  All queries of a
-    // pass run their greedy chains concurrently, one wavefront each, so the more queries per pass the better the
-    // chip is filled: at 64 per pass (the first version) 1024 pools took 16 rounds of gather + Gram + greedy + sync.
-    const uint64_t per_query = static_cast<uint64_t>(P) * P + 3ull * P + 2;
-    const uint32_t QC = static_cast<uint32_t>(std::max<uint64_t>(64, std::min<uint64_t>(4096, (3ull << 30) / 4 / std::max<uint64_t>(per_query, 1))));
-    std::vector<uint64_t> rows_chunk;
-    for (uint32_t q0 = 0; q0 < n_queries; q0 += QC) {
-        const uint32_t m = std::min(QC, n_queries - q0);
-        const uint32_t n_list = m * P;
-        for (uint32_t q = 0; q < m; ++q)
-            if (pool_sizes[q0 + q] > P)
-                return set_error(RLR_E_INVALID, "pool_sizes[%u] = %u exceeds P = %u", q0 + q, pool_sizes[q0 + q], P);
-        RLR_TRY(pin_reserve(c, MmrStaging(nullptr, m, P).h.bytes));
-        if (pool_rows) {
-            // unused slots (j >= pool_sizes[q]) gather row 0: never read by the greedy kernel
-            bool all_full = true;
-            for (uint32_t q = 0; q < m && all_full; ++q)
-                all_full = pool_sizes[q0 + q] == P;
-            const uint64_t *src_rows = pool_rows + static_cast<size_t>(q0) * P;
-            if (!all_full) { // (full pools are taken as they stand: no 8 n_list-byte fill + copy in front of every batch)
-                rows_chunk.assign(n_list, 0);
-                for (uint32_t q = 0; q < m; ++q)
-                    std::memcpy(rows_chunk.data() + static_cast<size_t>(q) * P, pool_rows + static_cast<size_t>(q0 + q) * P,
-                                pool_sizes[q0 + q] * sizeof(uint64_t));
-                src_rows = rows_chunk.data();
-            }
-            RLR_TRY(upload_list(ix, c, src_rows, n_list, d_matrix ? n_matrix : ~0ull));
-        }
-        RLR_HIP(c->d_pool.reserve(MmrWs(nullptr, m, P).d.floats()));
-        const MmrWs ws(c->d_pool.get(), m, P);
-        const MmrStaging h(c->h_pin.get(), m, P);
-        std::memcpy(h.scores, pool_scores + static_cast<size_t>(q0) * P, static_cast<size_t>(n_list) * sizeof(float));
-        std::memcpy(h.sizes, pool_sizes + q0, m * sizeof(uint32_t));
-        RLR_HIP(hipMemcpyAsync(ws.scores, h.scores, static_cast<size_t>(n_list) * sizeof(float), hipMemcpyHostToDevice, s));
-        RLR_HIP(hipMemcpyAsync(ws.sizes, h.sizes, m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        const bool timed = ix->profiling;
-        if (timed) RLR_HIP(hipEventRecord(c->ev[0], s));
-        if (pool_rows) // the Gram kernel reads the index rows through the list: no gathered copy
-            RLR_HIP(launch_gram_rows(d_matrix ? d_matrix : ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, c->d_list.get(), P, ws.gram, m, s));
-        else
-            RLR_HIP(launch_gram(d_values + static_cast<size_t>(q0) * P * ix->dim, P, ix->dim, ws.gram, m, s));
-        RLR_HIP(launch_mmr_greedy(ws.gram, ws.scores, P, k, lambda, ws.res.order, ws.res.mmr, ws.res.n, ws.sizes, m, s));
-        if (timed) RLR_HIP(hipEventRecord(c->ev[1], s));
-        RLR_HIP(hipMemcpyAsync(h.res.order, ws.res.order, MmrResults::words(m, P) * 4, hipMemcpyDeviceToHost, s));
-        RLR_HIP(hipStreamSynchronize(s));
-        if (timed)
-            note_mmr(ix, c, m);
-        for (uint32_t q = 0; q < m; ++q) {
-            const uint32_t ns = h.res.n[q];
-            n_out[q0 + q] = ns;
-            std::memcpy(order_out + static_cast<size_t>(q0 + q) * P, h.res.order + static_cast<size_t>(q) * P, ns * sizeof(uint32_t));
-            if (mmr_out)
-                std::memcpy(mmr_out + static_cast<size_t>(q0 + q) * P, h.res.mmr + static_cast<size_t>(q) * P, ns * sizeof(float));
-        }
-    }
-    return RLR_OK;
-}
-
-int32_t rlr_mmr_select_batch(rlr_index *ix, const uint64_t *pool_rows, const float *pool_scores,
-                             const uint32_t *pool_sizes, uint32_t n_queries, uint32_t P, uint32_t k, float lambda,
-                             uint32_t *order_out, float *mmr_out, uint32_t *n_out)
-{
-    if (n_queries && !pool_rows)
-        return set_error(RLR_E_INVALID, "null argument");
-    return mmr_batch_impl(ix, pool_rows, nullptr, pool_scores, pool_sizes, n_queries, P, k, lambda, order_out, mmr_out, n_out);
-}
-
-int32_t rlr_mmr_select_values(rlr_index *ix, const void *d_values, const float *pool_scores, const uint32_t *pool_sizes,
-                              uint32_t n_queries, uint32_t P, uint32_t k, float lambda, uint32_t *order_out,
-                              float *mmr_out, uint32_t *n_out)
-{
-    if (n_queries && !d_values)
-        return set_error(RLR_E_INVALID, "null argument");
-    return mmr_batch_impl(ix, nullptr, static_cast<const float *>(d_values), pool_scores, pool_sizes, n_queries, P, k, lambda,
-                          order_out, mmr_out, n_out);
-}
-
-int32_t rlr_mmr_select_staged(rlr_index *ix, const void *d_staged, uint64_t n_staged, const uint64_t *pool_slots,
-                              const float *pool_scores, const uint32_t *pool_sizes, uint32_t n_queries, uint32_t P, uint32_t k,
-                              float lambda, uint32_t *order_out, float *mmr_out, uint32_t *n_out)
-{
-    if (n_queries && (!d_staged || !pool_slots || n_staged == 0))
-        return set_error(RLR_E_INVALID, "null argument");
-    // one large pool: the single-pool kernels (up to 4096).  P is only the stride, which one pool does not use, so a
-    // small pool in a wide slot list goes the same way
-    if (n_queries == 1 && pool_sizes && (pool_sizes[0] > 1024 || P > 1024)) {
-        if (pool_sizes[0] > P)
-            return set_error(RLR_E_INVALID, "pool_sizes[0] = %u exceeds P = %u", pool_sizes[0], P);
-        return mmr_single_impl(ix, pool_slots, pool_scores, pool_sizes[0], k, lambda, order_out, mmr_out, n_out, d_staged,
-                               n_staged);
-    }
-    return mmr_batch_impl(ix, pool_slots, nullptr, pool_scores, pool_sizes, n_queries, P, k, lambda, order_out, mmr_out, n_out,
-                          d_staged, n_staged);
+    return read_forms(ix, &rlr_index::capped_forms, counts, reset);
 }
 
 int32_t rlr_index_row_bytes(const rlr_index *ix, uint32_t *bytes_out)
@@ -5552,53 +4206,5 @@ int32_t filter_view(const rlr_filter *f, FilterView *out)
 int32_t filter_check(const rlr_index *ix, const rlr_filter *f)
 {
     return check_filter(ix, f);
-}
-
-// rlr_score_rows for nq queries with a list each: queries, lists and counts go up in one copy, launch_score_rows_batch
-// scores every list (the reference-order dot product of rlr_score_rows per pair), one copy back, one synchronisation.
-int32_t score_rows_batch(rlr_index *ix, const float *queries, uint32_t nq, const uint64_t *rows, const uint32_t *counts,
-                         uint32_t stride, float *cos_out)
-{
-    RLR_TRY(check_handle(ix));
-    if (nq == 0 || stride == 0)
-        return RLR_OK;
-    if (!queries || !rows || !counts || !cos_out)
-        return set_error(RLR_E_INVALID, "null argument");
-    RLR_TRY(use_device(ix));
-    CtxLease lease(ix);
-    RLR_TRY(ctx_acquire(ix, &lease.c));
-    Ctx *c = lease.c;
-    // [queries nq x q_pitch | lists nq x stride | counts nq | cosines nq x stride], 32-bit words, on both sides
-    const size_t w_q = static_cast<size_t>(nq) * ix->q_pitch, w_list = static_cast<size_t>(nq) * stride;
-    const size_t w_in = w_q + w_list + nq, w_all = w_in + w_list;
-    RLR_TRY(pin_reserve(c, w_all * 4));
-    RLR_HIP(c->d_pool.reserve(w_all));
-    float *h_q = static_cast<float *>(c->h_pin.get());
-    uint32_t *h_list = reinterpret_cast<uint32_t *>(h_q + w_q), *h_cnt = h_list + w_list;
-    pad_queries(ix, queries, nq, h_q);
-    for (uint32_t q = 0; q < nq; ++q) {
-        if (counts[q] > stride)
-            return set_error(RLR_E_INVALID, "list %u holds %u rows, the stride is %u", q, counts[q], stride);
-        h_cnt[q] = counts[q];
-        for (uint32_t i = 0; i < stride; ++i) {
-            const uint64_t r = i < counts[q] ? rows[static_cast<size_t>(q) * stride + i] : 0;
-            if (r >= ix->n_rows)
-                return set_error(RLR_E_RANGE, "row %llu out of range (%llu rows)", static_cast<unsigned long long>(r),
-                                 static_cast<unsigned long long>(ix->n_rows));
-            h_list[static_cast<size_t>(q) * stride + i] = static_cast<uint32_t>(r);
-        }
-    }
-    float *d_q = c->d_pool.get();
-    const uint32_t *d_list = reinterpret_cast<const uint32_t *>(d_q + w_q), *d_cnt = d_list + w_list;
-    float *d_cos = d_q + w_in;
-    RLR_HIP(hipMemcpyAsync(d_q, h_q, w_in * 4, hipMemcpyHostToDevice, c->stream));
-    RLR_HIP(launch_score_rows_batch(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, d_q, ix->q_pitch, nq, d_list, stride, d_cos, d_cnt, 1,
-                                    static_cast<uint32_t>(ix->n_rows), c->stream));
-    float *h_cos = reinterpret_cast<float *>(h_cnt + nq);
-    RLR_HIP(hipMemcpyAsync(h_cos, d_cos, w_list * 4, hipMemcpyDeviceToHost, c->stream));
-    RLR_HIP(hipStreamSynchronize(c->stream));
-    for (uint32_t q = 0; q < nq; ++q)
-        std::memcpy(cos_out + static_cast<size_t>(q) * stride, h_cos + static_cast<size_t>(q) * stride, counts[q] * sizeof(float));
-    return RLR_OK;
 }
 } // namespace rlr

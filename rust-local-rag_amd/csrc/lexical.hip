@@ -2160,7 +2160,7 @@ void lexical_batch_finish(LexBatchPending *p, bool ok)
 
 // ---- rlr_lexical_score_batch: the batched BM25 chain on its own ------------------------------------------------------
 namespace {
-struct LexBatchHeader { // index.hip's HybridLexHeader, as lex_unpack_batch_kernel writes it
+struct LexBatchHeader { // index_fused.hip's HybridLexHeader, as lex_unpack_batch_kernel writes it
     uint32_t n_lex;
     float max_lex;
 };

@@ -28,7 +28,7 @@ struct LexPending {
     bool unpacked = false;  // the scoring stream also wrote the rows / scores / header a LexSink asked for (in front of `ready`)
 };
 
-// Where a hybrid search wants a scoring call's result unpacked (index.hip: lex_unpack_kernel): lexical_enqueue launches that
+// Where a hybrid search wants a scoring call's result unpacked (index_fused.hip: lex_unpack_kernel): lexical_enqueue launches that
 // on ITS stream in front of `ready`, so the search's own stream finds rows, scores and header (count, max score) in place
 // when it has joined -- one dependent launch less behind the join.
 struct LexSink {
@@ -38,7 +38,7 @@ struct LexSink {
     uint32_t n_bound = 0;       // most pairs the search takes
     uint32_t n_index_rows = 0;  // rows of the embedding index (pairs beyond it are marked, see lex_unpack_kernel)
 };
-// (index.hip) no error check inside: the caller's hipGetLastError sees it
+// (index_fused.hip) no error check inside: the caller's hipGetLastError sees it
 void launch_lex_unpack(const uint64_t *d_packed, const uint32_t *d_count, uint32_t limit, const LexSink &sink, void *stream);
 
 // LexicalIndex::score (rag_engine.rs:2169-2225) up to the ordered result list in device memory.  No synchronisation.
@@ -59,7 +59,7 @@ int32_t lexical_score_exact(rlr_lexical *lx, const char *tokens, size_t len, uin
 // ok = false: something failed after the enqueue -- the workspace is re-zeroed before its next use
 void lexical_finish(LexPending *p, bool ok);
 
-// index.hip: rlr_search_hybrid (include/rlr_gpu.h) in two enqueues, so that the BM25 kernels can be launched in between:
+// index_fused.hip: rlr_search_hybrid (include/rlr_gpu.h) in two enqueues, so that the BM25 kernels can be launched in between:
 // begin puts the scan .. sort of the need + n_lex_bound + 8 best rows by cosine on the index' stream (*fallback != 0: not
 // covered by the fused kernels, no ticket); finish joins `lex` (null or limit 0: no lexical pair) by event, enqueues
 // blend .. results, synchronises and consumes the ticket; abort drains and frees a ticket that will not be finished.
@@ -76,7 +76,7 @@ int32_t search_hybrid_finish(HybridTicket *ticket, const LexPending *lex, uint64
 void search_hybrid_abort(HybridTicket *ticket);
 
 // ---- many queries at once (csrc/engine.cpp: rlr_engine_search_text_batch) ------------------------------------------------
-// Where a batched hybrid search wants the lexical pairs of query q: rows / scores at [q * bound, ...), header q (index.hip's
+// Where a batched hybrid search wants the lexical pairs of query q: rows / scores at [q * bound, ...), header q (index_fused.hip's
 // HybridLexHeader: count, max score), as lex_unpack_kernel writes them for one query.
 struct LexBatchSink {
     uint32_t *d_rows = nullptr;
@@ -107,7 +107,7 @@ int32_t lexical_batch_enqueue(rlr_lexical *lx, uint32_t nq, const char *tokens, 
                               const FilterView *filter = nullptr, const FilterView *scopes = nullptr);
 // drains the workspace's stream, hands it back and drops the readers' lock (also after a failed enqueue)
 void lexical_batch_finish(LexBatchPending *p, bool ok);
-// (index.hip) query q's keys at d_sel[q * sel_stride], count at d_count[q * count_stride]; no error check inside
+// (index_fused.hip) query q's keys at d_sel[q * sel_stride], count at d_count[q * count_stride]; no error check inside
 void launch_lex_unpack_batch(const uint64_t *d_sel, uint32_t sel_stride, const uint32_t *d_count, uint32_t count_stride,
                              uint32_t nq, uint32_t limit, const LexBatchSink &sink, void *stream);
 
@@ -118,7 +118,7 @@ inline uint32_t result_k_cap(uint32_t k, uint32_t need, bool diversify)
     return diversify ? std::max<uint32_t>(std::min<uint32_t>(std::max<uint32_t>(k, 1u), need), 1u) : need;
 }
 
-// index.hip: the cosine side, blend and MMR of nq hybrid searches at once.  `queries`: nq prepared (normalised, dim-long)
+// index_fused.hip: the cosine side, blend and MMR of nq hybrid searches at once.  `queries`: nq prepared (normalised, dim-long)
 // queries; `need`, `k`, `lambda`, `diversify`, weights, `n_lex_bound` as for search_hybrid_begin.  lex_launch (may be null:
 // no lexical pairs) is called once the workspace exists, before the cosine batch: it enqueues the BM25 chain into the sink
 // on its own stream and returns the event to join (*ready).  Results of query q at [q * k_cap, ...) with k_cap =

@@ -9,7 +9,7 @@
 // chain reaches the last fetched row while rows remain unfetched the order cannot be decided from this fetch:
 // info[1] = 2 and the host takes the widening two-call path, exactly as search_impl does.
 //   info[0] = pool size, info[1] = status (0 ok, 1 guard-band overflow upstream, 2 boundary tie)
-// Shared by index.hip (the stand-alone launch behind sort_emit / the split pipeline) and tail.hip (the fused tail's
+// Shared by index_fused.hip (the stand-alone launch behind sort_emit / the split pipeline) and tail.hip (the fused tail's
 // finish: the workgroup that holds all re-scored candidates builds the pool in the same launch).
 #pragma once
 

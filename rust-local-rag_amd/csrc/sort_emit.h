@@ -1,7 +1,8 @@
 // sort_emit.h -- the last step of a single-query search: one workgroup of 1024 threads orders the exactly re-scored
 // candidates (packed (score key, ~row) words, <= 4096 of them) and writes the best k.  Replaces the tail of
 // `scores.sort_by(..)` + `take(..)`, /root/reference/src/rag_engine.rs:543-548, for the handful of rows that survived
-// the nomination.  Shared by index.hip (the stand-alone launch) and tail.hip (the fused select tail).
+// the nomination.  Shared by index.hip (the stand-alone launch), tail.hip (the fused select tail) and, for the result
+// block at the end of this file, index_fused.hip (the blend that emits by itself) and exact.hip / group.hip.
 #pragma once
 
 #include "common.h"

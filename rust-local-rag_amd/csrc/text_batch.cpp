@@ -1,6 +1,6 @@
 // text_batch.cpp -- rlr_engine_search_text_batch (include/rlr_engine.h): rlr_engine_search_text for many queries at once.
 // The host side of the batch: sizes and the gate of the fused kernels exactly as rlr_engine_search_text computes them, the
-// queries prepared the same way, sub-batches through rlr::search_hybrid_batch (index.hip) with the BM25 chain of
+// queries prepared the same way, sub-batches through rlr::search_hybrid_batch (index_fused.hip) with the BM25 chain of
 // rlr::lexical_batch_enqueue (lexical.hip) beside the cosine batch, and every query the batch could not decide re-run alone
 // through rlr_engine_search_text.  Compiled with -ffp-contract=off like engine.cpp.
 #include "../../include/rlr_engine.h"

@@ -90,7 +90,7 @@ def gram_instance(dtype, pools, P):
 
 
 def pools_per_pass(P):
-    """mmr_batch_impl (csrc/index.hip): a call is cut into passes of this many pools; the Gram instance is chosen per pass"""
+    """mmr_batch_impl (csrc/index_fused.hip): a call is cut into passes of this many pools; the Gram instance is chosen per pass"""
     per_query = P * P + 3 * P + 2
     return max(64, min(4096, (3 << 30) // 4 // per_query))
 

@@ -1,5 +1,5 @@
 """Rows and lexical pairs that put the fused pool and blend stage into each of its states on purpose: hybrid_pool_body
-(csrc/index.hip; hybrid_pool_kernel and hybrid_pool_batch_kernel) and pool_prepare_body<FROM_CANDIDATES, COHERENT>
+(csrc/index_fused.hip; hybrid_pool_kernel and hybrid_pool_batch_kernel) and pool_prepare_body<FROM_CANDIDATES, COHERENT>
 (csrc/pool_prepare.h; pool_prepare_kernel<true>, pool_prepare_kernel<false> and the fused tail's finish).
 test_pool_vectors_cpu.py proves that the cases reach those states, test_gpu_pool.py runs them.
 

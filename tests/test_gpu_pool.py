@@ -1,5 +1,5 @@
 """Every branch of the fused pool and blend stage on the designed rows of tests/pool_vectors.py: hybrid_pool_body
-(csrc/index.hip) through rlr_search_hybrid and, for many queries, through rlr_engine_search_text_batch; pool_prepare_body
+(csrc/index_fused.hip) through rlr_search_hybrid and, for many queries, through rlr_engine_search_text_batch; pool_prepare_body
 (csrc/pool_prepare.h) through rlr_search_diverse in its three forms -- pool_prepare_kernel<true> (fetch <= 512, RLR_TAIL=0),
 the fused tail's finish (fetch <= 512, RLR_TAIL=1) and sort_emit + pool_prepare_kernel<false> (fetch > 512).
 

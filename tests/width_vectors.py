@@ -25,8 +25,8 @@ import numpy as np
 
 F32 = np.float32
 KIB = 1024
-MAX_DIM = 8192                     # rlr_index_create (csrc/index.hip: kMaxDim)
-LDS_SORT_CAP = 4096                # kLdsSortCap (csrc/index.hip): a larger k takes big_query's one-lane re-score
+MAX_DIM = 8192                     # rlr_index_create (csrc/index_internal.h: kMaxDim)
+LDS_SORT_CAP = 4096                # kLdsSortCap (csrc/index_internal.h): a larger k takes big_query's one-lane re-score
 SCORE_ROWS_STAGED_MIN = 65         # launch_score_rows (csrc/exact.hip): `fits && n > 64`
 N_SPECIAL = 3
 ZERO_ROW, INF_ROW, NAN_ROW = 0, 1, 2
