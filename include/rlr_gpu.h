@@ -446,7 +446,8 @@ int32_t rlr_index_delete_documents(rlr_index *idx, const uint32_t *docs, uint32_
  *   index' filter) as for rlr_search_topk_filtered; an empty filter: RLR_OK with n_out = 0.
  *   Results of query q start at q * k in rows_out / cos_out / docs_out; docs_out (may be null) receives each result row's
  *   document id.
- * Queries run one by one over the master rows: no coalescer, no nomination copy, no shared pass.  The selection runs on
+ * Queries run one by one over the master rows: no coalescer, no nomination copy, no shared pass
+ * (rlr_search_topk_grouped_batch below shares passes among the queries of a call).  The selection runs on
  * the device behind the scan (DESIGN.md "Grouped top-k"); what it cannot decide it hands to an exact form (reference-order
  * scores of every allowed row, the walk on the host), never silently: */
 #define RLR_MAX_PER_DOCUMENT 8
@@ -457,6 +458,29 @@ int32_t rlr_search_topk_grouped(rlr_index *idx, const rlr_filter *f, const float
  * overflow, [2] because rows with NaN nominations were needed to fill k or a masked row came back, [3] by rule (a
  * list-path filter, k beyond the device finish, rows too wide for the staged re-score).  counts may be null. */
 int32_t rlr_index_grouped_forms(rlr_index *idx, uint64_t counts[4], int32_t reset);
+/* rlr_search_topk_grouped for a BATCH: the same arguments, output layout, error rules and result definition, query by
+ * query, and for every input the same bits in every output -- only the number of passes over the rows differs.  Over f32
+ * rows of 256 / 512 / 768 / 1024 elements (inside a mask-path filter too) the queries run in chunks of up to 8: one shared
+ * scan, then ONE set of selection launches for the chunk, with one document table for all of its queries (DESIGN.md
+ * "Batched grouped top-k").  The chunk width is the largest of 2..8 whose workspace stays within the bytes of the index's
+ * rows; a larger batch is split evenly into consecutive chunks (9 queries: 5 + 4).  A query the device cannot decide is
+ * handed to the single-query path of rlr_search_topk_grouped on its own -- the rest of its chunk stays decided -- never
+ * dropped or answered approximately.  One host synchronisation per chunk plus those of the queries handed back. */
+int32_t rlr_search_topk_grouped_batch(rlr_index *idx, const rlr_filter *f, const float *queries, uint32_t n_queries,
+                                      uint32_t k, uint32_t per_doc, float guard_eps, uint64_t *rows_out, float *cos_out,
+                                      uint32_t *docs_out, uint32_t *n_out);
+/* When rlr_search_topk_grouped_batch shares a pass: 0 (the default) where a cost model over the measured rates expects the
+ * shared chunk to win, 1 never (every query one by one), 2 wherever the shape allows.  Any other mode: RLR_E_INVALID.
+ * The answers do not depend on it. */
+int32_t rlr_index_set_grouped_sharing(rlr_index *idx, int32_t mode);
+/* Queries of rlr_search_topk_grouped_batch by form since the last reset, each query in exactly one: [0] selected on the
+ * device behind a shared scan; handed to the single-query path [1] on a capacity (more than 2048 candidates, a workgroup's
+ * local list or the table overflowed), [2] because the answer is short while allowed rows with NaN nominations exist, a
+ * masked row came back or the chunk's workspace could not be reserved, [3] by rule (one query, mode 1, the cost model
+ * declined, a list-path filter, k beyond the device finish, rows too wide for the staged re-score, a row shape no shared
+ * scan serves -- binary16 rows among them --, the lone remainder of a batch, no chunk width of two within the workspace
+ * rule).  A handed-over query is counted by rlr_index_grouped_forms as well.  counts may be null. */
+int32_t rlr_index_grouped_batch_forms(rlr_index *idx, uint64_t counts[4], int32_t reset);
 
 /* ---- range search: every row scoring at or above a threshold, and how many -- */
 /* For one query over the allowed rows (all rows, or the rows of f) and a threshold tau: row r is a HIT iff e(r) >= tau in

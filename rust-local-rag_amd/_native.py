@@ -158,6 +158,9 @@ PROTOTYPES = [
     ("rlr_index_delete_documents", C.c_int32, [_H, u32p, C.c_uint32, u64p, C.c_uint64, u64p]),
     ("rlr_search_topk_grouped", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, u64p, f32p, u32p, u32p]),
     ("rlr_index_grouped_forms", C.c_int32, [_H, u64p, C.c_int32]),
+    ("rlr_search_topk_grouped_batch", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, u64p, f32p, u32p, u32p]),
+    ("rlr_index_set_grouped_sharing", C.c_int32, [_H, C.c_int32]),
+    ("rlr_index_grouped_batch_forms", C.c_int32, [_H, u64p, C.c_int32]),
     ("rlr_search_range", C.c_int32, [_H, _H, f32p, C.c_uint32, f32p, C.c_uint32, C.c_float, u64p, f32p, u32p, u64p]),
     ("rlr_index_range_forms", C.c_int32, [_H, u64p, C.c_int32]),
     ("rlr_search_range_batch", C.c_int32, [_H, _H, f32p, C.c_uint32, f32p, C.c_uint32, C.c_float, u64p, f32p, u32p, u64p]),

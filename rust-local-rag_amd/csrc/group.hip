@@ -14,6 +14,8 @@
 //   finish     one workgroup: exact order, rank inside the group, accept below per_doc, emit the first k.
 // A capped hybrid search (rlr_search_capped) runs the same launches with k = the pool size and capped_finish_kernel as its
 // finish: the candidates united with the lexical rows, blended, ranked inside the group in COMBINED order (below).
+// A batched grouped search (rlr_search_topk_grouped_batch) runs ONE set of these launches for a chunk of up to 8 queries
+// behind a shared scan, with one key table for the chunk and a value plane per query ("the batched tail", below).
 // An order between workgroups comes from the order of launches on one stream, never from a flag (the rule of tail.hip);
 // inside a launch the table is only touched by atomics, between launches by plain loads.
 #include "../../include/rlr_gpu.h"
@@ -177,7 +179,8 @@ __device__ inline bool group_is_head(uint32_t key, uint32_t row, uint64_t tg)
     return key != 0u && ((static_cast<uint64_t>(key) << 32) | (0xFFFFFFFFu - row)) >= tg;
 }
 
-__global__ __launch_bounds__(kGroupBlock) void group_heads_kernel(GroupDev a)
+// (the bodies of heads, refine and collect are shared with the batched tail below: one GroupDev per query)
+__device__ inline void group_heads_body(const GroupDev &a)
 {
     __shared__ uint32_t s_hist[kHistBins];
     __shared__ uint32_t s_valid;
@@ -219,8 +222,13 @@ __global__ __launch_bounds__(kGroupBlock) void group_heads_kernel(GroupDev a)
         atomicAdd(&a.st->n_valid, s_valid);
 }
 
+__global__ __launch_bounds__(kGroupBlock) void group_heads_kernel(GroupDev a)
+{
+    group_heads_body(a);
+}
+
 // digit 2 (key bits 20..10) of the heads whose digit 1 is the k-th head's
-__global__ __launch_bounds__(kGroupBlock) void group_refine_kernel(GroupDev a)
+__device__ inline void group_refine_body(const GroupDev &a)
 {
     __shared__ uint32_t s_hist[kHistBins];
     uint32_t bin1, k2, in_bin;
@@ -245,8 +253,13 @@ __global__ __launch_bounds__(kGroupBlock) void group_refine_kernel(GroupDev a)
     }
 }
 
+__global__ __launch_bounds__(kGroupBlock) void group_refine_kernel(GroupDev a)
+{
+    group_refine_body(a);
+}
+
 template <bool F16>
-__global__ __launch_bounds__(kGroupBlock) void group_collect_kernel(GroupDev a)
+__device__ inline void group_collect_body(const GroupDev &a)
 {
     extern __shared__ __attribute__((aligned(16))) float s_mem[];
     __shared__ uint32_t s_row[kGroupLocalCap];
@@ -315,8 +328,72 @@ __global__ __launch_bounds__(kGroupBlock) void group_collect_kernel(GroupDev a)
     }
 }
 
-// One workgroup: the candidates in exact order, each one's rank inside its group, the accepted ones compacted, the
-// first k and their document ids into `out`, then the completion word.
+template <bool F16>
+__global__ __launch_bounds__(kGroupBlock) void group_collect_kernel(GroupDev a)
+{
+    group_collect_body<F16>(a);
+}
+
+// The body of a finish, one workgroup of 1024 threads over n_raw <= kGroupCap re-scored candidates: the candidates in exact
+// order, each one's rank inside its group, the accepted ones compacted, the first k and their document ids into `out` behind
+// them, then the n_valid | n_out << 32 word.  *s_chk and *s_nacc are zero on entry (set before a barrier the caller need
+// not add: the first one here follows); *s_chk receives the checksum terms of every word written.
+__device__ inline void group_finish_body(const uint64_t *cand, const uint32_t *cand_doc, uint32_t n_raw, uint32_t n_valid, uint32_t k,
+                                         uint32_t per_doc, uint64_t *out, uint64_t *s_pk, uint32_t *s_doc, uint32_t *s_acc,
+                                         uint32_t *s_outdoc, uint32_t *s_chk, uint32_t *s_nacc)
+{
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < n_raw; i += 1024) {
+        s_pk[i] = cand[i];
+        s_doc[i] = cand_doc[i];
+    }
+    for (uint32_t i = tid; i <= kGroupKMax; i += 1024)
+        s_outdoc[i] = 0;
+    __syncthreads();
+    for (uint32_t i = tid; i < n_raw; i += 1024) {
+        const uint64_t mine = s_pk[i];
+        const uint32_t d = s_doc[i];
+        uint32_t ahead = 0;
+        if (d != RLR_DOC_NONE)
+            for (uint32_t j = 0; j < n_raw; ++j)
+                ahead += (s_pk[j] > mine && s_doc[j] == d) ? 1u : 0u;
+        s_acc[i] = ahead < per_doc ? 1u : 0u;
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < n_raw; i += 1024) {
+        if (!s_acc[i])
+            continue;
+        const uint64_t mine = s_pk[i];
+        uint32_t pos = 0;
+        for (uint32_t j = 0; j < n_raw; ++j)
+            pos += (s_acc[j] && s_pk[j] > mine) ? 1u : 0u;
+        atomicAdd(s_nacc, 1u);
+        if (pos < k) {
+            out[pos] = mine;
+            s_outdoc[pos] = s_doc[i];
+            atomicAdd(s_chk, result_chk_term(mine, pos));
+        }
+    }
+    __syncthreads();
+    const uint32_t n_out = min(*s_nacc, k);
+    for (uint32_t i = n_out + tid; i < k; i += 1024)
+        out[i] = 0ull;
+    const uint32_t doc_words = (k + 1) / 2;
+    for (uint32_t w = tid; w < doc_words; w += 1024) {
+        const uint64_t word = static_cast<uint64_t>(s_outdoc[2 * w]) | (static_cast<uint64_t>(s_outdoc[2 * w + 1]) << 32);
+        out[k + w] = word;
+        if (word)
+            atomicAdd(s_chk, result_chk_term(word, k + w));
+    }
+    if (tid == 0) {
+        const uint64_t info = static_cast<uint64_t>(n_valid) | (static_cast<uint64_t>(n_out) << 32);
+        out[k + doc_words] = info;
+        if (info)
+            atomicAdd(s_chk, result_chk_term(info, k + doc_words));
+    }
+}
+
+// One workgroup: group_finish_body over the context's candidates into the pinned block, then the completion word.
 __global__ __launch_bounds__(1024) void group_finish_kernel(GroupDev a)
 {
     __shared__ uint64_t s_pk[kGroupCap];
@@ -337,54 +414,7 @@ __global__ __launch_bounds__(1024) void group_finish_kernel(GroupDev a)
             *a.meta = 0xFFFFFFFFull;
         return;
     }
-    for (uint32_t i = tid; i < n_raw; i += 1024) {
-        s_pk[i] = a.cand[i];
-        s_doc[i] = a.cand_doc[i];
-    }
-    for (uint32_t i = tid; i <= kGroupKMax; i += 1024)
-        s_outdoc[i] = 0;
-    __syncthreads();
-    for (uint32_t i = tid; i < n_raw; i += 1024) {
-        const uint64_t mine = s_pk[i];
-        const uint32_t d = s_doc[i];
-        uint32_t ahead = 0;
-        if (d != RLR_DOC_NONE)
-            for (uint32_t j = 0; j < n_raw; ++j)
-                ahead += (s_pk[j] > mine && s_doc[j] == d) ? 1u : 0u;
-        s_acc[i] = ahead < a.per_doc ? 1u : 0u;
-    }
-    __syncthreads();
-    for (uint32_t i = tid; i < n_raw; i += 1024) {
-        if (!s_acc[i])
-            continue;
-        const uint64_t mine = s_pk[i];
-        uint32_t pos = 0;
-        for (uint32_t j = 0; j < n_raw; ++j)
-            pos += (s_acc[j] && s_pk[j] > mine) ? 1u : 0u;
-        atomicAdd(&s_nacc, 1u);
-        if (pos < a.k) {
-            a.out[pos] = mine;
-            s_outdoc[pos] = s_doc[i];
-            atomicAdd(&s_chk, result_chk_term(mine, pos));
-        }
-    }
-    __syncthreads();
-    const uint32_t n_out = min(s_nacc, a.k);
-    for (uint32_t i = n_out + tid; i < a.k; i += 1024)
-        a.out[i] = 0ull;
-    const uint32_t doc_words = (a.k + 1) / 2;
-    for (uint32_t w = tid; w < doc_words; w += 1024) {
-        const uint64_t word = static_cast<uint64_t>(s_outdoc[2 * w]) | (static_cast<uint64_t>(s_outdoc[2 * w + 1]) << 32);
-        a.out[a.k + w] = word;
-        if (word)
-            atomicAdd(&s_chk, result_chk_term(word, a.k + w));
-    }
-    if (tid == 0) {
-        const uint64_t info = static_cast<uint64_t>(n_valid) | (static_cast<uint64_t>(n_out) << 32);
-        a.out[a.k + doc_words] = info;
-        if (info)
-            atomicAdd(&s_chk, result_chk_term(info, a.k + doc_words));
-    }
+    group_finish_body(a.cand, a.cand_doc, n_raw, n_valid, a.k, a.per_doc, a.out, s_pk, s_doc, s_acc, s_outdoc, &s_chk, &s_nacc);
     __threadfence_system();
     __syncthreads();
     if (tid == 0)
@@ -609,6 +639,199 @@ __global__ __launch_bounds__(kGroupBlock) void group_iota_kernel(uint32_t *__res
         list[i] = i;
 }
 
+// ---- the batched tail (rlr_search_topk_grouped_batch; kernels.h "GroupBatchArgs") -------------------------------------
+// A chunk of 2..8 queries behind ONE shared scan and one set of launches: clear, per_doc rounds, heads, refine, collect,
+// finish.  Per query the arithmetic and the decisions are those of the kernels above.  The document table is where the
+// sharing pays: the allowed rows and the column are the same for every query, so the chunk has ONE key table (inserted
+// once, in round 1, from any query's active row) and a value plane per query.  A round reads a wave's document ids once,
+// works out the runs of equal ids once, probes the table once per lane and then runs the segmented maximum and the guarded
+// atomicMax per query on that query's plane.  A row whose score is NaN for query q (a masked row is NaN for all) has key
+// 0 and is skipped for q only.  Heads, refine and collect take their query from blockIdx.y and run the single-query bodies
+// over that query's slice (group_view); the finish is one workgroup per query.  The rules of the file hold: the table is
+// touched by atomics only inside a launch and by plain loads between launches, no workgroup waits for another, order
+// comes from the order of launches on one stream, integer maxima make the table independent of workgroup order.
+struct GroupBatchDev {
+    uint32_t n_queries;
+    const float *scores;
+    size_t score_stride;
+    const uint32_t *docs;
+    uint32_t n, k, per_doc;
+    float two_eps;
+    uint32_t *tab_keys;
+    uint64_t *tab_vals;
+    uint32_t tab_bits;
+    uint64_t *tg;
+    uint32_t *hist;
+    GroupState *st;
+    const float4 *rows;
+    uint32_t pitch16, dim;
+    const float *queries;
+    uint32_t q_pitch;
+    uint64_t *cand;
+    uint32_t *cand_doc;
+    uint64_t *out;
+    uint32_t out_words; // group_batch_words(k)
+    uint32_t cpb;
+};
+
+// query q's slice of the chunk as the single-query bodies take it (meta / ctx_hist: not used by them)
+__device__ inline GroupDev group_view(const GroupBatchDev &a, uint32_t q)
+{
+    GroupDev d;
+    d.scores = a.scores + static_cast<size_t>(q) * a.score_stride;
+    d.docs = a.docs;
+    d.n = a.n;
+    d.k = a.k;
+    d.per_doc = a.per_doc;
+    d.two_eps = a.two_eps;
+    d.tab_keys = a.tab_keys;
+    d.tab_vals = a.tab_vals + ((static_cast<uint64_t>(q) << a.tab_bits) * a.per_doc);
+    d.tab_bits = a.tab_bits;
+    d.tg = a.tg + static_cast<uint64_t>(q) * a.n;
+    d.hist = a.hist + static_cast<size_t>(q) * 2u * kHistBins;
+    d.st = a.st + q;
+    d.rows = a.rows;
+    d.pitch16 = a.pitch16;
+    d.dim = a.dim;
+    d.query = a.queries + static_cast<size_t>(q) * a.q_pitch;
+    d.cand = a.cand + static_cast<size_t>(q) * kGroupCap;
+    d.cand_doc = a.cand_doc + static_cast<size_t>(q) * kGroupCap;
+    d.out = a.out + static_cast<size_t>(q) * a.out_words;
+    d.meta = nullptr;
+    d.ctx_hist = nullptr;
+    d.cpb = a.cpb;
+    return d;
+}
+
+__global__ __launch_bounds__(kGroupBlock) void group_clear_multi_kernel(GroupBatchDev a)
+{
+    const uint32_t stride = gridDim.x * kGroupBlock, t0 = blockIdx.x * kGroupBlock + threadIdx.x;
+    const uint32_t slots = a.docs ? 1u << a.tab_bits : 0u;
+    for (uint32_t i = t0; i < slots; i += stride)
+        a.tab_keys[i] = RLR_DOC_NONE;
+    const uint64_t n_vals = static_cast<uint64_t>(slots) * a.per_doc * a.n_queries;
+    for (uint64_t i = t0; i < n_vals; i += stride)
+        a.tab_vals[i] = 0ull;
+    for (uint32_t i = t0; i < a.n_queries * 2u * kHistBins; i += stride)
+        a.hist[i] = 0u;
+    if (t0 < a.n_queries) {
+        a.st[t0].n_cand = 0;
+        a.st[t0].n_valid = 0;
+        a.st[t0].flags = 0;
+        a.st[t0].u_bits = 0;
+    }
+}
+
+// Round j (0-based) for every query of the chunk: plane q's tab_vals[slot][j] = the largest packed key of the slot's
+// document below its tab_vals[slot][j - 1], by query q's scores.  group_round_kernel's wave walk; what does not depend on
+// the query is done once per wave: the document ids, which lanes below share a lane's id (`same`, bit d for distance d),
+// the run's last lane, and the lane's slot (looked up, or claimed in round 1, when the first query needs it).
+template <bool FIRST>
+__global__ __launch_bounds__(kGroupBlock) void group_round_multi_kernel(GroupBatchDev a, uint32_t j)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t n_words = a.n / 64 + ((a.n & 63) != 0 ? 1u : 0u);
+    const uint32_t waves = gridDim.x * (kGroupBlock / 64);
+    const uint64_t plane = (1ull << a.tab_bits) * a.per_doc;
+    for (uint64_t w = blockIdx.x * (kGroupBlock / 64) + (threadIdx.x >> 6); w < n_words; w += waves) { // (wave-uniform)
+        const uint64_t row = w * 64 + lane;
+        const bool in = row < a.n;
+        const uint32_t id = in ? a.docs[row] : RLR_DOC_NONE;
+        uint32_t same = 0;
+#pragma unroll
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const uint32_t oid = __shfl_up(id, d, 64);
+            if (lane >= d && oid == id)
+                same |= d;
+        }
+        const uint32_t next_id = __shfl_down(id, 1, 64);
+        const bool tail = (lane == 63 || next_id != id) && id != RLR_DOC_NONE;
+        uint32_t slot = kNoSlot;
+        bool probed = false;
+        for (uint32_t q = 0; q < a.n_queries; ++q) { // (uniform: every lane takes every shuffle)
+            const uint32_t key = in ? score_key(a.scores[static_cast<size_t>(q) * a.score_stride + row]) : 0u;
+            const bool act = id != RLR_DOC_NONE && key != 0u;
+            uint64_t v = act ? (static_cast<uint64_t>(key) << 32) | (0xFFFFFFFFu - static_cast<uint32_t>(row)) : 0ull;
+            uint64_t *vals = a.tab_vals + q * plane;
+            if (!FIRST && act) {
+                if (!probed) {
+                    slot = group_find(a.tab_keys, a.tab_bits, id);
+                    probed = true;
+                }
+                const uint64_t bound = slot != kNoSlot ? vals[static_cast<uint64_t>(slot) * a.per_doc + j - 1] : 0ull;
+                if (!(v < bound))
+                    v = 0ull; // taken by an earlier round (or the document has no slot: the table overflowed, flagged)
+            }
+#pragma unroll
+            for (uint32_t d = 1; d < 64; d <<= 1) {
+                const uint64_t ov = shfl_up_u64(v, d);
+                if ((same & d) != 0u && ov > v)
+                    v = ov;
+            }
+            if (tail && v != 0ull) {
+                if (!probed) {
+                    slot = FIRST ? group_insert(a.tab_keys, a.tab_bits, id) : group_find(a.tab_keys, a.tab_bits, id);
+                    probed = true;
+                }
+                if (slot != kNoSlot) {
+                    // (the guard of group_round_kernel: a key at or below what a load sees cannot be the maximum)
+                    unsigned long long *p = reinterpret_cast<unsigned long long *>(&vals[static_cast<uint64_t>(slot) * a.per_doc + j]);
+                    if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < v)
+                        atomicMax(p, static_cast<unsigned long long>(v));
+                } else {
+                    atomicOr(&a.st[q].flags, 2u);
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kGroupBlock) void group_heads_multi_kernel(GroupBatchDev a)
+{
+    group_heads_body(group_view(a, blockIdx.y));
+}
+
+__global__ __launch_bounds__(kGroupBlock) void group_refine_multi_kernel(GroupBatchDev a)
+{
+    group_refine_body(group_view(a, blockIdx.y));
+}
+
+template <bool F16>
+__global__ __launch_bounds__(kGroupBlock) void group_collect_multi_kernel(GroupBatchDev a)
+{
+    group_collect_body<F16>(group_view(a, blockIdx.y));
+}
+
+// One workgroup per query: group_finish_body into the query's slice of the device result block, then its status word.
+// (c->d_hist is not touched: the shared scans run without a histogram.)
+__global__ __launch_bounds__(1024) void group_finish_multi_kernel(GroupBatchDev a)
+{
+    __shared__ uint64_t s_pk[kGroupCap];
+    __shared__ uint32_t s_doc[kGroupCap];
+    __shared__ uint32_t s_acc[kGroupCap];
+    __shared__ uint32_t s_outdoc[kGroupKMax + 1];
+    __shared__ uint32_t s_chk, s_nacc;
+    const uint32_t tid = threadIdx.x, q = blockIdx.x;
+    const GroupState *st = a.st + q;
+    uint64_t *out = a.out + static_cast<size_t>(q) * a.out_words;
+    const uint32_t n_raw = st->n_cand, flags = st->flags, n_valid = st->n_valid;
+    if (tid == 0) {
+        s_chk = 0;
+        s_nacc = 0;
+    }
+    if (flags != 0 || n_raw > kGroupCap) { // (uniform) the host hands the query to the single-query path
+        for (uint32_t i = tid; i + 1 < a.out_words; i += 1024)
+            out[i] = 0ull;
+        if (tid == 0)
+            out[a.out_words - 1] = kGroupBatchBack;
+        return;
+    }
+    group_finish_body(a.cand + static_cast<size_t>(q) * kGroupCap, a.cand_doc + static_cast<size_t>(q) * kGroupCap, n_raw, n_valid, a.k,
+                      a.per_doc, out, s_pk, s_doc, s_acc, s_outdoc, &s_chk, &s_nacc);
+    if (tid == 0)
+        out[a.out_words - 1] = n_raw;
+}
+
 } // namespace
 
 // the staging of collect's re-score: the query and cpb rows of products (tail.hip's layout, under what is left of the
@@ -697,6 +920,66 @@ hipError_t launch_group_tail(const GroupArgs &a, hipStream_t s, hipEvent_t after
         hipLaunchKernelGGL(capped_finish_kernel, dim3(1), dim3(1024), 0, s, d, *a.capped);
     else
         hipLaunchKernelGGL(group_finish_kernel, dim3(1), dim3(1024), 0, s, d);
+    return hipGetLastError();
+}
+
+hipError_t launch_group_batch_tail(const GroupBatchArgs &a, hipStream_t s)
+{
+    uint32_t cpb;
+    size_t staging;
+    if (a.n == 0 || a.n_queries < 2 || a.n_queries > 8 || a.k == 0 || a.k > kGroupKMax || a.per_doc == 0 ||
+        a.per_doc > RLR_MAX_PER_DOCUMENT || a.tab_bits < 1 || a.tab_bits > 31 || a.score_stride < a.n || !a.scores || !a.out ||
+        !group_shape(a.pitch16, a.dim, a.dtype, &cpb, &staging))
+        return hipErrorInvalidValue;
+    GroupBatchDev d;
+    d.n_queries = a.n_queries;
+    d.scores = a.scores;
+    d.score_stride = a.score_stride;
+    d.docs = a.docs;
+    d.n = a.n;
+    d.k = a.k;
+    d.per_doc = a.per_doc;
+    d.two_eps = a.two_eps;
+    d.tab_keys = a.tab_keys;
+    d.tab_vals = a.tab_vals;
+    d.tab_bits = a.tab_bits;
+    d.tg = a.tg;
+    d.hist = a.hist;
+    d.st = a.st;
+    d.rows = static_cast<const float4 *>(a.rows);
+    d.pitch16 = a.pitch16;
+    d.dim = a.dim;
+    d.queries = a.queries;
+    d.q_pitch = a.q_pitch;
+    d.cand = a.cand;
+    d.cand_doc = a.cand_doc;
+    d.out = a.out;
+    d.out_words = group_batch_words(a.k);
+    d.cpb = cpb;
+    // the launch shapes of launch_group_tail; heads, refine and collect with the query in the grid's y
+    const uint32_t max_blocks = static_cast<uint32_t>(std::max(a.n_cu, 1)) * 8;
+    const uint32_t row_blocks = std::max<uint32_t>(1, std::min<uint32_t>((a.n + kGroupBlock - 1) / kGroupBlock, max_blocks));
+    const uint64_t slots = a.docs ? 1ull << a.tab_bits : 0ull;
+    const uint32_t clear_blocks = static_cast<uint32_t>(std::max<uint64_t>(
+        a.n_queries * 2u * kHistBins / kGroupBlock, std::min<uint64_t>((slots * a.per_doc * a.n_queries + kGroupBlock - 1) / kGroupBlock, max_blocks)));
+    hipLaunchKernelGGL(group_clear_multi_kernel, dim3(clear_blocks), dim3(kGroupBlock), 0, s, d);
+    if (a.docs) {
+        hipLaunchKernelGGL(group_round_multi_kernel<true>, dim3(row_blocks), dim3(kGroupBlock), 0, s, d, 0u);
+        for (uint32_t j = 1; j < a.per_doc; ++j)
+            hipLaunchKernelGGL(group_round_multi_kernel<false>, dim3(row_blocks), dim3(kGroupBlock), 0, s, d, j);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(group_heads_multi_kernel, dim3(row_blocks, a.n_queries), dim3(kGroupBlock), 0, s, d);
+    hipLaunchKernelGGL(group_refine_multi_kernel, dim3(row_blocks, a.n_queries), dim3(kGroupBlock), 0, s, d);
+    const uint32_t collect_blocks =
+        std::max<uint32_t>(1, std::min<uint32_t>(std::max<uint32_t>(row_blocks, (a.n + 31) / 32), max_blocks));
+    if (a.dtype == RLR_F16)
+        hipLaunchKernelGGL(group_collect_multi_kernel<true>, dim3(collect_blocks, a.n_queries), dim3(kGroupBlock), staging, s, d);
+    else
+        hipLaunchKernelGGL(group_collect_multi_kernel<false>, dim3(collect_blocks, a.n_queries), dim3(kGroupBlock), staging, s, d);
+    hipLaunchKernelGGL(group_finish_multi_kernel, dim3(a.n_queries), dim3(1024), 0, s, d);
     return hipGetLastError();
 }
 

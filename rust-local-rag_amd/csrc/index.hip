@@ -1886,6 +1886,160 @@ int32_t grouped_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *q
     return note_search(ix, c, 1, n_cand, form != 0 ? 1 : 0, timed && form != 3);
 }
 
+// ---- batched grouped search (rlr_search_topk_grouped_batch): the queries of a call share passes over the rows ----------
+// The chunk width: the largest w in 2..8 whose workspace -- the key table (4 B a slot), w value planes (8 B x per_doc a
+// slot), w t_g arrays (8 B a row) and w score arrays (4 B a row) -- stays at or below the bytes of the index's rows, so the
+// state of a search is never larger than what it searches; 0: none fits.
+uint32_t grouped_chunk_width(const rlr_index *ix, uint64_t n_allowed, uint32_t per_doc)
+{
+    const uint64_t n = ix->n_rows, s_stride = (n + 3) / 4 * 4, slots = 1ull << group_table_bits(n_allowed);
+    const uint64_t budget = n * row_bytes(ix);
+    for (uint64_t w = 8; w >= 2; --w)
+        if (4 * slots + w * (8 * per_doc * slots + 8 * n + 4 * s_stride) <= budget)
+            return static_cast<uint32_t>(w);
+    return 0;
+}
+
+// The gate (rlr_index_set_grouped_sharing mode 0): does a chunk of nq queries through one shared scan and one set of tail
+// launches beat the same queries one by one by 10 %?  A cost model in the style of range_share_wins:
+//   one by one   per query 77 us (its launches and its own synchronisation) + 2 us per round + the ALLOWED bytes at
+//                7.3 TB/s + per row 25 ps and 9.5 ps per round (the tail's passes over the score array, t_g, the ids)
+//   shared       80 us (one copy, one synchronisation, one set of launches) + 13 us per query (its collect and finish
+//                workgroups) + the allowed bytes at the rate of the Q = 2 / 4 / 8 instance of the shared scan (6.45 / 6.1 /
+//                5.8 TB/s) + per row and query 20 ps and 10 ps per round
+// The fixed costs and the per-row terms are fitted to tools/bench_grouped_batch.py's cells at 100 k and 1 M rows of 768 f32
+// elements (profiles/grouped_batch_bench.json; DESIGN.md "Batched grouped top-k" has the table, the fit and what was NOT
+// measured); the four scan rates are the range gate's, borrowed: the cells agree with them but do not separate them from
+// the per-row terms.  No measured cell lost with sharing forced, and this model declines none of them.
+bool grouped_share_wins(const rlr_index *ix, const rlr_filter *f, uint32_t nq, uint32_t per_doc)
+{
+    const double el = ix->dtype == RLR_F16 ? 2.0 : 4.0;
+    const double n = static_cast<double>(ix->n_rows), allowed = static_cast<double>(f ? f->n_allowed : ix->n_rows);
+    const double rounds = ix->d_docs ? per_doc : 0.0;
+    const double t_single = nq * (77e-6 + rounds * 2e-6 + allowed * ix->dim * el / 7.3e12 + n * (25e-12 + rounds * 9.5e-12));
+    const double rate = nq <= 2 ? 6.45e12 : nq <= 4 ? 6.1e12 : 5.8e12;
+    const double t_shared = 80e-6 + nq * 13e-6 + allowed * ix->dim * el / rate + nq * n * (20e-12 + rounds * 10e-12);
+    return t_single > 1.1 * t_shared;
+}
+
+// One chunk of m (2..8) queries through ONE shared scan and group.hip's batched tail: the queries staged and uploaded
+// once, the scan, one set of tail launches, ONE copy of the chunk's result words and one synchronisation.  The band is the
+// plan's f32 band, exactly as in grouped_query; the plan is the chunk's (the largest query norm): a band wider than a
+// query's own only adds candidates, the order is decided on the reference-order score.  forms[q]: 0 decided on the device;
+// 1 handed back on a capacity (more than kGroupCap candidates, a local list or the table overflowed); 2 handed back because
+// the answer is short while allowed rows with NaN nominations exist, a masked row came back, or the chunk's workspace
+// could not be reserved.  A handed-back query is answered by grouped_query on the same context, after every decided
+// query has been read out of the pinned block (grouped_query stages into it again); its neighbours stay decided.
+// c->d_hist is not touched: the shared scans run without a histogram.
+int32_t grouped_batch_chunk(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *queries, uint32_t m, uint32_t k, uint32_t per_doc,
+                            float guard_eps, uint64_t *rows_out, float *cos_out, uint32_t *docs_out, uint32_t *n_out, uint32_t *forms)
+{
+    const uint64_t n_allowed = f ? f->n_allowed : ix->n_rows;
+    const uint32_t n = static_cast<uint32_t>(ix->n_rows);
+    const SearchPlan p = make_plan(ix, queries, m, static_cast<uint32_t>(std::min<uint64_t>(k, n_allowed)), guard_eps);
+    RLR_TRY(ctx_prepare(ix, c, m, p));
+    const uint32_t words = group_batch_words(p.k), res_words = group_out_words(p.k);
+    const size_t n_res = static_cast<size_t>(m) * words;
+    Staged pin;
+    RLR_TRY(stage_call(ix, c, queries, m, n_res, /*for_scans=*/false, &pin));
+    uint64_t *h_res = pin.h_res;
+    hipStream_t s = c->stream;
+    const uint32_t tab_bits = group_table_bits(n_allowed);
+    const size_t slots = static_cast<size_t>(1) << tab_bits;
+    const uint64_t s_stride = (static_cast<uint64_t>(n) + 3) / 4 * 4;
+    std::vector<uint32_t> redo;
+    uint64_t cand_total = 0;
+    // the chunk's workspace: the single-query buffers, a slice per query (and ONE key table)
+    hipError_t e = hipSuccess;
+    if (ix->d_docs)
+        e = reserve_group(Want{c->d_gkeys, slots}, Want{c->d_gvals, slots * per_doc * m});
+    if (e == hipSuccess)
+        e = c->d_gtg.reserve(std::max<uint64_t>(static_cast<uint64_t>(m) * n, 1024));
+    if (e == hipSuccess)
+        e = reserve_group(Want{c->d_ghist, static_cast<size_t>(m) * 2 * kHistBins}, Want{c->d_gstate, m},
+                          Want{c->d_gcand, static_cast<size_t>(m) * kGroupCap}, Want{c->d_gcdoc, static_cast<size_t>(m) * kGroupCap});
+    if (e == hipSuccess)
+        e = c->d_gout.reserve(n_res);
+    if (e == hipSuccess)
+        e = c->d_sample.reserve(static_cast<uint64_t>(m) * s_stride);
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError(); // no error of the call: the queries go one by one, in the single path's smaller workspace
+        for (uint32_t q = 0; q < m; ++q) {
+            forms[q] = 2;
+            redo.push_back(q);
+        }
+    } else {
+        RLR_HIP(e);
+        const ScanArgs sa = scan_args(ix, c->d_query.get(), c->d_sample.get(), nullptr);
+        if (!(f ? launch_scan_masked_multi(sa, f->d_mask.get(), f->n_allowed, ix->q_pitch, m, s_stride, s, &e)
+                : launch_scan_multi(sa, ix->q_pitch, m, s_stride, s, &e)))
+            return set_error(RLR_E_INTERNAL, "multi-query scan refused a shape the grouped gate accepted");
+        RLR_HIP(e);
+        GroupBatchArgs ga{};
+        ga.n_queries = m;
+        ga.scores = c->d_sample.get();
+        ga.score_stride = s_stride;
+        ga.docs = ix->d_docs.get();
+        ga.n = n;
+        ga.k = p.k;
+        ga.per_doc = per_doc;
+        ga.two_eps = p.two_eps;
+        ga.tab_keys = c->d_gkeys.get();
+        ga.tab_vals = c->d_gvals.get();
+        ga.tab_bits = tab_bits;
+        ga.tg = c->d_gtg.get();
+        ga.hist = c->d_ghist.get();
+        ga.st = c->d_gstate.get();
+        ga.rows = ix->d_rows.get();
+        ga.pitch16 = ix->pitch16;
+        ga.dim = ix->dim;
+        ga.dtype = ix->dtype;
+        ga.queries = c->d_query.get();
+        ga.q_pitch = ix->q_pitch;
+        ga.cand = c->d_gcand.get();
+        ga.cand_doc = c->d_gcdoc.get();
+        ga.out = c->d_gout.get();
+        ga.n_cu = ix->n_cu;
+        RLR_HIP(launch_group_batch_tail(ga, s));
+        RLR_HIP(hipMemcpyAsync(h_res, c->d_gout.get(), n_res * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        RLR_HIP(hipStreamSynchronize(s));
+        for (uint32_t q = 0; q < m; ++q) {
+            const uint64_t *r = h_res + static_cast<size_t>(q) * words;
+            const uint64_t status = r[words - 1], info = r[res_words - 1];
+            const uint32_t n_res_q = static_cast<uint32_t>(info >> 32), n_valid = static_cast<uint32_t>(info);
+            if (status > kGroupCap)
+                forms[q] = 1;
+            else if ((n_res_q < p.k && n_valid < n_allowed) || masked_row_among(f, r, n_res_q))
+                forms[q] = 2;
+            else
+                forms[q] = 0;
+            if (forms[q] != 0) {
+                redo.push_back(q);
+                continue;
+            }
+            cand_total += status;
+            n_out[q] = n_res_q;
+            unpack_results(r, n_res_q, rows_out + static_cast<size_t>(q) * k, cos_out + static_cast<size_t>(q) * k);
+            if (docs_out)
+                std::memcpy(docs_out + static_cast<size_t>(q) * k, r + p.k, static_cast<size_t>(n_res_q) * sizeof(uint32_t));
+        }
+    }
+    c->hist_dirty = false;
+    {
+        std::lock_guard<std::mutex> lk(ix->mu);
+        ix->prof.n_batches += 1;
+        ix->prof.n_batch_queries += m;
+        ix->prof.n_batch_fallbacks += redo.size();
+    }
+    RLR_TRY(note_search(ix, c, m - static_cast<uint32_t>(redo.size()), cand_total, 0, /*timed=*/false));
+    // (from here on the pinned block and the context are grouped_query's)
+    for (uint32_t q : redo)
+        RLR_TRY(grouped_query(ix, c, f, queries + static_cast<size_t>(q) * ix->dim, k, per_doc, guard_eps,
+                              rows_out + static_cast<size_t>(q) * k, cos_out + static_cast<size_t>(q) * k,
+                              docs_out ? docs_out + static_cast<size_t>(q) * k : nullptr, &n_out[q]));
+    return RLR_OK;
+}
+
 // ---- range search (rlr_search_range): every allowed row scoring at or above a threshold ---------------------------------
 // The exact form: reference-order scores of every allowed row, copied back; threshold, count and order on the host.  Slow
 // and always right.  The query is in c->d_query.  keys: the first min(n_total, cap) hits in result order.
@@ -3296,6 +3450,82 @@ int32_t rlr_search_topk_grouped(rlr_index *ix, const rlr_filter *f, const float 
 int32_t rlr_index_grouped_forms(rlr_index *ix, uint64_t counts[4], int32_t reset)
 {
     return read_forms(ix, &rlr_index::grouped_forms, counts, reset);
+}
+
+int32_t rlr_search_topk_grouped_batch(rlr_index *ix, const rlr_filter *f, const float *queries, uint32_t n_queries, uint32_t k,
+                                      uint32_t per_doc, float guard_eps, uint64_t *rows_out, float *cos_out, uint32_t *docs_out,
+                                      uint32_t *n_out)
+{
+    RLR_TRY(check_handle(ix));
+    if (f)
+        RLR_TRY(check_filter(ix, f)); // (a stale filter is refused before any GPU work)
+    if (k == 0 || per_doc < 1 || per_doc > RLR_MAX_PER_DOCUMENT)
+        return set_error(RLR_E_INVALID, "k must be positive and per_doc in 1..%d (k = %u, per_doc = %u)", RLR_MAX_PER_DOCUMENT, k, per_doc);
+    if (n_queries && (!queries || !n_out || !rows_out || !cos_out))
+        return set_error(RLR_E_INVALID, "queries / n_out / output buffers are null");
+    RLR_TRY(use_device(ix));
+    for (uint32_t q = 0; q < n_queries; ++q)
+        n_out[q] = 0;
+    const uint64_t n_allowed = f ? f->n_allowed : ix->n_rows;
+    if (n_allowed == 0 || n_queries == 0)
+        return RLR_OK;
+    CtxLease lease(ix);
+    RLR_TRY(ctx_acquire(ix, &lease.c));
+    StreamDrain drain{lease.c->stream};
+    // The chunk width w, 0 by rule: one query, mode 1, a list-path filter, k beyond the finish, rows the staged re-score or
+    // the shared scans do not serve, no width of two within the workspace rule, the gate declined.  Then the queries are
+    // split evenly over ceil(n_queries / w) chunks (9 -> 5 + 4); a chunk of one goes by rule as well.
+    const int32_t mode = ix->grouped_sharing.load();
+    uint32_t w = 0;
+    if (mode != 1 && n_queries >= 2 && !(f && f->path == 0) && std::min<uint64_t>(k, n_allowed) <= kGroupKMax &&
+        group_table_bits(n_allowed) <= 31 && group_fits(ix->pitch16, ix->dim, ix->dtype) && batch_multi_shape(ix, 2) &&
+        ix->n_rows <= 0xFFFFFFFFull) {
+        w = std::min(grouped_chunk_width(ix, n_allowed, per_doc), n_queries);
+        if (w >= 2 && mode == 0 && !grouped_share_wins(ix, f, w, per_doc))
+            w = 0;
+    }
+    const uint32_t n_chunks = w >= 2 ? (n_queries + w - 1) / w : 0;
+    uint64_t forms[4] = {0, 0, 0, 0};
+    uint32_t chunk_forms[8];
+    int32_t rc = RLR_OK;
+    for (uint32_t q0 = 0, ci = 0; q0 < n_queries && rc == RLR_OK; ++ci) {
+        const uint32_t m = n_chunks ? n_queries / n_chunks + (ci < n_queries % n_chunks ? 1u : 0u) : 1u;
+        const float *qs = queries + static_cast<size_t>(q0) * ix->dim;
+        uint64_t *ro = rows_out + static_cast<size_t>(q0) * k;
+        float *co = cos_out + static_cast<size_t>(q0) * k;
+        uint32_t *dout = docs_out ? docs_out + static_cast<size_t>(q0) * k : nullptr;
+        if (m < 2) {
+            rc = grouped_query(ix, lease.c, f, qs, k, per_doc, guard_eps, ro, co, dout, &n_out[q0]);
+            forms[3]++;
+        } else {
+            rc = grouped_batch_chunk(ix, lease.c, f, qs, m, k, per_doc, guard_eps, ro, co, dout, n_out + q0, chunk_forms);
+            for (uint32_t i = 0; i < m && rc == RLR_OK; ++i)
+                forms[chunk_forms[i]]++;
+        }
+        q0 += m;
+    }
+    {
+        std::lock_guard<std::mutex> lk(ix->mu);
+        for (int i = 0; i < 4; ++i)
+            ix->grouped_batch_forms[i] += forms[i];
+    }
+    RLR_TRY(rc);
+    drain.armed = false;
+    return RLR_OK;
+}
+
+int32_t rlr_index_set_grouped_sharing(rlr_index *ix, int32_t mode)
+{
+    RLR_TRY(check_handle(ix));
+    if (mode < 0 || mode > 2)
+        return set_error(RLR_E_INVALID, "grouped sharing mode %d (0 the gate, 1 never, 2 wherever the shape allows)", mode);
+    ix->grouped_sharing.store(mode);
+    return RLR_OK;
+}
+
+int32_t rlr_index_grouped_batch_forms(rlr_index *ix, uint64_t counts[4], int32_t reset)
+{
+    return read_forms(ix, &rlr_index::grouped_batch_forms, counts, reset);
 }
 
 int32_t rlr_search_range(rlr_index *ix, const rlr_filter *f, const float *queries, uint32_t n_queries, const float *tau, uint32_t cap,

@@ -95,6 +95,7 @@ struct Ctx {
     DevBuf<GroupState> d_gstate;
     DevBuf<uint64_t> d_gcand;      // kGroupCap
     DevBuf<uint32_t> d_gcdoc;      // kGroupCap
+    DevBuf<uint64_t> d_gout;       // batched grouped search (grouped_batch_chunk): the chunk's result words; the buffers above hold a slice per query
     // range search (range.hip), grown lazily: the two counters and the unordered exact keys of the hits
     DevBuf<RangeState> d_rstate;   // with d_rhits
     DevBuf<uint64_t> d_rhits;      // min(cap, RLR_RANGE_DEVICE_MAX) of the largest call so far
@@ -200,6 +201,8 @@ struct rlr_index {
     uint64_t range_forms[4] = {0, 0, 0, 0};   // rlr_index_range_forms: the same for rlr_search_range (mu)
     uint64_t range_batch_forms[4] = {0, 0, 0, 0}; // rlr_index_range_batch_forms: the same for rlr_search_range_batch (mu)
     std::atomic<int32_t> range_sharing{0};    // rlr_index_set_range_sharing: 0 auto (the cost model), 1 never, 2 wherever the shape allows
+    uint64_t grouped_batch_forms[4] = {0, 0, 0, 0}; // rlr_index_grouped_batch_forms: queries of rlr_search_topk_grouped_batch by form (mu)
+    std::atomic<int32_t> grouped_sharing{0};  // rlr_index_set_grouped_sharing: 0 the gate (grouped_share_wins), 1 never, 2 wherever the shape allows
 };
 
 // A set of rows of one index, fixed at creation (rlr_filter_create_*): one bit per index row on the device (tail bits of

@@ -318,6 +318,41 @@ hipError_t launch_group_iota(uint32_t *list, uint32_t n, hipStream_t s); // list
 // the LDS staging of a workgroup's re-score (at most 56 KB): candidates per pass and the dynamic LDS bytes; false: too wide
 bool group_shape(uint32_t pitch16, uint32_t dim, int dtype, uint32_t *cpb_out, size_t *staging_out);
 
+// The tail of a BATCHED grouped search (rlr_search_topk_grouped_batch): a chunk of n_queries (2..8) queries whose nominated
+// scores came from ONE shared scan, one score array per query, score_stride apart.  One set of launches serves the chunk.
+// The allowed rows and the document column are the same for every query, so the chunk has ONE key table; everything else
+// is per query: value plane q at tab_vals + q * slots * per_doc, t_g at tg + q * n, the two histograms at
+// hist + q * 2 * kHistBins, st[q], kGroupCap candidate slots at cand + q * kGroupCap, and group_batch_words(k) words of `out`
+// (device memory; one copy brings the whole chunk back):
+//   group_out_words(k) words as GroupArgs::out has them | status: the candidate count, or kGroupBatchBack when the finish
+//   could not decide (more than kGroupCap candidates, a local list or the table overflowed)
+constexpr uint64_t kGroupBatchBack = 0xFFFFFFFFull;
+struct GroupBatchArgs {
+    uint32_t n_queries;
+    const float *scores;  // n_queries x score_stride nominated scores (NaN: masked, or a NaN nomination)
+    size_t score_stride;
+    const uint32_t *docs; // n document ids, or null: no column
+    uint32_t n, k, per_doc;
+    float two_eps;
+    uint32_t *tab_keys;   // 1 << tab_bits document ids, shared by the chunk
+    uint64_t *tab_vals;   // n_queries planes of (1 << tab_bits) x per_doc packed keys
+    uint32_t tab_bits;
+    uint64_t *tg;         // n_queries x n
+    uint32_t *hist;       // n_queries x 2 * kHistBins
+    GroupState *st;       // n_queries
+    const void *rows;
+    uint32_t pitch16, dim;
+    int dtype;
+    const float *queries; // device, q_pitch floats each
+    uint32_t q_pitch;
+    uint64_t *cand;       // n_queries x kGroupCap
+    uint32_t *cand_doc;
+    uint64_t *out;        // n_queries x group_batch_words(k)
+    int n_cu;
+};
+inline uint32_t group_batch_words(uint32_t k) { return group_out_words(k) + 1; }
+hipError_t launch_group_batch_tail(const GroupBatchArgs &a, hipStream_t s);
+
 // ---- range.hip : the tail of a range search (every row scoring at or above a threshold), behind the scan ----
 constexpr uint32_t kRangeFinishMax = 2048; // hits the one-workgroup finish orders and emits
 struct RangeState {

@@ -663,6 +663,24 @@ class RagEngine:
         per document, keyed by document name."""
         return [(r.document, r) for r in self.search_per_document(query_embedding, top_k, 1, documents)]
 
+    def search_per_document_batch(self, query_embeddings, top_k: int, per_document: int = 1,
+                                  documents: Optional[Sequence[str]] = None) -> List[List[SearchResult]]:
+        """search_per_document for every row of `query_embeddings` through one search_topk_grouped_batch call: the rows
+        are read once per shared pass, not once per query.  Per query exactly what search_per_document returns."""
+        emb = _f32(query_embeddings).reshape(-1, self.dim)
+        if top_k <= 0 or len(self._chunks) == 0 or emb.shape[0] == 0:
+            return [[] for _ in range(emb.shape[0])]
+        self._sync_documents()
+        f = self._filter_for(documents) if documents is not None else None
+        q = np.stack([normalize(e) for e in emb])
+        res = self.index.search_topk_grouped_batch(q, top_k, per_document, filter=f)
+        return [self._embedding_results(rows, cos) for rows, cos, _ in res]
+
+    def rank_documents_batch(self, query_embeddings, top_k: int,
+                             documents: Optional[Sequence[str]] = None) -> List[List[Tuple[str, SearchResult]]]:
+        """rank_documents for every row of `query_embeddings`, the queries sharing passes over the rows"""
+        return [[(r.document, r) for r in res] for res in self.search_per_document_batch(query_embeddings, top_k, 1, documents)]
+
     # -- every chunk at or above a cosine, and how many (rlr_search_range; no reference site) ---------------
     def _embedding_results(self, rows, cos) -> List[SearchResult]:
         out = []

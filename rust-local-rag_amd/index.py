@@ -298,6 +298,34 @@ class GpuIndex:
         N.check(self._L.rlr_index_grouped_forms(self._h, _up(counts), int(reset)))
         return [int(c) for c in counts]
 
+    def search_topk_grouped_batch(self, queries, k: int, per_document: int = 1, filter: "RowFilter | None" = None,
+                                  guard_eps: float = -1.0):
+        """search_topk_grouped with the queries of the call sharing passes over the rows (rlr_search_topk_grouped_batch):
+        the same arguments, the same list of (rows u64, cos f32, docs u32) per query, bit for bit -- chunks of up to 8
+        queries share one scan and one document table (set_grouped_sharing, grouped_batch_forms)"""
+        q = _f32(queries).reshape(-1, self.dim)
+        nq = q.shape[0]
+        rows = np.zeros((nq, max(k, 1)), dtype=np.uint64)
+        cos = np.zeros((nq, max(k, 1)), dtype=np.float32)
+        docs = np.zeros((nq, max(k, 1)), dtype=np.uint32)
+        n_out = np.zeros(max(nq, 1), dtype=np.uint32)
+        N.check(self._L.rlr_search_topk_grouped_batch(self._h, None if filter is None else filter.handle, _fp(q), nq, k,
+                                                      per_document, guard_eps, _up(rows), _fp(cos), _u32ptr(docs), _u32ptr(n_out)))
+        return [(rows[i, :int(n_out[i])], cos[i, :int(n_out[i])], docs[i, :int(n_out[i])]) for i in range(nq)]
+
+    def set_grouped_sharing(self, mode: int) -> None:
+        """when search_topk_grouped_batch shares a pass: 0 where the cost model expects it to win (the default), 1 never,
+        2 wherever the shape allows (rlr_index_set_grouped_sharing); the answers do not depend on it"""
+        N.check(self._L.rlr_index_set_grouped_sharing(self._h, int(mode)))
+
+    def grouped_batch_forms(self, reset: bool = False) -> list:
+        """queries search_topk_grouped_batch served by each form: [selected on the device behind a shared scan, handed to
+        the single-query path on a capacity, handed to it because NaN nominations were needed / a masked row came back /
+        the workspace could not be reserved, handed to it by rule] (rlr_index_grouped_batch_forms)"""
+        counts = np.zeros(4, dtype=np.uint64)
+        N.check(self._L.rlr_index_grouped_batch_forms(self._h, _up(counts), int(reset)))
+        return [int(c) for c in counts]
+
     def search_range(self, queries, tau, cap: int, filter: "RowFilter | None" = None, guard_eps: float = -1.0):
         """every row whose reference-order score is at least tau (rlr_search_range).  queries: [Q, dim] (or [dim]) already
         normalised, tau: one threshold or one per query -> a list of (rows u64, cos f32, n_total) per query: the first
