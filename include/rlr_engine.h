@@ -170,6 +170,27 @@ int32_t rlr_engine_search_text_capped(rlr_index *idx, rlr_lexical *lex, const rl
                                       uint32_t dq, const char *query_tokens, size_t tokens_len, uint32_t top_k,
                                       float diversity_factor, int32_t stage, const rlr_query_weights *weights,
                                       uint32_t per_doc, rlr_search_hit *out, uint32_t cap, uint32_t *n_out);
+/* rlr_engine_search_capped for n_queries requests that share top_k, diversity_factor, stage, the weights, per_doc and
+ * the filter: every query is prepared as that entry prepares it and the selection is ONE rlr_search_capped_batch
+ * (include/rlr_gpu.h), so per query the hits carry the bits of the single entry.  Query q is queries_raw + q * dq; its
+ * caller-computed pairs are lex_rows / lex_scores [lex_offsets[q], lex_offsets[q + 1]) (n_queries + 1 non-decreasing
+ * offsets).  Hits of query q start at out[q * cap], their count is n_out[q]; cap must hold a query's largest result.
+ * Argument and error rules as for rlr_engine_search_capped. */
+int32_t rlr_engine_search_capped_batch(rlr_index *idx, const rlr_filter *f, const float *queries_raw, uint32_t dq,
+                                       uint32_t n_queries, uint32_t top_k, float diversity_factor, int32_t stage,
+                                       const rlr_query_weights *weights, const uint64_t *lex_rows, const float *lex_scores,
+                                       const uint64_t *lex_offsets, uint32_t per_doc, rlr_search_hit *out, uint32_t cap,
+                                       uint32_t *n_out);
+/* The same from query text, laid out as rlr_engine_search_text_batch takes it (a token blob and n_queries + 1 offsets):
+ * ONE rlr_lexical_score_batch (rlr_lexical_score_batch_filtered with a filter) with the limit
+ * rlr_engine_search_text_capped uses, then the capped batch -- two host synchronisations per set of chunks instead of two
+ * per query.  Where that limit is outside what the batched BM25 takes, every query goes through
+ * rlr_engine_search_text_capped. */
+int32_t rlr_engine_search_text_capped_batch(rlr_index *idx, rlr_lexical *lex, const rlr_filter *f, const float *queries_raw,
+                                            uint32_t dq, uint32_t n_queries, const char *tokens, const uint64_t *token_offsets,
+                                            uint32_t top_k, float diversity_factor, int32_t stage,
+                                            const rlr_query_weights *weights, uint32_t per_doc, rlr_search_hit *out,
+                                            uint32_t cap, uint32_t *n_out);
 /* Every chunk whose cosine with the query is at least min_cosine, and how many there are (rlr_search_range,
  * include/rlr_gpu.h), over the whole index (f null) or inside a filter.  No reference site: the reference only colours
  * results by fixed score thresholds.  The query is normalised as rlr_engine_search does (rlr_normalize, zip-truncated

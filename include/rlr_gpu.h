@@ -557,6 +557,38 @@ int32_t rlr_search_capped(rlr_index *idx, const rlr_filter *f, const float *quer
  * need > 1024, more than 2048 lexical rows, w_embedding <= 0, w_lexical < 0 or a non-finite weight, a negative lexical
  * score, rows too wide for the staged re-score).  counts may be null. */
 int32_t rlr_index_capped_forms(rlr_index *idx, uint64_t counts[4], int32_t reset);
+/* rlr_search_capped for a BATCH: n_queries queries of dim floats each; need, k, lambda, diversify, the weights, per_doc,
+ * guard_eps and f hold for the whole call.  Query q's lexical pairs are lex_rows / lex_scores [lex_offsets[q],
+ * lex_offsets[q + 1]) (lex_offsets: n_queries + 1 entries, non-decreasing; each query's rows ascending, unique, inside the
+ * index), its normaliser max_lex[q].  The result definition, the argument and error rules are those of rlr_search_capped
+ * query by query, and for every input every output carries the same bits -- only the number of passes over the rows,
+ * launches and synchronisations differs.  Results of query q start at q * need (the need passed in) in rows_out / cos_out /
+ * score_out / lex_out / docs_out (may be null); n_out[q] is their count.  An empty filter or index, or need == 0: RLR_OK
+ * with every n_out[q] = 0.
+ * Over f32 rows of 256 / 512 / 768 / 1024 elements (inside a mask-path filter too) the queries run in chunks of up to 8:
+ * one upload, one shared scan, the exact cosines of every query's lexical rows in one launch, ONE set of selection
+ * launches with a capped finish per query, one Gram and one greedy launch for the chunk's pools, one copy back and one
+ * synchronisation (DESIGN.md "Batched capped search").  The chunk width follows rlr_search_topk_grouped_batch; a larger
+ * batch is split evenly into consecutive chunks (9 queries: 5 + 4).  A query the device cannot decide is handed to the
+ * path of rlr_search_capped on its own -- the rest of its chunk stays decided -- never dropped or answered approximately. */
+int32_t rlr_search_capped_batch(rlr_index *idx, const rlr_filter *f, const float *queries, uint32_t n_queries, uint32_t need,
+                                uint32_t k, float lambda, int32_t diversify, float w_embedding, float w_lexical,
+                                const uint64_t *lex_rows, const float *lex_scores, const uint64_t *lex_offsets,
+                                const float *max_lex, uint32_t per_doc, float guard_eps, uint64_t *rows_out, float *cos_out,
+                                float *score_out, float *lex_out, uint32_t *docs_out, uint32_t *n_out);
+/* When rlr_search_capped_batch shares a pass: 0 (the default) where a cost model expects the shared chunk to win, 1 never
+ * (every query one by one), 2 wherever the shape allows.  Any other mode: RLR_E_INVALID.  The answers do not depend on it. */
+int32_t rlr_index_set_capped_sharing(rlr_index *idx, int32_t mode);
+/* Queries of rlr_search_capped_batch by form since the last reset, each query in exactly one: [0] decided on the device
+ * behind a shared scan; handed to the path of rlr_search_capped [1] on a capacity (more than 2048 candidates, a workgroup's
+ * local list or the table overflowed), [2] because it was undecidable there (the boundary rule, rows that order last were
+ * needed, a masked row came back, the chunk's workspace could not be reserved), [3] by rule (one query, mode 1, the cost
+ * model declined, a list-path filter, need > 1024, weights outside the proof's assumptions, rows too wide for the staged
+ * re-score, a row shape no shared scan serves -- binary16 rows among them --, no chunk width of two within the workspace
+ * rule, the lone remainder of a batch; and for that query alone: more than 2048 lexical rows inside the filter, a negative
+ * or NaN lexical score, a non-finite or non-positive max_lex).  A handed-over query is counted by rlr_index_capped_forms
+ * as well.  counts may be null. */
+int32_t rlr_index_capped_batch_forms(rlr_index *idx, uint64_t counts[4], int32_t reset);
 
 /* ---- coalescing of concurrent single-query searches ----------------------- */
 /* Serve concurrent single-query rlr_search_topk calls on this index from shared passes over the rows.

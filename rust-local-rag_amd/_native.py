@@ -169,6 +169,11 @@ PROTOTYPES = [
     ("rlr_search_capped", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, C.c_float, C.c_int32, C.c_float, C.c_float, u64p, f32p,
                                       C.c_uint32, C.c_float, C.c_uint32, C.c_float, u64p, f32p, f32p, f32p, u32p, u32p]),
     ("rlr_index_capped_forms", C.c_int32, [_H, u64p, C.c_int32]),
+    ("rlr_search_capped_batch", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_int32, C.c_float,
+                                            C.c_float, u64p, f32p, u64p, f32p, C.c_uint32, C.c_float, u64p, f32p, f32p, f32p, u32p,
+                                            u32p]),
+    ("rlr_index_set_capped_sharing", C.c_int32, [_H, C.c_int32]),
+    ("rlr_index_capped_batch_forms", C.c_int32, [_H, u64p, C.c_int32]),
     ("rlr_index_set_coalescing", C.c_int32, [_H, C.c_uint32, C.c_uint32]),
     ("rlr_index_coalesce_stats", C.c_int32, [_H, C.POINTER(CoalesceStatsC), C.c_int32]),
     ("rlr_profile_enable", C.c_int32, [_H, C.c_int32]),
@@ -201,6 +206,12 @@ PROTOTYPES = [
     ("rlr_engine_search_text_capped", C.c_int32, [_H, _H, _H, f32p, C.c_uint32, C.c_char_p, C.c_size_t, C.c_uint32, C.c_float,
                                                   C.c_int32, C.POINTER(QueryWeightsC), C.c_uint32, C.POINTER(SearchHitC),
                                                   C.c_uint32, u32p]),
+    ("rlr_engine_search_capped_batch", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_int32,
+                                                   C.POINTER(QueryWeightsC), u64p, f32p, u64p, C.c_uint32, C.POINTER(SearchHitC),
+                                                   C.c_uint32, u32p]),
+    ("rlr_engine_search_text_capped_batch", C.c_int32, [_H, _H, _H, f32p, C.c_uint32, C.c_uint32, C.c_char_p, u64p, C.c_uint32,
+                                                        C.c_float, C.c_int32, C.POINTER(QueryWeightsC), C.c_uint32,
+                                                        C.POINTER(SearchHitC), C.c_uint32, u32p]),
     ("rlr_engine_search_range", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_float, C.c_uint32, C.POINTER(SearchHitC), u32p, u64p]),
     ("rlr_engine_search_range_batch", C.c_int32, [_H, _H, f32p, C.c_uint32, C.c_uint32, f32p, C.c_uint32, C.POINTER(SearchHitC), u32p,
                                                   u64p]),

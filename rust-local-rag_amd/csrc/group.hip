@@ -15,7 +15,8 @@
 // A capped hybrid search (rlr_search_capped) runs the same launches with k = the pool size and capped_finish_kernel as its
 // finish: the candidates united with the lexical rows, blended, ranked inside the group in COMBINED order (below).
 // A batched grouped search (rlr_search_topk_grouped_batch) runs ONE set of these launches for a chunk of up to 8 queries
-// behind a shared scan, with one key table for the chunk and a value plane per query ("the batched tail", below).
+// behind a shared scan, with one key table for the chunk and a value plane per query ("the batched tail", below); a
+// batched capped search (rlr_search_capped_batch) runs that tail with capped_finish_multi_kernel as its finish.
 // An order between workgroups comes from the order of launches on one stream, never from a flag (the rule of tail.hip);
 // inside a launch the table is only touched by atomics, between launches by plain loads.
 #include "../../include/rlr_gpu.h"
@@ -466,7 +467,13 @@ __device__ inline uint32_t capped_bound_key(float t, float u, float two_eps, flo
 // every other group with rows left behind (untagged rows and groups without an entry have t <= u: the bound of u covers
 // them) must lie strictly below the need-th accepted entry: the walk ends before it reaches such a row.  If the collect
 // left no row behind (n_raw == n_valid) there is nothing to bound.
-__global__ __launch_bounds__(1024) void capped_finish_kernel(GroupDev a, CappedArgs c)
+//
+// The body over one query's view (the batched tail runs it once per query of a chunk: capped_finish_multi_kernel): `a` as
+// the finish of that query sees it, `c` its lexical pairs, scratch and pool, pool_doc (may be null) the pool's document
+// ids in device memory, c.h_side (may be null) the pinned side block.  Returns the status, *n_pool_out the pool size and
+// *side_out the checksum of the side block's values, all uniform, behind a barrier.
+__device__ inline uint32_t capped_finish_body(const GroupDev &a, const CappedArgs &c, uint32_t *pool_doc, uint32_t *n_pool_out,
+                                              uint32_t *side_out)
 {
     __shared__ uint64_t s_key[kCappedSlots];
     __shared__ uint32_t s_doc[kCappedSlots];
@@ -474,8 +481,6 @@ __global__ __launch_bounds__(1024) void capped_finish_kernel(GroupDev a, CappedA
     __shared__ uint32_t s_flag[kCappedLexMax]; // lexical pair j is one of the candidates
     __shared__ uint32_t s_nacc, s_nan, s_req, s_tkey, s_status, s_side;
     const uint32_t tid = threadIdx.x;
-    for (uint32_t i = tid; i < kHistBins; i += 1024)
-        a.ctx_hist[i] = 0; // the scan counted its scores into the context's digit-1 histogram; nothing here read it
     const uint32_t n_raw = a.st->n_cand, flags = a.st->flags, n_valid = a.st->n_valid;
     const float u = __builtin_bit_cast(float, a.st->u_bits);
     const uint32_t need = a.k, m = a.per_doc, n_lex = min(c.n_lex, kCappedLexMax);
@@ -595,9 +600,13 @@ __global__ __launch_bounds__(1024) void capped_finish_kernel(GroupDev a, CappedA
                 c.comb[pos] = cc[i];
                 c.cosv[pos] = ce[i];
                 c.lexv[pos] = cl[i];
-                c.h_side[2 + pos] = row;
-                c.h_side[2 + need + pos] = d;
-                atomicAdd(&s_side, result_chk_term(row, 2 + pos) + result_chk_term(d, 2 + need + pos));
+                if (pool_doc)
+                    pool_doc[pos] = d;
+                if (c.h_side) {
+                    c.h_side[2 + pos] = row;
+                    c.h_side[2 + need + pos] = d;
+                    atomicAdd(&s_side, result_chk_term(row, 2 + pos) + result_chk_term(d, 2 + need + pos));
+                }
                 if (pos == need - 1)
                     s_tkey = static_cast<uint32_t>(mine >> 32);
             }
@@ -620,10 +629,25 @@ __global__ __launch_bounds__(1024) void capped_finish_kernel(GroupDev a, CappedA
         c.comb[r] = 0.0f;
         c.cosv[r] = 0.0f;
         c.lexv[r] = 0.0f;
+        if (pool_doc)
+            pool_doc[r] = RLR_DOC_NONE;
     }
     __threadfence_system();
     __syncthreads();
-    const uint32_t status = s_status;
+    *n_pool_out = n_pool;
+    *side_out = s_side;
+    return s_status;
+}
+
+// One workgroup in place of group_finish_kernel: the body over the context's single query, then the pinned side block's
+// header and -- without diversification -- the result block.
+__global__ __launch_bounds__(1024) void capped_finish_kernel(GroupDev a, CappedArgs c)
+{
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < kHistBins; i += 1024)
+        a.ctx_hist[i] = 0; // the scan counted its scores into the context's digit-1 histogram; nothing here read it
+    uint32_t n_pool, s_side;
+    const uint32_t status = capped_finish_body(a, c, nullptr, &n_pool, &s_side);
     if (tid == 0) {
         c.h_side[1] = status ? 0u : s_side;
         __threadfence_system();
@@ -832,6 +856,41 @@ __global__ __launch_bounds__(1024) void group_finish_multi_kernel(GroupBatchDev 
         out[a.out_words - 1] = n_raw;
 }
 
+// The finish of a batched capped search (rlr_search_capped_batch): one workgroup per query, capped_finish_body over the
+// query's view -- its candidates, state, t_g slice and value plane as the collect left them (group_view), its lexical
+// slice and max_lex, its slice of the scratch and of the pool planes.  Nothing is shared between two workgroups but the
+// read-only key table, the column and the per-call scalars.  A non-zero status leaves pool size 0 in info and in sizes:
+// the Gram and greedy launches behind it do nothing for that query.  (c->d_hist is not touched: the shared scans run
+// without a histogram.)
+__global__ __launch_bounds__(1024) void capped_finish_multi_kernel(GroupBatchDev a, CappedBatchArgs b)
+{
+    const uint32_t q = blockIdx.x, need = a.k;
+    const GroupDev v = group_view(a, q);
+    CappedArgs c;
+    c.w_e = b.w_e;
+    c.w_l = b.w_l;
+    c.eps = b.eps;
+    c.n_allowed = b.n_allowed;
+    c.lrow = b.lrow + static_cast<size_t>(q) * b.lex_stride;
+    c.lscore = b.lscore + static_cast<size_t>(q) * b.lex_stride;
+    c.lcos = b.lcos + static_cast<size_t>(q) * b.lex_stride;
+    c.n_lex = b.n_lex[q];
+    c.max_lex = b.max_lex[q];
+    c.scratch = b.scratch + static_cast<size_t>(q) * 3u * kCappedSlots;
+    c.list = b.list + static_cast<size_t>(q) * need;
+    c.comb = b.comb + static_cast<size_t>(q) * need;
+    c.cosv = b.cosv + static_cast<size_t>(q) * need;
+    c.lexv = b.lexv + static_cast<size_t>(q) * need;
+    c.info = b.info + 2u * q;
+    c.h_side = nullptr;
+    c.k_cap = 0;
+    c.h_out = nullptr;
+    uint32_t n_pool, side;
+    const uint32_t status = capped_finish_body(v, c, b.docs + static_cast<size_t>(q) * need, &n_pool, &side);
+    if (threadIdx.x == 0)
+        b.sizes[q] = status ? 0u : n_pool;
+}
+
 } // namespace
 
 // the staging of collect's re-score: the query and cpb rows of products (tail.hip's layout, under what is left of the
@@ -928,9 +987,17 @@ hipError_t launch_group_batch_tail(const GroupBatchArgs &a, hipStream_t s)
     uint32_t cpb;
     size_t staging;
     if (a.n == 0 || a.n_queries < 2 || a.n_queries > 8 || a.k == 0 || a.k > kGroupKMax || a.per_doc == 0 ||
-        a.per_doc > RLR_MAX_PER_DOCUMENT || a.tab_bits < 1 || a.tab_bits > 31 || a.score_stride < a.n || !a.scores || !a.out ||
-        !group_shape(a.pitch16, a.dim, a.dtype, &cpb, &staging))
+        a.per_doc > RLR_MAX_PER_DOCUMENT || a.tab_bits < 1 || a.tab_bits > 31 || a.score_stride < a.n || !a.scores ||
+        (!a.out && !a.capped) || !group_shape(a.pitch16, a.dim, a.dtype, &cpb, &staging))
         return hipErrorInvalidValue;
+    if (a.capped) {
+        const CappedBatchArgs &b = *a.capped;
+        if (!b.scratch || !b.list || !b.comb || !b.cosv || !b.lexv || !b.docs || !b.info || !b.sizes)
+            return hipErrorInvalidValue;
+        for (uint32_t q = 0; q < a.n_queries; ++q)
+            if (b.n_lex[q] > kCappedLexMax || b.n_lex[q] > b.lex_stride || (b.n_lex[q] && (!b.lrow || !b.lscore || !b.lcos)))
+                return hipErrorInvalidValue;
+    }
     GroupBatchDev d;
     d.n_queries = a.n_queries;
     d.scores = a.scores;
@@ -979,7 +1046,10 @@ hipError_t launch_group_batch_tail(const GroupBatchArgs &a, hipStream_t s)
         hipLaunchKernelGGL(group_collect_multi_kernel<true>, dim3(collect_blocks, a.n_queries), dim3(kGroupBlock), staging, s, d);
     else
         hipLaunchKernelGGL(group_collect_multi_kernel<false>, dim3(collect_blocks, a.n_queries), dim3(kGroupBlock), staging, s, d);
-    hipLaunchKernelGGL(group_finish_multi_kernel, dim3(a.n_queries), dim3(1024), 0, s, d);
+    if (a.capped)
+        hipLaunchKernelGGL(capped_finish_multi_kernel, dim3(a.n_queries), dim3(1024), 0, s, d, *a.capped);
+    else
+        hipLaunchKernelGGL(group_finish_multi_kernel, dim3(a.n_queries), dim3(1024), 0, s, d);
     return hipGetLastError();
 }
 

@@ -4178,6 +4178,39 @@ static int32_t capped_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const Ca
     return note_search(ix, c, 1, n_cand, form != 0 ? 1 : 0, timed && form != 3);
 }
 
+// The last step of a capped call, with no context held: an exact form's pool (!picked) goes through mmr_diversify,
+// unchanged, then the hits into the caller's arrays.
+static int32_t capped_deliver(rlr_index *ix, std::vector<CappedHit> &hits, bool picked, uint32_t k, float lambda, uint64_t *rows_out,
+                              float *cos_out, float *score_out, float *lex_out, uint32_t *docs_out, uint32_t *n_out)
+{
+    if (!picked && !hits.empty()) { // the exact form's pool: mmr_diversify over it, unchanged
+        const uint32_t P = static_cast<uint32_t>(hits.size());
+        std::vector<uint64_t> rows(P);
+        std::vector<float> scores(P);
+        for (uint32_t i = 0; i < P; ++i) {
+            rows[i] = hits[i].row;
+            scores[i] = hits[i].c;
+        }
+        std::vector<uint32_t> order(P);
+        uint32_t n_sel = 0;
+        RLR_TRY(mmr_single_impl(ix, rows.data(), scores.data(), P, k, lambda, order.data(), nullptr, &n_sel, nullptr, 0));
+        std::vector<CappedHit> sel(n_sel);
+        for (uint32_t i = 0; i < n_sel; ++i)
+            sel[i] = hits[order[i]];
+        hits.swap(sel);
+    }
+    for (size_t i = 0; i < hits.size(); ++i) {
+        rows_out[i] = hits[i].row;
+        cos_out[i] = hits[i].e;
+        score_out[i] = hits[i].c;
+        lex_out[i] = hits[i].l;
+        if (docs_out)
+            docs_out[i] = hits[i].doc;
+    }
+    *n_out = static_cast<uint32_t>(hits.size());
+    return RLR_OK;
+}
+
 int32_t rlr_search_capped(rlr_index *ix, const rlr_filter *f, const float *query, uint32_t need_in, uint32_t k, float lambda,
                           int32_t diversify, float w_embedding, float w_lexical, const uint64_t *lex_rows, const float *lex_scores,
                           uint32_t n_lex, float max_lex, uint32_t per_doc, float guard_eps, uint64_t *rows_out, float *cos_out,
@@ -4225,32 +4258,386 @@ int32_t rlr_search_capped(rlr_index *ix, const rlr_filter *f, const float *query
         RLR_TRY(capped_query(ix, lease.c, f, call, hits, &picked));
         drain.armed = false;
     }
-    if (!picked && !hits.empty()) { // the exact form's pool: mmr_diversify over it, unchanged
-        const uint32_t P = static_cast<uint32_t>(hits.size());
-        std::vector<uint64_t> rows(P);
-        std::vector<float> scores(P);
-        for (uint32_t i = 0; i < P; ++i) {
-            rows[i] = hits[i].row;
-            scores[i] = hits[i].c;
+    return capped_deliver(ix, hits, picked, k, lambda, rows_out, cos_out, score_out, lex_out, docs_out, n_out);
+}
+
+// ---- batched capped search (rlr_search_capped_batch): the queries of a call share passes over the rows ----------------
+// The gate (rlr_index_set_capped_sharing mode 0): does a chunk of nq capped queries through one shared scan, one set of
+// tail launches and one Gram / greedy pair beat the same queries one by one by 10 %?  grouped_share_wins' form with
+// rounds = per_doc.  BORROWED from the grouped gate, unchanged: the scan rates (7.3 TB/s single, 6.45 / 6.1 / 5.8 TB/s
+// shared), the four per-row terms and the 2 us per round.  FITTED to tools/bench_capped_batch.py's cells at 100 k rows,
+// top_k = 5 (profiles/capped_batch_bench.json; DESIGN.md "Batched capped search" has the table, the fit and what was NOT
+// measured): the three fixed costs.  The cells are whole text requests, so the fixed costs carry the BM25 side too -- one
+// by one 160 us a request (its launches, the Gram / greedy pair, the BM25 call and two synchronisations); shared 200 us a
+// chunk and 45 us a query (its collect, finish and greedy workgroups, its share of the batched BM25).  A call with
+// caller-computed pairs pays less on both sides; the gate does not tell the two apart.
+constexpr double kCappedGateSingleUs = 160.0, kCappedGateSharedUs = 200.0, kCappedGateQueryUs = 45.0;
+static bool capped_share_wins(const rlr_index *ix, const rlr_filter *f, uint32_t nq, uint32_t per_doc)
+{
+    const double el = ix->dtype == RLR_F16 ? 2.0 : 4.0;
+    const double n = static_cast<double>(ix->n_rows), allowed = static_cast<double>(f ? f->n_allowed : ix->n_rows);
+    const double rounds = ix->d_docs ? per_doc : 0.0;
+    const double t_single = nq * (kCappedGateSingleUs * 1e-6 + rounds * 2e-6 + allowed * ix->dim * el / 7.3e12 + n * (25e-12 + rounds * 9.5e-12));
+    const double rate = nq <= 2 ? 6.45e12 : nq <= 4 ? 6.1e12 : 5.8e12;
+    const double t_shared = kCappedGateSharedUs * 1e-6 + nq * kCappedGateQueryUs * 1e-6 + allowed * ix->dim * el / rate +
+                            nq * n * (20e-12 + rounds * 10e-12);
+    return t_single > 1.1 * t_shared;
+}
+
+// The workspace of one chunk: device (c->d_pool, beside the grouped state) and pinned (c->h_pin).  The lexical pairs lie
+// B apart per query (the layout launch_score_rows_batch scores), rows | scores | counts in one region: one upload.  The
+// result block (list .. nsel) is one region as well: one copy back.
+struct CappedBatchWs {
+    uint64_t m, P, B, q_pitch, gram_floats;
+    Carver d, h;
+    float *gram = d.take<float>(gram_floats), *mmr = d.take<float>(m * P);
+    float *scratch = d.take<float>(m * 3ull * rlr::kCappedSlots);
+    uint32_t *lrow = d.take<uint32_t>(m * B);
+    float *lscore = d.take<float>(m * B);
+    uint32_t *lcnt = d.take<uint32_t>(m);
+    float *lcos = d.take<float>(m * B);
+    uint32_t *list = d.take<uint32_t>(m * P);
+    float *comb = d.take<float>(m * P), *cos = d.take<float>(m * P), *lexv = d.take<float>(m * P);
+    uint32_t *docs = d.take<uint32_t>(m * P), *order = d.take<uint32_t>(m * P);
+    uint32_t *info = d.take<uint32_t>(2 * m), *sizes = d.take<uint32_t>(m), *nsel = d.take<uint32_t>(m);
+    float *h_q = h.take<float>(m * q_pitch);
+    uint32_t *h_lrow = h.take<uint32_t>(m * B);
+    float *h_lscore = h.take<float>(m * B);
+    uint32_t *h_lcnt = h.take<uint32_t>(m);
+    uint32_t *h_res = h.take<uint32_t>(res_words());
+    char *h_pad = h.take<char>(64);
+    uint64_t res_words() const { return 6 * m * P + 4 * m; }
+    uint64_t lex_words() const { return 2 * m * B + m; }
+    CappedBatchWs(float *d_base, void *h_base, uint32_t q_pitch_, uint32_t m_, uint32_t P_, uint32_t B_, bool diversify)
+        : m(m_), P(P_), B(B_), q_pitch(q_pitch_), gram_floats(diversify ? static_cast<uint64_t>(m_) * P_ * P_ : 0), d(d_base),
+          h(h_base) {}
+};
+
+// What holds for every query of a capped batch, and where query q's answer goes (the caller's buffers, `need_in` apart).
+struct CappedBatchCall {
+    uint32_t need, k; // need: already min(., |A|)
+    float lambda;
+    bool diversify;
+    float w_e, w_l;
+    uint32_t per_doc;
+    float guard_eps;
+};
+
+// the per-query checks of capped_query's by-rule test: what sends this query, alone, to the single path
+static bool capped_query_by_rule(const CappedCall &call)
+{
+    bool lex_ok = std::isfinite(call.max_lex) && call.max_lex > 0.0f;
+    for (size_t i = 0; i < call.lscore.size() && lex_ok; ++i)
+        lex_ok = call.lscore[i] >= 0.0f;
+    return !lex_ok || call.lrow.size() > rlr::kCappedLexMax;
+}
+
+// One chunk of m (2..8) capped queries (calls[q].query = queries + q * dim: consecutive) in ONE enqueue: the queries staged
+// and uploaded once and every query's lexical pairs in one copy, the shared scan over the master rows (masked inside a
+// filter), launch_score_rows_batch for the exact cosines of all lexical rows, group.hip's batched tail with k = need and
+// the capped multi finish, -- diversified -- one batched Gram and one batched greedy launch whose pool sizes are the
+// finish's, ONE copy of the chunk's result block and one synchronisation.  The plan is the chunk's (the largest query
+// norm): a band wider than a query's own only adds candidates and can only make the boundary rule more cautious; what is
+// decided is decided on reference-order scores, so a decided answer is the definition's, as the single path's is.
+// forms[q]: 0 decided on the device; 1 handed back on a capacity; 2 handed back as undecidable here (status 2 of the
+// finish, a masked row came back, the workspace could not be reserved); 3 by rule for this query alone (it rode the scan
+// with an empty lexical slice and its result is not read).  Every query with a non-zero form is answered by capped_query
+// on the same context after all decided queries have been read out of the pinned block; its neighbours stay decided.
+// hits[q] / picked[q] as capped_query leaves them.  c->d_hist is not touched: the shared scans run without a histogram.
+static int32_t capped_batch_chunk(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *queries, const CappedCall *calls, uint32_t m,
+                                  const CappedBatchCall &bc, std::vector<CappedHit> *hits, bool *picked, uint32_t *forms)
+{
+    const uint64_t n_allowed = f ? f->n_allowed : ix->n_rows;
+    const uint32_t n = static_cast<uint32_t>(ix->n_rows), P = bc.need;
+    const SearchPlan p = make_plan(ix, queries, m, P, bc.guard_eps);
+    RLR_TRY(ctx_prepare(ix, c, m, p));
+    uint32_t B = 1;
+    for (uint32_t q = 0; q < m; ++q) {
+        forms[q] = capped_query_by_rule(calls[q]) ? 3 : 0;
+        picked[q] = true;
+        if (forms[q] == 0)
+            B = std::max<uint32_t>(B, static_cast<uint32_t>(calls[q].lrow.size()));
+    }
+    const uint32_t k_cap = rlr::result_k_cap(bc.k, P, bc.diversify);
+    const uint32_t tab_bits = group_table_bits(n_allowed);
+    const size_t slots = static_cast<size_t>(1) << tab_bits;
+    const uint64_t s_stride = (static_cast<uint64_t>(n) + 3) / 4 * 4;
+    const CappedBatchWs sizes(nullptr, nullptr, ix->q_pitch, m, P, B, bc.diversify);
+    hipStream_t s = c->stream;
+    uint64_t cand_total = 0;
+    uint32_t n_decided = 0;
+    // the chunk's workspace: the grouped state, a slice per query (and ONE key table), and the pool workspace beside it
+    hipError_t e = hipSuccess;
+    if (ix->d_docs)
+        e = reserve_group(Want{c->d_gkeys, slots}, Want{c->d_gvals, slots * bc.per_doc * m});
+    if (e == hipSuccess)
+        e = c->d_gtg.reserve(std::max<uint64_t>(static_cast<uint64_t>(m) * n, 1024));
+    if (e == hipSuccess)
+        e = reserve_group(Want{c->d_ghist, static_cast<size_t>(m) * 2 * kHistBins}, Want{c->d_gstate, m},
+                          Want{c->d_gcand, static_cast<size_t>(m) * kGroupCap}, Want{c->d_gcdoc, static_cast<size_t>(m) * kGroupCap});
+    if (e == hipSuccess)
+        e = c->d_sample.reserve(static_cast<uint64_t>(m) * s_stride);
+    if (e == hipSuccess)
+        e = c->d_pool.reserve(sizes.d.floats());
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError(); // no error of the call: the queries go one by one, in the single path's smaller workspace
+        for (uint32_t q = 0; q < m; ++q)
+            if (forms[q] == 0)
+                forms[q] = 2;
+    } else {
+        RLR_HIP(e);
+        RLR_TRY(pin_reserve(c, sizes.h.bytes));
+        const CappedBatchWs ws(c->d_pool.get(), c->h_pin.get(), ix->q_pitch, m, P, B, bc.diversify);
+        stage_queries(ix, c, queries, m, ws.h_q);
+        c->h_q_kq = nullptr;
+        RLR_HIP(upload_queries(c, ws.h_q, static_cast<size_t>(m) * ix->q_pitch * sizeof(float), s));
+        rlr::CappedBatchArgs ca{};
+        for (uint32_t q = 0; q < m; ++q) { // (a by-rule query rides with an empty slice)
+            const uint32_t nl = forms[q] == 0 ? static_cast<uint32_t>(calls[q].lrow.size()) : 0u;
+            uint32_t *hr = ws.h_lrow + static_cast<size_t>(q) * B;
+            float *hs = ws.h_lscore + static_cast<size_t>(q) * B;
+            if (nl) {
+                std::memcpy(hr, calls[q].lrow.data(), static_cast<size_t>(nl) * sizeof(uint32_t));
+                std::memcpy(hs, calls[q].lscore.data(), static_cast<size_t>(nl) * sizeof(float));
+            }
+            std::memset(hr + nl, 0, static_cast<size_t>(B - nl) * sizeof(uint32_t));
+            std::memset(hs + nl, 0, static_cast<size_t>(B - nl) * sizeof(float));
+            ws.h_lcnt[q] = nl;
+            ca.n_lex[q] = nl;
+            ca.max_lex[q] = forms[q] == 0 ? calls[q].max_lex : 1.0f;
         }
-        std::vector<uint32_t> order(P);
-        uint32_t n_sel = 0;
-        RLR_TRY(mmr_single_impl(ix, rows.data(), scores.data(), P, k, lambda, order.data(), nullptr, &n_sel, nullptr, 0));
-        std::vector<CappedHit> sel(n_sel);
-        for (uint32_t i = 0; i < n_sel; ++i)
-            sel[i] = hits[order[i]];
-        hits.swap(sel);
+        RLR_HIP(hipMemcpyAsync(ws.lrow, ws.h_lrow, ws.lex_words() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        const ScanArgs sa = scan_args(ix, c->d_query.get(), c->d_sample.get(), nullptr);
+        if (!(f ? launch_scan_masked_multi(sa, f->d_mask.get(), f->n_allowed, ix->q_pitch, m, s_stride, s, &e)
+                : launch_scan_multi(sa, ix->q_pitch, m, s_stride, s, &e)))
+            return set_error(RLR_E_INTERNAL, "multi-query scan refused a shape the capped gate accepted");
+        RLR_HIP(e);
+        RLR_HIP(launch_score_rows_batch(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, c->d_query.get(), ix->q_pitch, m, ws.lrow, B,
+                                        ws.lcos, ws.lcnt, 1, n, s));
+        ca.w_e = bc.w_e;
+        ca.w_l = bc.w_l;
+        ca.eps = p.two_eps * 0.5f;
+        ca.n_allowed = static_cast<uint32_t>(n_allowed);
+        ca.lrow = ws.lrow;
+        ca.lscore = ws.lscore;
+        ca.lcos = ws.lcos;
+        ca.lex_stride = B;
+        ca.scratch = ws.scratch;
+        ca.list = ws.list;
+        ca.comb = ws.comb;
+        ca.cosv = ws.cos;
+        ca.lexv = ws.lexv;
+        ca.docs = ws.docs;
+        ca.info = ws.info;
+        ca.sizes = ws.sizes;
+        GroupBatchArgs ga{};
+        ga.n_queries = m;
+        ga.scores = c->d_sample.get();
+        ga.score_stride = s_stride;
+        ga.docs = ix->d_docs.get();
+        ga.n = n;
+        ga.k = P;
+        ga.per_doc = bc.per_doc;
+        ga.two_eps = p.two_eps;
+        ga.tab_keys = c->d_gkeys.get();
+        ga.tab_vals = c->d_gvals.get();
+        ga.tab_bits = tab_bits;
+        ga.tg = c->d_gtg.get();
+        ga.hist = c->d_ghist.get();
+        ga.st = c->d_gstate.get();
+        ga.rows = ix->d_rows.get();
+        ga.pitch16 = ix->pitch16;
+        ga.dim = ix->dim;
+        ga.dtype = ix->dtype;
+        ga.queries = c->d_query.get();
+        ga.q_pitch = ix->q_pitch;
+        ga.cand = c->d_gcand.get();
+        ga.cand_doc = c->d_gcdoc.get();
+        ga.out = nullptr;
+        ga.n_cu = ix->n_cu;
+        ga.capped = &ca;
+        RLR_HIP(launch_group_batch_tail(ga, s));
+        if (bc.diversify) {
+            RLR_HIP(launch_gram_rows(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, ws.list, P, ws.gram, m, s));
+            RLR_HIP(launch_mmr_greedy(ws.gram, ws.comb, P, bc.k, bc.lambda, ws.order, ws.mmr, ws.nsel, ws.sizes, m, s));
+        }
+        RLR_HIP(hipMemcpyAsync(ws.h_res, ws.list, ws.res_words() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        RLR_HIP(hipStreamSynchronize(s));
+        // the result block as the device laid it out: list | comb | cos | lexv | docs | order | info | sizes | nsel
+        const size_t plane = static_cast<size_t>(m) * P;
+        const uint32_t *r_list = ws.h_res, *r_docs = ws.h_res + 4 * plane, *r_order = ws.h_res + 5 * plane;
+        const float *r_comb = reinterpret_cast<const float *>(ws.h_res + plane), *r_cos = reinterpret_cast<const float *>(ws.h_res + 2 * plane);
+        const float *r_lex = reinterpret_cast<const float *>(ws.h_res + 3 * plane);
+        const uint32_t *r_info = ws.h_res + 6 * plane, *r_nsel = r_info + 3 * static_cast<size_t>(m);
+        for (uint32_t q = 0; q < m; ++q) {
+            if (forms[q] != 0)
+                continue;
+            const uint32_t status = r_info[2 * q + 1], n_pool = r_info[2 * q];
+            if (status != 0 || n_pool > P) {
+                forms[q] = status == 1 ? 1 : 2; // capacity | undecidable here (the boundary rule, rows that order last are wanted)
+                continue;
+            }
+            const size_t base = static_cast<size_t>(q) * P;
+            const uint32_t cnt = std::min<uint32_t>(bc.diversify ? r_nsel[q] : n_pool, k_cap);
+            std::vector<CappedHit> &out = hits[q];
+            out.resize(cnt);
+            for (uint32_t i = 0; i < cnt && forms[q] == 0; ++i) {
+                const uint32_t o = bc.diversify ? r_order[base + i] : i;
+                if (o >= n_pool || (f && !filter_holds(f, r_list[base + o])))
+                    forms[q] = 2; // a masked row came back (the hazard masked_row_among documents)
+                else
+                    out[i] = CappedHit{r_list[base + o], r_docs[base + o], r_comb[base + o], r_cos[base + o], r_lex[base + o]};
+            }
+            if (forms[q] == 0) {
+                cand_total += n_pool;
+                n_decided++;
+            }
+        }
     }
-    for (size_t i = 0; i < hits.size(); ++i) {
-        rows_out[i] = hits[i].row;
-        cos_out[i] = hits[i].e;
-        score_out[i] = hits[i].c;
-        lex_out[i] = hits[i].l;
-        if (docs_out)
-            docs_out[i] = hits[i].doc;
+    c->hist_dirty = false;
+    {
+        std::lock_guard<std::mutex> lk(ix->mu);
+        ix->prof.n_batches += 1;
+        ix->prof.n_batch_queries += m;
+        ix->prof.n_batch_fallbacks += m - n_decided;
     }
-    *n_out = static_cast<uint32_t>(hits.size());
+    RLR_TRY(note_search(ix, c, n_decided, cand_total, 0, /*timed=*/false));
+    // (from here on the pinned block and the context are capped_query's)
+    for (uint32_t q = 0; q < m; ++q)
+        if (forms[q] != 0) {
+            hits[q].clear();
+            RLR_TRY(capped_query(ix, c, f, calls[q], hits[q], &picked[q]));
+        }
     return RLR_OK;
+}
+
+int32_t rlr_search_capped_batch(rlr_index *ix, const rlr_filter *f, const float *queries, uint32_t n_queries, uint32_t need_in,
+                                uint32_t k, float lambda, int32_t diversify, float w_embedding, float w_lexical,
+                                const uint64_t *lex_rows, const float *lex_scores, const uint64_t *lex_offsets, const float *max_lex,
+                                uint32_t per_doc, float guard_eps, uint64_t *rows_out, float *cos_out, float *score_out,
+                                float *lex_out, uint32_t *docs_out, uint32_t *n_out)
+{
+    RLR_TRY(check_handle(ix));
+    if (f)
+        RLR_TRY(check_filter(ix, f)); // (a stale filter is refused before any GPU work)
+    if (per_doc < 1 || per_doc > RLR_MAX_PER_DOCUMENT)
+        return set_error(RLR_E_INVALID, "per_doc must be in 1..%d (per_doc = %u)", RLR_MAX_PER_DOCUMENT, per_doc);
+    if (n_queries && !n_out)
+        return set_error(RLR_E_INVALID, "n_out is null");
+    for (uint32_t q = 0; q < n_queries; ++q)
+        n_out[q] = 0;
+    const uint64_t n_allowed = f ? f->n_allowed : ix->n_rows;
+    if (n_allowed == 0 || need_in == 0 || n_queries == 0)
+        return RLR_OK;
+    if (!queries || !rows_out || !cos_out || !score_out || !lex_out || !lex_offsets || !max_lex)
+        return set_error(RLR_E_INVALID, "null argument");
+    for (uint32_t q = 0; q < n_queries; ++q)
+        if (lex_offsets[q + 1] < lex_offsets[q])
+            return set_error(RLR_E_INVALID, "lex_offsets must be non-decreasing (query %u)", q);
+    if (lex_offsets[n_queries] > lex_offsets[0] && (!lex_rows || !lex_scores))
+        return set_error(RLR_E_INVALID, "null argument");
+    std::vector<CappedCall> calls(n_queries);
+    CappedBatchCall bc;
+    bc.need = static_cast<uint32_t>(std::min<uint64_t>(need_in, n_allowed));
+    bc.k = k;
+    bc.lambda = lambda;
+    bc.diversify = diversify != 0;
+    bc.w_e = w_embedding;
+    bc.w_l = w_lexical;
+    bc.per_doc = per_doc;
+    bc.guard_eps = guard_eps;
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        CappedCall &call = calls[q];
+        call.query = queries + static_cast<size_t>(q) * ix->dim;
+        call.need = bc.need;
+        call.k = k;
+        call.lambda = lambda;
+        call.diversify = bc.diversify;
+        call.w_e = w_embedding;
+        call.w_l = w_lexical;
+        call.max_lex = max_lex[q];
+        call.per_doc = per_doc;
+        call.guard_eps = guard_eps;
+        for (uint64_t i = lex_offsets[q]; i < lex_offsets[q + 1]; ++i) {
+            if (lex_rows[i] >= ix->n_rows || (i > lex_offsets[q] && lex_rows[i] <= lex_rows[i - 1]))
+                return set_error(RLR_E_INVALID, "lex_rows must be ascending, unique and inside the index (query %u)", q);
+            if (f && !filter_holds(f, static_cast<uint32_t>(lex_rows[i])))
+                continue; // a lexical row outside the filter is no candidate
+            call.lrow.push_back(static_cast<uint32_t>(lex_rows[i]));
+            call.lscore.push_back(lex_scores[i]);
+        }
+    }
+    RLR_TRY(use_device(ix));
+    std::vector<std::vector<CappedHit>> hits(n_queries);
+    std::unique_ptr<bool[]> picked(new bool[n_queries]);
+    uint64_t forms[4] = {0, 0, 0, 0};
+    int32_t rc = RLR_OK;
+    {
+        CtxLease lease(ix);
+        RLR_TRY(ctx_acquire(ix, &lease.c));
+        StreamDrain drain{lease.c->stream};
+        // The chunk width w, 0 by rule for the whole call: one query, mode 1, a list-path filter, need beyond the finish,
+        // weights outside the proof's assumptions, rows the staged re-score or the shared scans do not serve, no width of two
+        // within the workspace rule, the gate declined.  Then the queries are split evenly over ceil(n_queries / w) chunks
+        // (9 -> 5 + 4); a chunk of one goes by rule as well.
+        const int32_t mode = ix->capped_sharing.load();
+        uint32_t w = 0;
+        if (mode != 1 && n_queries >= 2 && !(f && f->path == 0) && bc.need <= kGroupKMax && group_table_bits(n_allowed) <= 31 &&
+            bc.w_e > 0.0f && std::isfinite(bc.w_e) && bc.w_l >= 0.0f && std::isfinite(bc.w_l) &&
+            group_fits(ix->pitch16, ix->dim, ix->dtype) && batch_multi_shape(ix, 2) && ix->n_rows <= 0xFFFFFFFFull) {
+            w = std::min(grouped_chunk_width(ix, n_allowed, per_doc), n_queries);
+            if (w >= 2 && mode == 0 && !capped_share_wins(ix, f, w, per_doc))
+                w = 0;
+        }
+        const uint32_t n_chunks = w >= 2 ? (n_queries + w - 1) / w : 0;
+        uint32_t chunk_forms[8];
+        bool chunk_picked[8];
+        for (uint32_t q0 = 0, ci = 0; q0 < n_queries && rc == RLR_OK; ++ci) {
+            const uint32_t m = n_chunks ? n_queries / n_chunks + (ci < n_queries % n_chunks ? 1u : 0u) : 1u;
+            if (m < 2) {
+                bool one = true;
+                rc = capped_query(ix, lease.c, f, calls[q0], hits[q0], &one);
+                picked[q0] = one;
+                forms[3]++;
+            } else {
+                rc = capped_batch_chunk(ix, lease.c, f, queries + static_cast<size_t>(q0) * ix->dim, calls.data() + q0, m, bc,
+                                        hits.data() + q0, chunk_picked, chunk_forms);
+                for (uint32_t i = 0; i < m && rc == RLR_OK; ++i) {
+                    forms[chunk_forms[i]]++;
+                    picked[q0 + i] = chunk_picked[i];
+                }
+            }
+            q0 += m;
+        }
+        {
+            std::lock_guard<std::mutex> lk(ix->mu);
+            for (int i = 0; i < 4; ++i)
+                ix->capped_batch_forms[i] += forms[i];
+        }
+        RLR_TRY(rc);
+        drain.armed = false;
+    }
+    // (the contexts are back: the exact forms' pools go through mmr_diversify, as in rlr_search_capped)
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        const size_t at = static_cast<size_t>(q) * need_in;
+        RLR_TRY(capped_deliver(ix, hits[q], picked[q], k, lambda, rows_out + at, cos_out + at, score_out + at, lex_out + at,
+                               docs_out ? docs_out + at : nullptr, &n_out[q]));
+    }
+    return RLR_OK;
+}
+
+int32_t rlr_index_set_capped_sharing(rlr_index *ix, int32_t mode)
+{
+    RLR_TRY(check_handle(ix));
+    if (mode < 0 || mode > 2)
+        return set_error(RLR_E_INVALID, "capped sharing mode %d (0 the gate, 1 never, 2 wherever the shape allows)", mode);
+    ix->capped_sharing.store(mode);
+    return RLR_OK;
+}
+
+int32_t rlr_index_capped_batch_forms(rlr_index *ix, uint64_t counts[4], int32_t reset)
+{
+    return read_forms(ix, &rlr_index::capped_batch_forms, counts, reset);
 }
 
 int32_t rlr_index_capped_forms(rlr_index *ix, uint64_t counts[4], int32_t reset)

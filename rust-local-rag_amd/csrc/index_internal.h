@@ -203,6 +203,8 @@ struct rlr_index {
     std::atomic<int32_t> range_sharing{0};    // rlr_index_set_range_sharing: 0 auto (the cost model), 1 never, 2 wherever the shape allows
     uint64_t grouped_batch_forms[4] = {0, 0, 0, 0}; // rlr_index_grouped_batch_forms: queries of rlr_search_topk_grouped_batch by form (mu)
     std::atomic<int32_t> grouped_sharing{0};  // rlr_index_set_grouped_sharing: 0 the gate (grouped_share_wins), 1 never, 2 wherever the shape allows
+    uint64_t capped_batch_forms[4] = {0, 0, 0, 0}; // rlr_index_capped_batch_forms: queries of rlr_search_capped_batch by form (mu)
+    std::atomic<int32_t> capped_sharing{0};   // rlr_index_set_capped_sharing: 0 the gate (capped_share_wins), 1 never, 2 wherever the shape allows
 };
 
 // A set of rows of one index, fixed at creation (rlr_filter_create_*): one bit per index row on the device (tail bits of

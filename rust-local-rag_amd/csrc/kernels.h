@@ -327,6 +327,26 @@ bool group_shape(uint32_t pitch16, uint32_t dim, int dtype, uint32_t *cpb_out, s
 //   group_out_words(k) words as GroupArgs::out has them | status: the candidate count, or kGroupBatchBack when the finish
 //   could not decide (more than kGroupCap candidates, a local list or the table overflowed)
 constexpr uint64_t kGroupBatchBack = 0xFFFFFFFFull;
+// The capped part of a batched tail (rlr_search_capped_batch): capped_finish_multi_kernel in place of the grouped finish,
+// one workgroup per query of the chunk.  What CappedArgs holds once is held per query here.  The lexical pairs lie
+// lex_stride apart (query q's rows, scores and cosines at lrow / lscore / lcos + q * lex_stride, n_lex[q] of them:
+// ascending, unique, inside A -- the fixed-stride layout launch_score_rows_batch scores); scratch, the pool planes and
+// the document ids are `need` (= GroupBatchArgs::k) respectively 3 * kCappedSlots apart.
+struct CappedBatchArgs {
+    float w_e, w_l, eps;       // per call: the resolved weights and the chunk plan's half band
+    uint32_t n_allowed;        // |A|
+    const uint32_t *lrow;
+    const float *lscore, *lcos;
+    uint32_t lex_stride;
+    uint32_t n_lex[8];         // <= kCappedLexMax each
+    float max_lex[8];
+    float *scratch;            // n_queries x 3 x kCappedSlots floats
+    uint32_t *list;            // n_queries x need: the pools, slot -> row ...
+    float *comb, *cosv, *lexv; // ... combined, cosine, normalised lexical score
+    uint32_t *docs;            // ... document id
+    uint32_t *info;            // n_queries x {pool size, status (0 decided, 1 capacity, 2 undecidable here)}
+    uint32_t *sizes;           // n_queries pool sizes (0 with a non-zero status): what the batched greedy launch reads
+};
 struct GroupBatchArgs {
     uint32_t n_queries;
     const float *scores;  // n_queries x score_stride nominated scores (NaN: masked, or a NaN nomination)
@@ -349,6 +369,7 @@ struct GroupBatchArgs {
     uint32_t *cand_doc;
     uint64_t *out;        // n_queries x group_batch_words(k)
     int n_cu;
+    const CappedBatchArgs *capped = nullptr; // non-null: out unused, the capped multi finish runs (k = need)
 };
 inline uint32_t group_batch_words(uint32_t k) { return group_out_words(k) + 1; }
 hipError_t launch_group_batch_tail(const GroupBatchArgs &a, hipStream_t s);

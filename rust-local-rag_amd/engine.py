@@ -414,6 +414,41 @@ class RagEngine:
                 hits, cap, C.byref(n)))
         return self._results(hits, n.value)
 
+    def _search_capped_batch(self, q: np.ndarray, texts: Optional[Sequence[str]], top_k: int, diversity_factor: float,
+                             stage: int, weights: Optional[QueryWeights], documents, per_document: int) -> List[List[SearchResult]]:
+        """the batched entries with `per_document` set: rlr_engine_search_text_capped_batch with query texts (one batched
+        BM25, then the capped batch), rlr_engine_search_capped_batch without -- per query what _search_capped returns"""
+        if not isinstance(per_document, int) or isinstance(per_document, bool) or not 1 <= per_document <= N.MAX_PER_DOCUMENT:
+            raise ValueError(f"per_document must be an integer in 1..{N.MAX_PER_DOCUMENT}")
+        nq, dq = q.shape
+        if len(self._chunks) == 0 or nq == 0:
+            return [[] for _ in range(nq)]
+        self._sync_documents()
+        f = self._filter_for(documents) if documents is not None else None
+        fh = f.handle if f is not None else None
+        cap = max(3 * max(top_k, 1), top_k + 10)
+        hits = (N.SearchHitC * (cap * nq))()
+        n_out = np.zeros(nq, dtype=np.uint32)
+        wc = weights.to_c() if weights is not None else None
+        wp = C.byref(wc) if wc is not None else None
+        offsets = np.zeros(nq + 1, dtype=np.uint64)
+        if texts is not None:
+            toks = [" ".join(tokenize(t)).encode("utf-8") for t in texts]
+            offsets[1:] = np.cumsum([len(t) for t in toks], dtype=np.uint64)
+            N.check(N.lib().rlr_engine_search_text_capped_batch(
+                self.index.handle, self.lexical._h, fh, q.ctypes.data_as(N.f32p), dq, nq, b"".join(toks),
+                offsets.ctypes.data_as(N.u64p), top_k, float(diversity_factor), stage, wp, per_document, hits, cap,
+                n_out.ctypes.data_as(N.u32p)))
+        else:
+            N.check(N.lib().rlr_engine_search_capped_batch(
+                self.index.handle, fh, q.ctypes.data_as(N.f32p), dq, nq, top_k, float(diversity_factor), stage, wp, None, None,
+                offsets.ctypes.data_as(N.u64p), per_document, hits, cap, n_out.ctypes.data_as(N.u32p)))
+        out = []
+        for i in range(nq):
+            view = (N.SearchHitC * cap).from_buffer(hits, i * cap * C.sizeof(N.SearchHitC))
+            out.append(self._results(view, int(n_out[i])))
+        return out
+
     # -- tail of RagEngine::search when a reranker answered (rag_engine.rs:599-700) --------------
     def finish_with_reranker(self, candidates: Sequence[SearchResult], reranked: Sequence[Tuple[str, float]],
                              top_k: int, weights: Optional[QueryWeights] = None) -> List[SearchResult]:
@@ -446,17 +481,25 @@ class RagEngine:
     def search_with_diversity_batch(self, query_embeddings, top_k: int, diversity_factor: float,
                                     weights: Optional[QueryWeights] = None,
                                     documents: Optional[Sequence[str]] = None,
-                                    scopes: Optional[Sequence[Sequence[str]]] = None) -> List[List[SearchResult]]:
+                                    scopes: Optional[Sequence[Sequence[str]]] = None,
+                                    per_document: Optional[int] = None) -> List[List[SearchResult]]:
         """`documents`: as for search_with_diversity -- every query searches only inside these documents (None: the
         whole corpus; an empty list or unknown names: no rows, an empty list per query); chunks of up to 8 queries
         share one masked pass over the documents' rows.
         `scopes`: one document list PER QUERY instead (not together with `documents`): query i is
         search_with_diversity(q_i, ..., documents=scopes[i]); chunks of up to 8 queries share one masked pass over the
-        union of their scopes (rlr_engine_search_with_diversity_batch_scoped)."""
+        union of their scopes (rlr_engine_search_with_diversity_batch_scoped).
+        `per_document`: as for search_with_diversity, through the batched capped search (not together with `scopes`);
+        None: no cap, the paths below untouched."""
         q = _f32(query_embeddings)
         if q.ndim == 1:
             q = q.reshape(1, -1)
         nq, dq = q.shape
+        if per_document is not None:
+            if scopes is not None:
+                raise ValueError("search_with_diversity_batch: `per_document` cannot be combined with `scopes`")
+            return self._search_capped_batch(np.ascontiguousarray(q), None, top_k, float(diversity_factor), 0, weights, documents,
+                                             per_document)
         cap = max(3 * max(top_k, 1), top_k + 10)
         hits = (N.SearchHitC * (cap * max(nq, 1)))()
         n_out = np.zeros(max(nq, 1), dtype=np.uint32)
@@ -495,7 +538,8 @@ class RagEngine:
     def search_text_batch(self, query_embeddings, query_texts: Sequence[str], top_k: int, diversity_factor: float = 0.0,
                           weights: Optional[QueryWeights] = None, stage: int = 0, return_info: bool = False,
                           documents: Optional[Sequence[str]] = None,
-                          scopes: Optional[Sequence[Sequence[str]]] = None):
+                          scopes: Optional[Sequence[Sequence[str]]] = None,
+                          per_document: Optional[int] = None):
         """`search_with_diversity(q, top_k, diversity_factor, weights, query_text=t)` (diversity 0: `search(q, top_k,
         weights, stage=stage, query_text=t)`) for every (q, t) pair, bit for bit, through the batched kernels.  Returns
         one result list per query, and with return_info also a dict of how the queries were served.
@@ -506,15 +550,26 @@ class RagEngine:
         `scopes`: one document list PER QUERY instead (not together with `documents`): query i is the single call with
         query_text=t_i and documents=scopes[i] ([] or unknown names: an empty scope, no results for that query) -- one
         batched BM25 with a mask per query, one scoped top-k call over the union of the scopes, one scoring of the lexical
-        rows and one MMR per sub-batch (rlr_engine_search_text_batch_scoped)."""
+        rows and one MMR per sub-batch (rlr_engine_search_text_batch_scoped).
+        `per_document`: as on the single calls, through one batched BM25 and the batched capped search
+        (rlr_engine_search_text_capped_batch; not together with `scopes`; the info dict is then all zeros); None: no
+        cap, the paths below untouched."""
         if scopes is not None and documents is not None:
             raise ValueError("search_text_batch: give `documents` or `scopes`, not both")
+        if scopes is not None and per_document is not None:
+            raise ValueError("search_text_batch: `per_document` cannot be combined with `scopes`")
         q = _f32(query_embeddings)
         if q.ndim == 1:
             q = q.reshape(1, -1)
         nq, dq = q.shape
         if len(query_texts) != nq:
             raise ValueError(f"{nq} query embeddings but {len(query_texts)} query texts")
+        if per_document is not None:
+            res = self._search_capped_batch(np.ascontiguousarray(q), list(query_texts), top_k, float(diversity_factor), stage,
+                                            weights, documents, per_document)
+            if return_info:
+                return res, {name: 0 for name, _ in N.TextBatchInfoC._fields_}
+            return res
         if scopes is not None:
             scopes = list(scopes)
             if len(scopes) != nq:
@@ -550,7 +605,7 @@ class RagEngine:
         return out
 
     def search_documents_batch(self, requests: Sequence[SearchRequest], share_scopes: bool = False,
-                               share_text_scopes: bool = False) -> List[List[SearchResult]]:
+                               share_text_scopes: bool = False, share_capped: bool = False) -> List[List[SearchResult]]:
         """search_documents for every request, grouped by (top_k, diversity, weights, documents) after its caps and
         clamps.  Unscoped groups run through search_text_batch (a request without text is scored with no query terms);
         scoped groups without query text through search_with_diversity_batch(documents=...); the scoped requests of a
@@ -560,7 +615,11 @@ class RagEngine:
         search_with_diversity_batch(scopes=...) call, whatever their scopes; everything else routes as above.
         share_text_scopes (independent of share_scopes): the scoped requests WITH query text of one (top_k, diversity,
         weights) key go through one search_text_batch(scopes=...) call, whatever their scopes, when there are two or
-        more of them; a lone one through search_documents."""
+        more of them; a lone one through search_documents.
+        share_capped: the requests that set per_document, of one (top_k, diversity, weights, documents, per_document)
+        key, go through one batched capped call when there are two or more of them (those with query text through
+        search_text_batch(per_document=...), those without through search_with_diversity_batch(per_document=...)); a
+        lone one through search_documents.  False (the default): one search_documents call for each."""
         groups: Dict[tuple, List[int]] = {}
         shared: Dict[tuple, List[int]] = {}
         shared_text: Dict[tuple, List[int]] = {}
@@ -586,8 +645,35 @@ class RagEngine:
                 continue
             groups.setdefault((top_k, div, wkey, scope), []).append(i)
         out: List[List[SearchResult]] = [[] for _ in requests]
-        for i in capped:  # (the cap has no batched form: one capped call each)
-            out[i] = self.search_documents(requests[i])
+        if share_capped:  # (the batched capped search: one call per key and kind of request)
+            capped_groups: Dict[tuple, List[int]] = {}
+            for i in capped:
+                r = requests[i]
+                top_k = min(r.top_k if r.top_k is not None else N.DEFAULT_TOP_K, N.MAX_TOP_K)
+                div = r.diversity_factor if r.diversity_factor is not None else N.DEFAULT_DIVERSITY
+                div = min(max(div, 0.0), 1.0)
+                w = r.weights
+                wkey = None if w is None else (w.embedding, w.lexical, w.reranker, w.initial)
+                scope = None if r.documents is None else frozenset(r.documents)
+                # (a request without a query goes through the entry without text, as search_documents sends it)
+                capped_groups.setdefault((top_k, div, wkey, scope, r.per_document, r.query is not None), []).append(i)
+            for (top_k, div, _, scope, m, has_text), members in capped_groups.items():
+                if len(members) < 2:
+                    out[members[0]] = self.search_documents(requests[members[0]])
+                    continue
+                w = requests[members[0]].weights
+                docs = None if scope is None else sorted(scope)
+                emb = np.stack([_f32(requests[i].query_embedding).ravel() for i in members])
+                if has_text:
+                    res = self.search_text_batch(emb, [requests[i].query for i in members], top_k, div, w, documents=docs,
+                                                 per_document=m)
+                else:
+                    res = self.search_with_diversity_batch(emb, top_k, div, w, documents=docs, per_document=m)
+                for i, r_i in zip(members, res):
+                    out[i] = r_i
+        else:
+            for i in capped:  # (one capped call each: the present loop)
+                out[i] = self.search_documents(requests[i])
         for (top_k, div, _), members in shared.items():
             emb = np.stack([_f32(requests[i].query_embedding).ravel() for i in members])
             scopes = [sorted(set(requests[i].documents)) for i in members]

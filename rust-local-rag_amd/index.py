@@ -432,6 +432,55 @@ class GpuIndex:
         N.check(self._L.rlr_index_capped_forms(self._h, _up(counts), int(reset)))
         return [int(c) for c in counts]
 
+    def search_capped_batch(self, queries, need: int, per_document: int, k: int = 0, lam: float = 0.0, diversify: bool = False,
+                            w_embedding: float = 1.0, w_lexical: float = 0.0, lex_rows=None, lex_scores=None, max_lex=None,
+                            filter: "RowFilter | None" = None, guard_eps: float = -1.0):
+        """search_capped with the queries of the call sharing passes over the rows (rlr_search_capped_batch).  queries:
+        [Q, dim], already normalised; lex_rows / lex_scores: one sequence per query (None: no pairs at all), each query's
+        rows ascending and unique; max_lex: one value per query (None: 1.0); everything else holds for the whole call.
+        -> a list of (rows u64, cos f32, combined f32, lexn f32, docs u32) per query, bit for bit what search_capped
+        returns for that query alone (set_capped_sharing, capped_batch_forms)"""
+        q = _f32(queries).reshape(-1, self.dim)
+        nq = q.shape[0]
+        lrs = [_u64(r) for r in lex_rows] if lex_rows is not None else [_u64([]) for _ in range(nq)]
+        lss = [_f32(s) for s in lex_scores] if lex_scores is not None else [_f32([]) for _ in range(nq)]
+        if len(lrs) != nq or len(lss) != nq or any(r.size != s.size for r, s in zip(lrs, lss)):
+            raise ValueError("lex_rows / lex_scores: one sequence per query, of equal lengths")
+        off = np.zeros(nq + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([r.size for r in lrs], dtype=np.uint64)
+        lr = np.ascontiguousarray(np.concatenate(lrs)) if nq else _u64([])
+        ls = np.ascontiguousarray(np.concatenate(lss)) if nq else _f32([])
+        ml = np.ones(max(nq, 1), dtype=np.float32) if max_lex is None else _f32(max_lex).ravel()
+        if max_lex is not None and ml.size != nq:
+            raise ValueError(f"{nq} queries but {ml.size} max_lex values")
+        cap = max(int(need), 1)
+        rows = np.zeros((max(nq, 1), cap), dtype=np.uint64)
+        cos, comb, lexn = (np.zeros((max(nq, 1), cap), dtype=np.float32) for _ in range(3))
+        docs = np.zeros((max(nq, 1), cap), dtype=np.uint32)
+        n_out = np.zeros(max(nq, 1), dtype=np.uint32)
+        N.check(self._L.rlr_search_capped_batch(self._h, None if filter is None else filter.handle, _fp(q), nq, need, k, lam,
+                                                int(diversify), w_embedding, w_lexical, _up(lr) if lr.size else None,
+                                                _fp(ls) if ls.size else None, _up(off), _fp(ml), per_document, guard_eps, _up(rows),
+                                                _fp(cos), _fp(comb), _fp(lexn), _u32ptr(docs), _u32ptr(n_out)))
+        out = []
+        for i in range(nq):
+            n = int(n_out[i])
+            out.append((rows[i, :n], cos[i, :n], comb[i, :n], lexn[i, :n], docs[i, :n]))
+        return out
+
+    def set_capped_sharing(self, mode: int) -> None:
+        """when search_capped_batch shares a pass: 0 where the cost model expects it to win (the default), 1 never, 2
+        wherever the shape allows (rlr_index_set_capped_sharing); the answers do not depend on it"""
+        N.check(self._L.rlr_index_set_capped_sharing(self._h, int(mode)))
+
+    def capped_batch_forms(self, reset: bool = False) -> list:
+        """queries search_capped_batch served by each form: [decided on the device behind a shared scan, handed to the
+        single path on a capacity, handed to it as undecidable there (the boundary rule, NaN rows wanted, a masked row came
+        back, no workspace), handed to it by rule] (rlr_index_capped_batch_forms)"""
+        counts = np.zeros(4, dtype=np.uint64)
+        N.check(self._L.rlr_index_capped_batch_forms(self._h, _up(counts), int(reset)))
+        return [int(c) for c in counts]
+
     def search_topk_device(self, queries, k: int, d_out_ptr: int, stream: int = 0, guard_eps: float = -1.0) -> None:
         q = _f32(queries).reshape(-1, self.dim)
         N.check(self._L.rlr_search_topk_device(self._h, _fp(q), q.shape[0], k, guard_eps,
