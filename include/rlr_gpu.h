@@ -646,7 +646,8 @@ typedef struct rlr_profile {
     double batch_other_ms;     /* query prep + sample select + per-query finish */
     uint64_t batch_gemm_bytes; /* algorithmic bytes: the operand the GEMM streams (rows * dim * 2 B over the
                                 * nomination image or binary16 rows, * 4 B over f32 rows), ONCE per batch: the
-                                * query blocks of one row tile share it through the XCD's L2 */
+                                * query blocks of one row tile share it through the XCD's L2; a GEMM-served
+                                * chunk of rlr_search_range_batch counts the same way */
     double batch_gemm_flops;   /* 2 * queries * rows * dim */
     uint64_t n_batch_fallbacks;/* queries re-run through the single-query pipeline */
     /* the dominant launch of a batch alone: the filtered main pass over rows [sample end, n) */

@@ -2282,6 +2282,7 @@ int32_t range_batch_chunk(rlr_index *ix, Ctx *c, const rlr_filter *f, RangeShare
     ra.hits = c->d_rhits.get();
     ra.out = c->d_rout.get();
     ra.n_cu = ix->n_cu;
+    uint64_t gemm_bytes = 0; // the operand the GEMM pass streams, once per chunk (prof.batch_gemm_bytes, as run_batched counts it)
     if (path == kRangeShareScan) {
         const uint64_t s_stride = (static_cast<uint64_t>(n) + 3) / 4 * 4;
         RLR_HIP(c->d_sample.reserve(static_cast<uint64_t>(m) * s_stride));
@@ -2303,6 +2304,7 @@ int32_t range_batch_chunk(rlr_index *ix, Ctx *c, const rlr_filter *f, RangeShare
         RLR_TRY(batch_arm(c, m, fin_cap, 0, 1, n)); // the states: cap = fin_cap, n_cand = 0
         RLR_HIP(hipMemcpyAsync(c->d_tau.get(), h_tau, m * sizeof(float), hipMemcpyHostToDevice, s));
         const bool use_image = ix->image_enabled && ix->d_image.get() && gemm_image_usable(ix->dim);
+        gemm_bytes = static_cast<uint64_t>(n) * ix->dim * ((ix->dtype == RLR_F16 || use_image) ? 2 : 4);
         RLR_HIP(launch_prep_queries(c->d_query.get(), m, ix->q_pitch, ix->dim, use_image ? static_cast<int>(RLR_F16) : ix->dtype,
                                     c->d_qfrag.get(), s));
         RLR_HIP(launch_gemm_nominate(ix->d_rows.get(), ix->pitch16, ix->dim, ix->dtype, 0, n, c->d_qfrag.get(), m, c->d_tau.get(),
@@ -2343,6 +2345,7 @@ int32_t range_batch_chunk(rlr_index *ix, Ctx *c, const rlr_filter *f, RangeShare
         ix->prof.n_batches += 1;
         ix->prof.n_batch_queries += m;
         ix->prof.n_batch_fallbacks += redo.size();
+        ix->prof.batch_gemm_bytes += gemm_bytes;
     }
     RLR_TRY(note_search(ix, c, m - static_cast<uint32_t>(redo.size()), hits_total, 0, /*timed=*/false));
     // (from here on the pinned block and the context are range_query's)

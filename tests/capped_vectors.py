@@ -15,6 +15,7 @@ import grouped_vectors as G
 DOC_NONE = G.DOC_NONE
 F32_EPSILON = np.float32(1.1920929e-07)
 GROUP_CAP, LEX_CAP, NEED_MAX = 2048, 2048, 1024           # what the one-workgroup finish holds (kernels.h)
+W_EMBEDDING, W_LEXICAL = 0.7, 0.3                         # the engine's default blend (oracle.search)
 
 
 def f32(x):

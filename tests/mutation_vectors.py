@@ -212,6 +212,15 @@ def ordinary_queries(O, st):
     return np.stack([O.normalize(O.synth_query(DIM, seed=7000 + N_ORDINARY * st.index + i)) for i in range(N_ORDINARY)])
 
 
+def oracle_topk(scores, k, allowed=None):
+    """the top-k of one oracle scan (over the ascending rows `allowed` only), score descending, row ascending: rows u64,
+    scores f32"""
+    e = np.asarray(scores, np.float32)
+    rows = np.arange(len(e)) if allowed is None else np.asarray(allowed, np.int64)
+    order = np.lexsort((rows, -e[rows].astype(np.float64)))[:k]
+    return rows[order].astype(np.uint64), e[rows[order]]
+
+
 class StepProbes:
     """the queries of one step and the oracle's scan of each over the mirror: computed once per (step, dtype), shared by
     every configuration and test, never changed"""
@@ -235,10 +244,7 @@ class StepProbes:
 
     def expected(self, qi, k, allowed=None):
         """the oracle's top-k of query qi (over the ascending rows `allowed` only): rows u64, scores f32"""
-        e = self.scores[qi]
-        rows = np.arange(len(e)) if allowed is None else np.asarray(allowed, np.int64)
-        order = np.lexsort((rows, -e[rows].astype(np.float64)))[:k]
-        return rows[order].astype(np.uint64), e[rows[order]]
+        return oracle_topk(self.scores[qi], k, allowed)
 
 
 _PROBES = {}
