@@ -18,7 +18,7 @@ OBJ = os.path.join(HERE, "_obj")
 SO = os.path.join(HERE, "librlr_gpu.so")
 ROOT = os.path.dirname(HERE)
 
-SOURCES = ["scan.hip", "select.hip", "tail.hip", "exact.hip", "gemm.hip", "index.hip", "index_fused.hip", "engine.cpp", "multi.cpp", "lexical.hip",
+SOURCES = ["scan.hip", "select.hip", "tail.hip", "exact.hip", "gemm.hip", "index.hip", "index_fused.hip", "index_grouped.hip", "engine.cpp", "multi.cpp", "lexical.hip",
            "q8.hip", "jsonio.cpp", "text_batch.cpp", "engine_filtered.cpp", "docs.hip", "group.hip", "engine_capped.cpp", "range.hip"]
 HEADERS = ["common.h", "device_buffer.h", "kernels.h", "exact_dot.h", "lds_select.h", "staged_dot.h", "select_dev.h", "sort_emit.h", "pool_prepare.h",
            "engine_host.h", "lexical_internal.h", "filter_internal.h", "index_internal.h", os.path.join(ROOT, "include", "rlr_gpu.h"),

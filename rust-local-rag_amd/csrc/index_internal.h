@@ -1,9 +1,9 @@
 // index_internal.h -- the frame every search entry point of the index is built on, declared once for the translation units
 // that implement the C ABI of include/rlr_gpu.h:
-//   index.hip         state, ingest, contexts and the waits; the definitions of everything declared here; the plain, batched
-//                     and coalesced pipelines; the searches inside a row set (filters, the document column, grouped / range /
-//                     capped search)
-//   index_fused.hip   search chains that end in a blend or MMR on the device: MMR, diversified and hybrid search
+//   index.hip           state, ingest, contexts and the waits; the definitions of everything declared here; the plain,
+//                       batched and coalesced pipelines; the searches inside a row set (filters, the document column)
+//   index_fused.hip     search chains that end in a blend or MMR on the device: MMR, diversified and hybrid search
+//   index_grouped.hip   grouped, range and capped search, one query at a time and in chunks behind a shared scan
 // A new feature may rely on what this header declares and on nothing else of index.hip.
 #pragma once
 
@@ -37,6 +37,7 @@ namespace rlr {
 
 constexpr uint32_t kLdsSortCap = 4096; // candidates the single-workgroup sort can take
 constexpr uint32_t kMaxDim = 8192;
+constexpr uint32_t kBatchMaxQueries = 1024; // queries per batched pipeline run (bounds the workspace)
 
 inline uint32_t next_pow2(uint32_t v)
 {
@@ -249,6 +250,8 @@ struct CtxLease {
 };
 
 int32_t pin_reserve(Ctx *c, size_t bytes);
+// c->d_query / c->d_state for nq queries
+int32_t reserve_queries(const rlr_index *ix, Ctx *c, uint32_t nq);
 // c->d_list / c->d_vals for n rows (a power of two, at least 1024)
 int32_t reserve_list(Ctx *c, uint32_t n);
 int32_t upload_list(rlr_index *ix, Ctx *c, const uint64_t *rows, uint32_t n, uint64_t bound = ~0ull);
@@ -256,6 +259,14 @@ int32_t upload_list(rlr_index *ix, Ctx *c, const uint64_t *rows, uint32_t n, uin
 // ---- the waits ----------------------------------------------------------------------------------------------------
 // The result block of a fused search -> MMR call (sort_emit.h).
 int32_t wait_block(const volatile uint32_t *h_out, uint32_t k_cap, hipStream_t s, WaitEma *c);
+// The completion words of nq single-query pipelines (sort_emit.h: count | checksum << 32, written last).  res != null:
+// the k result words of each query are in host memory too and must match the checksum -- the word alone can overtake
+// the results on their way through PCIe.
+int32_t wait_results(const volatile uint64_t *meta, const volatile uint64_t *res, uint32_t nq, uint32_t k, uint32_t limit,
+                     hipStream_t s, WaitEma *c);
+// the completion words a polling wait watches (sort_emit.h): pre-set before the first enqueue, replaced by each
+// pipeline's last store
+void arm_meta(uint64_t *h_meta, uint32_t nq);
 // The host reader of a complete block: its n picks into the caller's arrays (lex_out may be null), its status returned.
 uint32_t read_block(const uint32_t *h_out, uint32_t k_cap, uint64_t *rows_out, float *cos_out, float *score_out, float *lex_out,
                     uint32_t *n_out);
@@ -289,6 +300,22 @@ void pad_queries(const rlr_index *ix, const float *queries, uint32_t nq, float *
 void stage_queries(const rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, float *h_q);
 // The queries of a call whose pipelines start with enqueue_query_scan: by the scans themselves where they can, else uploaded.
 hipError_t stage_queries_for_scans(const rlr_index *ix, Ctx *c, const float *h_q, size_t q_bytes, hipStream_t s);
+// The staged queries (pinned host memory, zero padded to the row pitch) -> the context's device buffer.  A few KB: one
+// small kernel on the search's own stream reads them over PCIe itself.  hipMemcpyAsync does the same with the runtime's
+// copy kernel, but the scan behind it then starts 4-5 us after that copy has finished (every other boundary of the
+// pipeline: < 1 us; scratch/step_timeline.py) -- a stream's copies and kernels are ordered through a signal, kernels
+// among themselves by the queue.
+hipError_t upload_queries(Ctx *c, const float *h_q, size_t q_bytes, hipStream_t s);
+// The pinned memory of a call (c->h_pin): nq staged queries, res_words result words behind them.
+struct Staged {
+    float *h_q;
+    uint64_t *h_res;
+};
+// Reserve and carve that memory, stage the queries (stage_queries) and send them on their way -- for_scans: left to the
+// scans where they can take them (stage_queries_for_scans), else uploaded, with c->h_q_kq null.
+int32_t stage_call(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, size_t res_words, bool for_scans, Staged *out);
+// a scan over the index' rows (query_host stays null: the caller sets it where the query may travel in the arguments)
+ScanArgs scan_args(const rlr_index *ix, const float *query, float *scores, uint32_t *hist);
 
 // ---- profile bookkeeping ----------------------------------------------------------------------------------------------
 // c->ev[0] .. c->ev[3] of a timed single-query pipeline: scan | select | re-score + sort, added to *t
@@ -370,12 +397,41 @@ int32_t run_search(rlr_index *ix, Ctx *c, const float *queries, uint32_t nq, uin
                    uint64_t *d_out_user, SearchPlan *plan_out, const uint64_t **h_results, bool coalesced = false,
                    uint32_t *n_handed_back = nullptr);
 
+// 2..8 queries over f32 rows of these shapes share one VALU scan (scan_multi_kernel) in run_batched.  `coalesced`: the
+// queries are a group of concurrent single-query calls (rlr_index_set_coalescing) -- those also share one pass over
+// binary16 rows of 256 / 512 / 768 / 1024 elements (scan_multi_h_kernel); explicit multi-query calls over binary16
+// rows keep the matrix-core pipeline.
+bool batch_multi_shape(const rlr_index *ix, uint32_t nq, bool coalesced = false);
+// The per-query workspace of a batched run of nq queries (select states, histograms, status words, fin_cap candidates and
+// s_stride sample scores each), the states armed for rank `rank` of n scored rows, histograms and status words cleared on
+// the context's stream.  Shared by run_batched and the filtered shared pass.
+int32_t batch_arm(Ctx *c, uint32_t nq, uint32_t fin_cap, uint64_t s_stride, uint32_t rank, uint64_t n);
+// unpack_result of `take` packed results into a caller's rows / cosines, written without branches so that the loop
+// vectorises (a batch of 1024 x 308 results is 315 k of them)
+void unpack_results(const uint64_t *__restrict__ src, uint32_t take, uint64_t *__restrict__ ro, float *cos_out);
+
+// ---- searches inside a row set ----------------------------------------------------------------------------------------
+int32_t check_filter(const rlr_index *ix, const rlr_filter *f);
+// is `row` an allowed row of `f`?  (the host copy of the mask: what every returned row is tested against)
+bool filter_holds(const rlr_filter *f, uint32_t row);
+// A masked row must never be returned.  Its sentinel keeps it out of every collect whose threshold key is above 0; a
+// threshold of 0 (k reaches allowed rows whose own nomination score is NaN) lets it in, and re-scored from its real values
+// it can rank anywhere.  So every returned row is tested against the host copy of the mask -- if none is masked the result
+// is the right one -- and a caller that finds one takes its exact path.  keys: n packed results; f == nullptr: no filter.
+bool masked_row_among(const rlr_filter *f, const uint64_t *keys, uint32_t n);
+// One query over the rows of `f` (n_allowed > 0, k > 0).  Filtered calls scan the master rows and never use the
+// nomination copies, the matrix-core batch or the coalescer.
+int32_t filtered_query(rlr_index *ix, Ctx *c, const rlr_filter *f, const float *query, uint32_t k, float guard_eps,
+                       uint64_t *rows_out, float *cos_out, uint32_t *n_out);
+// One form read-out (rlr_index_*_forms): the queries each form served since the last reset.
+int32_t read_forms(rlr_index *ix, uint64_t (rlr_index::*forms)[4], uint64_t counts[4], int32_t reset);
+
 // The fused one-enqueue calls (rlr_search_diverse / rlr_search_hybrid / search_hybrid_begin) cannot share their scan:
 // while coalescing is on and a group of two with this k would qualify, they hand the query back (*fallback = 1) so that
 // the caller's two-call path reaches the coalescer through rlr_search_topk.
 bool coalesce_hands_back(rlr_index *ix, uint32_t k);
 
-// ---- defined in index_fused.hip, called by rlr_search_capped / capped_query of index.hip ---------------------------------
+// ---- defined in index_fused.hip, called by rlr_search_capped / capped_query of index_grouped.hip -------------------------
 // one pool of up to 4096 candidates; d_matrix != null: pool_rows are slots of that staged matrix (see mmr_batch_impl)
 int32_t mmr_single_impl(rlr_index *ix, const uint64_t *pool_rows, const float *pool_scores, uint32_t P, uint32_t k,
                         float lambda, uint32_t *order_out, float *mmr_out, uint32_t *n_out, const void *d_matrix,

@@ -1,5 +1,5 @@
 """Batched capped search (rlr_search_capped_batch; capped_finish_multi_kernel of rust-local-rag_amd/csrc/group.hip and
-capped_batch_chunk of index.hip), pure numpy: one chunk of queries restated on top of tests/capped_vectors.py (the
+capped_batch_chunk of index_grouped.hip), pure numpy: one chunk of queries restated on top of tests/capped_vectors.py (the
 definition and the single device path) and tests/grouped_batch_vectors.py (the workspace rule and the split), with the
 defects batching can introduce planted one at a time, and designed chunks that each defect must break.  The definition is
 capped_vectors.define query by query (then the oracle's greedy MMR over the pool, when diversified).

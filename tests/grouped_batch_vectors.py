@@ -33,7 +33,7 @@ DEFECTS = ("plane_of_query_0", "plane_stride", "nan_skips_all", "hist_added", "t
 
 # ---- the workspace rule and the split -----------------------------------------------------------------------------------
 def table_bits(n_allowed):
-    """index.hip group_table_bits: twice the documents the table can meet, at least 1024 slots"""
+    """index_grouped.hip group_table_bits: twice the documents the table can meet, at least 1024 slots"""
     bits = 10
     while bits < 32 and (1 << bits) < 2 * n_allowed:
         bits += 1

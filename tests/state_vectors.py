@@ -308,7 +308,7 @@ def chunks(n, size=8):
 
 # ---------------------------------------------------------------- the forms the batched entries must report (sharing mode 2)
 def range_batch_forms(dtype, n, nq, list_path=False):
-    """range_share_path of index.hip at 256 columns: 2..8 queries over f32 rows share a scan at any row count; anything
+    """range_share_path of index_grouped.hip at 256 columns: 2..8 queries over f32 rows share a scan at any row count; anything
     else of two or more shares the GEMM from 4096 rows on; the rest goes by rule"""
     out = [0, 0, 0, 0]
     if n == 0 or nq == 0:
